@@ -3,7 +3,7 @@
 (WENO(order=5), tracers (T, S), FFT pressure solve) -- BASELINE.json's metric, measured like the reference measures it
 (benchmark/benchmarkable_nonhydrostatic_model.jl:23-27: device-synchronised `time_step!(model, Δt)` after warm-up).
 
-    python bench.py --gpus N --steps K --warmup W [--size 256] [--no-cpu-baseline]
+    python bench.py --gpus N --steps K --warmup W [--size 256] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 N = 1: 256^3 triply periodic on one MI355X (BASELINE.json configs[1]).
 N > 1: one rank process per GPU; x-slab decomposition, WEAK scaling (256^3 per GPU, i.e. global (256 N) x 256 x 256). The library
@@ -16,10 +16,17 @@ N > 1: one rank process per GPU; x-slab decomposition, WEAK scaling (256^3 per G
                                                 exits non-zero with the rank logs when one dies, leaves early or stalls)
        --gpus N with a WORLD_SIZE that says otherwise is refused.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job cell-updates/s with all inputs
-resident in HBM; "roofline" = the dominant kernel (fused WENO tendency evaluation) from HIP events recorded on the
-launch stream inside the timed region; "cpu_baseline" = the CPU oracle (a port, not the Julia reference) on the host
-cores over a bounded sample of the same workload.
+Prints ONE JSON line on rank 0: value = whole-job cell-updates/s with all inputs resident in HBM; ms_per_step = the mean
+over the K timed steps; "roofline" = the dominant kernel (fused WENO tendency evaluation) from HIP events recorded on the
+launch stream inside the timed region. A plain run does only that. --full adds what takes time of its own: K further
+steps synchronised one by one (ms_per_step_median / _min), the divergence check after the run and, at N = 1 unless
+--no-cpu-baseline, "cpu_baseline" = the CPU oracle (a port, not the Julia reference) on the host cores over a bounded
+sample of the same workload.
+
+--dump-outputs DIR: after the timed steps, every rank writes the state its last timed step left (velocities, tracers,
+pressures -- what a caller of time_step reads) as DIR/<name>.npy in float64 (DIR/<name>_rank<r>.npy when N > 1): the
+whole interior when it is small, otherwise a fixed, seeded sample of its elements (dump_outputs), 64 MB at most in all.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -139,6 +146,31 @@ def initial_state(ocn, model, seed=1234):
     flds = model.fields()
     nodes = {n: g.nodes(f.loc) for n, f in flds.items()}
     return smooth_state(nodes, seed)
+
+
+DUMP_VALUES_PER_ARRAY = 1 << 20      # 8 MB of float64 per array: 7 arrays at most (u, v, w, T, S, pNHS, pHY) stay under 64 MB
+DUMP_SAMPLE_SEED = 20240601
+
+
+def model_outputs(model):
+    """the arrays a caller of time_step reads after a step: velocities, tracers and pressures (interiors, host copies)"""
+    out = {n: f.interior() for n, f in model.fields().items()}
+    out.update({n: f.interior() for n, f in zip(model.pressures._fields, model.pressures)})
+    return out
+
+
+def dump_outputs(arrays, directory, rank, world):
+    """DIR/<name>.npy (float64): the whole interior when it holds at most DUMP_VALUES_PER_ARRAY / world values, otherwise that many
+    elements at fixed positions -- a seeded draw without replacement over the interior in column-major (x fastest) order, sorted, the
+    same positions for every array of the same shape and every run"""
+    os.makedirs(directory, exist_ok=True)
+    limit = DUMP_VALUES_PER_ARRAY // world
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > limit:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, limit, replace=False))
+            a = np.ravel(a, order="F")[idx]
+        np.save(os.path.join(directory, f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy"), a)
 
 
 def cpu_baseline(size, dt, budget_s=20.0, one_thread_budget_s=12.0):
@@ -311,7 +343,12 @@ def main():
                          "--gpus 8). Default 0: weak scaling, --size^3 cells per GPU, global (size*N) x size x size")
     ap.add_argument("--tendency-impl", type=int, default=2,
                     help="2: one field per workgroup (default); 1: all-fields kernel of round 1; 0: per-field kernels")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: K further individually synchronised steps "
+                         "(ms_per_step_median / _min), the divergence after the run, and at N = 1 the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left as DIR/<name>.npy (float64; a fixed seeded sample of large arrays)")
     ap.add_argument("--arithmetic", type=int, default=0,
                     help="0: the reference's IEEE operation sequence, bit-identical to the oracle (default, what every parity test runs); "
                          "1: the opt-in contracted mode of the WENO flux (FMA-contracted sub-stencil sums and weights, one normalisation, "
@@ -450,21 +487,25 @@ def main():
     tend_ms, tend_n = model.profile_read()
     model.set_option("profile", 0)
     phase("timed")
-    # the distribution of single steps (the reference reports min / median / mean of BenchmarkTools samples,
-    # benchmark/benchmarkable_nonhydrostatic_model.jl:23-27): K more steps, each bracketed by its own device synchronisation (and, N > 1,
-    # a barrier) -- OUTSIDE the timed region above, whose mean is `ms_per_step`
-    samples = []
-    for _ in range(args.steps):
-        barrier()
-        ocn.synchronize()
-        ts = time.perf_counter()
-        step(dt)
-        ocn.synchronize()
-        samples.append(time.perf_counter() - ts)
+    if args.dump_outputs:                 # the state the last timed step left, before anything else steps the model
+        dump_outputs(model_outputs(model), args.dump_outputs, rank, world)
+    median = fastest = div = None
+    if args.full:
+        # the distribution of single steps (the reference reports min / median / mean of BenchmarkTools samples,
+        # benchmark/benchmarkable_nonhydrostatic_model.jl:23-27): K more steps, each bracketed by its own device synchronisation (and,
+        # N > 1, a barrier) -- OUTSIDE the timed region above, whose mean is `ms_per_step`
+        samples = []
+        for _ in range(args.steps):
+            barrier()
+            ocn.synchronize()
+            ts = time.perf_counter()
+            step(dt)
+            ocn.synchronize()
+            samples.append(time.perf_counter() - ts)
+        median = float(np.median(samples)) if samples else None
+        fastest = float(np.min(samples)) if samples else None
+        div = ocn.max_abs_divergence(model)
     gc.enable()
-    median = float(np.median(samples)) if samples else None
-    fastest = float(np.min(samples)) if samples else None
-    div = ocn.max_abs_divergence(model)
     fused_substep = model.get_option("fuse_substep_active") == 1
     in_kernel = model.get_option("substep_in_tendency_kernel") == 1           # (read here: a partitioned model is closed before the line is built)
     dead_store_skipped = in_kernel and model.get_option("skip_dead_tendency_store") == 1
@@ -473,7 +514,8 @@ def main():
     communicator = None
     if distributed:
         elapsed = ctx.allreduce_max(elapsed)
-        median, fastest = ctx.allreduce_max(median), ctx.allreduce_max(fastest)
+        if args.full:
+            median, fastest = ctx.allreduce_max(median), ctx.allreduce_max(fastest)
         communicator = ctx.info()
         ctx.barrier()
         model.close()
@@ -500,10 +542,8 @@ def main():
     traffic, traffic_path = measured_traffic(args.tendency_impl, N) if world == 1 and args.workload == "ppp" else (None, None)
     out = {
         "metric": "cell_updates_per_s", "value": value, "unit": "cell-updates/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "ms_per_step_median": 1e3 * median if median else None,
-        "ms_per_step_min": 1e3 * fastest if fastest else None,
-        "ms_per_step_note": "ms_per_step = mean over the K steps of the timed region (one synchronisation at each end); median / min = K further "
-                            "steps synchronised one by one (max over ranks)",
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
+        "ms_per_step_note": "ms_per_step = mean over the K steps of the timed region (one synchronisation at each end)",
         "higher_is_better": True, "scaling": "strong" if args.global_size else "weak",
         "vs_baseline": value / V100_PUBLISHED_CELL_UPDATES if world == 1 and N == 256 and args.workload == "ppp" and not distributed else None,
         "dtype": "f64", "data": "synthetic; SELF-LOOP: one rank running the N > 1 code path, its RCCL transfers going to itself" if (distributed and os.environ.get("OCN_SELF_LOOP") == "1" and world == 1)
@@ -526,7 +566,7 @@ def main():
                    (f"x-slab Partition({world}): RCCL send/recv halos, " +
                     ("substructured x solve (one all-gather of 2 complex per mode per solve)" if args.workload == "ppp" else
                      "distributed Fourier-tridiagonal solve (two all-to-all transposes)")),
-                   "dt": dt, "max_abs_divergence_after_run": div,
+                   "dt": dt,
                    "arithmetic": ("reference operation sequence (IEEE, bit-identical to the oracle)" if not arithmetic_active else
                                   "contracted WENO flux (opt-in, option arithmetic = 1): within 1e-12 of the oracle, not bit-identical"),
                    "tolerance_note": "1e-12 relative vs the oracle holds for u, v, w, T; NOT for a tracer with a large offset (S = 35 + ...) "
@@ -556,8 +596,13 @@ def main():
                      "avg_launch_ms": 1e3 * t_launch, "launches_timed": tend_n,
                      "share_of_step": tend_ms / (1e3 * elapsed) if elapsed else None},
     }
-    if not args.no_cpu_baseline and world == 1:          # rank 0 at N = 1 only (the bench contract)
-        out["cpu_baseline"] = cpu_baseline(N, dt)
+    if args.full:
+        out["ms_per_step_median"] = 1e3 * median if median else None
+        out["ms_per_step_min"] = 1e3 * fastest if fastest else None
+        out["ms_per_step_note"] += "; median / min = K further steps synchronised one by one (max over ranks)"
+        out["config"]["max_abs_divergence_after_run"] = div
+        if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (the bench contract)
+            out["cpu_baseline"] = cpu_baseline(N, dt)
     print(json.dumps(out))
 
 

@@ -24,7 +24,8 @@ def _bench(args, env_extra, timeout=600):
 
 
 def test_self_launched_two_rank_rehearsal_prints_one_line_with_n_gpus_2():
-    res, _ = _bench(["--gpus", "2", "--size", "32", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], {"OCN_REHEARSE_ON_ONE_GPU": "1"})
+    res, _ = _bench(["--gpus", "2", "--size", "32", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
+                    {"OCN_REHEARSE_ON_ONE_GPU": "1"})
     assert res.returncode == 0, res.stdout[-1000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, res.stdout

@@ -1,11 +1,12 @@
-"""copy a rocprofv3 kernel-stats summary that tools/prof_stats.sh left under gpurun_out/ into profiles/ with the header lines the committed
+"""copy a rocprofv3 kernel-stats summary that tools/prof_stats.sh left under prof_out/ ($OCN_PROF_OUT) into profiles/ with the header lines the committed
 profiles carry (command, bench line of the same run):  python tools/commit_profile.py <tag> <profiles/name.csv> "<command as run>" """
 import csv, glob, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OCN_PROF_OUT") or os.path.join(ROOT, "prof_out")
 tag, out, cmd = sys.argv[1], sys.argv[2], sys.argv[3]
-f = max(glob.glob(os.path.join(ROOT, "gpurun_out", tag + "_stats", "**", "*kernel_stats.csv"), recursive=True), key=os.path.getmtime)   # the newest collection
+f = max(glob.glob(os.path.join(OUT, tag + "_stats", "**", "*kernel_stats.csv"), recursive=True), key=os.path.getmtime)   # the newest collection
 line = None
-for ln in open(os.path.join(ROOT, "gpurun_out", tag + "_stats.log")):
+for ln in open(os.path.join(OUT, tag + "_stats.log")):
     if ln.startswith('{"metric"'):
         line = json.loads(ln)
 rows = list(csv.DictReader(open(f)))

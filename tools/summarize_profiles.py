@@ -1,4 +1,4 @@
-"""turn the rocprofv3 outputs of tools/collect_profiles.sh (gpurun_out/<tag>_{stats,fetch,write}) into the committed
+"""turn the rocprofv3 outputs of tools/collect_profiles.sh (prof_out/<tag>_{stats,fetch,write}, or $OCN_PROF_OUT) into the committed
 summaries under profiles/:  <tag>_kernel_stats_256cubed.csv, <tag>_hbm_traffic_256cubed.csv, <tag>_tendency_traffic.json.
 
 FETCH_SIZE / WRITE_SIZE are in KiB (rocprofv3 derived counters). On gfx950 FETCH_SIZE under-reports wide coalesced streaming
@@ -17,7 +17,7 @@ tag = sys.argv[1] if len(sys.argv) > 1 else "r02"
 suffix = sys.argv[2] if len(sys.argv) > 2 else "256cubed"      # name of the workload in the output files
 N = 256
 cells = float(N) ** 3
-out = os.path.join(ROOT, "gpurun_out")
+out = os.environ.get("OCN_PROF_OUT") or os.path.join(ROOT, "prof_out")
 
 
 def one(pattern):
@@ -36,7 +36,7 @@ bench = json.loads(bench_line[0]) if bench_line else {}
 rows = list(csv.DictReader(open(one(f"{tag}_stats/**/*kernel_stats.csv"))))
 dst = os.path.join(ROOT, "profiles", f"{tag}_kernel_stats_{suffix}.csv")
 with open(dst, "w") as f:
-    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline  (MI355X, 256^3)\n")
+    f.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline  (MI355X, 256^3)\n")
     if bench:
         f.write(f"# bench line of the same run: ms_per_step {bench['ms_per_step']:.3f}, roofline.avg_launch_ms "
                 f"{bench['roofline']['avg_launch_ms']:.4f} (HIP events on the launch stream) -- compare with AverageNs of the fused kernel below\n")
