@@ -276,7 +276,8 @@ int ocn_dist_poisson_backward_yz(ocn_dist_poisson_t solver, double *phi);
 
 /* ---------------------------------------------------------------- model fast path ------------------------------- */
 /* NonhydrostaticModel(; grid, advection = WENO(), tracers, timestepper = :RungeKutta3) with coriolis / buoyancy /
- * closure / forcing = nothing (nonhydrostatic_model.jl:115-244). Fields are allocated (zeroed) by the library. */
+ * closure / forcing = nothing (nonhydrostatic_model.jl:115-244); the ocn_model_set_* calls below add them. Fields are allocated (zeroed)
+ * by the library. */
 int ocn_model_create(ocn_model_t *model, ocn_grid_t grid, int ntracers);
 int ocn_model_destroy(ocn_model_t model);
 /* names: "u","v","w","c0".."c7" (tracers), "p" (pNHS), "Gu".."Gc7" (Gⁿ), "Mu".."Mc7" (G⁻). Returns the device
@@ -345,6 +346,37 @@ int ocn_model_set_boundary_condition(ocn_model_t model, const char *name, int si
 int ocn_model_set_boundary_condition_array(ocn_model_t model, const char *name, int side, int kind, const double *device_array);
 /* name.side = FluxBoundaryCondition((ξ, η, t, φ, p) -> a + b φ, field_dependencies = dep); dep at the location of `name` */
 int ocn_model_set_linear_flux_bc(ocn_model_t model, const char *name, int side, double a, double b, const char *dep);
+/* forcing = (name = F,) of the model constructor (Forcings/model_forcing.jl; nonhydrostatic_tendency_kernel_functions.jl:81-93, the last
+ * term `+ forcing(i, j, k, grid, clock, model_fields)`) for the closure-free forcings of src/Forcings/:
+ *   OCN_FORCING_ARRAY       Forcing(array) / forcing = (T = array,): F = array[i, j, k] (forcing.jl:165-177, model_forcing.jl:29)
+ *   OCN_FORCING_RELAXATION  Relaxation(; rate, mask, target) (relaxation.jl): F = (rate·mask)(ξ_m) * (target(ξ_t) - φ), φ the field itself
+ *                           (the dependency regularize_forcing adds, relaxation.jl:75-78); GaussianMask / PiecewiseLinearMask / LinearTarget
+ *                           depend on one coordinate and not on time, so the CALLER evaluates them at the field's location: a binder calls
+ *                           the reference's own functions and passes the bits
+ * `nterms` terms are summed as MultipleForcings does (multiple_forcings.jl: left to right for N <= 4, `total = 0; total += Fₙ` beyond);
+ * G = G_rest + F, Flux-condition terms after it. field 0 .. 2 = u, v, w, 3 + t = tracer t; 1 <= nterms <= OCN_MAX_FORCING_TERMS, 0 clears
+ * the field's forcing. OCN_EINVAL: bad field index, kind or direction, a NULL that is needed, too many terms, a table along a Flat
+ * direction (relaxation.jl has no 1- or 2-coordinate mask methods: the reference cannot build such a model either). Tables are copied;
+ * an array stays BORROWED while it is set. A partitioned model takes its rank-local tables and arrays. Model option "forcing_path"
+ * reports which pass adds the term: 0 none; 1 the role tendency kernel (no physics terms, no Flux condition, Periodic z, single GPU: the
+ * RK3 substep stays fused); 3 a standalone pass after the tendency launches (every other configuration; the substeps then run as their
+ * own launches); 2 (inside the physics epilogue) is reserved and never reported. "fused_forcing" = 0 forces the standalone pass. */
+#define OCN_FORCING_ARRAY 1
+#define OCN_FORCING_RELAXATION 2
+#define OCN_MAX_FORCING_TERMS 8
+typedef struct {
+    int kind;
+    const double *array;        /* ARRAY: DEVICE pointer in the parent layout of a (Center, Center, Center) field of the model's grid
+                                   (ocn_grid_parent_size), read at the forced field's own (i, j, k) */
+    int mask_dir;               /* -1: mask = onefunction, the factor is `rate_mask` (= rate); 0 / 1 / 2: the table along x / y / z */
+    const double *mask_table;   /* HOST, rate * mask(node) at the field's location over the haloed index range of mask_dir (parent size
+                                   along it: element ξ - 1 + H holds node ξ) */
+    double rate_mask;
+    int target_dir;             /* -1: constant target `target` (zerofunction: 0.0); 0 / 1 / 2: the table along x / y / z */
+    const double *target_table; /* HOST, target(node), same layout */
+    double target;
+} ocn_forcing_t;
+int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *terms, int nterms);
 /* library-wide knobs (no reference equivalent; the defaults are the tuned values, 0 / 1 unless noted):
  *   pressure solve: "real_fft" (1: D2Z/Z2D, 0: the reference's complex-to-complex), "c2r_strided", "fused_zfft" (z FFT + divide +
  *     inverse z FFT as one LDS pass), "split_solve" (model time-step: 1-D x plans on 128-B-padded rows + LDS column-FFT kernel for y +

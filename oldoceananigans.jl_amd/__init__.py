@@ -12,6 +12,8 @@ from .boundary_conditions import (BoundaryCondition, FieldBoundaryConditions, Fl
 from .buoyancy import BuoyancyTracer, FPlane, LinearEquationOfState, SeawaterBuoyancy
 from .checkpointer import set_from_checkpoint, write_checkpoint
 from .closures import AnisotropicMinimumDissipation, ScalarDiffusivity
+from .forcings import (AdvectiveForcing, ContinuousForcing, DiscreteForcing, Forcing, GaussianMask, LinearTarget, MultipleForcings,
+                       PiecewiseLinearMask, Relaxation)
 from .fields import (CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions, interior, set_)
 from .grids import (Bounded, Center, Face, Flat, FullyConnected, LeftConnected, Periodic, RectilinearGrid, RightConnected,
                     with_halo)

@@ -33,6 +33,12 @@ class BC(C.Structure):
     """ocn_bc_t"""
     _fields_ = [("kind", C.c_int), ("value", C.c_double), ("array", C.c_void_p)]
 
+class Forcing(C.Structure):
+    """ocn_forcing_t"""
+    _fields_ = [("kind", C.c_int), ("array", C.c_void_p), ("mask_dir", C.c_int), ("mask_table", C.POINTER(C.c_double)),
+                ("rate_mask", C.c_double), ("target_dir", C.c_int), ("target_table", C.POINTER(C.c_double)), ("target", C.c_double)]
+
+
 class Transport(C.Structure):
     """ocn_transport_t: caller-supplied collectives (device addresses as integers)"""
     EXCHANGE_START = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -94,6 +100,7 @@ SYMBOLS = {
     "ocn_unpack_x_halos": (C.c_int, [_vp, _pp, _vp, C.c_int, _vp, _vp]),
     "ocn_compute_linear_flux_bc": (C.c_int, [_vp, _vp, _ip, C.c_int, C.c_double, C.c_double, _vp]),
     "ocn_model_set_linear_flux_bc": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_double, C.c_double, C.c_char_p]),
+    "ocn_model_set_forcing": (C.c_int, [_vp, C.c_int, C.POINTER(Forcing), C.c_int]),
     "ocn_make_pressure_correction_range": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _ip]),
     "ocn_make_pressure_correction_divide": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _ip]),
     "ocn_model_reset": (C.c_int, [_vp]),

@@ -6,6 +6,7 @@
 #include "ocn_tendency_fused.h"
 #include "ocn_tendency_roles.h"
 #include "ocn_epilogue_march.h"
+#include "ocn_forcing.h"
 #include <hipfft/hipfft.h>
 #include <cmath>
 #include <cstdarg>
@@ -578,13 +579,15 @@ static bool fused_path(const DGrid &g, const int *range, int ntr, int impl) {
 
 static int compute_tendencies(const DGrid &g, const double *u, const double *v, const double *w, const double *const *tr,
                               int ntr, double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range, int impl,
-                              const FusedSubstep *sub = nullptr) {
+                              const FusedSubstep *sub = nullptr, const ForcingTable *ftab = nullptr) {
     if (sub && !fused_path(g, range, ntr, impl)) return fail(OCN_ESTATE, "fused substep requested on the per-field tendency path");
+    if (ftab && !(impl == 2 && fused_path(g, range, ntr, impl) && role_tendency_supported(g)))
+        return fail(OCN_ESTATE, "forcing term requested in a tendency launch other than the role kernel");
     if (fused_path(g, range, ntr, impl)) {
         int rc = check_range(g, range, nullptr);
         if (rc) return rc;
         if (impl == 2 && !role_tendency_supported(g)) impl = 1;          // planes too large for the role kernel's offsets: the all-fields kernel
-        rc = impl == 2 ? launch_role_tendency(g, g_stream, u, v, w, tr, ntr, Gu, Gv, Gw, Gc, range, sub)
+        rc = impl == 2 ? launch_role_tendency(g, g_stream, u, v, w, tr, ntr, Gu, Gv, Gw, Gc, range, sub, ftab)
                        : launch_fused_tendency(g, g_stream, u, v, w, tr, ntr, Gu, Gv, Gw, Gc, range, sub);
         if (rc) return fail(rc, "fused tendency launch failed");
         KERNEL_CHECK();
@@ -2371,6 +2374,12 @@ struct ocn_model_s {
     bool has_amd = false;                   // closure = AnisotropicMinimumDissipation(Cν, Cκ)
     double Cnu = 0.0, Ckappa[OCN_MAX_FIELDS] = {};
     double *nu_e = nullptr, *kappa_e[OCN_MAX_FIELDS] = {};   // diffusivity_fields.νₑ, .κₑ (ccc, with halos)
+    // forcing = (name = F,) (ocn_forcing.h): host copy of the descriptors, the device-resident table the kernels read, the device copies
+    // of the tables (per field and term: mask, target)
+    ForcingTable forcing_h = {};
+    ForcingTable *forcing_d = nullptr;
+    double *forcing_tables[OCN_MAX_FIELDS][OCN_MAX_FORCING_TERMS][2] = {};
+    int fused_forcing = 1;
     bool has_coriolis = false;              // coriolis = FPlane(f)
     double fcor = 0.0;
     int buoyancy_kind = 0, bT_index = 0, S_index = 0;    // 0 nothing, 1 BuoyancyTracer, 2 linear SeawaterBuoyancy
@@ -2398,6 +2407,9 @@ extern "C" int ocn_model_destroy(ocn_model_t m) {
     if (m->graph_exec) hipGraphExecDestroy(m->graph_exec);
     for (int f = 0; f < m->nf; ++f) { hipFree(m->U[f]); hipFree(m->U2[f]); hipFree(m->Gn[f]); hipFree(m->Gm[f]); }
     hipFree(m->pHY);
+    hipFree(m->forcing_d);
+    for (auto &f : m->forcing_tables)
+        for (auto &t : f) { hipFree(t[0]); hipFree(t[1]); }
     hipFree(m->nu_e);
     for (int t = 0; t < OCN_MAX_FIELDS; ++t) hipFree(m->kappa_e[t]);
     hipFree(m->p); hipFree(m->blockmax);
@@ -2545,12 +2557,49 @@ extern "C" int ocn_model_set_option(ocn_model_t m, const char *key, int value) {
     if (!strcmp(key, "swap_tendencies")) { m->swap_tendencies = value; return OCN_OK; }
     if (!strcmp(key, "fuse_substep")) { m->fuse_substep = value; return OCN_OK; }
     if (!strcmp(key, "fused_epilogue")) { m->fused_epilogue = value; return OCN_OK; }
+    if (!strcmp(key, "fused_forcing")) { m->fused_forcing = value; return OCN_OK; }
     if (!strcmp(key, "profile")) { m->profile = value; m->events_used = 0; return OCN_OK; }
     if (dist_model_set_option(m, key, value) == OCN_OK) return OCN_OK;
     return ocn_set_option(key, value);
 }
 
 static bool has_physics(const ocn_model_s *m) { return m->has_coriolis || m->buoyancy_kind != 0 || m->has_closure || m->has_amd; }
+
+static bool has_forcing(const ocn_model_s *m) {
+    for (int f = 0; f < m->nf; ++f)
+        if (m->forcing_h.nterms[f] > 0) return true;
+    return false;
+}
+static bool epilogue_runs(const ocn_model_s *m);
+// the forcing term rides in the role tendency kernel (FORCE instantiation) when that kernel completes the tendency by itself: no physics
+// epilogue, no Flux condition, the role kernel on the whole single-GPU grid, reference arithmetic, Periodic z (the Bounded-z instantiation
+// spilled, ocn_tendency_roles.h) -- the configs[1]-plus-sponge case, which keeps the RK3 substep fused. Partitioned models (interior / strip launches) and everything else take the standalone pass.
+static bool forcing_in_role(const ocn_model_s *m) {
+    const DGrid &g = m->grid->d;
+    return has_forcing(m) && m->fused_forcing && !m->dm && !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && !epilogue_runs(m) &&
+           m->tendency_impl == 2 && g_arithmetic == 0 && g.tz == OCN_PERIODIC && fused_path(g, nullptr, m->ntr, 2) && role_tendency_supported(g);
+}
+// which pass adds the forcing term (option "forcing_path"): 0 none, 1 the role tendency kernel, 3 the standalone pass (add_forcing_kernel);
+// 2 (inside the physics epilogue) is reserved: that fusion is not built
+static int forcing_path(const ocn_model_s *m) { return has_forcing(m) ? (forcing_in_role(m) ? 1 : 3) : 0; }
+
+// G = G_rest + F of every forced field (ocn_forcing.h), one launch after the tendency evaluation is complete (advection, physics
+// epilogue) and before the Flux-condition terms (compute_flux_bc_tendencies, which the steppers call when the next stage begins)
+static int add_forcing(ocn_model_s *m) {
+    ForcingLaunch L = {};
+    int nx = 0, ny = 0, nz = 0;
+    for (int f = 0; f < m->nf; ++f) {
+        if (m->forcing_h.nterms[f] <= 0) continue;
+        const Range6 &r = m->forcing_h.r[f];
+        if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) continue;
+        L.f[L.n] = f; L.U[L.n] = m->U[f]; L.G[L.n] = m->Gn[f]; ++L.n;
+        nx = std::max(nx, r.i1 - r.i0 + 1); ny = std::max(ny, r.j1 - r.j0 + 1); nz = std::max(nz, r.k1 - r.k0 + 1);
+    }
+    if (L.n == 0) return OCN_OK;
+    hipLaunchKernelGGL(add_forcing_kernel, grid3(nx, ny, nz * L.n, BLK), BLK, 0, g_stream, m->grid->d, (const ForcingTable *)m->forcing_d, L, nz);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
 
 // Coriolis, hydrostatic pressure gradient and closure terms of every field -- and, when `sub` is given, the RK3 substep of the next
 // stage -- in one launch (tendency_epilogue_kernel)
@@ -2676,6 +2725,7 @@ static bool can_fuse_substep(const ocn_model_s *m) {
     // without extra physics the substep rides in the fused advection kernel; with Coriolis / buoyancy / closure terms it rides in
     // the epilogue pass that completes the tendencies (any advection path); a valued Flux condition is added after both
     if (!m->fuse_substep || !m->swap_tendencies) return false;
+    if (has_forcing(m) && !forcing_in_role(m)) return false;         // the forcing pass completes G after the launch the substep would ride in
     if (epilogue_runs(m)) return true;                               // the epilogue pass also applies the Flux conditions
     return !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && fused_path(m->grid->d, nullptr, m->ntr, m->tendency_impl);
 }
@@ -2689,6 +2739,8 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     if (!strcmp(key, "graph_captures")) { *value = m->graph_captures; return OCN_OK; }
     if (!strcmp(key, "graph_failures")) { *value = m->graph_failures; return OCN_OK; }
     if (!strcmp(key, "fuse_substep")) { *value = m->fuse_substep; return OCN_OK; }
+    if (!strcmp(key, "fused_forcing")) { *value = m->fused_forcing; return OCN_OK; }
+    if (!strcmp(key, "forcing_path")) { *value = forcing_path(m); return OCN_OK; }
     if (!strcmp(key, "fuse_substep_active")) { *value = can_fuse_substep(m) ? 1 : 0; return OCN_OK; }
     // what the tendency LAUNCH itself carries (bench.py prices its bytes with these): the next stage's substep rides in the advection kernel
     // only without physics / Flux conditions (with them it rides in the epilogue pass); the tendency of the second stage is then not stored
@@ -2701,7 +2753,7 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     return fail(OCN_EINVAL, "unknown model option '%s'", key);
 }
 
-// update_state! (update_nonhydrostatic_model_state.jl:20-56), closure / buoyancy / forcing = nothing
+// update_state! (update_nonhydrostatic_model_state.jl:20-56)
 static int dist_update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub);
 static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub, const int *amd_range);
 static int update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub = nullptr) {
@@ -2745,7 +2797,7 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
         }
         const bool physics = has_physics(m) || epilogue_runs(m);
         rc = compute_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
-                                m->tendency_impl, physics ? nullptr : sub);
+                                m->tendency_impl, physics ? nullptr : sub, forcing_in_role(m) ? m->forcing_d : nullptr);
         if (ev) HIP_TRY(hipEventRecord(ev->second, g_stream));
         if (!rc && physics) {
             if (epilogue_runs(m)) { if (has_physics(m) || sub) rc = tendency_epilogue(m, sub); }      // (Flux conditions alone and no substep: nothing to do)
@@ -2761,6 +2813,8 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
                                             m->Gn[2], m->Gn + 3, nullptr, m->nu_e, m->kappa_e);
             }
         }
+        // the last interior term: in the role kernel above, or one pass here (then no substep rides along: can_fuse_substep)
+        if (!rc && has_forcing(m) && !forcing_in_role(m)) rc = add_forcing(m);
     }
     return rc;
 }
@@ -2901,6 +2955,88 @@ extern "C" int ocn_model_set_linear_flux_bc(ocn_model_t m, const char *name, int
     m->any_bc = true;
     m->lin[f][side].on = true; m->lin[f][side].dep = fd; m->lin[f][side].a = a; m->lin[f][side].b = b;
     m->any_linear_flux = true;
+    return OCN_OK;
+}
+
+// forcing = (name = F,) of the model constructor (Forcings/model_forcing.jl, relaxation.jl, forcing.jl:165-177, multiple_forcings.jl):
+// the descriptors of field `field` are replaced; the device-resident table is rewritten (ocn_forcing.h)
+extern "C" int ocn_model_set_forcing(ocn_model_t m, int field, const ocn_forcing_t *terms, int nterms) {
+    NEED_INIT();
+    if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (field < 0 || field >= m->nf) return fail(OCN_EINVAL, "forcing field index %d outside 0..%d", field, m->nf - 1);
+    if (nterms < 0 || nterms > OCN_MAX_FORCING_TERMS) return fail(OCN_EINVAL, "nterms = %d outside 0..%d", nterms, OCN_MAX_FORCING_TERMS);
+    if (nterms > 0 && !terms) return fail(OCN_EINVAL, "NULL terms");
+    const DGrid &g = m->grid->d;
+    const int T[3] = {g.tx, g.ty, g.tz};
+    int P[3];
+    parent_size(g, m->loc[field], P);
+    for (int q = 0; q < nterms; ++q) {
+        const ocn_forcing_t &t = terms[q];
+        if (t.kind == OCN_FORCING_ARRAY) {
+            if (!t.array) return fail(OCN_EINVAL, "term %d: Forcing(array) with a NULL array", q);
+        } else if (t.kind == OCN_FORCING_RELAXATION) {
+            const int dirs[2] = {t.mask_dir, t.target_dir};
+            const double *tabs[2] = {t.mask_table, t.target_table};
+            for (int w = 0; w < 2; ++w) {
+                if (dirs[w] < -1 || dirs[w] > 2) return fail(OCN_EINVAL, "term %d: %s direction %d is not -1, 0, 1 or 2", q, w ? "target" : "mask", dirs[w]);
+                if (dirs[w] >= 0 && !tabs[w]) return fail(OCN_EINVAL, "term %d: NULL %s table", q, w ? "target" : "mask");
+                if (dirs[w] >= 0 && T[dirs[w]] == OCN_FLAT)
+                    return fail(OCN_EINVAL, "term %d: a %s along %c, which is Flat (relaxation.jl has no method for it)", q, w ? "target" : "mask", "xyz"[dirs[w]]);
+            }
+        } else return fail(OCN_EINVAL, "term %d: unknown forcing kind %d", q, t.kind);
+    }
+    // device copies of the tables first: nothing of the previous forcing is released before the new one is complete
+    double *dev[OCN_MAX_FORCING_TERMS][2] = {};
+    auto release = [&]() { for (auto &d : dev) { hipFree(d[0]); hipFree(d[1]); } };
+    for (int q = 0; q < nterms; ++q)
+        for (int w = 0; w < 2; ++w) {
+            const int dir = w ? terms[q].target_dir : terms[q].mask_dir;
+            if (terms[q].kind != OCN_FORCING_RELAXATION || dir < 0) continue;
+            const size_t bytes = (size_t)P[dir] * sizeof(double);
+            hipError_t e = dev_alloc((void **)&dev[q][w], bytes);
+            if (e == hipSuccess) e = hipMemcpyAsync(dev[q][w], w ? terms[q].target_table : terms[q].mask_table, bytes, hipMemcpyHostToDevice, g_stream);
+            if (e != hipSuccess) { release(); return fail((int)e, "forcing table: %s", hipGetErrorString(e)); }
+        }
+    if (!m->forcing_d) {
+        hipError_t e = dev_alloc((void **)&m->forcing_d, sizeof(ForcingTable));
+        if (e != hipSuccess) { m->forcing_d = nullptr; release(); return fail((int)e, "dev_alloc(forcing table): %s", hipGetErrorString(e)); }
+    }
+    // the table must not change under work already queued that reads it
+    hipError_t e = hipStreamSynchronize(g_stream);
+    if (e != hipSuccess) { release(); return fail((int)e, "hipStreamSynchronize: %s", hipGetErrorString(e)); }
+    // the new host table is completed and copied first; the model's table and the old device tables change only once that succeeded
+    ForcingTable h = m->forcing_h;
+    h.nterms[field] = nterms;
+    for (int q = 0; q < OCN_MAX_FORCING_TERMS; ++q) {
+        ForcingTerm &d = h.t[field][q];
+        d = ForcingTerm{};
+        if (q >= nterms) continue;
+        const ocn_forcing_t &t = terms[q];
+        d.kind = t.kind;
+        d.array = t.kind == OCN_FORCING_ARRAY ? t.array : nullptr;
+        d.mask_dir = t.kind == OCN_FORCING_RELAXATION ? t.mask_dir : -1;
+        d.target_dir = t.kind == OCN_FORCING_RELAXATION ? t.target_dir : -1;
+        d.rate_mask = t.rate_mask; d.target = t.target;
+        d.mask_table = dev[q][0]; d.target_table = dev[q][1];
+    }
+    for (int f = 0; f < m->nf; ++f) {
+        h.r[f] = default_range(g, m->loc[f], f < 3);
+        const FView v = make_view(g, nullptr, m->loc[f]);
+        h.s1[f] = v.s1; h.s2[f] = v.s2; h.off[f] = v.off;
+    }
+    const FView a = make_view(g, nullptr, LOC_C);
+    h.as1 = a.s1; h.as2 = a.s2; h.aoff = a.off;
+    e = hipMemcpy(m->forcing_d, &h, sizeof(ForcingTable), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        // the device copy may be partial: try to restore the previous table (whose tables are still allocated) before reporting
+        (void)hipMemcpy(m->forcing_d, &m->forcing_h, sizeof(ForcingTable), hipMemcpyHostToDevice);
+        release();
+        return fail((int)e, "forcing table: %s", hipGetErrorString(e));
+    }
+    m->forcing_h = h;
+    for (int q = 0; q < OCN_MAX_FORCING_TERMS; ++q)
+        for (int w = 0; w < 2; ++w) { hipFree(m->forcing_tables[field][q][w]); m->forcing_tables[field][q][w] = dev[q][w]; }
+    m->epoch += 1;                  // a captured time-step graph launches other kernels now
     return OCN_OK;
 }
 

@@ -717,6 +717,7 @@ static int dist_update_state(ocn_model_s *m, bool compute_tend, const FusedSubst
     if ((rc = ocn_dist_exchange_wait(dm->dist))) return rc;                // synchronize_communication! (distributed_fields.jl:71-88)
     if ((rc = x_halo_buffers(g, m->U, m->loc, m->nf, dm->wr, dm->er, false))) return rc;
     if ((rc = tend(ws)) || (rc = tend(es))) return rc;                     // compute_buffer_tendencies!
+    if (has_forcing(m)) return add_forcing(m);                             // pointwise: one pass over interior and strips together
     return OCN_OK;
 }
 

@@ -17,6 +17,7 @@
 // spent on addresses inside the loop.
 #pragma once
 #include "ocn_tendency_fused.h"
+#include "ocn_forcing.h"
 
 #ifndef OCN_ROLE_WAVES
 #define OCN_ROLE_WAVES 6      // waves per SIMD the register allocation must allow (8-wave workgroups: 4 = two per CU, 6 = three)
@@ -53,6 +54,7 @@ struct RoleArgs {
     int has_zeta;
     int store_G;               // 0: the tendency is consumed by the fused substep only (FusedSubstep::store_G)
     double dt, gamma, zeta;
+    const ForcingTable *ftab;  // FORCE instantiations: the model's forcing table (ocn_forcing.h), added when a cell closes
 };
 
 // Buffer addressing (MUBUF): descriptor of the whole parent array (4 SGPRs) + scalar plane offset + per-thread 32-bit byte offset
@@ -231,7 +233,7 @@ __device__ __forceinline__ void role_barrier() {
 // operations of the plane, right behind the loads of the y-window, so that no wait of this plane includes them: they have the
 // arithmetic of the y-flux, the barrier and the first loads of the next plane to complete. The new element of the z-window
 // arrives one plane ahead of its use (qn), the previous tendency of the cell closed in the next plane likewise (gmn).
-template <int ROLE, int TY, bool SUB, bool BZ, int ARITH, typename Args>
+template <int ROLE, int TY, bool SUB, bool BZ, int ARITH, bool FORCE, typename Args>
 __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const int fidx, const int i0, const int j0, const int kc0,
                                            const int kc1, double (*FX)[TY][66], double (*FY)[TY + 1][64]) {
     // Bounded z: only the planes within reach of a wall need the fallback logic of the scheme (every z-stencil test of
@@ -352,6 +354,12 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
         const double dy = FY[pb][row0 + 1][lane] - FY[pb][row0][lane];
         const double div = vinv * ((dx + dy) + (fz - fz_prev));
         Gn = -div + 0.0;
+        if (FORCE) {
+            // G = G_rest + F (ocn_forcing.h) on the cell just closed, (i, j, k - 1); φ = its value, already in the z-window. Lanes outside
+            // the range (their stores are dropped) evaluate a clamped in-range cell, so no table or array is read out of bounds.
+            if (a.ftab->nterms[fidx] > 0)
+                Gn = Gn + forcing_sum(a.ftab, fidx, g, min(i, a.r.i1), min(j, a.r.j1), max(k - 1, a.r.k0), qz.s[2]);
+        }
         store = cell_r && k > kc0 && (ROLE != ROLE_W || k - 1 >= a.wk0) && (!(OCN_ROLE_ABLATE & 4) || Gn == 1.2345);
         if (SUB) {
             // rk3_substep_field! of the next stage on the cell just closed (runge_kutta_3.jl:212-226)
@@ -423,7 +431,7 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
     }
 }
 
-template <int NTR, int TY, bool BZ, bool SUB, int ARITH = 0>
+template <int NTR, int TY, bool BZ, bool SUB, int ARITH = 0, bool FORCE = false>
 __global__ void __launch_bounds__(64 * (TY + 1), OCN_ROLE_WAVES) role_tendency_kernel(DGrid gin, RoleArgs<3 + NTR> a) {
     constexpr int NF = 3 + NTR;
     __shared__ double FX[2][TY][66];                // low-side x-fluxes of columns 0..64 (65 used, padded)
@@ -442,10 +450,10 @@ __global__ void __launch_bounds__(64 * (TY + 1), OCN_ROLE_WAVES) role_tendency_k
     const int i0 = a.r.i0 + (int)(tile % (unsigned)a.ntile_x) * 64, j0 = a.r.j0 + (int)(tile / (unsigned)a.ntile_x) * TY;
     const int kc0 = a.r.k0 + (int)chunk * a.kchunk;
     const int kc1 = min(kc0 + a.kchunk - 1, a.r.k1);
-    if (role == 0) role_march<ROLE_U, TY, SUB, BZ, ARITH>(g, a, 0, i0, j0, kc0, kc1, FX, FY);
-    else if (role == 1) role_march<ROLE_V, TY, SUB, BZ, ARITH>(g, a, 1, i0, j0, kc0, kc1, FX, FY);
-    else if (role == 2) role_march<ROLE_W, TY, SUB, BZ, ARITH>(g, a, 2, i0, j0, kc0, kc1, FX, FY);
-    else role_march<ROLE_C, TY, SUB, BZ, ARITH>(g, a, (int)role, i0, j0, kc0, kc1, FX, FY);
+    if (role == 0) role_march<ROLE_U, TY, SUB, BZ, ARITH, FORCE>(g, a, 0, i0, j0, kc0, kc1, FX, FY);
+    else if (role == 1) role_march<ROLE_V, TY, SUB, BZ, ARITH, FORCE>(g, a, 1, i0, j0, kc0, kc1, FX, FY);
+    else if (role == 2) role_march<ROLE_W, TY, SUB, BZ, ARITH, FORCE>(g, a, 2, i0, j0, kc0, kc1, FX, FY);
+    else role_march<ROLE_C, TY, SUB, BZ, ARITH, FORCE>(g, a, (int)role, i0, j0, kc0, kc1, FX, FY);
 }
 
 // The role kernel addresses memory with a 31-bit byte offset (bit 31 is the out-of-range flag of its buffer descriptors, whose num_records
@@ -493,22 +501,31 @@ static int launch_roles_t(const DGrid &g, hipStream_t stream, RoleArgs<3 + NTR> 
     const unsigned nblocks = (unsigned)a.band * 8u * NF;
     const dim3 blk(64 * (TY + 1));
 #define OCN_LAUNCH_ROLES(BZV, SUBV, AR) hipLaunchKernelGGL((role_tendency_kernel<NTR, TY, BZV, SUBV, AR>), dim3(nblocks), blk, (size_t)g_role_ldspad, stream, g, a)
-    if (g_arithmetic == 1) {          // the opt-in contracted arithmetic of the WENO flux (ocn_device.h; option "arithmetic")
+#define OCN_LAUNCH_ROLES_F(BZV, SUBV) hipLaunchKernelGGL((role_tendency_kernel<NTR, TY, BZV, SUBV, 0, true>), dim3(nblocks), blk, (size_t)g_role_ldspad, stream, g, a)
+    if (a.ftab) {
+        // forcing term in the kernel: reference arithmetic and a Periodic z only (the caller checks both). The Bounded-z instantiation with
+        // the substep riding along needs 3 VGPRs more than OCN_ROLE_WAVES = 6 leaves and spilled to scratch: it is not built
+        if (g_arithmetic != 0 || g.tz != 0) return -2;
+        if (sub) OCN_LAUNCH_ROLES_F(false, true); else OCN_LAUNCH_ROLES_F(false, false);
+    } else if (g_arithmetic == 1) {          // the opt-in contracted arithmetic of the WENO flux (ocn_device.h; option "arithmetic")
         if (g.tz != 0) { if (sub) OCN_LAUNCH_ROLES(true, true, 1); else OCN_LAUNCH_ROLES(true, false, 1); }
         else           { if (sub) OCN_LAUNCH_ROLES(false, true, 1); else OCN_LAUNCH_ROLES(false, false, 1); }
     } else {
         if (g.tz != 0) { if (sub) OCN_LAUNCH_ROLES(true, true, 0); else OCN_LAUNCH_ROLES(true, false, 0); }
         else           { if (sub) OCN_LAUNCH_ROLES(false, true, 0); else OCN_LAUNCH_ROLES(false, false, 0); }
     }
+#undef OCN_LAUNCH_ROLES_F
 #undef OCN_LAUNCH_ROLES
     return 0;
 }
 
 template <int NTR>
 static int launch_roles_n(const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w, const double *const *tr,
-                          double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range, const FusedSubstep *sub) {
+                          double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range, const FusedSubstep *sub,
+                          const ForcingTable *ftab) {
     constexpr int NF = 3 + NTR;
     RoleArgs<NF> a;
+    a.ftab = ftab;
     a.U[0] = u; a.U[1] = v; a.U[2] = w; a.G[0] = Gu; a.G[1] = Gv; a.G[2] = Gw;
     for (int t = 0; t < NTR; ++t) { a.U[3 + t] = tr[t]; a.G[3 + t] = Gc[t]; }
     a.has_zeta = sub ? sub->has_zeta : 0;
@@ -531,12 +548,12 @@ static int launch_roles_n(const DGrid &g, hipStream_t stream, const double *u, c
 
 static inline int launch_role_tendency(const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w,
                                        const double *const *tr, int ntr, double *Gu, double *Gv, double *Gw, double *const *Gc,
-                                       const int *range, const FusedSubstep *sub = nullptr) {
+                                       const int *range, const FusedSubstep *sub = nullptr, const ForcingTable *ftab = nullptr) {
     switch (ntr) {
-        case 0: return launch_roles_n<0>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub);
-        case 1: return launch_roles_n<1>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub);
-        case 2: return launch_roles_n<2>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub);
-        case 3: return launch_roles_n<3>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub);
+        case 0: return launch_roles_n<0>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
+        case 1: return launch_roles_n<1>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
+        case 2: return launch_roles_n<2>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
+        case 3: return launch_roles_n<3>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
         default: return -2;
     }
 }

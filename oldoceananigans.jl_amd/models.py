@@ -35,8 +35,9 @@ class Clock:
 
 
 class NonhydrostaticModel:
-    """NonhydrostaticModel(; grid, advection=WENO(), tracers=(:T, :S), timestepper=:RungeKutta3) with
-    coriolis / buoyancy / closure / forcing = nothing -- the configuration BASELINE.json benchmarks."""
+    """NonhydrostaticModel(; grid, advection=WENO(), tracers=(:T, :S), timestepper=:RungeKutta3, coriolis, buoyancy, closure, forcing,
+    boundary_conditions); BASELINE.json benchmarks the configuration with all of them = nothing. `forcing` takes the closure-free
+    forcings of forcings.py (Relaxation, Forcing(array), MultipleForcings / tuples)."""
 
     def __init__(self, grid, advection=None, tracers=("T", "S"), timestepper="RungeKutta3", buoyancy=None, coriolis=None,
                  closure=None, forcing=None, boundary_conditions=None):
@@ -48,8 +49,6 @@ class NonhydrostaticModel:
         if timestepper not in ("RungeKutta3", "QuasiAdamsBashforth2"):
             raise NotImplementedError("timestepper must be :RungeKutta3 (hot path) or :QuasiAdamsBashforth2 (SURVEY.md 8f.1)")
         self.timestepper, self.χ = timestepper, 0.1          # QuasiAdamsBashforth2TimeStepper(χ = 0.1)
-        if forcing is not None:
-            raise NotImplementedError("forcing != nothing is outside the accelerated hot path (SURVEY.md 8f)")
         from .buoyancy import BuoyancyTracer, FPlane, SeawaterBuoyancy
         if coriolis is not None and not isinstance(coriolis, FPlane):
             raise NotImplementedError("coriolis must be nothing or FPlane(f)")
@@ -76,6 +75,12 @@ class NonhydrostaticModel:
             grid = with_halo(required, grid)
         self.grid, self.advection = grid, advection
         self.tracer_names = tuple(str(t) for t in (tracers if isinstance(tracers, (tuple, list)) else (tracers,)))
+        # forcing = (u = ..., T = ...,) (model_forcing.jl): regularised before the handle exists, so a refused forcing costs no device memory
+        from . import forcings as _forcings
+        locations = {"u": (Face, Center, Center), "v": (Center, Face, Center), "w": (Center, Center, Face)}
+        locations.update({t: (Center, Center, Center) for t in self.tracer_names})
+        self._forcing_terms = _forcings.model_forcing(getattr(grid, "local", grid), locations, forcing)
+        self.forcing = dict(forcing or {})
         self.handle = self._create_handle(grid, len(self.tracer_names))
         self.clock = Clock(self)
         V = namedtuple("Velocities", "u v w")
@@ -114,6 +119,10 @@ class NonhydrostaticModel:
         elif closure is not None:
             self._kappa, kp = closure.kappa_array(self.tracer_names)
             _lib.check(_lib.lib().ocn_model_set_closure(self.handle, closure.ν, kp))
+        self._forcing_keep = []                          # device arrays of Forcing(array): owned (numpy) or borrowed (Field)
+        for name, terms in self._forcing_terms.items():
+            _forcings.set_forcing(self.handle, ("u", "v", "w").index(name) if name in ("u", "v", "w") else 3 + self.tracer_names.index(name),
+                                  terms, getattr(grid, "local", grid), self._forcing_keep)
         # boundary_conditions = (u = FieldBoundaryConditions(top = FluxBoundaryCondition(Q)), ...) (nonhydrostatic_model.jl:
         # 163-190): constant Flux / Value / Gradient / Open conditions on Bounded sides
         self.boundary_conditions = dict(boundary_conditions or {})

@@ -22,6 +22,8 @@ def jl_type(t):
         return "Ptr{Ptr{Cvoid}}" if ptr else "Ptr{Cvoid}"
     if base == "ocn_bc_t":
         return "Ptr{OcnBC}"
+    if base == "ocn_forcing_t":
+        return "Ptr{OcnForcing}"
     if base == "ocn_transport_t":
         return "Ptr{OcnTransport}"
     if base == "char":
@@ -49,7 +51,8 @@ table = [MARK, "",
          "reference function it replaces). Handles are `Ptr{Cvoid}`, device arrays are passed as `Ptr{Cdouble}` obtained from",
          "`pointer(parent(field.data))`, arrays of device pointers as `Ptr{Ptr{Cdouble}}` built on the host; `OcnBC` / `OcnTransport` mirror",
          "`ocn_bc_t` / `ocn_transport_t` field by field (`struct OcnBC; kind::Cint; value::Cdouble; array::Ptr{Cdouble}; end`). Every `Cint`",
-         "return is a status: `check(rc)` of §1.", "", "| entry point | binding |", "|---|---|"] + rows
+         "return is a status: `check(rc)` of §1. `OcnForcing` mirrors `ocn_forcing_t` the same way; its mask and target tables are host",
+         "`Vector{Float64}`s the binder fills with the reference's own `GaussianMask` / `PiecewiseLinearMask` / `LinearTarget` at the field's nodes.", "", "| entry point | binding |", "|---|---|"] + rows
 p = os.path.join(ROOT, "INTEGRATION.md")
 s = open(p).read()
 if MARK in s:
