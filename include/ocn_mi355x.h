@@ -316,15 +316,16 @@ int ocn_model_cell_advection_timescale(ocn_model_t model, double *tau);
  * array, halos included); *result = 1 if any is NaN */
 int ocn_hasnan(const double *data, size_t n, int *result);
 int ocn_max_abs_divergence(ocn_grid_t grid, const double *u, const double *v, const double *w, double *value);
-/* options: "tendency_impl" 0 = per-field kernels as the reference launches them, 1 = fused flux-sharing kernel;
- * "swap_tendencies" 1 = cache_previous_tendencies! by pointer swap, 0 = by copy kernel; "fuse_substep" 1 = fuse the
- * substeps of RK3 stages 2 and 3 into the preceding tendency evaluation (second set of prognostic arrays, swapped twice per
- * time-step); "profile" 1 = record HIP
- * events around every tendency evaluation on the launch stream */
+/* sets a tuning option of this model only (the keys: ocn_set_option). A creation key fails with OCN_ESTATE, a partitioned key on a
+ * single-GPU model with OCN_EINVAL. One more key: "profile" 1 = record HIP events around every tendency evaluation on the launch stream
+ * (ocn_model_profile_read). */
 int ocn_model_set_option(ocn_model_t model, const char *key, int value);
-/* reads an option back; additionally "fused_tendency_active" (1 when the fused flux-sharing kernel runs for this grid) and
- * "fuse_substep_active" (1 when the rk3_substep! of stages 2 and 3 is fused into the preceding tendency evaluation:
- * option "fuse_substep" = 1 (default), fused kernel, tendencies cached by pointer swap, no Flux boundary condition) */
+/* reads this model's value of every option key (ocn_set_option; "fused_step": whether the fused pressure step runs, 0 on a single-GPU
+ * model) and what the configuration makes of them: "fused_tendency_active" (1 when a flux-sharing tendency kernel runs for this grid),
+ * "fuse_substep_active" (1 when the rk3_substep! of stages 2 and 3 is fused into the preceding tendency evaluation: option
+ * "fuse_substep" = 1, flux-sharing kernel, tendencies cached by pointer swap, no Flux boundary condition), "substep_in_tendency_kernel"
+ * (1 when that substep rides in the tendency launch itself), "forcing_path" (ocn_model_set_forcing), "graph_captures",
+ * "graph_replays", "graph_failures" (option "use_graph") and, on a partitioned model, "dist_poisson_layout" */
 int ocn_model_get_option(ocn_model_t model, const char *key, int *value);
 /* boundary_conditions = (name = FieldBoundaryConditions(side = BoundaryCondition(kind, value)),) of the model
  * constructor (nonhydrostatic_model.jl:115-244); name "u","v","w","c0".. and, with an LES closure, the diffusivity fields "nu_e",
@@ -377,32 +378,68 @@ typedef struct {
     double target;
 } ocn_forcing_t;
 int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *terms, int nterms);
-/* library-wide knobs (no reference equivalent; the defaults are the tuned values, 0 / 1 unless noted):
- *   pressure solve: "real_fft" (1: D2Z/Z2D, 0: the reference's complex-to-complex), "c2r_strided", "fused_zfft" (z FFT + divide +
- *     inverse z FFT as one LDS pass), "split_solve" (model time-step: 1-D x plans on 128-B-padded rows + LDS column-FFT kernel for y +
- *     pressure correction and p/Δt from the dense solution), "skip_stage_pressure" (1: RK3 stages 1 and 2 do not store their pNHS --
- *     nothing can read it before the next stage overwrites it; after a time-step the field holds the last stage's pressure either way),
- *     "skip_dead_tendency_store" (1: the tendency evaluated after RK3's second stage feeds the third stage's substep riding along and is
- *     not stored -- nothing else reads it; after a time-step Gⁿ = G(U³) and G⁻ = G(U¹) either way);
- *   x-slab solve: "dist_substructured" (1: gathered interface solve, 0: the reference's two transposes), "dist_zfirst" (z-fastest
- *     local layout), "dist_yline" (LDS column-FFT kernel for the local y transform), "dist_xfast" (the substructured solve in the fields'
- *     own x-fastest layout), "dist_fuse_source" (source term written straight into the z transform's line buffer), "dist_xline_group"
- *     (several short x lines per wave in the Thomas scans), "dist_fused_step" (pressure step without fills / copies between its stages),
- *     "dist_pencil_transposes" (pencil partitions: the reference's transposing solver; 0: gathered solve), "line_zl512" (4 | 8 lines per
- *     workgroup of the LDS line transforms at 512-point lines);
- *   physics passes: "amd_march" / "epilogue_march" (z-marching eddy-diffusivity kernel / tendency epilogue that evaluate every point
- *     operand / face flux once; 0: one thread per value, everything recomputed -- same bits), "epilogue_kchunk" (levels per workgroup,
- *     0 = automatic), "epilogue_rows" (rows per workgroup, 1 .. 8);
- *   fused tendency kernel: "fused_ty" (tile rows 3 | 7), "fused_kchunk" (levels per workgroup, 0 = automatic), "fused_minw",
- *     "fused_zwin" (register z-windows), "fused_xcd" (XCD-aware tile order; measured: no effect);
- *   halo fills: "fused_halo" (one launch per periodic fill);
- *   "arithmetic": 0 (default) the reference's IEEE operation sequence in every kernel -- results bit-identical to a faithful CPU
- *     evaluation of weno_interpolants.jl; 1 the opt-in CONTRACTED WENO-5 flux of the flux-sharing tendency kernel (fma-contracted
- *     sub-stencil polynomials and alpha weights, one normalisation of the weighted sum, reciprocal without the IEEE divide's fix-up,
- *     advecting transport multiplied by the area after its interpolation): fewer FP64 instructions, fields within 1e-12 of mode 0
- *     on O(1) data but not bit-identical.
- * Model options (ocn_model_set_option): "tendency_impl" (1 fused, 0 per-field kernels), "swap_tendencies", "fuse_substep",
- * "fused_epilogue", "use_graph" (hipGraph replay of the RK3 step; measured: no gain, default 0), "profile". */
+/* Tuning options (no reference equivalent; the defaults are the tuned values). ocn_set_option sets the library default of a key; may be
+ * called before ocn_init. A model copies the defaults when it is created, and ocn_model_set_option changes that model's copy only.
+ * Grid-level entry points and standalone solvers (ocn_compute_*, ocn_fill_halo_regions*, ocn_poisson_*, ocn_solve_for_pressure,
+ * ocn_dist_poisson_*) read the defaults when they are called.
+ * Scopes: step -- read while stepping; creation -- read only when a model or solver is built, so set it with ocn_set_option before
+ * creating the model; partitioned -- read by the partitioned step only. Values are 0 / 1 unless a range is given.
+ *   tendency evaluation:
+ *   "tendency_impl" = 2 (step): 0 the per-field kernels as the reference launches them, 1 the all-fields flux-sharing kernel, 2 the
+ *       one-field-per-workgroup flux-sharing kernel; 0 .. 2 (the grid-level tendency entry points take 1 for 0)
+ *   "arithmetic" = 0 (step): 0 the reference's IEEE operation sequence in every kernel -- results bit-identical to a faithful CPU
+ *       evaluation of weno_interpolants.jl; 1 the opt-in CONTRACTED WENO-5 flux of the one-field-per-workgroup kernel (fma-contracted
+ *       sub-stencil polynomials and alpha weights, one normalisation of the weighted sum, reciprocal without the IEEE divide's fix-up,
+ *       advecting transport multiplied by the area after its interpolation): fewer FP64 instructions, fields within 1e-12 of mode 0
+ *       on O(1) data but not bit-identical; the other tendency kernels ignore it
+ *   "role_kchunk" = 0 (step): levels per workgroup of the one-field-per-workgroup kernel, >= 0 (0 = automatic)
+ *   "role_ldspad" = 0 (step): extra dynamic LDS per workgroup of that kernel in bytes (experiments)
+ *   "fused_ty" = 7 (step): tile rows of the all-fields kernel, 3 | 7
+ *   "fused_kchunk" = 0 (step): levels per workgroup of the all-fields kernel, >= 0 (0 = automatic)
+ *   "fused_zwin" = 1 (step): register z-windows in the all-fields kernel
+ *   "fused_xcd" = 0 (step): XCD-aware tile order of the all-fields kernel (measured: no effect)
+ *   "swap_tendencies" = 1 (step): cache_previous_tendencies! by pointer swap (0: by copy kernel)
+ *   "fuse_substep" = 1 (step): the substeps of RK3 stages 2 and 3 fused into the preceding tendency evaluation (second set of
+ *       prognostic arrays, swapped twice per time-step)
+ *   "fused_epilogue" = 1 (step): Coriolis, hydrostatic gradient, closure terms (and the substep) as one launch
+ *   "fused_forcing" = 1 (step): the forcing term in the tendency kernel when it can ride there (0: always the standalone pass)
+ *   "use_graph" = 0 (step): hipGraph replay of the RK3 step (measured: no gain)
+ *   physics passes and halo fills:
+ *   "epilogue_march" = 1 (step): z-marching tendency epilogue that evaluates every face flux once (0: one thread per value,
+ *       everything recomputed -- same bits)
+ *   "epilogue_rows" = 4 (step): rows per workgroup of the marching epilogue, 1 .. 8
+ *   "epilogue_kchunk" = 0 (step): levels per workgroup of the marching epilogue, >= 0 (0 = automatic)
+ *   "amd_march" = 1 (step): z-marching eddy-diffusivity kernel that evaluates every point operand once (0: one thread per cell,
+ *       everything recomputed -- same bits)
+ *   "fused_halo" = 1 (step): one launch per periodic fill
+ *   pressure solve:
+ *   "real_fft" = 1 (step): D2Z / Z2D transforms (0: the reference's complex-to-complex)
+ *   "c2r_strided" = 1 (creation): Z2D straight into the interior of the haloed pressure field
+ *   "fused_zfft" = 1 (creation): z FFT + divide + inverse z FFT as one LDS pass
+ *   "split_solve" = 1 (step): model time-step: 1-D x plans on 128-B-padded rows + LDS column-FFT kernel for y + pressure correction
+ *       and p/Δt from the dense solution (the solver prepares it when the option is on at creation)
+ *   "line_zl512" = 4 (step): lines per workgroup of the LDS line transforms at 512-point lines, 4 | 8
+ *   "skip_stage_pressure" = 1 (step): RK3 stages 1 and 2 do not store their pNHS -- nothing can read it before the next stage
+ *       overwrites it; after a time-step the field holds the last stage's pressure either way
+ *   "skip_dead_tendency_store" = 1 (step): the tendency evaluated after RK3's second stage feeds the third stage's substep riding
+ *       along and is not stored -- nothing else reads it; after a time-step Gⁿ = G(U³) and G⁻ = G(U¹) either way
+ *   x-slab and pencil solves:
+ *   "dist_substructured" = 1 (creation): gathered interface solve (0: the reference's two transposes)
+ *   "dist_zfirst" = 1 (creation): z-fastest local layout
+ *   "dist_xfast" = 1 (creation): the substructured solve in the fields' own x-fastest layout
+ *   "dist_yline" = 1 (creation): LDS column-FFT kernel for the local y transform
+ *   "dist_fuse_source" = 1 (step): source term written straight into the z transform's line buffer
+ *   "dist_xline_group" = 1 (step): several short x lines per wave in the Thomas scans
+ *   "dist_pencil_transposes" = 1 (creation): pencil partitions take the reference's transposing solver (0: gathered solve)
+ *   partitioned step:
+ *   "async_halos" = -1 (partitioned): interior / buffer split of update_state! (-1 automatic, 0 off, 1 on)
+ *   "thin_halos" = 1 (partitioned): the pressure step exchanges the one column that is read instead of Hx columns
+ *   "early_exchange" = 1 (partitioned): update_state!'s exchange starts from make_pressure_correction!
+ *   "strip_width" = 0 (partitioned): columns of the buffer strips (0 = automatic)
+ *   "fused_step" (alias "dist_fused_step") = 1 (partitioned): the pressure step without fills / copies between its stages on
+ *       (connected, Periodic, Periodic) slabs; its buffers are made when a model is created with it, so switching it on later
+ *       needs a model created with it (OCN_ENOTSUP otherwise)
+ * OCN_EINVAL: NULL or unknown key, value out of range. */
 int ocn_set_option(const char *key, int value);
 /* sum of the event-timed tendency evaluations since the last read (ms) and their count; synchronous. This is the
  * measurement hook the reference lacks (it is profiled externally with nsys, .buildkite/pipeline-benchmarks.yml:57) */
@@ -478,8 +515,8 @@ int ocn_dist_allreduce_max(ocn_dist_t dist, double *value);      /* synchronous 
 int ocn_dist_barrier(ocn_dist_t dist);                           /* synchronous */
 /* NonhydrostaticModel on a Distributed architecture: `local_grid` is this rank's slab (x topology OCN_CONNECTED when x is
  * partitioned: distributed_grids.jl:339-346), `Lx_global` the extent of the global domain along x. The returned handle is an
- * ocn_model_t: every ocn_model_* call works on it (set_option also takes "async_halos" -1 automatic / 0 / 1, "thin_halos",
- * "early_exchange", "strip_width"); ocn_model_time_step runs the partitioned RK3 step -- fill_halo_regions! with the x exchange
+ * ocn_model_t: every ocn_model_* call works on it (set_option also takes the partitioned options, ocn_set_option);
+ * ocn_model_time_step runs the partitioned RK3 step -- fill_halo_regions! with the x exchange
  * (halo_communication.jl:87-110), the interior / buffer split (Models/interleave_communication_and_computation.jl:9-67) or the
  * exchange started from make_pressure_correction!, and solve! of the distributed solvers
  * (distributed_fft_based_poisson_solver.jl:141-178, distributed_fft_tridiagonal_solver.jl:153-257) -- entirely inside the library. */

@@ -35,7 +35,9 @@ def synchronize(arch=None):
 
 
 def set_option(key, value):
-    """library-wide tuning knobs (see include/ocn_mi355x.h: ocn_set_option)"""
+    """the library default of a tuning option (include/ocn_mi355x.h: ocn_set_option lists the keys): models created afterwards
+    start from it; grid-level calls (kernels, fill_halo_regions, standalone solvers) read it when they run; models that exist keep
+    their own value (NonhydrostaticModel.set_option)"""
     _lib.check(_lib.lib().ocn_set_option(key.encode(), int(value)))
 
 

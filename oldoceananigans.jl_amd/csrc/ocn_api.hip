@@ -3,6 +3,7 @@
 // one non-blocking HIP stream.
 #include "../../include/ocn_mi355x.h"
 #include "ocn_kernels.h"
+#include "ocn_options.h"
 #include "ocn_tendency_fused.h"
 #include "ocn_tendency_roles.h"
 #include "ocn_epilogue_march.h"
@@ -20,11 +21,14 @@
 // runtime state / error handling
 // ---------------------------------------------------------------------------------------------------------------------
 static thread_local char g_err[512] = "";
-static uint64_t g_epoch = 1;             // bumped by every library-wide option / stream change (invalidates captured time-step graphs)
+static uint64_t g_epoch = 1;             // bumped by every stream change (invalidates captured time-step graphs)
 static hipStream_t g_stream = nullptr;   // may legitimately be the null (legacy default) stream after ocn_set_stream
 static int g_device = -1;
 static bool g_initialized = false;
 static bool g_stream_owned = true;
+// the library defaults of the tuning options (ocn_set_option): grid-level entry points and standalone solvers read them at call time,
+// a model copies them when it is created
+static OcnOptions g_defaults;
 
 static int fail(int code, const char *fmt, ...) {
     va_list ap;
@@ -311,9 +315,7 @@ static int check_range(const DGrid &g, const int *range, Range6 *out, const int 
 // ---------------------------------------------------------------------------------------------------------------------
 // halo fills
 // ---------------------------------------------------------------------------------------------------------------------
-static int g_fused_halo = 1;     // triply periodic grids: the three directional periodic fills as one launch
-
-static int fill_halo_group(const ocn_grid_s *grid, double *const *fields, int n, const int loc[3], bool fill_open,
+static int fill_halo_group(const OcnOptions &o, const ocn_grid_s *grid, double *const *fields, int n, const int loc[3], bool fill_open,
                            const ocn_bc_t (*bcs)[6], bool extend_x = false) {
     if (n <= 0) return OCN_OK;
     const DGrid &g = grid->d;
@@ -325,7 +327,7 @@ static int fill_halo_group(const ocn_grid_s *grid, double *const *fields, int n,
     const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz}, T[3] = {g.tx, g.ty, g.tz};
     FView view = make_view(g, nullptr, loc);
     // (Periodic | FullyConnected, Periodic, Bounded): bounded z fill + periodic y and x fills as one launch
-    if (g_fused_halo && (T[0] == OCN_PERIODIC || T[0] == OCN_CONNECTED) && T[1] == OCN_PERIODIC && T[2] == OCN_BOUNDED &&
+    if (o.fused_halo && (T[0] == OCN_PERIODIC || T[0] == OCN_CONNECTED) && T[1] == OCN_PERIODIC && T[2] == OCN_BOUNDED &&
         (T[0] == OCN_CONNECTED || N[0] >= H[0]) && N[1] >= H[1]) {
         const bool face = loc[2] == OCN_FACE, zfill = !face || fill_open;
         BcSides bc;
@@ -376,7 +378,7 @@ static int fill_halo_group(const ocn_grid_s *grid, double *const *fields, int n,
         }
     }
     // triply periodic with N >= H everywhere: one launch writes every halo cell from its wrapped interior source
-    if (g_fused_halo && T[0] == OCN_PERIODIC && T[1] == OCN_PERIODIC && T[2] == OCN_PERIODIC && N[0] >= H[0] && N[1] >= H[1] && N[2] >= H[2]) {
+    if (o.fused_halo && T[0] == OCN_PERIODIC && T[1] == OCN_PERIODIC && T[2] == OCN_PERIODIC && N[0] >= H[0] && N[1] >= H[1] && N[2] >= H[2]) {
         const long total = (long)P[0] * P[1] * (2 * H[2]) + (long)P[0] * (2 * H[1]) * N[2] + (long)(2 * H[0]) * N[1] * N[2];
         hipLaunchKernelGGL(fill_periodic_xyz_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g_stream, fl, P[0], P[1], P[2], N[0],
                            N[1], N[2], H[0], H[1], H[2]);
@@ -385,7 +387,7 @@ static int fill_halo_group(const ocn_grid_s *grid, double *const *fields, int n,
     }
     // an x-slab rank (x FullyConnected: its x halos come from the neighbours) with periodic y and z: the same kernel with no x slab
     // -- H0 = 0, N0 = P0 makes every i its own source -- fills the y and z halos over the whole x extent in one launch
-    if (g_fused_halo && T[0] == OCN_CONNECTED && T[1] == OCN_PERIODIC && T[2] == OCN_PERIODIC && N[1] >= H[1] && N[2] >= H[2]) {
+    if (o.fused_halo && T[0] == OCN_CONNECTED && T[1] == OCN_PERIODIC && T[2] == OCN_PERIODIC && N[1] >= H[1] && N[2] >= H[2]) {
         const long total = (long)P[0] * P[1] * (2 * H[2]) + (long)P[0] * (2 * H[1]) * N[2];
         hipLaunchKernelGGL(fill_periodic_xyz_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g_stream, fl, P[0], P[1], P[2], P[0],
                            N[1], N[2], 0, H[1], H[2]);
@@ -421,7 +423,7 @@ static int validate_bc(const DGrid &g, const int loc[3], int side, int kind) {
 }
 
 // groups fields by identical location (identical parent shape) -> one set of launches per group
-static int fill_halo_regions(const ocn_grid_s *grid, double *const *fields, const int (*locs)[3], int nfields, bool fill_open,
+static int fill_halo_regions(const OcnOptions &o, const ocn_grid_s *grid, double *const *fields, const int (*locs)[3], int nfields, bool fill_open,
                              const ocn_bc_t (*bcs)[6] = nullptr, bool extend_x = false) {
     const DGrid &g = grid->d;
     if (nfields > OCN_MAX_FIELDS) return fail(OCN_EINVAL, "at most %d fields per call", OCN_MAX_FIELDS);
@@ -447,7 +449,7 @@ static int fill_halo_regions(const ocn_grid_s *grid, double *const *fields, cons
                 done[h] = true;
             }
         }
-        int rc = fill_halo_group(grid, grp, n, locs[f], fill_open, bcs ? gbc : nullptr, extend_x);
+        int rc = fill_halo_group(o, grid, grp, n, locs[f], fill_open, bcs ? gbc : nullptr, extend_x);
         if (rc) return rc;
     }
     return OCN_OK;
@@ -456,7 +458,7 @@ static int fill_halo_regions(const ocn_grid_s *grid, double *const *fields, cons
 extern "C" int ocn_fill_halo_regions(ocn_grid_t grid, double *const *fields, const int (*locs)[3], int nfields, int fill_open_bcs) {
     NEED_INIT();
     if (!grid || !fields || !locs || nfields < 0) return fail(OCN_EINVAL, "invalid argument");
-    return fill_halo_regions(grid, fields, locs, nfields, fill_open_bcs != 0);
+    return fill_halo_regions(g_defaults, grid, fields, locs, nfields, fill_open_bcs != 0);
 }
 
 extern "C" int ocn_fill_halo_regions_bcs(ocn_grid_t grid, double *const *fields, const int (*locs)[3], int nfields,
@@ -469,7 +471,7 @@ extern "C" int ocn_fill_halo_regions_bcs(ocn_grid_t grid, double *const *fields,
                 int rc = validate_bc(grid->d, locs[f], sd, bcs[f][sd].kind);
                 if (rc) return rc;
             }
-    return fill_halo_regions(grid, fields, locs, nfields, fill_open_bcs != 0, bcs);
+    return fill_halo_regions(g_defaults, grid, fields, locs, nfields, fill_open_bcs != 0, bcs);
 }
 
 static int compute_flux_bcs(const DGrid &g, double *G, const int loc[3], const ocn_bc_t bcs[6]) {
@@ -566,29 +568,25 @@ extern "C" int ocn_compute_Gc(ocn_grid_t grid, const double *u, const double *v,
     return launch_tendency<F_C>(grid->d, u, v, w, c, Gc, range);
 }
 
-// tendency implementation of the raw entry points: 0 per-field kernels (the reference's launch structure), 1 all-fields flux-sharing
-// kernel (ocn_tendency_fused.h), 2 one-field-per-workgroup flux-sharing kernel (ocn_tendency_roles.h, default)
-static int g_tendency_impl = 2;
-
-static bool fused_path(const DGrid &g, const int *range, int ntr, int impl) {
+static bool fused_path(const OcnOptions &o, const DGrid &g, const int *range, int ntr, int impl) {
     // the role kernel's limit is on the plane size, the all-fields kernel's on the array (4 GiB): a role launch falls back to the all-fields
     // kernel, and that one to the per-field kernels
     return (impl == 1 || impl == 2) && fused_tendency_supported(g, range) && ntr <= 3 &&
-           ((impl == 2 && role_tendency_supported(g)) || fused_tendency_size_supported(g));
+           ((impl == 2 && role_tendency_supported(o, g)) || fused_tendency_size_supported(g));
 }
 
-static int compute_tendencies(const DGrid &g, const double *u, const double *v, const double *w, const double *const *tr,
+static int compute_tendencies(const OcnOptions &o, const DGrid &g, const double *u, const double *v, const double *w, const double *const *tr,
                               int ntr, double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range, int impl,
                               const FusedSubstep *sub = nullptr, const ForcingTable *ftab = nullptr) {
-    if (sub && !fused_path(g, range, ntr, impl)) return fail(OCN_ESTATE, "fused substep requested on the per-field tendency path");
-    if (ftab && !(impl == 2 && fused_path(g, range, ntr, impl) && role_tendency_supported(g)))
+    if (sub && !fused_path(o, g, range, ntr, impl)) return fail(OCN_ESTATE, "fused substep requested on the per-field tendency path");
+    if (ftab && !(impl == 2 && fused_path(o, g, range, ntr, impl) && role_tendency_supported(o, g)))
         return fail(OCN_ESTATE, "forcing term requested in a tendency launch other than the role kernel");
-    if (fused_path(g, range, ntr, impl)) {
+    if (fused_path(o, g, range, ntr, impl)) {
         int rc = check_range(g, range, nullptr);
         if (rc) return rc;
-        if (impl == 2 && !role_tendency_supported(g)) impl = 1;          // planes too large for the role kernel's offsets: the all-fields kernel
-        rc = impl == 2 ? launch_role_tendency(g, g_stream, u, v, w, tr, ntr, Gu, Gv, Gw, Gc, range, sub, ftab)
-                       : launch_fused_tendency(g, g_stream, u, v, w, tr, ntr, Gu, Gv, Gw, Gc, range, sub);
+        if (impl == 2 && !role_tendency_supported(o, g)) impl = 1;          // planes too large for the role kernel's offsets: the all-fields kernel
+        rc = impl == 2 ? launch_role_tendency(o, g, g_stream, u, v, w, tr, ntr, Gu, Gv, Gw, Gc, range, sub, ftab)
+                       : launch_fused_tendency(o, g, g_stream, u, v, w, tr, ntr, Gu, Gv, Gw, Gc, range, sub);
         if (rc) return fail(rc, "fused tendency launch failed");
         KERNEL_CHECK();
         return OCN_OK;
@@ -610,7 +608,8 @@ extern "C" int ocn_compute_tendencies(ocn_grid_t grid, const double *u, const do
         (ntracers > 0 && (!tracers || !Gc)))
         return fail(OCN_EINVAL, "invalid argument");
     if (!grid->advection_error.empty()) return fail(OCN_EINVAL, "%s", grid->advection_error.c_str());
-    int rc = compute_tendencies(grid->d, u, v, w, tracers, ntracers, Gu, Gv, Gw, Gc, range, g_tendency_impl ? g_tendency_impl : 1);
+    // (the raw entry points map tendency_impl 0 to the all-fields kernel)
+    int rc = compute_tendencies(g_defaults, grid->d, u, v, w, tracers, ntracers, Gu, Gv, Gw, Gc, range, g_defaults.tendency_impl ? g_defaults.tendency_impl : 1);
     if (rc) return rc;
     KERNEL_CHECK();
     return OCN_OK;
@@ -724,11 +723,7 @@ extern "C" int ocn_compute_closure_tendencies_field(ocn_grid_t grid, const doubl
     return closure_tendencies(grid->d, u, v, w, tracers, ntracers, 0.0, nullptr, Gu, Gv, Gw, Gc, range, nu_e, kappa_e);
 }
 
-static int g_epilogue_march = 1;       // closure / Coriolis / pHY′ epilogue as a z-march that shares the symmetric flux tensor (0: one thread per field value)
-static int g_epilogue_rows = 4;        // rows (waves) per block of that kernel
-static int g_epilogue_kchunk = 0;      // levels per block of that kernel (0: automatic)
-static int g_amd_march = 1;            // eddy diffusivities by the z-marching kernel that shares the point operands (0: one thread per cell, everything recomputed)
-static int amd_diffusivities(const DGrid &g, double Cnu, const double *Ckappa, const double *u, const double *v, const double *w,
+static int amd_diffusivities(const OcnOptions &o, const DGrid &g, double Cnu, const double *Ckappa, const double *u, const double *v, const double *w,
                              const double *const *tr, int ntr, double *nu_e, double *const *kappa_e, const int *range = nullptr) {
     if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT)
         return fail(OCN_ENOTSUP, "AnisotropicMinimumDissipation needs a grid without Flat directions");
@@ -752,7 +747,7 @@ static int amd_diffusivities(const DGrid &g, double Cnu, const double *Ckappa, c
         a.kappa_e[t] = make_view(g, kappa_e[t], LOC_C);
         a.Ck[t] = Ckappa[t];
     }
-    if (g_amd_march && ntr <= 3) {
+    if (o.amd_march && ntr <= 3) {
         // z-marching kernel (ocn_kernels.h): 63 columns per wave, 4 rows per block, chunks of levels so that ~2000 blocks fill the chip
         const int bx = (nx + 62) / 63, by = (ny + 3) / 4;
         const int want = std::max(1, 2048 / std::max(1, bx * by));
@@ -776,7 +771,7 @@ extern "C" int ocn_compute_amd_diffusivities(ocn_grid_t grid, double Cnu, const 
     NEED_INIT();
     if (!grid || !u || !v || !w || !nu_e || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 || (ntracers > 0 && (!tracers || !kappa_e || !Ckappa)))
         return fail(OCN_EINVAL, "invalid argument");
-    return amd_diffusivities(grid->d, Cnu, Ckappa, u, v, w, tracers, ntracers, nu_e, kappa_e, range);
+    return amd_diffusivities(g_defaults, grid->d, Cnu, Ckappa, u, v, w, tracers, ntracers, nu_e, kappa_e, range);
 }
 
 extern "C" int ocn_compute_tendencies_and_substep(ocn_grid_t grid, const double *const *fields, int ntracers, double *const *Gn,
@@ -787,11 +782,11 @@ extern "C" int ocn_compute_tendencies_and_substep(ocn_grid_t grid, const double 
     for (int f = 0; f < 3 + ntracers; ++f)
         if (!fields[f] || !Gn[f] || !next[f] || (has_zeta && !Gm[f])) return fail(OCN_EINVAL, "NULL field pointer");
     if (!grid->advection_error.empty()) return fail(OCN_EINVAL, "%s", grid->advection_error.c_str());
-    const int impl = g_tendency_impl ? g_tendency_impl : 1;
-    if (!fused_path(grid->d, range, ntracers, impl))
+    const int impl = g_defaults.tendency_impl ? g_defaults.tendency_impl : 1;
+    if (!fused_path(g_defaults, grid->d, range, ntracers, impl))
         return fail(OCN_ENOTSUP, "the fused tendency + substep pass needs Periodic / FullyConnected x and y");
     const FusedSubstep sub{next, has_zeta ? Gm : Gn, dt, gamma, zeta, has_zeta ? 1 : 0};
-    return compute_tendencies(grid->d, fields[0], fields[1], fields[2], fields + 3, ntracers, Gn[0], Gn[1], Gn[2], Gn + 3, range, impl, &sub);
+    return compute_tendencies(g_defaults, grid->d, fields[0], fields[1], fields[2], fields + 3, ntracers, Gn[0], Gn[1], Gn[2], Gn + 3, range, impl, &sub);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -942,18 +937,17 @@ extern "C" int ocn_divide_interior(ocn_grid_t grid, double *p, double divisor) {
 #ifndef OCN_LINE_MAX
 #define OCN_LINE_MAX 1024
 #endif
-static int g_line_zl512 = 4;            // lines per workgroup of the LDS line-FFT kernels at 512-point lines (8: 64 KB of LDS per workgroup)
-static inline int line_zl(int n) { return n >= 1024 ? 4 : (n >= 512 ? g_line_zl512 : 8); }
-static inline void launch_strided_line_fft(double2 *data, const double2 *tw, long C, long ncols, unsigned batches, int N, int logn, int inverse,
+static inline int line_zl(const OcnOptions &o, int n) { return n >= 1024 ? 4 : (n >= 512 ? o.line_zl512 : 8); }
+static inline void launch_strided_line_fft(const OcnOptions &o, double2 *data, const double2 *tw, long C, long ncols, unsigned batches, int N, int logn, int inverse,
                                            double scale, long plane_stride = 0) {
-    const int zl = line_zl(N);
+    const int zl = line_zl(o, N);
     const dim3 grd((unsigned)((ncols + zl - 1) / zl), batches);
     const size_t lds = (size_t)N * zl * sizeof(double2);
     if (zl == 4) hipLaunchKernelGGL(strided_line_fft_kernel<4>, grd, dim3(256), lds, g_stream, data, tw, C, N, logn, inverse, scale, plane_stride);
     else         hipLaunchKernelGGL(strided_line_fft_kernel<8>, grd, dim3(256), lds, g_stream, data, tw, C, N, logn, inverse, scale, plane_stride);
 }
-static inline void launch_paired_zline(bool forward, const double2 *in, double2 *out, const double2 *tw, long C, int N, int logn, double scale) {
-    const int zl = line_zl(N);
+static inline void launch_paired_zline(const OcnOptions &o, bool forward, const double2 *in, double2 *out, const double2 *tw, long C, int N, int logn, double scale) {
+    const int zl = line_zl(o, N);
     const dim3 grd((unsigned)((C + zl - 1) / zl));
     const size_t lds = (size_t)N * zl * sizeof(double2);
     if (forward) {
@@ -964,12 +958,11 @@ static inline void launch_paired_zline(bool forward, const double2 *in, double2 
         else         hipLaunchKernelGGL(paired_zline_c2r_kernel<8>, grd, dim3(256), lds, g_stream, in, out, tw, C, N, logn, scale);
     }
 }
-static int g_dist_xline_group = 1;     // x-fastest solve on short local lines (32 / 64 / 128 points): several lines per wave instead of one
 template <bool SOLVE>
-static inline void launch_xline_thomas(int E, double2 *S, const double *rden, long M, int N, double a, double2 *payload, const double2 *iface, double scale) {
+static inline void launch_xline_thomas(const OcnOptions &o, int E, double2 *S, const double *rden, long M, int N, double a, double2 *payload, const double2 *iface, double scale) {
     const dim3 blk(256);
     // short lines (thin slabs): 4 elements per lane and N / 4 lanes per line -- 2, 4 or 8 lines per wave
-    if (g_dist_xline_group && (N == 32 || N == 64 || N == 128)) {
+    if (o.dist_xline_group && (N == 32 || N == 64 || N == 128)) {
         const int lpw = 256 / N;
         const dim3 grp((unsigned)((M + 4 * lpw - 1) / (4 * lpw)));
         if (N == 32)       hipLaunchKernelGGL((xline_thomas_kernel<4, SOLVE, 8>), grp, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale);
@@ -986,29 +979,17 @@ static inline void launch_xline_thomas(int E, double2 *S, const double *rden, lo
         default: hipLaunchKernelGGL((xline_thomas_kernel<16, SOLVE>), grd, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale); break;
     }
 }
-static inline void launch_zline_solve(double2 *hc, const double2 *tw, const double *lx, const double *ly, const double *lz, int Nxs, int Ny, int Nz,
+static inline void launch_zline_solve(const OcnOptions &o, double2 *hc, const double2 *tw, const double *lx, const double *ly, const double *lz, int Nxs, int Ny, int Nz,
                                       int logn, double scale, int pitch = 0) {
-    const int zl = line_zl(Nz);
+    const int zl = line_zl(o, Nz);
     const dim3 grd((unsigned)((Nxs + zl - 1) / zl), (unsigned)Ny);
     const size_t lds = (size_t)Nz * zl * sizeof(double2);
     if (zl == 4) hipLaunchKernelGGL(zline_solve_kernel<4>, grd, dim3(256), lds, g_stream, hc, tw, lx, ly, lz, Nxs, Ny, Nz, logn, scale, pitch);
     else         hipLaunchKernelGGL(zline_solve_kernel<8>, grd, dim3(256), lds, g_stream, hc, tw, lx, ly, lz, Nxs, Ny, Nz, logn, scale, pitch);
 }
-static int g_real_fft = 1, g_c2r_strided = 1;
-static int g_fused_zfft = 1;
-static int g_skip_dead_tendency_store = 1;   // the tendency evaluated after RK3's second stage is not stored (FusedSubstep::store_G)
-static int g_skip_stage_pressure = 1;   // RK3 stages 1, 2: pNHS of the stage is not stored (overwritten by the next stage before anything can read it)
-static int g_split_solve = 1;            // model time-step: split (x, y) transforms + pressure correction from the dense solution (see ocn_poisson_s::split)
-static int g_dist_substructured = 1;   // distributed FFT solver (z Periodic): substructured x solve + one small all-gather instead of two all-to-alls    // FFT solver, z Periodic, Nz = 2^m <= 1024: z transform + divide + inverse z transform in one pass
-static int g_dist_fuse_source = 1;     // x-fastest solve: source term and paired z transform in one kernel (no dense real right-hand side)
-static int g_dist_xfast = 1;           // substructured x solve in the fields' own x-fastest layout (paired z transform in LDS, one-wave-per-line Thomas scans) when sizes allow
-static int g_dist_pencil_transposes = 1;   // pencil partitions of triply Periodic grids: the reference's transposing solver (0: gathered solve)
-static int g_dist_fused_step = 1;      // partitioned model, (connected, Periodic, Periodic) slabs: the pressure step without fills / copies between its stages (ocn_dist.h)
-static int g_dist_yline = 1;           // z Bounded: local y transform by strided_line_fft_kernel (Ny = 2^m <= 1024) instead of rocFFT's 1-D strided plan
-static int g_dist_zfirst = 1;          // substructured solve on the z-fastest layout (R2C along z); 0: paired-column layout
-
 struct ocn_poisson_s {
     ocn_grid_t grid;
+    const OcnOptions *opt = nullptr;        // the owning model's options (standalone solvers: the library defaults)
     int kind;
     size_t n;                   // Nx*Ny*Nz
     double2 *storage = nullptr; // kind 0: rhs + solution; kind 1: solution
@@ -1252,7 +1233,7 @@ static int transform_all(ocn_poisson_s *s, double2 *A, bool forward) {
     return OCN_OK;
 }
 
-extern "C" int ocn_poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int kind) {
+static int poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int kind, const OcnOptions *opt) {
     NEED_INIT();
     if (!solver || !grid) return fail(OCN_EINVAL, "NULL argument");
     const DGrid &g = grid->d;
@@ -1265,7 +1246,7 @@ extern "C" int ocn_poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int ki
         return fail(OCN_EINVAL, "`FourierTridiagonalPoissonSolver` can only be used when the stretched direction's topology is `Bounded`.");
     if (kind != 0 && kind != 1) return fail(OCN_EINVAL, "unknown solver kind %d", kind);
     ocn_poisson_s *s = new ocn_poisson_s();
-    s->grid = grid; s->kind = kind;
+    s->grid = grid; s->opt = opt; s->kind = kind;
     s->n = (size_t)g.Nx * g.Ny * g.Nz;
     s->general = g.tx == OCN_BOUNDED || g.ty == OCN_BOUNDED || (kind == 0 && g.tz == OCN_BOUNDED) ||
                  g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT;      // Flat directions are not transformed
@@ -1325,7 +1306,7 @@ extern "C" int ocn_poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int ki
             TRY_OR_FREE(hipMemset(s->hc2, 0, s->nh * sizeof(double2)));
         }
         const int Px = g.Nx + 2 * g.Hx, Py = g.Ny + 2 * g.Hy, Pz = g.Nz + 2 * g.Hz;
-        if (kind == 0 && g_fused_zfft && g.Nz >= 8 && g.Nz <= OCN_LINE_MAX && (g.Nz & (g.Nz - 1)) == 0) {
+        if (kind == 0 && opt->fused_zfft && g.Nz >= 8 && g.Nz <= OCN_LINE_MAX && (g.Nz & (g.Nz - 1)) == 0) {
             s->zfused = true;
             while ((1 << s->logn_z) < g.Nz) ++s->logn_z;
             std::vector<double2> tw(g.Nz / 2);
@@ -1342,8 +1323,8 @@ extern "C" int ocn_poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int ki
             if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(D2Z 3-D) failed (%d)", (int)r); goto bad; }
             s->has_r2c = true;
             int inembed[3] = {g.Nz, g.Ny, s->Nxh}, onembed[3] = {Pz, Py, Px};
-            r = g_c2r_strided ? hipfftPlanMany(&s->plan_c2r, 3, n3, inembed, 1, (int)s->nh, onembed, 1, Px * Py * Pz, HIPFFT_Z2D, 1) : HIPFFT_NOT_SUPPORTED;
-            s->c2r_strided = r == HIPFFT_SUCCESS && g_c2r_strided;
+            r = opt->c2r_strided ? hipfftPlanMany(&s->plan_c2r, 3, n3, inembed, 1, (int)s->nh, onembed, 1, Px * Py * Pz, HIPFFT_Z2D, 1) : HIPFFT_NOT_SUPPORTED;
+            s->c2r_strided = r == HIPFFT_SUCCESS && opt->c2r_strided;
             if (!s->c2r_strided) r = hipfftPlanMany(&s->plan_c2r, 3, n3, nullptr, 1, 0, nullptr, 1, 0, HIPFFT_Z2D, 1);
             if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(Z2D 3-D) failed (%d)", (int)r); goto bad; }
             s->has_c2r = true;
@@ -1353,7 +1334,7 @@ extern "C" int ocn_poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int ki
             r = hipfftPlanMany(&s->plan_r2c, 2, n2, rin, 1, g.Nx * g.Ny, cemb, 1, s->Nxh * g.Ny, HIPFFT_D2Z, g.Nz);
             if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(D2Z 2-D) failed (%d)", (int)r); goto bad; }
             s->has_r2c = true;
-            r = g_c2r_strided ? hipfftPlanMany(&s->plan_c2r, 2, n2, cemb, 1, s->Nxh * g.Ny, pemb, 1, Px * Py, HIPFFT_Z2D, g.Nz) : HIPFFT_NOT_SUPPORTED;
+            r = opt->c2r_strided ? hipfftPlanMany(&s->plan_c2r, 2, n2, cemb, 1, s->Nxh * g.Ny, pemb, 1, Px * Py, HIPFFT_Z2D, g.Nz) : HIPFFT_NOT_SUPPORTED;
             s->c2r_strided = r == HIPFFT_SUCCESS;
             if (!s->c2r_strided) r = hipfftPlanMany(&s->plan_c2r, 2, n2, cemb, 1, s->Nxh * g.Ny, rin, 1, g.Nx * g.Ny, HIPFFT_Z2D, g.Nz);
             if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(Z2D 2-D) failed (%d)", (int)r); goto bad; }
@@ -1371,7 +1352,7 @@ extern "C" int ocn_poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int ki
             *solver = s;
             return OCN_OK;
         }
-        if (g_split_solve && (kind == 1 || s->zfused) && g.Ny >= 8 && g.Ny <= OCN_LINE_MAX && (g.Ny & (g.Ny - 1)) == 0 && g.tx == OCN_PERIODIC &&
+        if (opt->split_solve && (kind == 1 || s->zfused) && g.Ny >= 8 && g.Ny <= OCN_LINE_MAX && (g.Ny & (g.Ny - 1)) == 0 && g.tx == OCN_PERIODIC &&
             g.ty == OCN_PERIODIC) {
             int nx1[1] = {g.Nx};
             int rembx[1] = {g.Nx}, cembx[1] = {s->Nxp};
@@ -1398,11 +1379,11 @@ extern "C" int ocn_poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int ki
                     hipLaunchKernelGGL(selfcheck_fill_real, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, s->rrhs, n);
                     ok = hipfftExecD2Z(s->plan_r2c, s->rrhs, (hipfftDoubleComplex *)ref) == HIPFFT_SUCCESS &&
                          hipfftExecD2Z(s->plan_xr2c, s->rrhs, (hipfftDoubleComplex *)s->hc) == HIPFFT_SUCCESS;
-                    launch_strided_line_fft(s->hc, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 0, 1.0, (long)s->Nxp * g.Ny);
+                    launch_strided_line_fft(*s->opt, s->hc, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 0, 1.0, (long)s->Nxp * g.Ny);
                     hipLaunchKernelGGL(max_abs_diff_pitched_kernel, dim3(256), dim3(256), 0, g_stream, (const double2 *)ref, s->Nxh,
                                        (const double2 *)s->hc, s->Nxp, s->Nxh, (long)g.Ny * g.Nz, bm);
                     ok = ok && reduce_blockmax(bm, 256, &e_fwd) == OCN_OK;
-                    launch_strided_line_fft(s->hc, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 1, 1.0, (long)s->Nxp * g.Ny);
+                    launch_strided_line_fft(*s->opt, s->hc, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 1, 1.0, (long)s->Nxp * g.Ny);
                     ok = ok && hipfftExecZ2D(s->plan_xc2r, (hipfftDoubleComplex *)s->hc, s->rrhs) == HIPFFT_SUCCESS;
                     hipLaunchKernelGGL(selfcheck_compare_real, dim3(256), dim3(256), 0, g_stream, s->rrhs, g.Nx, g.Ny, g.Nz, g.Nx, g.Ny, 0, 0, 0,
                                        1.0 / ((double)g.Nx * g.Ny), bm);
@@ -1422,6 +1403,7 @@ bad:
     return rc;
 #undef TRY_OR_FREE
 }
+extern "C" int ocn_poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int kind) { return poisson_create(solver, grid, kind, &g_defaults); }
 
 extern "C" int ocn_poisson_kind(ocn_poisson_t s) { return s ? s->kind : OCN_EINVAL; }
 
@@ -1502,7 +1484,7 @@ static int poisson_solve_real(ocn_poisson_s *s, double *phi) {
     double2 *sol = s->hc;
     if (s->kind == 0 && s->zfused) {
         const double scale = 1.0 / ((double)g.Nx * (double)g.Ny * (double)g.Nz);
-        launch_zline_solve(s->hc, s->ztw, s->lam[0], s->lam[1], s->lam[2], s->Nxh, g.Ny, g.Nz, s->logn_z, scale);
+        launch_zline_solve(*s->opt, s->hc, s->ztw, s->lam[0], s->lam[1], s->lam[2], s->Nxh, g.Ny, g.Nz, s->logn_z, scale);
     } else if (s->kind == 0) {
         const double scale = 1.0 / ((double)g.Nx * (double)g.Ny * (double)g.Nz);
         hipLaunchKernelGGL(spectral_divide_kernel, grid3(s->Nxh, g.Ny, g.Nz, BLK), BLK, 0, g_stream, s->hc, s->lam[0], s->lam[1],
@@ -1532,11 +1514,11 @@ static int poisson_solve_real_split(ocn_poisson_s *s) {
     { int rc_; if ((rc_ = plan_set_stream(s->plan_xr2c)) || (rc_ = plan_set_stream(s->plan_xc2r))) return rc_; }
     // rows of pitch Nxp: whole, 128-B aligned groups of lines
     FFT_TRY(hipfftExecD2Z(s->plan_xr2c, s->rrhs, (hipfftDoubleComplex *)s->hc));
-    launch_strided_line_fft(s->hc, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 0, 1.0, (long)s->Nxp * g.Ny);
+    launch_strided_line_fft(*s->opt, s->hc, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 0, 1.0, (long)s->Nxp * g.Ny);
     double2 *sol = s->hc;
     if (s->kind == 0) {
         const double scale = 1.0 / ((double)g.Nx * (double)g.Ny * (double)g.Nz);
-        launch_zline_solve(s->hc, s->ztw, s->lam[0], s->lam[1], s->lam[2], s->Nxh, g.Ny, g.Nz, s->logn_z, scale, s->Nxp);
+        launch_zline_solve(*s->opt, s->hc, s->ztw, s->lam[0], s->lam[1], s->lam[2], s->Nxh, g.Ny, g.Nz, s->logn_z, scale, s->Nxp);
     } else {
         const double scale = 1.0 / ((double)g.Nx * (double)g.Ny);
         hipLaunchKernelGGL(tridiagonal_z_kernel, dim3((s->Nxh + 63) / 64, g.Ny), dim3(64), 0, g_stream, s->Nxh, g.Nx, g.Ny, g.Nz,
@@ -1544,7 +1526,7 @@ static int poisson_solve_real_split(ocn_poisson_s *s) {
         hipLaunchKernelGGL(remove_mean_mode_kernel, dim3(1), dim3(256), 0, g_stream, s->hc2, (long)s->Nxp * g.Ny, g.Nz);
         sol = s->hc2;
     }
-    launch_strided_line_fft(sol, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 1, 1.0, (long)s->Nxp * g.Ny);
+    launch_strided_line_fft(*s->opt, sol, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 1, 1.0, (long)s->Nxp * g.Ny);
     FFT_TRY(hipfftExecZ2D(s->plan_xc2r, (hipfftDoubleComplex *)sol, s->rrhs));
     KERNEL_CHECK();
     return OCN_OK;
@@ -1553,7 +1535,7 @@ static int poisson_solve_real_split(ocn_poisson_s *s) {
 static int solve_for_pressure(ocn_poisson_s *s, const double *u, const double *v, const double *w, double *p) {
     const DGrid &g = s->grid->d;
     int rc;
-    if (g_real_fft && !s->general) {
+    if (s->opt->real_fft && !s->general) {
         if ((rc = source_term(g, u, v, w, s->rrhs, s->kind == 1, true))) return rc;
         return poisson_solve_real(s, p);
     }
@@ -1661,6 +1643,7 @@ extern "C" int ocn_unpack_x_halos_depth(ocn_grid_t grid, double *const *fields, 
 //   -> inverse x transform -> pack -> all-to-all -> rebuild full spectrum -> inverse local transform -> haloed pressure.
 struct ocn_dist_poisson_s {
     ocn_grid_t grid;            // LOCAL grid (Nxl, Ny, Nz)
+    const OcnOptions *opt = nullptr;        // the owning model's options (standalone solvers: the library defaults)
     int R, rank, zmode;         // zmode 0: z Periodic (FFT); 1: z Bounded (tridiagonal solve in the x-local layout)
     int Nxl, Nxe, Nxh, Nxg, Ny, Nyh, Nyc, Nyp, Nz;
     size_t nz_c;                // complex elements of the local paired array  Nxh*Ny*Nz
@@ -1720,7 +1703,7 @@ extern "C" int ocn_dist_poisson_destroy(ocn_dist_poisson_t s) {
     return OCN_OK;
 }
 
-extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t local_grid, int R, int rank, double Lx_global) {
+static int dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t local_grid, int R, int rank, double Lx_global, const OcnOptions *opt) {
     NEED_INIT();
     if (!solver || !local_grid) return fail(OCN_EINVAL, "NULL argument");
     const DGrid &g = local_grid->d;
@@ -1733,7 +1716,7 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
     const int zmode = g.tz == OCN_BOUNDED ? 1 : 0;
     if (zmode == 0 && !local_grid->z_regular) return fail(OCN_EINVAL, "DistributedFFTBasedPoissonSolver requires a regular grid");
     ocn_dist_poisson_s *s = new ocn_dist_poisson_s();
-    s->grid = local_grid; s->R = R; s->rank = rank; s->zmode = zmode;
+    s->grid = local_grid; s->opt = opt; s->R = R; s->rank = rank; s->zmode = zmode;
     s->Nxl = g.Nx; s->Nxe = g.Nx + (g.Nx & 1); s->Nxh = s->Nxe / 2; s->Nxg = g.Nx * R;
     s->Ny = g.Ny; s->Nyh = g.Ny / 2 + 1; s->Nyc = (s->Nyh + R - 1) / R; s->Nyp = s->Nyc * R; s->Nz = g.Nz;
     s->nz_c = (size_t)s->Nxh * s->Ny * s->Nz;
@@ -1796,7 +1779,7 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
         if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(local y/z) failed (%d)", (int)r); goto bad; }
         s->has_loc = true;
         auto pow2_line = [](int n) { return n >= 8 && n <= OCN_LINE_MAX && (n & (n - 1)) == 0; };
-        if (zmode == 0 && g_dist_substructured && g_dist_xfast && (s->Nxl % 2) == 0 && s->Nxl <= 1024 && pow2_line(s->Ny) && pow2_line(s->Nz)) {
+        if (zmode == 0 && opt->dist_substructured && opt->dist_xfast && (s->Nxl % 2) == 0 && s->Nxl <= 1024 && pow2_line(s->Ny) && pow2_line(s->Nz)) {
             // ---- x-fastest variant (ocn_kernels.h "xfast") ----
             s->sub = true; s->xfast = true;
             s->Nzh = s->Nz / 2 + 1;
@@ -1836,9 +1819,9 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
                 double *bm = nullptr;
                 TRY_OR_FREE(dev_alloc((void **)&bm, 2 * sizeof(double)));
                 hipLaunchKernelGGL(xfast_kat_fill_kernel, dim3((unsigned)((nreal / 2 + 255) / 256)), dim3(256), 0, g_stream, (double2 *)s->rx, C, s->Nz);
-                launch_paired_zline(true, (const double2 *)s->rx, s->xs, s->ztw, C, s->Nz, s->logn_z, 1.0);
+                launch_paired_zline(*s->opt, true, (const double2 *)s->rx, s->xs, s->ztw, C, s->Nz, s->logn_z, 1.0);
                 hipLaunchKernelGGL(xfast_kat_check_kernel, dim3(1), dim3(256), 0, g_stream, (const double2 *)s->xs, C, s->Nz, bm);
-                launch_paired_zline(false, s->xs, (double2 *)s->rx, s->ztw, C, s->Nz, s->logn_z, 1.0 / (double)s->Nz);
+                launch_paired_zline(*s->opt, false, s->xs, (double2 *)s->rx, s->ztw, C, s->Nz, s->logn_z, 1.0 / (double)s->Nz);
                 hipLaunchKernelGGL(xfast_kat_check_real_kernel, dim3(1), dim3(256), 0, g_stream, (const double2 *)s->rx, C, s->Nz, bm + 1);
                 double err[2] = {1.0, 1.0};
                 hipError_t e_ = hipMemcpyAsync(err, bm, sizeof(err), hipMemcpyDeviceToHost, g_stream);
@@ -1850,7 +1833,7 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
                     goto bad;
                 }
             }
-        } else if (zmode == 0 && g_dist_substructured && g_dist_zfirst) {
+        } else if (zmode == 0 && opt->dist_substructured && opt->dist_zfirst) {
             s->sub = true; s->zfirst = true;
             s->Nzh = s->Nz / 2 + 1;
             s->Nzp = (s->Nzh + 7) & ~7;
@@ -1876,7 +1859,7 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
             int remb[2] = {s->Ny, s->Nz * s->Nxl}, cemb[2] = {s->Ny, s->Nzp * s->Nxl};
             // ... unless Ny = 2^m <= 1024: then the y pass is strided_line_fft_kernel (3x faster again than the column kernel of the 2-D
             // plan) next to plain 1-D plans along z
-            const bool want_yline = g_dist_yline && s->Ny >= 8 && s->Ny <= OCN_LINE_MAX && (s->Ny & (s->Ny - 1)) == 0;
+            const bool want_yline = opt->dist_yline && s->Ny >= 8 && s->Ny <= OCN_LINE_MAX && (s->Ny & (s->Ny - 1)) == 0;
             hipfftResult rz = want_yline ? HIPFFT_NOT_SUPPORTED
                                          : hipfftPlanMany(&s->plan_zr2c, 2, nyz, remb, 1, s->Nz, cemb, 1, s->Nzp, HIPFFT_D2Z, s->Nxl);
             if (rz == HIPFFT_SUCCESS) {
@@ -1915,7 +1898,7 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
                         hipLaunchKernelGGL(selfcheck_fill_complex, dim3((unsigned)((pslab + 255) / 256)), dim3(256), 0, g_stream, s->spec, (long)pslab);
                         ok = hipMemcpyAsync(ref, s->spec, pslab * sizeof(double2), hipMemcpyDeviceToDevice, g_stream) == hipSuccess &&
                              hipfftExecZ2Z(s->plan_y, (hipfftDoubleComplex *)ref, (hipfftDoubleComplex *)ref, dir ? HIPFFT_BACKWARD : HIPFFT_FORWARD) == HIPFFT_SUCCESS;
-                        launch_strided_line_fft(s->spec, s->ytw, C, C, 1, s->Ny, s->logn_y, dir, 1.0);
+                        launch_strided_line_fft(*s->opt, s->spec, s->ytw, C, C, 1, s->Ny, s->logn_y, dir, 1.0);
                         hipLaunchKernelGGL(max_abs_diff_kernel, dim3(256), dim3(256), 0, g_stream, (const double *)ref, (const double *)s->spec,
                                            2 * (long)pslab, bm);
                         ok = ok && reduce_blockmax(bm, 256, &err[dir]) == OCN_OK;
@@ -1977,7 +1960,7 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
                 if (rc) goto bad;
                 if (!(err < 1e-10)) { rc = fail(OCN_EFFT, "rocFFT self-check failed for the (y, z) real transform pair (round-trip error %.3g)", err); goto bad; }
             }
-        } else if (zmode == 0 && g_dist_substructured) {
+        } else if (zmode == 0 && opt->dist_substructured) {
             s->sub = true;
             s->M = (long)s->Nyh * s->Nz;
             const size_t slab = (size_t)s->M * s->Nxl;
@@ -1991,7 +1974,7 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
                                s->lam[1], s->lam[2], s->rden, s->cpf, s->svec, (double *)(s->iface + 2 * s->M + 1));
             TRY_OR_FREE(hipGetLastError());
         }
-        if (!s->sub && zmode == 0 && g_fused_zfft && s->Nxg >= 8 && s->Nxg <= 4096 && (s->Nxg & (s->Nxg - 1)) == 0) {
+        if (!s->sub && zmode == 0 && opt->fused_zfft && s->Nxg >= 8 && s->Nxg <= 4096 && (s->Nxg & (s->Nxg - 1)) == 0) {
             s->xfused = true;
             while ((1 << s->logn_x) < s->Nxg) ++s->logn_x;
             s->xlines = std::max(1, 4096 / s->Nxg);           // 64 KB of LDS per workgroup
@@ -2006,7 +1989,7 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
         if ((rc = plan_set_stream(s->plan_loc))) goto bad;
         const double sc = zmode == 0 ? 1.0 / ((double)s->Ny * s->Nz) : 1.0 / (double)s->Ny;
         if ((rc = verify_complex_plan(s->plan_loc, s->zfield, (long)s->nz_c, sc, "distributed local (y, z)"))) goto bad;
-        if (zmode == 1 && g_dist_yline && s->Ny >= 8 && s->Ny <= OCN_LINE_MAX && (s->Ny & (s->Ny - 1)) == 0) {
+        if (zmode == 1 && opt->dist_yline && s->Ny >= 8 && s->Ny <= OCN_LINE_MAX && (s->Ny & (s->Ny - 1)) == 0) {
             while ((1 << s->logn_y) < s->Ny) ++s->logn_y;
             std::vector<double2> tw(s->Ny / 2);
             for (int m = 0; m < s->Ny / 2; ++m) {
@@ -2027,7 +2010,7 @@ extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t lo
                 hipLaunchKernelGGL(selfcheck_fill_complex, dim3((unsigned)((s->nz_c + 255) / 256)), dim3(256), 0, g_stream, s->zfield, (long)s->nz_c);
                 ok = hipMemcpyAsync(ref, s->zfield, s->nz_c * sizeof(double2), hipMemcpyDeviceToDevice, g_stream) == hipSuccess &&
                      hipfftExecZ2Z(s->plan_loc, (hipfftDoubleComplex *)ref, (hipfftDoubleComplex *)ref, dir ? HIPFFT_BACKWARD : HIPFFT_FORWARD) == HIPFFT_SUCCESS;
-                launch_strided_line_fft(s->zfield, s->ytw, C, C, 1, s->Ny, s->logn_y, dir, 1.0);
+                launch_strided_line_fft(*s->opt, s->zfield, s->ytw, C, C, 1, s->Ny, s->logn_y, dir, 1.0);
                 hipLaunchKernelGGL(max_abs_diff_kernel, dim3(256), dim3(256), 0, g_stream, (const double *)ref, (const double *)s->zfield,
                                    2 * (long)s->nz_c, bm);
                 ok = ok && reduce_blockmax(bm, 256, &err[dir]) == OCN_OK;
@@ -2051,6 +2034,9 @@ bad:
     ocn_dist_poisson_destroy(s);
     return rc;
 #undef TRY_OR_FREE
+}
+extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t local_grid, int R, int rank, double Lx_global) {
+    return dist_poisson_create(solver, local_grid, R, rank, Lx_global, &g_defaults);
 }
 
 extern "C" int ocn_dist_poisson_buffer_size(ocn_dist_poisson_t s, size_t *complex_elements) {
@@ -2090,10 +2076,10 @@ extern "C" int ocn_dist_poisson_forward_local(ocn_dist_poisson_t s) {
     const double a = 1.0 / (s->grid->d.dx * s->grid->d.dx);
     if (s->xfast) {
         const long C = (long)s->Nxl * s->Ny / 2, P = (long)s->Nxl * s->Ny;
-        if (!s->src_in_spectrum) launch_paired_zline(true, (const double2 *)s->rx, s->xs, s->ztw, C, s->Nz, s->logn_z, 1.0);
+        if (!s->src_in_spectrum) launch_paired_zline(*s->opt, true, (const double2 *)s->rx, s->xs, s->ztw, C, s->Nz, s->logn_z, 1.0);
         s->src_in_spectrum = false;
-        launch_strided_line_fft(s->xs, s->ytw, (long)s->Nxl, (long)s->Nxl, (unsigned)s->Nzh, s->Ny, s->logn_y, 0, 1.0, P);
-        launch_xline_thomas<false>(s->xE, s->xs, s->rden_x, s->M, s->Nxl, a, s->payload, nullptr, 1.0);      // reads only: the payload
+        launch_strided_line_fft(*s->opt, s->xs, s->ytw, (long)s->Nxl, (long)s->Nxl, (unsigned)s->Nzh, s->Ny, s->logn_y, 0, 1.0, P);
+        launch_xline_thomas<false>(*s->opt, s->xE, s->xs, s->rden_x, s->M, s->Nxl, a, s->payload, nullptr, 1.0);      // reads only: the payload
         KERNEL_CHECK();
         return OCN_OK;
     }
@@ -2102,7 +2088,7 @@ extern "C" int ocn_dist_poisson_forward_local(ocn_dist_poisson_t s) {
         FFT_TRY(hipfftExecD2Z(s->plan_zr2c, s->rreal, (hipfftDoubleComplex *)s->spec));
         if (s->yline) {
             const long C = (long)s->Nzp * s->Nxl;
-            launch_strided_line_fft(s->spec, s->ytw, C, C, 1, s->Ny, s->logn_y, 0, 1.0);
+            launch_strided_line_fft(*s->opt, s->spec, s->ytw, C, C, 1, s->Ny, s->logn_y, 0, 1.0);
         } else if (!s->zf_2d) {
             if ((rc = plan_set_stream(s->plan_y))) return rc;
             FFT_TRY(hipfftExecZ2Z(s->plan_y, (hipfftDoubleComplex *)s->spec, (hipfftDoubleComplex *)s->spec, HIPFFT_FORWARD));
@@ -2140,10 +2126,10 @@ static int dist_poisson_backward_local(ocn_dist_poisson_t s, double *phi, bool k
         // interface unknowns, then the SAME line solve on the right-hand side that carries them in its two end entries: the final solution
         hipLaunchKernelGGL(sub_interface_kernel, dim3((unsigned)((s->M + 255) / 256)), dim3(256), 0, g_stream, s->M, s->Ny, s->Nxl, s->R, s->rank,
                            a, s->lam[1], s->lam[2], s->s_first, s->s_last, (const double *)(s->iface + 2 * s->M + 1), s->gathered, s->iface);
-        launch_xline_thomas<true>(s->xE, s->xs, s->rden_x, s->M, s->Nxl, a, nullptr, s->iface, scale);
+        launch_xline_thomas<true>(*s->opt, s->xE, s->xs, s->rden_x, s->M, s->Nxl, a, nullptr, s->iface, scale);
         const long C = (long)s->Nxl * s->Ny / 2, P = (long)s->Nxl * s->Ny;
-        launch_strided_line_fft(s->xs, s->ytw, (long)s->Nxl, (long)s->Nxl, (unsigned)s->Nzh, s->Ny, s->logn_y, 1, 1.0, P);
-        launch_paired_zline(false, s->xs, (double2 *)s->rx, s->ztw, C, s->Nz, s->logn_z, 1.0);
+        launch_strided_line_fft(*s->opt, s->xs, s->ytw, (long)s->Nxl, (long)s->Nxl, (unsigned)s->Nzh, s->Ny, s->logn_y, 1, 1.0, P);
+        launch_paired_zline(*s->opt, false, s->xs, (double2 *)s->rx, s->ztw, C, s->Nz, s->logn_z, 1.0);
         if (!keep_zfast && !phi) return fail(OCN_EINVAL, "NULL pressure field");
         if (!keep_zfast)           // (here: keep the dense x-fastest solution in s->rx)
             hipLaunchKernelGGL(copy_dense_to_field_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, phi, LOC_C), (const double *)s->rx);
@@ -2159,7 +2145,7 @@ static int dist_poisson_backward_local(ocn_dist_poisson_t s, double *phi, bool k
         int rcz;
         if (s->yline) {
             const long C = (long)s->Nzp * s->Nxl;
-            launch_strided_line_fft(s->spec, s->ytw, C, C, 1, s->Ny, s->logn_y, 1, 1.0);
+            launch_strided_line_fft(*s->opt, s->spec, s->ytw, C, C, 1, s->Ny, s->logn_y, 1, 1.0);
         } else if (!s->zf_2d) {
             if ((rcz = plan_set_stream(s->plan_y))) return rcz;
             FFT_TRY(hipfftExecZ2Z(s->plan_y, (hipfftDoubleComplex *)s->spec, (hipfftDoubleComplex *)s->spec, HIPFFT_BACKWARD));
@@ -2212,9 +2198,9 @@ extern "C" int ocn_dist_poisson_source_term(ocn_dist_poisson_t s, const double *
 // (Ny, Nz) column received by the one-column exchange
 static int dist_poisson_source_term_wrapped(ocn_dist_poisson_t s, const double *u, const double *v, const double *w, const double *u_east) {
     const DGrid &g = s->grid->d;
-    if (s->xfast && g_dist_fuse_source) {
+    if (s->xfast && s->opt->dist_fuse_source) {
         const long C = (long)s->Nxl * s->Ny / 2;
-        const int zl = line_zl(s->Nz);
+        const int zl = line_zl(*s->opt, s->Nz);
         const dim3 grd((unsigned)((C + zl - 1) / zl));
         const size_t lds = (size_t)s->Nz * zl * sizeof(double2);
         const FView fu = make_view(g, u, LOC_U), fv = make_view(g, v, LOC_V), fw = make_view(g, w, LOC_W);
@@ -2255,7 +2241,7 @@ extern "C" int ocn_dist_poisson_forward_yz(ocn_dist_poisson_t s) {
     int rc;
     if (s->yline) {
         const long C = (long)s->Nxh * s->Nz;
-        launch_strided_line_fft(s->zfield, s->ytw, C, C, 1, s->Ny, s->logn_y, 0, 1.0);
+        launch_strided_line_fft(*s->opt, s->zfield, s->ytw, C, C, 1, s->Ny, s->logn_y, 0, 1.0);
     } else {
         if ((rc = plan_set_stream(s->plan_loc))) return rc;
         FFT_TRY(hipfftExecZ2Z(s->plan_loc, (hipfftDoubleComplex *)s->zfield, (hipfftDoubleComplex *)s->zfield, HIPFFT_FORWARD));
@@ -2322,7 +2308,7 @@ static int dist_poisson_backward_yz(ocn_dist_poisson_t s, double *phi, bool keep
                        s->Ny, s->Nyh, s->Nyc, s->Nz, s->zmode == 0);
     if (s->yline) {
         const long C = (long)s->Nxh * s->Nz;
-        launch_strided_line_fft(s->zfield, s->ytw, C, C, 1, s->Ny, s->logn_y, 1, 1.0);
+        launch_strided_line_fft(*s->opt, s->zfield, s->ytw, C, C, 1, s->Ny, s->logn_y, 1, 1.0);
     } else {
         if ((rc = plan_set_stream(s->plan_loc))) return rc;
         FFT_TRY(hipfftExecZ2Z(s->plan_loc, (hipfftDoubleComplex *)s->zfield, (hipfftDoubleComplex *)s->zfield, HIPFFT_BACKWARD));
@@ -2343,6 +2329,7 @@ struct DistModel;
 static void dist_model_free(DistModel *dm);
 struct ocn_model_s {
     ocn_grid_t grid;
+    OcnOptions opt;                         // this model's options: the library defaults when it was created, then ocn_model_set_option
     DistModel *dm = nullptr;                // x-slab partition (ocn_dist.h): communicator, distributed solver, halo buffers
     int ntr, nf;
     double *U[OCN_MAX_FIELDS], *Gn[OCN_MAX_FIELDS], *Gm[OCN_MAX_FIELDS];
@@ -2350,14 +2337,8 @@ struct ocn_model_s {
     // write here (other workgroups still read U), then the two sets swap roles. Two swaps per time-step: the pointers
     // handed out by ocn_model_field are the live ones again at every time-step boundary.
     double *U2[OCN_MAX_FIELDS];
-    int fuse_substep = 1;
-    int fused_epilogue = 1;                 // Coriolis + hydrostatic gradient + closure (+ substep) as one launch
-    // One RK3 time-step is ~50 dependent launches. Option use_graph = 1 captures the step once per (Δt, configuration) into a
-    // hipGraph and replays it: all pointer swaps of a step cancel out, kernel arguments depend on Δt only; `epoch` is bumped by
-    // everything that changes what a step launches. OFF by default: measured on MI355X (tools/time_small.py) replay and plain
-    // launches take the same time at every size (16^3: 0.436 vs 0.441 ms/step, 256^3: 7.58 vs 7.51) -- small grids are bound by
-    // the ~9 us GPU-side latency between DEPENDENT dispatches, which a graph does not remove; only fewer kernels would.
-    int use_graph = 0;
+    // option use_graph: the captured step (all pointer swaps of a step cancel out, kernel arguments depend on Δt only); `epoch` is
+    // bumped by everything that changes what a step launches
     hipGraphExec_t graph_exec = nullptr;
     double graph_dt = 0.0;
     uint64_t graph_epoch = 0, epoch = 1;
@@ -2379,7 +2360,6 @@ struct ocn_model_s {
     ForcingTable forcing_h = {};
     ForcingTable *forcing_d = nullptr;
     double *forcing_tables[OCN_MAX_FIELDS][OCN_MAX_FORCING_TERMS][2] = {};
-    int fused_forcing = 1;
     bool has_coriolis = false;              // coriolis = FPlane(f)
     double fcor = 0.0;
     int buoyancy_kind = 0, bT_index = 0, S_index = 0;    // 0 nothing, 1 BuoyancyTracer, 2 linear SeawaterBuoyancy
@@ -2392,8 +2372,6 @@ struct ocn_model_s {
     double time = 0, last_dt = INFINITY, last_stage_dt = INFINITY;
     int64_t iteration = 0;
     int stage = 1;
-    int tendency_impl = 2;
-    int swap_tendencies = 1;
     // live kernel timing for bench.py's roofline block: hipEvent pairs on the launch stream around every tendency
     // evaluation (the dominant kernel), resolved by ocn_model_profile_read
     int profile = 0;
@@ -2426,7 +2404,7 @@ static int model_create(ocn_model_t *model, ocn_grid_t grid, int ntracers, bool 
     // before it creates the handle
     if (!grid->advection_error.empty()) return fail(OCN_EINVAL, "%s", grid->advection_error.c_str());
     ocn_model_s *m = new ocn_model_s();
-    m->grid = grid; m->ntr = ntracers; m->nf = 3 + ntracers;
+    m->grid = grid; m->opt = g_defaults; m->ntr = ntracers; m->nf = 3 + ntracers;
     for (int f = 0; f < OCN_MAX_FIELDS; ++f) m->U[f] = m->U2[f] = m->Gn[f] = m->Gm[f] = nullptr;
     m->p = nullptr; m->solver = nullptr; m->blockmax = nullptr;
     const int *locs[3] = {LOC_U, LOC_V, LOC_W};
@@ -2454,7 +2432,7 @@ static int model_create(ocn_model_t *model, ocn_grid_t grid, int ntracers, bool 
         hipError_t e = dev_alloc((void **)&m->blockmax, 1024 * sizeof(double));
         if (e != hipSuccess) rc = fail((int)e, "hipMalloc: %s", hipGetErrorString(e));
     }
-    if (!rc && with_solver) rc = ocn_poisson_create(&m->solver, grid, -1);
+    if (!rc && with_solver) rc = poisson_create(&m->solver, grid, -1, &m->opt);
     if (rc) { ocn_model_destroy(m); return rc; }
     *model = m;
     return OCN_OK;
@@ -2508,59 +2486,100 @@ extern "C" int ocn_model_field(ocn_model_t m, const char *name, double **ptr, in
     return OCN_OK;
 }
 
-// library-wide tuning knobs (no reference equivalent; defaults are the tuned values)
-extern "C" int ocn_set_option(const char *key, int value) {
-    if (!key) return fail(OCN_EINVAL, "NULL argument");
-    g_epoch += 1;
-    if (!strcmp(key, "real_fft")) { g_real_fft = value; return OCN_OK; }
-    if (!strcmp(key, "c2r_strided")) { g_c2r_strided = value; return OCN_OK; }
-    if (!strcmp(key, "tendency_impl")) { if (value < 0 || value > 2) return fail(OCN_EINVAL, "tendency_impl is 0, 1 or 2"); g_tendency_impl = value; return OCN_OK; }
-    if (!strcmp(key, "fused_ty")) { g_fused_ty = value; return OCN_OK; }
-    if (!strcmp(key, "role_ldspad")) { g_role_ldspad = value; return OCN_OK; }
-    // 0: the reference's IEEE operation sequence (default); 1: the contracted WENO flux of the role kernel (ocn_device.h) -- opt-in,
-    // within north_star's 1e-12 of the default but not bit-identical to it; other tendency kernels ignore it
-    if (!strcmp(key, "arithmetic")) { if (value < 0 || value > 1) return fail(OCN_EINVAL, "arithmetic is 0 (reference sequence) or 1 (contracted)"); g_arithmetic = value; return OCN_OK; }
-    if (!strcmp(key, "role_kchunk")) { if (value < 0) return fail(OCN_EINVAL, "role_kchunk must be >= 0 (0 = automatic)"); g_role_kchunk = value; return OCN_OK; }
-    if (!strcmp(key, "fused_minw")) { g_fused_minw = value; return OCN_OK; }
-    if (!strcmp(key, "fused_zwin")) { g_fused_zwin = value; return OCN_OK; }
-    if (!strcmp(key, "fused_xcd")) { g_fused_xcd = value; return OCN_OK; }
-    if (!strcmp(key, "fused_zfft")) { g_fused_zfft = value; return OCN_OK; }
-    if (!strcmp(key, "fused_halo")) { g_fused_halo = value; return OCN_OK; }
-    if (!strcmp(key, "dist_substructured")) { g_dist_substructured = value; return OCN_OK; }
-    if (!strcmp(key, "dist_zfirst")) { g_dist_zfirst = value; return OCN_OK; }
-    if (!strcmp(key, "dist_yline")) { g_dist_yline = value; return OCN_OK; }
-    if (!strcmp(key, "dist_fused_step")) { g_dist_fused_step = value; return OCN_OK; }
-    if (!strcmp(key, "dist_xfast")) { g_dist_xfast = value; return OCN_OK; }
-    if (!strcmp(key, "dist_fuse_source")) { g_dist_fuse_source = value; return OCN_OK; }
-    if (!strcmp(key, "line_zl512")) { if (value != 4 && value != 8) return fail(OCN_EINVAL, "line_zl512 is 4 or 8"); g_line_zl512 = value; return OCN_OK; }
-    if (!strcmp(key, "dist_xline_group")) { g_dist_xline_group = value; return OCN_OK; }
-    if (!strcmp(key, "dist_pencil_transposes")) { g_dist_pencil_transposes = value; return OCN_OK; }
-    if (!strcmp(key, "amd_march")) { g_amd_march = value; return OCN_OK; }
-    if (!strcmp(key, "epilogue_march")) { g_epilogue_march = value; return OCN_OK; }
-    if (!strcmp(key, "epilogue_rows")) { if (value < 1 || value > 8) return fail(OCN_EINVAL, "epilogue_rows is 1 .. 8"); g_epilogue_rows = value; return OCN_OK; }
-    if (!strcmp(key, "epilogue_kchunk")) { if (value < 0) return fail(OCN_EINVAL, "epilogue_kchunk must be >= 0 (0 = automatic)"); g_epilogue_kchunk = value; return OCN_OK; }
-    if (!strcmp(key, "split_solve")) { g_split_solve = value; return OCN_OK; }
-    if (!strcmp(key, "skip_stage_pressure")) { g_skip_stage_pressure = value; return OCN_OK; }
-    if (!strcmp(key, "skip_dead_tendency_store")) { g_skip_dead_tendency_store = value; return OCN_OK; }
-    if (!strcmp(key, "fused_kchunk")) { if (value < 0) return fail(OCN_EINVAL, "fused_kchunk must be >= 0 (0 = automatic)"); g_fused_kchunk = value; return OCN_OK; }
-    return fail(OCN_EINVAL, "unknown option %s", key);
+// ---------------------------------------------------------------------------------------------------------------------
+// tuning options (ocn_options.h): the one table of keys behind ocn_set_option, ocn_model_set_option and ocn_model_get_option
+// ---------------------------------------------------------------------------------------------------------------------
+enum OptionScope {
+    OPT_STEP,          // read while stepping: a model's setting takes effect at its next launch
+    OPT_CREATION,      // read only when a model or solver is built: ocn_set_option before the model is created
+    OPT_PARTITIONED,   // the partitioned step's: refused on a single-GPU model
+};
+struct OptionRow {
+    const char *key;
+    int OcnOptions::*member;
+    OptionScope scope;
+    bool (*valid)(int);           // nullptr: any value
+    const char *range;            // the error message when `valid` refuses a value
+    const char *alias;            // the library's earlier name of the same option
+};
+static bool nonneg(int v) { return v >= 0; }
+static const OptionRow kOptions[] = {
+    {"tendency_impl", &OcnOptions::tendency_impl, OPT_STEP, [](int v) { return v >= 0 && v <= 2; }, "tendency_impl is 0, 1 or 2"},
+    {"arithmetic", &OcnOptions::arithmetic, OPT_STEP, [](int v) { return v == 0 || v == 1; }, "arithmetic is 0 (reference sequence) or 1 (contracted)"},
+    {"role_kchunk", &OcnOptions::role_kchunk, OPT_STEP, nonneg, "role_kchunk must be >= 0 (0 = automatic)"},
+    {"role_ldspad", &OcnOptions::role_ldspad, OPT_STEP},
+    {"fused_ty", &OcnOptions::fused_ty, OPT_STEP},
+    {"fused_kchunk", &OcnOptions::fused_kchunk, OPT_STEP, nonneg, "fused_kchunk must be >= 0 (0 = automatic)"},
+    {"fused_zwin", &OcnOptions::fused_zwin, OPT_STEP},
+    {"fused_xcd", &OcnOptions::fused_xcd, OPT_STEP},
+    {"epilogue_march", &OcnOptions::epilogue_march, OPT_STEP},
+    {"epilogue_rows", &OcnOptions::epilogue_rows, OPT_STEP, [](int v) { return v >= 1 && v <= 8; }, "epilogue_rows is 1 .. 8"},
+    {"epilogue_kchunk", &OcnOptions::epilogue_kchunk, OPT_STEP, nonneg, "epilogue_kchunk must be >= 0 (0 = automatic)"},
+    {"amd_march", &OcnOptions::amd_march, OPT_STEP},
+    {"fused_halo", &OcnOptions::fused_halo, OPT_STEP},
+    {"real_fft", &OcnOptions::real_fft, OPT_STEP},
+    {"c2r_strided", &OcnOptions::c2r_strided, OPT_CREATION},
+    {"fused_zfft", &OcnOptions::fused_zfft, OPT_CREATION},
+    {"split_solve", &OcnOptions::split_solve, OPT_STEP},
+    {"line_zl512", &OcnOptions::line_zl512, OPT_STEP, [](int v) { return v == 4 || v == 8; }, "line_zl512 is 4 or 8"},
+    {"skip_stage_pressure", &OcnOptions::skip_stage_pressure, OPT_STEP},
+    {"skip_dead_tendency_store", &OcnOptions::skip_dead_tendency_store, OPT_STEP},
+    {"dist_substructured", &OcnOptions::dist_substructured, OPT_CREATION},
+    {"dist_zfirst", &OcnOptions::dist_zfirst, OPT_CREATION},
+    {"dist_xfast", &OcnOptions::dist_xfast, OPT_CREATION},
+    {"dist_yline", &OcnOptions::dist_yline, OPT_CREATION},
+    {"dist_fuse_source", &OcnOptions::dist_fuse_source, OPT_STEP},
+    {"dist_xline_group", &OcnOptions::dist_xline_group, OPT_STEP},
+    {"dist_pencil_transposes", &OcnOptions::dist_pencil_transposes, OPT_CREATION},
+    {"swap_tendencies", &OcnOptions::swap_tendencies, OPT_STEP},
+    {"fuse_substep", &OcnOptions::fuse_substep, OPT_STEP},
+    {"fused_epilogue", &OcnOptions::fused_epilogue, OPT_STEP},
+    {"fused_forcing", &OcnOptions::fused_forcing, OPT_STEP},
+    {"use_graph", &OcnOptions::use_graph, OPT_STEP},
+    {"async_halos", &OcnOptions::async_halos, OPT_PARTITIONED},
+    {"thin_halos", &OcnOptions::thin_halos, OPT_PARTITIONED},
+    {"early_exchange", &OcnOptions::early_exchange, OPT_PARTITIONED},
+    {"strip_width", &OcnOptions::strip_width, OPT_PARTITIONED},
+    {"fused_step", &OcnOptions::fused_step, OPT_PARTITIONED, nullptr, nullptr, "dist_fused_step"},
+};
+
+static const OptionRow *find_option(const char *key) {
+    for (const OptionRow &r : kOptions)
+        if (!strcmp(key, r.key) || (r.alias && !strcmp(key, r.alias))) return &r;
+    return nullptr;
+}
+// the row of `key` after checking `value` against it (nullptr: unknown key or refused value, the error is set)
+static const OptionRow *option_row(const char *key, int value) {
+    const OptionRow *r = find_option(key);
+    if (!r) { fail(OCN_EINVAL, "unknown option %s", key); return nullptr; }
+    if (r->valid && !r->valid(value)) { fail(OCN_EINVAL, "%s", r->range); return nullptr; }
+    return r;
 }
 
-static int dist_model_set_option(ocn_model_s *m, const char *key, int value);
-static void dist_abandon_exchange(ocn_model_s *m);
+extern "C" int ocn_set_option(const char *key, int value) {
+    if (!key) return fail(OCN_EINVAL, "NULL argument");
+    const OptionRow *r = option_row(key, value);
+    if (!r) return OCN_EINVAL;
+    g_defaults.*r->member = value;
+    return OCN_OK;
+}
+
+static bool dist_fused_step_buffers(const ocn_model_s *m);
 static int dist_model_get_option(const ocn_model_s *m, const char *key, int *value);
+static void dist_abandon_exchange(ocn_model_s *m);
 extern "C" int ocn_model_set_option(ocn_model_t m, const char *key, int value) {
     if (!m || !key) return fail(OCN_EINVAL, "NULL argument");
     m->epoch += 1;
-    if (!strcmp(key, "use_graph")) { m->use_graph = value; return OCN_OK; }
-    if (!strcmp(key, "tendency_impl")) { m->tendency_impl = value; return OCN_OK; }
-    if (!strcmp(key, "swap_tendencies")) { m->swap_tendencies = value; return OCN_OK; }
-    if (!strcmp(key, "fuse_substep")) { m->fuse_substep = value; return OCN_OK; }
-    if (!strcmp(key, "fused_epilogue")) { m->fused_epilogue = value; return OCN_OK; }
-    if (!strcmp(key, "fused_forcing")) { m->fused_forcing = value; return OCN_OK; }
     if (!strcmp(key, "profile")) { m->profile = value; m->events_used = 0; return OCN_OK; }
-    if (dist_model_set_option(m, key, value) == OCN_OK) return OCN_OK;
-    return ocn_set_option(key, value);
+    const OptionRow *r = option_row(key, value);
+    if (!r) return OCN_EINVAL;
+    if (r->scope == OPT_CREATION)
+        return fail(OCN_ESTATE, "option %s is read when a model is created: set it with ocn_set_option before creating the model", key);
+    if (r->scope == OPT_PARTITIONED && !m->dm) return fail(OCN_EINVAL, "option %s belongs to a partitioned model", key);
+    if (r->member == &OcnOptions::fused_step && value && !dist_fused_step_buffers(m))
+        return fail(OCN_ENOTSUP, "fused_step needs a (connected, Periodic, Periodic) slab with the z-fastest substructured solver");
+    m->opt.*r->member = value;
+    return OCN_OK;
 }
 
 static bool has_physics(const ocn_model_s *m) { return m->has_coriolis || m->buoyancy_kind != 0 || m->has_closure || m->has_amd; }
@@ -2576,8 +2595,9 @@ static bool epilogue_runs(const ocn_model_s *m);
 // spilled, ocn_tendency_roles.h) -- the configs[1]-plus-sponge case, which keeps the RK3 substep fused. Partitioned models (interior / strip launches) and everything else take the standalone pass.
 static bool forcing_in_role(const ocn_model_s *m) {
     const DGrid &g = m->grid->d;
-    return has_forcing(m) && m->fused_forcing && !m->dm && !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && !epilogue_runs(m) &&
-           m->tendency_impl == 2 && g_arithmetic == 0 && g.tz == OCN_PERIODIC && fused_path(g, nullptr, m->ntr, 2) && role_tendency_supported(g);
+    return has_forcing(m) && m->opt.fused_forcing && !m->dm && !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && !epilogue_runs(m) &&
+           m->opt.tendency_impl == 2 && m->opt.arithmetic == 0 && g.tz == OCN_PERIODIC && fused_path(m->opt, g, nullptr, m->ntr, 2) &&
+           role_tendency_supported(m->opt, g);
 }
 // which pass adds the forcing term (option "forcing_path"): 0 none, 1 the role tendency kernel, 3 the standalone pass (add_forcing_kernel);
 // 2 (inside the physics epilogue) is reserved: that fusion is not built
@@ -2656,7 +2676,8 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
     const int clo = m->has_amd ? 2 : (m->has_closure ? 1 : 0);
     // closure terms on a grid without Flat directions: the z-marching form (ocn_epilogue_march.h) -- the union of the fields' ranges, one
     // column of halo around it readable
-    if (g_epilogue_march && clo != 0 && m->ntr <= 2 && g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT) {
+    const OcnOptions &o = m->opt;
+    if (o.epilogue_march && clo != 0 && m->ntr <= 2 && g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT) {
         Range6 R = a.r[0];
         for (int f = 1; f < m->nf; ++f) {
             R.i0 = std::min(R.i0, a.r[f].i0); R.i1 = std::max(R.i1, a.r[f].i1); R.j0 = std::min(R.j0, a.r[f].j0); R.j1 = std::max(R.j1, a.r[f].j1);
@@ -2664,13 +2685,13 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
         }
         if (R.i0 - 1 >= 1 - g.Hx && R.i1 + 1 <= g.Nx + g.Hx && R.j0 - 1 >= 1 - g.Hy && R.j1 + 1 <= g.Ny + g.Hy && R.k0 - 1 >= 1 - g.Hz && R.k1 + 1 <= g.Nz + g.Hz) {
             const int ni = R.i1 - R.i0 + 1, nj = R.j1 - R.j0 + 1, nk = R.k1 - R.k0 + 1;
-            const int bx = (ni + OCN_EPI_MARCH_COLS - 1) / OCN_EPI_MARCH_COLS, by = (nj + g_epilogue_rows - 1) / g_epilogue_rows;
-            int kchunk = g_epilogue_kchunk;
+            const int bx = (ni + OCN_EPI_MARCH_COLS - 1) / OCN_EPI_MARCH_COLS, by = (nj + o.epilogue_rows - 1) / o.epilogue_rows;
+            int kchunk = o.epilogue_kchunk;
             if (kchunk <= 0) {                       // >= ~8 waves per SIMD over the chip, chunks of at least 8 levels
                 kchunk = nk;
-                while (kchunk > 8 && (long)bx * by * ((nk + kchunk - 1) / kchunk) * g_epilogue_rows < 8192) kchunk = (kchunk + 1) / 2;
+                while (kchunk > 8 && (long)bx * by * ((nk + kchunk - 1) / kchunk) * o.epilogue_rows < 8192) kchunk = (kchunk + 1) / 2;
             }
-            const dim3 mg(bx, by, (nk + kchunk - 1) / kchunk), mb(64, g_epilogue_rows);
+            const dim3 mg(bx, by, (nk + kchunk - 1) / kchunk), mb(64, o.epilogue_rows);
             int mask = 0;                 // sides that carry a Flux condition: epilogue_flux_shell_kernel re-does their cells from the STORED tendency
             for (int f = 0; f < m->nf; ++f)
                 for (int sd = 0; sd < 6; ++sd)
@@ -2719,37 +2740,30 @@ static int count_linear_flux(const ocn_model_s *m) {
     return n;
 }
 static bool epilogue_runs(const ocn_model_s *m) {
-    return m->fused_epilogue && (has_physics(m) || m->any_flux_bc || m->any_linear_flux) && count_linear_flux(m) <= OCN_EPILOGUE_MAX_LIN;
+    return m->opt.fused_epilogue && (has_physics(m) || m->any_flux_bc || m->any_linear_flux) && count_linear_flux(m) <= OCN_EPILOGUE_MAX_LIN;
 }
 static bool can_fuse_substep(const ocn_model_s *m) {
     // without extra physics the substep rides in the fused advection kernel; with Coriolis / buoyancy / closure terms it rides in
     // the epilogue pass that completes the tendencies (any advection path); a valued Flux condition is added after both
-    if (!m->fuse_substep || !m->swap_tendencies) return false;
+    if (!m->opt.fuse_substep || !m->opt.swap_tendencies) return false;
     if (has_forcing(m) && !forcing_in_role(m)) return false;         // the forcing pass completes G after the launch the substep would ride in
     if (epilogue_runs(m)) return true;                               // the epilogue pass also applies the Flux conditions
-    return !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && fused_path(m->grid->d, nullptr, m->ntr, m->tendency_impl);
+    return !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && fused_path(m->opt, m->grid->d, nullptr, m->ntr, m->opt.tendency_impl);
 }
 
 extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) {
     if (!m || !key || !value) return fail(OCN_EINVAL, "NULL argument");
-    if (!strcmp(key, "tendency_impl")) { *value = m->tendency_impl; return OCN_OK; }
-    if (!strcmp(key, "swap_tendencies")) { *value = m->swap_tendencies; return OCN_OK; }
-    if (!strcmp(key, "use_graph")) { *value = m->use_graph; return OCN_OK; }
+    if (!dist_model_get_option(m, key, value)) return OCN_OK;                        // fused_step, dist_poisson_layout
+    if (const OptionRow *r = find_option(key)) { *value = m->opt.*r->member; return OCN_OK; }
     if (!strcmp(key, "graph_replays")) { *value = m->graph_replays; return OCN_OK; }
     if (!strcmp(key, "graph_captures")) { *value = m->graph_captures; return OCN_OK; }
     if (!strcmp(key, "graph_failures")) { *value = m->graph_failures; return OCN_OK; }
-    if (!strcmp(key, "fuse_substep")) { *value = m->fuse_substep; return OCN_OK; }
-    if (!strcmp(key, "fused_forcing")) { *value = m->fused_forcing; return OCN_OK; }
     if (!strcmp(key, "forcing_path")) { *value = forcing_path(m); return OCN_OK; }
     if (!strcmp(key, "fuse_substep_active")) { *value = can_fuse_substep(m) ? 1 : 0; return OCN_OK; }
     // what the tendency LAUNCH itself carries (bench.py prices its bytes with these): the next stage's substep rides in the advection kernel
     // only without physics / Flux conditions (with them it rides in the epilogue pass); the tendency of the second stage is then not stored
     if (!strcmp(key, "substep_in_tendency_kernel")) { *value = (can_fuse_substep(m) && !epilogue_runs(m)) ? 1 : 0; return OCN_OK; }
-    if (!strcmp(key, "skip_dead_tendency_store")) { *value = g_skip_dead_tendency_store; return OCN_OK; }
-    if (!strcmp(key, "skip_stage_pressure")) { *value = g_skip_stage_pressure; return OCN_OK; }
-    if (!strcmp(key, "arithmetic")) { *value = g_arithmetic; return OCN_OK; }
-    if (dist_model_get_option(m, key, value) == OCN_OK) return OCN_OK;
-    if (!strcmp(key, "fused_tendency_active")) { *value = fused_path(m->grid->d, nullptr, m->ntr, m->tendency_impl) ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "fused_tendency_active")) { *value = fused_path(m->opt, m->grid->d, nullptr, m->ntr, m->opt.tendency_impl) ? 1 : 0; return OCN_OK; }
     return fail(OCN_EINVAL, "unknown model option '%s'", key);
 }
 
@@ -2758,7 +2772,7 @@ static int dist_update_state(ocn_model_s *m, bool compute_tend, const FusedSubst
 static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub, const int *amd_range);
 static int update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub = nullptr) {
     if (m->dm) return dist_update_state(m, compute_tend, sub);
-    int rc = fill_halo_regions(m->grid, m->U, m->loc, m->nf, /*fill_open_bcs=*/false, m->any_bc ? m->bcs : nullptr);
+    int rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, /*fill_open_bcs=*/false, m->any_bc ? m->bcs : nullptr);
     if (rc) return rc;
     return update_state_tail(m, compute_tend, sub, nullptr);
 }
@@ -2769,7 +2783,7 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
     // compute_auxiliaries!: compute_diffusivities! over :xyz (update_nonhydrostatic_model_state.jl:58-69), then
     // fill_halo_regions!(model.diffusivity_fields; only_local_halos = true) (:44) with the default ccc conditions
     if (m->has_amd) {
-        if ((rc = amd_diffusivities(g, m->Cnu, m->Ckappa, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->nu_e, m->kappa_e, amd_range))) return rc;
+        if ((rc = amd_diffusivities(m->opt, g, m->Cnu, m->Ckappa, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->nu_e, m->kappa_e, amd_range))) return rc;
         double *K[OCN_MAX_FIELDS];
         int kl[OCN_MAX_FIELDS][3];
         K[0] = m->nu_e;
@@ -2777,7 +2791,7 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
         for (int q = 0; q < 1 + m->ntr; ++q) memcpy(kl[q], LOC_C, sizeof(int) * 3);
         // (on an x-slab rank amd_range includes i = 0 and Nx + 1: their z halo cell is filled too, the value a serial run's periodic x
         // fill copies there -- the reference's only_local_halos fill leaves it unwritten on a partitioned grid, halo_communication.jl:87-110)
-        if ((rc = fill_halo_regions(m->grid, K, kl, 1 + m->ntr, true, m->any_kbc ? m->kbcs : nullptr, amd_range != nullptr))) return rc;
+        if ((rc = fill_halo_regions(m->opt, m->grid, K, kl, 1 + m->ntr, true, m->any_kbc ? m->kbcs : nullptr, amd_range != nullptr))) return rc;
     }
     // compute_auxiliaries!: update_hydrostatic_pressure! (update_nonhydrostatic_model_state.jl:58-69)
     if (m->buoyancy_kind &&
@@ -2796,8 +2810,8 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
             HIP_TRY(hipEventRecord(ev->first, g_stream));
         }
         const bool physics = has_physics(m) || epilogue_runs(m);
-        rc = compute_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
-                                m->tendency_impl, physics ? nullptr : sub, forcing_in_role(m) ? m->forcing_d : nullptr);
+        rc = compute_tendencies(m->opt, g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
+                                m->opt.tendency_impl, physics ? nullptr : sub, forcing_in_role(m) ? m->forcing_d : nullptr);
         if (ev) HIP_TRY(hipEventRecord(ev->second, g_stream));
         if (!rc && physics) {
             if (epilogue_runs(m)) { if (has_physics(m) || sub) rc = tendency_epilogue(m, sub); }      // (Flux conditions alone and no substep: nothing to do)
@@ -2838,13 +2852,13 @@ static int compute_flux_bc_tendencies(ocn_model_s *m) {
 // compute_pressure_correction! (pressure_correction.jl:8-20)
 static int compute_pressure_correction(ocn_model_s *m) {
     const DGrid &g = m->grid->d;
-    int rc = fill_halo_regions(m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr);
+    int rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr);
     if (rc) return rc;
     if ((rc = solve_for_pressure(m->solver, m->U[0], m->U[1], m->U[2], m->p))) return rc;
     double *pp[1] = {m->p};
     const int pl[1][3] = {{OCN_CENTER, OCN_CENTER, OCN_CENTER}};
     (void)g;
-    return fill_halo_regions(m->grid, pp, pl, 1, true);
+    return fill_halo_regions(m->opt, m->grid, pp, pl, 1, true);
 }
 
 // make_pressure_correction! (pressure_correction.jl:40-53)
@@ -2864,10 +2878,10 @@ static int dist_pressure_step(ocn_model_s *m, double dt, bool tendencies_follow,
 // dense-solution path neither stores p / Δt⁺ nor fills its halos there -- after the step the field holds the last stage's pressure, as the
 // reference's does
 static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = true, bool keep_p = true) {
-    if (m->dm) return dist_pressure_step(m, dt, tendencies_follow, keep_p || !g_skip_stage_pressure);
+    if (m->dm) return dist_pressure_step(m, dt, tendencies_follow, keep_p || !m->opt.skip_stage_pressure);
     int rc;
     ocn_poisson_s *s = m->solver;
-    if (!(s->split && g_split_solve && g_real_fft && !s->general)) {
+    if (!(s->split && m->opt.split_solve && m->opt.real_fft && !s->general)) {
         if ((rc = compute_pressure_correction(m))) return rc;
         return make_pressure_correction(m, dt);
     }
@@ -2875,18 +2889,18 @@ static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = tru
     // triply periodic: the divergence reads its upper neighbours at the wrapped interior index, so fill_halo_regions!(velocities)
     // (pressure_correction.jl:10) is not needed here -- update_state! fills every halo again before anything else reads one
     const bool ppp = g.tx == OCN_PERIODIC && g.ty == OCN_PERIODIC && g.tz == OCN_PERIODIC;
-    if (!ppp && (rc = fill_halo_regions(m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr))) return rc;
+    if (!ppp && (rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr))) return rc;
     if ((rc = source_term(g, m->U[0], m->U[1], m->U[2], s->rrhs, s->kind == 1, true, 0, 0, false, ppp))) return rc;
     if ((rc = poisson_solve_real_split(s))) return rc;
     const double dtp = std::fmax(2.220446049250313e-16, dt);
     hipLaunchKernelGGL(pressure_correction_dense_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, m->U[0], LOC_U),
                        make_view(g, m->U[1], LOC_V), make_view(g, m->U[2], LOC_W), (const double *)s->rrhs, make_view(g, m->p, LOC_C), dtp,
-                       g.tz == OCN_BOUNDED, keep_p || !g_skip_stage_pressure);
+                       g.tz == OCN_BOUNDED, keep_p || !m->opt.skip_stage_pressure);
     KERNEL_CHECK();
-    if (!keep_p && g_skip_stage_pressure) return OCN_OK;
+    if (!keep_p && m->opt.skip_stage_pressure) return OCN_OK;
     double *pp[1] = {m->p};
     const int pl[1][3] = {{OCN_CENTER, OCN_CENTER, OCN_CENTER}};
-    return fill_halo_regions(m->grid, pp, pl, 1, true);
+    return fill_halo_regions(m->opt, m->grid, pp, pl, 1, true);
 }
 
 extern "C" int ocn_model_set_buoyancy(ocn_model_t m, int kind, int b_or_T_index, int S_index, double grav, double alpha, double beta) {
@@ -3132,7 +3146,7 @@ extern "C" int ocn_model_set_finalize(ocn_model_t m, int enforce_incompressibili
     if (!m) return fail(OCN_EINVAL, "NULL argument");
     const DGrid &g = m->grid->d;
     (void)g;
-    int rc = fill_halo_regions(m->grid, m->U, m->loc, m->nf, true, m->any_bc ? m->bcs : nullptr);     // set!(ϕ, value); fill_halo_regions!(ϕ) per field
+    int rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, true, m->any_bc ? m->bcs : nullptr);     // set!(ϕ, value); fill_halo_regions!(ϕ) per field
     if (rc) return rc;
     if ((rc = update_state(m, false))) return rc;
     if (enforce_incompressibility) {
@@ -3152,7 +3166,7 @@ static void tick(ocn_model_s *m, double dt, bool stage) {       // clock.jl:128-
 // pointer swap on this architecture: cells the tendency kernels never write (halos, excluded periphery) are zero in
 // both buffers for the model's lifetime.
 static int cache_previous_tendencies(ocn_model_s *m) {
-    if (m->swap_tendencies) {
+    if (m->opt.swap_tendencies) {
         for (int f = 0; f < m->nf; ++f) std::swap(m->Gn[f], m->Gm[f]);
         return OCN_OK;
     }
@@ -3194,7 +3208,7 @@ static int rk3_time_step(ocn_model_s *m, double dt) {
         if (stage < 2 && (rc = cache_previous_tendencies(m))) return rc;
         if (stage < 2 && can_fuse) {
             FusedSubstep sub{m->U2, m->Gm, dt, gam[stage + 1], zet[stage + 1], 1};
-            sub.store_G = stage != 1 || !g_skip_dead_tendency_store;        // G(U²): read by the third stage's substep only
+            sub.store_G = stage != 1 || !m->opt.skip_dead_tendency_store;        // G(U²): read by the third stage's substep only
             if ((rc = update_state(m, true, &sub))) return rc;
             for (int f = 0; f < m->nf; ++f) std::swap(m->U[f], m->U2[f]);
             substep_done = true;
@@ -3221,7 +3235,7 @@ extern "C" int ocn_model_time_step(ocn_model_t m, double dt) {
         if (rc) dist_abandon_exchange(m);
         return rc;
     }
-    if (!m->use_graph || m->profile || m->iteration == 0 || !g_stream_owned) return rk3_time_step(m, dt);
+    if (!m->opt.use_graph || m->profile || m->iteration == 0 || !g_stream_owned) return rk3_time_step(m, dt);
     if (m->graph_exec && m->graph_dt == dt && m->graph_epoch == m->epoch * 1000003ull + g_epoch) {
         hipError_t e = hipGraphLaunch(m->graph_exec, g_stream);
         if (e != hipSuccess) return fail((int)e, "hipGraphLaunch: %s", hipGetErrorString(e));

@@ -363,20 +363,16 @@ struct DistModel {
     double *buf_a = nullptr, *buf_b = nullptr;                              // the solver's payload / gathered or send / recv buffers
     size_t payload = 0, nbuf = 0;
     bool halos_in_flight = false;
-    int async_halos = -1;       // -1 automatic (slab wide enough for whole-tile strips), 0 off, 1 on
-    int thin_halos = 1;         // pressure step: exchange the ONE column that is read (u[Nx+1], p[0]) instead of Hx columns
-    int early_exchange = 1;     // start update_state!'s exchange from make_pressure_correction!
-    int strip_width = 0;        // 0 automatic
     bool bounded_x = false;     // the partitioned direction is Bounded: Right / LeftConnected end ranks, no wrap-around neighbour
     bool pencil = false;        // Partition(Rx, Ry) with Ry > 1: a second hop along y per fill (corners ride along)
     double *ss = nullptr, *ns = nullptr, *sr = nullptr, *nr = nullptr;     // y-halo buffers: Hy rows of every prognostic field per side
     bool plain_y = true;        // the non-partitioned y direction is Periodic (what the partitioned solvers transform); Bounded / Flat y: gathered solve
     // Round 3 -- the pressure step of (connected, Periodic, Periodic) x-slabs without the passes between its stages (ocn_kernels.h,
     // "Round 3"): one-column exchanges of u and p through dense (Ny, Nz) buffers that the source-term / correction kernels read directly,
-    // the solution left z-fastest, the early exchange packed from wrapped interior indices
-    bool fused_step = false;
+    // the solution left z-fastest, the early exchange packed from wrapped interior indices; the column buffers exist when the model was
+    // created with option fused_step on a slab that takes it, the option switches it on and off afterwards
     double *cws = nullptr, *ces = nullptr, *cwr = nullptr, *cer = nullptr;   // column buffers: Ny * Nz doubles each
-    bool fused() const { return fused_step && thin_halos != 0 && partitioned(); }
+    bool fused(const OcnOptions &o) const { return o.fused_step && cws && o.thin_halos != 0 && partitioned(); }
     bool general() const { return bounded_x || pencil || !plain_y; }                    // no overlap / thin exchanges on such partitions
     bool partitioned() const { return dist->world > 1 || dist->self_loop; }
 };
@@ -459,7 +455,7 @@ static int x_halo_pack_wrapped(const DGrid &g, double *const *fields, const int 
 static int dist_fill_halo_regions(ocn_model_s *m, double *const *fields, const int (*locs)[3], int n, bool fill_open,
                                   const ocn_bc_t (*bcs)[6], int nx = -1, int depth = 0) {
     DistModel *dm = m->dm;
-    int rc = fill_halo_regions(m->grid, fields, locs, n, fill_open, bcs);
+    int rc = fill_halo_regions(m->opt, m->grid, fields, locs, n, fill_open, bcs);
     if (rc || !dm->partitioned()) return rc;
     const DGrid &g = m->grid->d;
     if (nx < 0 || dm->pencil) nx = n;
@@ -508,7 +504,7 @@ static int dist_solve_for_pressure(ocn_model_s *m) {
         const size_t piece = (size_t)q->nmax * q->nymax * g.Nz;
         if ((rc = source_term(g, m->U[0], m->U[1], m->U[2], q->loc, ps->kind == 1, true, q->nmax, (long)q->nmax * q->nymax))) return rc;
         if ((rc = ocn_dist_all_gather(dm->dist, q->loc, q->all, piece))) return rc;
-        const bool real_path = g_real_fft && !ps->general;
+        const bool real_path = m->opt.real_fft && !ps->general;
         if (!real_path && (rc = ensure_complex(ps))) return rc;
         if (real_path)
             hipLaunchKernelGGL(gather_assemble_kernel<false>, grid3(G.Nx, G.Ny, G.Nz, BLK), BLK, 0, g_stream, (const double *)q->all, (void *)ps->rrhs,
@@ -575,7 +571,7 @@ static int dist_compute_pressure_correction_fused(ocn_model_s *m) {
     ocn_dist_poisson_s *s = dm->solver;
     const size_t col = (size_t)g.Ny * g.Nz;
     int rc;
-    if (g.tz != OCN_PERIODIC && (rc = fill_halo_regions(m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr))) return rc;
+    if (g.tz != OCN_PERIODIC && (rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr))) return rc;
     hipLaunchKernelGGL(column_pack_kernel, dim3((g.Ny + 255) / 256, g.Nz), dim3(256), 0, g_stream, g, make_view(g, m->U[0], LOC_U), 1, g.Nx,
                        dm->cws, dm->ces);
     KERNEL_CHECK();
@@ -606,8 +602,8 @@ static int dist_compute_pressure_correction_fused(ocn_model_s *m) {
 
 static int dist_compute_pressure_correction(ocn_model_s *m) {
     DistModel *dm = m->dm;
-    if (dm->fused()) return dist_compute_pressure_correction_fused(m);
-    const bool thin = dm->thin_halos != 0 && !dm->pencil;
+    if (dm->fused(m->opt)) return dist_compute_pressure_correction_fused(m);
+    const bool thin = m->opt.thin_halos != 0 && !dm->pencil;
     int rc = dist_fill_halo_regions(m, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr, thin ? 1 : 3, thin ? 1 : 0);
     if (rc) return rc;
     if ((rc = dist_solve_for_pressure(m))) return rc;
@@ -625,8 +621,8 @@ static int dist_make_pressure_correction(ocn_model_s *m, double dt, bool start_h
     const DGrid &g = m->grid->d;
     const double dtp = std::fmax(2.220446049250313e-16, dt);
     int rc;
-    const bool early = start_halo_exchange && dm->partitioned() && dm->early_exchange && dm->async_halos != 0 && g.Nx > 2 * g.Hx && !dm->general();
-    if (dm->fused()) {
+    const bool early = start_halo_exchange && dm->partitioned() && m->opt.early_exchange && m->opt.async_halos != 0 && g.Nx > 2 * g.Hx && !dm->general();
+    if (dm->fused(m->opt)) {
         // corrections straight from the z-fastest solution (p[0] from the received column): both strips in one launch, pack from wrapped
         // interior indices (no local fill of the strips), start the exchange, then the interior
         const bool zf = dm->solver->zfirst, zb = g.tz != OCN_PERIODIC;
@@ -651,7 +647,7 @@ static int dist_make_pressure_correction(ocn_model_s *m, double dt, bool start_h
             hipLaunchKernelGGL(pressure_correction_zfast_strips_kernel, dim3(1, (g.Ny + 31) / 32, g.Nz), dim3(8, 32), 0, g_stream, g, vu, vv, vw, pd, pw, vp, dtp, g.Hx);
         KERNEL_CHECK();
         if (zb) {            // a Bounded z: the strips' z halos come from their boundary conditions -- local fill, then the plain pack
-            if ((rc = fill_halo_regions(m->grid, m->U, m->loc, m->nf, false, m->any_bc ? m->bcs : nullptr))) return rc;
+            if ((rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, false, m->any_bc ? m->bcs : nullptr))) return rc;
             if ((rc = x_halo_buffers(g, m->U, m->loc, m->nf, dm->ws, dm->es, true))) return rc;
         } else if ((rc = x_halo_pack_wrapped(g, m->U, m->loc, m->nf, dm->ws, dm->es))) return rc;
         if ((rc = ocn_dist_exchange_start(dm->dist, dm->ws, dm->es, dm->wr, dm->er, dm->slab_total))) return rc;
@@ -663,7 +659,7 @@ static int dist_make_pressure_correction(ocn_model_s *m, double dt, bool start_h
     const int west[6] = {1, g.Hx, 1, g.Ny, 1, g.Nz}, east[6] = {g.Nx - g.Hx + 1, g.Nx, 1, g.Ny, 1, g.Nz};
     const int mid[6] = {g.Hx + 1, g.Nx - g.Hx, 1, g.Ny, 1, g.Nz};
     if ((rc = pc(west)) || (rc = pc(east))) return rc;
-    if ((rc = fill_halo_regions(m->grid, m->U, m->loc, m->nf, false, m->any_bc ? m->bcs : nullptr))) return rc;   // the strips' y / z halos
+    if ((rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, false, m->any_bc ? m->bcs : nullptr))) return rc;   // the strips' y / z halos
     if ((rc = x_halo_buffers(g, m->U, m->loc, m->nf, dm->ws, dm->es, true))) return rc;
     if ((rc = ocn_dist_exchange_start(dm->dist, dm->ws, dm->es, dm->wr, dm->er, dm->slab_total))) return rc;
     dm->halos_in_flight = true;
@@ -690,28 +686,28 @@ static int dist_update_state(ocn_model_s *m, bool compute_tend, const FusedSubst
         // the x exchange was started by make_pressure_correction!: finish the local fills (all columns are final now), take the
         // halos, then everything in one piece
         dm->halos_in_flight = false;
-        if ((rc = fill_halo_regions(m->grid, m->U, m->loc, m->nf, false, bcs))) return rc;
+        if ((rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, false, bcs))) return rc;
         if ((rc = ocn_dist_exchange_wait(dm->dist))) return rc;
         if ((rc = x_halo_buffers(g, m->U, m->loc, m->nf, dm->wr, dm->er, false))) return rc;
         return update_state_tail(m, compute_tend, sub, amd_range);
     }
     const bool physics = has_physics(m) || m->any_flux_bc || m->any_linear_flux;
-    const bool overlap = dm->async_halos < 0 ? g.Nx >= 3 * 64 : dm->async_halos != 0;
+    const bool overlap = m->opt.async_halos < 0 ? g.Nx >= 3 * 64 : m->opt.async_halos != 0;
     if (!compute_tend || !dm->partitioned() || !overlap || g.Nx <= 2 * g.Hx || physics || dm->general()) {
         if ((rc = dist_fill_halo_regions(m, m->U, m->loc, m->nf, false, bcs))) return rc;
         return update_state_tail(m, compute_tend, sub, amd_range);
     }
     // start the exchange, compute the interior that does not depend on x halos, finish, compute the two strips. The reference's strips
     // are Hx wide; the tendency kernel works on 64-lane tiles, so the strips are one tile wide whenever that leaves a tile of interior.
-    int W = dm->strip_width > 0 ? dm->strip_width : (g.Nx >= 3 * 64 ? 64 : g.Hx);
+    int W = m->opt.strip_width > 0 ? m->opt.strip_width : (g.Nx >= 3 * 64 ? 64 : g.Hx);
     if (!(g.Hx <= W && 2 * W < g.Nx)) return fail(OCN_EINVAL, "strip width %d must satisfy Hx <= W < Nx / 2", W);
-    if ((rc = fill_halo_regions(m->grid, m->U, m->loc, m->nf, false, bcs))) return rc;
+    if ((rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, false, bcs))) return rc;
     if ((rc = x_halo_buffers(g, m->U, m->loc, m->nf, dm->ws, dm->es, true))) return rc;
     if ((rc = ocn_dist_exchange_start(dm->dist, dm->ws, dm->es, dm->wr, dm->er, dm->slab_total))) return rc;
     const int interior[6] = {W + 1, g.Nx - W, 1, g.Ny, 1, g.Nz}, ws[6] = {1, W, 1, g.Ny, 1, g.Nz}, es[6] = {g.Nx - W + 1, g.Nx, 1, g.Ny, 1, g.Nz};
     auto tend = [&](const int *range) {
-        return compute_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, range,
-                                  m->tendency_impl, sub);
+        return compute_tendencies(m->opt, g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, range,
+                                  m->opt.tendency_impl, sub);
     };
     if ((rc = tend(interior))) return rc;                                  // ... while the halos fly (:27-67)
     if ((rc = ocn_dist_exchange_wait(dm->dist))) return rc;                // synchronize_communication! (distributed_fields.jl:71-88)
@@ -768,7 +764,7 @@ extern "C" int ocn_dist_model_create_partition(ocn_model_t *model, ocn_grid_t lo
     return dist_model_create(model, local_grid, ntracers, dist, Lx_global, local_sizes, global_x_topology);
 }
 
-static int gathered_solve_create(DistModel *dm, ocn_grid_t local_grid, double Lx_global, const int *sizes, int global_tx, double Ly_global,
+static int gathered_solve_create(DistModel *dm, const OcnOptions *opt, ocn_grid_t local_grid, double Lx_global, const int *sizes, int global_tx, double Ly_global,
                                  const int *sizes_y, int global_ty) {
     const DGrid &g = local_grid->d;
     const int R = dm->dist->Rx, Ry = dm->dist->Ry, ix = dm->dist->rank / Ry, iy = dm->dist->rank % Ry;
@@ -799,7 +795,7 @@ static int gathered_solve_create(DistModel *dm, ocn_grid_t local_grid, double Lx
     int rc = ocn_grid_create(&q->ggrid, N, H, topo, L, Lx_global / (double)q->Nxg, Ry > 1 ? Ly_global / (double)q->Nyg : g.dy, local_grid->h_dzc[g.Hz],
                              zr ? nullptr : local_grid->h_dzc.data(), zr ? nullptr : local_grid->h_dzf.data());
     if (rc) return rc;
-    if ((rc = ocn_poisson_create(&q->solver, q->ggrid, -1))) return rc;
+    if ((rc = poisson_create(&q->solver, q->ggrid, -1, opt))) return rc;
     int P[3];
     parent_size(q->ggrid->d, LOC_C, P);
     const size_t piece = (size_t)q->nmax * q->nymax * g.Nz;
@@ -815,8 +811,8 @@ static int gathered_solve_create(DistModel *dm, ocn_grid_t local_grid, double Lx
 // the pressure step without fills / copies between its stages (ocn_kernels.h "Round 3"): a partitioned (connected, Periodic, *) slab with one
 // of the accelerated solvers -- the substructured ones (z Periodic: every field shares one parent shape, which the wrapped pack relies on)
 // or the transposing ones (z Periodic or Bounded: the solution stays in their dense paired-column array)
-static int dist_enable_fused_step(DistModel *dm, const DGrid &g, bool part) {
-    if (!(g_dist_fused_step && part && g.ty == OCN_PERIODIC && g.Nx >= 2 && (g.tz == OCN_PERIODIC || g.tz == OCN_BOUNDED))) return OCN_OK;
+static int dist_enable_fused_step(const OcnOptions &o, DistModel *dm, const DGrid &g, bool part) {
+    if (!(o.fused_step && part && g.ty == OCN_PERIODIC && g.Nx >= 2 && (g.tz == OCN_PERIODIC || g.tz == OCN_BOUNDED))) return OCN_OK;
     if (dm->solver->sub && (g.tz != OCN_PERIODIC || !(dm->solver->zfirst || dm->solver->xfast))) return OCN_OK;    // (the paired-column substructured layout keeps the unfused step)
     const size_t col = (size_t)g.Ny * g.Nz * sizeof(double);
     double **cb[4] = {&dm->cws, &dm->ces, &dm->cwr, &dm->cer};
@@ -825,7 +821,6 @@ static int dist_enable_fused_step(DistModel *dm, const DGrid &g, bool part) {
         if (e != hipSuccess) return fail((int)e, "dev_alloc(column buffers): %s", hipGetErrorString(e));
         hipMemsetAsync(*b, 0, col, g_stream);
     }
-    dm->fused_step = true;
     return OCN_OK;
 }
 
@@ -893,7 +888,7 @@ static int dist_model_create(ocn_model_t *model, ocn_grid_t local_grid, int ntra
     // Partition(Rx, Ry) pencils of a triply Periodic regular grid with equal blocks that the reference's transposes can move
     // (distributed_fft_based_poisson_solver.jl:213-226): its DistributedFFTBasedPoissonSolver (z / y / x transforms with two transposes
     // each way); every other pencil keeps the gathered solve
-    if (pencil && g_dist_pencil_transposes && !irregular && global_x_topology == OCN_PERIODIC && global_y_topology == OCN_PERIODIC &&
+    if (pencil && m->opt.dist_pencil_transposes && !irregular && global_x_topology == OCN_PERIODIC && global_y_topology == OCN_PERIODIC &&
         g.tz == OCN_PERIODIC && local_grid->z_regular) {
         bool equal_y = true;
         if (sizes_y)
@@ -908,11 +903,11 @@ static int dist_model_create(ocn_model_t *model, ocn_grid_t local_grid, int ntra
     if (irregular || dm->general()) {
         if (dist->self_loop) return bail(fail(OCN_EINVAL, "self_loop has one slab"));
         std::vector<int> equal((size_t)Rx, g.Nx);
-        if ((rc = gathered_solve_create(dm, local_grid, Lx_global, local_sizes ? local_sizes : equal.data(), global_x_topology, Ly_global, sizes_y, global_y_topology)))
+        if ((rc = gathered_solve_create(dm, &m->opt, local_grid, Lx_global, local_sizes ? local_sizes : equal.data(), global_x_topology, Ly_global, sizes_y, global_y_topology)))
             return bail(rc);
         return OCN_OK;
     }
-    if ((rc = ocn_dist_poisson_create(&dm->solver, local_grid, dist->world, dist->rank, Lx_global))) return bail(rc);
+    if ((rc = dist_poisson_create(&dm->solver, local_grid, dist->world, dist->rank, Lx_global, &m->opt))) return bail(rc);
     size_t n = 0;
     ocn_dist_poisson_payload_size(dm->solver, &n);
     if (n) {
@@ -923,7 +918,7 @@ static int dist_model_create(ocn_model_t *model, ocn_grid_t local_grid, int ntra
         hipMemsetAsync(dm->buf_a, 0, 2 * n * sizeof(double), g_stream);
         hipMemsetAsync(dm->buf_b, 0, 2 * n * sizeof(double) * (size_t)dist->world, g_stream);
         if ((rc = ocn_dist_poisson_set_gather_buffers(dm->solver, dm->buf_a, dm->buf_b))) return bail(rc);
-        if ((rc = dist_enable_fused_step(dm, g, part))) return bail(rc);
+        if ((rc = dist_enable_fused_step(m->opt, dm, g, part))) return bail(rc);
     } else {
         ocn_dist_poisson_buffer_size(dm->solver, &n);
         dm->nbuf = n;
@@ -935,37 +930,23 @@ static int dist_model_create(ocn_model_t *model, ocn_grid_t local_grid, int ntra
         hipMemsetAsync(dm->buf_a, 0, 2 * n * sizeof(double), g_stream);
         if (dm->buf_b != dm->buf_a) hipMemsetAsync(dm->buf_b, 0, 2 * n * sizeof(double), g_stream);
         if ((rc = ocn_dist_poisson_set_buffers(dm->solver, dm->buf_a, dm->buf_b))) return bail(rc);
-        if ((rc = dist_enable_fused_step(dm, g, part))) return bail(rc);
+        if ((rc = dist_enable_fused_step(m->opt, dm, g, part))) return bail(rc);
     }
     return OCN_OK;
 }
 
-static int dist_model_set_option(ocn_model_s *m, const char *key, int value) {
-    DistModel *dm = m->dm;
-    if (!dm) return -1;
-    if (!strcmp(key, "async_halos")) { dm->async_halos = value; return OCN_OK; }
-    if (!strcmp(key, "thin_halos")) { dm->thin_halos = value; return OCN_OK; }
-    if (!strcmp(key, "early_exchange")) { dm->early_exchange = value; return OCN_OK; }
-    if (!strcmp(key, "strip_width")) { dm->strip_width = value; return OCN_OK; }
-    if (!strcmp(key, "fused_step")) {
-        if (value && !dm->cws) return fail(OCN_ENOTSUP, "fused_step needs a (connected, Periodic, Periodic) slab with the z-fastest substructured solver");
-        dm->fused_step = value != 0;
-        return OCN_OK;
-    }
-    return -1;
-}
+// option fused_step on a partitioned model: the column buffers exist when the model was created with it on a slab that takes it
+static bool dist_fused_step_buffers(const ocn_model_s *m) { return m->dm && m->dm->cws; }
 
+// the model options that depend on the partition: whether the fused pressure step runs (0 on a single-GPU model) and which distributed
+// pressure solver the model runs -- ocn_dist_poisson_layout's code (4 x-fastest, 1..3 z-fastest, 0 paired columns, -1 transposing),
+// -2 = the gathered solve on the global grid, -3 = the pencil transposes (TransposableField)
 static int dist_model_get_option(const ocn_model_s *m, const char *key, int *value) {
     const DistModel *dm = m->dm;
-    if (!dm) return -1;
-    // which distributed pressure solver the model runs: ocn_dist_poisson_layout's code (4 x-fastest, 1..3 z-fastest, 0 paired columns,
-    // -1 transposing), -2 = the gathered solve on the global grid, -3 = the pencil transposes (TransposableField)
-    if (!strcmp(key, "dist_poisson_layout")) { *value = dm->gs ? -2 : (dm->ps ? -3 : -1); return dm->solver ? ocn_dist_poisson_layout(dm->solver, value) : OCN_OK; }
-    if (!strcmp(key, "fused_step")) { *value = dm->fused() ? 1 : 0; return OCN_OK; }
-    if (!strcmp(key, "async_halos")) { *value = dm->async_halos; return OCN_OK; }
-    if (!strcmp(key, "thin_halos")) { *value = dm->thin_halos; return OCN_OK; }
-    if (!strcmp(key, "early_exchange")) { *value = dm->early_exchange; return OCN_OK; }
-    return -1;
+    if (!strcmp(key, "fused_step")) { *value = dm && dm->fused(m->opt) ? 1 : 0; return OCN_OK; }
+    if (!dm || strcmp(key, "dist_poisson_layout")) return -1;
+    *value = dm->gs ? -2 : (dm->ps ? -3 : -1);
+    return dm->solver ? ocn_dist_poisson_layout(dm->solver, value) : OCN_OK;
 }
 
 // global maximum of |div u| (test helper of the partitioned model)

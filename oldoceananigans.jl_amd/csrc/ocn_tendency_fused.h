@@ -19,6 +19,7 @@
 // The arithmetic of every flux is the same IEEE sequence as the per-field kernels => results are bit-identical.
 #pragma once
 #include "ocn_device.h"
+#include "ocn_options.h"
 
 #define OCN_FUSED_MAXTR 8
 
@@ -340,10 +341,6 @@ static inline bool fused_tendency_size_supported(const DGrid &g) {
     return 8.0 * (g.Nx + 2.0 * g.Hx) * (g.Ny + 2.0 * g.Hy) * (g.Nz + 2.0 * g.Hz + 1.0) < 4294967296.0;
 }
 
-// tuned on MI355X at 256^3 (tools/tune_fused.py): 64 x 7 tiles, register z-windows, 2 waves/SIMD (no spills);
-// kchunk = 0: levels per workgroup chosen per launch so that the grid fills whole rounds of the chip (see pick_kchunk)
-static int g_fused_ty = 7, g_fused_kchunk = 0, g_fused_minw = 2, g_fused_zwin = 1;
-static int g_fused_xcd = 0;     // XCD-aware tile order (FusedArgs::xcd_swizzle): measured 1.445 vs 1.440 ms at 256^3 -- no effect, off
 static int g_num_cus = 256;
 
 // Each workgroup primes 3 planes before its first cell closes, and the grid runs in rounds of one workgroup per CU (2 waves
@@ -362,7 +359,7 @@ static inline int pick_kchunk(int tiles_xy, int nz) {
 
 
 template <int NTR, int TY>
-static int launch_fused_t(const DGrid &g, hipStream_t stream, FusedArgs &a) {
+static int launch_fused_t(const OcnOptions &o, const DGrid &g, hipStream_t stream, FusedArgs &a) {
     const int nx = a.r.i1 - a.r.i0 + 1, ny = a.r.j1 - a.r.j0 + 1, nz = a.r.k1 - a.r.k0 + 1;
     if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
     if (a.kchunk <= 0) a.kchunk = pick_kchunk(((nx + 63) / 64) * ((ny + TY - 1) / TY), nz);
@@ -371,7 +368,7 @@ static int launch_fused_t(const DGrid &g, hipStream_t stream, FusedArgs &a) {
 #define OCN_LAUNCH_FUSED(BZV, MWV, ZWV) hipLaunchKernelGGL((fused_tendency_kernel<NTR, TY, BZV, MWV, ZWV>), grid, blk, 0, stream, g, a)
     // waves per SIMD the register allocator must allow without the register z-windows: two (TY+1)-wave workgroups per CU
     constexpr int MW2 = (2 * (TY + 1) + 3) / 4;
-    if (g_fused_zwin) {
+    if (o.fused_zwin) {
         if (g.tz != 0) OCN_LAUNCH_FUSED(true, 2, true); else OCN_LAUNCH_FUSED(false, 2, true);
     } else {
         if (g.tz != 0) OCN_LAUNCH_FUSED(true, MW2, false); else OCN_LAUNCH_FUSED(false, MW2, false);
@@ -392,7 +389,7 @@ struct FusedSubstep {
     bool store_G = true;
 };
 
-static inline int launch_fused_tendency(const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w,
+static inline int launch_fused_tendency(const OcnOptions &o, const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w,
                                         const double *const *tr, int ntr, double *Gu, double *Gv, double *Gw,
                                         double *const *Gc, const int *range, const FusedSubstep *sub = nullptr) {
     FusedArgs a;
@@ -416,12 +413,12 @@ static inline int launch_fused_tendency(const DGrid &g, hipStream_t stream, cons
         a.ru = a.rv = a.rc = a.r;
         a.rw = Range6{1, g.Nx, 1, g.Ny, 1 + ofs, g.Nz};
     }
-    a.kchunk = g_fused_kchunk;
-    a.xcd_swizzle = g_fused_xcd;
+    a.kchunk = o.fused_kchunk;
+    a.xcd_swizzle = o.fused_xcd;
 #define OCN_FUSED_CASE(NTR)                                                          \
     case NTR:                                                                        \
-        if (g_fused_ty == 3) return launch_fused_t<NTR, 3>(g, stream, a);            \
-        return launch_fused_t<NTR, 7>(g, stream, a);
+        if (o.fused_ty == 3) return launch_fused_t<NTR, 3>(o, g, stream, a);         \
+        return launch_fused_t<NTR, 7>(o, g, stream, a);
     switch (ntr) {
         OCN_FUSED_CASE(0)
         OCN_FUSED_CASE(1)

@@ -460,14 +460,10 @@ __global__ void __launch_bounds__(64 * (TY + 1), OCN_ROLE_WAVES) role_tendency_k
 // is 2 GiB) relative to the lowest plane of the workgroup's chunk: (kchunk + 3 below + 4 of look-ahead + 1) planes + the row / column offsets
 // must stay below 2^31 -- a limit on the PLANE size (29 MB at the largest chunk: 1900 x 1900 points), not on the array (a single-GPU
 // 1024 x 1024 x 256 grid, 2.2 GB per field, took the slower all-fields kernel before round 3's per-workgroup descriptor base).
-static int g_role_kchunk = 0;      // 0: automatic
-static inline bool role_tendency_supported(const DGrid &g) {
+static inline bool role_tendency_supported(const OcnOptions &o, const DGrid &g) {
     const double plane = 8.0 * (g.Nx + 2.0 * g.Hx) * (g.Ny + 2.0 * g.Hy);
-    return plane * ((g_role_kchunk > 0 ? g_role_kchunk : 64) + 8.0) < 2147483648.0;
+    return plane * ((o.role_kchunk > 0 ? o.role_kchunk : 64) + 8.0) < 2147483648.0;
 }
-
-static int g_arithmetic = 0;       // 0: the reference's operation sequence (bit-identical to the oracle); 1: contracted WENO flux (ocn_device.h)
-static int g_role_ldspad = 0;      // experiments: extra dynamic LDS per workgroup (bytes) to limit the workgroups per CU
 
 // Work per launch in plane-iterations: blocks x (kchunk + 1) spread over the resident workgroups (3 per CU at <= 80 VGPRs); smaller chunks balance the
 // tail, every chunk pays one extra z-flux plane and the window priming loads.
@@ -488,26 +484,26 @@ static inline int pick_role_kchunk(long tiles_roles, int nz) {
 }
 
 template <int NTR, int TY>
-static int launch_roles_t(const DGrid &g, hipStream_t stream, RoleArgs<3 + NTR> &a, bool sub) {
+static int launch_roles_t(const OcnOptions &o, const DGrid &g, hipStream_t stream, RoleArgs<3 + NTR> &a, bool sub) {
     constexpr int NF = 3 + NTR;
     const int nx = a.r.i1 - a.r.i0 + 1, ny = a.r.j1 - a.r.j0 + 1, nz = a.r.k1 - a.r.k0 + 1;
     if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
     a.ntile_x = (nx + 63) / 64;
     a.ntile = a.ntile_x * ((ny + TY - 1) / TY);
-    a.kchunk = g_role_kchunk > 0 ? g_role_kchunk : pick_role_kchunk((long)a.ntile * NF, nz);
+    a.kchunk = o.role_kchunk > 0 ? o.role_kchunk : pick_role_kchunk((long)a.ntile * NF, nz);
     const int nchunk = (nz + a.kchunk - 1) / a.kchunk;
     a.npair = a.ntile * nchunk;
     a.band = (a.npair + 7) / 8;
     const unsigned nblocks = (unsigned)a.band * 8u * NF;
     const dim3 blk(64 * (TY + 1));
-#define OCN_LAUNCH_ROLES(BZV, SUBV, AR) hipLaunchKernelGGL((role_tendency_kernel<NTR, TY, BZV, SUBV, AR>), dim3(nblocks), blk, (size_t)g_role_ldspad, stream, g, a)
-#define OCN_LAUNCH_ROLES_F(BZV, SUBV) hipLaunchKernelGGL((role_tendency_kernel<NTR, TY, BZV, SUBV, 0, true>), dim3(nblocks), blk, (size_t)g_role_ldspad, stream, g, a)
+#define OCN_LAUNCH_ROLES(BZV, SUBV, AR) hipLaunchKernelGGL((role_tendency_kernel<NTR, TY, BZV, SUBV, AR>), dim3(nblocks), blk, (size_t)o.role_ldspad, stream, g, a)
+#define OCN_LAUNCH_ROLES_F(BZV, SUBV) hipLaunchKernelGGL((role_tendency_kernel<NTR, TY, BZV, SUBV, 0, true>), dim3(nblocks), blk, (size_t)o.role_ldspad, stream, g, a)
     if (a.ftab) {
         // forcing term in the kernel: reference arithmetic and a Periodic z only (the caller checks both). The Bounded-z instantiation with
         // the substep riding along needs 3 VGPRs more than OCN_ROLE_WAVES = 6 leaves and spilled to scratch: it is not built
-        if (g_arithmetic != 0 || g.tz != 0) return -2;
+        if (o.arithmetic != 0 || g.tz != 0) return -2;
         if (sub) OCN_LAUNCH_ROLES_F(false, true); else OCN_LAUNCH_ROLES_F(false, false);
-    } else if (g_arithmetic == 1) {          // the opt-in contracted arithmetic of the WENO flux (ocn_device.h; option "arithmetic")
+    } else if (o.arithmetic == 1) {          // the opt-in contracted arithmetic of the WENO flux (ocn_device.h; option "arithmetic")
         if (g.tz != 0) { if (sub) OCN_LAUNCH_ROLES(true, true, 1); else OCN_LAUNCH_ROLES(true, false, 1); }
         else           { if (sub) OCN_LAUNCH_ROLES(false, true, 1); else OCN_LAUNCH_ROLES(false, false, 1); }
     } else {
@@ -520,7 +516,7 @@ static int launch_roles_t(const DGrid &g, hipStream_t stream, RoleArgs<3 + NTR> 
 }
 
 template <int NTR>
-static int launch_roles_n(const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w, const double *const *tr,
+static int launch_roles_n(const OcnOptions &o, const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w, const double *const *tr,
                           double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range, const FusedSubstep *sub,
                           const ForcingTable *ftab) {
     constexpr int NF = 3 + NTR;
@@ -543,17 +539,17 @@ static int launch_roles_n(const DGrid &g, hipStream_t stream, const double *u, c
         a.r = Range6{1, g.Nx, 1, g.Ny, 1, g.Nz};
         a.wk0 = (g.tz != 0 && g.Nz > 1) ? 2 : 1;          // exclude_periphery: w tendencies start at k = 2 on Bounded z
     }
-    return launch_roles_t<NTR, OCN_ROLE_TY>(g, stream, a, sub != nullptr);
+    return launch_roles_t<NTR, OCN_ROLE_TY>(o, g, stream, a, sub != nullptr);
 }
 
-static inline int launch_role_tendency(const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w,
+static inline int launch_role_tendency(const OcnOptions &o, const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w,
                                        const double *const *tr, int ntr, double *Gu, double *Gv, double *Gw, double *const *Gc,
                                        const int *range, const FusedSubstep *sub = nullptr, const ForcingTable *ftab = nullptr) {
     switch (ntr) {
-        case 0: return launch_roles_n<0>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
-        case 1: return launch_roles_n<1>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
-        case 2: return launch_roles_n<2>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
-        case 3: return launch_roles_n<3>(g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
+        case 0: return launch_roles_n<0>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
+        case 1: return launch_roles_n<1>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
+        case 2: return launch_roles_n<2>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
+        case 3: return launch_roles_n<3>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
         default: return -2;
     }
 }

@@ -194,6 +194,8 @@ class NonhydrostaticModel:
         return d
 
     def set_option(self, key, value):
+        """a tuning option of this model only (include/ocn_mi355x.h: ocn_set_option lists the keys); options read when the model is
+        built raise OcnError here: set them with architectures.set_option before creating the model"""
         _lib.check(_lib.lib().ocn_model_set_option(self.handle, key.encode(), int(value)))
 
     def get_option(self, key):

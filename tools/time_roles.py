@@ -16,7 +16,7 @@ flds = model.fields()
 ocn.set_model(model, **smooth_state({n: grid.nodes(f.loc) for n, f in flds.items()}, 1234))
 model.set_option("tendency_impl", 2)
 arith = int(os.environ.get("OCN_ARITHMETIC", "0"))      # 1: the opt-in contracted WENO flux
-ocn.set_option("arithmetic", arith)
+model.set_option("arithmetic", arith)
 model.set_option("role_kchunk", kc)
 for _ in range(5): ocn.update_state(model, True)
 ocn.synchronize()
