@@ -309,8 +309,14 @@ int ocn_model_set_clock(ocn_model_t model, double time, int64_t iteration, int s
 /* max |∇·u| over the interior (test helper: test/test_time_stepping.jl:124-160); synchronous */
 int ocn_model_max_abs_divergence(ocn_model_t model, double *value);
 /* cell_advection_timescale(grid, velocities) (Advection/cell_advection_timescale.jl:13-34): min over cells of
- * 1 / (|u|/Δx + |v|/Δy + |w|/Δz) -- what TimeStepWizard multiplies by the CFL number. Synchronous. */
+ * 1 / (|u|/Δx + |v|/Δy + |w|/Δz) -- what TimeStepWizard multiplies by the CFL number. Synchronous.
+ * The raw-pointer form knows no model and no communicator: it reduces over the cells of `grid` only -- on the local grid of a
+ * partitioned model that is the rank's own timescale, not the global one. */
 int ocn_cell_advection_timescale(ocn_grid_t grid, const double *u, const double *v, const double *w, double *tau);
+/* The model form on a partitioned model (ocn_dist_model_create*) returns the minimum over ALL ranks, like the reference's all-reduce
+ * (DistributedComputations/distributed_fields.jl:144-196): the maximum of the inverse timescale crosses the model's communicator
+ * before the one divide, so every rank gets the bits of the serial model on the global grid. There the call is COLLECTIVE: every
+ * rank of the communicator has to make it. */
 int ocn_model_cell_advection_timescale(ocn_model_t model, double *tau);
 /* hasnan(field) = any(isnan, parent(field)) (Diagnostics/nan_checker.jl:32): `n` doubles starting at `data` (the whole parent
  * array, halos included); *result = 1 if any is NaN */

@@ -3410,9 +3410,8 @@ extern "C" int ocn_debug_permute_indices(int N, int backward, int *destination) 
     return OCN_OK;
 }
 
-extern "C" int ocn_cell_advection_timescale(ocn_grid_t grid, const double *u, const double *v, const double *w, double *tau) {
-    NEED_INIT();
-    if (!grid || !u || !v || !w || !tau) return fail(OCN_EINVAL, "NULL argument");
+// maximum over the cells 1..Nx x 1..Ny x 1..Nz of `grid` of the inverse advective timescale |u| Δx⁻¹ + |v| Δy⁻¹ + |w| Δzᶠ⁻¹
+static int max_inverse_advection_timescale(ocn_grid_t grid, const double *u, const double *v, const double *w, double *value) {
     const DGrid &g = grid->d;
     const int nb = 1024;
     double *blockmax;
@@ -3422,14 +3421,34 @@ extern "C" int ocn_cell_advection_timescale(ocn_grid_t grid, const double *u, co
     double m = 0;
     int rc = reduce_blockmax(blockmax, nb, &m);
     hipFree(blockmax);
+    *value = m;
+    return rc;
+}
+
+// the cells of `grid` only: on the local grid of a partitioned model this is the rank's own timescale (no model, no communicator here)
+extern "C" int ocn_cell_advection_timescale(ocn_grid_t grid, const double *u, const double *v, const double *w, double *tau) {
+    NEED_INIT();
+    if (!grid || !u || !v || !w || !tau) return fail(OCN_EINVAL, "NULL argument");
+    double m = 0;
+    int rc = max_inverse_advection_timescale(grid, u, v, w, &m);
     if (rc) return rc;
     *tau = 1.0 / m;              // Inf for a fluid at rest, like the reference's 1 / 0
     return OCN_OK;
 }
 
+// on a partitioned model the minimum over ALL ranks (the reference all-reduces, distributed_fields.jl:144-196): the MAXIMUM of the inverse
+// timescale crosses the communicator before the one divide, so every rank returns the bits the serial model returns on the global grid
+// (the ranks' cells 1..Nx x 1..Ny x 1..Nz tile the global ones; the wall face Nx + 1 of a LeftConnected rank carries no flow).
+// Collective there: every rank of the model's communicator makes the call.
 extern "C" int ocn_model_cell_advection_timescale(ocn_model_t m, double *tau) {
-    if (!m) return fail(OCN_EINVAL, "NULL argument");
-    return ocn_cell_advection_timescale(m->grid, m->U[0], m->U[1], m->U[2], tau);
+    NEED_INIT();
+    if (!m || !tau) return fail(OCN_EINVAL, "NULL argument");
+    double inv = 0;
+    int rc = max_inverse_advection_timescale(m->grid, m->U[0], m->U[1], m->U[2], &inv);
+    if (rc) return rc;
+    if (m->dm && (rc = ocn_dist_allreduce_max(m->dm->dist, &inv))) return rc;
+    *tau = 1.0 / inv;
+    return OCN_OK;
 }
 
 extern "C" int ocn_hasnan(const double *data, size_t n, int *result) {

@@ -15,7 +15,8 @@ from .grids import Flat
 
 
 def cell_advection_timescale(model):
-    """min over cells of 1 / (|u|/Δx + |v|/Δy + |w|/Δz); on a distributed model the minimum over ranks"""
+    """min over cells of 1 / (|u|/Δx + |v|/Δy + |w|/Δz); on a distributed model the minimum over ranks: the library all-reduces the
+    maximum inverse timescale before the divide (the serial model's bits on every rank), so the call is collective there"""
     tau = C.c_double()
     _lib.check(_lib.lib().ocn_model_cell_advection_timescale(model.handle, C.byref(tau)))
     return tau.value

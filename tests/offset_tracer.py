@@ -15,7 +15,8 @@ because that state shows a property of the REFERENCE's WENO formulation that no 
 
 Consequence: north_star's "1e-12 relative" holds for u, v, w, T (and for S once it varies generically, helpers.smooth_state) but NOT for
 the survey's S on directions of N >~ 64 points -- in ANY implementation, the reference's included: two exact-arithmetic-equivalent
-evaluations (rocFFT vs the oracle's FFT, substructured vs single-GPU pressure solve) differ by `offset_tracer_bound`, not by 1e-12."""
+evaluations (rocFFT vs the oracle's FFT, substructured vs single-GPU pressure solve) differ by what the oracle itself moves under a last-bit
+perturbation (`measured_offset_tracer_bound`, measured at the test's own size; `offset_tracer_bound` is its upper envelope), not by 1e-12."""
 import numpy as np
 
 
@@ -45,13 +46,66 @@ def offset_tracer_bound(size, nsteps, offset=35.0):
 
         4e-12 * (N / 32)^2 * nsteps * (offset / 35)
 
-    EMPIRICAL: fitted with a margin of >= 2 to the oracle's own sensitivity to a last-bit perturbation of the initial velocities
-    (8.6e-13 at 32^3, 2.6e-12 at 64^3, 2.9e-12 .. 4.5e-12 on 32 x 128 x 128, 1.4e-12 .. 5.1e-12 on 16 x 256 x 256 over 1 .. 3 steps:
-    tests/test_offset_tracer_sensitivity.py) and to the difference between the partitioned and the single-GPU pressure solver on the
-    64 x 512 x 512 slab of configs[3] (5e-11 after one step, 7e-10 after three: tools/diag_slab.py, round 2). The relative error grows
-    in proportion to the offset (absolute: to its square -- beta's round-off is eps * S0^2)."""
+    UPPER ENVELOPE, see the measured bound: the tests that compare two evaluations assert `measured_offset_tracer_bound` -- the oracle's own
+    sensitivity at the test's size -- and only check that it stays below this formula, which is 6 (64^3) to 900 (64 x 512 x 512) times
+    the oracle's sensitivity. The relative error grows in proportion to the offset (absolute: to its square -- beta's round-off is
+    eps * S0^2)."""
     N = max(size)
     return 4e-12 * (N / 32.0) ** 2 * nsteps * (abs(offset) / 35.0)
+
+
+ORACLE_NAMES = {"u": "u", "v": "v", "w": "w", "T": "c0", "S": "c1"}
+
+
+def oracle_run(O, size, nsteps, vals, ulp=0.0, seed=7):
+    """`nsteps` RK3 steps of the oracle on the triply periodic unit cube from `vals` (interior arrays of u, v, w, T, S) at
+    dt = 0.1 / max(size) / 0.6; with `ulp` every initial velocity value is multiplied by 1 +- ulp (signs drawn from `seed`).
+    Returns the interiors of the five fields after every step."""
+    g = O.Grid(size)
+    m = O.Model(g, 2)
+    v = {k: a.copy() for k, a in vals.items()}
+    if ulp:
+        rng = np.random.default_rng(seed)
+        for k in ("u", "v", "w"):
+            v[k] = v[k] * (1.0 + ulp * rng.choice([-1.0, 1.0], v[k].shape))
+    m.set(**{ORACLE_NAMES[k]: a for k, a in v.items()})
+    dt = 0.1 / max(size) / 0.6
+    out = []
+    for _ in range(nsteps):
+        m.time_step(dt)
+        out.append({k: g.interior_cells(m.field(n)).copy() for k, n in ORACLE_NAMES.items()})
+    return out
+
+
+def oracle_sensitivity(O, size, nsteps, vals, seed=7, baseline=None):
+    """relative movement (max |da| / max |a|) of every field after each step when the initial velocities move by one unit in the last
+    place; `baseline`: the unperturbed run (what `oracle_run` returns; fields it does not hold are skipped), made here when not given"""
+    a = oracle_run(O, size, nsteps, vals) if baseline is None else baseline
+    b = oracle_run(O, size, nsteps, vals, ulp=2.0 ** -52, seed=seed)
+    return [{k: float(np.abs(a[s][k] - b[s][k]).max() / np.abs(a[s][k]).max()) for k in a[s]} for s in range(nsteps)]
+
+
+def measured_offset_tracer_bound(oracle, size, nsteps, state, seeds=(7, 8), margin=4.0, baseline=None):
+    """the bound on S measured on the ORACLE at the test's own size: `margin` x the largest relative movement of S after `nsteps` steps
+    over one last-bit perturbation of the initial velocities per seed. Returns (bound, raw movements, one per seed).
+
+    margin = 4: what the tests compare (rocFFT against the oracle's FFT in three pressure solves per step; a substructured against an FFT x
+    solve) is several round-off-level perturbations, not one, and the maximum over 1.7e7 cells scatters by up to 50 % between seeds
+    (3.3e-12 / 4.9e-12 at 256^3, seeds 7 / 8)."""
+    if baseline is None:
+        baseline = oracle_run(oracle, size, nsteps, state)
+    raw = [oracle_sensitivity(oracle, size, nsteps, state, seed=s, baseline=baseline)[nsteps - 1]["S"] for s in seeds]
+    return margin * max(raw), raw
+
+
+def check_offset_tracer(S, S_ref, measured, size, nsteps, offset=35.0):
+    """the comparison the full-size tests share: S against S_ref within the MEASURED bound, and the measured bound below the formula (so
+    nothing that failed before the bound was measured can pass now). Returns the error."""
+    err = float(np.abs(S - S_ref).max() / np.abs(S_ref).max())
+    formula = offset_tracer_bound(size, nsteps, offset)
+    assert measured <= formula, (measured, formula)
+    assert err <= measured, (err, measured, formula)
+    return err
 
 
 def cell_nodes(size, extent=(1.0, 1.0, 1.0)):

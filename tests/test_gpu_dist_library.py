@@ -5,7 +5,13 @@ ocn_model_time_step on a distributed model) -- the product's N > 1 path.
     path runs through ncclSend / ncclRecv / ncclAllGather on the one-GPU box, against the single-GPU model;
   * with R virtual ranks (threads sharing the card) over the caller-supplied transport (ocn_dist_create_transport, tests/loopback.py),
     against the single-GPU model: same-peer case R = 2, R = 4, odd local sizes, Bounded / stretched z (transposing
-    Fourier-tridiagonal solver), the configs[4] physics.
+    Fourier-tridiagonal solver), the configs[4] physics;
+  * DIRECTLY AGAINST THE SERIAL ORACLE on the global grid (_compare_with_oracle; test_gpu_distributed._serial_oracle restates each preset's
+    closure, buoyancy, Coriolis and boundary conditions on the CPU): every rank's slab of u, v, w, T, S and p to 1e-12 and the clock `==`, in
+    the self-loop, virtual-rank, irregular, Bounded-partition, pencil and seeded-random cases -- HIP against HIP alone would pass a defect the
+    partitioned and the single-GPU path share (same tendency kernels, same epilogue, same boundary-condition code);
+  * the advective timescale of a partitioned model is the global one on every rank (all-reduced inside the library), bit-identical to the
+    single-GPU model and the oracle, and a TimeStepWizard keeps the ranks' clocks together.
 
 Reference tests mirrored: test_distributed_models.jl:334-404 (rank ids in the halos), test_distributed_poisson_solvers.jl:70-163 and
 the distributed-vs-serial agreement of test_distributed_models.jl."""
@@ -16,7 +22,7 @@ import numpy as np
 import pytest
 
 from dist_worker import analytic
-from test_gpu_distributed import _bcs, _closure, _tracers_and_buoyancy, _z_and_topology
+from test_gpu_distributed import _bcs, _closure, _serial_oracle, _tracers_and_buoyancy, _z_and_topology
 
 pytestmark = pytest.mark.gpu
 
@@ -56,23 +62,36 @@ def _library_model(ocn, dist, ctx, size, zkind, xbounded=False, ybounded=False, 
     return grid, model
 
 
-def _compare(out, ref, r, nxl, size, offset=None, joffset=0):
+def _compare(out, ref, r, nxl, size, offset=None, joffset=0, against="single-GPU model"):
+    """rank r's slab of every array in `out` against the same cells of the global parent arrays `ref`, 1e-12 of the global maximum"""
     i0 = r * nxl if offset is None else offset
     for name, a in out.items():
         n = a.shape[0] - 6                  # nxl, or nxl + 1 for the Face-in-x field of a LeftConnected rank (its wall face)
         want = ref[name][3 + i0:3 + i0 + n, 3 + joffset:3 + joffset + a.shape[1] - 6, 3:3 + a.shape[2] - 6]
         scale = np.abs(ref[name]).max()
         err = np.abs(a[3:-3, 3:-3, 3:-3] - want).max() / scale
-        assert err <= 1e-12, (r, name, err, int(np.isnan(a).sum()))
+        assert err <= 1e-12, (against, r, name, err, int(np.isnan(a).sum()))
+
+
+def _compare_with_oracle(ocn, oracle, results, size, zkind, nsteps, slab, xbounded=False, ybounded=False):
+    """the oracle leg: EVERY rank's slab of u, v, w, T, S and p against the SERIAL ORACLE on the global grid (_serial_oracle: the preset's
+    physics restated on the CPU), 1e-12 of the global maximum, and the clock `==`. `results`: per rank (arrays, divergence, time, ...);
+    `slab(r, result)`: that rank's (width or None, i offset, j offset)."""
+    oref, otime = _serial_oracle(ocn, oracle, size, zkind, nsteps, xbounded, ybounded)
+    for r, res in enumerate(results):
+        nxl, i0, j0 = slab(r, res)
+        assert res[2] == otime, ("oracle clock", r, res[2], otime)
+        assert set(res[0]) == {"u", "v", "w", "T", "S", "p"}
+        _compare(res[0], oref, r, nxl, size, offset=i0, joffset=j0, against=("oracle", size, zkind, xbounded, ybounded))
 
 
 @pytest.mark.parametrize("size,zkind,substructured,async_halos", [
     ((32, 16, 8), "periodic", 1, 1), ((32, 16, 8), "periodic", 0, 1), ((32, 12, 10), "stretched", 1, 1), ((384, 8, 8), "periodic", 1, -1),
     ((32, 16, 8), "periodic", 1, 0)])
-def test_library_self_loop_over_rccl_equals_single_gpu(ocn, arch, size, zkind, substructured, async_halos):
+def test_library_self_loop_over_rccl_equals_single_gpu(ocn, oracle, arch, size, zkind, substructured, async_halos):
     """RCCL communicator of ONE rank that is its own west and east neighbour: pack / ncclSend + ncclRecv on the communication
     stream / unpack, the exchange started from make_pressure_correction!, thin exchanges, ncclAllGather of the interface values (or
-    the two all-to-alls as grouped send / recv) -- the fields equal the single-GPU model's"""
+    the two all-to-alls as grouped send / recv) -- the fields equal the single-GPU model's and the serial oracle's"""
     from oldoceananigans_jl_amd import _lib, distributed as dist
     _own_stream()
     ocn.set_option("dist_substructured", substructured)
@@ -95,6 +114,7 @@ def test_library_self_loop_over_rccl_equals_single_gpu(ocn, arch, size, zkind, s
     finally:
         ocn.set_option("dist_substructured", 1)
     _compare(out, ref, 0, size[0], size)
+    _compare_with_oracle(ocn, oracle, [(out, None, time)], size, zkind, 3, lambda r, res: (size[0], 0, 0))
     for name in ("u", "v", "w", "T", "S"):      # the x halos hold bit-exact copies of the other side's interior columns
         assert np.array_equal(out[name][:3, 3:-3, 3:-3], out[name][-6:-3, 3:-3, 3:-3]), name
 
@@ -134,11 +154,12 @@ def test_library_x_solve_layouts_agree(ocn, arch, size, R):
             _compare(out, ref, r, nxl, size)
 
 
-def test_seeded_random_x_slab_partitions_match_single_gpu(ocn, arch):
+def test_seeded_random_x_slab_partitions_match_single_gpu(ocn, oracle, arch):
     """eight seeded random x-slab runs through the in-library partitioned step (threads sharing the card) against the single-GPU model:
     2 .. 4 ranks, local widths 7 .. 40 (regular: every solver path -- x-fastest / z-fastest substructured, transposing), Ny (a multiple
     of the rank count, distributed_fft_based_poisson_solver.jl:218-226) and Nz at random, one of the four physics presets (triply periodic; Bounded z with ScalarDiffusivity + buoyancy;
-    stretched z with Coriolis and Flux / Value / Gradient conditions; the configs[4] physics), three RK3 steps, 1e-12"""
+    stretched z with Coriolis and Flux / Value / Gradient conditions; the configs[4] physics), three RK3 steps, 1e-12; every drawn case also
+    against the serial oracle"""
     _own_stream()
     rng = np.random.default_rng(31337)
     for case in range(8):
@@ -157,6 +178,7 @@ def test_seeded_random_x_slab_partitions_match_single_gpu(ocn, arch):
                 _compare(out, ref, r, nxl, size)
             except AssertionError as e:
                 raise AssertionError((case, R, size, zkind, str(e)))
+        _compare_with_oracle(ocn, oracle, results, size, zkind, 3, lambda r, res: (nxl, r * nxl, 0))
 
 
 def test_fused_source_term_and_z_transform_is_bit_identical(ocn, arch):
@@ -315,7 +337,8 @@ def _run_library_ranks(ocn, arch, R, size, nsteps, zkind, options, xbounded=Fals
     (8, (64, 8, 8), "stretched", {}),                                   # transposing solver over 8 ranks, Coriolis, boundary conditions
     (4, (32, 12, 10), "amd", {}),                                       # the configs[4] physics
 ])
-def test_library_virtual_ranks_match_single_gpu(ocn, arch, R, size, zkind, options):
+def test_library_virtual_ranks_match_single_gpu(ocn, oracle, arch, R, size, zkind, options):
+    """R virtual ranks of the in-library partitioned model against the single-GPU model AND against the serial oracle"""
     _own_stream()
     nsteps = 3
     results = _run_library_ranks(ocn, arch, R, size, nsteps, zkind, options)
@@ -324,6 +347,7 @@ def test_library_virtual_ranks_match_single_gpu(ocn, arch, R, size, zkind, optio
     for r, (out, div, t, _off) in enumerate(results):
         assert div < 5e-8 and t == time
         _compare(out, ref, r, nxl, size)
+    _compare_with_oracle(ocn, oracle, results, size, zkind, nsteps, lambda r, res: (nxl, r * nxl, 0))
 
 
 @pytest.mark.parametrize("R,size,zkind", [
@@ -332,10 +356,11 @@ def test_library_virtual_ranks_match_single_gpu(ocn, arch, R, size, zkind, optio
     (4, (30, 8, 8), "stretched"),         # 7, 7, 7, 9 columns, stretched z, Coriolis, boundary conditions
     (4, (31, 8, 8), "amd"),               # the configs[4] physics on 7, 7, 7, 10 columns
 ])
-def test_library_irregular_partition_matches_single_gpu(ocn, arch, R, size, zkind):
+def test_library_irregular_partition_matches_single_gpu(ocn, oracle, arch, R, size, zkind):
     """Nx not divisible by the number of ranks: local_size puts the remainder on the last rank (distributed_grids.jl:44-58,
     partition_coordinate partition_assemble.jl:63-76). The halo exchange is unchanged (Hx columns per side whatever the slab width); the
-    pressure solve takes the gathered form (every rank assembles the global source term and runs the single-GPU solver)."""
+    pressure solve takes the gathered form (every rank assembles the global source term and runs the single-GPU solver). Against the
+    single-GPU model and the serial oracle."""
     from oldoceananigans_jl_amd import distributed as dist
     assert dist.local_sizes(25, 3) == [8, 8, 9] and dist.local_sizes(24, 3) == [8, 8, 8] and dist.local_sizes(7, 4) == [1, 1, 1, 4]
     edges = [dist.partition_coordinate((0.0, 2.0), dist.local_sizes(25, 3), 3, r) for r in range(3)]
@@ -348,6 +373,7 @@ def test_library_irregular_partition_matches_single_gpu(ocn, arch, R, size, zkin
     for r, (out, div, t, _off) in enumerate(results):
         assert div < 5e-8 and t == time
         _compare(out, ref, r, sizes[r], size, offset=sum(sizes[:r]))
+    _compare_with_oracle(ocn, oracle, results, size, zkind, nsteps, lambda r, res: (sizes[r], sum(sizes[:r]), 0))
 
 
 @pytest.mark.parametrize("R,size,zkind,ybounded", [
@@ -358,11 +384,12 @@ def test_library_irregular_partition_matches_single_gpu(ocn, arch, R, size, zkin
     (4, (30, 8, 8), "stretched", False),    # stretched z, Coriolis next to the walls, boundary conditions, irregular slabs
     (3, (24, 8, 8), "amd", False),          # the configs[4] physics next to walls
 ])
-def test_library_bounded_partition_matches_single_gpu(ocn, arch, R, size, zkind, ybounded):
+def test_library_bounded_partition_matches_single_gpu(ocn, oracle, arch, R, size, zkind, ybounded):
     """a Bounded partitioned direction: insert_connected_topology (distributed_grids.jl:339-346) gives the first rank a RightConnected
     local grid (wall on its west side), the last one a LeftConnected one (wall on the east side, Nx + 1 x-faces), the others
     FullyConnected; the advection scheme falls back next to the wall side only (topologically_conditional_interpolation.jl:54-70),
-    boundary conditions fill the wall side, the ring has no wrap-around neighbour. Against the single-GPU model on the global grid."""
+    boundary conditions fill the wall side, the ring has no wrap-around neighbour. Against the single-GPU model and the serial oracle on
+    the global grid."""
     _own_stream()
     from oldoceananigans_jl_amd import distributed as dist
     nsteps = 3
@@ -373,6 +400,7 @@ def test_library_bounded_partition_matches_single_gpu(ocn, arch, R, size, zkind,
         assert div < 5e-8 and t == time
         _compare(out, ref, r, sizes[r], size, offset=sum(sizes[:r]))
         assert out["u"].shape[0] == sizes[r] + 6 + (1 if r == R - 1 else 0)
+    _compare_with_oracle(ocn, oracle, results, size, zkind, nsteps, lambda r, res: (sizes[r], sum(sizes[:r]), 0), xbounded=True, ybounded=ybounded)
 
 
 @pytest.mark.parametrize("partition,size,zkind,xbounded", [
@@ -384,11 +412,11 @@ def test_library_bounded_partition_matches_single_gpu(ocn, arch, R, size, zkind,
     ((2, 2), (16, 12, 8), "stretched", True),     # Bounded x + pencils: Right / LeftConnected columns of ranks
 ])
 @pytest.mark.parametrize("ybounded", [False, True])
-def test_library_pencil_partition_matches_single_gpu(ocn, arch, partition, size, zkind, xbounded, ybounded):
+def test_library_pencil_partition_matches_single_gpu(ocn, oracle, arch, partition, size, zkind, xbounded, ybounded):
     """Partition(Rx, Ry) (row (f).4 of SURVEY.md 8: pencil decomposition + corner exchange): rank = ix * Ry + iy
     (distributed_architectures.jl:354-434), local grids connected in x and FullyConnected in y; a fill makes two hops (x, then y over
     the whole x extent) so the corners hold the diagonal neighbours' data like after fill_corners! (halo_communication.jl:137-162) --
-    asserted with rank ids --; the pressure solve is the gathered one. Against the single-GPU model on the global grid.
+    asserted with rank ids --; the pressure solve is the gathered one. Against the single-GPU model and the serial oracle on the global grid.
     ybounded: the partitioned y direction is Bounded -- Right / Fully / LeftConnected rows of ranks (insert_connected_topology,
     distributed_grids.jl:339-346), walls, wall fallbacks and boundary conditions on the first and the last row only, Ny + 1 y-faces on
     the last row -- the (1, 4, 1) and (2, 2, 1) partitions of Bounded topologies in test_distributed_poisson_solvers.jl:123-148."""
@@ -400,12 +428,14 @@ def test_library_pencil_partition_matches_single_gpu(ocn, arch, partition, size,
     for r, (out, div, t, (i0, j0)) in enumerate(results):
         assert div < 5e-8 and t == time
         _compare(out, ref, r, None, size, offset=i0, joffset=j0)
+    _compare_with_oracle(ocn, oracle, results, size, zkind, nsteps, lambda r, res: (None, res[3][0], res[3][1]), xbounded=xbounded, ybounded=ybounded)
 
 
-def test_seeded_random_pencil_and_wall_partitions_match_single_gpu(ocn, arch):
+def test_seeded_random_pencil_and_wall_partitions_match_single_gpu(ocn, oracle, arch):
     """eight seeded random partitions with pencils and / or walls in the partitioned directions: Partition(Rx, Ry) with Rx, Ry in 1 .. 3 (at most
     six ranks share the card), x and y Periodic or Bounded at random, irregular local sizes (remainder on the last rank), one of the four
-    physics presets -- the transposing pencil solver on triply periodic regular cases, the gathered solve elsewhere --, three RK3 steps, 1e-12"""
+    physics presets -- the transposing pencil solver on triply periodic regular cases, the gathered solve elsewhere --, three RK3 steps, 1e-12;
+    every drawn case also against the serial oracle"""
     _own_stream()
     rng = np.random.default_rng(2718)
     done = 0
@@ -429,6 +459,7 @@ def test_seeded_random_pencil_and_wall_partitions_match_single_gpu(ocn, arch):
                 _compare(out, ref, r, None, size, offset=i0, joffset=j0)
             except AssertionError as e:
                 raise AssertionError((done, (Rx, Ry), size, zkind, xb, yb, str(e)))
+        _compare_with_oracle(ocn, oracle, results, size, zkind, 3, lambda r, res: (None, res[3][0], res[3][1]), xbounded=xb, ybounded=yb)
         done += 1
 
 
@@ -791,3 +822,119 @@ def test_library_pencil_models_take_the_transposing_solver(ocn, arch, partition,
         for r, (out, div, t, (i0, j0)) in enumerate(results):
             assert div < 5e-8 and t == time
             _compare(out, ref, r, None, size, offset=i0, joffset=j0)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# cell_advection_timescale / TimeStepWizard on a partitioned model: the GLOBAL timescale on every rank
+# ----------------------------------------------------------------------------------------------------------------------
+def _fast_cells(shapes, where):
+    """zero velocities except one fast cell each of u, v and w (global interior arrays)"""
+    G = {n: np.zeros(s) for n, s in shapes.items()}
+    for n, (cell, value) in where.items():
+        G[n][cell] = value
+    return G
+
+
+@pytest.mark.parametrize("edge", [False, True])
+@pytest.mark.parametrize("R,partition,xbounded", [(2, None, False), (4, None, False), (4, None, True), (4, (2, 2), False)])
+def test_advection_timescale_of_a_partitioned_model_is_global(ocn, oracle, arch, R, partition, xbounded, edge):
+    """cell_advection_timescale(model) on a LibraryDistributedModel is the minimum over ALL ranks (the reference all-reduces,
+    distributed_fields.jl:144-196; with a rank-local value every rank's TimeStepWizard would pick its own Δt and then enter one coupled
+    pressure solve). 32 x 16 x 8 cells, stretched Bounded z, over R = 2 (both neighbours are the same rank), R = 4, a Bounded-x partition
+    and Partition(2, 2); the fluid is at rest except ONE fast cell each of u, v and w that sit on DIFFERENT ranks -- `edge`: the fastest one
+    (u) in the last interior column of its rank. On every rank the value is `==` the single-GPU model's on the global grid `==` the
+    oracle's (a maximum and one divide: the max of the inverse timescale crosses the communicator before the divide; local and global
+    spacings are the same binary fractions here), new_time_step and AdvectiveCFL agree across the ranks, and a fluid at rest gives inf
+    everywhere. The raw-pointer entry ocn_cell_advection_timescale(grid, ...) stays rank-local (what the model call returned before it
+    reduced): equal to the global value on the rank that holds the fastest cell only, so the reduction is what this test sees.
+    Before the model call reduced (measured once on an MI355X): R = 2 -- rank 0 returned 0.0125, the global value, rank 1 0.025 (its own v cell);
+    R = 4 -- 0.0125, inf (a rank at rest), 0.04555130640756422 (the w cell), 0.025; Partition(2, 2) -- 0.0125, inf, 0.025, 0.0455...: all eight
+    cases failed on the ranks that do not hold the u cell."""
+    import ctypes as C
+    from oldoceananigans_jl_amd import _lib
+    _own_stream()
+    size, zkind = (32, 16, 8), "stretched"
+    z, topo = _z_and_topology(ocn, zkind, size[2])
+    topo = _xb(ocn, topo, xbounded)
+    sgrid = ocn.RectilinearGrid(arch, size=size, x=(0.0, 2.0), y=(0.0, 1.0), z=z, topology=topo)
+    smodel = ocn.NonhydrostaticModel(grid=sgrid, tracers=("T", "S"))
+    shapes = {n: sgrid.interior_size(f.loc) for n, f in smodel.fields().items()}
+    Rx, Ry = partition if partition else (R, 1)
+    nxl, nyl = size[0] // Rx, size[1] // Ry
+    # u: rank (ix, iy) = (0, 0), the fastest (5 / Δx = 80); v (2.5 / Δy = 40): the last column of ranks, first row; w: the first column past the
+    # middle, last row -- three different ranks (R = 2: v and w share rank 1)
+    iu = nxl - 1 if edge else 2
+    where = {"u": ((iu, 1, 3), -5.0), "v": ((size[0] - 2, 2, 5), 2.5), "w": ((size[0] // 2 + 1, size[1] - 2, 4), 4.0)}
+    G = _fast_cells(shapes, where)
+    owner = {n: (cell[0] // nxl) * Ry + cell[1] // nyl for n, (cell, _) in where.items()}
+    assert owner["u"] == 0 and owner["v"] != 0 and (R == 2 or len(set(owner.values())) == 3), owner
+    ocn.set_model(smodel, enforce_incompressibility=False, **G)
+    want = ocn.cell_advection_timescale(smodel)
+    g_cpu = oracle.Grid(size, topology=tuple(oracle.BOUNDED if t is ocn.Bounded else oracle.PERIODIC for t in topo), x=(0.0, 2.0), y=(0.0, 1.0), z=z)
+    m_cpu = oracle.Model(g_cpu, 2)
+    m_cpu.set(enforce_incompressibility=False, u=G["u"], v=G["v"], w=G["w"])
+    assert want == m_cpu.cell_advection_timescale() == sgrid.Δxᶜᵃᵃ / 5.0
+    wizard = ocn.TimeStepWizard(cfl=0.3, max_change=np.inf, min_change=0)
+    seen = [None] * R
+
+    def probe(model):
+        grid, rank = model.grid, model.ctx.rank
+        i0, j0 = grid.i_offset, grid.j_offset
+        vals = {}
+        for n, f in model.fields().items():
+            sx, sy, sz = f.interior().shape
+            vals[n] = G[n][i0:i0 + sx, j0:j0 + sy, :sz]
+        ocn.set_model(model, enforce_incompressibility=False, **vals)
+        tau = ocn.cell_advection_timescale(model)
+        local = C.c_double()
+        V = model.velocities
+        _lib.check(_lib.lib().ocn_cell_advection_timescale(grid.local.handle, V.u.data, V.v.data, V.w.data, C.byref(local)))
+        dt, cfl = ocn.new_time_step(1.0, wizard, model), ocn.AdvectiveCFL(0.01)(model)
+        ocn.set_model(model, enforce_incompressibility=False, **{n: np.zeros_like(a) for n, a in vals.items()})
+        seen[rank] = (tau, local.value, dt, cfl, ocn.cell_advection_timescale(model))
+    _run_library_ranks(ocn, arch, R, size, 0, zkind, {}, xbounded=xbounded, partition=partition, probe=probe)
+    print(f"[advection timescale, R = {R}, partition {partition}, Bounded x {xbounded}, edge {edge}] global {want!r}; per rank (model call, rank-local raw call): "
+          + " ".join(f"({s[0]!r}, {s[1]!r})" for s in seen))
+    for rank, (tau, local, dt, cfl, at_rest) in enumerate(seen):
+        assert tau == want, (rank, tau, want, local)
+        assert dt == seen[0][2] == 0.3 * want and cfl == seen[0][3] == 0.01 / want, (rank, dt, cfl)
+        assert at_rest == np.inf, (rank, at_rest)
+        assert (local == want) == (rank == owner["u"]) and local >= want, (rank, local, want)
+
+
+def test_time_step_wizard_keeps_the_ranks_of_a_partitioned_simulation_together(ocn, arch):
+    """Simulation + TimeStepWizard (every iteration) on two ranks of the in-library partitioned model: the wizard's Δt comes from the
+    all-reduced advective timescale, so both ranks take the same steps -- same clock (time, iteration, last Δt) `==` -- and match the same
+    Simulation of the single-GPU model on the global grid to 1e-12 (the timescale is evaluated on fields that agree to round-off, so Δt
+    does too). The first steps are limited by max_change, the later ones by the timescale itself."""
+    _own_stream()
+    R, size, zkind, stop = 2, (32, 16, 8), "stretched", 7
+    dt0 = 0.1 * (2.0 / size[0]) / 0.6
+
+    def drive(model):
+        sim = ocn.Simulation(model, Δt=dt0, stop_iteration=stop)
+        sim.callbacks["wizard"] = ocn.Callback(ocn.TimeStepWizard(cfl=0.16, max_change=1.1), ocn.IterationInterval(1))
+        ocn.run(sim)
+        return sim.Δt, model.clock.time, model.clock.iteration, model.clock.last_Δt
+
+    z, topo = _z_and_topology(ocn, zkind, size[2])
+    sgrid = ocn.RectilinearGrid(arch, size=size, x=(0.0, 2.0), y=(0.0, 1.0), z=z, topology=topo)
+    smodel = ocn.NonhydrostaticModel(grid=sgrid, tracers=("T", "S"), boundary_conditions=_bcs(ocn, zkind), coriolis=ocn.FPlane(f=0.5))
+    ocn.set_model(smodel, **{n: analytic(n, *sgrid.nodes(f.loc)) for n, f in smodel.fields().items()})
+    want = drive(smodel)
+    ref = {n: f.parent() for n, f in smodel.fields().items()} | {"p": smodel.pressures.pNHS.parent()}
+    # the wizard acted stop + 1 times: the first Δt grew by max_change, the last one is what the timescale gives
+    assert want[2] == stop and dt0 * 1.1 < want[0] < dt0 * 1.1 ** (stop + 1) * (1 - 1e-6), (want, dt0)
+    clocks = [None] * R
+    outs = [None] * R
+
+    def probe(model):
+        clocks[model.ctx.rank] = drive(model)
+        outs[model.ctx.rank] = {n: f.parent() for n, f in model.fields().items()} | {"p": model.pressures.pNHS.parent()}
+    _run_library_ranks(ocn, arch, R, size, 0, zkind, {}, probe=probe)
+    assert clocks[0] == clocks[1], clocks
+    for got, expected in zip(clocks[0], want):
+        assert abs(got - expected) <= 1e-12 * abs(expected), (clocks[0], want)
+    assert clocks[0][2] == stop
+    for r in range(R):
+        _compare(outs[r], ref, r, size[0] // R, size)

@@ -48,6 +48,43 @@ def _closure(ocn, zkind):
     return ocn.ScalarDiffusivity(ν=2e-3, κ={"T": 1e-3, "S": 5e-4}) if zkind == "bounded" else None
 
 
+def _serial_oracle(ocn, oracle, size, zkind, nsteps, xbounded=False, ybounded=False):
+    """the SERIAL ORACLE on the global grid of a preset (zkind: periodic | bounded | stretched | amd; x / y Periodic or Bounded): the twin of
+    the product models these tests build from _z_and_topology, _bcs, _closure and _tracers_and_buoyancy -- same analytic state on the same
+    node coordinates (a host-only RectilinearGrid of the product generates them), same Δt. Returns the parent arrays of u, v, w, T, S, p
+    after `nsteps` RK3 steps (the product's layout: 3 halo cells, one more face in a Bounded direction) and the oracle's clock time."""
+    z, topo = _z_and_topology(ocn, zkind, size[2])
+    topo = ((ocn.Bounded if xbounded else topo[0]), (ocn.Bounded if ybounded else topo[1]), topo[2])
+    host = ocn.RectilinearGrid(None, size, x=(0.0, 2.0), y=(0.0, 1.0), z=z, topology=topo, halo=(3, 3, 3))
+    g = oracle.Grid(size, topology=tuple(oracle.BOUNDED if t is ocn.Bounded else oracle.PERIODIC for t in topo), x=(0.0, 2.0), y=(0.0, 1.0), z=z)
+    m = oracle.Model(g, 2)
+    if zkind == "amd":              # _closure, _tracers_and_buoyancy, _bcs of the preset, one oracle call each
+        m.set_amd(C=1 / 3, Ckappa=[1 / 3, 1 / 12])
+        m.set_seawater_buoyancy(alpha=2e-4, beta=8e-4)
+        m.set_bc("u", "top", "flux", -1e-3)
+        m.set_bc("c0", "top", "flux", 4e-3)
+        m.set_bc("c0", "bottom", "gradient", 0.01)
+        m.set_linear_flux_bc("c1", "top", 0.0, -2.5e-3, "c1")
+    elif zkind == "bounded":
+        m.set_closure(nu=2e-3, kappa=[1e-3, 5e-4])
+        m.set_seawater_buoyancy()
+    elif zkind == "stretched":
+        m.set_coriolis(0.5)
+        m.set_bc("u", "top", "flux", -2e-3)
+        m.set_bc("u", "bottom", "value", 0.0)
+        m.set_bc("c0", "top", "flux", 5e-3)
+        m.set_bc("c0", "bottom", "gradient", 0.4)
+    names = {"u": "u", "v": "v", "w": "w", "T": "c0", "S": "c1"}
+    locs = {"u": (ocn.Face, ocn.Center, ocn.Center), "v": (ocn.Center, ocn.Face, ocn.Center), "w": (ocn.Center, ocn.Center, ocn.Face)}
+    m.set(**{cn: analytic(n, *host.nodes(locs.get(n, (ocn.Center,) * 3))) for n, cn in names.items()})
+    dt = 0.1 * host.Δxᶜᵃᵃ / 0.6
+    for _ in range(nsteps):
+        m.time_step(dt)
+    out = {n: m.field(cn).copy() for n, cn in names.items()}
+    out["p"] = m.field("p").copy()
+    return out, m.time
+
+
 def _run_virtual_ranks(ocn, arch, R, size, nsteps, async_halos, zkind="periodic", thin_halos=True):
     import torch
     import host_orchestration as dist
@@ -154,13 +191,13 @@ def _virtual_rank_case(ocn, oracle, arch, R, async_halos, size, zkind):
     glob = {n: f.parent() for n, f in model.fields().items()}
     glob["p"] = model.pressures.pNHS.parent()
     nxl = size[0] // R
-    if zkind == "periodic":
-        # third opinion: the serial oracle (tells which side is wrong if the two product paths ever disagree)
-        from test_distributed_cpu import _serial
-        om = _serial(oracle, size, nsteps)
-        for name, cn in (("u", "u"), ("T", "c0"), ("p", "p")):
-            ref = om.field(cn)
-            assert rel_err(glob[name][3:-3, 3:-3, 3:-3], ref[3:-3, 3:-3, 3:-3]) < 1e-12, ("single-GPU model vs oracle", name)
+    # third opinion: the serial oracle with the preset's physics (tells which side is wrong if the two product paths ever disagree, and
+    # catches what both share): every field and the pressure
+    oref, otime = _serial_oracle(ocn, oracle, size, zkind, nsteps)
+    assert model.clock.time == otime
+    for name in ("u", "v", "w", "T", "S", "p"):
+        err = rel_err(glob[name][3:-3, 3:-3, 3:-3], oref[name][3:-3, 3:-3, 3:-3])
+        assert err < 1e-12, ("single-GPU model vs oracle", zkind, name, err)
     for r, (out, div, time) in enumerate(results):
         assert div < 5e-8 and time == model.clock.time
         for name, a in out.items():
