@@ -173,6 +173,21 @@ int ocn_compute_closure_tendencies_field(ocn_grid_t grid, const double *u, const
 int ocn_compute_amd_diffusivities(ocn_grid_t grid, double Cnu, const double *Ckappa, const double *u, const double *v,
                                   const double *w, const double *const *tracers, int ntracers, double *nu_e,
                                   double *const *kappa_e, const int *range);
+/* compute_diffusivities!(diffusivity_fields, closure::Smagorinsky, model; parameters) (turbulence_closure_implementations/Smagorinskys/
+ * smagorinsky.jl:92-127): νₑ = (cs² Δᶠ²) sqrt(2 Σ²) with Σ² = ΣᵢⱼΣᵢⱼᶜᶜᶜ (scale_invariant_operators.jl:10-13; strain components
+ * velocity_tracer_gradients.jl:25-46) and Δᶠ = cbrt(Δx Δy Δz). lilly == 0: cs² = C² (Smagorinsky(coefficient = C)); lilly != 0:
+ * cs² = ς C², ς = Σ² == 0 ? 0 : sqrt(1 - min(1, Cb max(0, N²) / Σ²)), N² = ℑzᵃᵃᶜ(∂z_b) (lilly_coefficient.jl:129-142) with ∂z_b of
+ * buoyancy_kind 0 (nothing: 0), 1 (BuoyancyTracer, b_or_T = b: BuoyancyFormulations/buoyancy_tracer.jl:16) or 2 (linear SeawaterBuoyancy,
+ * b_or_T = T, S: g (α ∂z T - β ∂z S), seawater_buoyancy.jl:219-224). Fields with filled halos; the caller fills the halos of νₑ.
+ * range as in ocn_compute_amd_diffusivities. */
+int ocn_compute_smagorinsky_viscosity(ocn_grid_t grid, double C, double Cb, int lilly, int buoyancy_kind, const double *b_or_T,
+                                      const double *S, double g, double alpha, double beta, const double *u, const double *v,
+                                      const double *w, double *nu_e, const int *range);
+/* ocn_compute_closure_tendencies_field for a Smagorinsky closure: the momentum terms with νₑ, tracer t's with κ = ℑ(νₑ) / Pr[t] at its
+ * flux points -- interpolate, then divide (κᶠᶜᶜ, κᶜᶠᶜ, κᶜᶜᶠ, smagorinsky.jl:141-143) */
+int ocn_compute_closure_tendencies_smagorinsky(ocn_grid_t grid, const double *u, const double *v, const double *w,
+                                               const double *const *tracers, int ntracers, const double *nu_e, const double *Pr,
+                                               double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range);
 
 /* ---------------------------------------------------------------- RK3 (TimeSteppers/runge_kutta_3.jl) ----------- */
 /* rk3_substep_field! (:212-226), launched with exclude_periphery (:187). has_zeta == 0 selects the first-stage
@@ -348,6 +363,12 @@ int ocn_model_set_closure(ocn_model_t model, double nu, const double *kappa);
 /* closure = AnisotropicMinimumDissipation(Cν = Cnu, Cκ = Ckappa[tracer]) (replaces a ScalarDiffusivity). update_state! then
  * computes the model fields "nu_e", "kappa_e0", ... and fills their halos before the tendencies. */
 int ocn_model_set_amd(ocn_model_t model, double Cnu, const double *Ckappa);
+/* closure = Smagorinsky(coefficient = C, Pr) (lilly == 0) | SmagorinskyLilly(C, Cb, Pr) (Smagorinskys/smagorinsky.jl:62-83,
+ * lilly_coefficient.jl:5-35); Pr: one Prandtl number per tracer. Replaces any other closure. The model then carries "nu_e" only
+ * (build_diffusivity_fields, smagorinsky.jl:131-139; "kappa_e*" answers OCN_ESTATE); update_state! computes it with the buoyancy
+ * ocn_model_set_buoyancy names at that moment and fills its halos before the tendencies. OCN_EINVAL on a grid with a Flat
+ * direction, for C < 0 and for Pr <= 0. */
+int ocn_model_set_smagorinsky(ocn_model_t model, double C, double Cb, int lilly, const double *Pr);
 int ocn_model_set_boundary_condition(ocn_model_t model, const char *name, int side, int kind, double value);
 /* the same with an array-valued condition (see ocn_bc_t; borrowed device pointer, valid for the model's lifetime) */
 int ocn_model_set_boundary_condition_array(ocn_model_t model, const char *name, int side, int kind, const double *device_array);
@@ -417,6 +438,8 @@ int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *ter
  *   "epilogue_kchunk" = 0 (step): levels per workgroup of the marching epilogue, >= 0 (0 = automatic)
  *   "amd_march" = 1 (step): z-marching eddy-diffusivity kernel that evaluates every point operand once (0: one thread per cell,
  *       everything recomputed -- same bits)
+ *   "smag_march" = 1 (step): z-marching Smagorinsky eddy-viscosity kernel that evaluates every strain point value once (0: one
+ *       thread per cell, everything recomputed -- same bits)
  *   "fused_halo" = 1 (step): one launch per periodic fill
  *   pressure solve:
  *   "real_fft" = 1 (step): D2Z / Z2D transforms (0: the reference's complex-to-complex)

@@ -1,6 +1,7 @@
 """Turbulence closures on the accelerated path: ScalarDiffusivity with constant isotropic ν, κ and explicit time
 discretisation (reference: TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl), and (8f.2)
-AnisotropicMinimumDissipation with constant Poincaré coefficients (…/anisotropic_minimum_dissipation.jl)."""
+AnisotropicMinimumDissipation with constant Poincaré coefficients (…/anisotropic_minimum_dissipation.jl), and Smagorinsky /
+SmagorinskyLilly with constant coefficients (…/Smagorinskys/smagorinsky.jl, lilly_coefficient.jl)."""
 import ctypes as C
 
 import numpy as np
@@ -66,3 +67,63 @@ class AnisotropicMinimumDissipation:
 
     def __repr__(self):
         return f"AnisotropicMinimumDissipation{{ExplicitTimeDiscretization}}(Cν={self.Cν}, Cκ={self.Cκ}, Cb=nothing)"
+
+
+class DynamicCoefficient:
+    """DynamicCoefficient(; averaging, ...) (Smagorinskys/dynamic_coefficient.jl): named so that it can be refused; not on the accelerated path."""
+
+    def __init__(self, *args, **kwargs):
+        self.args, self.kwargs = args, kwargs
+
+
+class Smagorinsky:
+    """Smagorinsky(; coefficient = 0.16, Pr = 1.0) (Smagorinskys/smagorinsky.jl:62-83): νₑ = (C Δᶠ)² sqrt(2 Σ²), the tracers' diffusivity
+    is νₑ / Pr at their flux points. Pr a number (all tracers) or a dict tracer-name -> number. The eddy viscosity is the model's
+    `diffusivity_fields.νₑ`."""
+
+    buffer = 2                          # AbstractScalarDiffusivity{TD, ThreeDimensionalFormulation, 2}: required halo size (smagorinsky.jl:11)
+    lilly = False
+    Cb = 0.0
+
+    def __init__(self, coefficient=0.16, Pr=1.0):
+        if isinstance(coefficient, DynamicCoefficient) or callable(coefficient):
+            raise NotImplementedError("only a constant (Number) Smagorinsky coefficient is on the accelerated path")
+        if callable(Pr) or (isinstance(Pr, dict) and any(callable(x) for x in Pr.values())):
+            raise NotImplementedError("only constant (Number) Prandtl numbers are on the accelerated path")
+        self.coefficient = float(coefficient)
+        self.Pr = {n: float(v) for n, v in Pr.items()} if isinstance(Pr, dict) else float(Pr)
+        if self.coefficient < 0:
+            raise ValueError("the Smagorinsky coefficient must be non-negative")
+        if any(not v > 0 for v in (self.Pr.values() if isinstance(self.Pr, dict) else [self.Pr])):
+            raise ValueError("the Prandtl number must be positive")
+
+    def Pr_array(self, tracer_names):
+        if isinstance(self.Pr, dict):
+            missing = [n for n in tracer_names if n not in self.Pr]
+            if missing:
+                raise ValueError(f"Pr is missing tracers {missing}")     # tracer_diffusivities via with_tracers (smagorinsky.jl:87-90)
+            vals = [self.Pr[n] for n in tracer_names]
+        else:
+            vals = [self.Pr] * len(tracer_names)
+        arr = np.ascontiguousarray(vals if vals else [1.0], dtype=np.float64)
+        return arr, arr.ctypes.data_as(C.POINTER(C.c_double))
+
+    def __repr__(self):
+        return f"Smagorinsky closure with coefficient = {self.coefficient}, Pr = {self.Pr}"
+
+
+class SmagorinskyLilly(Smagorinsky):
+    """SmagorinskyLilly(; C = 0.16, Cb = 1.0, Pr = 1.0) (Smagorinskys/lilly_coefficient.jl:5-35): the Smagorinsky coefficient reduced by the
+    stability function sqrt(1 - Cb N² / Σ²) where the stratification is stable; the buoyancy is the model's."""
+
+    lilly = True
+
+    def __init__(self, C=0.16, Cb=1.0, Pr=1.0):
+        if callable(Cb):
+            raise NotImplementedError("only a constant (Number) reduction factor Cb is on the accelerated path")
+        super().__init__(coefficient=C, Pr=Pr)
+        self.Cb = float(Cb)
+
+    def __repr__(self):
+        return (f"Smagorinsky closure with coefficient = LillyCoefficient(smagorinsky = {self.coefficient}, reduction_factor = {self.Cb}), "
+                f"Pr = {self.Pr}")

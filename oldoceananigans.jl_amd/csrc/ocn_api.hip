@@ -156,7 +156,8 @@ struct ocn_grid_s {
     DGrid d;
     double L[3];
     bool z_regular;
-    double *tables;   // one device allocation holding dzc, dzf, ax, ay, vinv_c, vinv_f, rdzf, rdzc
+    double *tables;   // one device allocation holding dzc, dzf, ax, ay, vinv_c, vinv_f, rdzf, rdzc, df2
+    const double *df2; // Δf² = cbrt((Δx Δy) Δzᶜ)² per level: the Smagorinsky filter width (smagorinsky.jl:99-100), formed on the host
     std::vector<double> h_dzc, h_dzf;
     // why the advection scheme cannot be evaluated on this grid (empty: it can). A grid whose halo is smaller than the scheme needs
     // -- RectilinearGrid(halo = (1, 1, 1)), what test/test_halo_regions.jl fills -- serves fields, halo fills and the Poisson
@@ -247,7 +248,7 @@ extern "C" int ocn_grid_create(ocn_grid_t *grid, const int N[3], const int H[3],
     }
     for (int k = 1; k <= N[2]; ++k)
         if (g->h_dzc[k - 1 + H[2]] != g->h_dzc[H[2]] || g->h_dzf[k - 1 + H[2]] != g->h_dzc[H[2]]) g->z_regular = false;
-    std::vector<double> tab(8 * (size_t)n);
+    std::vector<double> tab(9 * (size_t)n);
     for (int q = 0; q < n; ++q) {
         const double zc = g->h_dzc[q], zf = g->h_dzf[q];
         tab[0 * n + q] = zc;
@@ -258,6 +259,8 @@ extern "C" int ocn_grid_create(ocn_grid_t *grid, const int N[3], const int H[3],
         tab[5 * n + q] = 1.0 / ((dx * dy) * zf);
         tab[6 * n + q] = 1.0 / zf;
         tab[7 * n + q] = 1.0 / zc;
+        const double df = std::cbrt((dx * dy) * zc);
+        tab[8 * n + q] = df * df;
     }
     hipError_t e = dev_alloc((void **)&g->tables, tab.size() * sizeof(double));
     if (e != hipSuccess) { delete g; return fail((int)e, "dev_alloc(grid tables): %s", hipGetErrorString(e)); }
@@ -266,6 +269,7 @@ extern "C" int ocn_grid_create(ocn_grid_t *grid, const int N[3], const int H[3],
     D.dzc = g->tables; D.dzf = g->tables + n; D.ax = g->tables + 2 * n; D.ay = g->tables + 3 * n;
     D.vinv_c = g->tables + 4 * n; D.vinv_f = g->tables + 5 * n; D.rdzf = g->tables + 6 * n;
     D.rdzc = g->tables + 7 * n;
+    g->df2 = g->tables + 8 * n;
     *grid = g;
     return OCN_OK;
 }
@@ -670,9 +674,11 @@ extern "C" int ocn_add_fplane_coriolis(ocn_grid_t grid, double f, const double *
 
 static int closure_tendencies(const DGrid &g, const double *u, const double *v, const double *w, const double *const *tr, int ntr,
                               double nu, const double *kappa, double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range,
-                              const double *nu_e = nullptr, const double *const *kappa_e = nullptr) {
+                              const double *nu_e = nullptr, const double *const *kappa_e = nullptr, const double *Pr = nullptr) {
+    // Pr (Smagorinsky): kappa_e[t] is νₑ and tracer t's coefficient is the interpolated νₑ divided by Pr[t]; Pr[t] == 1 takes the
+    // plain instantiation (x / 1.0 is x)
     const FView vu = make_view(g, u, LOC_U), vv = make_view(g, v, LOC_V), vw = make_view(g, w, LOC_W);
-    auto launch = [&](int F, const double *c, double *G, const int loc[3], double coef, const double *K) -> int {
+    auto launch = [&](int F, const double *c, double *G, const int loc[3], double coef, const double *K, bool prd = false) -> int {
         if (coef == 0.0 && !K) return OCN_OK;
         const bool var = K != nullptr;
         const FView vK = make_view(g, K ? K : u, LOC_C);
@@ -686,7 +692,8 @@ static int closure_tendencies(const DGrid &g, const double *u, const double *v, 
         if (F == F_U) hipLaunchKernelGGL(closure_tendency_kernel<F_U>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
         if (F == F_V) hipLaunchKernelGGL(closure_tendency_kernel<F_V>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
         if (F == F_W) hipLaunchKernelGGL(closure_tendency_kernel<F_W>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
-        if (F == F_C) hipLaunchKernelGGL(closure_tendency_kernel<F_C>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
+        if (F == F_C && !prd) hipLaunchKernelGGL(closure_tendency_kernel<F_C>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
+        if (F == F_C && prd) hipLaunchKernelGGL(closure_tendency_prandtl_kernel, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, vK);
         return OCN_OK;
     };
     int rc;
@@ -694,7 +701,8 @@ static int closure_tendencies(const DGrid &g, const double *u, const double *v, 
         (rc = launch(F_W, nullptr, Gw, LOC_W, nu, nu_e)))
         return rc;
     for (int t = 0; t < ntr; ++t)
-        if ((rc = launch(F_C, tr[t], Gc[t], LOC_C, kappa ? kappa[t] : 0.0, kappa_e ? kappa_e[t] : nullptr))) return rc;
+        if ((rc = Pr ? launch(F_C, tr[t], Gc[t], LOC_C, Pr[t], nu_e, Pr[t] != 1.0)
+                     : launch(F_C, tr[t], Gc[t], LOC_C, kappa ? kappa[t] : 0.0, kappa_e ? kappa_e[t] : nullptr))) return rc;
     KERNEL_CHECK();
     return OCN_OK;
 }
@@ -772,6 +780,75 @@ extern "C" int ocn_compute_amd_diffusivities(ocn_grid_t grid, double Cnu, const 
     if (!grid || !u || !v || !w || !nu_e || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 || (ntracers > 0 && (!tracers || !kappa_e || !Ckappa)))
         return fail(OCN_EINVAL, "invalid argument");
     return amd_diffusivities(g_defaults, grid->d, Cnu, Ckappa, u, v, w, tracers, ntracers, nu_e, kappa_e, range);
+}
+
+extern "C" int ocn_compute_closure_tendencies_smagorinsky(ocn_grid_t grid, const double *u, const double *v, const double *w,
+                                                          const double *const *tracers, int ntracers, const double *nu_e, const double *Pr,
+                                                          double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range) {
+    NEED_INIT();
+    if (!grid || !u || !v || !w || !nu_e || !Gu || !Gv || !Gw || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 ||
+        (ntracers > 0 && (!tracers || !Gc || !Pr)))
+        return fail(OCN_EINVAL, "invalid argument");
+    for (int t = 0; t < ntracers; ++t)
+        if (!(Pr[t] > 0)) return fail(OCN_EINVAL, "the Prandtl number must be positive");
+    if (grid->d.tx == OCN_FLAT || grid->d.ty == OCN_FLAT || grid->d.tz == OCN_FLAT)
+        return fail(OCN_ENOTSUP, "eddy-coefficient arrays (Smagorinsky) need a grid without Flat directions");
+    const double one = 1.0;
+    return closure_tendencies(grid->d, u, v, w, tracers, ntracers, 0.0, nullptr, Gu, Gv, Gw, Gc, range, nu_e, nullptr, ntracers > 0 ? Pr : &one);
+}
+
+// compute_diffusivities!(diffusivity_fields, closure::Smagorinsky, model; parameters) (smagorinsky.jl:113-127)
+static int smagorinsky_viscosity(const OcnOptions &o, ocn_grid_t grid, double C, double Cb, bool lilly, int bk, const double *bT, const double *S,
+                                 double grav, double alpha, double beta, const double *u, const double *v, const double *w, double *nu_e,
+                                 const int *range = nullptr) {
+    const DGrid &g = grid->d;
+    if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT) return fail(OCN_ENOTSUP, "Smagorinsky needs a grid without Flat directions");
+    SmagArgs a;
+    a.r = Range6{1, g.Nx, 1, g.Ny, 1, g.Nz};
+    if (range) {
+        // the stencils reach one cell further: the range may extend into the halos by at most H - 1
+        const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz};
+        for (int d = 0; d < 3; ++d)
+            if (range[2 * d] < 2 - H[d] || range[2 * d + 1] > N[d] + H[d] - 1)
+                return fail(OCN_EINVAL, "range [%d, %d] along dimension %d leaves no halo for the stencil", range[2 * d], range[2 * d + 1], d);
+        a.r = Range6{range[0], range[1], range[2], range[3], range[4], range[5]};
+    }
+    const int nx = a.r.i1 - a.r.i0 + 1, ny = a.r.j1 - a.r.j0 + 1, nz = a.r.k1 - a.r.k0 + 1;
+    if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
+    if (!lilly) bk = 0;                      // the constant coefficient reads no tracer
+    a.u = make_view(g, u, LOC_U); a.v = make_view(g, v, LOC_V); a.w = make_view(g, w, LOC_W);
+    a.bT = make_view(g, bk >= 1 ? bT : u, LOC_C); a.S = make_view(g, bk == 2 ? S : u, LOC_C);
+    a.nu_e = make_view(g, nu_e, LOC_C);
+    a.C = C; a.Cb = Cb; a.grav = grav; a.alpha = alpha; a.beta = beta; a.df2 = grid->df2;
+    if (o.smag_march) {
+        // 63 columns per wave, 4 rows per block, chunks of levels so that ~2000 blocks fill the chip (as amd_diffusivities)
+        const int bx = (nx + 62) / 63, by = (ny + 3) / 4;
+        const int want = std::max(1, 2048 / std::max(1, bx * by));
+        const int kchunk = std::max(std::min(nz, 8), (nz + want - 1) / want);
+        const dim3 grd(bx, by, (nz + kchunk - 1) / kchunk), blk(64, 4);
+        if (!lilly) hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<0, false>), grd, blk, 0, g_stream, g, a, kchunk);
+        else if (bk == 0) hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<0, true>), grd, blk, 0, g_stream, g, a, kchunk);
+        else if (bk == 1) hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<1, true>), grd, blk, 0, g_stream, g, a, kchunk);
+        else hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<2, true>), grd, blk, 0, g_stream, g, a, kchunk);
+    } else {
+        const dim3 grd = grid3(nx, ny, nz, BLK);
+        if (!lilly) hipLaunchKernelGGL((smagorinsky_viscosity_kernel<0, false>), grd, BLK, 0, g_stream, g, a);
+        else if (bk == 0) hipLaunchKernelGGL((smagorinsky_viscosity_kernel<0, true>), grd, BLK, 0, g_stream, g, a);
+        else if (bk == 1) hipLaunchKernelGGL((smagorinsky_viscosity_kernel<1, true>), grd, BLK, 0, g_stream, g, a);
+        else hipLaunchKernelGGL((smagorinsky_viscosity_kernel<2, true>), grd, BLK, 0, g_stream, g, a);
+    }
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+extern "C" int ocn_compute_smagorinsky_viscosity(ocn_grid_t grid, double C, double Cb, int lilly, int buoyancy_kind, const double *b_or_T,
+                                                 const double *S, double g, double alpha, double beta, const double *u, const double *v,
+                                                 const double *w, double *nu_e, const int *range) {
+    NEED_INIT();
+    if (!grid || !u || !v || !w || !nu_e || buoyancy_kind < 0 || buoyancy_kind > 2 || (buoyancy_kind >= 1 && !b_or_T) || (buoyancy_kind == 2 && !S))
+        return fail(OCN_EINVAL, "invalid argument");
+    if (!(C >= 0)) return fail(OCN_EINVAL, "the Smagorinsky coefficient must be non-negative");
+    return smagorinsky_viscosity(g_defaults, grid, C, Cb, lilly != 0, buoyancy_kind, b_or_T, S, g, alpha, beta, u, v, w, nu_e, range);
 }
 
 extern "C" int ocn_compute_tendencies_and_substep(ocn_grid_t grid, const double *const *fields, int ntracers, double *const *Gn,
@@ -2355,6 +2432,9 @@ struct ocn_model_s {
     bool has_amd = false;                   // closure = AnisotropicMinimumDissipation(Cν, Cκ)
     double Cnu = 0.0, Ckappa[OCN_MAX_FIELDS] = {};
     double *nu_e = nullptr, *kappa_e[OCN_MAX_FIELDS] = {};   // diffusivity_fields.νₑ, .κₑ (ccc, with halos)
+    bool has_smag = false;                  // closure = Smagorinsky(C, Pr) | SmagorinskyLilly(C, Cb, Pr): νₑ only (build_diffusivity_fields, smagorinsky.jl:131-139)
+    bool smag_lilly = false, smag_unit_pr = true;
+    double smag_C = 0.0, smag_Cb = 0.0, Pr[OCN_MAX_FIELDS] = {};
     // forcing = (name = F,) (ocn_forcing.h): host copy of the descriptors, the device-resident table the kernels read, the device copies
     // of the tables (per field and term: mask, target)
     ForcingTable forcing_h = {};
@@ -2455,9 +2535,10 @@ static int field_lookup(ocn_model_s *m, const char *name, double ***slot, int **
         *slot = &m->pHY; *loc = const_cast<int *>(LOC_C); return OCN_OK;
     }
     if (!strcmp(name, "nu_e") || !strncmp(name, "kappa_e", 7)) {
-        if (!m->has_amd) return fail(OCN_ESTATE, "the model has no eddy diffusivity fields (closure is not AnisotropicMinimumDissipation)");
+        if (!m->has_amd && !m->has_smag) return fail(OCN_ESTATE, "the model has no eddy diffusivity fields (closure is not an LES closure)");
         *loc = const_cast<int *>(LOC_C);
         if (!strcmp(name, "nu_e")) { *slot = &m->nu_e; return OCN_OK; }
+        if (m->has_smag) return fail(OCN_ESTATE, "a Smagorinsky closure has the eddy viscosity nu_e only (the tracers' coefficient is nu_e / Pr at their flux points)");
         const int t = name[7] - '0';
         if (name[7] < '0' || name[7] > '9' || name[8] || t >= m->ntr) return fail(OCN_EINVAL, "no eddy diffusivity field %s", name);
         *slot = &m->kappa_e[t];
@@ -2516,6 +2597,7 @@ static const OptionRow kOptions[] = {
     {"epilogue_rows", &OcnOptions::epilogue_rows, OPT_STEP, [](int v) { return v >= 1 && v <= 8; }, "epilogue_rows is 1 .. 8"},
     {"epilogue_kchunk", &OcnOptions::epilogue_kchunk, OPT_STEP, nonneg, "epilogue_kchunk must be >= 0 (0 = automatic)"},
     {"amd_march", &OcnOptions::amd_march, OPT_STEP},
+    {"smag_march", &OcnOptions::smag_march, OPT_STEP},
     {"fused_halo", &OcnOptions::fused_halo, OPT_STEP},
     {"real_fft", &OcnOptions::real_fft, OPT_STEP},
     {"c2r_strided", &OcnOptions::c2r_strided, OPT_CREATION},
@@ -2582,7 +2664,7 @@ extern "C" int ocn_model_set_option(ocn_model_t m, const char *key, int value) {
     return OCN_OK;
 }
 
-static bool has_physics(const ocn_model_s *m) { return m->has_coriolis || m->buoyancy_kind != 0 || m->has_closure || m->has_amd; }
+static bool has_physics(const ocn_model_s *m) { return m->has_coriolis || m->buoyancy_kind != 0 || m->has_closure || m->has_amd || m->has_smag; }
 
 static bool has_forcing(const ocn_model_s *m) {
     for (int f = 0; f < m->nf; ++f)
@@ -2640,10 +2722,15 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
     a.has_buoyancy = m->buoyancy_kind != 0;
     a.nu = m->nu;
     for (int t = 0; t < OCN_MAX_FIELDS; ++t) a.kappa[t] = t < m->ntr ? m->kappa[t] : 0.0;
-    a.amd = m->has_amd;
+    a.amd = m->has_amd || m->has_smag;
     if (m->has_amd) {
         a.nu_e = make_view(g, m->nu_e, LOC_C);
         for (int t = 0; t < m->ntr; ++t) a.kappa_e[t] = make_view(g, m->kappa_e[t], LOC_C);
+    }
+    if (m->has_smag) {
+        // every tracer's coefficient array is νₑ; with a Pr ≠ 1 the kernels divide the interpolated value by kappa[t] = Pr[t] (CLO 3)
+        a.nu_e = make_view(g, m->nu_e, LOC_C);
+        for (int t = 0; t < m->ntr; ++t) { a.kappa_e[t] = a.nu_e; a.kappa[t] = m->Pr[t]; }
     }
     a.substep = sub != nullptr; a.has_zeta = sub && sub->has_zeta;
     a.store_G = !sub || sub->store_G;
@@ -2673,7 +2760,7 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
             if (sd < 3) a.loc[f][sd] = f < m->nf ? m->loc[f][sd] : 0;
         }
     if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
-    const int clo = m->has_amd ? 2 : (m->has_closure ? 1 : 0);
+    const int clo = m->has_smag ? (m->smag_unit_pr ? 2 : 3) : (m->has_amd ? 2 : (m->has_closure ? 1 : 0));
     // closure terms on a grid without Flat directions: the z-marching form (ocn_epilogue_march.h) -- the union of the fields' ranges, one
     // column of halo around it readable
     const OcnOptions &o = m->opt;
@@ -2699,7 +2786,7 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
             a.store_sides = mask;         // (a tendency that is not stored otherwise still is on those sides)
 #define OCN_EPM(COR, BUOY, CLO, NTR) hipLaunchKernelGGL((tendency_epilogue_march_kernel<COR, BUOY, CLO, NTR>), mg, mb, 0, g_stream, g, a, R, kchunk)
 #define OCN_EPM_N(COR, BUOY, CLO) do { if (m->ntr == 2) OCN_EPM(COR, BUOY, CLO, 2); else if (m->ntr == 1) OCN_EPM(COR, BUOY, CLO, 1); else OCN_EPM(COR, BUOY, CLO, 0); } while (0)
-#define OCN_EPM_CLO(COR, BUOY) do { if (clo == 2) OCN_EPM_N(COR, BUOY, 2); else OCN_EPM_N(COR, BUOY, 1); } while (0)
+#define OCN_EPM_CLO(COR, BUOY) do { if (clo == 3) OCN_EPM_N(COR, BUOY, 3); else if (clo == 2) OCN_EPM_N(COR, BUOY, 2); else OCN_EPM_N(COR, BUOY, 1); } while (0)
             if (a.has_coriolis) { if (a.has_buoyancy) OCN_EPM_CLO(true, true); else OCN_EPM_CLO(true, false); }
             else                { if (a.has_buoyancy) OCN_EPM_CLO(false, true); else OCN_EPM_CLO(false, false); }
 #undef OCN_EPM_CLO
@@ -2723,7 +2810,7 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
     }
     const dim3 grd = grid3(nx, ny, nz * m->nf, BLK);
 #define OCN_EPI(COR, BUOY, CLO) hipLaunchKernelGGL((tendency_epilogue_kernel<COR, BUOY, CLO>), grd, BLK, 0, g_stream, g, a)
-#define OCN_EPI_CLO(COR, BUOY) do { if (clo == 2) OCN_EPI(COR, BUOY, 2); else if (clo == 1) OCN_EPI(COR, BUOY, 1); else OCN_EPI(COR, BUOY, 0); } while (0)
+#define OCN_EPI_CLO(COR, BUOY) do { if (clo == 3) OCN_EPI(COR, BUOY, 3); else if (clo == 2) OCN_EPI(COR, BUOY, 2); else if (clo == 1) OCN_EPI(COR, BUOY, 1); else OCN_EPI(COR, BUOY, 0); } while (0)
     if (a.has_coriolis) { if (a.has_buoyancy) OCN_EPI_CLO(true, true); else OCN_EPI_CLO(true, false); }
     else                { if (a.has_buoyancy) OCN_EPI_CLO(false, true); else OCN_EPI_CLO(false, false); }
 #undef OCN_EPI_CLO
@@ -2793,6 +2880,17 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
         // fill copies there -- the reference's only_local_halos fill leaves it unwritten on a partitioned grid, halo_communication.jl:87-110)
         if ((rc = fill_halo_regions(m->opt, m->grid, K, kl, 1 + m->ntr, true, m->any_kbc ? m->kbcs : nullptr, amd_range != nullptr))) return rc;
     }
+    if (m->has_smag) {
+        // buoyancy is the model's at this moment (nothing: N² = 0); νₑ's halos as above, with the rank-edge z-halo column
+        const int bk = m->buoyancy_kind;
+        if ((rc = smagorinsky_viscosity(m->opt, m->grid, m->smag_C, m->smag_Cb, m->smag_lilly, bk, bk ? m->U[3 + m->bT_index] : nullptr,
+                                        bk == 2 ? m->U[3 + m->S_index] : nullptr, m->grav, m->alpha, m->beta, m->U[0], m->U[1], m->U[2], m->nu_e, amd_range)))
+            return rc;
+        double *K[1] = {m->nu_e};
+        int kl[1][3];
+        memcpy(kl[0], LOC_C, sizeof(int) * 3);
+        if ((rc = fill_halo_regions(m->opt, m->grid, K, kl, 1, true, m->any_kbc ? m->kbcs : nullptr, amd_range != nullptr))) return rc;
+    }
     // compute_auxiliaries!: update_hydrostatic_pressure! (update_nonhydrostatic_model_state.jl:58-69)
     if (m->buoyancy_kind &&
         (rc = update_hydrostatic_pressure(g, m->buoyancy_kind, m->U[3 + m->bT_index], m->U[3 + m->S_index], m->grav, m->alpha, m->beta, m->pHY)))
@@ -2825,6 +2923,9 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
                 if (!rc && m->has_amd)
                     rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, 0.0, nullptr, m->Gn[0], m->Gn[1],
                                             m->Gn[2], m->Gn + 3, nullptr, m->nu_e, m->kappa_e);
+                if (!rc && m->has_smag)
+                    rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, 0.0, nullptr, m->Gn[0], m->Gn[1],
+                                            m->Gn[2], m->Gn + 3, nullptr, m->nu_e, nullptr, m->Pr);
             }
         }
         // the last interior term: in the role kernel above, or one pass here (then no substep rides along: can_fuse_substep)
@@ -3074,9 +3175,33 @@ extern "C" int ocn_model_set_amd(ocn_model_t m, double Cnu, const double *Ckappa
     int rc = alloc0(&m->nu_e);
     for (int t = 0; t < m->ntr && !rc; ++t) rc = alloc0(&m->kappa_e[t]);
     if (rc) return rc;
-    m->has_amd = true; m->has_closure = false; m->nu = 0.0;
+    m->has_amd = true; m->has_closure = false; m->has_smag = false; m->nu = 0.0;
     m->Cnu = Cnu;
     for (int t = 0; t < m->ntr; ++t) { m->kappa[t] = 0.0; m->Ckappa[t] = Ckappa[t]; }
+    return OCN_OK;
+}
+
+// closure = Smagorinsky(coefficient = C, Pr) (lilly = 0) | SmagorinskyLilly(C, Cb, Pr) (smagorinsky.jl:62-83, lilly_coefficient.jl); replaces
+// any other closure. The buoyancy of the Lilly coefficient is what ocn_model_set_buoyancy says when a step runs.
+extern "C" int ocn_model_set_smagorinsky(ocn_model_t m, double C, double Cb, int lilly, const double *Pr) {
+    if (m) m->epoch += 1;
+    NEED_INIT();
+    if (!m || (m->ntr > 0 && !Pr)) return fail(OCN_EINVAL, "NULL argument");
+    const DGrid &g = m->grid->d;
+    if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT) return fail(OCN_EINVAL, "Smagorinsky needs a grid without Flat directions");
+    if (!(C >= 0)) return fail(OCN_EINVAL, "the Smagorinsky coefficient must be non-negative");
+    for (int t = 0; t < m->ntr; ++t)
+        if (!(Pr[t] > 0)) return fail(OCN_EINVAL, "the Prandtl number must be positive");
+    if (!m->nu_e) {
+        int P[3];
+        parent_size(g, LOC_C, P);
+        const size_t bytes = (size_t)P[0] * P[1] * P[2] * sizeof(double);
+        HIP_TRY(dev_alloc((void **)&m->nu_e, bytes));
+        HIP_TRY(hipMemsetAsync(m->nu_e, 0, bytes, g_stream));
+    }
+    m->has_smag = true; m->has_amd = false; m->has_closure = false; m->nu = 0.0;
+    m->smag_C = C; m->smag_Cb = Cb; m->smag_lilly = lilly != 0; m->smag_unit_pr = true;
+    for (int t = 0; t < m->ntr; ++t) { m->kappa[t] = 0.0; m->Pr[t] = Pr[t]; m->smag_unit_pr = m->smag_unit_pr && Pr[t] == 1.0; }
     return OCN_OK;
 }
 
@@ -3088,6 +3213,7 @@ static int model_set_bc(ocn_model_t m, const char *name, int side, int kind, dou
     // filled with them after compute_diffusivities!
     if (!strcmp(name, "nu_e") || (!strncmp(name, "kappa_e", 7) && name[7] >= '0' && name[7] <= '9' && !name[8])) {
         const int q = name[0] == 'n' ? 0 : 1 + (name[7] - '0');
+        if (q > 0 && m->has_smag) return fail(OCN_ESTATE, "a Smagorinsky closure has the eddy viscosity nu_e only");
         if (q > m->ntr) return fail(OCN_EINVAL, "no tracer %d", q - 1);
         if (kind == OCN_BC_FLUX || kind == OCN_BC_OPEN) return fail(OCN_EINVAL, "a diffusivity field takes Value or Gradient conditions");
         int rcq = validate_bc(m->grid->d, LOC_C, side, kind);

@@ -34,7 +34,7 @@ __device__ __forceinline__ double lane_prev(double x) {              // the valu
 
 template <bool COR, bool BUOY, int CLO, int NTR>
 __global__ void __launch_bounds__(512) tendency_epilogue_march_kernel(DGrid g, EpilogueArgs a, Range6 R, int kchunk) {
-    constexpr bool VAR = CLO == 2;
+    constexpr bool VAR = CLO >= 2, PRD = CLO == 3;      // PRD: the interpolated coefficient of tracer t divided by a.kappa[t] = Pr[t] (kappa_e[t] is νₑ)
     constexpr int NT = NTR > 0 ? NTR : 1;
     const int lane = threadIdx.x;                                        // block (64, 4): a wave per row
     const int i = R.i0 + blockIdx.x * OCN_EPI_MARCH_COLS + lane - 1;
@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(512) tendency_epilogue_march_kernel(DGrid g, E
             n_m = n1; kfcc_m = 0.5 * (lane_prev(n1) + n1); kcfc_m = 0.5 * (n0 + n1); kcfc1_m = 0.5 * (n1 + n2);
         }
 #pragma unroll
-        for (int t = 0; t < NTR; ++t) { c_m[t] = a.c[t].at(ic, j, L); k_m[t] = VAR ? a.kappa_e[t].at(ic, j, L) : a.kappa[t]; }
+        for (int t = 0; t < NTR; ++t) { c_m[t] = a.c[t].at(ic, j, L); k_m[t] = PRD ? n_m : (VAR ? a.kappa_e[t].at(ic, j, L) : a.kappa[t]); }      // (PRD: kappa_e[t] IS νₑ -- no second load)
     }
     // carried from iteration L - 1: the x + y parts of the divergences of cell L - 1, its Coriolis / pHY′ terms, the face fluxes of level L - 1
     double s_u = 0, s_v = 0, s_w = 0, s_c[NT], cor_u = 0, cor_v = 0, pg_u = 0, pg_v = 0, p13_m = 0, p23_m = 0, p33_m = 0, qz_m[NT];
@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(512) tendency_epilogue_march_kernel(DGrid g, E
 #pragma unroll
             for (int t = 0; t < NTR; ++t) {
                 cL[t][r] = a.c[t].at(ic, j - 1 + r, L);
-                kL[t][r] = VAR ? a.kappa_e[t].at(ic, j - 1 + r, L) : a.kappa[t];
+                kL[t][r] = PRD ? nL[r] : (VAR ? a.kappa_e[t].at(ic, j - 1 + r, L) : a.kappa[t]);
             }
         }
         double pL0 = 0, pL1 = 0;
@@ -117,7 +117,7 @@ __global__ void __launch_bounds__(512) tendency_epilogue_march_kernel(DGrid g, E
         double qz[NT];
 #pragma unroll
         for (int t = 0; t < NTR; ++t) {
-            const double kccf = VAR ? 0.5 * (k_m[t] + kL[t][1]) : a.kappa[t];
+            const double kccf = PRD ? (0.5 * (k_m[t] + kL[t][1])) / a.kappa[t] : (VAR ? 0.5 * (k_m[t] + kL[t][1]) : a.kappa[t]);
             qz[t] = -(kccf * ((cL[t][1] - c_m[t]) * rdzf));
         }
 
@@ -182,8 +182,9 @@ __global__ void __launch_bounds__(512) tendency_epilogue_march_kernel(DGrid g, E
             s_v = (ax * lane_next(p12_j) - ax * p12_j) + (ay * p22_j - ay * p22_jm);
 #pragma unroll
             for (int t = 0; t < NTR; ++t) {
-                const double kx = VAR ? 0.5 * (lane_prev(kL[t][1]) + kL[t][1]) : a.kappa[t];
-                const double ky_j = VAR ? 0.5 * (kL[t][0] + kL[t][1]) : a.kappa[t], ky_j1 = VAR ? 0.5 * (kL[t][1] + kL[t][2]) : a.kappa[t];
+                const double kx = PRD ? (0.5 * (lane_prev(kL[t][1]) + kL[t][1])) / a.kappa[t] : (VAR ? 0.5 * (lane_prev(kL[t][1]) + kL[t][1]) : a.kappa[t]);
+                const double ky_j = PRD ? (0.5 * (kL[t][0] + kL[t][1])) / a.kappa[t] : (VAR ? 0.5 * (kL[t][0] + kL[t][1]) : a.kappa[t]);
+                const double ky_j1 = PRD ? (0.5 * (kL[t][1] + kL[t][2])) / a.kappa[t] : (VAR ? 0.5 * (kL[t][1] + kL[t][2]) : a.kappa[t]);
                 const double qx = -(kx * ((cL[t][1] - lane_prev(cL[t][1])) * rdx));
                 const double qy_j = -(ky_j * ((cL[t][1] - cL[t][0]) * rdy)), qy_j1 = -(ky_j1 * ((cL[t][2] - cL[t][1]) * rdy));
                 s_c[t] = (ax * lane_next(qx) - ax * qx) + (ay * qy_j1 - ay * qy_j);

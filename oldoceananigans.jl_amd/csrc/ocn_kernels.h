@@ -161,8 +161,10 @@ struct ClosureCtx {
     __device__ __forceinline__ double vf23(int i, int j, int k) const { return -(2 * (K_cff(i, j, k) * S23(i, j, k))); }
 };
 
-// V⁻¹ (δx(Ax flux) + δy(Ay flux) + δz(Az flux)) of the closure for field F at (i, j, k); coef = ν (momentum) or κ (tracer c)
-template <int F>
+// V⁻¹ (δx(Ax flux) + δy(Ay flux) + δz(Az flux)) of the closure for field F at (i, j, k); coef = ν (momentum) or κ (tracer c).
+// PRD (tracers of a Smagorinsky closure with Pr ≠ 1, smagorinsky.jl:141-143): K is νₑ and the coefficient at a flux point is the
+// interpolated νₑ DIVIDED by the Prandtl number, which `coef` then holds (interpolate, then divide)
+template <int F, bool PRD = false>
 __device__ __forceinline__ double closure_divergence(const DGrid &g, const FView &u, const FView &v, const FView &w, const FView &c,
                                                      double coef, int i, int j, int k, bool var, const FView &K) {
     // eddy-coefficient arrays come with grids that have no Flat direction (ocn_model_set_amd): with `var` a compile-time constant the
@@ -188,9 +190,15 @@ __device__ __forceinline__ double closure_divergence(const DGrid &g, const FView
     } else {                   // ∇_dot_qᶜ at ccc: Ax_qᶠᶜᶜ, Ay_qᶜᶠᶜ, Az_qᶜᶜᶠ of -(κ ∂c)
         vinv = g.vinv_c[k - 1 + g.Hz];
         const double ax = dy_ * X.dzc(k), ay = dx_ * X.dzc(k), az = dx_ * dy_;
-        dx = X.fx ? 0.0 : ax * -(X.K_fcc(i + 1, j, k) * X.ddx_f(c, i + 1, j, k)) - ax * -(X.K_fcc(i, j, k) * X.ddx_f(c, i, j, k));
-        dy = X.fy ? 0.0 : ay * -(X.K_cfc(i, j + 1, k) * X.ddy_f(c, i, j + 1, k)) - ay * -(X.K_cfc(i, j, k) * X.ddy_f(c, i, j, k));
-        dz = X.fz ? 0.0 : az * -(X.K_ccf(i, j, k + 1) * X.ddz_f(c, i, j, k + 1)) - az * -(X.K_ccf(i, j, k) * X.ddz_f(c, i, j, k));
+        if (PRD) {
+            dx = ax * -((X.K_fcc(i + 1, j, k) / coef) * X.ddx_f(c, i + 1, j, k)) - ax * -((X.K_fcc(i, j, k) / coef) * X.ddx_f(c, i, j, k));
+            dy = ay * -((X.K_cfc(i, j + 1, k) / coef) * X.ddy_f(c, i, j + 1, k)) - ay * -((X.K_cfc(i, j, k) / coef) * X.ddy_f(c, i, j, k));
+            dz = az * -((X.K_ccf(i, j, k + 1) / coef) * X.ddz_f(c, i, j, k + 1)) - az * -((X.K_ccf(i, j, k) / coef) * X.ddz_f(c, i, j, k));
+        } else {
+            dx = X.fx ? 0.0 : ax * -(X.K_fcc(i + 1, j, k) * X.ddx_f(c, i + 1, j, k)) - ax * -(X.K_fcc(i, j, k) * X.ddx_f(c, i, j, k));
+            dy = X.fy ? 0.0 : ay * -(X.K_cfc(i, j + 1, k) * X.ddy_f(c, i, j + 1, k)) - ay * -(X.K_cfc(i, j, k) * X.ddy_f(c, i, j, k));
+            dz = X.fz ? 0.0 : az * -(X.K_ccf(i, j, k + 1) * X.ddz_f(c, i, j, k + 1)) - az * -(X.K_ccf(i, j, k) * X.ddz_f(c, i, j, k));
+        }
     }
     return vinv * ((dx + dy) + dz);
 }
@@ -203,6 +211,15 @@ __global__ void __launch_bounds__(256) closure_tendency_kernel(DGrid g, FView u,
     const int k = r.k0 + blockIdx.z;
     if (i > r.i1 || j > r.j1 || k > r.k1) return;
     G.at(i, j, k) = (G.at(i, j, k) - closure_divergence<F>(g, u, v, w, c, coef, i, j, k, var, K)) + 0.0;
+}
+
+// a tracer of a Smagorinsky closure with Pr ≠ 1: κ = ℑ(νₑ) / Pr at the flux points
+__global__ void __launch_bounds__(256) closure_tendency_prandtl_kernel(DGrid g, FView u, FView v, FView w, FView c, FView G, double Pr, Range6 r, FView nu_e) {
+    const int i = r.i0 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = r.j0 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = r.k0 + blockIdx.z;
+    if (i > r.i1 || j > r.j1 || k > r.k1) return;
+    G.at(i, j, k) = (G.at(i, j, k) - closure_divergence<F_C, true>(g, u, v, w, c, Pr, i, j, k, true, nu_e)) + 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -590,6 +607,143 @@ __global__ void __launch_bounds__(256, OCN_AMD_MARCH_WAVES) amd_diffusivities_ma
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Smagorinsky(coefficient = C, Pr) and SmagorinskyLilly(C, Cb, Pr): the eddy viscosity νₑ at ccc
+// (turbulence_closure_implementations/Smagorinskys/smagorinsky.jl:92-106 kernel, lilly_coefficient.jl:129-142 stability function,
+// scale_invariant_operators.jl:10-13 ΣᵢⱼΣᵢⱼ at ccc, velocity_tracer_gradients.jl:25-46 strain components, BuoyancyFormulations/
+// buoyancy_tracer.jl:16 and seawater_buoyancy.jl:219-224 ∂z_b). Restated:
+//   Σ²  = ((((Σ11² + Σ22²) + Σ33²) + 2 Ixy(Σ12²)) + 2 Ixz(Σ13²)) + 2 Iyz(Σ23²)     Σ12 at ffc, Σ13 at fcf, Σ23 at cff; ∂ = δ * Δ⁻¹ as ClosureCtx;
+//                                                                                  the interpolations nest like AmdTerms::Ixy / Ixz / Iyz
+//   νₑ  = (cs² Δf²) sqrt(2 Σ²),  Δf² = cbrt((Δx Δy) Δzᶜ)² from the host's per-level table `df2`
+//   cs² = C C                                              (constant coefficient)
+//   cs² = (Σ² == 0 ? 0 : sqrt(1 - min(1, (Cb max(0, N²)) / Σ²))) (C C),  N² = 0.5 (∂z_b(k) + ∂z_b(k + 1))   (Lilly)
+// The tracers' coefficient is ℑ(νₑ) / Pr at their flux points (smagorinsky.jl:141-143): closure_divergence<F_C, PRD>.
+// ---------------------------------------------------------------------------------------------------------------------
+struct SmagArgs {
+    Range6 r;
+    FView u, v, w, bT, S, nu_e;       // bT: the buoyancy tracer (BK 1) or T (BK 2); S: salinity (BK 2)
+    double C, Cb, grav, alpha, beta;
+    const double *df2;                // Δf² per level, indexed like the grid's tables [k - 1 + Hz]
+};
+
+// ∂z_b at ccf from the tracer differences ∂z bT, ∂z S (BK: 0 no buoyancy, 1 BuoyancyTracer, 2 linear SeawaterBuoyancy)
+template <int BK> __device__ __forceinline__ double smag_dzb(const SmagArgs &a, double dz_bT, double dz_S) {
+    return BK == 0 ? 0.0 : (BK == 1 ? dz_bT : a.grav * (a.alpha * dz_bT - a.beta * dz_S));
+}
+
+// what a cell is assembled from: the three diagonal strain components, the three interpolated squares and ∂z_b below and above the cell
+struct SmagCell { double s11, s22, s33, ixy12, ixz13, iyz23, dzb_k, dzb_k1; };
+
+// the one assembly of a cell, shared by the per-cell and the marching kernel (=> bit-identical)
+template <bool LILLY>
+__device__ __forceinline__ double smagorinsky_viscosity(const SmagCell &c, const SmagArgs &a, double df2) {
+    double s2 = c.s11 * c.s11 + c.s22 * c.s22;
+    s2 = s2 + c.s33 * c.s33;
+    s2 = s2 + 2 * c.ixy12; s2 = s2 + 2 * c.ixz13; s2 = s2 + 2 * c.iyz23;
+    double cs2 = a.C * a.C;
+    if (LILLY) {
+        const double N2 = 0.5 * (c.dzb_k + c.dzb_k1);
+        const double N2p = fmax(0.0, N2);
+        const double sig2 = 1.0 - fmin(1.0, (a.Cb * N2p) / s2);
+        cs2 = (s2 == 0 ? 0.0 : sqrt(sig2)) * cs2;            // a select: the quotient is NaN / Inf in fluid at rest and must not reach νₑ
+    }
+    return (cs2 * df2) * sqrt(2 * s2);
+}
+
+// (a) one thread per cell, every point value recomputed where it is needed
+template <int BK, bool LILLY>
+__global__ void __launch_bounds__(256) smagorinsky_viscosity_kernel(DGrid g, SmagArgs a) {
+    const int i = a.r.i0 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = a.r.j0 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = a.r.k0 + blockIdx.z;
+    if (i > a.r.i1 || j > a.r.j1 || k > a.r.k1) return;
+    const ClosureCtx X{g, a.u, a.v, a.w, 0.0, false, false, false, false, a.u};
+    auto q12 = [&](int ii, int jj, int kk) { const double x = X.S12(ii, jj, kk); return x * x; };
+    auto q13 = [&](int ii, int jj, int kk) { const double x = X.S13(ii, jj, kk); return x * x; };
+    auto q23 = [&](int ii, int jj, int kk) { const double x = X.S23(ii, jj, kk); return x * x; };
+    auto dzb = [&](int kk) { return smag_dzb<BK>(a, BK >= 1 ? X.ddz_f(a.bT, i, j, kk) : 0.0, BK == 2 ? X.ddz_f(a.S, i, j, kk) : 0.0); };
+    SmagCell c;
+    c.s11 = X.S11(i, j, k); c.s22 = X.S22(i, j, k); c.s33 = X.S33(i, j, k);
+    c.ixy12 = 0.5 * (0.5 * (q12(i, j, k) + q12(i + 1, j, k)) + 0.5 * (q12(i, j + 1, k) + q12(i + 1, j + 1, k)));
+    c.ixz13 = 0.5 * (0.5 * (q13(i, j, k) + q13(i + 1, j, k)) + 0.5 * (q13(i, j, k + 1) + q13(i + 1, j, k + 1)));
+    c.iyz23 = 0.5 * (0.5 * (q23(i, j, k) + q23(i, j + 1, k)) + 0.5 * (q23(i, j, k + 1) + q23(i, j + 1, k + 1)));
+    c.dzb_k = LILLY ? dzb(k) : 0.0; c.dzb_k1 = LILLY ? dzb(k + 1) : 0.0;
+    a.nu_e.at(i, j, k) = smagorinsky_viscosity<LILLY>(c, a, a.df2[k - 1 + g.Hz]);
+}
+
+// (b) the z-march (the pattern of amd_diffusivities_march_kernel): a wave owns a 64-wide row and marches along z; every Σ12², Σ13², Σ23²
+// point value is evaluated ONCE --
+//   x: the value of the next column is the next lane's (one DPP move per 32 bits); lane 63 only supplies its column (63 columns written);
+//   z: the x-interpolated Σ13², the y-interpolated Σ23² and ∂z_b of face level k + 1 stay in registers and are those of face level k
+//      in the next iteration;
+//   y: the thread evaluates the rows j and j + 1 itself.
+// No LDS, no barrier. Block (64, 4): a wave per row. Measured at 256 x 256 x 128 (tools/time_smagorinsky.py, medians of interleaved runs): constant
+// coefficient 0.097 ms against 0.108 of the per-cell kernel, Lilly + SeawaterBuoyancy 0.128 against 0.151; 76 .. 88 VGPRs, no scratch.
+template <int BK, bool LILLY>
+__global__ void __launch_bounds__(256) smagorinsky_viscosity_march_kernel(DGrid g, SmagArgs a, int kchunk) {
+    const int lane = threadIdx.x;
+    const int i = a.r.i0 + blockIdx.x * 63 + lane;
+    const int j = a.r.j0 + blockIdx.y * blockDim.y + threadIdx.y;
+    if (j > a.r.j1) return;                                              // rows are independent: whole waves leave
+    const int kc0 = a.r.k0 + blockIdx.z * kchunk, kc1 = min(kc0 + kchunk - 1, a.r.k1);
+    const bool out_lane = lane < 63 && i <= a.r.i1;
+    const int ic = min(i, a.r.i1 + 1);                                   // lanes beyond the last needed column repeat it (in bounds)
+    const double rdx = g.rdx, rdy = g.rdy;
+    const FView &u = a.u, &v = a.v, &w = a.w;
+    constexpr bool NB = LILLY && BK >= 1, NS = LILLY && BK == 2;         // which tracers are read at all
+    struct Raw {
+        double uc, ujm, ujp;                 // u at (ic, j), (ic, j - 1), (ic, j + 1)
+        double vc, vjp, vim, vimjp;          // v at (ic, j), (ic, j + 1), (ic - 1, j), (ic - 1, j + 1)
+        double wc, wim, wjm, wjp;            // w at (ic, j), (ic - 1, j), (ic, j - 1), (ic, j + 1)
+        double b, s;                         // the buoyancy tracers at (ic, j)
+    };
+    auto load = [&](int L) {                                             // levels beyond the chunk's last needed one: that one again (unused)
+        Raw r;
+        L = min(L, kc1 + 1);
+        r.uc = u.at(ic, j, L); r.ujm = u.at(ic, j - 1, L); r.ujp = u.at(ic, j + 1, L);
+        r.vc = v.at(ic, j, L); r.vjp = v.at(ic, j + 1, L); r.vim = v.at(ic - 1, j, L); r.vimjp = v.at(ic - 1, j + 1, L);
+        r.wc = w.at(ic, j, L); r.wim = w.at(ic - 1, j, L); r.wjm = w.at(ic, j - 1, L); r.wjp = w.at(ic, j + 1, L);
+        r.b = NB ? a.bT.at(ic, j, L) : 0.0; r.s = NS ? a.S.at(ic, j, L) : 0.0;
+        return r;
+    };
+    // face level L (r: level L, rb: level L - 1): Ix of Σ13² at (·, j, L), Iy of Σ23² at (i, ·, L), ∂z_b at (i, j, L)
+    auto vertical = [&](int L, const Raw &r, const Raw &rb, double &ix13, double &iy23, double &dzb) {
+        const double rdzf = g.rdzf[L - 1 + g.Hz];
+        const double s13 = 0.5 * ((r.uc - rb.uc) * rdzf + (r.wc - r.wim) * rdx);
+        ix13 = ix_lane(s13 * s13);
+        const double s23_0 = 0.5 * ((r.vc - rb.vc) * rdzf + (r.wc - r.wjm) * rdy), s23_1 = 0.5 * ((r.vjp - rb.vjp) * rdzf + (r.wjp - r.wc) * rdy);
+        iy23 = 0.5 * (s23_0 * s23_0 + s23_1 * s23_1);
+        dzb = smag_dzb<BK>(a, NB ? (r.b - rb.b) * rdzf : 0.0, NS ? (r.s - rb.s) * rdzf : 0.0);
+    };
+    // own level: Ixy of Σ12² (rows j and j + 1)
+    auto horizontal = [&](const Raw &r) {
+        const double s12_0 = 0.5 * ((r.uc - r.ujm) * rdy + (r.vc - r.vim) * rdx), s12_1 = 0.5 * ((r.ujp - r.uc) * rdy + (r.vjp - r.vimjp) * rdx);
+        return 0.5 * (ix_lane(s12_0 * s12_0) + ix_lane(s12_1 * s12_1));
+    };
+    Raw r0 = load(kc0), r1 = load(kc0 + 1);
+    double ix13, iy23, dzb;
+    {
+        const Raw rm = load(kc0 - 1);
+        vertical(kc0, r0, rm, ix13, iy23, dzb);
+    }
+    for (int k = kc0; k <= kc1; ++k) {
+        // r0: level k, r1: level k + 1
+        double n13, n23, ndzb;
+        vertical(k + 1, r1, r0, n13, n23, ndzb);
+        SmagCell c;
+        c.s11 = (lane_next(r0.uc) - r0.uc) * rdx;                        // (the next lane holds column i + 1 for every lane that writes)
+        c.s22 = (r0.vjp - r0.vc) * rdy;
+        c.s33 = (r1.wc - r0.wc) * g.rdzc[k - 1 + g.Hz];
+        c.ixy12 = horizontal(r0);
+        c.ixz13 = 0.5 * (ix13 + n13); c.iyz23 = 0.5 * (iy23 + n23);
+        c.dzb_k = dzb; c.dzb_k1 = ndzb;
+        if (out_lane) a.nu_e.at(i, j, k) = smagorinsky_viscosity<LILLY>(c, a, a.df2[k - 1 + g.Hz]);
+        ix13 = n13; iy23 = n23; dzb = ndzb;
+        r0 = r1;
+        r1 = load(k + 2);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Buoyancy: BuoyancyTracer | SeawaterBuoyancy(LinearEquationOfState), gravity along -z.
 // _update_hydrostatic_pressure! (Models/NonhydrostaticModels/update_hydrostatic_pressure.jl:12-22) over i = 0:Nx+1, j = 0:Ny+1
 // (:43-50): pHY′[Nz] = -z_dot_g_b(Nz+1) Δzᶠ(Nz+1); pHY′[k] = pHY′[k+1] - z_dot_g_b(k+1) Δzᶠ(k+1), z_dot_g_bᶜᶜᶠ = 1 * ℑzᵃᵃᶠ(b)
@@ -739,7 +893,7 @@ struct EpilogueArgs {
     bool store_G;                               // false: the completed tendency feeds the substep riding along and nothing else (FusedSubstep::store_G)
     int store_sides;                            // ... except on these sides (bit = side): epilogue_flux_shell_kernel re-does their cells from the stored value
     double fcor, nu, kappa[OCN_MAX_FIELDS], dt, gamma, zeta;
-    bool amd;                                   // eddy coefficients from arrays (AnisotropicMinimumDissipation)
+    bool amd;                                   // eddy coefficients from arrays (AnisotropicMinimumDissipation, Smagorinsky)
     FView nu_e, kappa_e[OCN_MAX_FIELDS];
     // valued Flux boundary conditions (compute_flux_bcs.jl:57-163), applied after the interior terms: [field][side]
     bool any_flux;
@@ -794,7 +948,8 @@ __device__ __forceinline__ double epilogue_flux_conditions(const DGrid &g, const
     return G;
 }
 
-// COR / BUOY / CLO (0 none, 1 constant ν, κ, 2 eddy-coefficient arrays) are compile-time: the terms of one cell then form ONE basic
+// COR / BUOY / CLO (0 none, 1 constant ν, κ, 2 eddy-coefficient arrays, 3 the same with the tracers' interpolated coefficient divided by
+// the Prandtl number that a.kappa[t] then holds -- Smagorinsky with Pr ≠ 1) are compile-time: the terms of one cell then form ONE basic
 // block whose ~40 loads the compiler issues together -- with run-time flags every term was its own block behind a branch and its
 // loads waited one after the other (0.94 -> see DESIGN.md for the measured time at 256 x 256 x 128).
 template <bool COR, bool BUOY, int CLO>
@@ -810,7 +965,7 @@ __global__ void __launch_bounds__(256) tendency_epilogue_kernel(DGrid g, Epilogu
     const FView &fv = f == 0 ? a.u : (f == 1 ? a.v : (f == 2 ? a.w : a.c[f - 3]));
     const long q = fv.lin(i, j, k);
     double G = a.Gn[f][q];
-    constexpr bool VAR = CLO == 2;
+    constexpr bool VAR = CLO >= 2, PRD = CLO == 3;
     if (f == 0) {
         if (COR) G = G - x_f_cross_U(g, a.fcor, a.v, i, j, k);
         if (BUOY) G = G - hydrostatic_gradient_x(g, a.pHY, i, j, k);
@@ -824,7 +979,7 @@ __global__ void __launch_bounds__(256) tendency_epilogue_kernel(DGrid g, Epilogu
     } else {
         const double kap = a.kappa[f - 3];
         if (CLO && (VAR || kap != 0.0))
-            G = (G - closure_divergence<F_C>(g, a.u, a.v, a.w, a.c[f - 3], kap, i, j, k, VAR, a.kappa_e[f - 3])) + 0.0;
+            G = (G - closure_divergence<F_C, PRD>(g, a.u, a.v, a.w, a.c[f - 3], kap, i, j, k, VAR, a.kappa_e[f - 3])) + 0.0;
     }
     G = epilogue_flux_conditions(g, a, f, i, j, k, q, G);
     if (a.store_G) a.Gn[f][q] = G;

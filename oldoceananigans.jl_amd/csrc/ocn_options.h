@@ -22,6 +22,7 @@ struct OcnOptions {
     int epilogue_rows = 4;             // rows (waves) per block of that kernel
     int epilogue_kchunk = 0;           // levels per block of that kernel (0: automatic)
     int amd_march = 1;                 // eddy diffusivities by the z-marching kernel that shares the point operands (0: one thread per cell, everything recomputed)
+    int smag_march = 1;                // Smagorinsky eddy viscosity by its z-marching kernel (0: one thread per cell, every point value recomputed)
     // halo fills
     int fused_halo = 1;                // triply periodic grids: the three directional periodic fills as one launch
     // pressure solve

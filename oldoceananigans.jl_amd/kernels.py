@@ -68,6 +68,30 @@ def compute_closure_tendencies_field(grid, fields, Gn, νₑ, κₑ, kernel_para
         _ptr_array(κₑ) if κₑ else None, Gn[0].data, Gn[1].data, Gn[2].data, _ptr_array(gc) if gc else None, _range(kernel_parameters)))
 
 
+def compute_smagorinsky_viscosity(grid, closure, buoyancy, tracers_by_name, u, v, w, νₑ, kernel_parameters=None):
+    """compute_diffusivities!(…, closure::Smagorinsky, …) (smagorinsky.jl:113-127) over the interior or `kernel_parameters`; u, v, w and the
+    buoyancy's tracers with filled halos; fill the halos of νₑ afterwards. buoyancy: None | BuoyancyTracer | linear SeawaterBuoyancy"""
+    from .buoyancy import BuoyancyTracer
+    kind, bT, S, g, α, β = 0, None, None, 0.0, 0.0, 0.0
+    if isinstance(buoyancy, BuoyancyTracer):
+        kind, bT = 1, tracers_by_name["b"].data
+    elif buoyancy is not None:
+        e = buoyancy.equation_of_state
+        kind, bT, S = 2, tracers_by_name["T"].data, tracers_by_name["S"].data
+        g, α, β = buoyancy.gravitational_acceleration, e.thermal_expansion, e.haline_contraction
+    _lib.check(_lib.lib().ocn_compute_smagorinsky_viscosity(grid.handle, closure.coefficient, closure.Cb, int(closure.lilly), kind, bT, S, g, α, β,
+                                                            u.data, v.data, w.data, νₑ.data, _range(kernel_parameters)))
+
+
+def compute_closure_tendencies_smagorinsky(grid, fields, Gn, νₑ, closure, tracer_names, kernel_parameters=None):
+    """adds -∂ⱼτᵢⱼ with νₑ and -∇·q with ℑ(νₑ) / Pr[tracer] (smagorinsky.jl:141-143); fields = u, v, w, tracers..., νₑ with filled halos"""
+    parr, pp = closure.Pr_array(tracer_names)
+    tr, gc = fields[3:], Gn[3:]
+    _lib.check(_lib.lib().ocn_compute_closure_tendencies_smagorinsky(
+        grid.handle, fields[0].data, fields[1].data, fields[2].data, _ptr_array(tr) if tr else None, len(tr), νₑ.data, pp,
+        Gn[0].data, Gn[1].data, Gn[2].data, _ptr_array(gc) if gc else None, _range(kernel_parameters)))
+
+
 def update_hydrostatic_pressure(grid, buoyancy, tracers_by_name, pHY):
     """update_hydrostatic_pressure! (update_hydrostatic_pressure.jl:12-49) for BuoyancyTracer | linear SeawaterBuoyancy"""
     from .buoyancy import BuoyancyTracer

@@ -56,10 +56,10 @@ class NonhydrostaticModel:
         if buoyancy is not None and not isinstance(buoyancy, (BuoyancyTracer, SeawaterBuoyancy)):
             raise NotImplementedError("buoyancy must be nothing, BuoyancyTracer() or SeawaterBuoyancy(LinearEquationOfState)")
         self.buoyancy = buoyancy
-        from .closures import AnisotropicMinimumDissipation, ScalarDiffusivity
-        if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation)):
-            raise NotImplementedError("only closure = nothing | ScalarDiffusivity(ν, κ) | AnisotropicMinimumDissipation(C, Cν, Cκ) is on "
-                                      "the accelerated path (SURVEY.md 8f)")
+        from .closures import AnisotropicMinimumDissipation, ScalarDiffusivity, Smagorinsky
+        if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
+            raise NotImplementedError("only closure = nothing | ScalarDiffusivity(ν, κ) | AnisotropicMinimumDissipation(C, Cν, Cκ) | "
+                                      "Smagorinsky(coefficient, Pr) | SmagorinskyLilly(C, Cb, Pr) is on the accelerated path (SURVEY.md 8f)")
         self.closure = closure
         # "Adjust advection scheme to be valid on a particular grid size" and "Adjust halos when the advection scheme or turbulence
         # closure requires it" (nonhydrostatic_model.jl:176-184). The library derives the same per-direction schemes from the grid
@@ -116,6 +116,13 @@ class NonhydrostaticModel:
             D = namedtuple("DiffusivityFields", [unicodedata.normalize("NFKC", n) for n in ("νₑ", "κₑ")])
             K = namedtuple("EddyDiffusivities", self.tracer_names) if self.tracer_names else tuple
             self.diffusivity_fields = D(self._field("nu_e"), K(*[self._field("kappa_e%d" % n) for n in range(len(self.tracer_names))]))
+        elif isinstance(closure, Smagorinsky):
+            self._kappa, pp = closure.Pr_array(self.tracer_names)
+            _lib.check(_lib.lib().ocn_model_set_smagorinsky(self.handle, closure.coefficient, closure.Cb, int(closure.lilly), pp))
+            # build_diffusivity_fields (smagorinsky.jl:131-139): νₑ only
+            import unicodedata
+            D = namedtuple("DiffusivityFields", [unicodedata.normalize("NFKC", "νₑ")])
+            self.diffusivity_fields = D(self._field("nu_e"))
         elif closure is not None:
             self._kappa, kp = closure.kappa_array(self.tracer_names)
             _lib.check(_lib.lib().ocn_model_set_closure(self.handle, closure.ν, kp))
@@ -138,6 +145,8 @@ class NonhydrostaticModel:
                     raise ValueError(f"boundary conditions given for {name}, but the closure has no diffusivity fields")
                 if key in ("νe", "nu_e"):
                     targets.append(("nu_e", fbcs))
+                elif len(self.diffusivity_fields) < 2:
+                    raise ValueError(f"boundary conditions given for {name}, but the closure's diffusivity fields are νₑ only")
                 else:
                     for tracer, tb in dict(fbcs).items():
                         if tracer not in self.tracer_names:

@@ -40,6 +40,16 @@ def cell_diffusion_timescale(model):
             biggest = model.ctx.allreduce_max(biggest)
         with np.errstate(divide="ignore"):
             return float(np.float64(delta ** 2) / np.float64(biggest))
+    from .closures import Smagorinsky
+    if isinstance(closure, Smagorinsky):
+        # Δ² / max(νₑ, νₑ / min Pr) over the model's eddy viscosity (and over the ranks)
+        prs = [closure.Pr[n] for n in model.tracer_names] if isinstance(closure.Pr, dict) else ([closure.Pr] if model.tracer_names else [])
+        biggest = float(np.max(model.diffusivity_fields[0].parent()))
+        if hasattr(model, "ctx") and hasattr(model.ctx, "allreduce_max"):
+            biggest = model.ctx.allreduce_max(biggest)
+        biggest = max(biggest, biggest / min(prs)) if prs else biggest
+        with np.errstate(divide="ignore"):
+            return float(np.float64(delta ** 2) / np.float64(biggest))
     kappas = list(closure.κ.values()) if isinstance(closure.κ, dict) else [closure.κ]
     max_k = max([float(k) for k in kappas] or [0.0])
     with np.errstate(divide="ignore"):
