@@ -346,7 +346,13 @@ int ocn_model_set_option(ocn_model_t model, const char *key, int value);
  * "fuse_substep_active" (1 when the rk3_substep! of stages 2 and 3 is fused into the preceding tendency evaluation: option
  * "fuse_substep" = 1, flux-sharing kernel, tendencies cached by pointer swap, no Flux boundary condition), "substep_in_tendency_kernel"
  * (1 when that substep rides in the tendency launch itself), "forcing_path" (ocn_model_set_forcing), "graph_captures",
- * "graph_replays", "graph_failures" (option "use_graph") and, on a partitioned model, "dist_poisson_layout" */
+ * "graph_replays", "graph_failures" (option "use_graph"), which conditional path the model's pressure solver took -- "fused_zfft_active"
+ * (1 when solve_for_pressure! runs the z transform, the divide and the inverse z transform as one pass: options "real_fft" and
+ * "fused_zfft", FFT solver, Nz = 2^m in 8 .. 1024), "c2r_strided_active" (1 when the Z2D plan writes into the haloed pressure field:
+ * options "real_fft" and "c2r_strided" AND rocFFT accepted the plan); both 0 on a partitioned model -- and, on a partitioned model,
+ * "dist_poisson_layout", "dist_yline_active" (1 when the local y transform runs in the LDS line kernel: option "dist_yline", z Bounded,
+ * Ny = 2^m in 8 .. 1024 and the kernel passed its check at creation) and "dist_xline_group_active" (1 when the Thomas scans of the
+ * x-fastest solve run several lines per wave: option "dist_xline_group", local Nx 32, 64 or 128); both 0 on a single-GPU model */
 int ocn_model_get_option(ocn_model_t model, const char *key, int *value);
 /* boundary_conditions = (name = FieldBoundaryConditions(side = BoundaryCondition(kind, value)),) of the model
  * constructor (nonhydrostatic_model.jl:115-244); name "u","v","w","c0".. and, with an LES closure, the diffusivity fields "nu_e",
@@ -410,7 +416,8 @@ int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *ter
  * Grid-level entry points and standalone solvers (ocn_compute_*, ocn_fill_halo_regions*, ocn_poisson_*, ocn_solve_for_pressure,
  * ocn_dist_poisson_*) read the defaults when they are called.
  * Scopes: step -- read while stepping; creation -- read only when a model or solver is built, so set it with ocn_set_option before
- * creating the model; partitioned -- read by the partitioned step only. Values are 0 / 1 unless a range is given.
+ * creating the model; partitioned -- read by the partitioned step only. Values are 0 / 1 unless a range is given; every key refuses
+ * a value outside its range.
  *   tendency evaluation:
  *   "tendency_impl" = 2 (step): 0 the per-field kernels as the reference launches them, 1 the all-fields flux-sharing kernel, 2 the
  *       one-field-per-workgroup flux-sharing kernel; 0 .. 2 (the grid-level tendency entry points take 1 for 0)
@@ -420,7 +427,8 @@ int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *ter
  *       advecting transport multiplied by the area after its interpolation): fewer FP64 instructions, fields within 1e-12 of mode 0
  *       on O(1) data but not bit-identical; the other tendency kernels ignore it
  *   "role_kchunk" = 0 (step): levels per workgroup of the one-field-per-workgroup kernel, >= 0 (0 = automatic)
- *   "role_ldspad" = 0 (step): extra dynamic LDS per workgroup of that kernel in bytes (experiments)
+ *   "role_ldspad" = 0 (step): extra dynamic LDS per workgroup of that kernel in bytes (experiments), 0 .. 148256 (what the 160 KiB of a
+ *       CU leave beside the kernel's own arrays)
  *   "fused_ty" = 7 (step): tile rows of the all-fields kernel, 3 | 7
  *   "fused_kchunk" = 0 (step): levels per workgroup of the all-fields kernel, >= 0 (0 = automatic)
  *   "fused_zwin" = 1 (step): register z-windows in the all-fields kernel
@@ -464,7 +472,7 @@ int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *ter
  *   "async_halos" = -1 (partitioned): interior / buffer split of update_state! (-1 automatic, 0 off, 1 on)
  *   "thin_halos" = 1 (partitioned): the pressure step exchanges the one column that is read instead of Hx columns
  *   "early_exchange" = 1 (partitioned): update_state!'s exchange starts from make_pressure_correction!
- *   "strip_width" = 0 (partitioned): columns of the buffer strips (0 = automatic)
+ *   "strip_width" = 0 (partitioned): columns of the buffer strips, >= 0 (0 = automatic; the step needs Hx <= width < Nx / 2)
  *   "fused_step" (alias "dist_fused_step") = 1 (partitioned): the pressure step without fills / copies between its stages on
  *       (connected, Periodic, Periodic) slabs; its buffers are made when a model is created with it, so switching it on later
  *       needs a model created with it (OCN_ENOTSUP otherwise)

@@ -1035,11 +1035,12 @@ static inline void launch_paired_zline(const OcnOptions &o, bool forward, const 
         else         hipLaunchKernelGGL(paired_zline_c2r_kernel<8>, grd, dim3(256), lds, g_stream, in, out, tw, C, N, logn, scale);
     }
 }
+// short lines (thin slabs) take the grouped Thomas kernels: 4 elements per lane and N / 4 lanes per line -- 2, 4 or 8 lines per wave
+static inline bool xline_grouped(const OcnOptions &o, int N) { return o.dist_xline_group && (N == 32 || N == 64 || N == 128); }
 template <bool SOLVE>
 static inline void launch_xline_thomas(const OcnOptions &o, int E, double2 *S, const double *rden, long M, int N, double a, double2 *payload, const double2 *iface, double scale) {
     const dim3 blk(256);
-    // short lines (thin slabs): 4 elements per lane and N / 4 lanes per line -- 2, 4 or 8 lines per wave
-    if (o.dist_xline_group && (N == 32 || N == 64 || N == 128)) {
+    if (xline_grouped(o, N)) {
         const int lpw = 256 / N;
         const dim3 grp((unsigned)((M + 4 * lpw - 1) / (4 * lpw)));
         if (N == 32)       hipLaunchKernelGGL((xline_thomas_kernel<4, SOLVE, 8>), grp, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale);
@@ -2584,45 +2585,53 @@ struct OptionRow {
     const char *alias;            // the library's earlier name of the same option
 };
 static bool nonneg(int v) { return v >= 0; }
+static bool onoff(int v) { return v == 0 || v == 1; }
+// role_ldspad is dynamic LDS beside the role kernel's static arrays, FX[2][TY][66] and FY[2][TY + 1][64] doubles (role_tendency_kernel):
+// a workgroup may hold at most the 160 KiB of a CU, so what is left for the pad is 163840 bytes minus those arrays (148256 at TY = 7);
+// a larger request fails the launch
+static constexpr int kRoleStaticLds = 8 * (2 * OCN_ROLE_TY * 66 + 2 * (OCN_ROLE_TY + 1) * 64);
+static constexpr int kRoleLdspadMax = 160 * 1024 - kRoleStaticLds;
+static_assert(kRoleLdspadMax == 148256 || OCN_ROLE_TY != 7, "the message of role_ldspad states the bound at TY = 7");
+static bool ldspad_fits(int v) { return v >= 0 && v <= kRoleLdspadMax; }
 static const OptionRow kOptions[] = {
     {"tendency_impl", &OcnOptions::tendency_impl, OPT_STEP, [](int v) { return v >= 0 && v <= 2; }, "tendency_impl is 0, 1 or 2"},
     {"arithmetic", &OcnOptions::arithmetic, OPT_STEP, [](int v) { return v == 0 || v == 1; }, "arithmetic is 0 (reference sequence) or 1 (contracted)"},
     {"role_kchunk", &OcnOptions::role_kchunk, OPT_STEP, nonneg, "role_kchunk must be >= 0 (0 = automatic)"},
-    {"role_ldspad", &OcnOptions::role_ldspad, OPT_STEP},
-    {"fused_ty", &OcnOptions::fused_ty, OPT_STEP},
+    {"role_ldspad", &OcnOptions::role_ldspad, OPT_STEP, ldspad_fits, "role_ldspad is 0 .. 148256 bytes (the 160 KiB of a CU minus the kernel's own LDS)"},
+    {"fused_ty", &OcnOptions::fused_ty, OPT_STEP, [](int v) { return v == 3 || v == 7; }, "fused_ty is 3 or 7"},
     {"fused_kchunk", &OcnOptions::fused_kchunk, OPT_STEP, nonneg, "fused_kchunk must be >= 0 (0 = automatic)"},
-    {"fused_zwin", &OcnOptions::fused_zwin, OPT_STEP},
-    {"fused_xcd", &OcnOptions::fused_xcd, OPT_STEP},
-    {"epilogue_march", &OcnOptions::epilogue_march, OPT_STEP},
+    {"fused_zwin", &OcnOptions::fused_zwin, OPT_STEP, onoff, "fused_zwin is 0 or 1"},
+    {"fused_xcd", &OcnOptions::fused_xcd, OPT_STEP, onoff, "fused_xcd is 0 or 1"},
+    {"epilogue_march", &OcnOptions::epilogue_march, OPT_STEP, onoff, "epilogue_march is 0 or 1"},
     {"epilogue_rows", &OcnOptions::epilogue_rows, OPT_STEP, [](int v) { return v >= 1 && v <= 8; }, "epilogue_rows is 1 .. 8"},
     {"epilogue_kchunk", &OcnOptions::epilogue_kchunk, OPT_STEP, nonneg, "epilogue_kchunk must be >= 0 (0 = automatic)"},
-    {"amd_march", &OcnOptions::amd_march, OPT_STEP},
-    {"smag_march", &OcnOptions::smag_march, OPT_STEP},
-    {"fused_halo", &OcnOptions::fused_halo, OPT_STEP},
-    {"real_fft", &OcnOptions::real_fft, OPT_STEP},
-    {"c2r_strided", &OcnOptions::c2r_strided, OPT_CREATION},
-    {"fused_zfft", &OcnOptions::fused_zfft, OPT_CREATION},
-    {"split_solve", &OcnOptions::split_solve, OPT_STEP},
+    {"amd_march", &OcnOptions::amd_march, OPT_STEP, onoff, "amd_march is 0 or 1"},
+    {"smag_march", &OcnOptions::smag_march, OPT_STEP, onoff, "smag_march is 0 or 1"},
+    {"fused_halo", &OcnOptions::fused_halo, OPT_STEP, onoff, "fused_halo is 0 or 1"},
+    {"real_fft", &OcnOptions::real_fft, OPT_STEP, onoff, "real_fft is 0 or 1"},
+    {"c2r_strided", &OcnOptions::c2r_strided, OPT_CREATION, onoff, "c2r_strided is 0 or 1"},
+    {"fused_zfft", &OcnOptions::fused_zfft, OPT_CREATION, onoff, "fused_zfft is 0 or 1"},
+    {"split_solve", &OcnOptions::split_solve, OPT_STEP, onoff, "split_solve is 0 or 1"},
     {"line_zl512", &OcnOptions::line_zl512, OPT_STEP, [](int v) { return v == 4 || v == 8; }, "line_zl512 is 4 or 8"},
-    {"skip_stage_pressure", &OcnOptions::skip_stage_pressure, OPT_STEP},
-    {"skip_dead_tendency_store", &OcnOptions::skip_dead_tendency_store, OPT_STEP},
-    {"dist_substructured", &OcnOptions::dist_substructured, OPT_CREATION},
-    {"dist_zfirst", &OcnOptions::dist_zfirst, OPT_CREATION},
-    {"dist_xfast", &OcnOptions::dist_xfast, OPT_CREATION},
-    {"dist_yline", &OcnOptions::dist_yline, OPT_CREATION},
-    {"dist_fuse_source", &OcnOptions::dist_fuse_source, OPT_STEP},
-    {"dist_xline_group", &OcnOptions::dist_xline_group, OPT_STEP},
-    {"dist_pencil_transposes", &OcnOptions::dist_pencil_transposes, OPT_CREATION},
-    {"swap_tendencies", &OcnOptions::swap_tendencies, OPT_STEP},
-    {"fuse_substep", &OcnOptions::fuse_substep, OPT_STEP},
-    {"fused_epilogue", &OcnOptions::fused_epilogue, OPT_STEP},
-    {"fused_forcing", &OcnOptions::fused_forcing, OPT_STEP},
-    {"use_graph", &OcnOptions::use_graph, OPT_STEP},
-    {"async_halos", &OcnOptions::async_halos, OPT_PARTITIONED},
-    {"thin_halos", &OcnOptions::thin_halos, OPT_PARTITIONED},
-    {"early_exchange", &OcnOptions::early_exchange, OPT_PARTITIONED},
-    {"strip_width", &OcnOptions::strip_width, OPT_PARTITIONED},
-    {"fused_step", &OcnOptions::fused_step, OPT_PARTITIONED, nullptr, nullptr, "dist_fused_step"},
+    {"skip_stage_pressure", &OcnOptions::skip_stage_pressure, OPT_STEP, onoff, "skip_stage_pressure is 0 or 1"},
+    {"skip_dead_tendency_store", &OcnOptions::skip_dead_tendency_store, OPT_STEP, onoff, "skip_dead_tendency_store is 0 or 1"},
+    {"dist_substructured", &OcnOptions::dist_substructured, OPT_CREATION, onoff, "dist_substructured is 0 or 1"},
+    {"dist_zfirst", &OcnOptions::dist_zfirst, OPT_CREATION, onoff, "dist_zfirst is 0 or 1"},
+    {"dist_xfast", &OcnOptions::dist_xfast, OPT_CREATION, onoff, "dist_xfast is 0 or 1"},
+    {"dist_yline", &OcnOptions::dist_yline, OPT_CREATION, onoff, "dist_yline is 0 or 1"},
+    {"dist_fuse_source", &OcnOptions::dist_fuse_source, OPT_STEP, onoff, "dist_fuse_source is 0 or 1"},
+    {"dist_xline_group", &OcnOptions::dist_xline_group, OPT_STEP, onoff, "dist_xline_group is 0 or 1"},
+    {"dist_pencil_transposes", &OcnOptions::dist_pencil_transposes, OPT_CREATION, onoff, "dist_pencil_transposes is 0 or 1"},
+    {"swap_tendencies", &OcnOptions::swap_tendencies, OPT_STEP, onoff, "swap_tendencies is 0 or 1"},
+    {"fuse_substep", &OcnOptions::fuse_substep, OPT_STEP, onoff, "fuse_substep is 0 or 1"},
+    {"fused_epilogue", &OcnOptions::fused_epilogue, OPT_STEP, onoff, "fused_epilogue is 0 or 1"},
+    {"fused_forcing", &OcnOptions::fused_forcing, OPT_STEP, onoff, "fused_forcing is 0 or 1"},
+    {"use_graph", &OcnOptions::use_graph, OPT_STEP, onoff, "use_graph is 0 or 1"},
+    {"async_halos", &OcnOptions::async_halos, OPT_PARTITIONED, [](int v) { return v >= -1 && v <= 1; }, "async_halos is -1 (automatic), 0 or 1"},
+    {"thin_halos", &OcnOptions::thin_halos, OPT_PARTITIONED, onoff, "thin_halos is 0 or 1"},
+    {"early_exchange", &OcnOptions::early_exchange, OPT_PARTITIONED, onoff, "early_exchange is 0 or 1"},
+    {"strip_width", &OcnOptions::strip_width, OPT_PARTITIONED, nonneg, "strip_width must be >= 0 (0 = automatic)"},
+    {"fused_step", &OcnOptions::fused_step, OPT_PARTITIONED, onoff, "fused_step is 0 or 1", "dist_fused_step"},
 };
 
 static const OptionRow *find_option(const char *key) {
@@ -2850,6 +2859,15 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     // what the tendency LAUNCH itself carries (bench.py prices its bytes with these): the next stage's substep rides in the advection kernel
     // only without physics / Flux conditions (with them it rides in the epilogue pass); the tendency of the second stage is then not stored
     if (!strcmp(key, "substep_in_tendency_kernel")) { *value = (can_fuse_substep(m) && !epilogue_runs(m)) ? 1 : 0; return OCN_OK; }
+    // which path solve_for_pressure! takes on this model's solver: the real-transform path (option real_fft, plans that passed their check)
+    // with the z transform fused into the spectral divide, and with the Z2D plan that writes into the haloed pressure field -- rocFFT
+    // may refuse that plan, the solver then keeps the dense one. Both 0 on the complex path and on a partitioned model (its own solver)
+    if (!strcmp(key, "fused_zfft_active") || !strcmp(key, "c2r_strided_active")) {
+        const ocn_poisson_s *s = m->solver;
+        const bool real_path = s && m->opt.real_fft && !s->general && s->has_r2c && s->has_c2r;
+        *value = !real_path ? 0 : (key[0] == 'f' ? (s->kind == 0 && s->zfused) : s->c2r_strided) ? 1 : 0;
+        return OCN_OK;
+    }
     if (!strcmp(key, "fused_tendency_active")) { *value = fused_path(m->opt, m->grid->d, nullptr, m->ntr, m->opt.tendency_impl) ? 1 : 0; return OCN_OK; }
     return fail(OCN_EINVAL, "unknown model option '%s'", key);
 }

@@ -939,11 +939,14 @@ static int dist_model_create(ocn_model_t *model, ocn_grid_t local_grid, int ntra
 static bool dist_fused_step_buffers(const ocn_model_s *m) { return m->dm && m->dm->cws; }
 
 // the model options that depend on the partition: whether the fused pressure step runs (0 on a single-GPU model) and which distributed
-// pressure solver the model runs -- ocn_dist_poisson_layout's code (4 x-fastest, 1..3 z-fastest, 0 paired columns, -1 transposing),
+// pressure solver the model runs (and whether its y-line kernel / grouped x-line kernel are in use) -- ocn_dist_poisson_layout's code (4 x-fastest, 1..3 z-fastest, 0 paired columns, -1 transposing),
 // -2 = the gathered solve on the global grid, -3 = the pencil transposes (TransposableField)
 static int dist_model_get_option(const ocn_model_s *m, const char *key, int *value) {
     const DistModel *dm = m->dm;
     if (!strcmp(key, "fused_step")) { *value = dm && dm->fused(m->opt) ? 1 : 0; return OCN_OK; }
+    // the conditional kernels of the partitioned solver: 0 on a single-GPU model
+    if (!strcmp(key, "dist_yline_active")) { *value = dm && dm->solver && dm->solver->yline ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "dist_xline_group_active")) { *value = dm && dm->solver && dm->solver->xfast && xline_grouped(m->opt, dm->solver->Nxl) ? 1 : 0; return OCN_OK; }
     if (!dm || strcmp(key, "dist_poisson_layout")) return -1;
     *value = dm->gs ? -2 : (dm->ps ? -3 : -1);
     return dm->solver ? ocn_dist_poisson_layout(dm->solver, value) : OCN_OK;

@@ -324,6 +324,10 @@ def _run_library_ranks(ocn, arch, R, size, nsteps, zkind, options, xbounded=Fals
     return results
 
 
+_CREATION_KEYS = ("dist_yline",)
+_PATH_KEYS = {"dist_yline": "dist_yline_active", "dist_xline_group": "dist_xline_group_active"}
+
+
 @pytest.mark.parametrize("R,size,zkind,options", [
     (2, (32, 16, 8), "periodic", {}),                                   # both neighbours are the same rank
     (2, (32, 16, 8), "periodic", {"async_halos": 0}),
@@ -336,12 +340,33 @@ def _run_library_ranks(ocn, arch, R, size, nsteps, zkind, options, xbounded=Fals
     (2, (32, 16, 8), "bounded", {}),                                    # distributed Fourier-tridiagonal solver + ScalarDiffusivity + buoyancy
     (8, (64, 8, 8), "stretched", {}),                                   # transposing solver over 8 ranks, Coriolis, boundary conditions
     (4, (32, 12, 10), "amd", {}),                                       # the configs[4] physics
+    # the non-default solver paths (tests/option_variants.py); _PATH_KEYS below: the model says on every rank which path it took
+    (2, (32, 16, 8), "bounded", {"dist_yline": 0}),                     # Bounded z, Ny = 16: rocFFT's strided 1-D y plan instead of the LDS line kernel
+    (2, (64, 16, 8), "periodic", {"dist_xline_group": 0}),              # local lines of 32 points, one line per wave
+    (2, (128, 16, 8), "periodic", {"dist_xline_group": 0}),             # local lines of 64 points, one line per wave
+    (2, (32, 16, 8), "periodic", {"early_exchange": 0, "async_halos": 1, "strip_width": 5}),    # buffer strips of 5 columns: Hx <= 5 < 16 / 2
 ])
 def test_library_virtual_ranks_match_single_gpu(ocn, oracle, arch, R, size, zkind, options):
-    """R virtual ranks of the in-library partitioned model against the single-GPU model AND against the serial oracle"""
+    """R virtual ranks of the in-library partitioned model against the single-GPU model AND against the serial oracle. Rows that switch a
+    conditional solver path off: the model reports the path off on every rank, and on with the default options on the same grid."""
     _own_stream()
     nsteps = 3
-    results = _run_library_ranks(ocn, arch, R, size, nsteps, zkind, options)
+    creation = {k: options[k] for k in options if k in _CREATION_KEYS}          # read when the model is built: library defaults around the run
+    paths = [k for k in options if k in _PATH_KEYS]
+    seen = []
+    if paths:
+        _run_library_ranks(ocn, arch, R, size, 0, zkind, {}, probe=lambda m: seen.append([m.get_option(_PATH_KEYS[k]) for k in paths]))
+        assert seen == [[1] * len(paths)] * R, ("default options", paths, seen)
+        del seen[:]
+    for k, v in creation.items():
+        ocn.set_option(k, v)
+    try:
+        results = _run_library_ranks(ocn, arch, R, size, nsteps, zkind, {k: v for k, v in options.items() if k not in creation},
+                                     probe=lambda m: seen.append([m.get_option(_PATH_KEYS[k]) for k in paths]))
+    finally:
+        for k in creation:
+            ocn.set_option(k, 1)
+    assert seen == [[options[k] for k in paths]] * R, (paths, seen)
     ref, time, _ = _single_gpu(ocn, arch, size, zkind, nsteps)
     nxl = size[0] // R
     for r, (out, div, t, _off) in enumerate(results):

@@ -13,7 +13,7 @@ flds = model.fields()
 vals = smooth_state({n: grid.nodes(f.loc) for n, f in flds.items()}, 1234)
 ocn.set_model(model, **vals)
 ref = None
-variants = [(0, 8, 16, 0, 0), (1, 7, 0, 1, 0), (1, 7, 0, 1, 1), (1, 7, 32, 1, 1), (1, 7, 52, 1, 1), (1, 7, 22, 1, 1)]
+variants = [(0, 7, 16, 0, 0), (1, 7, 0, 1, 0), (1, 7, 0, 1, 1), (1, 7, 32, 1, 1), (1, 7, 52, 1, 1), (1, 7, 22, 1, 1)]
 for impl, ty, kc, zw, lds in variants:
     model.set_option("tendency_impl", impl); model.set_option("fused_ty", ty); model.set_option("fused_kchunk", kc); model.set_option("fused_zwin", zw);
     ocn.update_state(model, True); ocn.synchronize()
