@@ -159,6 +159,20 @@ int ocn_add_fplane_coriolis(ocn_grid_t grid, double f, const double *u, const do
 int ocn_compute_closure_tendencies(ocn_grid_t grid, const double *u, const double *v, const double *w,
                                    const double *const *tracers, int ntracers, double nu, const double *kappa,
                                    double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range);
+/* the explicit part of closure = ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ν, κ) on a vertically Bounded grid
+ * (abstract_scalar_diffusivity_closure.jl:245-291): as above, but only the z fluxes at the indices k == 1 | k == Nz + 1 are the explicit
+ * ones; elsewhere viscous_flux_uz = -(ν ∂xᶠᶜᶠ w), viscous_flux_vz = -(ν ∂yᶜᶠᶠ w), viscous_flux_wz = 0, diffusive_flux_z = 0.
+ * OCN_EINVAL when z is not Bounded. */
+int ocn_compute_closure_tendencies_vertically_implicit(ocn_grid_t grid, const double *u, const double *v, const double *w,
+                                                       const double *const *tracers, int ntracers, double nu, const double *kappa,
+                                                       double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range);
+/* implicit_step!(field, implicit_solver, closure, ..., Δt) of one field for constant coefficients (TurbulenceClosures/
+ * vertically_implicit_diffusion_solver.jl:58-121,189-213; solve! of Solvers/batched_tridiagonal_solver.jl:110-133,219-245): solves
+ * (1 - Δt ∂z coef ∂z) ϕ = ϕ in place over the columns (1..Nx, 1..Ny) and the levels 1..Nz of a haloed field at the location of u, v, w or
+ * a tracer; coef = ν for velocities, κ for the tracer. form: 0, the reference-shaped kernel (every thread runs the reference's loop for
+ * its column, scratch t in memory) -- the tuned forms that were tried measured slower and are not shipped, any other
+ * value answers OCN_EINVAL. OCN_EINVAL when z is not Bounded. */
+int ocn_implicit_step_z(ocn_grid_t grid, double *field, const int loc[3], double coef, double dt, int form);
 /* the same with the coefficients read from ccc arrays with filled halos -- the eddy viscosity / diffusivities of an LES closure,
  * interpolated to the flux locations (abstract_scalar_diffusivity_closure.jl:310-330: ν[i,j,k], ℑxyᶠᶠᵃ, ℑxzᶠᵃᶠ, ℑyzᵃᶠᶠ, ℑxᶠᵃᵃ, ...) */
 int ocn_compute_closure_tendencies_field(ocn_grid_t grid, const double *u, const double *v, const double *w,
@@ -366,6 +380,13 @@ int ocn_model_set_buoyancy(ocn_model_t model, int kind, int b_or_T_index, int S_
 int ocn_model_set_coriolis(ocn_model_t model, int enabled, double f);
 /* closure = ScalarDiffusivity(ν = nu, κ = kappa[tracer]) of the model constructor; all zeros / NULL: closure = nothing */
 int ocn_model_set_closure(ocn_model_t model, double nu, const double *kappa);
+/* time discretisation of the model's ScalarDiffusivity (scalar_diffusivity.jl:116-141): enabled = 1 is
+ * VerticallyImplicitTimeDiscretization() -- the tendencies keep the explicit part only and every substep of RK3 / AB2 is followed by
+ * implicit_step! of each prognostic field (runge_kutta_3.jl:179-203, quasi_adams_bashforth_2.jl:127-154); 0 is ExplicitTimeDiscretization().
+ * OCN_EINVAL when z is not Bounded ("VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the
+ * z-direction.", vertically_implicit_diffusion_solver.jl:149-153); OCN_ENOTSUP with an AMD or Smagorinsky closure, and setting one of
+ * those clears it. ocn_model_get_option answers "vertically_implicit", "implicit_step_form" and "epilogue_march_active". */
+int ocn_model_set_vertically_implicit(ocn_model_t model, int enabled);
 /* closure = AnisotropicMinimumDissipation(Cν = Cnu, Cκ = Ckappa[tracer]) (replaces a ScalarDiffusivity). update_state! then
  * computes the model fields "nu_e", "kappa_e0", ... and fills their halos before the tendencies. */
 int ocn_model_set_amd(ocn_model_t model, double Cnu, const double *Ckappa);

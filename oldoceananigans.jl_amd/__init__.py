@@ -11,7 +11,8 @@ from .boundary_conditions import (BoundaryCondition, FieldBoundaryConditions, Fl
                                   GradientBoundaryCondition, LinearFieldFlux, OpenBoundaryCondition, ValueBoundaryCondition, compute_flux_bcs)
 from .buoyancy import BuoyancyTracer, FPlane, LinearEquationOfState, SeawaterBuoyancy
 from .checkpointer import set_from_checkpoint, write_checkpoint
-from .closures import AnisotropicMinimumDissipation, DynamicCoefficient, ScalarDiffusivity, Smagorinsky, SmagorinskyLilly
+from .closures import (AnisotropicMinimumDissipation, DynamicCoefficient, ExplicitTimeDiscretization, ScalarDiffusivity, Smagorinsky,
+                       SmagorinskyLilly, VerticalScalarDiffusivity, VerticallyImplicitTimeDiscretization)
 from .forcings import (AdvectiveForcing, ContinuousForcing, DiscreteForcing, Forcing, GaussianMask, LinearTarget, MultipleForcings,
                        PiecewiseLinearMask, Relaxation)
 from .fields import (CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions, interior, set_)

@@ -115,6 +115,9 @@ SYMBOLS = {
     "ocn_debug_rcp64_check": (C.c_int, [C.c_ulonglong, C.c_int, C.c_int, C.c_ulonglong, C.POINTER(C.c_ulonglong)]),
     "ocn_compute_closure_tendencies": (C.c_int, [_vp, _vp, _vp, _vp, _pp, C.c_int, C.c_double, _dp, _vp, _vp, _vp, _pp, _ip]),
     "ocn_model_set_closure": (C.c_int, [_vp, C.c_double, _dp]),
+    "ocn_compute_closure_tendencies_vertically_implicit": (C.c_int, [_vp, _vp, _vp, _vp, _pp, C.c_int, C.c_double, _dp, _vp, _vp, _vp, _pp, _ip]),
+    "ocn_implicit_step_z": (C.c_int, [_vp, _vp, _ip, C.c_double, C.c_double, C.c_int]),
+    "ocn_model_set_vertically_implicit": (C.c_int, [_vp, C.c_int]),
     "ocn_model_set_amd": (C.c_int, [_vp, C.c_double, _dp]),
     "ocn_compute_closure_tendencies_field": (C.c_int, [_vp, _vp, _vp, _vp, _pp, C.c_int, _vp, _pp, _vp, _vp, _vp, _pp, _ip]),
     "ocn_compute_amd_diffusivities": (C.c_int, [_vp, C.c_double, _dp, _vp, _vp, _vp, _pp, C.c_int, _vp, _pp, _ip]),

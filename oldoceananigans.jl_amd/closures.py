@@ -1,5 +1,5 @@
-"""Turbulence closures on the accelerated path: ScalarDiffusivity with constant isotropic ν, κ and explicit time
-discretisation (reference: TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl), and (8f.2)
+"""Turbulence closures on the accelerated path: ScalarDiffusivity with constant isotropic ν, κ and explicit or
+vertically implicit time discretisation (reference: TurbulenceClosures/turbulence_closure_implementations/scalar_diffusivity.jl), and (8f.2)
 AnisotropicMinimumDissipation with constant Poincaré coefficients (…/anisotropic_minimum_dissipation.jl), and Smagorinsky /
 SmagorinskyLilly with constant coefficients (…/Smagorinskys/smagorinsky.jl, lilly_coefficient.jl)."""
 import ctypes as C
@@ -7,10 +7,61 @@ import ctypes as C
 import numpy as np
 
 
-class ScalarDiffusivity:
-    """ScalarDiffusivity(ν = 0, κ = 0): κ a number (all tracers) or a dict tracer-name -> number (scalar_diffusivity.jl:21-118)."""
+class ExplicitTimeDiscretization:
+    """A fully-explicit time-discretization of a TurbulenceClosure (implicit_explicit_time_discretization.jl:5-12)."""
 
-    def __init__(self, ν=0.0, κ=0.0, nu=None, kappa=None):
+    def __repr__(self):
+        return "ExplicitTimeDiscretization"
+
+    def __eq__(self, other):
+        return type(other) is type(self)
+
+    __hash__ = object.__hash__
+
+
+class VerticallyImplicitTimeDiscretization(ExplicitTimeDiscretization):
+    """A vertically-implicit time-discretization of a TurbulenceClosure (implicit_explicit_time_discretization.jl:14-28):
+    [∇ ⋅ q]ⁿ = [explicit_flux_divergence]ⁿ + [∂z (κ ∂z c)]ⁿ⁺¹, the implicit part solved after every substep (implicit_step!)."""
+
+    def __repr__(self):
+        return "VerticallyImplicitTimeDiscretization"
+
+
+def _is_time_discretization(x):
+    return isinstance(x, ExplicitTimeDiscretization) or (isinstance(x, type) and issubclass(x, ExplicitTimeDiscretization))
+
+
+def _time_discretization(td):
+    if isinstance(td, type) and issubclass(td, ExplicitTimeDiscretization):
+        td = td()
+    if not isinstance(td, ExplicitTimeDiscretization):
+        raise TypeError("time_discretization must be ExplicitTimeDiscretization() or VerticallyImplicitTimeDiscretization()")
+    return td
+
+
+def is_vertically_implicit(closure):
+    """is_vertically_implicit(closure) (vertically_implicit_diffusion_solver.jl:178)"""
+    return isinstance(getattr(closure, "time_discretization", None), VerticallyImplicitTimeDiscretization)
+
+
+class ScalarDiffusivity:
+    """ScalarDiffusivity(time_discretization = ExplicitTimeDiscretization(), ν = 0, κ = 0) (scalar_diffusivity.jl:21-141): the time
+    discretisation is the first positional argument or a keyword; a number in first position is ν. κ a number (all tracers) or a dict
+    tracer-name -> number."""
+
+    def __init__(self, *args, ν=0.0, κ=0.0, nu=None, kappa=None, time_discretization=None):
+        args = list(args)
+        if args and _is_time_discretization(args[0]):
+            if time_discretization is not None:
+                raise TypeError("time_discretization given twice")
+            time_discretization = args.pop(0)
+        if len(args) > 2:
+            raise TypeError("ScalarDiffusivity([time_discretization,] ν, κ)")
+        if args:
+            ν = args.pop(0)
+        if args:
+            κ = args.pop(0)
+        self.time_discretization = _time_discretization(ExplicitTimeDiscretization() if time_discretization is None else time_discretization)
         ν = ν if nu is None else nu
         κ = κ if kappa is None else kappa
         if callable(ν) or callable(κ) or (isinstance(κ, dict) and any(callable(x) for x in κ.values())):
@@ -33,7 +84,20 @@ class ScalarDiffusivity:
         return arr, arr.ctypes.data_as(C.POINTER(C.c_double))
 
     def __repr__(self):
-        return f"ScalarDiffusivity{{ExplicitTimeDiscretization}}(ν={self.ν}, κ={self.κ})"
+        return f"ScalarDiffusivity{{{self.time_discretization!r}}}(ν={self.ν}, κ={self.κ})"
+
+
+def VerticalScalarDiffusivity(*args, **kwargs):
+    """VerticalScalarDiffusivity(...) (scalar_diffusivity.jl:120-121): named so that it can be refused -- the vertical formulation needs its
+    own explicit flux kernels"""
+    raise NotImplementedError("VerticalScalarDiffusivity is not on the accelerated path: only the isotropic ScalarDiffusivity is")
+
+
+def _refuse_vertically_implicit(name, time_discretization):
+    """the eddy-coefficient closures are accelerated with ExplicitTimeDiscretization only"""
+    if time_discretization is not None and isinstance(_time_discretization(time_discretization), VerticallyImplicitTimeDiscretization):
+        raise NotImplementedError(f"{name} with VerticallyImplicitTimeDiscretization is not on the accelerated path: its coefficients "
+                                  "differ from column to column")
 
 
 class AnisotropicMinimumDissipation:
@@ -41,7 +105,10 @@ class AnisotropicMinimumDissipation:
     Cκ a number (all tracers) or a dict tracer-name -> number. The eddy viscosity / diffusivities are the model's
     `diffusivity_fields` (νₑ, κₑ)."""
 
-    def __init__(self, C=1 / 3, Cν=None, Cκ=None, Cb=None, Cnu=None, Ckappa=None):
+    def __init__(self, C=1 / 3, Cν=None, Cκ=None, Cb=None, Cnu=None, Ckappa=None, time_discretization=None):
+        if _is_time_discretization(C):                  # AnisotropicMinimumDissipation(time_discretization; C, ...) (:128)
+            C, time_discretization = 1 / 3, C
+        _refuse_vertically_implicit("AnisotropicMinimumDissipation", time_discretization)
         Cν = Cν if Cnu is None else Cnu
         Cκ = Cκ if Ckappa is None else Ckappa
         if Cb is not None:
@@ -85,7 +152,10 @@ class Smagorinsky:
     lilly = False
     Cb = 0.0
 
-    def __init__(self, coefficient=0.16, Pr=1.0):
+    def __init__(self, coefficient=0.16, Pr=1.0, time_discretization=None):
+        if _is_time_discretization(coefficient):        # Smagorinsky(time_discretization; coefficient, Pr) (smagorinsky.jl:62)
+            coefficient, time_discretization = 0.16, coefficient
+        _refuse_vertically_implicit(type(self).__name__, time_discretization)
         if isinstance(coefficient, DynamicCoefficient) or callable(coefficient):
             raise NotImplementedError("only a constant (Number) Smagorinsky coefficient is on the accelerated path")
         if callable(Pr) or (isinstance(Pr, dict) and any(callable(x) for x in Pr.values())):
@@ -118,10 +188,12 @@ class SmagorinskyLilly(Smagorinsky):
 
     lilly = True
 
-    def __init__(self, C=0.16, Cb=1.0, Pr=1.0):
+    def __init__(self, C=0.16, Cb=1.0, Pr=1.0, time_discretization=None):
+        if _is_time_discretization(C):
+            C, time_discretization = 0.16, C
         if callable(Cb):
             raise NotImplementedError("only a constant (Number) reduction factor Cb is on the accelerated path")
-        super().__init__(coefficient=C, Pr=Pr)
+        super().__init__(coefficient=C, Pr=Pr, time_discretization=time_discretization)
         self.Cb = float(Cb)
 
     def __repr__(self):

@@ -8,6 +8,7 @@
 #include "ocn_tendency_roles.h"
 #include "ocn_epilogue_march.h"
 #include "ocn_forcing.h"
+#include "ocn_implicit_z.h"
 #include <hipfft/hipfft.h>
 #include <cmath>
 #include <cstdarg>
@@ -163,6 +164,8 @@ struct ocn_grid_s {
     // -- RectilinearGrid(halo = (1, 1, 1)), what test/test_halo_regions.jl fills -- serves fields, halo fills and the Poisson
     // solvers; tendencies and models need the halo the reference's model constructor would inflate it to.
     std::string advection_error;
+    // scratch t of the vertically implicit solve (ocn_implicit_z.h), Nx Ny Nz, allocated on first use
+    double *ivd_scratch = nullptr;
 };
 
 static void parent_size(const DGrid &g, const int loc[3], int P[3]) {
@@ -277,6 +280,7 @@ extern "C" int ocn_grid_create(ocn_grid_t *grid, const int N[3], const int H[3],
 extern "C" int ocn_grid_destroy(ocn_grid_t grid) {
     if (!grid) return OCN_OK;
     hipFree(grid->tables);
+    hipFree(grid->ivd_scratch);
     delete grid;
     return OCN_OK;
 }
@@ -674,7 +678,7 @@ extern "C" int ocn_add_fplane_coriolis(ocn_grid_t grid, double f, const double *
 
 static int closure_tendencies(const DGrid &g, const double *u, const double *v, const double *w, const double *const *tr, int ntr,
                               double nu, const double *kappa, double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range,
-                              const double *nu_e = nullptr, const double *const *kappa_e = nullptr, const double *Pr = nullptr) {
+                              const double *nu_e = nullptr, const double *const *kappa_e = nullptr, const double *Pr = nullptr, bool vi = false) {
     // Pr (Smagorinsky): kappa_e[t] is νₑ and tracer t's coefficient is the interpolated νₑ divided by Pr[t]; Pr[t] == 1 takes the
     // plain instantiation (x / 1.0 is x)
     const FView vu = make_view(g, u, LOC_U), vv = make_view(g, v, LOC_V), vw = make_view(g, w, LOC_W);
@@ -689,6 +693,13 @@ static int closure_tendencies(const DGrid &g, const double *u, const double *v, 
         if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
         const FView vc = make_view(g, c ? c : u, LOC_C), vG = make_view(g, G, loc);
         const dim3 grd = grid3(nx, ny, nz, BLK);
+        if (vi) {               // constant coefficients, the explicit part of a vertically implicit discretisation
+            if (F == F_U) hipLaunchKernelGGL((closure_tendency_kernel<F_U, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
+            if (F == F_V) hipLaunchKernelGGL((closure_tendency_kernel<F_V, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
+            if (F == F_W) hipLaunchKernelGGL((closure_tendency_kernel<F_W, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
+            if (F == F_C) hipLaunchKernelGGL((closure_tendency_kernel<F_C, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
+            return OCN_OK;
+        }
         if (F == F_U) hipLaunchKernelGGL(closure_tendency_kernel<F_U>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
         if (F == F_V) hipLaunchKernelGGL(closure_tendency_kernel<F_V>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
         if (F == F_W) hipLaunchKernelGGL(closure_tendency_kernel<F_W>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
@@ -716,6 +727,56 @@ extern "C" int ocn_compute_closure_tendencies(ocn_grid_t grid, const double *u, 
         return fail(OCN_EINVAL, "invalid argument");
     if (nu < 0) return fail(OCN_EINVAL, "viscosity must be non-negative");
     return closure_tendencies(grid->d, u, v, w, tracers, ntracers, nu, kappa, Gu, Gv, Gw, Gc, range);
+}
+
+// the same with the z fluxes of ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ν, κ) on a vertically Bounded grid
+// (abstract_scalar_diffusivity_closure.jl:245-291): explicit at the z-flux indices 1 and Nz + 1, -(ν ∂x w), -(ν ∂y w), 0, 0 elsewhere
+extern "C" int ocn_compute_closure_tendencies_vertically_implicit(ocn_grid_t grid, const double *u, const double *v, const double *w,
+                                                                  const double *const *tracers, int ntracers, double nu, const double *kappa,
+                                                                  double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range) {
+    NEED_INIT();
+    if (!grid || !u || !v || !w || !Gu || !Gv || !Gw || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 ||
+        (ntracers > 0 && (!tracers || !Gc || !kappa)))
+        return fail(OCN_EINVAL, "invalid argument");
+    if (nu < 0) return fail(OCN_EINVAL, "viscosity must be non-negative");
+    if (grid->d.tz != OCN_BOUNDED)
+        return fail(OCN_EINVAL, "VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.");
+    return closure_tendencies(grid->d, u, v, w, tracers, ntracers, nu, kappa, Gu, Gv, Gw, Gc, range, nullptr, nullptr, nullptr, true);
+}
+
+// implicit_step!(field, implicit_solver, closure, ..., Δt) of one field (vertically_implicit_diffusion_solver.jl:189-213 with the
+// diagonals of :58-121 and solve! of batched_tridiagonal_solver.jl:110-133,219-245), constant coefficient `coef` (ν for u, v, w; κ of the
+// tracer). form: 0, the reference-shaped kernel (scratch t in memory) -- the only form shipped (ocn_implicit_z.h)
+// (the scratch has a size the grid fixes and is never reallocated: a captured time-step may hold its address)
+static int ivd_workspace(ocn_grid_s *grid) {
+    const DGrid &g = grid->d;
+    if (grid->ivd_scratch) return OCN_OK;
+    hipError_t e = dev_alloc((void **)&grid->ivd_scratch, sizeof(double) * (size_t)g.Nx * g.Ny * g.Nz);
+    if (e != hipSuccess) return fail((int)e, "dev_alloc(implicit solve scratch): %s", hipGetErrorString(e));
+    return OCN_OK;
+}
+static int implicit_step_z(ocn_grid_s *grid, double *field, const int loc[3], double coef, double dt, int form) {
+    const DGrid &g = grid->d;
+    if (g.tz != OCN_BOUNDED)
+        return fail(OCN_EINVAL, "VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.");
+    if (form != 0) return fail(OCN_EINVAL, "form is 0 (the reference-shaped kernel): no other form is shipped");
+    const bool fx = loc[0] == OCN_FACE, fy = loc[1] == OCN_FACE, zf = loc[2] == OCN_FACE;
+    if ((fx && fy) || (zf && (fx || fy))) return fail(OCN_EINVAL, "location must be that of u, v, w or a tracer");
+    if (!(coef >= 0)) return fail(OCN_EINVAL, "diffusivity must be non-negative");
+    int rc = ivd_workspace(grid);
+    if (rc) return rc;
+    const FView phi = make_view(g, field, loc);
+    const dim3 grd((g.Nx + 63) / 64, g.Ny), blk(64);
+    if (zf) hipLaunchKernelGGL(implicit_step_z_kernel<true>, grd, blk, 0, g_stream, g, phi, grid->ivd_scratch, dt, coef, fx, fy);
+    else    hipLaunchKernelGGL(implicit_step_z_kernel<false>, grd, blk, 0, g_stream, g, phi, grid->ivd_scratch, dt, coef, fx, fy);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+extern "C" int ocn_implicit_step_z(ocn_grid_t grid, double *field, const int loc[3], double coef, double dt, int form) {
+    NEED_INIT();
+    if (!grid || !field || !loc) return fail(OCN_EINVAL, "NULL argument");
+    return implicit_step_z(grid, field, loc, coef, dt, form);
 }
 
 extern "C" int ocn_compute_closure_tendencies_field(ocn_grid_t grid, const double *u, const double *v, const double *w,
@@ -2430,6 +2491,7 @@ struct ocn_model_s {
     bool any_linear_flux = false;
     bool has_closure = false;               // closure = ScalarDiffusivity(ν, κ)
     double nu = 0.0, kappa[OCN_MAX_FIELDS] = {};
+    bool vi = false;                        // ... with VerticallyImplicitTimeDiscretization(): implicit_step! after every substep
     bool has_amd = false;                   // closure = AnisotropicMinimumDissipation(Cν, Cκ)
     double Cnu = 0.0, Ckappa[OCN_MAX_FIELDS] = {};
     double *nu_e = nullptr, *kappa_e[OCN_MAX_FIELDS] = {};   // diffusivity_fields.νₑ, .κₑ (ccc, with halos)
@@ -2675,6 +2737,9 @@ extern "C" int ocn_model_set_option(ocn_model_t m, const char *key, int value) {
 
 static bool has_physics(const ocn_model_s *m) { return m->has_coriolis || m->buoyancy_kind != 0 || m->has_closure || m->has_amd || m->has_smag; }
 
+// the form of the vertically implicit solve a model runs (ocn_implicit_z.h): the reference-shaped one, the only one shipped
+static int model_ivd_form(const ocn_model_s *) { return 0; }
+
 static bool has_forcing(const ocn_model_s *m) {
     for (int f = 0; f < m->nf; ++f)
         if (m->forcing_h.nterms[f] > 0) return true;
@@ -2710,6 +2775,14 @@ static int add_forcing(ocn_model_s *m) {
     hipLaunchKernelGGL(add_forcing_kernel, grid3(nx, ny, nz * L.n, BLK), BLK, 0, g_stream, m->grid->d, (const ForcingTable *)m->forcing_d, L, nz);
     KERNEL_CHECK();
     return OCN_OK;
+}
+
+// whether the closure terms take the z-marching epilogue (ocn_epilogue_march.h): a grid without Flat directions, at most two tracers, and
+// not the explicit part of a vertically implicit discretisation -- that variant exists in the per-value epilogue only
+static bool epilogue_march_selected(const ocn_model_s *m) {
+    const DGrid &g = m->grid->d;
+    const bool clo = m->has_smag || m->has_amd || m->has_closure;
+    return m->opt.epilogue_march && clo && !(m->has_closure && m->vi) && m->ntr <= 2 && g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT;
 }
 
 // Coriolis, hydrostatic pressure gradient and closure terms of every field -- and, when `sub` is given, the RK3 substep of the next
@@ -2769,11 +2842,11 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
             if (sd < 3) a.loc[f][sd] = f < m->nf ? m->loc[f][sd] : 0;
         }
     if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
-    const int clo = m->has_smag ? (m->smag_unit_pr ? 2 : 3) : (m->has_amd ? 2 : (m->has_closure ? 1 : 0));
+    const int clo = m->has_smag ? (m->smag_unit_pr ? 2 : 3) : (m->has_amd ? 2 : (m->has_closure ? (m->vi ? 4 : 1) : 0));
     // closure terms on a grid without Flat directions: the z-marching form (ocn_epilogue_march.h) -- the union of the fields' ranges, one
     // column of halo around it readable
     const OcnOptions &o = m->opt;
-    if (o.epilogue_march && clo != 0 && m->ntr <= 2 && g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT) {
+    if (epilogue_march_selected(m)) {
         Range6 R = a.r[0];
         for (int f = 1; f < m->nf; ++f) {
             R.i0 = std::min(R.i0, a.r[f].i0); R.i1 = std::max(R.i1, a.r[f].i1); R.j0 = std::min(R.j0, a.r[f].j0); R.j1 = std::max(R.j1, a.r[f].j1);
@@ -2819,7 +2892,7 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
     }
     const dim3 grd = grid3(nx, ny, nz * m->nf, BLK);
 #define OCN_EPI(COR, BUOY, CLO) hipLaunchKernelGGL((tendency_epilogue_kernel<COR, BUOY, CLO>), grd, BLK, 0, g_stream, g, a)
-#define OCN_EPI_CLO(COR, BUOY) do { if (clo == 3) OCN_EPI(COR, BUOY, 3); else if (clo == 2) OCN_EPI(COR, BUOY, 2); else if (clo == 1) OCN_EPI(COR, BUOY, 1); else OCN_EPI(COR, BUOY, 0); } while (0)
+#define OCN_EPI_CLO(COR, BUOY) do { if (clo == 4) OCN_EPI(COR, BUOY, 4); else if (clo == 3) OCN_EPI(COR, BUOY, 3); else if (clo == 2) OCN_EPI(COR, BUOY, 2); else if (clo == 1) OCN_EPI(COR, BUOY, 1); else OCN_EPI(COR, BUOY, 0); } while (0)
     if (a.has_coriolis) { if (a.has_buoyancy) OCN_EPI_CLO(true, true); else OCN_EPI_CLO(true, false); }
     else                { if (a.has_buoyancy) OCN_EPI_CLO(false, true); else OCN_EPI_CLO(false, false); }
 #undef OCN_EPI_CLO
@@ -2855,6 +2928,11 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     if (!strcmp(key, "graph_captures")) { *value = m->graph_captures; return OCN_OK; }
     if (!strcmp(key, "graph_failures")) { *value = m->graph_failures; return OCN_OK; }
     if (!strcmp(key, "forcing_path")) { *value = forcing_path(m); return OCN_OK; }
+    if (!strcmp(key, "vertically_implicit")) { *value = m->vi ? 1 : 0; return OCN_OK; }
+    // which epilogue adds the closure terms: the z-marching one (1) or the per-value one (0) -- the explicit part of a vertically implicit
+    // discretisation exists in the per-value epilogue only
+    if (!strcmp(key, "epilogue_march_active")) { *value = (epilogue_runs(m) && epilogue_march_selected(m)) ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "implicit_step_form")) { *value = model_ivd_form(m); return OCN_OK; }
     if (!strcmp(key, "fuse_substep_active")) { *value = can_fuse_substep(m) ? 1 : 0; return OCN_OK; }
     // what the tendency LAUNCH itself carries (bench.py prices its bytes with these): the next stage's substep rides in the advection kernel
     // only without physics / Flux conditions (with them it rides in the epilogue pass); the tendency of the second stage is then not stored
@@ -2937,7 +3015,7 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
                 if (!rc && m->buoyancy_kind) rc = add_hydrostatic_pressure_gradient(g, m->pHY, m->Gn[0], m->Gn[1], nullptr);
                 if (!rc && m->has_closure)
                     rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->nu, m->kappa, m->Gn[0], m->Gn[1],
-                                            m->Gn[2], m->Gn + 3, nullptr);
+                                            m->Gn[2], m->Gn + 3, nullptr, nullptr, nullptr, nullptr, m->vi);
                 if (!rc && m->has_amd)
                     rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, 0.0, nullptr, m->Gn[0], m->Gn[1],
                                             m->Gn[2], m->Gn + 3, nullptr, m->nu_e, m->kappa_e);
@@ -3059,6 +3137,39 @@ extern "C" int ocn_model_set_closure(ocn_model_t m, double nu, const double *kap
         m->kappa[t] = kappa ? kappa[t] : 0.0;
         if (m->kappa[t] < 0) return fail(OCN_EINVAL, "diffusivity must be non-negative");
         if (m->kappa[t] != 0.0) m->has_closure = true;
+    }
+    return OCN_OK;
+}
+
+// time_discretization of the model's ScalarDiffusivity (scalar_diffusivity.jl:116-141): VerticallyImplicitTimeDiscretization() when
+// `enabled`. implicit_diffusion_solver (vertically_implicit_diffusion_solver.jl:149-153) refuses a grid whose z is not Bounded. The eddy-
+// coefficient closures have per-column coefficients, which the per-level tables do not serve: the setting is refused with them, and
+// ocn_model_set_amd / ocn_model_set_smagorinsky clear it.
+extern "C" int ocn_model_set_vertically_implicit(ocn_model_t m, int enabled) {
+    if (m) m->epoch += 1;
+    NEED_INIT();
+    if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (!enabled) { m->vi = false; return OCN_OK; }
+    if (m->grid->d.tz != OCN_BOUNDED)
+        return fail(OCN_EINVAL, "VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.");
+    if (m->has_amd || m->has_smag)
+        return fail(OCN_ENOTSUP, "VerticallyImplicitTimeDiscretization is accelerated for ScalarDiffusivity with constant coefficients only");
+    int rc = ivd_workspace(m->grid);       // (allocated here: not inside a captured step)
+    if (rc) return rc;
+    m->vi = true;
+    return OCN_OK;
+}
+
+// implicit_step! of every prognostic field after its substep (runge_kutta_3.jl:185-200, quasi_adams_bashforth_2.jl:133-152); a field
+// whose coefficient is zero has the identity system
+static int implicit_step(ocn_model_s *m, double dt) {
+    if (!m->vi || !m->has_closure) return OCN_OK;
+    const int form = model_ivd_form(m);
+    for (int f = 0; f < m->nf; ++f) {
+        const double coef = f < 3 ? m->nu : m->kappa[f - 3];
+        if (coef == 0.0) continue;
+        const int rc = implicit_step_z(m->grid, m->U[f], m->loc[f], coef, dt, form);
+        if (rc) return rc;
     }
     return OCN_OK;
 }
@@ -3193,7 +3304,7 @@ extern "C" int ocn_model_set_amd(ocn_model_t m, double Cnu, const double *Ckappa
     int rc = alloc0(&m->nu_e);
     for (int t = 0; t < m->ntr && !rc; ++t) rc = alloc0(&m->kappa_e[t]);
     if (rc) return rc;
-    m->has_amd = true; m->has_closure = false; m->has_smag = false; m->nu = 0.0;
+    m->has_amd = true; m->has_closure = false; m->has_smag = false; m->nu = 0.0; m->vi = false;
     m->Cnu = Cnu;
     for (int t = 0; t < m->ntr; ++t) { m->kappa[t] = 0.0; m->Ckappa[t] = Ckappa[t]; }
     return OCN_OK;
@@ -3217,7 +3328,7 @@ extern "C" int ocn_model_set_smagorinsky(ocn_model_t m, double C, double Cb, int
         HIP_TRY(dev_alloc((void **)&m->nu_e, bytes));
         HIP_TRY(hipMemsetAsync(m->nu_e, 0, bytes, g_stream));
     }
-    m->has_smag = true; m->has_amd = false; m->has_closure = false; m->nu = 0.0;
+    m->has_smag = true; m->has_amd = false; m->has_closure = false; m->nu = 0.0; m->vi = false;
     m->smag_C = C; m->smag_Cb = Cb; m->smag_lilly = lilly != 0; m->smag_unit_pr = true;
     for (int t = 0; t < m->ntr; ++t) { m->kappa[t] = 0.0; m->Pr[t] = Pr[t]; m->smag_unit_pr = m->smag_unit_pr && Pr[t] == 1.0; }
     return OCN_OK;
@@ -3341,6 +3452,7 @@ static int rk3_time_step(ocn_model_s *m, double dt) {
         if (!substep_done && (rc = compute_flux_bc_tendencies(m))) return rc;
         if (!substep_done && (rc = rk3_substep(g, m->U, m->Gn, m->Gm, m->loc, m->nf, dt, gam[stage], zet[stage], stage > 0))) return rc;
         substep_done = false;
+        if ((rc = implicit_step(m, sdt[stage]))) return rc;          // after the substep -- on its own or ridden in the tendency launch -- and before tick!
         if (stage < 2) tick(m, sdt[stage], true);
         else {
             double corrected = tn1 - m->time;
@@ -3438,6 +3550,7 @@ extern "C" int ocn_model_time_step_ab2(ocn_model_t m, double dt, double chi, int
     const double x = eul ? -0.5 : chi;
     if ((rc = compute_flux_bc_tendencies(m))) return rc;                                   // quasi_adams_bashforth_2.jl:99
     if ((rc = ab2_step(g, m->U, m->Gn, m->Gm, m->loc, m->nf, dt, x))) return rc;
+    if ((rc = implicit_step(m, dt))) return rc;                                            // quasi_adams_bashforth_2.jl:143-151
     tick(m, dt, false);
     if ((rc = pressure_step(m, dt))) return rc;
     if ((rc = cache_previous_tendencies(m))) return rc;

@@ -164,7 +164,11 @@ struct ClosureCtx {
 // V⁻¹ (δx(Ax flux) + δy(Ay flux) + δz(Az flux)) of the closure for field F at (i, j, k); coef = ν (momentum) or κ (tracer c).
 // PRD (tracers of a Smagorinsky closure with Pr ≠ 1, smagorinsky.jl:141-143): K is νₑ and the coefficient at a flux point is the
 // interpolated νₑ DIVIDED by the Prandtl number, which `coef` then holds (interpolate, then divide)
-template <int F, bool PRD = false>
+// VI (constant coefficients, Bounded z): the explicit part of a VerticallyImplicitTimeDiscretization (abstract_scalar_diffusivity_closure.jl:
+// 245-291). At the z-flux indices k == 1 | k == Nz + 1 every z flux is the explicit one; elsewhere viscous_flux_uz = -(ν ∂xᶠᶜᶠ w),
+// viscous_flux_vz = -(ν ∂yᶜᶠᶠ w), viscous_flux_wz = 0 (the test applied at its own ccc index) and diffusive_flux_z = 0: implicit_step!
+// (ocn_implicit_z.h) supplies the rest. The x and y fluxes are the explicit ones.
+template <int F, bool PRD = false, bool VI = false>
 __device__ __forceinline__ double closure_divergence(const DGrid &g, const FView &u, const FView &v, const FView &w, const FView &c,
                                                      double coef, int i, int j, int k, bool var, const FView &K) {
     // eddy-coefficient arrays come with grids that have no Flat direction (ocn_model_set_amd): with `var` a compile-time constant the
@@ -176,16 +180,31 @@ __device__ __forceinline__ double closure_divergence(const DGrid &g, const FView
         vinv = g.vinv_c[k - 1 + g.Hz];
         dx = X.fx ? 0.0 : (dy_ * X.dzc(k)) * X.vf11(i, j, k) - (dy_ * X.dzc(k)) * X.vf11(i - 1, j, k);
         dy = X.fy ? 0.0 : (dx_ * X.dzc(k)) * X.vf12(i, j + 1, k) - (dx_ * X.dzc(k)) * X.vf12(i, j, k);
+        if (VI) {
+            const double up = ((k + 1 == 1) | (k + 1 == g.Nz + 1)) ? X.vf13(i, j, k + 1) : -(X.K_fcf(i, j, k + 1) * X.ddx_f(w, i, j, k + 1));
+            const double lo = ((k == 1) | (k == g.Nz + 1)) ? X.vf13(i, j, k) : -(X.K_fcf(i, j, k) * X.ddx_f(w, i, j, k));
+            dz = (dx_ * dy_) * up - (dx_ * dy_) * lo;
+        } else
         dz = X.fz ? 0.0 : (dx_ * dy_) * X.vf13(i, j, k + 1) - (dx_ * dy_) * X.vf13(i, j, k);
     } else if (F == F_V) {     // ∂ⱼ_τ₂ⱼ at cfc: Ax_qᶠᶠᶜ, Ay_qᶜᶜᶜ, Az_qᶜᶠᶠ
         vinv = g.vinv_c[k - 1 + g.Hz];
         dx = X.fx ? 0.0 : (dy_ * X.dzc(k)) * X.vf12(i + 1, j, k) - (dy_ * X.dzc(k)) * X.vf12(i, j, k);
         dy = X.fy ? 0.0 : (dx_ * X.dzc(k)) * X.vf22(i, j, k) - (dx_ * X.dzc(k)) * X.vf22(i, j - 1, k);
+        if (VI) {
+            const double up = ((k + 1 == 1) | (k + 1 == g.Nz + 1)) ? X.vf23(i, j, k + 1) : -(X.K_cff(i, j, k + 1) * X.ddy_f(w, i, j, k + 1));
+            const double lo = ((k == 1) | (k == g.Nz + 1)) ? X.vf23(i, j, k) : -(X.K_cff(i, j, k) * X.ddy_f(w, i, j, k));
+            dz = (dx_ * dy_) * up - (dx_ * dy_) * lo;
+        } else
         dz = X.fz ? 0.0 : (dx_ * dy_) * X.vf23(i, j, k + 1) - (dx_ * dy_) * X.vf23(i, j, k);
     } else if (F == F_W) {     // ∂ⱼ_τ₃ⱼ at ccf: Ax_qᶠᶜᶠ, Ay_qᶜᶠᶠ, Az_qᶜᶜᶜ
         vinv = g.vinv_f[k - 1 + g.Hz];
         dx = X.fx ? 0.0 : (dy_ * X.dzf(k)) * X.vf13(i + 1, j, k) - (dy_ * X.dzf(k)) * X.vf13(i, j, k);
         dy = X.fy ? 0.0 : (dx_ * X.dzf(k)) * X.vf23(i, j + 1, k) - (dx_ * X.dzf(k)) * X.vf23(i, j, k);
+        if (VI) {
+            const double up = ((k == 1) | (k == g.Nz + 1)) ? X.vf33(i, j, k) : 0.0;
+            const double lo = ((k - 1 == 1) | (k - 1 == g.Nz + 1)) ? X.vf33(i, j, k - 1) : 0.0;
+            dz = (dx_ * dy_) * up - (dx_ * dy_) * lo;
+        } else
         dz = X.fz ? 0.0 : (dx_ * dy_) * X.vf33(i, j, k) - (dx_ * dy_) * X.vf33(i, j, k - 1);
     } else {                   // ∇_dot_qᶜ at ccc: Ax_qᶠᶜᶜ, Ay_qᶜᶠᶜ, Az_qᶜᶜᶠ of -(κ ∂c)
         vinv = g.vinv_c[k - 1 + g.Hz];
@@ -197,20 +216,25 @@ __device__ __forceinline__ double closure_divergence(const DGrid &g, const FView
         } else {
             dx = X.fx ? 0.0 : ax * -(X.K_fcc(i + 1, j, k) * X.ddx_f(c, i + 1, j, k)) - ax * -(X.K_fcc(i, j, k) * X.ddx_f(c, i, j, k));
             dy = X.fy ? 0.0 : ay * -(X.K_cfc(i, j + 1, k) * X.ddy_f(c, i, j + 1, k)) - ay * -(X.K_cfc(i, j, k) * X.ddy_f(c, i, j, k));
+            if (VI) {
+                const double up = ((k + 1 == 1) | (k + 1 == g.Nz + 1)) ? -(X.K_ccf(i, j, k + 1) * X.ddz_f(c, i, j, k + 1)) : 0.0;
+                const double lo = ((k == 1) | (k == g.Nz + 1)) ? -(X.K_ccf(i, j, k) * X.ddz_f(c, i, j, k)) : 0.0;
+                dz = az * up - az * lo;
+            } else
             dz = X.fz ? 0.0 : az * -(X.K_ccf(i, j, k + 1) * X.ddz_f(c, i, j, k + 1)) - az * -(X.K_ccf(i, j, k) * X.ddz_f(c, i, j, k));
         }
     }
     return vinv * ((dx + dy) + dz);
 }
 
-template <int F>
+template <int F, bool VI = false>
 __global__ void __launch_bounds__(256) closure_tendency_kernel(DGrid g, FView u, FView v, FView w, FView c, FView G, double coef, Range6 r,
                                                                bool var, FView K) {
     const int i = r.i0 + blockIdx.x * blockDim.x + threadIdx.x;
     const int j = r.j0 + blockIdx.y * blockDim.y + threadIdx.y;
     const int k = r.k0 + blockIdx.z;
     if (i > r.i1 || j > r.j1 || k > r.k1) return;
-    G.at(i, j, k) = (G.at(i, j, k) - closure_divergence<F>(g, u, v, w, c, coef, i, j, k, var, K)) + 0.0;
+    G.at(i, j, k) = (G.at(i, j, k) - closure_divergence<F, false, VI>(g, u, v, w, c, coef, i, j, k, VI ? false : var, K)) + 0.0;
 }
 
 // a tracer of a Smagorinsky closure with Pr ≠ 1: κ = ℑ(νₑ) / Pr at the flux points
@@ -949,7 +973,8 @@ __device__ __forceinline__ double epilogue_flux_conditions(const DGrid &g, const
 }
 
 // COR / BUOY / CLO (0 none, 1 constant ν, κ, 2 eddy-coefficient arrays, 3 the same with the tracers' interpolated coefficient divided by
-// the Prandtl number that a.kappa[t] then holds -- Smagorinsky with Pr ≠ 1) are compile-time: the terms of one cell then form ONE basic
+// the Prandtl number that a.kappa[t] then holds -- Smagorinsky with Pr ≠ 1, 4 constant ν, κ with the explicit part of a vertically implicit
+// time discretisation) are compile-time: the terms of one cell then form ONE basic
 // block whose ~40 loads the compiler issues together -- with run-time flags every term was its own block behind a branch and its
 // loads waited one after the other (0.94 -> see DESIGN.md for the measured time at 256 x 256 x 128).
 template <bool COR, bool BUOY, int CLO>
@@ -965,21 +990,21 @@ __global__ void __launch_bounds__(256) tendency_epilogue_kernel(DGrid g, Epilogu
     const FView &fv = f == 0 ? a.u : (f == 1 ? a.v : (f == 2 ? a.w : a.c[f - 3]));
     const long q = fv.lin(i, j, k);
     double G = a.Gn[f][q];
-    constexpr bool VAR = CLO >= 2, PRD = CLO == 3;
+    constexpr bool VAR = CLO == 2 || CLO == 3, PRD = CLO == 3, VI = CLO == 4;
     if (f == 0) {
         if (COR) G = G - x_f_cross_U(g, a.fcor, a.v, i, j, k);
         if (BUOY) G = G - hydrostatic_gradient_x(g, a.pHY, i, j, k);
-        if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_U>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
+        if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_U, false, VI>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
     } else if (f == 1) {
         if (COR) G = G - y_f_cross_U(g, a.fcor, a.u, i, j, k);
         if (BUOY) G = G - hydrostatic_gradient_y(g, a.pHY, i, j, k);
-        if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_V>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
+        if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_V, false, VI>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
     } else if (f == 2) {
-        if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_W>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
+        if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_W, false, VI>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
     } else {
         const double kap = a.kappa[f - 3];
         if (CLO && (VAR || kap != 0.0))
-            G = (G - closure_divergence<F_C, PRD>(g, a.u, a.v, a.w, a.c[f - 3], kap, i, j, k, VAR, a.kappa_e[f - 3])) + 0.0;
+            G = (G - closure_divergence<F_C, PRD, VI>(g, a.u, a.v, a.w, a.c[f - 3], kap, i, j, k, VAR, a.kappa_e[f - 3])) + 0.0;
     }
     G = epilogue_flux_conditions(g, a, f, i, j, k, q, G);
     if (a.store_G) a.Gn[f][q] = G;

@@ -50,6 +50,22 @@ def compute_closure_tendencies(grid, fields, Gn, closure, tracer_names, kernel_p
         Gn[0].data, Gn[1].data, Gn[2].data, _ptr_array(gc) if gc else None, _range(kernel_parameters)))
 
 
+def compute_closure_tendencies_vertically_implicit(grid, fields, Gn, closure, tracer_names, kernel_parameters=None):
+    """the explicit part of ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ν, κ) (abstract_scalar_diffusivity_closure.jl:245-291),
+    added to tendencies that hold the advective part; fields = u, v, w, tracers..."""
+    karr, kp = closure.kappa_array(tracer_names)
+    tr, gc = fields[3:], Gn[3:]
+    _lib.check(_lib.lib().ocn_compute_closure_tendencies_vertically_implicit(
+        grid.handle, fields[0].data, fields[1].data, fields[2].data, _ptr_array(tr) if tr else None, len(tr), closure.ν, kp,
+        Gn[0].data, Gn[1].data, Gn[2].data, _ptr_array(gc) if gc else None, _range(kernel_parameters)))
+
+
+def implicit_step(grid, field, coefficient, Δt, form=0):
+    """implicit_step!(field, ...) for a constant coefficient (vertically_implicit_diffusion_solver.jl:189-213): the tridiagonal solve along
+    z in place; form 0 is the reference-shaped kernel, the only form shipped"""
+    _lib.check(_lib.lib().ocn_implicit_step_z(grid.handle, field.data, _lib.i3(field.loc_codes), float(coefficient), float(Δt), int(form)))
+
+
 def compute_amd_diffusivities(grid, closure, tracer_names, fields, νₑ, κₑ, kernel_parameters=None):
     """compute_diffusivities!(…, closure::AnisotropicMinimumDissipation, …) over the interior; fields = u, v, w, tracers... with filled
     halos; fill the halos of νₑ, κₑ afterwards (fill_halo_regions)"""

@@ -60,6 +60,11 @@ class NonhydrostaticModel:
         if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
             raise NotImplementedError("only closure = nothing | ScalarDiffusivity(ν, κ) | AnisotropicMinimumDissipation(C, Cν, Cκ) | "
                                       "Smagorinsky(coefficient, Pr) | SmagorinskyLilly(C, Cb, Pr) is on the accelerated path (SURVEY.md 8f)")
+        from .closures import is_vertically_implicit
+        from .grids import Bounded
+        if is_vertically_implicit(closure) and getattr(grid, "local", grid).topology[2] is not Bounded:
+            # implicit_diffusion_solver (vertically_implicit_diffusion_solver.jl:149-153)
+            raise ValueError("VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.")
         self.closure = closure
         # "Adjust advection scheme to be valid on a particular grid size" and "Adjust halos when the advection scheme or turbulence
         # closure requires it" (nonhydrostatic_model.jl:176-184). The library derives the same per-direction schemes from the grid
@@ -126,6 +131,8 @@ class NonhydrostaticModel:
         elif closure is not None:
             self._kappa, kp = closure.kappa_array(self.tracer_names)
             _lib.check(_lib.lib().ocn_model_set_closure(self.handle, closure.ν, kp))
+            if is_vertically_implicit(closure):
+                _lib.check(_lib.lib().ocn_model_set_vertically_implicit(self.handle, 1))
         self._forcing_keep = []                          # device arrays of Forcing(array): owned (numpy) or borrowed (Field)
         for name, terms in self._forcing_terms.items():
             _forcings.set_forcing(self.handle, ("u", "v", "w").index(name) if name in ("u", "v", "w") else 3 + self.tracer_names.index(name),
