@@ -359,7 +359,10 @@ int ocn_model_set_option(ocn_model_t model, const char *key, int value);
  * model) and what the configuration makes of them: "fused_tendency_active" (1 when a flux-sharing tendency kernel runs for this grid),
  * "fuse_substep_active" (1 when the rk3_substep! of stages 2 and 3 is fused into the preceding tendency evaluation: option
  * "fuse_substep" = 1, flux-sharing kernel, tendencies cached by pointer swap, no Flux boundary condition), "substep_in_tendency_kernel"
- * (1 when that substep rides in the tendency launch itself), "forcing_path" (ocn_model_set_forcing), "graph_captures",
+ * (1 when that substep rides in the tendency launch itself), "halo_fill_folded" and "stage1_source_fused" (what the last time-step did
+ * on a triply periodic grid with the split pressure solve: 1 when the pressure-correction kernel wrote every halo, so that the step
+ * launched no halo fill -- option "fused_halo"; 1 when the first RK3 substep rode in the source-term and correction kernels -- option
+ * "fuse_substep"), "forcing_path" (ocn_model_set_forcing), "graph_captures",
  * "graph_replays", "graph_failures" (option "use_graph"), which conditional path the model's pressure solver took -- "fused_zfft_active"
  * (1 when solve_for_pressure! runs the z transform, the divide and the inverse z transform as one pass: options "real_fft" and
  * "fused_zfft", FFT solver, Nz = 2^m in 8 .. 1024), "c2r_strided_active" (1 when the Z2D plan writes into the haloed pressure field:
@@ -456,7 +459,7 @@ int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *ter
  *   "fused_xcd" = 0 (step): XCD-aware tile order of the all-fields kernel (measured: no effect)
  *   "swap_tendencies" = 1 (step): cache_previous_tendencies! by pointer swap (0: by copy kernel)
  *   "fuse_substep" = 1 (step): the substeps of RK3 stages 2 and 3 fused into the preceding tendency evaluation (second set of
- *       prognostic arrays, swapped twice per time-step)
+ *       prognostic arrays, swapped twice per time-step); triply periodic grids: the substep of stage 1 fused into the pressure step
  *   "fused_epilogue" = 1 (step): Coriolis, hydrostatic gradient, closure terms (and the substep) as one launch
  *   "fused_forcing" = 1 (step): the forcing term in the tendency kernel when it can ride there (0: always the standalone pass)
  *   "use_graph" = 0 (step): hipGraph replay of the RK3 step (measured: no gain)
@@ -469,7 +472,8 @@ int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *ter
  *       everything recomputed -- same bits)
  *   "smag_march" = 1 (step): z-marching Smagorinsky eddy-viscosity kernel that evaluates every strain point value once (0: one
  *       thread per cell, everything recomputed -- same bits)
- *   "fused_halo" = 1 (step): one launch per periodic fill
+ *   "fused_halo" = 1 (step): one launch per periodic fill; inside a time-step on a triply periodic grid no launch at all -- the
+ *       pressure-correction kernel writes the halos
  *   pressure solve:
  *   "real_fft" = 1 (step): D2Z / Z2D transforms (0: the reference's complex-to-complex)
  *   "c2r_strided" = 1 (creation): Z2D straight into the interior of the haloed pressure field

@@ -2482,6 +2482,7 @@ struct ocn_model_s {
     double graph_dt = 0.0;
     uint64_t graph_epoch = 0, epoch = 1;
     int graph_replays = 0, graph_captures = 0, graph_failures = 0;
+    bool halo_fill_folded = false, stage1_source_fused = false;     // report only (ocn_model_get_option): the path the last time-step took
     int loc[OCN_MAX_FIELDS][3];
     ocn_bc_t bcs[OCN_MAX_FIELDS][6] = {};   // field boundary conditions (default: field_boundary_conditions.jl:15-25)
     ocn_bc_t kbcs[OCN_MAX_FIELDS][6] = {};  // ... of the diffusivity fields: [0] = νₑ, [1 + t] = κₑ of tracer t (boundary_conditions = (κₑ = (b = ...,),))
@@ -2934,6 +2935,10 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     if (!strcmp(key, "epilogue_march_active")) { *value = (epilogue_runs(m) && epilogue_march_selected(m)) ? 1 : 0; return OCN_OK; }
     if (!strcmp(key, "implicit_step_form")) { *value = model_ivd_form(m); return OCN_OK; }
     if (!strcmp(key, "fuse_substep_active")) { *value = can_fuse_substep(m) ? 1 : 0; return OCN_OK; }
+    // what the last time-step did on a triply periodic grid: the correction kernel wrote the halos (no fill launches), and the first RK3
+    // substep rode in the pressure step's kernels
+    if (!strcmp(key, "halo_fill_folded")) { *value = m->halo_fill_folded ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "stage1_source_fused")) { *value = m->stage1_source_fused ? 1 : 0; return OCN_OK; }
     // what the tendency LAUNCH itself carries (bench.py prices its bytes with these): the next stage's substep rides in the advection kernel
     // only without physics / Flux conditions (with them it rides in the epilogue pass); the tendency of the second stage is then not stored
     if (!strcmp(key, "substep_in_tendency_kernel")) { *value = (can_fuse_substep(m) && !epilogue_runs(m)) ? 1 : 0; return OCN_OK; }
@@ -2953,9 +2958,10 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
 // update_state! (update_nonhydrostatic_model_state.jl:20-56)
 static int dist_update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub);
 static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub, const int *amd_range);
-static int update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub = nullptr) {
+// halos_current: the pressure step of the same time-step has just written every halo (pressure_step, fold_halos)
+static int update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub = nullptr, bool halos_current = false) {
     if (m->dm) return dist_update_state(m, compute_tend, sub);
-    int rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, /*fill_open_bcs=*/false, m->any_bc ? m->bcs : nullptr);
+    int rc = halos_current ? OCN_OK : fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, /*fill_open_bcs=*/false, m->any_bc ? m->bcs : nullptr);
     if (rc) return rc;
     return update_state_tail(m, compute_tend, sub, nullptr);
 }
@@ -3074,10 +3080,31 @@ static int dist_pressure_step(ocn_model_s *m, double dt, bool tendencies_follow,
 // keep_p = false (stages 1 and 2 of an RK3 step): nothing can read pNHS before the next stage overwrites it (the time-step is one call), so the
 // dense-solution path neither stores p / Δt⁺ nor fills its halos there -- after the step the field holds the last stage's pressure, as the
 // reference's does
-static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = true, bool keep_p = true) {
+//
+// Triply periodic grids on the dense-solution path fold the neighbouring passes into the two kernels of this step, on request of the
+// time-step that calls it (never remembered in the model: set!, a restored checkpoint or ocn_model_update_state get their own fills):
+//   fold_halos: the correction kernel leaves every halo of the prognostic fields and of a stored pNHS current, so the caller skips the
+//               fill_halo_regions! at the head of the update_state! that follows, and the pNHS fill below is not launched;
+//   pending:    the first RK3 substep has not been applied yet -- it rides in the source-term and correction kernels.
+struct PendingSubstep { double dt, gamma; };
+static bool periodic_dense_path(const ocn_model_s *m) {
+    const ocn_poisson_s *s = m->solver;
+    const DGrid &g = m->grid->d;
+    return !m->dm && s && s->split && m->opt.split_solve && m->opt.real_fft && !s->general && g.tx == OCN_PERIODIC && g.ty == OCN_PERIODIC &&
+           g.tz == OCN_PERIODIC;
+}
+static bool can_fold_halo_fill(const ocn_model_s *m) {                // N >= H: the fused fill's own condition
+    const DGrid &g = m->grid->d;
+    return periodic_dense_path(m) && m->opt.fused_halo && g.Nx >= g.Hx && g.Ny >= g.Hy && g.Nz >= g.Hz;
+}
+static bool can_fuse_stage1_source(const ocn_model_s *m) { return periodic_dense_path(m) && m->opt.fuse_substep; }
+
+static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = true, bool keep_p = true, const PendingSubstep *pending = nullptr,
+                         bool fold_halos = false) {
     if (m->dm) return dist_pressure_step(m, dt, tendencies_follow, keep_p || !m->opt.skip_stage_pressure);
     int rc;
     ocn_poisson_s *s = m->solver;
+    if ((pending || fold_halos) && !periodic_dense_path(m)) return fail(OCN_ESTATE, "folded pressure step off the periodic dense-solution path");
     if (!(s->split && m->opt.split_solve && m->opt.real_fft && !s->general)) {
         if ((rc = compute_pressure_correction(m))) return rc;
         return make_pressure_correction(m, dt);
@@ -3087,14 +3114,33 @@ static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = tru
     // (pressure_correction.jl:10) is not needed here -- update_state! fills every halo again before anything else reads one
     const bool ppp = g.tx == OCN_PERIODIC && g.ty == OCN_PERIODIC && g.tz == OCN_PERIODIC;
     if (!ppp && (rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr))) return rc;
-    if ((rc = source_term(g, m->U[0], m->U[1], m->U[2], s->rrhs, s->kind == 1, true, 0, 0, false, ppp))) return rc;
+    if (pending) {
+        SubstepArgs a;
+        int nx, ny, nz;
+        if ((rc = fill_substep_args(g, a, m->U, m->Gn, nullptr, m->loc, m->nf, true, &nx, &ny, &nz))) return rc;
+        hipLaunchKernelGGL(substep_source_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, a, pending->dt, pending->gamma, s->rrhs,
+                           s->kind == 1);
+        KERNEL_CHECK();
+    } else if ((rc = source_term(g, m->U[0], m->U[1], m->U[2], s->rrhs, s->kind == 1, true, 0, 0, false, ppp))) return rc;
     if ((rc = poisson_solve_real_split(s))) return rc;
     const double dtp = std::fmax(2.220446049250313e-16, dt);
-    hipLaunchKernelGGL(pressure_correction_dense_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, m->U[0], LOC_U),
-                       make_view(g, m->U[1], LOC_V), make_view(g, m->U[2], LOC_W), (const double *)s->rrhs, make_view(g, m->p, LOC_C), dtp,
-                       g.tz == OCN_BOUNDED, keep_p || !m->opt.skip_stage_pressure);
+    const bool store_p = keep_p || !m->opt.skip_stage_pressure;
+    if (pending || fold_halos) {
+        FieldList tr;
+        tr.n = fold_halos ? m->ntr : 0;
+        for (int t = 0; t < tr.n; ++t) tr.p[t] = m->U[3 + t];
+        const auto kernel = fold_halos ? (pending ? pressure_correction_periodic_kernel<true, true> : pressure_correction_periodic_kernel<true, false>)
+                                       : pressure_correction_periodic_kernel<false, true>;
+        hipLaunchKernelGGL(kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, m->U[0], LOC_U), make_view(g, m->U[1], LOC_V),
+                           make_view(g, m->U[2], LOC_W), (const double *)s->rrhs, make_view(g, m->p, LOC_C), dtp, store_p, tr,
+                           (const double *)m->Gn[0], (const double *)m->Gn[1], (const double *)m->Gn[2], pending ? pending->dt : 0.0,
+                           pending ? pending->gamma : 0.0);
+    } else
+        hipLaunchKernelGGL(pressure_correction_dense_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, m->U[0], LOC_U),
+                           make_view(g, m->U[1], LOC_V), make_view(g, m->U[2], LOC_W), (const double *)s->rrhs, make_view(g, m->p, LOC_C), dtp,
+                           g.tz == OCN_BOUNDED, store_p);
     KERNEL_CHECK();
-    if (!keep_p && m->opt.skip_stage_pressure) return OCN_OK;
+    if (!store_p || fold_halos) return OCN_OK;
     double *pp[1] = {m->p};
     const int pl[1][3] = {{OCN_CENTER, OCN_CENTER, OCN_CENTER}};
     return fill_halo_regions(m->opt, m->grid, pp, pl, 1, true);
@@ -3447,10 +3493,17 @@ static int rk3_time_step(ocn_model_s *m, double dt) {
     // previous one are at hand when the cell is closed) -- possible when the fused kernel runs, tendencies are cached by
     // pointer swap and no Flux boundary condition is added to G after the kernel
     const bool can_fuse = can_fuse_substep(m);
+    // triply periodic grids: the first substep rides in the pressure step's source-term and correction kernels, and the correction kernel
+    // of every stage leaves all halos current, so the update_state! that follows fills none (pressure_step)
+    const bool fuse_stage1 = can_fuse_stage1_source(m), fold = can_fold_halo_fill(m);
+    const PendingSubstep stage1{dt, g1};
+    m->stage1_source_fused = fuse_stage1;
+    m->halo_fill_folded = fold;
     bool substep_done = false;
     for (int stage = 0; stage < 3; ++stage) {
+        const bool pending = stage == 0 && fuse_stage1;
         if (!substep_done && (rc = compute_flux_bc_tendencies(m))) return rc;
-        if (!substep_done && (rc = rk3_substep(g, m->U, m->Gn, m->Gm, m->loc, m->nf, dt, gam[stage], zet[stage], stage > 0))) return rc;
+        if (!substep_done && !pending && (rc = rk3_substep(g, m->U, m->Gn, m->Gm, m->loc, m->nf, dt, gam[stage], zet[stage], stage > 0))) return rc;
         substep_done = false;
         if ((rc = implicit_step(m, sdt[stage]))) return rc;          // after the substep -- on its own or ridden in the tendency launch -- and before tick!
         if (stage < 2) tick(m, sdt[stage], true);
@@ -3460,15 +3513,15 @@ static int rk3_time_step(ocn_model_s *m, double dt) {
             m->last_stage_dt = corrected;
             m->last_dt = dt;
         }
-        if ((rc = pressure_step(m, sdt[stage], true, stage == 2))) return rc;
+        if ((rc = pressure_step(m, sdt[stage], true, stage == 2, pending ? &stage1 : nullptr, fold))) return rc;
         if (stage < 2 && (rc = cache_previous_tendencies(m))) return rc;
         if (stage < 2 && can_fuse) {
             FusedSubstep sub{m->U2, m->Gm, dt, gam[stage + 1], zet[stage + 1], 1};
             sub.store_G = stage != 1 || !m->opt.skip_dead_tendency_store;        // G(U²): read by the third stage's substep only
-            if ((rc = update_state(m, true, &sub))) return rc;
+            if ((rc = update_state(m, true, &sub, fold))) return rc;
             for (int f = 0; f < m->nf; ++f) std::swap(m->U[f], m->U2[f]);
             substep_done = true;
-        } else if ((rc = update_state(m, true))) return rc;
+        } else if ((rc = update_state(m, true, nullptr, fold))) return rc;
     }
     return OCN_OK;
 }
@@ -3552,9 +3605,12 @@ extern "C" int ocn_model_time_step_ab2(ocn_model_t m, double dt, double chi, int
     if ((rc = ab2_step(g, m->U, m->Gn, m->Gm, m->loc, m->nf, dt, x))) return rc;
     if ((rc = implicit_step(m, dt))) return rc;                                            // quasi_adams_bashforth_2.jl:143-151
     tick(m, dt, false);
-    if ((rc = pressure_step(m, dt))) return rc;
+    const bool fold = can_fold_halo_fill(m);
+    m->stage1_source_fused = false;
+    m->halo_fill_folded = fold;
+    if ((rc = pressure_step(m, dt, true, true, nullptr, fold))) return rc;
     if ((rc = cache_previous_tendencies(m))) return rc;
-    return update_state(m, true);
+    return update_state(m, true, nullptr, fold);
 }
 
 // reset!(model.clock) + reset!(model.timestepper) (TimeSteppers/clock.jl reset!, runge_kutta_3.jl / quasi_adams_bashforth_2.jl reset!):

@@ -1302,18 +1302,25 @@ __global__ void __launch_bounds__(256) cache_tendencies_kernel(SubstepArgs a) {
 // (solve_for_pressure.jl:12-84, Operators/divergence_operators.jl:16-19)
 // wrap: bit 0 / 1 / 2 = the upper x / y / z neighbour of the last cell is read at its wrapped interior index instead of the halo;
 // ue (x-slab ranks): u[Nx + 1, j, k] is read from this dense (Ny, Nz) buffer -- the east neighbour's first column, just received
-__device__ __forceinline__ double source_value(const DGrid &g, const FView &u, const FView &v, const FView &w, int i, int j, int k,
-                                               bool weight_by_dz, int wrap, const double *ue = nullptr) {
-    const int kk = k - 1 + g.Hz;
+// from the six face values of the cell at level kk = k - 1 + Hz: (u0, up) = u[i], u[i + 1], likewise v along y and w along z
+__device__ __forceinline__ double source_from_faces(const DGrid &g, int kk, double u0, double up, double v0, double vp, double w0, double wp,
+                                                    bool weight_by_dz) {
     const double ax = g.ax[kk], ay = g.ay[kk], az = g.az;
-    const int ip = ((wrap & 1) && i == g.Nx) ? 1 : i + 1, jp = ((wrap & 2) && j == g.Ny) ? 1 : j + 1, kp = ((wrap & 4) && k == g.Nz) ? 1 : k + 1;
-    const double up = (ue && i == g.Nx) ? ue[(long)(j - 1) + (long)g.Ny * (k - 1)] : u.at(ip, j, k);
     // δ along a Flat direction is zero(FT) (Operators/difference_operators.jl:30-49)
-    double dx = g.tx == OCN_FLAT ? 0.0 : ax * up - ax * u.at(i, j, k);      // δxᶜᶜᶜ(Ax_qᶠᶜᶜ, u)
-    double dy = g.ty == OCN_FLAT ? 0.0 : ay * v.at(i, jp, k) - ay * v.at(i, j, k);
-    double dz = g.tz == OCN_FLAT ? 0.0 : az * w.at(i, j, kp) - az * w.at(i, j, k);
+    double dx = g.tx == OCN_FLAT ? 0.0 : ax * up - ax * u0;      // δxᶜᶜᶜ(Ax_qᶠᶜᶜ, u)
+    double dy = g.ty == OCN_FLAT ? 0.0 : ay * vp - ay * v0;
+    double dz = g.tz == OCN_FLAT ? 0.0 : az * wp - az * w0;
     double div = g.vinv_c[kk] * ((dx + dy) + dz);                 // divᶜᶜᶜ, Operators/divergence_operators.jl:16-19
     return weight_by_dz ? (1.0 * g.dzc[kk]) * div : 1.0 * div;
+}
+__device__ __forceinline__ double source_value(const DGrid &g, const FView &u, const FView &v, const FView &w, int i, int j, int k,
+                                               bool weight_by_dz, int wrap, const double *ue = nullptr) {
+    const int ip = ((wrap & 1) && i == g.Nx) ? 1 : i + 1, jp = ((wrap & 2) && j == g.Ny) ? 1 : j + 1, kp = ((wrap & 4) && k == g.Nz) ? 1 : k + 1;
+    const double up = (ue && i == g.Nx) ? ue[(long)(j - 1) + (long)g.Ny * (k - 1)] : u.at(ip, j, k);
+    // (a Flat direction has no upper neighbour to read)
+    const bool fx = g.tx == OCN_FLAT, fy = g.ty == OCN_FLAT, fz = g.tz == OCN_FLAT;
+    return source_from_faces(g, k - 1 + g.Hz, fx ? 0.0 : u.at(i, j, k), fx ? 0.0 : up, fy ? 0.0 : v.at(i, j, k), fy ? 0.0 : v.at(i, jp, k),
+                             fz ? 0.0 : w.at(i, j, k), fz ? 0.0 : w.at(i, j, kp), weight_by_dz);
 }
 
 template <bool REAL_OUT>
@@ -1333,6 +1340,32 @@ __global__ void __launch_bounds__(256) source_term_kernel(DGrid g, FView u, FVie
         ((double *)rhs)[q] = val;
         if (pad && i == g.Nx) ((double *)rhs)[q + 1] = 0.0;
     } else ((double2 *)rhs)[q] = make_double2(val, 0.0);    // the reference's complex storage
+}
+
+// Stage 1 of an RK3 step on a triply periodic grid: rk3_substep_kernel (no ζ term) and source_term_kernel<true> (wrap = 7) in one pass.
+// The tracers are advanced in place. u*, v*, w* = U + Δt γ G are formed for the cell and for its three upper neighbours (at the wrapped
+// interior index: G is zero in the halo) but NOT stored: a neighbour's thread may run before or after this one, so an in-place store
+// would let it read u* where it expects U. pressure_correction_periodic_kernel<., true> forms the same u* again -- the same expression
+// on the same operands, the same bits -- and corrects it, so the velocities are still read once and written once per stage.
+__global__ void __launch_bounds__(256) substep_source_kernel(DGrid g, SubstepArgs a, double dt, double gamma, double *rhs, bool weight_by_dz) {
+    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = 1 + blockIdx.z;
+    if (i > g.Nx || j > g.Ny || k > g.Nz) return;
+    for (int f = 3; f < a.n; ++f) {
+        const long q = a.view[f].lin(i, j, k);
+        double Uv = a.U[f][q];
+        Uv += dt * gamma * a.Gn[f][q];
+        a.U[f][q] = Uv;
+    }
+    const int ip = i == g.Nx ? 1 : i + 1, jp = j == g.Ny ? 1 : j + 1, kp = k == g.Nz ? 1 : k + 1;
+    const long qu = a.view[0].lin(i, j, k), qup = a.view[0].lin(ip, j, k);
+    const long qv = a.view[1].lin(i, j, k), qvp = a.view[1].lin(i, jp, k);
+    const long qw = a.view[2].lin(i, j, k), qwp = a.view[2].lin(i, j, kp);
+    const double u0 = a.U[0][qu] + dt * gamma * a.Gn[0][qu], up = a.U[0][qup] + dt * gamma * a.Gn[0][qup];
+    const double v0 = a.U[1][qv] + dt * gamma * a.Gn[1][qv], vp = a.U[1][qvp] + dt * gamma * a.Gn[1][qvp];
+    const double w0 = a.U[2][qw] + dt * gamma * a.Gn[2][qw], wp = a.U[2][qwp] + dt * gamma * a.Gn[2][qwp];
+    rhs[(long)(i - 1) + (long)g.Nx * ((j - 1) + (long)g.Ny * (k - 1))] = source_from_faces(g, k - 1 + g.Hz, u0, up, v0, vp, w0, wp, weight_by_dz);
 }
 
 // pdiv != nullptr: also `pNHS ./= Δt⁺`, written to a SECOND haloed array (neighbouring threads still read p) that the caller swaps in
@@ -1369,6 +1402,65 @@ __global__ void __launch_bounds__(256) pressure_correction_dense_kernel(DGrid g,
     v.at(i, j, k) -= (pc - pjm) * g.rdy;
     w.at(i, j, k) -= (pc - pkm) * g.rdzf[k - 1 + g.Hz];
     if (store_p) p.at(i, j, k) = pc / divisor;
+}
+
+// pressure_correction_dense_kernel on a triply periodic grid, with the passes that surround it folded in.
+// SUBSTEP (RK3 stage 1 after substep_source_kernel): u, v, w still hold U; the thread forms u* = U + Δt γ G first, as rk3_substep_kernel does.
+// FOLD: every halo cell of a periodic direction is a copy of an interior cell, and after this kernel u, v, w (and p / Δt⁺ when stored) are
+// final until the next tendency evaluation, as the tracers `tr` already are. The thread of interior cell (i, j, k) therefore also writes its
+// values to the periodic images of the cell -- per direction the offsets {0}, +N if the index <= H, -N if the index > N - H (both when
+// N < 2H), every combination but (0, 0, 0) -- which is what fill_periodic_xyz_kernel would copy there. Only halo cells are written and
+// none is read, so the threads do not depend on each other. All parents have the same shape (no Face field has an extra point).
+template <bool FOLD, bool SUBSTEP>
+__global__ void __launch_bounds__(256) pressure_correction_periodic_kernel(DGrid g, FView u, FView v, FView w, const double *pd, FView p,
+                                                                           double divisor, bool store_p, FieldList tr, const double *Gu,
+                                                                           const double *Gv, const double *Gw, double dt, double gamma) {
+    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = 1 + blockIdx.z;
+    if (i > g.Nx || j > g.Ny || k > g.Nz) return;
+    const long sx = g.Nx, sxy = (long)g.Nx * g.Ny;
+    const long q = (long)(i - 1) + sx * (j - 1) + sxy * (k - 1);
+    const double pc = pd[q];
+    const double pim = pd[i == 1 ? q + (g.Nx - 1) : q - 1];
+    const double pjm = pd[j == 1 ? q + sx * (g.Ny - 1) : q - sx];
+    const double pkm = pd[k == 1 ? q + sxy * (g.Nz - 1) : q - sxy];
+    const long qu = u.lin(i, j, k), qv = v.lin(i, j, k), qw = w.lin(i, j, k), qc = p.lin(i, j, k);
+    double un = u.p[qu], vn = v.p[qv], wn = w.p[qw];
+    if (SUBSTEP) {
+        un += dt * gamma * Gu[qu];
+        vn += dt * gamma * Gv[qv];
+        wn += dt * gamma * Gw[qw];
+    }
+    un -= (pc - pim) * g.rdx;
+    vn -= (pc - pjm) * g.rdy;
+    wn -= (pc - pkm) * g.rdzf[k - 1 + g.Hz];
+    u.p[qu] = un;
+    v.p[qv] = vn;
+    w.p[qw] = wn;
+    const double ps = pc / divisor;
+    if (store_p) p.p[qc] = ps;
+    if (!FOLD) return;
+    const bool lo[3] = {i <= g.Hx, j <= g.Hy, k <= g.Hz}, hi[3] = {i > g.Nx - g.Hx, j > g.Ny - g.Hy, k > g.Nz - g.Hz};
+    if (!(lo[0] || hi[0] || lo[1] || hi[1] || lo[2] || hi[2])) return;
+    for (int c = 0; c < 3; ++c) {                   // 0: the cell itself, 1: its image at +N, 2: at -N
+        if ((c == 1 && !lo[2]) || (c == 2 && !hi[2])) continue;
+        const int dk = c == 0 ? 0 : (c == 1 ? g.Nz : -g.Nz);
+        for (int b = 0; b < 3; ++b) {
+            if ((b == 1 && !lo[1]) || (b == 2 && !hi[1])) continue;
+            const int dj = b == 0 ? 0 : (b == 1 ? g.Ny : -g.Ny);
+            for (int a = 0; a < 3; ++a) {
+                if ((a == 1 && !lo[0]) || (a == 2 && !hi[0]) || (a == 0 && b == 0 && c == 0)) continue;
+                const int di = a == 0 ? 0 : (a == 1 ? g.Nx : -g.Nx);
+                u.p[qu + di + (long)u.s1 * dj + u.s2 * dk] = un;
+                v.p[qv + di + (long)v.s1 * dj + v.s2 * dk] = vn;
+                w.p[qw + di + (long)w.s1 * dj + w.s2 * dk] = wn;
+                const long d = di + (long)p.s1 * dj + p.s2 * dk;
+                if (store_p) p.p[qc + d] = ps;
+                for (int t = 0; t < tr.n; ++t) tr.p[t][qc + d] = tr.p[t][qc];
+            }
+        }
+    }
 }
 
 __global__ void __launch_bounds__(256) divide_interior_kernel(DGrid g, FView p, double divisor) {

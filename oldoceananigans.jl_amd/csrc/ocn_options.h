@@ -24,7 +24,8 @@ struct OcnOptions {
     int amd_march = 1;                 // eddy diffusivities by the z-marching kernel that shares the point operands (0: one thread per cell, everything recomputed)
     int smag_march = 1;                // Smagorinsky eddy viscosity by its z-marching kernel (0: one thread per cell, every point value recomputed)
     // halo fills
-    int fused_halo = 1;                // triply periodic grids: the three directional periodic fills as one launch
+    int fused_halo = 1;                // triply periodic grids: the three directional periodic fills as one launch; inside a time-step they
+                                       // ride in the pressure-correction kernel (pressure_step, fold_halos)
     // pressure solve
     int real_fft = 1;                  // D2Z / Z2D transforms (0: the reference's complex-to-complex)
     int c2r_strided = 1;               // Z2D straight into the interior of the haloed pressure field
@@ -43,7 +44,8 @@ struct OcnOptions {
     int dist_pencil_transposes = 1;    // pencil partitions of triply Periodic grids: the reference's transposing solver (0: gathered solve)
     // model time-step
     int swap_tendencies = 1;           // cache_previous_tendencies! by pointer swap (0: copy kernel)
-    int fuse_substep = 1;              // substeps of RK3 stages 2 and 3 fused into the preceding tendency evaluation (see ocn_model_s::U2)
+    int fuse_substep = 1;              // substeps of RK3 stages 2 and 3 fused into the preceding tendency evaluation (see ocn_model_s::U2);
+                                       // triply periodic grids: the substep of stage 1 fused into the pressure step (PendingSubstep)
     int fused_epilogue = 1;            // Coriolis + hydrostatic gradient + closure (+ substep) as one launch
     int fused_forcing = 1;             // the forcing term rides in the role tendency kernel when it can (0: always the standalone pass)
     // One RK3 time-step is ~50 dependent launches. use_graph = 1 captures the step once per (Δt, configuration) into a hipGraph and
