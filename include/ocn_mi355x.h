@@ -131,6 +131,18 @@ int ocn_compute_Gc(ocn_grid_t grid, const double *u, const double *v, const doub
 int ocn_compute_tendencies(ocn_grid_t grid, const double *u, const double *v, const double *w,
                            const double *const *tracers, int ntracers,
                            double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range);
+/* One advection term with the advecting velocities apart from the advected field: G = -div(advection, (ua, va, wa), psi), or with
+ * accumulate != 0 G = G - div(...). which: 0 div_𝐯u, 1 div_𝐯v, 2 div_𝐯w (Advection/momentum_advection_operators.jl:46-83; psi and G at
+ * the location of u / v / w), 3 div_Uc (tracer_advection_operators.jl:29-33; psi and G at ccc). These are the two terms a model with
+ * background_fields evaluates per field (nonhydrostatic_tendency_kernel_functions.jl:86-94,148-156,213-221,276-293). All arrays are
+ * haloed parents with filled halos; range as for ocn_compute_Gu; entries outside it keep their bits. Follows option "tendency_impl":
+ * 2 on a grid the role kernel serves (x, y Periodic, no Flat or reduced-order direction, option "arithmetic" 0) is one launch of the
+ * split role kernel, anything else the per-field kernel. */
+int ocn_compute_advective_tendency(ocn_grid_t grid, const double *ua, const double *va, const double *wa, const double *psi, int which,
+                                   double *G, const int *range, int accumulate);
+/* out = a + b over the whole parent array of a field at `loc`, halos included: one IEEE addition per element, what an access to the
+ * reference's SumOfArrays{2} computes (Utils/sum_of_arrays.jl:23,39-41) -- the total velocities u + Ū of a model with background fields */
+int ocn_sum_parent(ocn_grid_t grid, const double *a, const double *b, const int loc[3], double *out);
 /* the same pass with the rk3_substep! of the NEXT stage (runge_kutta_3.jl:179-226) fused in: when a cell's tendency is
  * complete, U_next = U + dt (gamma Gn + zeta Gm) is written to a SECOND set of prognostic arrays (U itself is still read by
  * neighbouring workgroups); the caller then swaps the two sets. fields / next / Gn / Gm are ordered u, v, w, tracers
@@ -435,6 +447,21 @@ typedef struct {
     double target;
 } ocn_forcing_t;
 int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *terms, int nterms);
+/* background_fields = (name = B,) of the model constructor (Models/NonhydrostaticModels/background_fields.jl:97-116, BackgroundFields{false}):
+ * name is "u", "v", "w" or "c<n>"; parent is a haloed device array at that field's location, BORROWED for the model's lifetime, whose
+ * halos hold what the background is there (a function's analytic continuation, not a periodic wrap); NULL removes it (ZeroField).
+ * Every tendency evaluation then computes G_φ = -div(U + Ū, φ) - div(U, Φ̄) + ... -- the second term only for fields that have a
+ * background -- and ocn_model_cell_advection_timescale uses U + Ū; closures, buoyancy, Coriolis, the hydrostatic pressure anomaly,
+ * boundary conditions and the pressure solve see the model's own fields only. update_state! writes U + Ū of the components that have a
+ * background over the whole parent array after the halo fill. ocn_model_field answers "bg_<name>" (the caller's array) and
+ * "total_u|v|w" (OCN_ESTATE when that field has no background); ocn_model_get_option answers "background_fields" (how many fields have
+ * one) and "background_tendency_path" (0 none, 1 per-field kernels, 2 the split role kernel). With a background the RK3 substep and the
+ * forcing do not ride in an advection launch: the substep rides in the epilogue pass when the model has one (physics terms or Flux
+ * conditions), otherwise "fuse_substep_active" answers 0. The "bg_<name>" pointer is the caller's own array, handed back READ-ONLY: the
+ * library never writes it and neither may a holder of that pointer while the model lives. With option "arithmetic" = 1 the background
+ * terms are evaluated in the reference's arithmetic (the per-field kernels) while a term 1 without background velocities keeps the
+ * contracted one: the two advection terms of one tendency then differ in arithmetic mode. OCN_ENOTSUP on a partitioned model. */
+int ocn_model_set_background_field(ocn_model_t model, const char *name, const double *parent);
 /* Tuning options (no reference equivalent; the defaults are the tuned values). ocn_set_option sets the library default of a key; may be
  * called before ocn_init. A model copies the defaults when it is created, and ocn_model_set_option changes that model's copy only.
  * Grid-level entry points and standalone solvers (ocn_compute_*, ocn_fill_halo_regions*, ocn_poisson_*, ocn_solve_for_pressure,

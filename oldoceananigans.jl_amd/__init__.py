@@ -9,6 +9,7 @@ from .advection import (Centered, FluxFormAdvection, UpwindBiased, WENO, adapt_a
 from .architectures import GPU, architecture, ndevices, own_stream, set_option, synchronize
 from .boundary_conditions import (BoundaryCondition, FieldBoundaryConditions, FluxBoundaryCondition,
                                   GradientBoundaryCondition, LinearFieldFlux, OpenBoundaryCondition, ValueBoundaryCondition, compute_flux_bcs)
+from .background_fields import BackgroundField, BackgroundFields
 from .buoyancy import BuoyancyTracer, FPlane, LinearEquationOfState, SeawaterBuoyancy
 from .checkpointer import set_from_checkpoint, write_checkpoint
 from .closures import (AnisotropicMinimumDissipation, DynamicCoefficient, ExplicitTimeDiscretization, ScalarDiffusivity, Smagorinsky,

@@ -101,6 +101,9 @@ SYMBOLS = {
     "ocn_compute_linear_flux_bc": (C.c_int, [_vp, _vp, _ip, C.c_int, C.c_double, C.c_double, _vp]),
     "ocn_model_set_linear_flux_bc": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_double, C.c_double, C.c_char_p]),
     "ocn_model_set_forcing": (C.c_int, [_vp, C.c_int, C.POINTER(Forcing), C.c_int]),
+    "ocn_compute_advective_tendency": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _ip, C.c_int]),
+    "ocn_sum_parent": (C.c_int, [_vp, _vp, _vp, _ip, _vp]),
+    "ocn_model_set_background_field": (C.c_int, [_vp, C.c_char_p, _vp]),
     "ocn_make_pressure_correction_range": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _ip]),
     "ocn_make_pressure_correction_divide": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _ip]),
     "ocn_model_reset": (C.c_int, [_vp]),

@@ -13,7 +13,9 @@ open) -- while the CONTENT follows the reference's layout: one entry per address
 `set_from_checkpoint` is `set!(model, filepath)`: copy the arrays, set the clock; the next time-step continues bit for bit where the
 checkpointed run would have gone (tests/test_gpu_parity.py::test_checkpoint_and_restore_continue_bit_identically).
 One deliberate difference in the content: this library's Gⁿ holds the Flux-boundary-condition terms between time-steps,
-the reference adds them right before each substep -- a model without valued Flux conditions writes the same Gⁿ."""
+the reference adds them right before each substep -- a model without valued Flux conditions writes the same Gⁿ.
+Background fields are not stored (the reference's checkpointed properties, checkpointer.jl:60-66, do not name them either): the model
+restored into is built with the same `background_fields`."""
 import ctypes as C
 
 import numpy as np

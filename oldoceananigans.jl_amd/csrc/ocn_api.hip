@@ -6,6 +6,7 @@
 #include "ocn_options.h"
 #include "ocn_tendency_fused.h"
 #include "ocn_tendency_roles.h"
+#include "ocn_advect_split.h"
 #include "ocn_epilogue_march.h"
 #include "ocn_forcing.h"
 #include "ocn_implicit_z.h"
@@ -621,6 +622,88 @@ extern "C" int ocn_compute_tendencies(ocn_grid_t grid, const double *u, const do
     if (rc) return rc;
     KERNEL_CHECK();
     return OCN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// advection with advecting != advected (ocn_advect_split.h): the two advection terms of a model with background_fields
+// ---------------------------------------------------------------------------------------------------------------------
+static const int *field_loc(int f) { return f == 0 ? LOC_U : (f == 1 ? LOC_V : (f == 2 ? LOC_W : LOC_C)); }
+
+template <int F>
+static int launch_advective_tendency(const DGrid &g, const double *const adv[3], const double *psi, double *G, const int *range, bool accumulate) {
+    const int *loc = field_loc(F);
+    Range6 r;
+    int rc = check_range(g, range, &r, loc, F != F_C);
+    if (rc) return rc;
+    const int nx = r.i1 - r.i0 + 1, ny = r.j1 - r.j0 + 1, nz = r.k1 - r.k0 + 1;
+    if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
+    const FView fu = make_view(g, adv[0], LOC_U), fv = make_view(g, adv[1], LOC_V), fw = make_view(g, adv[2], LOC_W);
+    const FView fp = make_view(g, psi, loc), fG = make_view(g, G, loc);
+    if (accumulate) hipLaunchKernelGGL((advective_tendency_kernel<F, true>), grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, fu, fv, fw, fp, fG, r);
+    else            hipLaunchKernelGGL((advective_tendency_kernel<F, false>), grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, fu, fv, fw, fp, fG, r);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+// whether the split instantiation of the role kernel serves this grid: where the role kernel runs today (tendency_impl 2 on a grid both
+// flux-sharing conditions hold for), in the reference's arithmetic -- the contracted arithmetic (option "arithmetic") has no split build
+static bool split_role_path(const OcnOptions &o, const DGrid &g, int impl) {
+    return impl == 2 && o.arithmetic == 0 && fused_tendency_supported(g, nullptr) && role_tendency_supported(o, g);
+}
+
+// -div(advection, adv, psi[f]) of the fields `roles` into G[f] (accumulate: G[f] -= div): one role-kernel launch, or one per-field
+// launch each
+static int advective_terms(const OcnOptions &o, const DGrid &g, const double *const adv[3], const double *const *psi, double *const *G,
+                           const int *roles, int nrole, const int *range, bool accumulate, int impl) {
+    if (nrole <= 0) return OCN_OK;
+    if (split_role_path(o, g, impl)) {
+        int rc = check_range(g, range, nullptr);
+        if (rc) return rc;
+        rc = launch_role_split(o, g, g_stream, adv, psi, G, roles, nrole, range, accumulate);
+        if (rc) return fail(rc, "split role tendency launch failed");
+        KERNEL_CHECK();
+        return OCN_OK;
+    }
+    for (int q = 0; q < nrole; ++q) {
+        const int f = roles[q];
+        int rc = f == 0 ? launch_advective_tendency<F_U>(g, adv, psi[f], G[f], range, accumulate)
+               : f == 1 ? launch_advective_tendency<F_V>(g, adv, psi[f], G[f], range, accumulate)
+               : f == 2 ? launch_advective_tendency<F_W>(g, adv, psi[f], G[f], range, accumulate)
+                        : launch_advective_tendency<F_C>(g, adv, psi[f], G[f], range, accumulate);
+        if (rc) return rc;
+    }
+    return OCN_OK;
+}
+
+extern "C" int ocn_compute_advective_tendency(ocn_grid_t grid, const double *ua, const double *va, const double *wa, const double *psi,
+                                              int which, double *G, const int *range, int accumulate) {
+    NEED_INIT();
+    if (!grid || !ua || !va || !wa || !psi || !G) return fail(OCN_EINVAL, "NULL argument");
+    if (which < 0 || which > 3) return fail(OCN_EINVAL, "which is 0 (u), 1 (v), 2 (w) or 3 (tracer)");
+    if (!grid->advection_error.empty()) return fail(OCN_EINVAL, "%s", grid->advection_error.c_str());
+    const double *adv[3] = {ua, va, wa};
+    const double *P[OCN_MAX_FIELDS] = {};
+    double *Gs[OCN_MAX_FIELDS] = {};
+    P[which] = psi; Gs[which] = G;
+    return advective_terms(g_defaults, grid->d, adv, P, Gs, &which, 1, range, accumulate != 0, g_defaults.tendency_impl);
+}
+
+static int sum_parent(const DGrid &g, const double *a, const double *b, const int loc[3], double *out) {
+    int P[3];
+    parent_size(g, loc, P);
+    const long n = (long)P[0] * P[1] * P[2];
+    const int nb = (int)std::min<long>((n + 255) / 256, 8192);
+    hipLaunchKernelGGL(sum_parent_kernel, dim3(nb), dim3(256), 0, g_stream, a, b, out, n);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+extern "C" int ocn_sum_parent(ocn_grid_t grid, const double *a, const double *b, const int loc[3], double *out) {
+    NEED_INIT();
+    if (!grid || !a || !b || !loc || !out) return fail(OCN_EINVAL, "NULL argument");
+    for (int d = 0; d < 3; ++d)
+        if (loc[d] != OCN_CENTER && loc[d] != OCN_FACE) return fail(OCN_EINVAL, "loc[%d] is OCN_CENTER or OCN_FACE", d);
+    return sum_parent(grid->d, a, b, loc, out);
 }
 
 static int update_hydrostatic_pressure(const DGrid &g, int kind, const double *bT, const double *S, double grav, double alpha, double beta,
@@ -2509,6 +2592,10 @@ struct ocn_model_s {
     int buoyancy_kind = 0, bT_index = 0, S_index = 0;    // 0 nothing, 1 BuoyancyTracer, 2 linear SeawaterBuoyancy
     double grav = 0.0, alpha = 0.0, beta = 0.0;
     double *pHY = nullptr;                  // hydrostatic pressure anomaly (only with buoyancy)
+    // background_fields = (u = Ū, b = B̄, ...) (background_fields.jl): borrowed haloed arrays at their field's location (NULL: ZeroField),
+    // and the total velocities U + Ū update_state! forms for the components that have one (owned; allocated by the setter)
+    const double *bg[OCN_MAX_FIELDS] = {};
+    double *tot[3] = {};
     double *p;
     ocn_poisson_t solver;
     double *blockmax;
@@ -2529,6 +2616,7 @@ extern "C" int ocn_model_destroy(ocn_model_t m) {
     if (m->graph_exec) hipGraphExecDestroy(m->graph_exec);
     for (int f = 0; f < m->nf; ++f) { hipFree(m->U[f]); hipFree(m->U2[f]); hipFree(m->Gn[f]); hipFree(m->Gm[f]); }
     hipFree(m->pHY);
+    for (int c = 0; c < 3; ++c) hipFree(m->tot[c]);
     hipFree(m->forcing_d);
     for (auto &f : m->forcing_tables)
         for (auto &t : f) { hipFree(t[0]); hipFree(t[1]); }
@@ -2590,6 +2678,14 @@ extern "C" int ocn_model_create(ocn_model_t *model, ocn_grid_t grid, int ntracer
     return model_create(model, grid, ntracers, true);
 }
 
+static int model_field_index(const ocn_model_s *m, const char *name) {
+    if (!strcmp(name, "u")) return 0;
+    if (!strcmp(name, "v")) return 1;
+    if (!strcmp(name, "w")) return 2;
+    if (name[0] == 'c' && name[1] >= '0' && name[1] <= '9' && !name[2] && name[1] - '0' < m->ntr) return 3 + (name[1] - '0');
+    return -1;
+}
+
 static int field_lookup(ocn_model_s *m, const char *name, double ***slot, int **loc) {
     const char *q = name;
     char kind = 'U';
@@ -2606,6 +2702,16 @@ static int field_lookup(ocn_model_s *m, const char *name, double ***slot, int **
         const int t = name[7] - '0';
         if (name[7] < '0' || name[7] > '9' || name[8] || t >= m->ntr) return fail(OCN_EINVAL, "no eddy diffusivity field %s", name);
         *slot = &m->kappa_e[t];
+        return OCN_OK;
+    }
+    // background_fields: "bg_<name>" is the caller's array, "total_<name>" a velocity component's U + Ū as of the last update_state!
+    if (!strncmp(name, "bg_", 3) || !strncmp(name, "total_", 6)) {
+        const bool total = name[0] == 't';
+        const int f = model_field_index(m, name + (total ? 6 : 3));
+        if (f < 0 || (total && f > 2)) return fail(OCN_EINVAL, "no background field %s", name);
+        if (!m->bg[f]) return fail(OCN_ESTATE, "the model has no background field for %s", name + (total ? 6 : 3));
+        *slot = total ? &m->tot[f] : const_cast<double **>(&m->bg[f]);
+        *loc = m->loc[f];
         return OCN_OK;
     }
     if (q[0] == 'G' || q[0] == 'M') { kind = q[0]; ++q; }
@@ -2741,6 +2847,29 @@ static bool has_physics(const ocn_model_s *m) { return m->has_coriolis || m->buo
 // the form of the vertically implicit solve a model runs (ocn_implicit_z.h): the reference-shaped one, the only one shipped
 static int model_ivd_form(const ocn_model_s *) { return 0; }
 
+// background_fields: how many fields carry one, whether a velocity component does (then the advecting velocities are the totals)
+static int count_background(const ocn_model_s *m) {
+    int n = 0;
+    for (int f = 0; f < m->nf; ++f) n += m->bg[f] ? 1 : 0;
+    return n;
+}
+static bool has_background(const ocn_model_s *m) { return count_background(m) > 0; }
+static bool has_background_velocity(const ocn_model_s *m) { return m->bg[0] || m->bg[1] || m->bg[2]; }
+// total_velocities(model) (nonhydrostatic_model.jl:265-266): the model's own array where a component has no background (ZeroField)
+static const double *total_velocity(const ocn_model_s *m, int c) { return m->bg[c] ? m->tot[c] : m->U[c]; }
+static int update_total_velocities(ocn_model_s *m) {
+    for (int c = 0; c < 3; ++c)
+        if (m->bg[c]) {
+            int rc = sum_parent(m->grid->d, m->U[c], m->bg[c], m->loc[c], m->tot[c]);
+            if (rc) return rc;
+        }
+    return OCN_OK;
+}
+// which kernels evaluate the background terms (option "background_tendency_path"): 0 none, 1 the per-field kernels, 2 the role kernel
+static int background_tendency_path(const ocn_model_s *m) {
+    return !has_background(m) ? 0 : (split_role_path(m->opt, m->grid->d, m->opt.tendency_impl) ? 2 : 1);
+}
+
 static bool has_forcing(const ocn_model_s *m) {
     for (int f = 0; f < m->nf; ++f)
         if (m->forcing_h.nterms[f] > 0) return true;
@@ -2752,7 +2881,7 @@ static bool epilogue_runs(const ocn_model_s *m);
 // spilled, ocn_tendency_roles.h) -- the configs[1]-plus-sponge case, which keeps the RK3 substep fused. Partitioned models (interior / strip launches) and everything else take the standalone pass.
 static bool forcing_in_role(const ocn_model_s *m) {
     const DGrid &g = m->grid->d;
-    return has_forcing(m) && m->opt.fused_forcing && !m->dm && !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && !epilogue_runs(m) &&
+    return has_forcing(m) && !has_background(m) && m->opt.fused_forcing && !m->dm && !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && !epilogue_runs(m) &&
            m->opt.tendency_impl == 2 && m->opt.arithmetic == 0 && g.tz == OCN_PERIODIC && fused_path(m->opt, g, nullptr, m->ntr, 2) &&
            role_tendency_supported(m->opt, g);
 }
@@ -2918,6 +3047,7 @@ static bool can_fuse_substep(const ocn_model_s *m) {
     if (!m->opt.fuse_substep || !m->opt.swap_tendencies) return false;
     if (has_forcing(m) && !forcing_in_role(m)) return false;         // the forcing pass completes G after the launch the substep would ride in
     if (epilogue_runs(m)) return true;                               // the epilogue pass also applies the Flux conditions
+    if (has_background(m)) return false;                             // the second advection term follows the launch the substep would ride in
     return !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && fused_path(m->opt, m->grid->d, nullptr, m->ntr, m->opt.tendency_impl);
 }
 
@@ -2929,6 +3059,8 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     if (!strcmp(key, "graph_captures")) { *value = m->graph_captures; return OCN_OK; }
     if (!strcmp(key, "graph_failures")) { *value = m->graph_failures; return OCN_OK; }
     if (!strcmp(key, "forcing_path")) { *value = forcing_path(m); return OCN_OK; }
+    if (!strcmp(key, "background_fields")) { *value = count_background(m); return OCN_OK; }
+    if (!strcmp(key, "background_tendency_path")) { *value = background_tendency_path(m); return OCN_OK; }
     if (!strcmp(key, "vertically_implicit")) { *value = m->vi ? 1 : 0; return OCN_OK; }
     // which epilogue adds the closure terms: the z-marching one (1) or the per-value one (0) -- the explicit part of a vertically implicit
     // discretisation exists in the per-value epilogue only
@@ -2969,6 +3101,8 @@ static int update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *s
 static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub, const int *amd_range) {
     const DGrid &g = m->grid->d;
     int rc;
+    // the total velocities of a model with background velocities, from the halo-filled prognostic ones (whole parent arrays)
+    if (has_background_velocity(m) && (rc = update_total_velocities(m))) return rc;
     // compute_auxiliaries!: compute_diffusivities! over :xyz (update_nonhydrostatic_model_state.jl:58-69), then
     // fill_halo_regions!(model.diffusivity_fields; only_local_halos = true) (:44) with the default ccc conditions
     if (m->has_amd) {
@@ -3010,6 +3144,25 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
             HIP_TRY(hipEventRecord(ev->first, g_stream));
         }
         const bool physics = has_physics(m) || epilogue_runs(m);
+        if (has_background(m)) {
+            // G = - div(U + Ū, φ) - div(U, Φ̄) ... (nonhydrostatic_tendency_kernel_functions.jl:86-94,148-156,213-221,276-293): term 1 is
+            // today's launch when no velocity has a background (U + ZeroField is U), else the split one with the totals; term 2 accumulates
+            // over the fields that have a background (div(U, ::ZeroField) = 0). Neither carries the substep or the forcing: a substep rides
+            // in the epilogue pass that closes the cells after both terms, or not at all (can_fuse_substep).
+            if (sub && !physics) return fail(OCN_ESTATE, "fused substep requested in the advection launch of a model with background fields");
+            int roles[OCN_MAX_FIELDS], nb = 0;
+            for (int f = 0; f < m->nf; ++f) roles[f] = f;
+            if (has_background_velocity(m)) {
+                const double *adv[3] = {total_velocity(m, 0), total_velocity(m, 1), total_velocity(m, 2)};
+                rc = advective_terms(m->opt, g, adv, m->U, m->Gn, roles, m->nf, nullptr, false, m->opt.tendency_impl);
+            } else
+                rc = compute_tendencies(m->opt, g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
+                                        m->opt.tendency_impl);
+            for (int f = 0; f < m->nf; ++f)
+                if (m->bg[f]) roles[nb++] = f;
+            const double *adv[3] = {m->U[0], m->U[1], m->U[2]};
+            if (!rc) rc = advective_terms(m->opt, g, adv, m->bg, m->Gn, roles, nb, nullptr, true, m->opt.tendency_impl);
+        } else
         rc = compute_tendencies(m->opt, g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
                                 m->opt.tendency_impl, physics ? nullptr : sub, forcing_in_role(m) ? m->forcing_d : nullptr);
         if (ev) HIP_TRY(hipEventRecord(ev->second, g_stream));
@@ -3220,14 +3373,6 @@ static int implicit_step(ocn_model_s *m, double dt) {
     return OCN_OK;
 }
 
-static int model_field_index(const ocn_model_s *m, const char *name) {
-    if (!strcmp(name, "u")) return 0;
-    if (!strcmp(name, "v")) return 1;
-    if (!strcmp(name, "w")) return 2;
-    if (name[0] == 'c' && name[1] >= '0' && name[1] <= '9' && !name[2] && name[1] - '0' < m->ntr) return 3 + (name[1] - '0');
-    return -1;
-}
-
 // name.side = FluxBoundaryCondition((ξ, η, t, φ, p) -> a + b φ, field_dependencies = dep) (continuous_boundary_function.jl:128-161)
 extern "C" int ocn_model_set_linear_flux_bc(ocn_model_t m, const char *name, int side, double a, double b, const char *dep) {
     if (!m || !name || !dep) return fail(OCN_EINVAL, "NULL argument");
@@ -3250,6 +3395,27 @@ extern "C" int ocn_model_set_linear_flux_bc(ocn_model_t m, const char *name, int
 
 // forcing = (name = F,) of the model constructor (Forcings/model_forcing.jl, relaxation.jl, forcing.jl:165-177, multiple_forcings.jl):
 // the descriptors of field `field` are replaced; the device-resident table is rewritten (ocn_forcing.h)
+// background_fields = (name = parent,) (background_fields.jl:97-116 after regularisation: an array at the field's location)
+extern "C" int ocn_model_set_background_field(ocn_model_t m, const char *name, const double *parent) {
+    NEED_INIT();
+    if (m) m->epoch += 1;
+    if (!m || !name) return fail(OCN_EINVAL, "NULL argument");
+    if (m->dm) return fail(OCN_ENOTSUP, "background fields are not served on a partitioned model");
+    const int f = model_field_index(m, name);
+    if (f < 0) return fail(OCN_EINVAL, "background fields can be set on u, v, w and the tracers c0..c%d; got '%s'", m->ntr - 1, name);
+    if (f < 3 && parent && !m->tot[f]) {
+        // the total-velocity buffer of this component: made here, never inside a (captured) time-step
+        int P[3];
+        parent_size(m->grid->d, m->loc[f], P);
+        const size_t bytes = (size_t)P[0] * P[1] * P[2] * sizeof(double);
+        hipError_t e = dev_alloc((void **)&m->tot[f], bytes);
+        if (e != hipSuccess) { m->tot[f] = nullptr; return fail((int)e, "dev_alloc(total velocity): %s", hipGetErrorString(e)); }
+        HIP_TRY(hipMemsetAsync(m->tot[f], 0, bytes, g_stream));
+    }
+    m->bg[f] = parent;
+    return OCN_OK;
+}
+
 extern "C" int ocn_model_set_forcing(ocn_model_t m, int field, const ocn_forcing_t *terms, int nterms) {
     NEED_INIT();
     if (!m) return fail(OCN_EINVAL, "NULL argument");
@@ -3757,7 +3923,10 @@ extern "C" int ocn_model_cell_advection_timescale(ocn_model_t m, double *tau) {
     NEED_INIT();
     if (!m || !tau) return fail(OCN_EINVAL, "NULL argument");
     double inv = 0;
-    int rc = max_inverse_advection_timescale(m->grid, m->U[0], m->U[1], m->U[2], &inv);
+    // cell_advection_timescale(model) uses total_velocities(model) (NonhydrostaticModels.jl:77-81): formed here from the fields as they are
+    int rc = has_background_velocity(m) ? update_total_velocities(m) : OCN_OK;
+    if (rc) return rc;
+    rc = max_inverse_advection_timescale(m->grid, total_velocity(m, 0), total_velocity(m, 1), total_velocity(m, 2), &inv);
     if (rc) return rc;
     if (m->dm && (rc = ocn_dist_allreduce_max(m->dm->dist, &inv))) return rc;
     *tau = 1.0 / inv;

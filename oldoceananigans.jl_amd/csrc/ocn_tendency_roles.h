@@ -135,7 +135,10 @@ struct PlaneCtx {
 
 // ---- loads and arithmetic of the three low-side fluxes of field ROLE at (i, j, k) ----
 // z-flux inputs besides the own z-window: the advecting w along x (role u) / along y (role v), indices 1 .. 4; w at the face (tracers)
-template <int ROLE> __device__ __forceinline__ Win6 load_zin(const PlaneCtx &p, unsigned so, const ColOff &o) {
+// SPLIT (ocn_advect_split.h): the advecting velocities are not the advected field, so the three self-advection fluxes (Uu, Vv, Ww) take
+// their symmetric transport from a second, 4-deep window of the ADVECTING component; the biased reconstruction keeps the own-field window
+template <int ROLE, bool SPLIT = false> __device__ __forceinline__ Win6 load_zin(const PlaneCtx &p, unsigned so, const ColOff &o) {
+    if (SPLIT && ROLE == ROLE_W) return zwin4(p.w, so, o, p.s2);
     if (ROLE == ROLE_U) return xwin4(p.w, so, o);
     if (ROLE == ROLE_V) return ywin4(p.w, so, o);
     Win6 w;
@@ -144,7 +147,7 @@ template <int ROLE> __device__ __forceinline__ Win6 load_zin(const PlaneCtx &p, 
     if (ROLE == ROLE_C) w.s[3] = ldb<24>(p.w, o.c, so);
     return w;
 }
-template <int ROLE, int ARITH>
+template <int ROLE, int ARITH, bool SPLIT = false>
 __device__ __forceinline__ double z_flux(const DGrid &g, const Win6 &zin, int i, int j, int k, const Win6 &qz) {
     const bool bx = g.tx != 0, by = g.ty != 0, bz = g.tz != 0;
     const double az = g.az;
@@ -155,7 +158,7 @@ __device__ __forceinline__ double z_flux(const DGrid &g, const Win6 &zin, int i,
         const double wt = sym4<ARITH>(zin, az, by, j, false, g.Ny);                         // Wv :63-69
         return wt * bias6<ARITH>(qz, wt > 0, bz, k, false, g.Nz);
     } else if (ROLE == ROLE_W) {
-        const double wt = sym4<ARITH>(qz, az, bz, k - 1, true, g.Nz);                       // Ww :87-93
+        const double wt = sym4<ARITH>(SPLIT ? zin : qz, az, bz, k - 1, true, g.Nz);                       // Ww :87-93
         return wt * bias6<ARITH>(qz, wt > 0, bz, k - 1, true, g.Nz);
     } else {
         const double w0 = zin.s[3];                                                  // advective_tracer_flux_z :115-121
@@ -163,7 +166,8 @@ __device__ __forceinline__ double z_flux(const DGrid &g, const Win6 &zin, int i,
     }
 }
 // x-flux: own field along x (qx) + the advecting u: along y (role v, indices 1 .. 4), along z (role w), at the face (tracers)
-template <int ROLE> __device__ __forceinline__ Win6 load_xaux(const PlaneCtx &p, const ColOff &o) {
+template <int ROLE, bool SPLIT = false> __device__ __forceinline__ Win6 load_xaux(const PlaneCtx &p, const ColOff &o) {
+    if (SPLIT && ROLE == ROLE_U) return xwin4(p.u, p.so, o);
     if (ROLE == ROLE_V) return ywin4(p.u, p.so, o);
     Win6 w;
 #pragma unroll
@@ -171,11 +175,11 @@ template <int ROLE> __device__ __forceinline__ Win6 load_xaux(const PlaneCtx &p,
     if (ROLE == ROLE_C) w.s[3] = ldb<24>(p.u, o.c, p.so);
     return w;
 }
-template <int ROLE, int ARITH>
+template <int ROLE, int ARITH, bool SPLIT = false>
 __device__ __forceinline__ double x_flux(const DGrid &g, const PlaneCtx &p, const Win6 &qx, const Win6 &aux, int i, int j, int k) {
     const bool bx = g.tx != 0, by = g.ty != 0, bz = g.tz != 0;
     if (ROLE == ROLE_U) {
-        const double ut = sym4<ARITH>(qx, p.axk, bx, i - 1, true, g.Nx);                    // advective_momentum_flux_Uu :23-29
+        const double ut = sym4<ARITH>(SPLIT ? aux : qx, p.axk, bx, i - 1, true, g.Nx);                    // advective_momentum_flux_Uu :23-29
         return ut * bias6<ARITH>(qx, ut > 0, bx, i - 1, true, g.Nx);
     } else if (ROLE == ROLE_V) {
         const double ut = sym4<ARITH>(aux, p.axk, by, j, false, g.Ny);                      // Uv :47-53
@@ -189,7 +193,8 @@ __device__ __forceinline__ double x_flux(const DGrid &g, const PlaneCtx &p, cons
     }
 }
 // y-flux: own field along y (qy) + the advecting v: along x (role u), along z (role w), at the face (tracers)
-template <int ROLE> __device__ __forceinline__ Win6 load_yaux(const PlaneCtx &p, const ColOff &o) {
+template <int ROLE, bool SPLIT = false> __device__ __forceinline__ Win6 load_yaux(const PlaneCtx &p, const ColOff &o) {
+    if (SPLIT && ROLE == ROLE_V) return ywin4(p.v, p.so, o);
     if (ROLE == ROLE_U) return xwin4(p.v, p.so, o);
     Win6 w;
 #pragma unroll
@@ -197,14 +202,14 @@ template <int ROLE> __device__ __forceinline__ Win6 load_yaux(const PlaneCtx &p,
     if (ROLE == ROLE_C) w.s[3] = ldb<24>(p.v, o.c, p.so);
     return w;
 }
-template <int ROLE, int ARITH>
+template <int ROLE, int ARITH, bool SPLIT = false>
 __device__ __forceinline__ double y_flux(const DGrid &g, const PlaneCtx &p, const Win6 &qy, const Win6 &aux, int i, int j, int k) {
     const bool bx = g.tx != 0, by = g.ty != 0, bz = g.tz != 0;
     if (ROLE == ROLE_U) {
         const double vt = sym4<ARITH>(aux, p.ayk, bx, i, false, g.Nx);                      // advective_momentum_flux_Vu :31-37
         return vt * bias6<ARITH>(qy, vt > 0, by, j, false, g.Ny);
     } else if (ROLE == ROLE_V) {
-        const double vt = sym4<ARITH>(qy, p.ayk, by, j - 1, true, g.Ny);                    // Vv :55-61
+        const double vt = sym4<ARITH>(SPLIT ? aux : qy, p.ayk, by, j - 1, true, g.Ny);                    // Vv :55-61
         return vt * bias6<ARITH>(qy, vt > 0, by, j - 1, true, g.Ny);
     } else if (ROLE == ROLE_W) {
         const double vt = sym4z(aux, p.ayz, bz, k, false, g.Nz);                     // Vw :79-85
@@ -233,7 +238,14 @@ __device__ __forceinline__ void role_barrier() {
 // operations of the plane, right behind the loads of the y-window, so that no wait of this plane includes them: they have the
 // arithmetic of the y-flux, the barrier and the first loads of the next plane to complete. The new element of the z-window
 // arrives one plane ahead of its use (qn), the previous tendency of the cell closed in the next plane likewise (gmn).
-template <int ROLE, int TY, bool SUB, bool BZ, int ARITH, bool FORCE, typename Args>
+// the advecting velocity component c of a launch: the prognostic fields themselves, or -- SPLIT -- the arrays RoleSplitArgs::A names
+template <bool SPLIT, typename Args> __device__ __forceinline__ const double *role_advecting(const Args &a, int c) {
+    if constexpr (SPLIT) return a.A[c]; else return a.U[c];
+}
+
+// SPLIT: advecting (a.A) and advected (a.U[fidx]) arrays differ. ACC: the tendency array already holds earlier terms, G = G - div (the
+// previous value of a cell arrives through the stream the fused substep uses for G⁻, one plane ahead of its use).
+template <int ROLE, int TY, bool SUB, bool BZ, int ARITH, bool FORCE, typename Args, bool SPLIT = false, bool ACC = false>
 __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const int fidx, const int i0, const int j0, const int kc0,
                                            const int kc1, double (*FX)[TY][66], double (*FY)[TY + 1][64]) {
     // Bounded z: only the planes within reach of a wall need the fallback logic of the scheme (every z-stencil test of
@@ -266,8 +278,9 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
     const long pb = max(0L, (long)(kc0 - 1 + Hz) - 3);
     const long sh = pb * (long)a.s2;
     PlaneCtx p;
-    p.u = make_rsrc(a.U[0] + sh); p.v = make_rsrc(a.U[1] + sh); p.w = make_rsrc(a.U[2] + sh);
-    p.q = ROLE == ROLE_U ? p.u : (ROLE == ROLE_V ? p.v : (ROLE == ROLE_W ? p.w : make_rsrc(a.U[fidx] + sh)));
+    p.u = make_rsrc(role_advecting<SPLIT>(a, 0) + sh); p.v = make_rsrc(role_advecting<SPLIT>(a, 1) + sh); p.w = make_rsrc(role_advecting<SPLIT>(a, 2) + sh);
+    p.q = SPLIT ? make_rsrc(a.U[fidx] + sh)
+                : (ROLE == ROLE_U ? p.u : (ROLE == ROLE_V ? p.v : (ROLE == ROLE_W ? p.w : make_rsrc(a.U[fidx] + sh))));
     p.s2 = s2;
     p.so = s2 * (unsigned)((long)(kc0 - 1 + Hz) - pb);   // plane of level kc0
     // the streams touched once per cell: tendency out, previous tendency in (a.Gm is the tendency array itself when the substep has
@@ -287,7 +300,7 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
         for (int n = 0; n < 5; ++n) qz.s[n + 1] = ldb<24>(p.q, o.c, p.so + (unsigned)(n - 3) * s2);   // levels kc0-3 .. kc0+1
         qn = ldb<24>(p.q, o.c, p.so + 2u * s2);                                                        // level kc0+2
         if (OCN_ROLE_PF == 2) qnn = ldb<24>(p.q, o.c, p.so + 3u * s2);                                 // level kc0+3 (inside the halo)
-        if (SUB && OCN_ROLE_PF == 2 && !edge) gmnn = ldb_once<24>(rGm, o.c | cell_off, p.so);          // level kc0: closed in plane kc0+1
+        if ((SUB || ACC) && OCN_ROLE_PF == 2 && !edge) gmnn = ldb_once<24>(rGm, o.c | cell_off, p.so);          // level kc0: closed in plane kc0+1
     }
 
     // The edge wave and the row waves run SEPARATE loops over the same planes (one barrier per plane in each): loop-carried values
@@ -303,14 +316,14 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
             auto edge_plane = [&](const DGrid &gg) {
                 if (edge_y && !(OCN_ROLE_ABLATE & 32)) {
                     const Win6 qy = ywin6<false>(p.q, p.so, o, 0.0);
-                    const Win6 aux = ROLE == ROLE_W ? zwin4(p.v, p.so, o, s2) : load_yaux<ROLE>(p, o);
-                    FY[buf][TY][lane] = y_flux<ROLE, ARITH>(gg, p, qy, aux, i, j, k);
+                    const Win6 aux = ROLE == ROLE_W ? zwin4(p.v, p.so, o, s2) : load_yaux<ROLE, SPLIT>(p, o);
+                    FY[buf][TY][lane] = y_flux<ROLE, ARITH, SPLIT>(gg, p, qy, aux, i, j, k);
                 }
                 if (edge_x && !(OCN_ROLE_ABLATE & 32)) {
                     asm volatile("" : "+v"(e.c));
                     const Win6 qxe = xwin6<false>(p.q, p.so, e, 0.0);
-                    const Win6 aux = ROLE == ROLE_W ? zwin4(p.u, p.so, e, s2) : load_xaux<ROLE>(p, e);
-                    FX[buf][lane][64] = x_flux<ROLE, ARITH>(gg, p, qxe, aux, ie, je, k);
+                    const Win6 aux = ROLE == ROLE_W ? zwin4(p.u, p.so, e, s2) : load_xaux<ROLE, SPLIT>(p, e);
+                    FX[buf][lane][64] = x_flux<ROLE, ARITH, SPLIT>(gg, p, qxe, aux, ie, je, k);
                 }
             };
             if (ROLE == ROLE_W && near_wall(k)) edge_plane(gB); else edge_plane(gP);     // only role w interpolates along z here
@@ -341,19 +354,19 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
         for (int n = 0; n < 5; ++n) vmov(qz.s[n], qz.s[n + 1]);
         vmov(qz.s[5], qn);
         if (OCN_ROLE_PF == 2) vmov(qn, qnn);
-        if (SUB) vmov(gm, gmn);
-        if (SUB && OCN_ROLE_PF == 2) vmov(gmn, gmnn);
-        zin = load_zin<ROLE>(p, p.so, o);
+        if (SUB || ACC) vmov(gm, gmn);
+        if ((SUB || ACC) && OCN_ROLE_PF == 2) vmov(gmn, gmnn);
+        zin = load_zin<ROLE, SPLIT>(p, p.so, o);
     };
     auto z_compute = [&](const DGrid &gg, const int k, const int buf, const long pk) {
-        const double fz = z_flux<ROLE, ARITH>(gg, zin, i, j, k, qz);
+        const double fz = z_flux<ROLE, ARITH, SPLIT>(gg, zin, i, j, k, qz);
         const int pb = buf ^ 1;
         const long pkm = pk - 1;
         const double vinv = ROLE == ROLE_W ? ktab(g.vinv_f)[pkm] : ktab(g.vinv_c)[pkm];
         const double dx = FX[pb][row0][lane + 1] - FX[pb][row0][lane];
         const double dy = FY[pb][row0 + 1][lane] - FY[pb][row0][lane];
         const double div = vinv * ((dx + dy) + (fz - fz_prev));
-        Gn = -div + 0.0;
+        Gn = ACC ? gm - div : -div + 0.0;
         if (FORCE) {
             // G = G_rest + F (ocn_forcing.h) on the cell just closed, (i, j, k - 1); φ = its value, already in the z-window. Lanes outside
             // the range (their stores are dropped) evaluate a clamped in-range cell, so no table or array is read out of bounds.
@@ -388,21 +401,23 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
         Win6 qx, xaux, qy, yaux;
         auto x_loads = [&]() {
             qx = (OCN_ROLE_ABLATE & 8) ? qz : xwin6<true>(p.q, p.so, o, qz.s[3]);
-            xaux = ROLE == ROLE_W ? zwin4(p.u, p.so, o, s2) : load_xaux<ROLE>(p, o);
+            xaux = ROLE == ROLE_W ? zwin4(p.u, p.so, o, s2) : load_xaux<ROLE, SPLIT>(p, o);
         };
         auto y_loads = [&]() {
             qy = (OCN_ROLE_ABLATE & 8) ? qz : ywin6<true>(p.q, p.so, o, qz.s[3]);
-            yaux = ROLE == ROLE_W ? zwin4(p.v, p.so, o, s2) : load_yaux<ROLE>(p, o);
+            yaux = ROLE == ROLE_W ? zwin4(p.v, p.so, o, s2) : load_yaux<ROLE, SPLIT>(p, o);
         };
         auto prefetches = [&]() {
             if (OCN_ROLE_PF == 2) {
                 // level k + 4 exists only while k + 1 <= kc1 can still use it (k + 4 <= Nz + Hz); the last plane re-reads level k + 3
                 qnn = ldb<24>(p.q, o.c, (OCN_ROLE_ABLATE & 1) ? p.so : p.so + (k < kc1 ? 4u : 3u) * s2);
-                if (SUB && !(OCN_ROLE_ABLATE & 2)) gmnn = ldb_once<24>(rGm, o.c | cell_off, p.so + s2);   // level k + 1: closed in plane k + 2
+                // (ACC: in the last plane of a chunk this reads level kc1 + 1 of the tendency while the neighbouring chunk's workgroup may
+                // be storing it -- the value is never consumed, the peeled plane closes level kc1 with the one loaded a plane earlier)
+                if ((SUB || ACC) && !(OCN_ROLE_ABLATE & 2)) gmnn = ldb_once<24>(rGm, o.c | cell_off, p.so + s2);   // level k + 1: closed in plane k + 2
                 return;
             }
             qn = ldb<24>(p.q, o.c, (OCN_ROLE_ABLATE & 1) ? p.so : p.so + 3u * s2);
-            if (SUB && !(OCN_ROLE_ABLATE & 2)) gmn = ldb_once<24>(rGm, o.c | cell_off, p.so);          // level k: closed in plane k + 1
+            if ((SUB || ACC) && !(OCN_ROLE_ABLATE & 2)) gmn = ldb_once<24>(rGm, o.c | cell_off, p.so);          // level k: closed in plane k + 1
         };
         auto plane = [&](const DGrid &gg) {
             __builtin_amdgcn_sched_barrier(0);
@@ -411,12 +426,12 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
             x_loads();
             stores();
             __builtin_amdgcn_sched_barrier(0);
-            FX[buf][row0][lane] = x_flux<ROLE, ARITH>(gg, p, qx, xaux, i, j, k);
+            FX[buf][row0][lane] = x_flux<ROLE, ARITH, SPLIT>(gg, p, qx, xaux, i, j, k);
             __builtin_amdgcn_sched_barrier(0);
             y_loads();
             prefetches();
             __builtin_amdgcn_sched_barrier(0);
-            FY[buf][row0][lane] = y_flux<ROLE, ARITH>(gg, p, qy, yaux, i, j, k);
+            FY[buf][row0][lane] = y_flux<ROLE, ARITH, SPLIT>(gg, p, qy, yaux, i, j, k);
         };
         if (near_wall(k)) plane(gB); else plane(gP);
         p.so += s2;

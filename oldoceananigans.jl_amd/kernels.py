@@ -34,6 +34,19 @@ def compute_tendencies(grid, u, v, w, tracers, Gu, Gv, Gw, Gc, kernel_parameters
                                                  Gw.data, gc, _range(kernel_parameters)))
 
 
+def compute_advective_tendency(grid, ua, va, wa, psi, which, G, kernel_parameters=None, accumulate=False):
+    """G = -div(advection, (ua, va, wa), psi), or G = G - div(...) with `accumulate`: one advection term with the advecting velocities apart
+    from the advected field (a model with background_fields evaluates two per field); which: "u" | "v" | "w" | "c" -- psi and G at that
+    field's location"""
+    _lib.check(_lib.lib().ocn_compute_advective_tendency(grid.handle, ua.data, va.data, wa.data, psi.data, "uvwc".index(which), G.data,
+                                                         _range(kernel_parameters), int(accumulate)))
+
+
+def sum_parent(grid, a, b, out):
+    """out = a + b over the whole parent array (the total velocities u + Ū of a model with background fields)"""
+    _lib.check(_lib.lib().ocn_sum_parent(grid.handle, a.data, b.data, _lib.i3(out.loc_codes), out.data))
+
+
 def compute_tendencies_and_substep(grid, fields, Gn, next_fields, Gm, Δt, γ, ζ, kernel_parameters=None):
     """tendencies of all prognostic fields (u, v, w, tracers...) + the rk3_substep! of the next stage into `next_fields`"""
     _lib.check(_lib.lib().ocn_compute_tendencies_and_substep(

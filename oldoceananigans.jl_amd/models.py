@@ -36,11 +36,12 @@ class Clock:
 
 class NonhydrostaticModel:
     """NonhydrostaticModel(; grid, advection=WENO(), tracers=(:T, :S), timestepper=:RungeKutta3, coriolis, buoyancy, closure, forcing,
-    boundary_conditions); BASELINE.json benchmarks the configuration with all of them = nothing. `forcing` takes the closure-free
-    forcings of forcings.py (Relaxation, Forcing(array), MultipleForcings / tuples)."""
+    boundary_conditions, background_fields); BASELINE.json benchmarks the configuration with all of them = nothing. `forcing` takes the
+    closure-free forcings of forcings.py (Relaxation, Forcing(array), MultipleForcings / tuples); `background_fields` a dict or a
+    BackgroundFields of time-independent backgrounds (background_fields.py)."""
 
     def __init__(self, grid, advection=None, tracers=("T", "S"), timestepper="RungeKutta3", buoyancy=None, coriolis=None,
-                 closure=None, forcing=None, boundary_conditions=None):
+                 closure=None, forcing=None, boundary_conditions=None, background_fields=None):
         if advection is None:
             advection = WENO()
         if not (isinstance(advection, WENO) and advection.order == 5 and advection.bounds is None):
@@ -86,6 +87,12 @@ class NonhydrostaticModel:
         locations.update({t: (Center, Center, Center) for t in self.tracer_names})
         self._forcing_terms = _forcings.model_forcing(getattr(grid, "local", grid), locations, forcing)
         self.forcing = dict(forcing or {})
+        # background_fields = (u = U, b = B) (nonhydrostatic_model.jl:196-197): regularised on the host for the same reason
+        from . import background_fields as _background
+        self.background_fields = _background.regularize_background_fields(background_fields, self.tracer_names, grid, 0.0)
+        self._has_background = self.background_fields is not None
+        if not self._has_background:                     # BackgroundFields of ZeroFields: every entry None
+            self.background_fields = _background.empty_background_fields(self.tracer_names)
         self.handle = self._create_handle(grid, len(self.tracer_names))
         self.clock = Clock(self)
         V = namedtuple("Velocities", "u v w")
@@ -133,6 +140,8 @@ class NonhydrostaticModel:
             _lib.check(_lib.lib().ocn_model_set_closure(self.handle, closure.ν, kp))
             if is_vertically_implicit(closure):
                 _lib.check(_lib.lib().ocn_model_set_vertically_implicit(self.handle, 1))
+        if self._has_background:
+            _background.upload(self, self.background_fields)                  # borrowed by the library: the Fields are kept here
         self._forcing_keep = []                          # device arrays of Forcing(array): owned (numpy) or borrowed (Field)
         for name, terms in self._forcing_terms.items():
             _forcings.set_forcing(self.handle, ("u", "v", "w").index(name) if name in ("u", "v", "w") else 3 + self.tracer_names.index(name),
