@@ -163,6 +163,24 @@ int ocn_add_hydrostatic_pressure_gradient(ocn_grid_t grid, const double *pHY, do
  * y_f_cross_U = f active_weighted_ℑxyᶜᶠᶜ(u) (Operators/interpolation_operators.jl:116-130), on tendencies holding the advective part */
 int ocn_add_fplane_coriolis(ocn_grid_t grid, double f, const double *u, const double *v, double *Gu, double *Gv, const int *range);
 
+/* coriolis = ConstantCartesianCoriolis(fx, fy, fz) (Coriolis/constant_cartesian_coriolis.jl:70-81): G_u -= x_f_cross_U = ℑxᶠᵃᵃ(fy ℑzᵃᵃᶜ(w) -
+ * fz ℑyᵃᶜᵃ(v)), G_v -= y_f_cross_U = ℑyᵃᶠᵃ(fz ℑxᶜᵃᵃ(u) - fx ℑzᵃᵃᶜ(w)), G_w -= z_f_cross_U = ℑzᵃᵃᶠ(fx ℑyᵃᶜᵃ(v) - fy ℑxᶜᵃᵃ(u)): plain
+ * two-point averages, the identity along a Flat direction (Operators/interpolation_operators.jl:87-112), on tendencies holding the
+ * advective part (nonhydrostatic_tendency_kernel_functions.jl:96,158,223). range as in ocn_add_fplane_coriolis: the cells whose tendencies
+ * are updated, within the interior; NULL = every cell of each field, the wall faces excluded. u, v, w with filled halos. */
+int ocn_add_cartesian_coriolis(ocn_grid_t grid, double fx, double fy, double fz, const double *u, const double *v, const double *w,
+                               double *Gu, double *Gv, double *Gw, const int *range);
+
+/* buoyancy = BuoyancyForce(formulation; gravity_unit_vector) (BuoyancyFormulations/buoyancy_force.jl:47-54): with ĝ = -gravity_unit_vector,
+ * G_u += x_dot_g_bᶠᶜᶜ = ghat_x ℑxᶠᵃᵃ(b), G_v += y_dot_g_bᶜᶠᶜ = ghat_y ℑyᵃᶠᵃ(b) (g_dot_b.jl:2-3; nonhydrostatic_tendency_kernel_functions.jl:
+ * 95,157), b the buoyancy perturbation of `kind` as in ocn_update_hydrostatic_pressure (bT, S with filled halos); range as above. */
+int ocn_add_buoyancy_acceleration(ocn_grid_t grid, int kind, const double *bT, const double *S, double g, double alpha, double beta,
+                                  double ghat_x, double ghat_y, double *Gu, double *Gv, const int *range);
+/* _update_hydrostatic_pressure! (update_hydrostatic_pressure.jl:12-22) with z_dot_g_bᶜᶜᶠ = ghat_z ℑzᵃᵃᶠ(b) (g_dot_b.jl:4): ghat_z = 1 gives
+ * the bits of ocn_update_hydrostatic_pressure */
+int ocn_update_hydrostatic_pressure_tilted(ocn_grid_t grid, int kind, const double *bT, const double *S, double g, double alpha, double beta,
+                                           double ghat_z, double *pHY);
+
 /* closure = ScalarDiffusivity(ν, κ): isotropic, constant, explicit (SURVEY.md 8f.1 -- the first "next" row).
  * ∂ⱼ_τ₁ⱼ / ∂ⱼ_τ₂ⱼ / ∂ⱼ_τ₃ⱼ / ∇_dot_qᶜ (TurbulenceClosures/closure_kernel_operators.jl:22-48) with viscous_flux_* = -2 ν Σᵢⱼ and
  * diffusive_flux_* = -κ ∂c (abstract_scalar_diffusivity_closure.jl:194-242). ADDS the closure term to tendencies that already
@@ -393,6 +411,18 @@ int ocn_model_get_option(ocn_model_t model, const char *key, int *value);
 int ocn_model_set_buoyancy(ocn_model_t model, int kind, int b_or_T_index, int S_index, double g, double alpha, double beta);
 /* coriolis = FPlane(f = f) of the model constructor; enabled = 0: coriolis = nothing */
 int ocn_model_set_coriolis(ocn_model_t model, int enabled, double f);
+/* coriolis = ConstantCartesianCoriolis(fx, fy, fz) of the model constructor (constant_cartesian_coriolis.jl:32-66); enabled = 0: coriolis =
+ * nothing. The model has ONE Coriolis: this and ocn_model_set_coriolis replace one another. The w tendency then has a Coriolis term too
+ * (nonhydrostatic_tendency_kernel_functions.jl:223). OCN_ENOTSUP on a partitioned model. ocn_model_get_option answers "coriolis_kind":
+ * 0 nothing, 1 FPlane, 2 ConstantCartesianCoriolis. */
+int ocn_model_set_cartesian_coriolis(ocn_model_t model, int enabled, double fx, double fy, double fz);
+/* buoyancy = BuoyancyForce(formulation; gravity_unit_vector = (gx, gy, gz)) (buoyancy_force.jl:47-54) for the formulation
+ * ocn_model_set_buoyancy names; enabled = 0: NegativeZDirection(). The u and v tendencies gain x_dot_g_b, y_dot_g_b and the hydrostatic
+ * pressure anomaly integrates ĝ_z ℑzᵃᵃᶠ(b) (g_dot_b.jl:2-4). OCN_EINVAL unless the components are finite and gx² + gy² + gz² ≈ 1
+ * (validate_unit_vector, Grids/input_validation.jl:177-186: isapprox, rtol = √eps); OCN_ENOTSUP on a partitioned model.
+ * ocn_model_get_option answers "tilted_gravity" (1 with a buoyancy and a gravity_unit_vector). Models with either of these two take the
+ * per-value tendency epilogue: "epilogue_march_active" answers 0. */
+int ocn_model_set_gravity_unit_vector(ocn_model_t model, int enabled, double gx, double gy, double gz);
 /* closure = ScalarDiffusivity(ν = nu, κ = kappa[tracer]) of the model constructor; all zeros / NULL: closure = nothing */
 int ocn_model_set_closure(ocn_model_t model, double nu, const double *kappa);
 /* time discretisation of the model's ScalarDiffusivity (scalar_diffusivity.jl:116-141): enabled = 1 is

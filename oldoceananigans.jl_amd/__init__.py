@@ -10,15 +10,15 @@ from .architectures import GPU, architecture, ndevices, own_stream, set_option, 
 from .boundary_conditions import (BoundaryCondition, FieldBoundaryConditions, FluxBoundaryCondition,
                                   GradientBoundaryCondition, LinearFieldFlux, OpenBoundaryCondition, ValueBoundaryCondition, compute_flux_bcs)
 from .background_fields import BackgroundField, BackgroundFields
-from .buoyancy import BuoyancyTracer, FPlane, LinearEquationOfState, SeawaterBuoyancy
+from .buoyancy import BuoyancyForce, BuoyancyTracer, ConstantCartesianCoriolis, FPlane, LinearEquationOfState, SeawaterBuoyancy
 from .checkpointer import set_from_checkpoint, write_checkpoint
 from .closures import (AnisotropicMinimumDissipation, DynamicCoefficient, ExplicitTimeDiscretization, ScalarDiffusivity, Smagorinsky,
                        SmagorinskyLilly, VerticalScalarDiffusivity, VerticallyImplicitTimeDiscretization)
 from .forcings import (AdvectiveForcing, ContinuousForcing, DiscreteForcing, Forcing, GaussianMask, LinearTarget, MultipleForcings,
                        PiecewiseLinearMask, Relaxation)
 from .fields import (CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions, interior, set_)
-from .grids import (Bounded, Center, Face, Flat, FullyConnected, LeftConnected, Periodic, RectilinearGrid, RightConnected,
-                    with_halo)
+from .grids import (Bounded, Center, Face, Flat, FullyConnected, LeftConnected, NegativeZDirection, Periodic, RectilinearGrid, RightConnected,
+                    ZDirection, validate_unit_vector, with_halo)
 from .models import NonhydrostaticModel, max_abs_divergence, set_model, time_step, update_state
 from .solvers import (FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver, batched_tridiagonal_solve_z, solve,
                       solve_for_pressure)

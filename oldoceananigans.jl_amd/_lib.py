@@ -135,6 +135,11 @@ SYMBOLS = {
     "ocn_model_set_buoyancy": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]),
     "ocn_add_fplane_coriolis": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp, _ip]),
     "ocn_model_set_coriolis": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "ocn_add_cartesian_coriolis": (C.c_int, [_vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _ip]),
+    "ocn_add_buoyancy_acceleration": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _ip]),
+    "ocn_update_hydrostatic_pressure_tilted": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
+    "ocn_model_set_cartesian_coriolis": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "ocn_model_set_gravity_unit_vector": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double]),
     "ocn_cell_advection_timescale": (C.c_int, [_vp, _vp, _vp, _vp, _dp]),
     "ocn_model_cell_advection_timescale": (C.c_int, [_vp, _dp]),
     "ocn_model_get_option": (C.c_int, [_vp, C.c_char_p, _ip]),

@@ -1,4 +1,7 @@
-"""Buoyancy formulations on the accelerated path, gravity along -z (reference: src/BuoyancyFormulations/)."""
+"""Buoyancy formulations and constant Coriolis terms on the accelerated path (reference: src/BuoyancyFormulations/,
+src/Coriolis/): BuoyancyTracer and linear SeawaterBuoyancy, with gravity along -z or, wrapped in a BuoyancyForce, along any unit vector;
+FPlane and ConstantCartesianCoriolis."""
+from .grids import NegativeZDirection, ZDirection, validate_unit_vector
 
 
 class BuoyancyTracer:
@@ -60,6 +63,76 @@ def sind(x):
         total += term
         n += 1
     return float(total) * sign
+
+
+def cosd(x):
+    """cos of an angle in degrees as Julia's `cosd` returns it: sind of the complementary angle, formed exactly"""
+    from fractions import Fraction
+    return sind(Fraction(90) - Fraction(float(x)))
+
+
+def _prettysummary(x):
+    """prettysummary(::AbstractFloat) (Grids/grid_utils.jl:282): the shortest representation, at most 6 significant digits"""
+    return repr(float("%.6g" % x))
+
+
+class BuoyancyForce:
+    """BuoyancyForce(formulation; gravity_unit_vector = NegativeZDirection()) (buoyancy_force.jl:4-50): the buoyancy acceleration acts in
+    the direction opposite to gravity; ĝ = -gravity_unit_vector (:52-54)"""
+
+    def __init__(self, formulation, gravity_unit_vector=None):
+        if isinstance(formulation, BuoyancyForce):
+            raise ValueError("the formulation of a BuoyancyForce is a buoyancy formulation, not another BuoyancyForce")
+        self.formulation = formulation
+        self.gravity_unit_vector = validate_unit_vector(NegativeZDirection() if gravity_unit_vector is None else gravity_unit_vector)
+
+    @property
+    def required_tracers(self):
+        return self.formulation.required_tracers
+
+    @property
+    def tilted(self):
+        """whether gravity is a vector rather than NegativeZDirection()"""
+        return not isinstance(self.gravity_unit_vector, NegativeZDirection)
+
+    def summary(self):
+        """Base.summary (buoyancy_force.jl:77-85)"""
+        g = self.gravity_unit_vector
+        vec = "(" + ", ".join(_prettysummary(c) for c in g) + ")" if self.tilted else "NegativeZDirection()"
+        return f"{type(self.formulation).__name__} with ĝ = {vec}"
+
+    def __repr__(self):
+        return self.summary()
+
+
+class ConstantCartesianCoriolis:
+    """ConstantCartesianCoriolis(fx, fy, fz) | (f, rotation_axis = ZDirection()) | (latitude, rotation_rate): a constant rotation vector
+    with all three components (Coriolis/constant_cartesian_coriolis.jl:32-66); the reference's ArgumentErrors are ValueErrors"""
+
+    def __init__(self, fx=None, fy=None, fz=None, f=None, rotation_axis=None, latitude=None, rotation_rate=7.292115e-5):
+        rotation_axis = ZDirection() if rotation_axis is None else rotation_axis
+        if latitude is not None:
+            if not all(c is None for c in (fx, fy, fz, f)):
+                raise ValueError("Only `rotation_rate` can be specified when using `latitude`.")
+            fx, fy, fz = 0, 2 * rotation_rate * cosd(latitude), 2 * rotation_rate * sind(latitude)
+        elif f is not None:
+            if not all(c is None for c in (fx, fy, fz, latitude)):
+                raise ValueError("Only `rotation_axis` can be specified when using `f`.")
+            rotation_axis = validate_unit_vector(rotation_axis)
+            if isinstance(rotation_axis, ZDirection):
+                fx, fy, fz = 0, 0, f
+            elif isinstance(rotation_axis, NegativeZDirection):
+                raise ValueError("rotation_axis must be ZDirection() or a unit vector")
+            else:
+                fx, fy, fz = f * rotation_axis[0], f * rotation_axis[1], f * rotation_axis[2]
+        elif all(c is not None for c in (fx, fy, fz)):
+            pass                                                 # (latitude and f are nothing here)
+        else:
+            raise ValueError("Either (i) `latitude`, or (ii) `f`, or (iii) `fx`, `fy` and `fz` must be specified.")
+        self.fx, self.fy, self.fz = float(fx), float(fy), float(fz)
+
+    def __repr__(self):
+        return "ConstantCartesianCoriolis{Float64}: " + "fx = %.2e, fy = %.2e, fz = %.2e" % (self.fx, self.fy, self.fz)
 
 
 class FPlane:

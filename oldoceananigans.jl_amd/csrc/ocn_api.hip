@@ -11,6 +11,7 @@
 #include "ocn_forcing.h"
 #include "ocn_implicit_z.h"
 #include <hipfft/hipfft.h>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -707,13 +708,20 @@ extern "C" int ocn_sum_parent(ocn_grid_t grid, const double *a, const double *b,
 }
 
 static int update_hydrostatic_pressure(const DGrid &g, int kind, const double *bT, const double *S, double grav, double alpha, double beta,
-                                       double *pHY) {
+                                       double *pHY, bool tilted = false, double ghat_z = 1.0) {
     if (g.tz == OCN_FLAT) return OCN_OK;                   // update_hydrostatic_pressure!(::ZFlatGrid) = nothing
     const int i0 = g.tx == OCN_FLAT ? 1 : 0, i1 = g.tx == OCN_FLAT ? g.Nx : g.Nx + 1;
     const int j0 = g.ty == OCN_FLAT ? 1 : 0, j1 = g.ty == OCN_FLAT ? g.Ny : g.Ny + 1;
     const BuoyancyArgs B{kind, bT, S, grav, alpha, beta};
     const dim3 blk(64, 4, 1);
     const dim3 grd((i1 - i0 + 64) / 64, (j1 - j0 + 4) / 4);
+    if (tilted) {
+        TiltedBuoyancyArgs Bt;
+        static_cast<BuoyancyArgs &>(Bt) = B;
+        Bt.ghat_z = ghat_z;
+        if (kind == 1) hipLaunchKernelGGL((hydrostatic_pressure_kernel<1, true>), grd, blk, 0, g_stream, g, make_view(g, bT, LOC_C), Bt, pHY, i0, i1, j0, j1);
+        else           hipLaunchKernelGGL((hydrostatic_pressure_kernel<2, true>), grd, blk, 0, g_stream, g, make_view(g, bT, LOC_C), Bt, pHY, i0, i1, j0, j1);
+    } else
     if (kind == 1) hipLaunchKernelGGL(hydrostatic_pressure_kernel<1>, grd, blk, 0, g_stream, g, make_view(g, bT, LOC_C), B, pHY, i0, i1, j0, j1);
     else           hipLaunchKernelGGL(hydrostatic_pressure_kernel<2>, grd, blk, 0, g_stream, g, make_view(g, bT, LOC_C), B, pHY, i0, i1, j0, j1);
     KERNEL_CHECK();
@@ -737,6 +745,13 @@ extern "C" int ocn_update_hydrostatic_pressure(ocn_grid_t grid, int kind, const 
     return update_hydrostatic_pressure(grid->d, kind, bT, S, grav, alpha, beta, pHY);
 }
 
+extern "C" int ocn_update_hydrostatic_pressure_tilted(ocn_grid_t grid, int kind, const double *bT, const double *S, double grav, double alpha,
+                                                      double beta, double ghat_z, double *pHY) {
+    NEED_INIT();
+    if (!grid || !bT || !pHY || (kind != 1 && kind != 2) || (kind == 2 && !S)) return fail(OCN_EINVAL, "invalid argument");
+    return update_hydrostatic_pressure(grid->d, kind, bT, S, grav, alpha, beta, pHY, true, ghat_z);
+}
+
 extern "C" int ocn_add_hydrostatic_pressure_gradient(ocn_grid_t grid, const double *pHY, double *Gu, double *Gv, const int *range) {
     NEED_INIT();
     if (!grid || !pHY || !Gu || !Gv) return fail(OCN_EINVAL, "NULL argument");
@@ -757,6 +772,51 @@ extern "C" int ocn_add_fplane_coriolis(ocn_grid_t grid, double f, const double *
     NEED_INIT();
     if (!grid || !u || !v || !Gu || !Gv) return fail(OCN_EINVAL, "NULL argument");
     return add_fplane_coriolis(grid->d, f, u, v, Gu, Gv, range);
+}
+
+// coriolis = ConstantCartesianCoriolis(fx, fy, fz): G_u -= x_f_cross_U, G_v -= y_f_cross_U, G_w -= z_f_cross_U (cartesian_coriolis_kernel)
+static int add_cartesian_coriolis(const DGrid &g, double fx, double fy, double fz, const double *u, const double *v, const double *w, double *Gu,
+                                  double *Gv, double *Gw, const int *range) {
+    Range6 ru, rv, rw;
+    int rc;
+    if ((rc = check_range(g, range, &ru, LOC_U, true)) || (rc = check_range(g, range, &rv, LOC_V, true)) || (rc = check_range(g, range, &rw, LOC_W, true)))
+        return rc;
+    hipLaunchKernelGGL(cartesian_coriolis_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, fx, fy, fz, make_view(g, u, LOC_U),
+                       make_view(g, v, LOC_V), make_view(g, w, LOC_W), make_view(g, Gu, LOC_U), make_view(g, Gv, LOC_V), make_view(g, Gw, LOC_W),
+                       ru, rv, rw);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+extern "C" int ocn_add_cartesian_coriolis(ocn_grid_t grid, double fx, double fy, double fz, const double *u, const double *v, const double *w,
+                                          double *Gu, double *Gv, double *Gw, const int *range) {
+    NEED_INIT();
+    if (!grid || !u || !v || !w || !Gu || !Gv || !Gw) return fail(OCN_EINVAL, "NULL argument");
+    return add_cartesian_coriolis(grid->d, fx, fy, fz, u, v, w, Gu, Gv, Gw, range);
+}
+
+// buoyancy = BuoyancyForce(formulation; gravity_unit_vector): G_u += x_dot_g_b, G_v += y_dot_g_b (buoyancy_acceleration_kernel)
+static int add_buoyancy_acceleration(const DGrid &g, int kind, const double *bT, const double *S, double grav, double alpha, double beta,
+                                     double ghat_x, double ghat_y, double *Gu, double *Gv, const int *range) {
+    Range6 ru, rv;
+    int rc;
+    if ((rc = check_range(g, range, &ru, LOC_U, true)) || (rc = check_range(g, range, &rv, LOC_V, true))) return rc;
+    const BuoyancyArgs B{kind, bT, S, grav, alpha, beta};
+    if (kind == 1)
+        hipLaunchKernelGGL(buoyancy_acceleration_kernel<1>, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, bT, LOC_C), B, ghat_x,
+                           ghat_y, make_view(g, Gu, LOC_U), make_view(g, Gv, LOC_V), ru, rv);
+    else
+        hipLaunchKernelGGL(buoyancy_acceleration_kernel<2>, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, bT, LOC_C), B, ghat_x,
+                           ghat_y, make_view(g, Gu, LOC_U), make_view(g, Gv, LOC_V), ru, rv);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+extern "C" int ocn_add_buoyancy_acceleration(ocn_grid_t grid, int kind, const double *bT, const double *S, double grav, double alpha, double beta,
+                                             double ghat_x, double ghat_y, double *Gu, double *Gv, const int *range) {
+    NEED_INIT();
+    if (!grid || !bT || !Gu || !Gv || (kind != 1 && kind != 2) || (kind == 2 && !S)) return fail(OCN_EINVAL, "invalid argument");
+    return add_buoyancy_acceleration(grid->d, kind, bT, S, grav, alpha, beta, ghat_x, ghat_y, Gu, Gv, range);
 }
 
 static int closure_tendencies(const DGrid &g, const double *u, const double *v, const double *w, const double *const *tr, int ntr,
@@ -2589,6 +2649,10 @@ struct ocn_model_s {
     double *forcing_tables[OCN_MAX_FIELDS][OCN_MAX_FORCING_TERMS][2] = {};
     bool has_coriolis = false;              // coriolis = FPlane(f)
     double fcor = 0.0;
+    bool has_cartesian = false;             // coriolis = ConstantCartesianCoriolis(fx, fy, fz): replaces FPlane and is replaced by it
+    double cfx = 0.0, cfy = 0.0, cfz = 0.0;
+    bool tilted = false;                    // buoyancy = BuoyancyForce(formulation; gravity_unit_vector): ĝ = -gravity_unit_vector
+    double ghat[3] = {0.0, 0.0, 1.0};
     int buoyancy_kind = 0, bT_index = 0, S_index = 0;    // 0 nothing, 1 BuoyancyTracer, 2 linear SeawaterBuoyancy
     double grav = 0.0, alpha = 0.0, beta = 0.0;
     double *pHY = nullptr;                  // hydrostatic pressure anomaly (only with buoyancy)
@@ -2842,7 +2906,7 @@ extern "C" int ocn_model_set_option(ocn_model_t m, const char *key, int value) {
     return OCN_OK;
 }
 
-static bool has_physics(const ocn_model_s *m) { return m->has_coriolis || m->buoyancy_kind != 0 || m->has_closure || m->has_amd || m->has_smag; }
+static bool has_physics(const ocn_model_s *m) { return m->has_coriolis || m->has_cartesian || m->buoyancy_kind != 0 || m->has_closure || m->has_amd || m->has_smag; }
 
 // the form of the vertically implicit solve a model runs (ocn_implicit_z.h): the reference-shaped one, the only one shipped
 static int model_ivd_form(const ocn_model_s *) { return 0; }
@@ -2908,10 +2972,13 @@ static int add_forcing(ocn_model_s *m) {
 }
 
 // whether the closure terms take the z-marching epilogue (ocn_epilogue_march.h): a grid without Flat directions, at most two tracers, and
-// not the explicit part of a vertically implicit discretisation -- that variant exists in the per-value epilogue only
+// not the explicit part of a vertically implicit discretisation -- that variant exists in the per-value epilogue only, as do the terms of a
+// ConstantCartesianCoriolis and of a buoyancy with a gravity_unit_vector
+static bool tilted_buoyancy(const ocn_model_s *m) { return m->tilted && m->buoyancy_kind != 0; }
 static bool epilogue_march_selected(const ocn_model_s *m) {
     const DGrid &g = m->grid->d;
     const bool clo = m->has_smag || m->has_amd || m->has_closure;
+    if (m->has_cartesian || tilted_buoyancy(m)) return false;
     return m->opt.epilogue_march && clo && !(m->has_closure && m->vi) && m->ntr <= 2 && g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT;
 }
 
@@ -2930,8 +2997,11 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
         a.r[f] = default_range(g, m->loc[f], f < 3);
         nx = std::max(nx, a.r[f].i1 - a.r[f].i0 + 1); ny = std::max(ny, a.r[f].j1 - a.r[f].j0 + 1); nz = std::max(nz, a.r[f].k1 - a.r[f].k0 + 1);
     }
-    a.has_coriolis = m->has_coriolis; a.fcor = m->fcor;
+    a.has_coriolis = m->has_coriolis || m->has_cartesian; a.fcor = m->fcor;
     a.has_buoyancy = m->buoyancy_kind != 0;
+    a.cfx = m->cfx; a.cfy = m->cfy; a.cfz = m->cfz; a.ghat_x = m->ghat[0]; a.ghat_y = m->ghat[1];
+    a.bT = m->buoyancy_kind ? m->U[3 + m->bT_index] : nullptr; a.bS = m->buoyancy_kind == 2 ? m->U[3 + m->S_index] : nullptr;
+    a.grav = m->grav; a.alpha = m->alpha; a.beta = m->beta;
     a.nu = m->nu;
     for (int t = 0; t < OCN_MAX_FIELDS; ++t) a.kappa[t] = t < m->ntr ? m->kappa[t] : 0.0;
     a.amd = m->has_amd || m->has_smag;
@@ -3021,6 +3091,21 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
         }
     }
     const dim3 grd = grid3(nx, ny, nz * m->nf, BLK);
+    // ConstantCartesianCoriolis (1) / gravity_unit_vector (2; 4: of a SeawaterBuoyancy): the EXT instantiations, the only ones with these terms
+    const int ext = (m->has_cartesian ? 1 : 0) | (tilted_buoyancy(m) ? (m->buoyancy_kind == 2 ? 6 : 2) : 0);
+    if (ext) {
+#define OCN_EPX(COR, BUOY, CLO, EXT) hipLaunchKernelGGL((tendency_epilogue_kernel<COR, BUOY, CLO, EXT>), grd, BLK, 0, g_stream, g, a)
+#define OCN_EPX_CLO(COR, BUOY, EXT) do { if (clo == 4) OCN_EPX(COR, BUOY, 4, EXT); else if (clo == 3) OCN_EPX(COR, BUOY, 3, EXT); else if (clo == 2) OCN_EPX(COR, BUOY, 2, EXT); else if (clo == 1) OCN_EPX(COR, BUOY, 1, EXT); else OCN_EPX(COR, BUOY, 0, EXT); } while (0)
+        if (ext == 1)      { if (a.has_buoyancy) OCN_EPX_CLO(true, true, 1); else OCN_EPX_CLO(true, false, 1); }
+        else if (ext == 2) { if (a.has_coriolis) OCN_EPX_CLO(true, true, 2); else OCN_EPX_CLO(false, true, 2); }
+        else if (ext == 6) { if (a.has_coriolis) OCN_EPX_CLO(true, true, 6); else OCN_EPX_CLO(false, true, 6); }
+        else if (ext == 3) OCN_EPX_CLO(true, true, 3);
+        else               OCN_EPX_CLO(true, true, 7);
+#undef OCN_EPX_CLO
+#undef OCN_EPX
+        KERNEL_CHECK();
+        return OCN_OK;
+    }
 #define OCN_EPI(COR, BUOY, CLO) hipLaunchKernelGGL((tendency_epilogue_kernel<COR, BUOY, CLO>), grd, BLK, 0, g_stream, g, a)
 #define OCN_EPI_CLO(COR, BUOY) do { if (clo == 4) OCN_EPI(COR, BUOY, 4); else if (clo == 3) OCN_EPI(COR, BUOY, 3); else if (clo == 2) OCN_EPI(COR, BUOY, 2); else if (clo == 1) OCN_EPI(COR, BUOY, 1); else OCN_EPI(COR, BUOY, 0); } while (0)
     if (a.has_coriolis) { if (a.has_buoyancy) OCN_EPI_CLO(true, true); else OCN_EPI_CLO(true, false); }
@@ -3062,6 +3147,9 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     if (!strcmp(key, "background_fields")) { *value = count_background(m); return OCN_OK; }
     if (!strcmp(key, "background_tendency_path")) { *value = background_tendency_path(m); return OCN_OK; }
     if (!strcmp(key, "vertically_implicit")) { *value = m->vi ? 1 : 0; return OCN_OK; }
+    // coriolis = nothing (0) | FPlane (1) | ConstantCartesianCoriolis (2); whether the buoyancy has a gravity_unit_vector
+    if (!strcmp(key, "coriolis_kind")) { *value = m->has_cartesian ? 2 : (m->has_coriolis ? 1 : 0); return OCN_OK; }
+    if (!strcmp(key, "tilted_gravity")) { *value = tilted_buoyancy(m) ? 1 : 0; return OCN_OK; }
     // which epilogue adds the closure terms: the z-marching one (1) or the per-value one (0) -- the explicit part of a vertically implicit
     // discretisation exists in the per-value epilogue only
     if (!strcmp(key, "epilogue_march_active")) { *value = (epilogue_runs(m) && epilogue_march_selected(m)) ? 1 : 0; return OCN_OK; }
@@ -3129,7 +3217,8 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
     }
     // compute_auxiliaries!: update_hydrostatic_pressure! (update_nonhydrostatic_model_state.jl:58-69)
     if (m->buoyancy_kind &&
-        (rc = update_hydrostatic_pressure(g, m->buoyancy_kind, m->U[3 + m->bT_index], m->U[3 + m->S_index], m->grav, m->alpha, m->beta, m->pHY)))
+        (rc = update_hydrostatic_pressure(g, m->buoyancy_kind, m->U[3 + m->bT_index], m->U[3 + m->S_index], m->grav, m->alpha, m->beta, m->pHY,
+                                          m->tilted, m->ghat[2])))
         return rc;
     if (compute_tend) {
         std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
@@ -3170,6 +3259,12 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
             if (epilogue_runs(m)) { if (has_physics(m) || sub) rc = tendency_epilogue(m, sub); }      // (Flux conditions alone and no substep: nothing to do)
             else {
                 if (sub) return fail(OCN_ESTATE, "fused substep needs the fused epilogue");
+                // the reference's order: x/y_dot_g_b, f x U, the hydrostatic gradient, the closure
+                if (!rc && tilted_buoyancy(m))
+                    rc = add_buoyancy_acceleration(g, m->buoyancy_kind, m->U[3 + m->bT_index], m->U[3 + m->S_index], m->grav, m->alpha, m->beta,
+                                                   m->ghat[0], m->ghat[1], m->Gn[0], m->Gn[1], nullptr);
+                if (!rc && m->has_cartesian)
+                    rc = add_cartesian_coriolis(g, m->cfx, m->cfy, m->cfz, m->U[0], m->U[1], m->U[2], m->Gn[0], m->Gn[1], m->Gn[2], nullptr);
                 if (!rc && m->has_coriolis) rc = add_fplane_coriolis(g, m->fcor, m->U[0], m->U[1], m->Gn[0], m->Gn[1], nullptr);
                 if (!rc && m->buoyancy_kind) rc = add_hydrostatic_pressure_gradient(g, m->pHY, m->Gn[0], m->Gn[1], nullptr);
                 if (!rc && m->has_closure)
@@ -3323,6 +3418,31 @@ extern "C" int ocn_model_set_coriolis(ocn_model_t m, int enabled, double f) {
     if (!m) return fail(OCN_EINVAL, "NULL argument");
     m->has_coriolis = enabled != 0;
     m->fcor = f;
+    m->has_cartesian = false;               // the model has one Coriolis
+    return OCN_OK;
+}
+
+extern "C" int ocn_model_set_cartesian_coriolis(ocn_model_t m, int enabled, double fx, double fy, double fz) {
+    if (m) m->epoch += 1;
+    if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (m->dm) return fail(OCN_ENOTSUP, "ConstantCartesianCoriolis is not served on a partitioned model");
+    m->has_cartesian = enabled != 0;
+    m->cfx = fx; m->cfy = fy; m->cfz = fz;
+    m->has_coriolis = false;                // the model has one Coriolis
+    return OCN_OK;
+}
+
+extern "C" int ocn_model_set_gravity_unit_vector(ocn_model_t m, int enabled, double gx, double gy, double gz) {
+    if (m) m->epoch += 1;
+    if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (m->dm) return fail(OCN_ENOTSUP, "gravity_unit_vector is not served on a partitioned model");
+    if (!enabled) { m->tilted = false; m->ghat[0] = 0.0; m->ghat[1] = 0.0; m->ghat[2] = 1.0; return OCN_OK; }      // NegativeZDirection()
+    // validate_unit_vector (Grids/input_validation.jl:177-186): ex^2 + ey^2 + ez^2 ≈ 1, isapprox with rtol = sqrt(eps)
+    const double n2 = gx * gx + gy * gy + gz * gz;
+    if (!std::isfinite(gx) || !std::isfinite(gy) || !std::isfinite(gz) || !(std::fabs(n2 - 1.0) <= std::sqrt(DBL_EPSILON) * std::fmax(std::fabs(n2), 1.0)))
+        return fail(OCN_EINVAL, "unit vector must satisfy gx^2 + gy^2 + gz^2 ≈ 1");
+    m->tilted = true;
+    m->ghat[0] = -gx; m->ghat[1] = -gy; m->ghat[2] = -gz;      // ĝ = -gravity_unit_vector (buoyancy_force.jl:52-54)
     return OCN_OK;
 }
 

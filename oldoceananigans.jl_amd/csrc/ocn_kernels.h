@@ -778,6 +778,13 @@ struct BuoyancyArgs {
     const double *bT, *S;
     double grav, alpha, beta;
 };
+// ... and ĝ_z = -gravity_unit_vector[3] (buoyancy_force.jl:54) for the TILT instantiations of hydrostatic_pressure_kernel: a type of its
+// own, so that the arguments of the others stay what they were
+struct TiltedBuoyancyArgs : BuoyancyArgs {
+    double ghat_z;
+};
+template <bool TILT> struct HydrostaticArgs { typedef BuoyancyArgs type; };
+template <> struct HydrostaticArgs<true> { typedef TiltedBuoyancyArgs type; };
 __device__ __forceinline__ double buoyancy_perturbation(const BuoyancyArgs &B, long q) {
     return B.kind == 1 ? B.bT[q] : B.grav * (B.alpha * B.bT[q] - B.beta * B.S[q]);
 }
@@ -788,8 +795,10 @@ __device__ __forceinline__ double buoyancy_perturbation(const BuoyancyArgs &B, l
 // KIND (BuoyancyArgs::kind) is compile-time and the levels of a batch are clamped instead of guarded, so that the 2 * TB loads of a batch are
 // straight-line code: with the run-time `kind` test and the `k >= 1` guard around each load the compiler waited for every level's pair before
 // issuing the next (one memory round trip per level: 0.098 ms at 256 x 256 x 128, one wave per SIMD, nothing to hide it behind).
-template <int KIND>
-__global__ void __launch_bounds__(256) hydrostatic_pressure_kernel(DGrid g, FView c, BuoyancyArgs B, double *pHY, int i0, int i1, int j0, int j1) {
+// TILT: BuoyancyForce(formulation; gravity_unit_vector) -- z_dot_g_bᶜᶜᶠ = ĝ_z * ℑzᵃᵃᶠ(b) (g_dot_b.jl:4) with ĝ_z from the arguments in
+// place of the literal 1 of NegativeZDirection (buoyancy_force.jl:54,58); compile-time, so the KIND-only instantiations keep their code.
+template <int KIND, bool TILT = false>
+__global__ void __launch_bounds__(256) hydrostatic_pressure_kernel(DGrid g, FView c, typename HydrostaticArgs<TILT>::type B, double *pHY, int i0, int i1, int j0, int j1) {
     const int i = i0 + blockIdx.x * blockDim.x + threadIdx.x;
     const int j = j0 + blockIdx.y * blockDim.y + threadIdx.y;
     if (i > i1 || j > j1) return;
@@ -814,7 +823,9 @@ __global__ void __launch_bounds__(256) hydrostatic_pressure_kernel(DGrid g, FVie
             const int k = k0 - n;
             if (k >= 1) {
                 const double bk = b_of(tb[n], sb[n]);
-                const double zb = 1 * (0.5 * (bk + bk1));
+                double zb;
+                if constexpr (TILT) zb = B.ghat_z * (0.5 * (bk + bk1));
+                else                zb = 1 * (0.5 * (bk + bk1));
                 const double dzf = g.dzf[k + g.Hz];            // Δzᶠ(k+1)
                 p = k == Nz ? -zb * dzf : p - zb * dzf;
                 pHY[q1 + (long)(k - 1) * c.s2] = p;
@@ -900,6 +911,97 @@ __global__ void __launch_bounds__(256) fplane_coriolis_kernel(DGrid g, double f,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// coriolis = ConstantCartesianCoriolis(fx, fy, fz) (Coriolis/constant_cartesian_coriolis.jl:70-81): a constant rotation vector with all
+// three components. x_f_cross_U = ℑxᶠᵃᵃ(fʸ ℑzᵃᵃᶜ(w) - fᶻ ℑyᵃᶜᵃ(v)), y_f_cross_U = ℑyᵃᶠᵃ(fᶻ ℑxᶜᵃᵃ(u) - fˣ ℑzᵃᵃᶜ(w)), z_f_cross_U =
+// ℑzᵃᵃᶠ(fˣ ℑyᵃᶜᵃ(v) - fʸ ℑxᶜᵃᵃ(u)): plain two-point averages (no active weighting, no wall logic); an interpolation along a Flat
+// direction is the identity (Operators/interpolation_operators.jl:87-112). The velocities are read through accessors
+// q(di, dj, dk) = value at (i + di, j + dj, k + dk), never called with an offset along a Flat direction: one body for the stand-alone
+// kernel and the epilogue.
+// ---------------------------------------------------------------------------------------------------------------------
+template <class QV, class QW>
+__device__ __forceinline__ double x_f_cross_U_cartesian(const DGrid &g, double fy, double fz, QV v, QW w) {
+    const bool flx = g.tx == OCN_FLAT, fly = g.ty == OCN_FLAT, flz = g.tz == OCN_FLAT;
+    auto A = [&](int di) {                                   // fʸw_minus_fᶻv at (c, c, c) (:70-71)
+        const double wz = flz ? w(di, 0, 0) : 0.5 * (w(di, 0, 0) + w(di, 0, 1));
+        const double vy = fly ? v(di, 0, 0) : 0.5 * (v(di, 0, 0) + v(di, 1, 0));
+        return fy * wz - fz * vy;
+    };
+    return flx ? A(0) : 0.5 * (A(-1) + A(0));                // ℑxᶠᵃᵃ (:79)
+}
+template <class QU, class QW>
+__device__ __forceinline__ double y_f_cross_U_cartesian(const DGrid &g, double fx, double fz, QU u, QW w) {
+    const bool flx = g.tx == OCN_FLAT, fly = g.ty == OCN_FLAT, flz = g.tz == OCN_FLAT;
+    auto B = [&](int dj) {                                   // fᶻu_minus_fˣw at (c, c, c) (:73-74)
+        const double ux = flx ? u(0, dj, 0) : 0.5 * (u(0, dj, 0) + u(1, dj, 0));
+        const double wz = flz ? w(0, dj, 0) : 0.5 * (w(0, dj, 0) + w(0, dj, 1));
+        return fz * ux - fx * wz;
+    };
+    return fly ? B(0) : 0.5 * (B(-1) + B(0));                // ℑyᵃᶠᵃ (:80)
+}
+template <class QU, class QV>
+__device__ __forceinline__ double z_f_cross_U_cartesian(const DGrid &g, double fx, double fy, QU u, QV v) {
+    const bool flx = g.tx == OCN_FLAT, fly = g.ty == OCN_FLAT, flz = g.tz == OCN_FLAT;
+    auto C = [&](int dk) {                                   // fˣv_minus_fʸu at (c, c, c) (:76-77)
+        const double vy = fly ? v(0, 0, dk) : 0.5 * (v(0, 0, dk) + v(0, 1, dk));
+        const double ux = flx ? u(0, 0, dk) : 0.5 * (u(0, 0, dk) + u(1, 0, dk));
+        return fx * vy - fy * ux;
+    };
+    return flz ? C(0) : 0.5 * (C(-1) + C(0));                // ℑzᵃᵃᶠ (:81)
+}
+
+// G_u -= x_f_cross_U, G_v -= y_f_cross_U, G_w -= z_f_cross_U on tendencies holding the advective part; each over its own range
+__global__ void __launch_bounds__(256) cartesian_coriolis_kernel(DGrid g, double fx, double fy, double fz, FView u, FView v, FView w, FView Gu,
+                                                                 FView Gv, FView Gw, Range6 ru, Range6 rv, Range6 rw) {
+    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = 1 + blockIdx.z;
+    if (i > g.Nx || j > g.Ny || k > g.Nz) return;
+    auto qu = [&](int di, int dj, int dk) { return u.at(i + di, j + dj, k + dk); };
+    auto qv = [&](int di, int dj, int dk) { return v.at(i + di, j + dj, k + dk); };
+    auto qw = [&](int di, int dj, int dk) { return w.at(i + di, j + dj, k + dk); };
+    if (i >= ru.i0 && i <= ru.i1 && j >= ru.j0 && j <= ru.j1 && k >= ru.k0 && k <= ru.k1)
+        Gu.at(i, j, k) = Gu.at(i, j, k) - x_f_cross_U_cartesian(g, fy, fz, qv, qw);
+    if (i >= rv.i0 && i <= rv.i1 && j >= rv.j0 && j <= rv.j1 && k >= rv.k0 && k <= rv.k1)
+        Gv.at(i, j, k) = Gv.at(i, j, k) - y_f_cross_U_cartesian(g, fx, fz, qu, qw);
+    if (i >= rw.i0 && i <= rw.i1 && j >= rw.j0 && j <= rw.j1 && k >= rw.k0 && k <= rw.k1)
+        Gw.at(i, j, k) = Gw.at(i, j, k) - z_f_cross_U_cartesian(g, fx, fy, qu, qv);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// buoyancy = BuoyancyForce(formulation; gravity_unit_vector) (BuoyancyFormulations/buoyancy_force.jl:47-54, g_dot_b.jl:2-3):
+// x_dot_g_bᶠᶜᶜ = ĝ_x ℑxᶠᵃᵃ(b), y_dot_g_bᶜᶠᶜ = ĝ_y ℑyᵃᶠᵃ(b) with ĝ = -gravity_unit_vector and b the buoyancy perturbation at (c, c, c),
+// read through b(di, dj) = its value at (i + di, j + dj, k). G_u += x_dot_g_b, G_v += y_dot_g_b
+// (nonhydrostatic_tendency_kernel_functions.jl:95,157) on tendencies holding the advective part.
+// ---------------------------------------------------------------------------------------------------------------------
+template <class Q>
+__device__ __forceinline__ double x_dot_g_b(const DGrid &g, double ghat_x, Q b) {
+    return ghat_x * (g.tx == OCN_FLAT ? b(0, 0) : 0.5 * (b(-1, 0) + b(0, 0)));
+}
+template <class Q>
+__device__ __forceinline__ double y_dot_g_b(const DGrid &g, double ghat_y, Q b) {
+    return ghat_y * (g.ty == OCN_FLAT ? b(0, 0) : 0.5 * (b(0, -1) + b(0, 0)));
+}
+// buoyancy_perturbationᶜᶜᶜ with a compile-time kind (the run-time test of buoyancy_perturbation puts a branch around the S load)
+template <int KIND>
+__device__ __forceinline__ double buoyancy_perturbation_of(const double *bT, const double *S, double grav, double alpha, double beta, long q) {
+    return KIND == 1 ? bT[q] : grav * (alpha * bT[q] - beta * S[q]);
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(256) buoyancy_acceleration_kernel(DGrid g, FView c, BuoyancyArgs B, double ghat_x, double ghat_y, FView Gu,
+                                                                    FView Gv, Range6 ru, Range6 rv) {
+    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = 1 + blockIdx.z;
+    if (i > g.Nx || j > g.Ny || k > g.Nz) return;
+    auto b = [&](int di, int dj) { return buoyancy_perturbation_of<KIND>(B.bT, B.S, B.grav, B.alpha, B.beta, c.lin(i + di, j + dj, k)); };
+    if (i >= ru.i0 && i <= ru.i1 && j >= ru.j0 && j <= ru.j1 && k >= ru.k0 && k <= ru.k1)
+        Gu.at(i, j, k) = Gu.at(i, j, k) + x_dot_g_b(g, ghat_x, b);
+    if (i >= rv.i0 && i <= rv.i1 && j >= rv.j0 && j <= rv.j1 && k >= rv.k0 && k <= rv.k1)
+        Gv.at(i, j, k) = Gv.at(i, j, k) + y_dot_g_b(g, ghat_y, b);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // One pass for everything that follows the advective part of the tendencies (nonhydrostatic_tendency_kernel_functions.jl:91-100,
 // 153-162,216-229,286-297): G = (((A - f×U) - ∇pHY′) - ∂ⱼτᵢⱼ) + 0 for every prognostic field, and -- optionally -- the RK3 substep
 // of the NEXT stage into the second set of prognostic arrays (the viscous stencils of neighbouring cells still read U). The
@@ -929,6 +1031,11 @@ struct EpilogueArgs {
     // order like the stand-alone launches
     int nlin;
     struct Lin { int f, side, dep; double a, b; } lin[OCN_EPILOGUE_MAX_LIN];
+    // ConstantCartesianCoriolis and BuoyancyForce(gravity_unit_vector) (the EXT instantiations of tendency_epilogue_kernel): the rotation
+    // vector, ĝ_x, ĝ_y and what buoyancy_perturbation needs. At the end: every member above keeps its place in the kernel arguments
+    double cfx, cfy, cfz, ghat_x, ghat_y;
+    const double *bT, *bS;
+    double grav, alpha, beta;
 };
 
 // the valued and the linear field-dependent Flux conditions of field f at (i, j, k) (parent index q), applied to a tendency G that holds
@@ -977,7 +1084,10 @@ __device__ __forceinline__ double epilogue_flux_conditions(const DGrid &g, const
 // time discretisation) are compile-time: the terms of one cell then form ONE basic
 // block whose ~40 loads the compiler issues together -- with run-time flags every term was its own block behind a branch and its
 // loads waited one after the other (0.94 -> see DESIGN.md for the measured time at 256 x 256 x 128).
-template <bool COR, bool BUOY, int CLO>
+// EXT (bits; 0: the kernel as it was): 1 -- the Coriolis term is ConstantCartesianCoriolis (with COR; then w has one too); 2 -- the buoyancy
+// has a gravity_unit_vector (with BUOY): x_dot_g_b / y_dot_g_b come first after the advective part, before Coriolis
+// (nonhydrostatic_tendency_kernel_functions.jl:95-97,157-159,222-223); 4 -- its buoyancy perturbation is g (α T - β S) instead of the tracer.
+template <bool COR, bool BUOY, int CLO, int EXT = 0>
 __global__ void __launch_bounds__(256) tendency_epilogue_kernel(DGrid g, EpilogueArgs a) {
     // 0.66 ms at 256 x 256 x 128 with the configs[4] physics: ~200 loads per cell, bound on the address / L1 path (VALU busy < 50 %, 3.5 TB/s). Grids without
     // a Flat direction run tendency_epilogue_march_kernel (ocn_epilogue_march.h, 0.48 ms) instead; this kernel stays for the others and as its reference.
@@ -991,15 +1101,26 @@ __global__ void __launch_bounds__(256) tendency_epilogue_kernel(DGrid g, Epilogu
     const long q = fv.lin(i, j, k);
     double G = a.Gn[f][q];
     constexpr bool VAR = CLO == 2 || CLO == 3, PRD = CLO == 3, VI = CLO == 4;
+    constexpr bool CART = (EXT & 1) != 0, TILT = (EXT & 2) != 0;
+    constexpr int BKIND = (EXT & 4) ? 2 : 1;
+    auto qu = [&](int di, int dj, int dk) { return a.u.at(i + di, j + dj, k + dk); };
+    auto qv = [&](int di, int dj, int dk) { return a.v.at(i + di, j + dj, k + dk); };
+    auto qw = [&](int di, int dj, int dk) { return a.w.at(i + di, j + dj, k + dk); };
+    auto qb = [&](int di, int dj) { return buoyancy_perturbation_of<BKIND>(a.bT, a.bS, a.grav, a.alpha, a.beta, a.pHY.lin(i + di, j + dj, k)); };
     if (f == 0) {
-        if (COR) G = G - x_f_cross_U(g, a.fcor, a.v, i, j, k);
+        if (TILT) G = G + x_dot_g_b(g, a.ghat_x, qb);
+        if (COR && CART) G = G - x_f_cross_U_cartesian(g, a.cfy, a.cfz, qv, qw);
+        if (COR && !CART) G = G - x_f_cross_U(g, a.fcor, a.v, i, j, k);
         if (BUOY) G = G - hydrostatic_gradient_x(g, a.pHY, i, j, k);
         if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_U, false, VI>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
     } else if (f == 1) {
-        if (COR) G = G - y_f_cross_U(g, a.fcor, a.u, i, j, k);
+        if (TILT) G = G + y_dot_g_b(g, a.ghat_y, qb);
+        if (COR && CART) G = G - y_f_cross_U_cartesian(g, a.cfx, a.cfz, qu, qw);
+        if (COR && !CART) G = G - y_f_cross_U(g, a.fcor, a.u, i, j, k);
         if (BUOY) G = G - hydrostatic_gradient_y(g, a.pHY, i, j, k);
         if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_V, false, VI>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
     } else if (f == 2) {
+        if (COR && CART) G = G - z_f_cross_U_cartesian(g, a.cfx, a.cfy, qu, qv);
         if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_W, false, VI>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
     } else {
         const double kap = a.kappa[f - 3];

@@ -43,6 +43,37 @@ class Face:
     code = 1
 
 
+class ZDirection:
+    """ZDirection(): the direction singleton a rotation axis defaults to (Grids/Grids.jl; constant_cartesian_coriolis.jl:34)"""
+
+    def __repr__(self):
+        return "ZDirection()"
+
+
+class NegativeZDirection:
+    """NegativeZDirection(): the direction singleton gravity defaults to (buoyancy_force.jl:47)"""
+
+    def __repr__(self):
+        return "NegativeZDirection()"
+
+
+def validate_unit_vector(ê):
+    """validate_unit_vector (Grids/input_validation.jl:174-186): the direction singletons pass through; anything else has length 3 and
+    ê[1]² + ê[2]² + ê[3]² ≈ 1 (isapprox: rtol = √eps) and comes back as a tuple of floats"""
+    if isinstance(ê, (ZDirection, NegativeZDirection)):
+        return ê
+    if isinstance(ê, type) and issubclass(ê, (ZDirection, NegativeZDirection)):
+        return ê()
+    ê = tuple(ê)
+    if len(ê) != 3:
+        raise ValueError("unit vector must have length 3")
+    ex, ey, ez = (float(e) for e in ê)
+    n2 = ex ** 2 + ey ** 2 + ez ** 2
+    if not abs(n2 - 1.0) <= 1.4901161193847656e-08 * max(abs(n2), 1.0):          # √eps(Float64)
+        raise ValueError("unit vector `ê` must satisfy ê[1]² + ê[2]² + ê[3]² ≈ 1")
+    return (ex, ey, ez)
+
+
 def _topo_code(t):
     t = t if isinstance(t, type) else type(t)
     return t.code

@@ -138,6 +138,40 @@ def add_fplane_coriolis(grid, f, u, v, Gu, Gv, kernel_parameters=None):
     _lib.check(_lib.lib().ocn_add_fplane_coriolis(grid.handle, float(f), u.data, v.data, Gu.data, Gv.data, _range(kernel_parameters)))
 
 
+def add_cartesian_coriolis(grid, coriolis, u, v, w, Gu, Gv, Gw, kernel_parameters=None):
+    """- x_f_cross_U, - y_f_cross_U, - z_f_cross_U of the u, v, w tendencies for coriolis = ConstantCartesianCoriolis(fx, fy, fz)"""
+    _lib.check(_lib.lib().ocn_add_cartesian_coriolis(grid.handle, coriolis.fx, coriolis.fy, coriolis.fz, u.data, v.data, w.data, Gu.data, Gv.data,
+                                                     Gw.data, _range(kernel_parameters)))
+
+
+def _buoyancy_arguments(buoyancy, tracers_by_name):
+    """(kind, b or T, S, g, α, β, ĝ) of a formulation or a BuoyancyForce"""
+    from .buoyancy import BuoyancyForce, BuoyancyTracer
+    ghat = (0.0, 0.0, 1.0)
+    if isinstance(buoyancy, BuoyancyForce):
+        if buoyancy.tilted:
+            ghat = tuple(-c for c in buoyancy.gravity_unit_vector)              # ĝ = -gravity_unit_vector (buoyancy_force.jl:52-54)
+        buoyancy = buoyancy.formulation
+    if isinstance(buoyancy, BuoyancyTracer):
+        return 1, tracers_by_name["b"].data, None, 0.0, 0.0, 0.0, ghat
+    e = buoyancy.equation_of_state
+    return (2, tracers_by_name["T"].data, tracers_by_name["S"].data, buoyancy.gravitational_acceleration, e.thermal_expansion,
+            e.haline_contraction, ghat)
+
+
+def add_buoyancy_acceleration(grid, buoyancy, tracers_by_name, Gu, Gv, kernel_parameters=None):
+    """+ x_dot_g_b, + y_dot_g_b of the u, v tendencies for buoyancy = BuoyancyForce(formulation; gravity_unit_vector)"""
+    kind, bT, S, g, α, β, ghat = _buoyancy_arguments(buoyancy, tracers_by_name)
+    _lib.check(_lib.lib().ocn_add_buoyancy_acceleration(grid.handle, kind, bT, S, g, α, β, ghat[0], ghat[1], Gu.data, Gv.data,
+                                                        _range(kernel_parameters)))
+
+
+def update_hydrostatic_pressure_tilted(grid, buoyancy, tracers_by_name, pHY):
+    """update_hydrostatic_pressure! with z_dot_g_b = ĝ_z ℑz(b) for buoyancy = BuoyancyForce(formulation; gravity_unit_vector)"""
+    kind, bT, S, g, α, β, ghat = _buoyancy_arguments(buoyancy, tracers_by_name)
+    _lib.check(_lib.lib().ocn_update_hydrostatic_pressure_tilted(grid.handle, kind, bT, S, g, α, β, ghat[2], pHY.data))
+
+
 def add_hydrostatic_pressure_gradient(grid, pHY, Gu, Gv, kernel_parameters=None):
     """-∂x pHY′, -∂y pHY′ of the u, v tendencies"""
     _lib.check(_lib.lib().ocn_add_hydrostatic_pressure_gradient(grid.handle, pHY.data, Gu.data, Gv.data, _range(kernel_parameters)))

@@ -50,13 +50,20 @@ class NonhydrostaticModel:
         if timestepper not in ("RungeKutta3", "QuasiAdamsBashforth2"):
             raise NotImplementedError("timestepper must be :RungeKutta3 (hot path) or :QuasiAdamsBashforth2 (SURVEY.md 8f.1)")
         self.timestepper, self.χ = timestepper, 0.1          # QuasiAdamsBashforth2TimeStepper(χ = 0.1)
-        from .buoyancy import BuoyancyTracer, FPlane, SeawaterBuoyancy
-        if coriolis is not None and not isinstance(coriolis, FPlane):
-            raise NotImplementedError("coriolis must be nothing or FPlane(f)")
+        from .buoyancy import BuoyancyForce, BuoyancyTracer, ConstantCartesianCoriolis, FPlane, SeawaterBuoyancy
+        if coriolis is not None and not isinstance(coriolis, (FPlane, ConstantCartesianCoriolis)):
+            raise NotImplementedError("coriolis must be nothing, FPlane(f) or ConstantCartesianCoriolis(fx, fy, fz)")
         self.coriolis = coriolis
-        if buoyancy is not None and not isinstance(buoyancy, (BuoyancyTracer, SeawaterBuoyancy)):
-            raise NotImplementedError("buoyancy must be nothing, BuoyancyTracer() or SeawaterBuoyancy(LinearEquationOfState)")
+        # a bare formulation is BuoyancyForce(formulation) with NegativeZDirection() (regularize_buoyancy, buoyancy_force.jl:74-75): the
+        # calls below are then the ones a bare formulation always made
+        force = buoyancy if isinstance(buoyancy, BuoyancyForce) else None
+        formulation = force.formulation if force is not None else buoyancy
+        if formulation is not None and not isinstance(formulation, (BuoyancyTracer, SeawaterBuoyancy)):
+            raise NotImplementedError("buoyancy must be nothing, BuoyancyTracer(), SeawaterBuoyancy(LinearEquationOfState) or a BuoyancyForce of one")
         self.buoyancy = buoyancy
+        tilted = force is not None and force.tilted
+        if hasattr(grid, "local") and (tilted or isinstance(coriolis, ConstantCartesianCoriolis)):
+            raise NotImplementedError("ConstantCartesianCoriolis and BuoyancyForce(gravity_unit_vector) are not served on partitioned grids")
         from .closures import AnisotropicMinimumDissipation, ScalarDiffusivity, Smagorinsky
         if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
             raise NotImplementedError("only closure = nothing | ScalarDiffusivity(ν, κ) | AnisotropicMinimumDissipation(C, Cν, Cκ) | "
@@ -105,18 +112,22 @@ class NonhydrostaticModel:
             if missing:
                 raise ValueError(f"{buoyancy!r} requires the tracers {missing}")
             idx = [self.tracer_names.index(t) for t in buoyancy.required_tracers]
-            if isinstance(buoyancy, BuoyancyTracer):
+            if isinstance(formulation, BuoyancyTracer):
                 _lib.check(_lib.lib().ocn_model_set_buoyancy(self.handle, 1, idx[0], 0, 0.0, 0.0, 0.0))
             else:
-                e = buoyancy.equation_of_state
-                _lib.check(_lib.lib().ocn_model_set_buoyancy(self.handle, 2, idx[0], idx[1], buoyancy.gravitational_acceleration,
+                e = formulation.equation_of_state
+                _lib.check(_lib.lib().ocn_model_set_buoyancy(self.handle, 2, idx[0], idx[1], formulation.gravitational_acceleration,
                                                              e.thermal_expansion, e.haline_contraction))
+            if tilted:
+                _lib.check(_lib.lib().ocn_model_set_gravity_unit_vector(self.handle, 1, *force.gravity_unit_vector))
             P = namedtuple("Pressures", "pNHS pHY")          # pHY′: the hydrostatic pressure anomaly (nonhydrostatic_model.jl:144-158)
             self.pressures = P(self._field("p"), self._field("pHY"))
         else:
             P = namedtuple("Pressures", "pNHS")
             self.pressures = P(self._field("p"))
-        if coriolis is not None:
+        if isinstance(coriolis, ConstantCartesianCoriolis):
+            _lib.check(_lib.lib().ocn_model_set_cartesian_coriolis(self.handle, 1, coriolis.fx, coriolis.fy, coriolis.fz))
+        elif coriolis is not None:
             _lib.check(_lib.lib().ocn_model_set_coriolis(self.handle, 1, coriolis.f))
         self.diffusivity_fields = None
         if isinstance(closure, AnisotropicMinimumDissipation):
