@@ -423,7 +423,8 @@ int ocn_model_set_cartesian_coriolis(ocn_model_t model, int enabled, double fx, 
  * ocn_model_get_option answers "tilted_gravity" (1 with a buoyancy and a gravity_unit_vector). Models with either of these two take the
  * per-value tendency epilogue: "epilogue_march_active" answers 0. */
 int ocn_model_set_gravity_unit_vector(ocn_model_t model, int enabled, double gx, double gy, double gz);
-/* closure = ScalarDiffusivity(ν = nu, κ = kappa[tracer]) of the model constructor; all zeros / NULL: closure = nothing */
+/* closure = ScalarDiffusivity(ν = nu, κ = kappa[tracer]) of the model constructor. The model has ONE closure: this replaces any other
+ * (an AMD or Smagorinsky closure too: "nu_e" then answers OCN_ESTATE again); all zeros / NULL: closure = nothing */
 int ocn_model_set_closure(ocn_model_t model, double nu, const double *kappa);
 /* time discretisation of the model's ScalarDiffusivity (scalar_diffusivity.jl:116-141): enabled = 1 is
  * VerticallyImplicitTimeDiscretization() -- the tendencies keep the explicit part only and every substep of RK3 / AB2 is followed by

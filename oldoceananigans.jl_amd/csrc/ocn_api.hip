@@ -11,6 +11,7 @@
 #include "ocn_forcing.h"
 #include "ocn_implicit_z.h"
 #include <hipfft/hipfft.h>
+#include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstdarg>
@@ -18,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2609,6 +2611,39 @@ static int dist_poisson_backward_yz(ocn_dist_poisson_t s, double *phi, bool keep
 // ---------------------------------------------------------------------------------------------------------------------
 struct DistModel;
 static void dist_model_free(DistModel *dm);
+// The physics of a model: ONE coriolis, ONE buoyancy, ONE closure. A setter assigns its value as a whole, so what replaces what follows from
+// the type; which kernels a step then launches is derived from the three in one place (plan, below).
+struct Coriolis {
+    enum Kind { NONE, FPLANE, CARTESIAN } kind = NONE;    // nothing | FPlane(f) | ConstantCartesianCoriolis(fx, fy, fz): "coriolis_kind" 0 / 1 / 2
+    double f = 0.0, fx = 0.0, fy = 0.0, fz = 0.0;
+};
+struct Buoyancy {
+    int kind = 0, bT = 0, S = 0;            // 0 nothing, 1 BuoyancyTracer, 2 linear SeawaterBuoyancy; the tracers' indices
+    double grav = 0.0, alpha = 0.0, beta = 0.0;
+    // BuoyancyForce(formulation; gravity_unit_vector): ĝ = -gravity_unit_vector, kept whatever the formulation is (each has its setter)
+    bool tilted = false;
+    double ghat[3] = {0.0, 0.0, 1.0};
+    bool acts_tilted() const { return tilted && kind != 0; }
+};
+struct Closure {
+    // nothing | ScalarDiffusivity(ν, κ), not all zero | AnisotropicMinimumDissipation(Cν, Cκ) | Smagorinsky(C, Pr) / SmagorinskyLilly(C, Cb, Pr)
+    enum Kind { NONE, SCALAR, AMD, SMAGORINSKY } kind = NONE;
+    double nu = 0.0, kappa[OCN_MAX_FIELDS] = {};
+    // ... with VerticallyImplicitTimeDiscretization(): implicit_step! after every substep. It may be named before the coefficients (kind
+    // NONE or SCALAR) and is never true with AMD / SMAGORINSKY
+    bool vi = false;
+    double Cnu = 0.0, Ckappa[OCN_MAX_FIELDS] = {};
+    double C = 0.0, Cb = 0.0, Pr[OCN_MAX_FIELDS] = {};
+    bool lilly = false;
+    bool eddy() const { return kind == AMD || kind == SMAGORINSKY; }      // the closures with diffusivity fields (Smagorinsky: νₑ only, smagorinsky.jl:131-139)
+    // the CLO coordinate of the epilogue kernels (ocn_kernels.h): 0 none, 1 constant ν, κ, 2 coefficient arrays, 3 the same with the tracers'
+    // coefficient divided by a Prandtl number (Smagorinsky with some Pr ≠ 1), 4 the explicit part of a vertically implicit ScalarDiffusivity
+    int clo(int ntr) const {
+        for (int t = 0; t < ntr && kind == SMAGORINSKY; ++t)
+            if (Pr[t] != 1.0) return 3;
+        return eddy() ? 2 : (kind == SCALAR ? (vi ? 4 : 1) : 0);
+    }
+};
 struct ocn_model_s {
     ocn_grid_t grid;
     OcnOptions opt;                         // this model's options: the library defaults when it was created, then ocn_model_set_option
@@ -2633,28 +2668,15 @@ struct ocn_model_s {
     bool any_bc = false, any_flux_bc = false;
     struct LinBC { bool on = false; int dep = 0; double a = 0.0, b = 0.0; } lin[OCN_MAX_FIELDS][6];   // linear field-dependent Flux
     bool any_linear_flux = false;
-    bool has_closure = false;               // closure = ScalarDiffusivity(ν, κ)
-    double nu = 0.0, kappa[OCN_MAX_FIELDS] = {};
-    bool vi = false;                        // ... with VerticallyImplicitTimeDiscretization(): implicit_step! after every substep
-    bool has_amd = false;                   // closure = AnisotropicMinimumDissipation(Cν, Cκ)
-    double Cnu = 0.0, Ckappa[OCN_MAX_FIELDS] = {};
-    double *nu_e = nullptr, *kappa_e[OCN_MAX_FIELDS] = {};   // diffusivity_fields.νₑ, .κₑ (ccc, with halos)
-    bool has_smag = false;                  // closure = Smagorinsky(C, Pr) | SmagorinskyLilly(C, Cb, Pr): νₑ only (build_diffusivity_fields, smagorinsky.jl:131-139)
-    bool smag_lilly = false, smag_unit_pr = true;
-    double smag_C = 0.0, smag_Cb = 0.0, Pr[OCN_MAX_FIELDS] = {};
+    Coriolis coriolis;
+    Buoyancy buoyancy;
+    Closure closure;
+    double *nu_e = nullptr, *kappa_e[OCN_MAX_FIELDS] = {};   // diffusivity_fields.νₑ, .κₑ (ccc, with halos): allocated by the setters, kept
     // forcing = (name = F,) (ocn_forcing.h): host copy of the descriptors, the device-resident table the kernels read, the device copies
     // of the tables (per field and term: mask, target)
     ForcingTable forcing_h = {};
     ForcingTable *forcing_d = nullptr;
     double *forcing_tables[OCN_MAX_FIELDS][OCN_MAX_FORCING_TERMS][2] = {};
-    bool has_coriolis = false;              // coriolis = FPlane(f)
-    double fcor = 0.0;
-    bool has_cartesian = false;             // coriolis = ConstantCartesianCoriolis(fx, fy, fz): replaces FPlane and is replaced by it
-    double cfx = 0.0, cfy = 0.0, cfz = 0.0;
-    bool tilted = false;                    // buoyancy = BuoyancyForce(formulation; gravity_unit_vector): ĝ = -gravity_unit_vector
-    double ghat[3] = {0.0, 0.0, 1.0};
-    int buoyancy_kind = 0, bT_index = 0, S_index = 0;    // 0 nothing, 1 BuoyancyTracer, 2 linear SeawaterBuoyancy
-    double grav = 0.0, alpha = 0.0, beta = 0.0;
     double *pHY = nullptr;                  // hydrostatic pressure anomaly (only with buoyancy)
     // background_fields = (u = Ū, b = B̄, ...) (background_fields.jl): borrowed haloed arrays at their field's location (NULL: ZeroField),
     // and the total velocities U + Ū update_state! forms for the components that have one (owned; allocated by the setter)
@@ -2693,6 +2715,20 @@ extern "C" int ocn_model_destroy(ocn_model_t m) {
     return OCN_OK;
 }
 
+// a zeroed haloed parent array at location `loc`, unless *p already has one: the model's arrays and what the setters add to them (never
+// inside a captured step)
+static int alloc_parent_zeroed(ocn_grid_t grid, const int loc[3], double **p) {
+    if (*p) return OCN_OK;
+    int P[3];
+    parent_size(grid->d, loc, P);
+    const size_t bytes = (size_t)P[0] * P[1] * P[2] * sizeof(double);
+    hipError_t e = dev_alloc((void **)p, bytes);
+    if (e != hipSuccess) { *p = nullptr; return fail((int)e, "dev_alloc(field): %s", hipGetErrorString(e)); }
+    e = hipMemsetAsync(*p, 0, bytes, g_stream);
+    if (e != hipSuccess) return fail((int)e, "hipMemset(field): %s", hipGetErrorString(e));
+    return OCN_OK;
+}
+
 static int model_create(ocn_model_t *model, ocn_grid_t grid, int ntracers, bool with_solver) {
     if (!model || !grid) return fail(OCN_EINVAL, "NULL argument");
     if (ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3) return fail(OCN_EINVAL, "ntracers must be in 0..%d", OCN_MAX_FIELDS - 3);
@@ -2705,25 +2741,15 @@ static int model_create(ocn_model_t *model, ocn_grid_t grid, int ntracers, bool 
     m->p = nullptr; m->solver = nullptr; m->blockmax = nullptr;
     const int *locs[3] = {LOC_U, LOC_V, LOC_W};
     int rc = OCN_OK;
-    auto alloc = [&](double **p, const int loc[3]) -> int {
-        int P[3];
-        parent_size(grid->d, loc, P);
-        size_t bytes = (size_t)P[0] * P[1] * P[2] * sizeof(double);
-        hipError_t e = dev_alloc((void **)p, bytes);
-        if (e != hipSuccess) return fail((int)e, "dev_alloc(field): %s", hipGetErrorString(e));
-        e = hipMemsetAsync(*p, 0, bytes, g_stream);
-        if (e != hipSuccess) return fail((int)e, "hipMemset(field): %s", hipGetErrorString(e));
-        return OCN_OK;
-    };
     for (int f = 0; f < m->nf && !rc; ++f) {
         const int *l = f < 3 ? locs[f] : LOC_C;
         memcpy(m->loc[f], l, sizeof(int) * 3);
-        if (!rc) rc = alloc(&m->U[f], l);
-        if (!rc) rc = alloc(&m->U2[f], l);
-        if (!rc) rc = alloc(&m->Gn[f], l);
-        if (!rc) rc = alloc(&m->Gm[f], l);
+        if (!rc) rc = alloc_parent_zeroed(grid, l, &m->U[f]);
+        if (!rc) rc = alloc_parent_zeroed(grid, l, &m->U2[f]);
+        if (!rc) rc = alloc_parent_zeroed(grid, l, &m->Gn[f]);
+        if (!rc) rc = alloc_parent_zeroed(grid, l, &m->Gm[f]);
     }
-    if (!rc) rc = alloc(&m->p, LOC_C);
+    if (!rc) rc = alloc_parent_zeroed(grid, LOC_C, &m->p);
     if (!rc) {
         hipError_t e = dev_alloc((void **)&m->blockmax, 1024 * sizeof(double));
         if (e != hipSuccess) rc = fail((int)e, "hipMalloc: %s", hipGetErrorString(e));
@@ -2742,7 +2768,8 @@ extern "C" int ocn_model_create(ocn_model_t *model, ocn_grid_t grid, int ntracer
     return model_create(model, grid, ntracers, true);
 }
 
-static int model_field_index(const ocn_model_s *m, const char *name) {
+// "u" | "v" | "w" | "cN" -> the index of the prognostic field, -1 when the model has none of that name
+static int field_index(const ocn_model_s *m, const char *name) {
     if (!strcmp(name, "u")) return 0;
     if (!strcmp(name, "v")) return 1;
     if (!strcmp(name, "w")) return 2;
@@ -2759,10 +2786,10 @@ static int field_lookup(ocn_model_s *m, const char *name, double ***slot, int **
         *slot = &m->pHY; *loc = const_cast<int *>(LOC_C); return OCN_OK;
     }
     if (!strcmp(name, "nu_e") || !strncmp(name, "kappa_e", 7)) {
-        if (!m->has_amd && !m->has_smag) return fail(OCN_ESTATE, "the model has no eddy diffusivity fields (closure is not an LES closure)");
+        if (!m->closure.eddy()) return fail(OCN_ESTATE, "the model has no eddy diffusivity fields (closure is not an LES closure)");
         *loc = const_cast<int *>(LOC_C);
         if (!strcmp(name, "nu_e")) { *slot = &m->nu_e; return OCN_OK; }
-        if (m->has_smag) return fail(OCN_ESTATE, "a Smagorinsky closure has the eddy viscosity nu_e only (the tracers' coefficient is nu_e / Pr at their flux points)");
+        if (m->closure.kind == Closure::SMAGORINSKY) return fail(OCN_ESTATE, "a Smagorinsky closure has the eddy viscosity nu_e only (the tracers' coefficient is nu_e / Pr at their flux points)");
         const int t = name[7] - '0';
         if (name[7] < '0' || name[7] > '9' || name[8] || t >= m->ntr) return fail(OCN_EINVAL, "no eddy diffusivity field %s", name);
         *slot = &m->kappa_e[t];
@@ -2771,7 +2798,7 @@ static int field_lookup(ocn_model_s *m, const char *name, double ***slot, int **
     // background_fields: "bg_<name>" is the caller's array, "total_<name>" a velocity component's U + Ū as of the last update_state!
     if (!strncmp(name, "bg_", 3) || !strncmp(name, "total_", 6)) {
         const bool total = name[0] == 't';
-        const int f = model_field_index(m, name + (total ? 6 : 3));
+        const int f = field_index(m, name + (total ? 6 : 3));
         if (f < 0 || (total && f > 2)) return fail(OCN_EINVAL, "no background field %s", name);
         if (!m->bg[f]) return fail(OCN_ESTATE, "the model has no background field for %s", name + (total ? 6 : 3));
         *slot = total ? &m->tot[f] : const_cast<double **>(&m->bg[f]);
@@ -2779,11 +2806,7 @@ static int field_lookup(ocn_model_s *m, const char *name, double ***slot, int **
         return OCN_OK;
     }
     if (q[0] == 'G' || q[0] == 'M') { kind = q[0]; ++q; }
-    int f = -1;
-    if (!strcmp(q, "u")) f = 0;
-    else if (!strcmp(q, "v")) f = 1;
-    else if (!strcmp(q, "w")) f = 2;
-    else if (q[0] == 'c' && q[1] >= '0' && q[1] <= '9' && !q[2] && (q[1] - '0') < m->ntr) f = 3 + (q[1] - '0');
+    const int f = field_index(m, q);
     if (f < 0) return fail(OCN_EINVAL, "name %s not found in model.velocities or model.tracers.", name);
     *slot = kind == 'U' ? &m->U[f] : (kind == 'G' ? &m->Gn[f] : &m->Gm[f]);
     *loc = m->loc[f];
@@ -2906,8 +2929,6 @@ extern "C" int ocn_model_set_option(ocn_model_t m, const char *key, int value) {
     return OCN_OK;
 }
 
-static bool has_physics(const ocn_model_s *m) { return m->has_coriolis || m->has_cartesian || m->buoyancy_kind != 0 || m->has_closure || m->has_amd || m->has_smag; }
-
 // the form of the vertically implicit solve a model runs (ocn_implicit_z.h): the reference-shaped one, the only one shipped
 static int model_ivd_form(const ocn_model_s *) { return 0; }
 
@@ -2929,29 +2950,70 @@ static int update_total_velocities(ocn_model_s *m) {
         }
     return OCN_OK;
 }
-// which kernels evaluate the background terms (option "background_tendency_path"): 0 none, 1 the per-field kernels, 2 the role kernel
-static int background_tendency_path(const ocn_model_s *m) {
-    return !has_background(m) ? 0 : (split_role_path(m->opt, m->grid->d, m->opt.tendency_impl) ? 2 : 1);
-}
 
 static bool has_forcing(const ocn_model_s *m) {
     for (int f = 0; f < m->nf; ++f)
         if (m->forcing_h.nterms[f] > 0) return true;
     return false;
 }
-static bool epilogue_runs(const ocn_model_s *m);
-// the forcing term rides in the role tendency kernel (FORCE instantiation) when that kernel completes the tendency by itself: no physics
-// epilogue, no Flux condition, the role kernel on the whole single-GPU grid, reference arithmetic, Periodic z (the Bounded-z instantiation
-// spilled, ocn_tendency_roles.h) -- the configs[1]-plus-sponge case, which keeps the RK3 substep fused. Partitioned models (interior / strip launches) and everything else take the standalone pass.
-static bool forcing_in_role(const ocn_model_s *m) {
-    const DGrid &g = m->grid->d;
-    return has_forcing(m) && !has_background(m) && m->opt.fused_forcing && !m->dm && !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && !epilogue_runs(m) &&
-           m->opt.tendency_impl == 2 && m->opt.arithmetic == 0 && g.tz == OCN_PERIODIC && fused_path(m->opt, g, nullptr, m->ntr, 2) &&
-           role_tendency_supported(m->opt, g);
+static int count_linear_flux(const ocn_model_s *m) {
+    int n = 0;
+    for (int f = 0; f < m->nf; ++f)
+        for (int sd = 0; sd < 6; ++sd) n += m->lin[f][sd].on ? 1 : 0;
+    return n;
 }
-// which pass adds the forcing term (option "forcing_path"): 0 none, 1 the role tendency kernel, 3 the standalone pass (add_forcing_kernel);
-// 2 (inside the physics epilogue) is reserved: that fusion is not built
-static int forcing_path(const ocn_model_s *m) { return has_forcing(m) ? (forcing_in_role(m) ? 1 : 3) : 0; }
+
+// What a tendency evaluation of this model launches, derived in ONE place from its physics, conditions and options: host arithmetic only,
+// no device call. update_state_tail, tendency_epilogue, the time steppers and the report-only keys of ocn_model_get_option read it; none of
+// them derives a rule again.
+struct StepPlan {
+    bool physics;               // a Coriolis, buoyancy or closure term exists
+    bool epilogue;              // the one-pass epilogue completes the tendencies (without it the stand-alone kernels add the physics terms)
+    bool march;                 // ... in its z-marching form, tendency_epilogue_march_kernel (option "epilogue_march_active")
+    bool cor, buoy;             // the template coordinates of the epilogue kernels (kEpilogueKernels, kEpilogueMarchKernels) ...
+    int clo, ext, ntr;          // ... Closure::clo; EXT bits: 1 ConstantCartesianCoriolis, 2 gravity_unit_vector, 4 of a SeawaterBuoyancy
+    bool fuse_substep;          // the RK3 substep of the next stage rides along (option "fuse_substep_active") ...
+    bool substep_in_advection;  // ... in the advection kernel; otherwise in the epilogue (option "substep_in_tendency_kernel")
+    // which pass adds the forcing term (option "forcing_path"): 0 none, 1 the role tendency kernel, 3 the standalone pass (add_forcing_kernel);
+    // 2 (inside the physics epilogue) is reserved: that fusion is not built
+    int forcing_path;
+    int background_path;        // which kernels evaluate the background terms (option "background_tendency_path"): 0 none, 1 per field, 2 the role kernel
+};
+static StepPlan plan(const ocn_model_s *m) {
+    const DGrid &g = m->grid->d;
+    const OcnOptions &o = m->opt;
+    const Buoyancy &b = m->buoyancy;
+    StepPlan p = {};
+    p.cor = m->coriolis.kind != Coriolis::NONE; p.buoy = b.kind != 0; p.clo = m->closure.clo(m->ntr); p.ntr = m->ntr;
+    // ConstantCartesianCoriolis (1) / gravity_unit_vector (2; 4: of a SeawaterBuoyancy): the EXT instantiations, the only ones with these terms
+    p.ext = (m->coriolis.kind == Coriolis::CARTESIAN ? 1 : 0) | (b.acts_tilted() ? (b.kind == 2 ? 6 : 2) : 0);
+    p.physics = p.cor || p.buoy || p.clo != 0;
+    // the one-pass epilogue runs whenever something follows the advective part: physics terms, valued or field-dependent Flux conditions
+    const bool flux = m->any_flux_bc || m->any_linear_flux;
+    p.epilogue = o.fused_epilogue && (p.physics || flux) && count_linear_flux(m) <= OCN_EPILOGUE_MAX_LIN;
+    // whether the closure terms take the z-marching epilogue (ocn_epilogue_march.h): a grid without Flat directions, at most two tracers, and
+    // not the explicit part of a vertically implicit discretisation -- that variant exists in the per-value epilogue only, as do the terms of a
+    // ConstantCartesianCoriolis and of a buoyancy with a gravity_unit_vector
+    p.march = p.epilogue && o.epilogue_march && p.clo >= 1 && p.clo <= 3 && p.ext == 0 && m->ntr <= 2 && g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT;
+    // the forcing term rides in the role tendency kernel (FORCE instantiation) when that kernel completes the tendency by itself: no physics
+    // epilogue, no Flux condition, the role kernel on the whole single-GPU grid, reference arithmetic, Periodic z (the Bounded-z instantiation
+    // spilled, ocn_tendency_roles.h) -- the configs[1]-plus-sponge case, which keeps the RK3 substep fused. Partitioned models (interior / strip launches) and everything else take the standalone pass.
+    const bool forcing = has_forcing(m), background = has_background(m);
+    const bool forcing_in_role = forcing && !background && o.fused_forcing && !m->dm && !p.physics && !flux && !p.epilogue && o.tendency_impl == 2 &&
+                                 o.arithmetic == 0 && g.tz == OCN_PERIODIC && fused_path(o, g, nullptr, m->ntr, 2) && role_tendency_supported(o, g);
+    p.forcing_path = forcing ? (forcing_in_role ? 1 : 3) : 0;
+    p.background_path = !background ? 0 : (split_role_path(o, g, o.tendency_impl) ? 2 : 1);
+    // without extra physics the substep rides in the fused advection kernel; with Coriolis / buoyancy / closure terms it rides in
+    // the epilogue pass that completes the tendencies (any advection path); a valued Flux condition is added after both
+    if (!o.fuse_substep || !o.swap_tendencies) p.fuse_substep = false;
+    else if (p.forcing_path == 3) p.fuse_substep = false;            // the forcing pass completes G after the launch the substep would ride in
+    else if (p.epilogue) p.fuse_substep = true;                      // the epilogue pass also applies the Flux conditions
+    else if (background) p.fuse_substep = false;                     // the second advection term follows the launch the substep would ride in
+    else p.fuse_substep = !p.physics && !flux && fused_path(o, g, nullptr, m->ntr, o.tendency_impl);
+    p.substep_in_advection = p.fuse_substep && !p.epilogue;
+    return p;
+}
+static bool has_physics(const ocn_model_s *m) { return plan(m).physics; }
 
 // G = G_rest + F of every forced field (ocn_forcing.h), one launch after the tendency evaluation is complete (advection, physics
 // epilogue) and before the Flux-condition terms (compute_flux_bc_tendencies, which the steppers call when the next stage begins)
@@ -2971,22 +3033,37 @@ static int add_forcing(ocn_model_s *m) {
     return OCN_OK;
 }
 
-// whether the closure terms take the z-marching epilogue (ocn_epilogue_march.h): a grid without Flat directions, at most two tracers, and
-// not the explicit part of a vertically implicit discretisation -- that variant exists in the per-value epilogue only, as do the terms of a
-// ConstantCartesianCoriolis and of a buoyancy with a gravity_unit_vector
-static bool tilted_buoyancy(const ocn_model_s *m) { return m->tilted && m->buoyancy_kind != 0; }
-static bool epilogue_march_selected(const ocn_model_s *m) {
-    const DGrid &g = m->grid->d;
-    const bool clo = m->has_smag || m->has_amd || m->has_closure;
-    if (m->has_cartesian || tilted_buoyancy(m)) return false;
-    return m->opt.epilogue_march && clo && !(m->has_closure && m->vi) && m->ntr <= 2 && g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT;
+// The instantiations of the two epilogue kernels: one table per family, indexed by the plan's coordinates. The validity predicates are the
+// list of what exists -- a slot they refuse holds nullptr and its kernel is never instantiated.
+//   per value: COR x BUOY x CLO 0..4 x EXT, where EXT's bit 1 (ConstantCartesianCoriolis) needs COR, bit 2 (gravity_unit_vector) needs BUOY
+//              and bit 4 (... of a SeawaterBuoyancy) needs bit 2: EXT in {0, 1, 2, 3, 6, 7}, 20 + 40 kernels
+//   marching:  COR x BUOY x CLO 1..3 x NTR 0..2, 36 kernels: no EXT terms and no vertically implicit variant (StepPlan::march)
+using EpilogueKernel = void (*)(DGrid, EpilogueArgs);
+using EpilogueMarchKernel = void (*)(DGrid, EpilogueArgs, Range6, int);
+constexpr bool epilogue_valid(bool cor, bool buoy, int clo, int ext) { return clo >= 0 && clo <= 4 && ext >= 0 && ext <= 7 && (!(ext & 1) || cor) && (!(ext & 2) || buoy) && (!(ext & 4) || (ext & 2)); }
+constexpr bool epilogue_march_valid(int clo, int ntr) { return clo >= 1 && clo <= 3 && ntr >= 0 && ntr <= 2; }
+constexpr int epilogue_slot(bool cor, bool buoy, int clo, int ext) { return (cor ? 1 : 0) + 2 * ((buoy ? 1 : 0) + 2 * (ext + 8 * clo)); }
+constexpr int epilogue_march_slot(bool cor, bool buoy, int clo, int ntr) { return (cor ? 1 : 0) + 2 * ((buoy ? 1 : 0) + 2 * (ntr + 3 * clo)); }
+template <int I> constexpr EpilogueKernel epilogue_kernel_at() {
+    constexpr bool COR = I % 2 != 0, BUOY = I / 2 % 2 != 0; constexpr int EXT = I / 4 % 8, CLO = I / 32;          // (epilogue_slot)
+    if constexpr (epilogue_valid(COR, BUOY, CLO, EXT)) return tendency_epilogue_kernel<COR, BUOY, CLO, EXT>; else return nullptr;
 }
+template <int I> constexpr EpilogueMarchKernel epilogue_march_kernel_at() {
+    constexpr bool COR = I % 2 != 0, BUOY = I / 2 % 2 != 0; constexpr int NTR = I / 4 % 3, CLO = I / 12;          // (epilogue_march_slot)
+    if constexpr (epilogue_march_valid(CLO, NTR)) return tendency_epilogue_march_kernel<COR, BUOY, CLO, NTR>; else return nullptr;
+}
+template <size_t... I> constexpr std::array<EpilogueKernel, sizeof...(I)> epilogue_kernels(std::index_sequence<I...>) { return {{epilogue_kernel_at<(int)I>()...}}; }
+template <size_t... I> constexpr std::array<EpilogueMarchKernel, sizeof...(I)> epilogue_march_kernels(std::index_sequence<I...>) { return {{epilogue_march_kernel_at<(int)I>()...}}; }
+static constexpr auto kEpilogueKernels = epilogue_kernels(std::make_index_sequence<epilogue_slot(true, true, 4, 7) + 1>{});
+static constexpr auto kEpilogueMarchKernels = epilogue_march_kernels(std::make_index_sequence<epilogue_march_slot(true, true, 3, 2) + 1>{});
 
 // Coriolis, hydrostatic pressure gradient and closure terms of every field -- and, when `sub` is given, the RK3 substep of the next
 // stage -- in one launch (tendency_epilogue_kernel)
-static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
+static int tendency_epilogue(ocn_model_s *m, const StepPlan &p, const FusedSubstep *sub) {
     const DGrid &g = m->grid->d;
-    EpilogueArgs a;
+    const Buoyancy &b = m->buoyancy;
+    const Closure &c = m->closure;
+    EpilogueArgs a = {};                          // (its run-time term flags stay unset: no kernel reads them, the terms are template arguments)
     a.n = m->nf; a.ntr = m->ntr;
     a.u = make_view(g, m->U[0], LOC_U); a.v = make_view(g, m->U[1], LOC_V); a.w = make_view(g, m->U[2], LOC_W);
     for (int t = 0; t < m->ntr; ++t) a.c[t] = make_view(g, m->U[3 + t], LOC_C);
@@ -2997,22 +3074,20 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
         a.r[f] = default_range(g, m->loc[f], f < 3);
         nx = std::max(nx, a.r[f].i1 - a.r[f].i0 + 1); ny = std::max(ny, a.r[f].j1 - a.r[f].j0 + 1); nz = std::max(nz, a.r[f].k1 - a.r[f].k0 + 1);
     }
-    a.has_coriolis = m->has_coriolis || m->has_cartesian; a.fcor = m->fcor;
-    a.has_buoyancy = m->buoyancy_kind != 0;
-    a.cfx = m->cfx; a.cfy = m->cfy; a.cfz = m->cfz; a.ghat_x = m->ghat[0]; a.ghat_y = m->ghat[1];
-    a.bT = m->buoyancy_kind ? m->U[3 + m->bT_index] : nullptr; a.bS = m->buoyancy_kind == 2 ? m->U[3 + m->S_index] : nullptr;
-    a.grav = m->grav; a.alpha = m->alpha; a.beta = m->beta;
-    a.nu = m->nu;
-    for (int t = 0; t < OCN_MAX_FIELDS; ++t) a.kappa[t] = t < m->ntr ? m->kappa[t] : 0.0;
-    a.amd = m->has_amd || m->has_smag;
-    if (m->has_amd) {
+    a.fcor = m->coriolis.f; a.cfx = m->coriolis.fx; a.cfy = m->coriolis.fy; a.cfz = m->coriolis.fz;
+    a.ghat_x = b.ghat[0]; a.ghat_y = b.ghat[1];
+    a.bT = b.kind ? m->U[3 + b.bT] : nullptr; a.bS = b.kind == 2 ? m->U[3 + b.S] : nullptr;
+    a.grav = b.grav; a.alpha = b.alpha; a.beta = b.beta;
+    a.nu = c.nu;
+    for (int t = 0; t < m->ntr; ++t) a.kappa[t] = c.kappa[t];
+    if (c.kind == Closure::AMD) {
         a.nu_e = make_view(g, m->nu_e, LOC_C);
         for (int t = 0; t < m->ntr; ++t) a.kappa_e[t] = make_view(g, m->kappa_e[t], LOC_C);
     }
-    if (m->has_smag) {
+    if (c.kind == Closure::SMAGORINSKY) {
         // every tracer's coefficient array is νₑ; with a Pr ≠ 1 the kernels divide the interpolated value by kappa[t] = Pr[t] (CLO 3)
         a.nu_e = make_view(g, m->nu_e, LOC_C);
-        for (int t = 0; t < m->ntr; ++t) { a.kappa_e[t] = a.nu_e; a.kappa[t] = m->Pr[t]; }
+        for (int t = 0; t < m->ntr; ++t) { a.kappa_e[t] = a.nu_e; a.kappa[t] = c.Pr[t]; }
     }
     a.substep = sub != nullptr; a.has_zeta = sub && sub->has_zeta;
     a.store_G = !sub || sub->store_G;
@@ -3042,11 +3117,10 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
             if (sd < 3) a.loc[f][sd] = f < m->nf ? m->loc[f][sd] : 0;
         }
     if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
-    const int clo = m->has_smag ? (m->smag_unit_pr ? 2 : 3) : (m->has_amd ? 2 : (m->has_closure ? (m->vi ? 4 : 1) : 0));
     // closure terms on a grid without Flat directions: the z-marching form (ocn_epilogue_march.h) -- the union of the fields' ranges, one
     // column of halo around it readable
     const OcnOptions &o = m->opt;
-    if (epilogue_march_selected(m)) {
+    if (p.march) {
         Range6 R = a.r[0];
         for (int f = 1; f < m->nf; ++f) {
             R.i0 = std::min(R.i0, a.r[f].i0); R.i1 = std::max(R.i1, a.r[f].i1); R.j0 = std::min(R.j0, a.r[f].j0); R.j1 = std::max(R.j1, a.r[f].j1);
@@ -3066,14 +3140,9 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
                 for (int sd = 0; sd < 6; ++sd)
                     if ((a.any_flux && a.has_flux[f][sd]) || (with_flux && m->lin[f][sd].on)) mask |= 1 << sd;
             a.store_sides = mask;         // (a tendency that is not stored otherwise still is on those sides)
-#define OCN_EPM(COR, BUOY, CLO, NTR) hipLaunchKernelGGL((tendency_epilogue_march_kernel<COR, BUOY, CLO, NTR>), mg, mb, 0, g_stream, g, a, R, kchunk)
-#define OCN_EPM_N(COR, BUOY, CLO) do { if (m->ntr == 2) OCN_EPM(COR, BUOY, CLO, 2); else if (m->ntr == 1) OCN_EPM(COR, BUOY, CLO, 1); else OCN_EPM(COR, BUOY, CLO, 0); } while (0)
-#define OCN_EPM_CLO(COR, BUOY) do { if (clo == 3) OCN_EPM_N(COR, BUOY, 3); else if (clo == 2) OCN_EPM_N(COR, BUOY, 2); else OCN_EPM_N(COR, BUOY, 1); } while (0)
-            if (a.has_coriolis) { if (a.has_buoyancy) OCN_EPM_CLO(true, true); else OCN_EPM_CLO(true, false); }
-            else                { if (a.has_buoyancy) OCN_EPM_CLO(false, true); else OCN_EPM_CLO(false, false); }
-#undef OCN_EPM_CLO
-#undef OCN_EPM_N
-#undef OCN_EPM
+            const EpilogueMarchKernel march = epilogue_march_valid(p.clo, p.ntr) ? kEpilogueMarchKernels[epilogue_march_slot(p.cor, p.buoy, p.clo, p.ntr)] : nullptr;
+            if (!march) return fail(OCN_ESTATE, "no tendency_epilogue_march_kernel<COR %d, BUOY %d, CLO %d, NTR %d>", p.cor, p.buoy, p.clo, p.ntr);
+            hipLaunchKernelGGL(march, mg, mb, 0, g_stream, g, a, R, kchunk);
             KERNEL_CHECK();
             if (mask) {
                 SideList sl;
@@ -3090,50 +3159,11 @@ static int tendency_epilogue(ocn_model_s *m, const FusedSubstep *sub) {
             return OCN_OK;
         }
     }
-    const dim3 grd = grid3(nx, ny, nz * m->nf, BLK);
-    // ConstantCartesianCoriolis (1) / gravity_unit_vector (2; 4: of a SeawaterBuoyancy): the EXT instantiations, the only ones with these terms
-    const int ext = (m->has_cartesian ? 1 : 0) | (tilted_buoyancy(m) ? (m->buoyancy_kind == 2 ? 6 : 2) : 0);
-    if (ext) {
-#define OCN_EPX(COR, BUOY, CLO, EXT) hipLaunchKernelGGL((tendency_epilogue_kernel<COR, BUOY, CLO, EXT>), grd, BLK, 0, g_stream, g, a)
-#define OCN_EPX_CLO(COR, BUOY, EXT) do { if (clo == 4) OCN_EPX(COR, BUOY, 4, EXT); else if (clo == 3) OCN_EPX(COR, BUOY, 3, EXT); else if (clo == 2) OCN_EPX(COR, BUOY, 2, EXT); else if (clo == 1) OCN_EPX(COR, BUOY, 1, EXT); else OCN_EPX(COR, BUOY, 0, EXT); } while (0)
-        if (ext == 1)      { if (a.has_buoyancy) OCN_EPX_CLO(true, true, 1); else OCN_EPX_CLO(true, false, 1); }
-        else if (ext == 2) { if (a.has_coriolis) OCN_EPX_CLO(true, true, 2); else OCN_EPX_CLO(false, true, 2); }
-        else if (ext == 6) { if (a.has_coriolis) OCN_EPX_CLO(true, true, 6); else OCN_EPX_CLO(false, true, 6); }
-        else if (ext == 3) OCN_EPX_CLO(true, true, 3);
-        else               OCN_EPX_CLO(true, true, 7);
-#undef OCN_EPX_CLO
-#undef OCN_EPX
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-#define OCN_EPI(COR, BUOY, CLO) hipLaunchKernelGGL((tendency_epilogue_kernel<COR, BUOY, CLO>), grd, BLK, 0, g_stream, g, a)
-#define OCN_EPI_CLO(COR, BUOY) do { if (clo == 4) OCN_EPI(COR, BUOY, 4); else if (clo == 3) OCN_EPI(COR, BUOY, 3); else if (clo == 2) OCN_EPI(COR, BUOY, 2); else if (clo == 1) OCN_EPI(COR, BUOY, 1); else OCN_EPI(COR, BUOY, 0); } while (0)
-    if (a.has_coriolis) { if (a.has_buoyancy) OCN_EPI_CLO(true, true); else OCN_EPI_CLO(true, false); }
-    else                { if (a.has_buoyancy) OCN_EPI_CLO(false, true); else OCN_EPI_CLO(false, false); }
-#undef OCN_EPI_CLO
-#undef OCN_EPI
+    const EpilogueKernel kernel = epilogue_valid(p.cor, p.buoy, p.clo, p.ext) ? kEpilogueKernels[epilogue_slot(p.cor, p.buoy, p.clo, p.ext)] : nullptr;
+    if (!kernel) return fail(OCN_ESTATE, "no tendency_epilogue_kernel<COR %d, BUOY %d, CLO %d, EXT %d>", p.cor, p.buoy, p.clo, p.ext);
+    hipLaunchKernelGGL(kernel, grid3(nx, ny, nz * m->nf, BLK), BLK, 0, g_stream, g, a);
     KERNEL_CHECK();
     return OCN_OK;
-}
-
-// the one-pass epilogue runs whenever something follows the advective part: physics terms, valued or field-dependent Flux conditions
-static int count_linear_flux(const ocn_model_s *m) {
-    int n = 0;
-    for (int f = 0; f < m->nf; ++f)
-        for (int sd = 0; sd < 6; ++sd) n += m->lin[f][sd].on ? 1 : 0;
-    return n;
-}
-static bool epilogue_runs(const ocn_model_s *m) {
-    return m->opt.fused_epilogue && (has_physics(m) || m->any_flux_bc || m->any_linear_flux) && count_linear_flux(m) <= OCN_EPILOGUE_MAX_LIN;
-}
-static bool can_fuse_substep(const ocn_model_s *m) {
-    // without extra physics the substep rides in the fused advection kernel; with Coriolis / buoyancy / closure terms it rides in
-    // the epilogue pass that completes the tendencies (any advection path); a valued Flux condition is added after both
-    if (!m->opt.fuse_substep || !m->opt.swap_tendencies) return false;
-    if (has_forcing(m) && !forcing_in_role(m)) return false;         // the forcing pass completes G after the launch the substep would ride in
-    if (epilogue_runs(m)) return true;                               // the epilogue pass also applies the Flux conditions
-    if (has_background(m)) return false;                             // the second advection term follows the launch the substep would ride in
-    return !has_physics(m) && !m->any_flux_bc && !m->any_linear_flux && fused_path(m->opt, m->grid->d, nullptr, m->ntr, m->opt.tendency_impl);
 }
 
 extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) {
@@ -3143,25 +3173,26 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     if (!strcmp(key, "graph_replays")) { *value = m->graph_replays; return OCN_OK; }
     if (!strcmp(key, "graph_captures")) { *value = m->graph_captures; return OCN_OK; }
     if (!strcmp(key, "graph_failures")) { *value = m->graph_failures; return OCN_OK; }
-    if (!strcmp(key, "forcing_path")) { *value = forcing_path(m); return OCN_OK; }
+    const StepPlan p = plan(m);
+    if (!strcmp(key, "forcing_path")) { *value = p.forcing_path; return OCN_OK; }
     if (!strcmp(key, "background_fields")) { *value = count_background(m); return OCN_OK; }
-    if (!strcmp(key, "background_tendency_path")) { *value = background_tendency_path(m); return OCN_OK; }
-    if (!strcmp(key, "vertically_implicit")) { *value = m->vi ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "background_tendency_path")) { *value = p.background_path; return OCN_OK; }
+    if (!strcmp(key, "vertically_implicit")) { *value = m->closure.vi ? 1 : 0; return OCN_OK; }
     // coriolis = nothing (0) | FPlane (1) | ConstantCartesianCoriolis (2); whether the buoyancy has a gravity_unit_vector
-    if (!strcmp(key, "coriolis_kind")) { *value = m->has_cartesian ? 2 : (m->has_coriolis ? 1 : 0); return OCN_OK; }
-    if (!strcmp(key, "tilted_gravity")) { *value = tilted_buoyancy(m) ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "coriolis_kind")) { *value = (p.ext & 1) ? 2 : (p.cor ? 1 : 0); return OCN_OK; }
+    if (!strcmp(key, "tilted_gravity")) { *value = (p.ext & 2) ? 1 : 0; return OCN_OK; }
     // which epilogue adds the closure terms: the z-marching one (1) or the per-value one (0) -- the explicit part of a vertically implicit
     // discretisation exists in the per-value epilogue only
-    if (!strcmp(key, "epilogue_march_active")) { *value = (epilogue_runs(m) && epilogue_march_selected(m)) ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "epilogue_march_active")) { *value = p.march ? 1 : 0; return OCN_OK; }
     if (!strcmp(key, "implicit_step_form")) { *value = model_ivd_form(m); return OCN_OK; }
-    if (!strcmp(key, "fuse_substep_active")) { *value = can_fuse_substep(m) ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "fuse_substep_active")) { *value = p.fuse_substep ? 1 : 0; return OCN_OK; }
     // what the last time-step did on a triply periodic grid: the correction kernel wrote the halos (no fill launches), and the first RK3
     // substep rode in the pressure step's kernels
     if (!strcmp(key, "halo_fill_folded")) { *value = m->halo_fill_folded ? 1 : 0; return OCN_OK; }
     if (!strcmp(key, "stage1_source_fused")) { *value = m->stage1_source_fused ? 1 : 0; return OCN_OK; }
     // what the tendency LAUNCH itself carries (bench.py prices its bytes with these): the next stage's substep rides in the advection kernel
     // only without physics / Flux conditions (with them it rides in the epilogue pass); the tendency of the second stage is then not stored
-    if (!strcmp(key, "substep_in_tendency_kernel")) { *value = (can_fuse_substep(m) && !epilogue_runs(m)) ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "substep_in_tendency_kernel")) { *value = p.substep_in_advection ? 1 : 0; return OCN_OK; }
     // which path solve_for_pressure! takes on this model's solver: the real-transform path (option real_fft, plans that passed their check)
     // with the z transform fused into the spectral divide, and with the Z2D plan that writes into the haloed pressure field -- rocFFT
     // may refuse that plan, the solver then keeps the dense one. Both 0 on the complex path and on a partitioned model (its own solver)
@@ -3175,52 +3206,40 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     return fail(OCN_EINVAL, "unknown model option '%s'", key);
 }
 
-// update_state! (update_nonhydrostatic_model_state.jl:20-56)
-static int dist_update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub);
-static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub, const int *amd_range);
-// halos_current: the pressure step of the same time-step has just written every halo (pressure_step, fold_halos)
-static int update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub = nullptr, bool halos_current = false) {
-    if (m->dm) return dist_update_state(m, compute_tend, sub);
-    int rc = halos_current ? OCN_OK : fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, /*fill_open_bcs=*/false, m->any_bc ? m->bcs : nullptr);
-    if (rc) return rc;
-    return update_state_tail(m, compute_tend, sub, nullptr);
-}
 // everything of update_state! that follows the halo fill of the prognostic fields
 static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub, const int *amd_range) {
     const DGrid &g = m->grid->d;
+    const Coriolis &cor = m->coriolis;
+    const Buoyancy &b = m->buoyancy;
+    const Closure &c = m->closure;
     int rc;
     // the total velocities of a model with background velocities, from the halo-filled prognostic ones (whole parent arrays)
     if (has_background_velocity(m) && (rc = update_total_velocities(m))) return rc;
     // compute_auxiliaries!: compute_diffusivities! over :xyz (update_nonhydrostatic_model_state.jl:58-69), then
     // fill_halo_regions!(model.diffusivity_fields; only_local_halos = true) (:44) with the default ccc conditions
-    if (m->has_amd) {
-        if ((rc = amd_diffusivities(m->opt, g, m->Cnu, m->Ckappa, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->nu_e, m->kappa_e, amd_range))) return rc;
+    if (c.eddy()) {
+        // Smagorinsky: the buoyancy is the model's at this moment (nothing: N² = 0), and νₑ is the only field
+        if (c.kind == Closure::AMD)
+            rc = amd_diffusivities(m->opt, g, c.Cnu, c.Ckappa, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->nu_e, m->kappa_e, amd_range);
+        else
+            rc = smagorinsky_viscosity(m->opt, m->grid, c.C, c.Cb, c.lilly, b.kind, b.kind ? m->U[3 + b.bT] : nullptr, b.kind == 2 ? m->U[3 + b.S] : nullptr,
+                                       b.grav, b.alpha, b.beta, m->U[0], m->U[1], m->U[2], m->nu_e, amd_range);
+        if (rc) return rc;
+        const int nk = c.kind == Closure::AMD ? 1 + m->ntr : 1;
         double *K[OCN_MAX_FIELDS];
         int kl[OCN_MAX_FIELDS][3];
         K[0] = m->nu_e;
-        for (int t = 0; t < m->ntr; ++t) K[1 + t] = m->kappa_e[t];
-        for (int q = 0; q < 1 + m->ntr; ++q) memcpy(kl[q], LOC_C, sizeof(int) * 3);
+        for (int t = 0; t + 1 < nk; ++t) K[1 + t] = m->kappa_e[t];
+        for (int q = 0; q < nk; ++q) memcpy(kl[q], LOC_C, sizeof(int) * 3);
         // (on an x-slab rank amd_range includes i = 0 and Nx + 1: their z halo cell is filled too, the value a serial run's periodic x
         // fill copies there -- the reference's only_local_halos fill leaves it unwritten on a partitioned grid, halo_communication.jl:87-110)
-        if ((rc = fill_halo_regions(m->opt, m->grid, K, kl, 1 + m->ntr, true, m->any_kbc ? m->kbcs : nullptr, amd_range != nullptr))) return rc;
-    }
-    if (m->has_smag) {
-        // buoyancy is the model's at this moment (nothing: N² = 0); νₑ's halos as above, with the rank-edge z-halo column
-        const int bk = m->buoyancy_kind;
-        if ((rc = smagorinsky_viscosity(m->opt, m->grid, m->smag_C, m->smag_Cb, m->smag_lilly, bk, bk ? m->U[3 + m->bT_index] : nullptr,
-                                        bk == 2 ? m->U[3 + m->S_index] : nullptr, m->grav, m->alpha, m->beta, m->U[0], m->U[1], m->U[2], m->nu_e, amd_range)))
-            return rc;
-        double *K[1] = {m->nu_e};
-        int kl[1][3];
-        memcpy(kl[0], LOC_C, sizeof(int) * 3);
-        if ((rc = fill_halo_regions(m->opt, m->grid, K, kl, 1, true, m->any_kbc ? m->kbcs : nullptr, amd_range != nullptr))) return rc;
+        if ((rc = fill_halo_regions(m->opt, m->grid, K, kl, nk, true, m->any_kbc ? m->kbcs : nullptr, amd_range != nullptr))) return rc;
     }
     // compute_auxiliaries!: update_hydrostatic_pressure! (update_nonhydrostatic_model_state.jl:58-69)
-    if (m->buoyancy_kind &&
-        (rc = update_hydrostatic_pressure(g, m->buoyancy_kind, m->U[3 + m->bT_index], m->U[3 + m->S_index], m->grav, m->alpha, m->beta, m->pHY,
-                                          m->tilted, m->ghat[2])))
+    if (b.kind && (rc = update_hydrostatic_pressure(g, b.kind, m->U[3 + b.bT], m->U[3 + b.S], b.grav, b.alpha, b.beta, m->pHY, b.tilted, b.ghat[2])))
         return rc;
     if (compute_tend) {
+        const StepPlan p = plan(m);
         std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
         if (m->profile) {
             if (m->events_used == m->events.size()) {
@@ -3232,12 +3251,12 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
             ev = &m->events[m->events_used++];
             HIP_TRY(hipEventRecord(ev->first, g_stream));
         }
-        const bool physics = has_physics(m) || epilogue_runs(m);
-        if (has_background(m)) {
+        const bool physics = p.physics || p.epilogue;
+        if (p.background_path) {
             // G = - div(U + Ū, φ) - div(U, Φ̄) ... (nonhydrostatic_tendency_kernel_functions.jl:86-94,148-156,213-221,276-293): term 1 is
             // today's launch when no velocity has a background (U + ZeroField is U), else the split one with the totals; term 2 accumulates
             // over the fields that have a background (div(U, ::ZeroField) = 0). Neither carries the substep or the forcing: a substep rides
-            // in the epilogue pass that closes the cells after both terms, or not at all (can_fuse_substep).
+            // in the epilogue pass that closes the cells after both terms, or not at all (StepPlan::fuse_substep).
             if (sub && !physics) return fail(OCN_ESTATE, "fused substep requested in the advection launch of a model with background fields");
             int roles[OCN_MAX_FIELDS], nb = 0;
             for (int f = 0; f < m->nf; ++f) roles[f] = f;
@@ -3253,35 +3272,42 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
             if (!rc) rc = advective_terms(m->opt, g, adv, m->bg, m->Gn, roles, nb, nullptr, true, m->opt.tendency_impl);
         } else
         rc = compute_tendencies(m->opt, g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
-                                m->opt.tendency_impl, physics ? nullptr : sub, forcing_in_role(m) ? m->forcing_d : nullptr);
+                                m->opt.tendency_impl, physics ? nullptr : sub, p.forcing_path == 1 ? m->forcing_d : nullptr);
         if (ev) HIP_TRY(hipEventRecord(ev->second, g_stream));
         if (!rc && physics) {
-            if (epilogue_runs(m)) { if (has_physics(m) || sub) rc = tendency_epilogue(m, sub); }      // (Flux conditions alone and no substep: nothing to do)
+            if (p.epilogue) { if (p.physics || sub) rc = tendency_epilogue(m, p, sub); }      // (Flux conditions alone and no substep: nothing to do)
             else {
                 if (sub) return fail(OCN_ESTATE, "fused substep needs the fused epilogue");
                 // the reference's order: x/y_dot_g_b, f x U, the hydrostatic gradient, the closure
-                if (!rc && tilted_buoyancy(m))
-                    rc = add_buoyancy_acceleration(g, m->buoyancy_kind, m->U[3 + m->bT_index], m->U[3 + m->S_index], m->grav, m->alpha, m->beta,
-                                                   m->ghat[0], m->ghat[1], m->Gn[0], m->Gn[1], nullptr);
-                if (!rc && m->has_cartesian)
-                    rc = add_cartesian_coriolis(g, m->cfx, m->cfy, m->cfz, m->U[0], m->U[1], m->U[2], m->Gn[0], m->Gn[1], m->Gn[2], nullptr);
-                if (!rc && m->has_coriolis) rc = add_fplane_coriolis(g, m->fcor, m->U[0], m->U[1], m->Gn[0], m->Gn[1], nullptr);
-                if (!rc && m->buoyancy_kind) rc = add_hydrostatic_pressure_gradient(g, m->pHY, m->Gn[0], m->Gn[1], nullptr);
-                if (!rc && m->has_closure)
-                    rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->nu, m->kappa, m->Gn[0], m->Gn[1],
-                                            m->Gn[2], m->Gn + 3, nullptr, nullptr, nullptr, nullptr, m->vi);
-                if (!rc && m->has_amd)
-                    rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, 0.0, nullptr, m->Gn[0], m->Gn[1],
-                                            m->Gn[2], m->Gn + 3, nullptr, m->nu_e, m->kappa_e);
-                if (!rc && m->has_smag)
-                    rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, 0.0, nullptr, m->Gn[0], m->Gn[1],
-                                            m->Gn[2], m->Gn + 3, nullptr, m->nu_e, nullptr, m->Pr);
+                if (!rc && b.acts_tilted())
+                    rc = add_buoyancy_acceleration(g, b.kind, m->U[3 + b.bT], m->U[3 + b.S], b.grav, b.alpha, b.beta, b.ghat[0], b.ghat[1], m->Gn[0],
+                                                   m->Gn[1], nullptr);
+                if (!rc && cor.kind == Coriolis::CARTESIAN)
+                    rc = add_cartesian_coriolis(g, cor.fx, cor.fy, cor.fz, m->U[0], m->U[1], m->U[2], m->Gn[0], m->Gn[1], m->Gn[2], nullptr);
+                if (!rc && cor.kind == Coriolis::FPLANE) rc = add_fplane_coriolis(g, cor.f, m->U[0], m->U[1], m->Gn[0], m->Gn[1], nullptr);
+                if (!rc && b.kind) rc = add_hydrostatic_pressure_gradient(g, m->pHY, m->Gn[0], m->Gn[1], nullptr);
+                if (!rc && c.kind == Closure::SCALAR)
+                    rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, c.nu, c.kappa, m->Gn[0], m->Gn[1],
+                                            m->Gn[2], m->Gn + 3, nullptr, nullptr, nullptr, nullptr, c.vi);
+                if (!rc && c.eddy())                  // AMD: νₑ and every κₑ; Smagorinsky: νₑ and the Prandtl numbers
+                    rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, 0.0, nullptr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
+                                            m->nu_e, c.kind == Closure::AMD ? m->kappa_e : nullptr, c.kind == Closure::AMD ? nullptr : c.Pr);
             }
         }
-        // the last interior term: in the role kernel above, or one pass here (then no substep rides along: can_fuse_substep)
-        if (!rc && has_forcing(m) && !forcing_in_role(m)) rc = add_forcing(m);
+        // the last interior term: in the role kernel above, or one pass here (then no substep rides along: StepPlan::fuse_substep)
+        if (!rc && p.forcing_path == 3) rc = add_forcing(m);
     }
     return rc;
+}
+
+// update_state! (update_nonhydrostatic_model_state.jl:20-56)
+static int dist_update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub);
+// halos_current: the pressure step of the same time-step has just written every halo (pressure_step, fold_halos)
+static int update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub = nullptr, bool halos_current = false) {
+    if (m->dm) return dist_update_state(m, compute_tend, sub);
+    int rc = halos_current ? OCN_OK : fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, /*fill_open_bcs=*/false, m->any_bc ? m->bcs : nullptr);
+    if (rc) return rc;
+    return update_state_tail(m, compute_tend, sub, nullptr);
 }
 
 // compute_flux_bc_tendencies! (compute_nonhydrostatic_tendencies.jl:170-184): the time steppers call it right before a substep
@@ -3302,13 +3328,11 @@ static int compute_flux_bc_tendencies(ocn_model_s *m) {
 
 // compute_pressure_correction! (pressure_correction.jl:8-20)
 static int compute_pressure_correction(ocn_model_s *m) {
-    const DGrid &g = m->grid->d;
     int rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr);
     if (rc) return rc;
     if ((rc = solve_for_pressure(m->solver, m->U[0], m->U[1], m->U[2], m->p))) return rc;
     double *pp[1] = {m->p};
     const int pl[1][3] = {{OCN_CENTER, OCN_CENTER, OCN_CENTER}};
-    (void)g;
     return fill_halo_regions(m->opt, m->grid, pp, pl, 1, true);
 }
 
@@ -3401,24 +3425,19 @@ extern "C" int ocn_model_set_buoyancy(ocn_model_t m, int kind, int b_or_T_index,
     if (kind < 0 || kind > 2) return fail(OCN_EINVAL, "buoyancy kind must be 0 (nothing), 1 (BuoyancyTracer) or 2 (linear SeawaterBuoyancy)");
     if (kind && (b_or_T_index < 0 || b_or_T_index >= m->ntr)) return fail(OCN_EINVAL, "tracer index %d out of range", b_or_T_index);
     if (kind == 2 && (S_index < 0 || S_index >= m->ntr)) return fail(OCN_EINVAL, "tracer index %d out of range", S_index);
-    if (kind && !m->pHY) {
-        int P[3];
-        parent_size(m->grid->d, LOC_C, P);
-        const size_t bytes = (size_t)P[0] * P[1] * P[2] * sizeof(double);
-        HIP_TRY(dev_alloc((void **)&m->pHY, bytes));
-        HIP_TRY(hipMemsetAsync(m->pHY, 0, bytes, g_stream));
-    }
-    m->buoyancy_kind = kind; m->bT_index = b_or_T_index; m->S_index = kind == 2 ? S_index : b_or_T_index;
-    m->grav = grav; m->alpha = alpha; m->beta = beta;
+    int rc;
+    if (kind && (rc = alloc_parent_zeroed(m->grid, LOC_C, &m->pHY))) return rc;
+    Buoyancy b = m->buoyancy;               // the gravity_unit_vector stays: it has its own setter
+    b.kind = kind; b.bT = b_or_T_index; b.S = kind == 2 ? S_index : b_or_T_index;
+    b.grav = grav; b.alpha = alpha; b.beta = beta;
+    m->buoyancy = b;
     return OCN_OK;
 }
 
 extern "C" int ocn_model_set_coriolis(ocn_model_t m, int enabled, double f) {
     if (m) m->epoch += 1;
     if (!m) return fail(OCN_EINVAL, "NULL argument");
-    m->has_coriolis = enabled != 0;
-    m->fcor = f;
-    m->has_cartesian = false;               // the model has one Coriolis
+    m->coriolis = Coriolis{enabled ? Coriolis::FPLANE : Coriolis::NONE, f};
     return OCN_OK;
 }
 
@@ -3426,9 +3445,7 @@ extern "C" int ocn_model_set_cartesian_coriolis(ocn_model_t m, int enabled, doub
     if (m) m->epoch += 1;
     if (!m) return fail(OCN_EINVAL, "NULL argument");
     if (m->dm) return fail(OCN_ENOTSUP, "ConstantCartesianCoriolis is not served on a partitioned model");
-    m->has_cartesian = enabled != 0;
-    m->cfx = fx; m->cfy = fy; m->cfz = fz;
-    m->has_coriolis = false;                // the model has one Coriolis
+    m->coriolis = Coriolis{enabled ? Coriolis::CARTESIAN : Coriolis::NONE, 0.0, fx, fy, fz};
     return OCN_OK;
 }
 
@@ -3436,27 +3453,33 @@ extern "C" int ocn_model_set_gravity_unit_vector(ocn_model_t m, int enabled, dou
     if (m) m->epoch += 1;
     if (!m) return fail(OCN_EINVAL, "NULL argument");
     if (m->dm) return fail(OCN_ENOTSUP, "gravity_unit_vector is not served on a partitioned model");
-    if (!enabled) { m->tilted = false; m->ghat[0] = 0.0; m->ghat[1] = 0.0; m->ghat[2] = 1.0; return OCN_OK; }      // NegativeZDirection()
+    Buoyancy &b = m->buoyancy;
+    if (!enabled) { b.tilted = false; b.ghat[0] = 0.0; b.ghat[1] = 0.0; b.ghat[2] = 1.0; return OCN_OK; }      // NegativeZDirection()
     // validate_unit_vector (Grids/input_validation.jl:177-186): ex^2 + ey^2 + ez^2 ≈ 1, isapprox with rtol = sqrt(eps)
     const double n2 = gx * gx + gy * gy + gz * gz;
     if (!std::isfinite(gx) || !std::isfinite(gy) || !std::isfinite(gz) || !(std::fabs(n2 - 1.0) <= std::sqrt(DBL_EPSILON) * std::fmax(std::fabs(n2), 1.0)))
         return fail(OCN_EINVAL, "unit vector must satisfy gx^2 + gy^2 + gz^2 ≈ 1");
-    m->tilted = true;
-    m->ghat[0] = -gx; m->ghat[1] = -gy; m->ghat[2] = -gz;      // ĝ = -gravity_unit_vector (buoyancy_force.jl:52-54)
+    b.tilted = true;
+    b.ghat[0] = -gx; b.ghat[1] = -gy; b.ghat[2] = -gz;      // ĝ = -gravity_unit_vector (buoyancy_force.jl:52-54)
     return OCN_OK;
 }
 
+// closure = ScalarDiffusivity(ν = nu, κ = kappa[tracer]); replaces any other closure, and with all zeros it is closure = nothing
 extern "C" int ocn_model_set_closure(ocn_model_t m, double nu, const double *kappa) {
     if (m) m->epoch += 1;
     if (!m) return fail(OCN_EINVAL, "NULL argument");
     if (nu < 0) return fail(OCN_EINVAL, "viscosity must be non-negative");
-    m->nu = nu;
-    m->has_closure = nu != 0.0;
+    Closure c;
+    c.vi = m->closure.vi;                   // the time discretisation has its own setter (and is false with the closures this one replaces)
+    c.nu = nu;
+    bool any = nu != 0.0;
     for (int t = 0; t < m->ntr; ++t) {
-        m->kappa[t] = kappa ? kappa[t] : 0.0;
-        if (m->kappa[t] < 0) return fail(OCN_EINVAL, "diffusivity must be non-negative");
-        if (m->kappa[t] != 0.0) m->has_closure = true;
+        c.kappa[t] = kappa ? kappa[t] : 0.0;
+        if (c.kappa[t] < 0) return fail(OCN_EINVAL, "diffusivity must be non-negative");
+        any = any || c.kappa[t] != 0.0;
     }
+    c.kind = any ? Closure::SCALAR : Closure::NONE;
+    m->closure = c;
     return OCN_OK;
 }
 
@@ -3468,24 +3491,24 @@ extern "C" int ocn_model_set_vertically_implicit(ocn_model_t m, int enabled) {
     if (m) m->epoch += 1;
     NEED_INIT();
     if (!m) return fail(OCN_EINVAL, "NULL argument");
-    if (!enabled) { m->vi = false; return OCN_OK; }
+    if (!enabled) { m->closure.vi = false; return OCN_OK; }
     if (m->grid->d.tz != OCN_BOUNDED)
         return fail(OCN_EINVAL, "VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.");
-    if (m->has_amd || m->has_smag)
+    if (m->closure.eddy())
         return fail(OCN_ENOTSUP, "VerticallyImplicitTimeDiscretization is accelerated for ScalarDiffusivity with constant coefficients only");
     int rc = ivd_workspace(m->grid);       // (allocated here: not inside a captured step)
     if (rc) return rc;
-    m->vi = true;
+    m->closure.vi = true;
     return OCN_OK;
 }
 
 // implicit_step! of every prognostic field after its substep (runge_kutta_3.jl:185-200, quasi_adams_bashforth_2.jl:133-152); a field
 // whose coefficient is zero has the identity system
 static int implicit_step(ocn_model_s *m, double dt) {
-    if (!m->vi || !m->has_closure) return OCN_OK;
+    if (m->closure.kind != Closure::SCALAR || !m->closure.vi) return OCN_OK;
     const int form = model_ivd_form(m);
     for (int f = 0; f < m->nf; ++f) {
-        const double coef = f < 3 ? m->nu : m->kappa[f - 3];
+        const double coef = f < 3 ? m->closure.nu : m->closure.kappa[f - 3];
         if (coef == 0.0) continue;
         const int rc = implicit_step_z(m->grid, m->U[f], m->loc[f], coef, dt, form);
         if (rc) return rc;
@@ -3497,15 +3520,13 @@ static int implicit_step(ocn_model_s *m, double dt) {
 extern "C" int ocn_model_set_linear_flux_bc(ocn_model_t m, const char *name, int side, double a, double b, const char *dep) {
     if (!m || !name || !dep) return fail(OCN_EINVAL, "NULL argument");
     m->epoch += 1;
-    const int f = model_field_index(m, name), fd = model_field_index(m, dep);
+    const int f = field_index(m, name), fd = field_index(m, dep);
     if (f < 0 || fd < 0) return fail(OCN_EINVAL, "name %s not found in model.velocities or model.tracers.", f < 0 ? name : dep);
     int rc = validate_bc(m->grid->d, m->loc[f], side, OCN_BC_FLUX);
     if (rc) return rc;
-    const int d = side / 2;
     for (int q = 0; q < 3; ++q)
         if (m->loc[fd][q] != m->loc[f][q])
             return fail(OCN_ENOTSUP, "the field dependency %s must sit at the location of %s (identity interpolation to the boundary)", dep, name);
-    (void)d;
     m->bcs[f][side].kind = OCN_BC_FLUX; m->bcs[f][side].value = 0.0; m->bcs[f][side].array = nullptr;   // halos of a Flux side: zero gradient
     m->any_bc = true;
     m->lin[f][side].on = true; m->lin[f][side].dep = fd; m->lin[f][side].a = a; m->lin[f][side].b = b;
@@ -3521,17 +3542,11 @@ extern "C" int ocn_model_set_background_field(ocn_model_t m, const char *name, c
     if (m) m->epoch += 1;
     if (!m || !name) return fail(OCN_EINVAL, "NULL argument");
     if (m->dm) return fail(OCN_ENOTSUP, "background fields are not served on a partitioned model");
-    const int f = model_field_index(m, name);
+    const int f = field_index(m, name);
     if (f < 0) return fail(OCN_EINVAL, "background fields can be set on u, v, w and the tracers c0..c%d; got '%s'", m->ntr - 1, name);
-    if (f < 3 && parent && !m->tot[f]) {
-        // the total-velocity buffer of this component: made here, never inside a (captured) time-step
-        int P[3];
-        parent_size(m->grid->d, m->loc[f], P);
-        const size_t bytes = (size_t)P[0] * P[1] * P[2] * sizeof(double);
-        hipError_t e = dev_alloc((void **)&m->tot[f], bytes);
-        if (e != hipSuccess) { m->tot[f] = nullptr; return fail((int)e, "dev_alloc(total velocity): %s", hipGetErrorString(e)); }
-        HIP_TRY(hipMemsetAsync(m->tot[f], 0, bytes, g_stream));
-    }
+    // the total-velocity buffer of this component: made here, never inside a (captured) time-step
+    int rc;
+    if (f < 3 && parent && (rc = alloc_parent_zeroed(m->grid, m->loc[f], &m->tot[f]))) return rc;
     m->bg[f] = parent;
     return OCN_OK;
 }
@@ -3616,7 +3631,7 @@ extern "C" int ocn_model_set_forcing(ocn_model_t m, int field, const ocn_forcing
     return OCN_OK;
 }
 
-// closure = AnisotropicMinimumDissipation(Cν = Cnu, Cκ = Ckappa[tracer]; Cb = nothing); replaces a ScalarDiffusivity
+// closure = AnisotropicMinimumDissipation(Cν = Cnu, Cκ = Ckappa[tracer]; Cb = nothing); replaces any other closure
 extern "C" int ocn_model_set_amd(ocn_model_t m, double Cnu, const double *Ckappa) {
     if (m) m->epoch += 1;
     NEED_INIT();
@@ -3624,21 +3639,14 @@ extern "C" int ocn_model_set_amd(ocn_model_t m, double Cnu, const double *Ckappa
     const DGrid &g = m->grid->d;
     if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT)
         return fail(OCN_ENOTSUP, "AnisotropicMinimumDissipation needs a grid without Flat directions");
-    int P[3];
-    parent_size(g, LOC_C, P);
-    const size_t bytes = (size_t)P[0] * P[1] * P[2] * sizeof(double);
-    auto alloc0 = [&](double **p) -> int {
-        if (*p) return OCN_OK;
-        HIP_TRY(dev_alloc((void **)p, bytes));
-        HIP_TRY(hipMemsetAsync(*p, 0, bytes, g_stream));
-        return OCN_OK;
-    };
-    int rc = alloc0(&m->nu_e);
-    for (int t = 0; t < m->ntr && !rc; ++t) rc = alloc0(&m->kappa_e[t]);
+    int rc = alloc_parent_zeroed(m->grid, LOC_C, &m->nu_e);
+    for (int t = 0; t < m->ntr && !rc; ++t) rc = alloc_parent_zeroed(m->grid, LOC_C, &m->kappa_e[t]);
     if (rc) return rc;
-    m->has_amd = true; m->has_closure = false; m->has_smag = false; m->nu = 0.0; m->vi = false;
-    m->Cnu = Cnu;
-    for (int t = 0; t < m->ntr; ++t) { m->kappa[t] = 0.0; m->Ckappa[t] = Ckappa[t]; }
+    Closure c;
+    c.kind = Closure::AMD;
+    c.Cnu = Cnu;
+    for (int t = 0; t < m->ntr; ++t) c.Ckappa[t] = Ckappa[t];
+    m->closure = c;
     return OCN_OK;
 }
 
@@ -3653,16 +3661,13 @@ extern "C" int ocn_model_set_smagorinsky(ocn_model_t m, double C, double Cb, int
     if (!(C >= 0)) return fail(OCN_EINVAL, "the Smagorinsky coefficient must be non-negative");
     for (int t = 0; t < m->ntr; ++t)
         if (!(Pr[t] > 0)) return fail(OCN_EINVAL, "the Prandtl number must be positive");
-    if (!m->nu_e) {
-        int P[3];
-        parent_size(g, LOC_C, P);
-        const size_t bytes = (size_t)P[0] * P[1] * P[2] * sizeof(double);
-        HIP_TRY(dev_alloc((void **)&m->nu_e, bytes));
-        HIP_TRY(hipMemsetAsync(m->nu_e, 0, bytes, g_stream));
-    }
-    m->has_smag = true; m->has_amd = false; m->has_closure = false; m->nu = 0.0; m->vi = false;
-    m->smag_C = C; m->smag_Cb = Cb; m->smag_lilly = lilly != 0; m->smag_unit_pr = true;
-    for (int t = 0; t < m->ntr; ++t) { m->kappa[t] = 0.0; m->Pr[t] = Pr[t]; m->smag_unit_pr = m->smag_unit_pr && Pr[t] == 1.0; }
+    int rc = alloc_parent_zeroed(m->grid, LOC_C, &m->nu_e);
+    if (rc) return rc;
+    Closure c;
+    c.kind = Closure::SMAGORINSKY;
+    c.C = C; c.Cb = Cb; c.lilly = lilly != 0;
+    for (int t = 0; t < m->ntr; ++t) c.Pr[t] = Pr[t];
+    m->closure = c;
     return OCN_OK;
 }
 
@@ -3674,7 +3679,7 @@ static int model_set_bc(ocn_model_t m, const char *name, int side, int kind, dou
     // filled with them after compute_diffusivities!
     if (!strcmp(name, "nu_e") || (!strncmp(name, "kappa_e", 7) && name[7] >= '0' && name[7] <= '9' && !name[8])) {
         const int q = name[0] == 'n' ? 0 : 1 + (name[7] - '0');
-        if (q > 0 && m->has_smag) return fail(OCN_ESTATE, "a Smagorinsky closure has the eddy viscosity nu_e only");
+        if (q > 0 && m->closure.kind == Closure::SMAGORINSKY) return fail(OCN_ESTATE, "a Smagorinsky closure has the eddy viscosity nu_e only");
         if (q > m->ntr) return fail(OCN_EINVAL, "no tracer %d", q - 1);
         if (kind == OCN_BC_FLUX || kind == OCN_BC_OPEN) return fail(OCN_EINVAL, "a diffusivity field takes Value or Gradient conditions");
         int rcq = validate_bc(m->grid->d, LOC_C, side, kind);
@@ -3687,11 +3692,7 @@ static int model_set_bc(ocn_model_t m, const char *name, int side, int kind, dou
             for (int sd = 0; sd < 6; ++sd) m->any_kbc = m->any_kbc || m->kbcs[a][sd].kind != OCN_BC_DEFAULT;
         return OCN_OK;
     }
-    int f = -1;
-    if (!strcmp(name, "u")) f = 0;
-    else if (!strcmp(name, "v")) f = 1;
-    else if (!strcmp(name, "w")) f = 2;
-    else if (name[0] == 'c' && name[1] >= '0' && name[1] <= '9' && !name[2] && name[1] - '0' < m->ntr) f = 3 + (name[1] - '0');
+    const int f = field_index(m, name);
     if (f < 0) return fail(OCN_EINVAL, "boundary conditions can be set on u, v, w and the tracers c0..c%d; got '%s'", m->ntr - 1, name);
     int rc = validate_bc(m->grid->d, m->loc[f], side, kind);
     if (rc) return rc;
@@ -3731,8 +3732,6 @@ extern "C" int ocn_model_update_state(ocn_model_t m, int compute_tendencies_flag
 extern "C" int ocn_model_set_finalize(ocn_model_t m, int enforce_incompressibility) {
     NEED_INIT();
     if (!m) return fail(OCN_EINVAL, "NULL argument");
-    const DGrid &g = m->grid->d;
-    (void)g;
     int rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, true, m->any_bc ? m->bcs : nullptr);     // set!(ϕ, value); fill_halo_regions!(ϕ) per field
     if (rc) return rc;
     if ((rc = update_state(m, false))) return rc;
@@ -3778,7 +3777,7 @@ static int rk3_time_step(ocn_model_s *m, double dt) {
     // stages 2 and 3: rk3_substep! fused into the tendency evaluation that precedes it (the cell's new tendency and its
     // previous one are at hand when the cell is closed) -- possible when the fused kernel runs, tendencies are cached by
     // pointer swap and no Flux boundary condition is added to G after the kernel
-    const bool can_fuse = can_fuse_substep(m);
+    const bool can_fuse = plan(m).fuse_substep;
     // triply periodic grids: the first substep rides in the pressure step's source-term and correction kernels, and the correction kernel
     // of every stage leaves all halos current, so the update_state! that follows fills none (pressure_step)
     const bool fuse_stage1 = can_fuse_stage1_source(m), fold = can_fold_halo_fill(m);

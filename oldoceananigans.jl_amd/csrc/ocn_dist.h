@@ -666,8 +666,6 @@ static int dist_make_pressure_correction(ocn_model_s *m, double dt, bool start_h
     return pc(mid);
 }
 
-static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub, const int *amd_range);
-
 // update_state! (update_nonhydrostatic_model_state.jl:20-56) with the interior / buffer split of
 // interleave_communication_and_computation.jl:9-67 when the exchange overlaps the interior tendencies
 static int dist_update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub) {
