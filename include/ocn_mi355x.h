@@ -171,6 +171,20 @@ int ocn_add_fplane_coriolis(ocn_grid_t grid, double f, const double *u, const do
 int ocn_add_cartesian_coriolis(ocn_grid_t grid, double fx, double fy, double fz, const double *u, const double *v, const double *w,
                                double *Gu, double *Gv, double *Gw, const int *range);
 
+/* stokes_drift = UniformStokesDrift (StokesDrifts.jl:170-178; x_curl_Uˢ_cross_U, y_curl_Uˢ_cross_U, z_curl_Uˢ_cross_U, ∂t_uˢ, ∂t_vˢ), on
+ * tendencies that hold everything up to the closure term (nonhydrostatic_tendency_kernel_functions.jl:100-101,162-163,226-227):
+ *   G_u = (G_u + ℑxzᶠᵃᶜ(w) dzu_c[k]) + dtu_c[k],  G_v = (G_v + ℑyzᵃᶠᶜ(w) dzv_c[k]) + dtv_c[k],
+ *   G_w = (G_w + ((-ℑxzᶜᵃᶠ(u)) dzu_f[k] - ℑyzᵃᶜᶠ(v) dzv_f[k])) + 0
+ * with ℑxz = ℑz(ℑx ·) etc. (Operators/interpolation_operators.jl:8-15,50-56), the identity along a Flat direction; every operation a
+ * separate IEEE multiply or add. The six tables are DEVICE arrays indexed [k - 1]: ∂z_uˢ / ∂z_vˢ at the centres (Nz values) and at the
+ * faces (Nz + 1), ∂t_uˢ / ∂t_vˢ at the centres (Nz); they are read while the kernel runs and not copied. A NULL table is a table of zeros
+ * (the products are still formed, as the reference multiplies by its zerofunction). range_u / range_v / range_w: the cells of each
+ * velocity whose tendency is updated, within the interior; NULL = every cell of that field, the wall faces excluded. u, v, w with
+ * filled halos. */
+int ocn_add_stokes_drift(ocn_grid_t grid, const double *dzu_c, const double *dzu_f, const double *dzv_c, const double *dzv_f,
+                         const double *dtu_c, const double *dtv_c, const double *u, const double *v, const double *w, double *Gu, double *Gv,
+                         double *Gw, const int *range_u, const int *range_v, const int *range_w);
+
 /* buoyancy = BuoyancyForce(formulation; gravity_unit_vector) (BuoyancyFormulations/buoyancy_force.jl:47-54): with ĝ = -gravity_unit_vector,
  * G_u += x_dot_g_bᶠᶜᶜ = ghat_x ℑxᶠᵃᵃ(b), G_v += y_dot_g_bᶜᶠᶜ = ghat_y ℑyᵃᶠᵃ(b) (g_dot_b.jl:2-3; nonhydrostatic_tendency_kernel_functions.jl:
  * 95,157), b the buoyancy perturbation of `kind` as in ocn_update_hydrostatic_pressure (bT, S with filled halos); range as above. */
@@ -423,6 +437,18 @@ int ocn_model_set_cartesian_coriolis(ocn_model_t model, int enabled, double fx, 
  * ocn_model_get_option answers "tilted_gravity" (1 with a buoyancy and a gravity_unit_vector). Models with either of these two take the
  * per-value tendency epilogue: "epilogue_march_active" answers 0. */
 int ocn_model_set_gravity_unit_vector(ocn_model_t model, int enabled, double gx, double gy, double gz);
+/* stokes_drift = UniformStokesDrift(∂z_uˢ, ∂z_vˢ, ∂t_uˢ, ∂t_vˢ) of the model constructor (StokesDrifts.jl:125-178), evaluated by the caller
+ * per level: HOST tables, ∂z at the centres (Nz doubles) and at the faces (Nz + 1), ∂t at the centres (Nz); NULL = zeros. They are copied
+ * into device memory the model owns, ordered on the library stream; the call may come between time-steps and replaces any earlier drift
+ * whole. enabled = 0: stokes_drift = nothing, the model launches what it launched before (the tables are ignored). The terms follow the
+ * closure term and precede the forcing. OCN_EINVAL: NULL model, or a Flat z (a drift that varies with z needs a z direction); OCN_ENOTSUP:
+ * a partitioned model; a refused call leaves the model untouched. The tables hold one moment in time: a time-dependent drift is the
+ * caller's to refresh between time-steps (all stages of a step then see the same tables). ocn_model_get_option answers "stokes_drift"
+ * (0 / 1) and "stokes_path": 0 none, 1 a stand-alone pass (stokes_drift_kernel, after the stand-alone physics kernels: option
+ * fused_epilogue = 0, or more linear Flux conditions than the epilogue holds), 2 inside the per-value tendency epilogue (the default;
+ * "epilogue_march_active" then answers 0). */
+int ocn_model_set_stokes_drift(ocn_model_t model, int enabled, const double *dzu_c, const double *dzu_f, const double *dzv_c,
+                               const double *dzv_f, const double *dtu_c, const double *dtv_c);
 /* closure = ScalarDiffusivity(ν = nu, κ = kappa[tracer]) of the model constructor. The model has ONE closure: this replaces any other
  * (an AMD or Smagorinsky closure too: "nu_e" then answers OCN_ESTATE again); all zeros / NULL: closure = nothing */
 int ocn_model_set_closure(ocn_model_t model, double nu, const double *kappa);

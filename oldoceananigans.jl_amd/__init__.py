@@ -25,6 +25,7 @@ from .solvers import (FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver, ba
 from .simulations import (CFL, AdvectiveCFL, DiffusiveCFL, Callback, IterationInterval, NaNChecker, Simulation, TimeInterval, TimeStepWizard, cell_advection_timescale,
                           cell_diffusion_timescale, default_nan_checker, hasnan, new_time_step, reset, run, stop_iteration_exceeded,
                           stop_time_exceeded, wall_time_limit_exceeded)
+from .stokes_drifts import StokesDrift, UniformStokesDrift
 from . import kernels
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -136,6 +136,8 @@ SYMBOLS = {
     "ocn_add_fplane_coriolis": (C.c_int, [_vp, C.c_double, _vp, _vp, _vp, _vp, _ip]),
     "ocn_model_set_coriolis": (C.c_int, [_vp, C.c_int, C.c_double]),
     "ocn_add_cartesian_coriolis": (C.c_int, [_vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _ip]),
+    "ocn_add_stokes_drift": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _ip]),
+    "ocn_model_set_stokes_drift": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "ocn_add_buoyancy_acceleration": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _ip]),
     "ocn_update_hydrostatic_pressure_tilted": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     "ocn_model_set_cartesian_coriolis": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double]),

@@ -797,6 +797,32 @@ extern "C" int ocn_add_cartesian_coriolis(ocn_grid_t grid, double fx, double fy,
     return add_cartesian_coriolis(grid->d, fx, fy, fz, u, v, w, Gu, Gv, Gw, range);
 }
 
+// stokes_drift = UniformStokesDrift: G_u += x_curl_Uˢ_cross_U + ∂t_uˢ, G_v += y_curl_Uˢ_cross_U + ∂t_vˢ, G_w += z_curl_Uˢ_cross_U
+// (stokes_drift_kernel); `sd`: device tables, a null one is a table of zeros; each velocity over its own range
+static int add_stokes_drift(const DGrid &g, const StokesTables &sd, const double *u, const double *v, const double *w, double *Gu, double *Gv,
+                            double *Gw, const int *range_u, const int *range_v, const int *range_w) {
+    Range6 ru, rv, rw;
+    int rc;
+    // the averages read one cell beyond a range in every direction that is not Flat
+    if ((g.tx != OCN_FLAT && g.Hx < 1) || (g.ty != OCN_FLAT && g.Hy < 1) || (g.tz != OCN_FLAT && g.Hz < 1))
+        return fail(OCN_EINVAL, "the Stokes-drift terms need a halo of at least 1 in every direction that is not Flat");
+    if ((rc = check_range(g, range_u, &ru, LOC_U, true)) || (rc = check_range(g, range_v, &rv, LOC_V, true)) ||
+        (rc = check_range(g, range_w, &rw, LOC_W, true)))
+        return rc;
+    hipLaunchKernelGGL(stokes_drift_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, sd, make_view(g, u, LOC_U), make_view(g, v, LOC_V),
+                       make_view(g, w, LOC_W), make_view(g, Gu, LOC_U), make_view(g, Gv, LOC_V), make_view(g, Gw, LOC_W), ru, rv, rw);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+extern "C" int ocn_add_stokes_drift(ocn_grid_t grid, const double *dzu_c, const double *dzu_f, const double *dzv_c, const double *dzv_f,
+                                    const double *dtu_c, const double *dtv_c, const double *u, const double *v, const double *w, double *Gu,
+                                    double *Gv, double *Gw, const int *range_u, const int *range_v, const int *range_w) {
+    NEED_INIT();
+    if (!grid || !u || !v || !w || !Gu || !Gv || !Gw) return fail(OCN_EINVAL, "NULL argument");
+    return add_stokes_drift(grid->d, StokesTables{dzu_c, dzu_f, dzv_c, dzv_f, dtu_c, dtv_c}, u, v, w, Gu, Gv, Gw, range_u, range_v, range_w);
+}
+
 // buoyancy = BuoyancyForce(formulation; gravity_unit_vector): G_u += x_dot_g_b, G_v += y_dot_g_b (buoyancy_acceleration_kernel)
 static int add_buoyancy_acceleration(const DGrid &g, int kind, const double *bT, const double *S, double grav, double alpha, double beta,
                                      double ghat_x, double ghat_y, double *Gu, double *Gv, const int *range) {
@@ -2611,8 +2637,8 @@ static int dist_poisson_backward_yz(ocn_dist_poisson_t s, double *phi, bool keep
 // ---------------------------------------------------------------------------------------------------------------------
 struct DistModel;
 static void dist_model_free(DistModel *dm);
-// The physics of a model: ONE coriolis, ONE buoyancy, ONE closure. A setter assigns its value as a whole, so what replaces what follows from
-// the type; which kernels a step then launches is derived from the three in one place (plan, below).
+// The physics of a model: ONE coriolis, ONE buoyancy, ONE closure, ONE Stokes drift. A setter assigns its value as a whole, so what replaces
+// what follows from the type; which kernels a step then launches is derived from the four in one place (plan, below).
 struct Coriolis {
     enum Kind { NONE, FPLANE, CARTESIAN } kind = NONE;    // nothing | FPlane(f) | ConstantCartesianCoriolis(fx, fy, fz): "coriolis_kind" 0 / 1 / 2
     double f = 0.0, fx = 0.0, fy = 0.0, fz = 0.0;
@@ -2644,6 +2670,12 @@ struct Closure {
         return eddy() ? 2 : (kind == SCALAR ? (vi ? 4 : 1) : 0);
     }
 };
+struct StokesDrift {
+    // nothing | UniformStokesDrift: six per-level tables in ONE device block owned by the model (`block`; the views point into it)
+    bool on = false;
+    double *block = nullptr;
+    StokesTables tables = {};
+};
 struct ocn_model_s {
     ocn_grid_t grid;
     OcnOptions opt;                         // this model's options: the library defaults when it was created, then ocn_model_set_option
@@ -2671,6 +2703,7 @@ struct ocn_model_s {
     Coriolis coriolis;
     Buoyancy buoyancy;
     Closure closure;
+    StokesDrift stokes;
     double *nu_e = nullptr, *kappa_e[OCN_MAX_FIELDS] = {};   // diffusivity_fields.νₑ, .κₑ (ccc, with halos): allocated by the setters, kept
     // forcing = (name = F,) (ocn_forcing.h): host copy of the descriptors, the device-resident table the kernels read, the device copies
     // of the tables (per field and term: mask, target)
@@ -2702,6 +2735,7 @@ extern "C" int ocn_model_destroy(ocn_model_t m) {
     if (m->graph_exec) hipGraphExecDestroy(m->graph_exec);
     for (int f = 0; f < m->nf; ++f) { hipFree(m->U[f]); hipFree(m->U2[f]); hipFree(m->Gn[f]); hipFree(m->Gm[f]); }
     hipFree(m->pHY);
+    hipFree(m->stokes.block);
     for (int c = 0; c < 3; ++c) hipFree(m->tot[c]);
     hipFree(m->forcing_d);
     for (auto &f : m->forcing_tables)
@@ -2967,11 +3001,13 @@ static int count_linear_flux(const ocn_model_s *m) {
 // no device call. update_state_tail, tendency_epilogue, the time steppers and the report-only keys of ocn_model_get_option read it; none of
 // them derives a rule again.
 struct StepPlan {
-    bool physics;               // a Coriolis, buoyancy or closure term exists
+    bool physics;               // a Coriolis, buoyancy, closure or Stokes-drift term exists
     bool epilogue;              // the one-pass epilogue completes the tendencies (without it the stand-alone kernels add the physics terms)
     bool march;                 // ... in its z-marching form, tendency_epilogue_march_kernel (option "epilogue_march_active")
     bool cor, buoy;             // the template coordinates of the epilogue kernels (kEpilogueKernels, kEpilogueMarchKernels) ...
     int clo, ext, ntr;          // ... Closure::clo; EXT bits: 1 ConstantCartesianCoriolis, 2 gravity_unit_vector, 4 of a SeawaterBuoyancy
+    bool stokes;                // ... and STOKES: whether the Stokes terms follow the closure term (kEpilogueStokesKernels)
+    int stokes_path;            // which pass adds them (option "stokes_path"): 0 none, 1 stand-alone (stokes_drift_kernel), 2 the per-value epilogue
     bool fuse_substep;          // the RK3 substep of the next stage rides along (option "fuse_substep_active") ...
     bool substep_in_advection;  // ... in the advection kernel; otherwise in the epilogue (option "substep_in_tendency_kernel")
     // which pass adds the forcing term (option "forcing_path"): 0 none, 1 the role tendency kernel, 3 the standalone pass (add_forcing_kernel);
@@ -2987,14 +3023,17 @@ static StepPlan plan(const ocn_model_s *m) {
     p.cor = m->coriolis.kind != Coriolis::NONE; p.buoy = b.kind != 0; p.clo = m->closure.clo(m->ntr); p.ntr = m->ntr;
     // ConstantCartesianCoriolis (1) / gravity_unit_vector (2; 4: of a SeawaterBuoyancy): the EXT instantiations, the only ones with these terms
     p.ext = (m->coriolis.kind == Coriolis::CARTESIAN ? 1 : 0) | (b.acts_tilted() ? (b.kind == 2 ? 6 : 2) : 0);
-    p.physics = p.cor || p.buoy || p.clo != 0;
+    p.stokes = m->stokes.on;
+    p.physics = p.cor || p.buoy || p.clo != 0 || p.stokes;
     // the one-pass epilogue runs whenever something follows the advective part: physics terms, valued or field-dependent Flux conditions
     const bool flux = m->any_flux_bc || m->any_linear_flux;
     p.epilogue = o.fused_epilogue && (p.physics || flux) && count_linear_flux(m) <= OCN_EPILOGUE_MAX_LIN;
     // whether the closure terms take the z-marching epilogue (ocn_epilogue_march.h): a grid without Flat directions, at most two tracers, and
     // not the explicit part of a vertically implicit discretisation -- that variant exists in the per-value epilogue only, as do the terms of a
-    // ConstantCartesianCoriolis and of a buoyancy with a gravity_unit_vector
-    p.march = p.epilogue && o.epilogue_march && p.clo >= 1 && p.clo <= 3 && p.ext == 0 && m->ntr <= 2 && g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT;
+    // ConstantCartesianCoriolis, of a buoyancy with a gravity_unit_vector and of a Stokes drift
+    p.march = p.epilogue && o.epilogue_march && p.clo >= 1 && p.clo <= 3 && p.ext == 0 && !p.stokes && m->ntr <= 2 && g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT;
+    // the Stokes terms: inside the per-value epilogue (a fixed rule, no option), else one stand-alone pass after the stand-alone physics kernels
+    p.stokes_path = !p.stokes ? 0 : (p.epilogue ? 2 : 1);
     // the forcing term rides in the role tendency kernel (FORCE instantiation) when that kernel completes the tendency by itself: no physics
     // epilogue, no Flux condition, the role kernel on the whole single-GPU grid, reference arithmetic, Periodic z (the Bounded-z instantiation
     // spilled, ocn_tendency_roles.h) -- the configs[1]-plus-sponge case, which keeps the RK3 substep fused. Partitioned models (interior / strip launches) and everything else take the standalone pass.
@@ -3035,10 +3074,12 @@ static int add_forcing(ocn_model_s *m) {
 
 // The instantiations of the two epilogue kernels: one table per family, indexed by the plan's coordinates. The validity predicates are the
 // list of what exists -- a slot they refuse holds nullptr and its kernel is never instantiated.
-//   per value: COR x BUOY x CLO 0..4 x EXT, where EXT's bit 1 (ConstantCartesianCoriolis) needs COR, bit 2 (gravity_unit_vector) needs BUOY
-//              and bit 4 (... of a SeawaterBuoyancy) needs bit 2: EXT in {0, 1, 2, 3, 6, 7}, 20 + 40 kernels
+//   per value: COR x BUOY x CLO 0..4 x EXT x STOKES, where EXT's bit 1 (ConstantCartesianCoriolis) needs COR, bit 2 (gravity_unit_vector)
+//              needs BUOY and bit 4 (... of a SeawaterBuoyancy) needs bit 2: EXT in {0, 1, 2, 3, 6, 7}, 20 + 40 kernels, and as many again
+//              with the Stokes terms (STOKES, kEpilogueStokesKernels: their arguments end with the tables): 120
 //   marching:  COR x BUOY x CLO 1..3 x NTR 0..2, 36 kernels: no EXT terms and no vertically implicit variant (StepPlan::march)
 using EpilogueKernel = void (*)(DGrid, EpilogueArgs);
+using EpilogueStokesKernel = void (*)(DGrid, EpilogueStokesArgs);
 using EpilogueMarchKernel = void (*)(DGrid, EpilogueArgs, Range6, int);
 constexpr bool epilogue_valid(bool cor, bool buoy, int clo, int ext) { return clo >= 0 && clo <= 4 && ext >= 0 && ext <= 7 && (!(ext & 1) || cor) && (!(ext & 2) || buoy) && (!(ext & 4) || (ext & 2)); }
 constexpr bool epilogue_march_valid(int clo, int ntr) { return clo >= 1 && clo <= 3 && ntr >= 0 && ntr <= 2; }
@@ -3048,13 +3089,19 @@ template <int I> constexpr EpilogueKernel epilogue_kernel_at() {
     constexpr bool COR = I % 2 != 0, BUOY = I / 2 % 2 != 0; constexpr int EXT = I / 4 % 8, CLO = I / 32;          // (epilogue_slot)
     if constexpr (epilogue_valid(COR, BUOY, CLO, EXT)) return tendency_epilogue_kernel<COR, BUOY, CLO, EXT>; else return nullptr;
 }
+template <int I> constexpr EpilogueStokesKernel epilogue_stokes_kernel_at() {
+    constexpr bool COR = I % 2 != 0, BUOY = I / 2 % 2 != 0; constexpr int EXT = I / 4 % 8, CLO = I / 32;          // (epilogue_slot)
+    if constexpr (epilogue_valid(COR, BUOY, CLO, EXT)) return tendency_epilogue_kernel<COR, BUOY, CLO, EXT, true>; else return nullptr;
+}
 template <int I> constexpr EpilogueMarchKernel epilogue_march_kernel_at() {
     constexpr bool COR = I % 2 != 0, BUOY = I / 2 % 2 != 0; constexpr int NTR = I / 4 % 3, CLO = I / 12;          // (epilogue_march_slot)
     if constexpr (epilogue_march_valid(CLO, NTR)) return tendency_epilogue_march_kernel<COR, BUOY, CLO, NTR>; else return nullptr;
 }
 template <size_t... I> constexpr std::array<EpilogueKernel, sizeof...(I)> epilogue_kernels(std::index_sequence<I...>) { return {{epilogue_kernel_at<(int)I>()...}}; }
+template <size_t... I> constexpr std::array<EpilogueStokesKernel, sizeof...(I)> epilogue_stokes_kernels(std::index_sequence<I...>) { return {{epilogue_stokes_kernel_at<(int)I>()...}}; }
 template <size_t... I> constexpr std::array<EpilogueMarchKernel, sizeof...(I)> epilogue_march_kernels(std::index_sequence<I...>) { return {{epilogue_march_kernel_at<(int)I>()...}}; }
 static constexpr auto kEpilogueKernels = epilogue_kernels(std::make_index_sequence<epilogue_slot(true, true, 4, 7) + 1>{});
+static constexpr auto kEpilogueStokesKernels = epilogue_stokes_kernels(std::make_index_sequence<epilogue_slot(true, true, 4, 7) + 1>{});      // the STOKES half: same slots
 static constexpr auto kEpilogueMarchKernels = epilogue_march_kernels(std::make_index_sequence<epilogue_march_slot(true, true, 3, 2) + 1>{});
 
 // Coriolis, hydrostatic pressure gradient and closure terms of every field -- and, when `sub` is given, the RK3 substep of the next
@@ -3159,9 +3206,14 @@ static int tendency_epilogue(ocn_model_s *m, const StepPlan &p, const FusedSubst
             return OCN_OK;
         }
     }
-    const EpilogueKernel kernel = epilogue_valid(p.cor, p.buoy, p.clo, p.ext) ? kEpilogueKernels[epilogue_slot(p.cor, p.buoy, p.clo, p.ext)] : nullptr;
-    if (!kernel) return fail(OCN_ESTATE, "no tendency_epilogue_kernel<COR %d, BUOY %d, CLO %d, EXT %d>", p.cor, p.buoy, p.clo, p.ext);
-    hipLaunchKernelGGL(kernel, grid3(nx, ny, nz * m->nf, BLK), BLK, 0, g_stream, g, a);
+    if (!epilogue_valid(p.cor, p.buoy, p.clo, p.ext)) return fail(OCN_ESTATE, "no tendency_epilogue_kernel<COR %d, BUOY %d, CLO %d, EXT %d>", p.cor, p.buoy, p.clo, p.ext);
+    const int slot = epilogue_slot(p.cor, p.buoy, p.clo, p.ext);
+    if (p.stokes) {
+        EpilogueStokesArgs s;
+        static_cast<EpilogueArgs &>(s) = a;
+        s.sd = m->stokes.tables;
+        hipLaunchKernelGGL(kEpilogueStokesKernels[slot], grid3(nx, ny, nz * m->nf, BLK), BLK, 0, g_stream, g, s);
+    } else hipLaunchKernelGGL(kEpilogueKernels[slot], grid3(nx, ny, nz * m->nf, BLK), BLK, 0, g_stream, g, a);
     KERNEL_CHECK();
     return OCN_OK;
 }
@@ -3181,6 +3233,9 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     // coriolis = nothing (0) | FPlane (1) | ConstantCartesianCoriolis (2); whether the buoyancy has a gravity_unit_vector
     if (!strcmp(key, "coriolis_kind")) { *value = (p.ext & 1) ? 2 : (p.cor ? 1 : 0); return OCN_OK; }
     if (!strcmp(key, "tilted_gravity")) { *value = (p.ext & 2) ? 1 : 0; return OCN_OK; }
+    // stokes_drift = nothing (0) | UniformStokesDrift (1); which pass adds its terms: none (0), stokes_drift_kernel (1), the per-value epilogue (2)
+    if (!strcmp(key, "stokes_drift")) { *value = p.stokes ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "stokes_path")) { *value = p.stokes_path; return OCN_OK; }
     // which epilogue adds the closure terms: the z-marching one (1) or the per-value one (0) -- the explicit part of a vertically implicit
     // discretisation exists in the per-value epilogue only
     if (!strcmp(key, "epilogue_march_active")) { *value = p.march ? 1 : 0; return OCN_OK; }
@@ -3292,6 +3347,8 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
                 if (!rc && c.eddy())                  // AMD: νₑ and every κₑ; Smagorinsky: νₑ and the Prandtl numbers
                     rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, 0.0, nullptr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
                                             m->nu_e, c.kind == Closure::AMD ? m->kappa_e : nullptr, c.kind == Closure::AMD ? nullptr : c.Pr);
+                if (!rc && p.stokes_path == 1)        // after the closure, before the forcing
+                    rc = add_stokes_drift(g, m->stokes.tables, m->U[0], m->U[1], m->U[2], m->Gn[0], m->Gn[1], m->Gn[2], nullptr, nullptr, nullptr);
             }
         }
         // the last interior term: in the role kernel above, or one pass here (then no substep rides along: StepPlan::fuse_substep)
@@ -3461,6 +3518,47 @@ extern "C" int ocn_model_set_gravity_unit_vector(ocn_model_t m, int enabled, dou
         return fail(OCN_EINVAL, "unit vector must satisfy gx^2 + gy^2 + gz^2 ≈ 1");
     b.tilted = true;
     b.ghat[0] = -gx; b.ghat[1] = -gy; b.ghat[2] = -gz;      // ĝ = -gravity_unit_vector (buoyancy_force.jl:52-54)
+    return OCN_OK;
+}
+
+// stokes_drift = UniformStokesDrift(∂z_uˢ, ∂z_vˢ, ∂t_uˢ, ∂t_vˢ) (StokesDrifts.jl:125-178) as host tables per level: ∂z at centres (Nz) and faces
+// (Nz + 1), ∂t at centres (Nz); NULL: zeros. Replaces any earlier drift whole; enabled = 0 is stokes_drift = nothing. The tables are copied
+// into one device block of the model on the library stream; a refused call leaves the model untouched.
+extern "C" int ocn_model_set_stokes_drift(ocn_model_t m, int enabled, const double *dzu_c, const double *dzu_f, const double *dzv_c,
+                                          const double *dzv_f, const double *dtu_c, const double *dtv_c) {
+    NEED_INIT();
+    if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (m->dm) return fail(OCN_ENOTSUP, "a Stokes drift is not served on a partitioned model");
+    const DGrid &g = m->grid->d;
+    if (g.tz == OCN_FLAT) return fail(OCN_EINVAL, "a UniformStokesDrift varies with z: the grid needs a z direction");
+    StokesDrift sd;
+    if (enabled) {
+        const int Nz = g.Nz;
+        const double *src[6] = {dzu_c, dzu_f, dzv_c, dzv_f, dtu_c, dtv_c};
+        const int len[6] = {Nz, Nz + 1, Nz, Nz + 1, Nz, Nz};
+        std::vector<double> h((size_t)6 * Nz + 2, 0.0);
+        const double *view[6];
+        size_t off = 0;
+        for (int q = 0; q < 6; ++q) {
+            if (src[q]) memcpy(h.data() + off, src[q], sizeof(double) * len[q]);
+            off += len[q];
+        }
+        hipError_t e = dev_alloc((void **)&sd.block, h.size() * sizeof(double));
+        if (e != hipSuccess) return fail((int)e, "dev_alloc(stokes drift tables): %s", hipGetErrorString(e));
+        e = hipMemcpyAsync(sd.block, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, g_stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);          // `h` goes away; work already queued may still read the old block
+        if (e != hipSuccess) { hipFree(sd.block); return fail((int)e, "stokes drift tables: %s", hipGetErrorString(e)); }
+        off = 0;
+        for (int q = 0; q < 6; ++q) { view[q] = sd.block + off; off += len[q]; }
+        sd.tables = StokesTables{view[0], view[1], view[2], view[3], view[4], view[5]};
+        sd.on = true;
+    } else {
+        hipError_t e = hipStreamSynchronize(g_stream);
+        if (e != hipSuccess) return fail((int)e, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    }
+    hipFree(m->stokes.block);
+    m->stokes = sd;
+    m->epoch += 1;
     return OCN_OK;
 }
 

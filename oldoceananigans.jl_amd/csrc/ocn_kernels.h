@@ -1002,6 +1002,72 @@ __global__ void __launch_bounds__(256) buoyancy_acceleration_kernel(DGrid g, FVi
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// stokes_drift = UniformStokesDrift(∂z_uˢ, ∂z_vˢ, ∂t_uˢ, ∂t_vˢ) (StokesDrifts.jl:39-178): a horizontally uniform surface-wave field, held as
+// six per-level tables [k - 1]: ∂z_uˢ, ∂z_vˢ at centres (Nz) and at faces (Nz + 1), ∂t_uˢ, ∂t_vˢ at centres (Nz). A null table is a table
+// of zeros -- the product is still formed, as the reference multiplies by its zerofunction. x_curl_Uˢ_cross_U = ℑxzᶠᵃᶜ(w) ∂z_uˢ(z_c),
+// y_curl_Uˢ_cross_U = ℑyzᵃᶠᶜ(w) ∂z_vˢ(z_c), z_curl_Uˢ_cross_U = (-ℑxzᶜᵃᶠ(u)) ∂z_uˢ(z_f) - ℑyzᵃᶜᶠ(v) ∂z_vˢ(z_f) (:170-178) with ℑxz = ℑz(ℑx ·)
+// (Operators/interpolation_operators.jl:8-15,50-56; the identity along a Flat direction). The velocities are read through accessors
+// q(di, dj, dk) = value at (i + di, j + dj, k + dk), never called with an offset along a Flat direction: one body for the stand-alone kernel
+// and the epilogue. k is the same for every lane of a wave, so the table values are scalar loads.
+// ---------------------------------------------------------------------------------------------------------------------
+struct StokesTables {
+    const double *dzu_c, *dzu_f, *dzv_c, *dzv_f, *dtu_c, *dtv_c;
+};
+__device__ __forceinline__ double stokes_table(const double *t, int k) { return t ? t[k - 1] : 0.0; }
+template <class QW>
+__device__ __forceinline__ double x_curl_Us_cross_U(const DGrid &g, const StokesTables &sd, QW w, int k) {
+    const bool flx = g.tx == OCN_FLAT, flz = g.tz == OCN_FLAT;
+    auto X = [&](int dk) { return flx ? w(0, 0, dk) : 0.5 * (w(-1, 0, dk) + w(0, 0, dk)); };       // ℑxᶠᵃᵃ
+    return (flz ? X(0) : 0.5 * (X(0) + X(1))) * stokes_table(sd.dzu_c, k);                       // ℑzᵃᵃᶜ (:170-171)
+}
+template <class QW>
+__device__ __forceinline__ double y_curl_Us_cross_U(const DGrid &g, const StokesTables &sd, QW w, int k) {
+    const bool fly = g.ty == OCN_FLAT, flz = g.tz == OCN_FLAT;
+    auto Y = [&](int dk) { return fly ? w(0, 0, dk) : 0.5 * (w(0, -1, dk) + w(0, 0, dk)); };       // ℑyᵃᶠᵃ
+    return (flz ? Y(0) : 0.5 * (Y(0) + Y(1))) * stokes_table(sd.dzv_c, k);                       // ℑzᵃᵃᶜ (:173-174)
+}
+template <class QU, class QV>
+__device__ __forceinline__ double z_curl_Us_cross_U(const DGrid &g, const StokesTables &sd, QU u, QV v, int k) {
+    const bool flx = g.tx == OCN_FLAT, fly = g.ty == OCN_FLAT, flz = g.tz == OCN_FLAT;
+    auto X = [&](int dk) { return flx ? u(0, 0, dk) : 0.5 * (u(0, 0, dk) + u(1, 0, dk)); };        // ℑxᶜᵃᵃ
+    auto Y = [&](int dk) { return fly ? v(0, 0, dk) : 0.5 * (v(0, 0, dk) + v(0, 1, dk)); };        // ℑyᵃᶜᵃ
+    const double ua = flz ? X(0) : 0.5 * (X(-1) + X(0)), va = flz ? Y(0) : 0.5 * (Y(-1) + Y(0));   // ℑzᵃᵃᶠ
+    return (-ua) * stokes_table(sd.dzu_f, k) - va * stokes_table(sd.dzv_f, k);                   // (:176-178)
+}
+// G = ((G_rest + curl) + ∂t_Uˢ) of each velocity (nonhydrostatic_tendency_kernel_functions.jl:100-101,162-163,226-227; ∂t_wˢ = zero(grid))
+template <class QW>
+__device__ __forceinline__ double stokes_Gu(const DGrid &g, const StokesTables &sd, QW w, int k, double G) {
+    return (G + x_curl_Us_cross_U(g, sd, w, k)) + stokes_table(sd.dtu_c, k);
+}
+template <class QW>
+__device__ __forceinline__ double stokes_Gv(const DGrid &g, const StokesTables &sd, QW w, int k, double G) {
+    return (G + y_curl_Us_cross_U(g, sd, w, k)) + stokes_table(sd.dtv_c, k);
+}
+template <class QU, class QV>
+__device__ __forceinline__ double stokes_Gw(const DGrid &g, const StokesTables &sd, QU u, QV v, int k, double G) {
+    return (G + z_curl_Us_cross_U(g, sd, u, v, k)) + 0.0;
+}
+
+// the three terms on tendencies that hold everything up to the closure; each velocity over its own range, one thread per cell (i, j, k) of
+// all three (w[k], w[k + 1] feed both G_u and G_v)
+__global__ void __launch_bounds__(256) stokes_drift_kernel(DGrid g, StokesTables sd, FView u, FView v, FView w, FView Gu, FView Gv, FView Gw,
+                                                           Range6 ru, Range6 rv, Range6 rw) {
+    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = 1 + blockIdx.z;
+    if (i > g.Nx || j > g.Ny || k > g.Nz) return;
+    auto qu = [&](int di, int dj, int dk) { return u.at(i + di, j + dj, k + dk); };
+    auto qv = [&](int di, int dj, int dk) { return v.at(i + di, j + dj, k + dk); };
+    auto qw = [&](int di, int dj, int dk) { return w.at(i + di, j + dj, k + dk); };
+    if (i >= ru.i0 && i <= ru.i1 && j >= ru.j0 && j <= ru.j1 && k >= ru.k0 && k <= ru.k1)
+        Gu.at(i, j, k) = stokes_Gu(g, sd, qw, k, Gu.at(i, j, k));
+    if (i >= rv.i0 && i <= rv.i1 && j >= rv.j0 && j <= rv.j1 && k >= rv.k0 && k <= rv.k1)
+        Gv.at(i, j, k) = stokes_Gv(g, sd, qw, k, Gv.at(i, j, k));
+    if (i >= rw.i0 && i <= rw.i1 && j >= rw.j0 && j <= rw.j1 && k >= rw.k0 && k <= rw.k1)
+        Gw.at(i, j, k) = stokes_Gw(g, sd, qu, qv, k, Gw.at(i, j, k));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // One pass for everything that follows the advective part of the tendencies (nonhydrostatic_tendency_kernel_functions.jl:91-100,
 // 153-162,216-229,286-297): G = (((A - f×U) - ∇pHY′) - ∂ⱼτᵢⱼ) + 0 for every prognostic field, and -- optionally -- the RK3 substep
 // of the NEXT stage into the second set of prognostic arrays (the viscous stencils of neighbouring cells still read U). The
@@ -1087,8 +1153,14 @@ __device__ __forceinline__ double epilogue_flux_conditions(const DGrid &g, const
 // EXT (bits; 0: the kernel as it was): 1 -- the Coriolis term is ConstantCartesianCoriolis (with COR; then w has one too); 2 -- the buoyancy
 // has a gravity_unit_vector (with BUOY): x_dot_g_b / y_dot_g_b come first after the advective part, before Coriolis
 // (nonhydrostatic_tendency_kernel_functions.jl:95-97,157-159,222-223); 4 -- its buoyancy perturbation is g (α T - β S) instead of the tracer.
-template <bool COR, bool BUOY, int CLO, int EXT = 0>
-__global__ void __launch_bounds__(256) tendency_epilogue_kernel(DGrid g, EpilogueArgs a) {
+// STOKES: the terms of a UniformStokesDrift follow the closure term of each velocity. Their tables ride behind the arguments in a struct
+// of the STOKES instantiations only, so EpilogueArgs, the instantiations without the terms and every other kernel that takes it keep their
+// code (shared through a __device__ function instead, the scalar code of all 60 existing instantiations changed).
+struct EpilogueStokesArgs : EpilogueArgs { StokesTables sd; };
+template <bool STOKES> struct EpilogueArgsOf { typedef EpilogueArgs type; };
+template <> struct EpilogueArgsOf<true> { typedef EpilogueStokesArgs type; };
+template <bool COR, bool BUOY, int CLO, int EXT = 0, bool STOKES = false>
+__global__ void __launch_bounds__(256) tendency_epilogue_kernel(DGrid g, typename EpilogueArgsOf<STOKES>::type a) {
     // 0.66 ms at 256 x 256 x 128 with the configs[4] physics: ~200 loads per cell, bound on the address / L1 path (VALU busy < 50 %, 3.5 TB/s). Grids without
     // a Flat direction run tendency_epilogue_march_kernel (ocn_epilogue_march.h, 0.48 ms) instead; this kernel stays for the others and as its reference.
     const int f = blockIdx.z % a.n;
@@ -1113,15 +1185,18 @@ __global__ void __launch_bounds__(256) tendency_epilogue_kernel(DGrid g, Epilogu
         if (COR && !CART) G = G - x_f_cross_U(g, a.fcor, a.v, i, j, k);
         if (BUOY) G = G - hydrostatic_gradient_x(g, a.pHY, i, j, k);
         if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_U, false, VI>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
+        if constexpr (STOKES) G = stokes_Gu(g, a.sd, qw, k, G);
     } else if (f == 1) {
         if (TILT) G = G + y_dot_g_b(g, a.ghat_y, qb);
         if (COR && CART) G = G - y_f_cross_U_cartesian(g, a.cfx, a.cfz, qu, qw);
         if (COR && !CART) G = G - y_f_cross_U(g, a.fcor, a.u, i, j, k);
         if (BUOY) G = G - hydrostatic_gradient_y(g, a.pHY, i, j, k);
         if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_V, false, VI>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
+        if constexpr (STOKES) G = stokes_Gv(g, a.sd, qw, k, G);
     } else if (f == 2) {
         if (COR && CART) G = G - z_f_cross_U_cartesian(g, a.cfx, a.cfy, qu, qv);
         if (CLO && (VAR || a.nu != 0.0)) G = (G - closure_divergence<F_W, false, VI>(g, a.u, a.v, a.w, a.u, a.nu, i, j, k, VAR, a.nu_e)) + 0.0;
+        if constexpr (STOKES) G = stokes_Gw(g, a.sd, qu, qv, k, G);
     } else {
         const double kap = a.kappa[f - 3];
         if (CLO && (VAR || kap != 0.0))

@@ -144,6 +144,27 @@ def add_cartesian_coriolis(grid, coriolis, u, v, w, Gu, Gv, Gw, kernel_parameter
                                                      Gw.data, _range(kernel_parameters)))
 
 
+def add_stokes_drift(grid, stokes_drift, u, v, w, Gu, Gv, Gw, kernel_parameters=None, time=0.0):
+    """+ x_curl_Uˢ_cross_U + ∂t_uˢ, + y_curl_Uˢ_cross_U + ∂t_vˢ, + z_curl_Uˢ_cross_U of the u, v, w tendencies for stokes_drift =
+    UniformStokesDrift(...) evaluated at `time`, on tendencies that hold everything up to the closure term; kernel_parameters: one range for
+    all three velocities (None: each field's own cells, the wall faces excluded)"""
+    tables = stokes_drift.tables(grid, time)
+    L = _lib.lib()
+    block = C.c_void_p()
+    _lib.check(L.ocn_malloc(C.byref(block), sum(t.nbytes for t in tables)))
+    try:
+        ptrs, off = [], 0
+        for t in tables:                                 # the library reads DEVICE tables: one block, released after the launch has run
+            ptrs.append(C.c_void_p(block.value + off))
+            _lib.check(L.ocn_memcpy_h2d(ptrs[-1], t.ctypes.data_as(C.c_void_p), t.nbytes))
+            off += t.nbytes
+        r = _range(kernel_parameters)
+        _lib.check(L.ocn_add_stokes_drift(grid.handle, *ptrs, u.data, v.data, w.data, Gu.data, Gv.data, Gw.data, r, r, r))
+        _lib.check(L.ocn_sync())
+    finally:
+        L.ocn_free(block)
+
+
 def _buoyancy_arguments(buoyancy, tracers_by_name):
     """(kind, b or T, S, g, α, β, ĝ) of a formulation or a BuoyancyForce"""
     from .buoyancy import BuoyancyForce, BuoyancyTracer

@@ -36,12 +36,13 @@ class Clock:
 
 class NonhydrostaticModel:
     """NonhydrostaticModel(; grid, advection=WENO(), tracers=(:T, :S), timestepper=:RungeKutta3, coriolis, buoyancy, closure, forcing,
-    boundary_conditions, background_fields); BASELINE.json benchmarks the configuration with all of them = nothing. `forcing` takes the
-    closure-free forcings of forcings.py (Relaxation, Forcing(array), MultipleForcings / tuples); `background_fields` a dict or a
-    BackgroundFields of time-independent backgrounds (background_fields.py)."""
+    boundary_conditions, background_fields, stokes_drift); BASELINE.json benchmarks the configuration with all of them = nothing. `forcing`
+    takes the closure-free forcings of forcings.py (Relaxation, Forcing(array), MultipleForcings / tuples); `background_fields` a dict or a
+    BackgroundFields of time-independent backgrounds (background_fields.py); `stokes_drift` a time-independent UniformStokesDrift
+    (stokes_drifts.py)."""
 
     def __init__(self, grid, advection=None, tracers=("T", "S"), timestepper="RungeKutta3", buoyancy=None, coriolis=None,
-                 closure=None, forcing=None, boundary_conditions=None, background_fields=None):
+                 closure=None, forcing=None, boundary_conditions=None, background_fields=None, stokes_drift=None):
         if advection is None:
             advection = WENO()
         if not (isinstance(advection, WENO) and advection.order == 5 and advection.bounds is None):
@@ -64,6 +65,8 @@ class NonhydrostaticModel:
         tilted = force is not None and force.tilted
         if hasattr(grid, "local") and (tilted or isinstance(coriolis, ConstantCartesianCoriolis)):
             raise NotImplementedError("ConstantCartesianCoriolis and BuoyancyForce(gravity_unit_vector) are not served on partitioned grids")
+        from . import stokes_drifts as _stokes
+        _stokes.validate_stokes_drift(stokes_drift, grid)
         from .closures import AnisotropicMinimumDissipation, ScalarDiffusivity, Smagorinsky
         if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
             raise NotImplementedError("only closure = nothing | ScalarDiffusivity(ν, κ) | AnisotropicMinimumDissipation(C, Cν, Cκ) | "
@@ -100,6 +103,9 @@ class NonhydrostaticModel:
         self._has_background = self.background_fields is not None
         if not self._has_background:                     # BackgroundFields of ZeroFields: every entry None
             self.background_fields = _background.empty_background_fields(self.tracer_names)
+        # stokes_drift = UniformStokesDrift(...) (nonhydrostatic_model.jl:115-130): its per-level tables, settled on the host as well
+        self.stokes_drift = stokes_drift
+        self._stokes_tables = _stokes.regularize_stokes_drift(stokes_drift, grid, 0.0)
         self.handle = self._create_handle(grid, len(self.tracer_names))
         self.clock = Clock(self)
         V = namedtuple("Velocities", "u v w")
@@ -151,6 +157,9 @@ class NonhydrostaticModel:
             _lib.check(_lib.lib().ocn_model_set_closure(self.handle, closure.ν, kp))
             if is_vertically_implicit(closure):
                 _lib.check(_lib.lib().ocn_model_set_vertically_implicit(self.handle, 1))
+        if self._stokes_tables is not None:
+            dp = C.POINTER(C.c_double)
+            _lib.check(_lib.lib().ocn_model_set_stokes_drift(self.handle, 1, *[t.ctypes.data_as(dp) for t in self._stokes_tables]))
         if self._has_background:
             _background.upload(self, self.background_fields)                  # borrowed by the library: the Fields are kept here
         self._forcing_keep = []                          # device arrays of Forcing(array): owned (numpy) or borrowed (Field)
