@@ -80,6 +80,13 @@ int ocn_grid_create(ocn_grid_t *grid, const int N[3], const int H[3], const int 
                     double dx, double dy, double dz, const double *dzc, const double *dzf);
 int ocn_grid_destroy(ocn_grid_t grid);
 int ocn_grid_parent_size(ocn_grid_t grid, const int loc[3], int P[3]);    /* total_size, grid_utils.jl:138-169 */
+/* The node coordinates of the grid, which ocn_grid_create (spacings only) does not know: per direction grid.xᶠᵃᵃ[1], grid.xᶜᵃᵃ[1] and
+ * grid.xᶠᵃᵃ[N + 1] (x₀ of fractional_x_index at a Face / a Center, Fields/interpolate.jl:67-83,137-188; xᴸ and xᴿ of
+ * enforce_boundary_conditions, lagrangian_particle_advection.jl:158-164). zf / zc: HOST arrays of the Nz + 1 face and Nz centre nodes,
+ * required for a stretched z (znodes, :181-188), ignored for a regular one. Needed by ocn_interpolate_at, ocn_advect_particles and
+ * ocn_model_set_particles (OCN_ESTATE without it). */
+int ocn_grid_set_nodes(ocn_grid_t grid, const double first_face[3], const double first_center[3], const double last_face[3],
+                       const double *zf, const double *zc);
 
 /* ---------------------------------------------------------------- halo fills (BoundaryConditions/) -------------- */
 /* fill_halo_regions!(field) with the default boundary conditions of field_boundary_conditions.jl:15-25
@@ -184,6 +191,27 @@ int ocn_add_cartesian_coriolis(ocn_grid_t grid, double fx, double fy, double fz,
 int ocn_add_stokes_drift(ocn_grid_t grid, const double *dzu_c, const double *dzu_f, const double *dzv_c, const double *dzv_f,
                          const double *dtu_c, const double *dtv_c, const double *u, const double *v, const double *w, double *Gu, double *Gv,
                          double *Gw, const int *range_u, const int *range_v, const int *range_w);
+
+/* interpolate(X, field, (ℓx, ℓy, ℓz), grid) (Fields/interpolate.jl:272-336) at n points: out[p] = the trilinear interpolation of `field`
+ * (haloed, at `loc`, filled halos) at (x[p], y[p], z[p]). DEVICE pointers. FractionalIndices (:190-262) with a true division for the
+ * regular directions and index_binary_search / fractional_index (:30-59) over the nodes of a stretched z; interpolator (:298-310) with
+ * unsafe_trunc and the floored mod; _interpolate (:313-336): all eight products, summed left to right. Unlike the reference's @inbounds
+ * reads, every corner index is clamped into the parent array, and a NaN or infinite coordinate reads a defined cell (its result is NaN);
+ * the clamp changes nothing within one halo cell of the domain. One launch of particle_step_kernel. */
+int ocn_interpolate_at(ocn_grid_t grid, int n, const double *x, const double *y, const double *z, const double *field, const int loc[3],
+                       double *out);
+/* advect_lagrangian_particles! (Models/LagrangianParticleTracking/lagrangian_particle_advection.jl:118-223): x, y, z (DEVICE, n values) move
+ * in place by Δt with u, v, w interpolated at them, then enforce_boundary_conditions per direction (:10-46): Bounded bounces with the
+ * coefficient of restitution, clamped to the far wall; Periodic wraps with the floored mod; Flat stays. depths (DEVICE, or NULL):
+ * _advect_drogued_particles! (drogued_dynamics.jl:45-72) -- the velocities at (x, y, depths[p]), z unchanged. u, v, w with filled halos. */
+int ocn_advect_particles(ocn_grid_t grid, int n, double *x, double *y, double *z, const double *depths, double restitution, double dt,
+                         const double *u, const double *v, const double *w);
+/* The index computation of the two calls above on the HOST -- the same function the kernel runs (interpolator after fractional_x_index /
+ * fractional_index, Fields/interpolate.jl:30-83,298-308, with the clamp) -- for n coordinates along one direction with N cells, halo H,
+ * topology code topo, at a Face (face != 0) or a Center: idx[2 p], idx[2 p + 1] = i⁻, i⁺ and w[p] = ξ. first_node, spacing: x₀ and Δ of a
+ * regular direction; nodes: the HOST node table of a stretched one (N + 1 faces / N centres), else NULL. Needs no device and no ocn_init. */
+int ocn_particle_indices_host(int N, int H, int topo, int face, double first_node, double spacing, const double *nodes, int n,
+                              const double *coordinate, int *idx, double *w);
 
 /* buoyancy = BuoyancyForce(formulation; gravity_unit_vector) (BuoyancyFormulations/buoyancy_force.jl:47-54): with ĝ = -gravity_unit_vector,
  * G_u += x_dot_g_bᶠᶜᶜ = ghat_x ℑxᶠᵃᵃ(b), G_v += y_dot_g_bᶜᶠᶜ = ghat_y ℑyᵃᶠᵃ(b) (g_dot_b.jl:2-3; nonhydrostatic_tendency_kernel_functions.jl:
@@ -449,6 +477,27 @@ int ocn_model_set_gravity_unit_vector(ocn_model_t model, int enabled, double gx,
  * "epilogue_march_active" then answers 0). */
 int ocn_model_set_stokes_drift(ocn_model_t model, int enabled, const double *dzu_c, const double *dzu_f, const double *dzv_c,
                                const double *dzv_f, const double *dtu_c, const double *dtv_c);
+/* particles = LagrangianParticles(x, y, z; restitution, dynamics) of the model constructor (LagrangianParticleTracking.jl:41-102): HOST
+ * arrays of n values, copied into one device block the model owns, ordered on the library stream; replaces the earlier particles whole,
+ * their tracked properties included. depths (or NULL): dynamics = DroguedParticleDynamics(depths) (drogued_dynamics.jl:34-72). n = 0 with
+ * arrays: zero particles; n = 0 with x = y = z = depths = NULL: particles = nothing, the model launches what it launched before. With
+ * particles every RK3 stage ends with step_lagrangian_particles!(model, stage Δt) (runge_kutta_3.jl:128,144,167: γ¹Δt, (γ² + ζ²)Δt and the
+ * uncorrected (γ³ + ζ³)Δt) and an AB2 step with step_lagrangian_particles!(model, Δt) (quasi_adams_bashforth_2.jl:108): ONE launch that
+ * sets the tracked properties at the position before the move and then moves the particles with total_velocities(model)
+ * (nonhydrostatic_model.jl:265-266). OCN_EINVAL: NULL model, n < 0, a NULL array; OCN_ENOTSUP: a partitioned model; OCN_ESTATE: a grid
+ * without ocn_grid_set_nodes. A refused call leaves the model untouched. ocn_model_get_option answers "particles" (their number, or 0). */
+int ocn_model_set_particles(ocn_model_t model, int n, const double *x, const double *y, const double *z, double restitution,
+                            const double *depths);
+/* tracked_fields = (property = field,) (LagrangianParticleTracking.jl:89-102; update_lagrangian_particle_properties!,
+ * update_lagrangian_particle_properties.jl:6-36): before every move, particles.<property> = the model field `field_name` interpolated at
+ * the particles. field_name: "u", "v", "w", "c<n>", "p", "pHY", "nu_e" (as ocn_model_field). At most 8 properties; a property named again
+ * takes the new field. OCN_EINVAL: an unknown field, a ninth property, x / y / z as the property; OCN_ESTATE: no particles. */
+int ocn_model_track_particle_field(ocn_model_t model, const char *property, const char *field_name);
+/* particles.properties.<name> (fetch_output, LagrangianParticleTracking.jl:157-161; the checkpointed `:particles`, checkpointer.jl:60-66):
+ * "x", "y", "z", "depths" or a tracked property, n doubles to / from a HOST array, after everything queued on the library stream. */
+int ocn_model_particle_property(ocn_model_t model, const char *name, double *host_out);
+int ocn_model_set_particle_property(ocn_model_t model, const char *name, const double *host_in);
+int ocn_model_particle_count(ocn_model_t model, int *count);           /* length(particles) (:105); 0 for particles = nothing */
 /* closure = ScalarDiffusivity(ν = nu, κ = kappa[tracer]) of the model constructor. The model has ONE closure: this replaces any other
  * (an AMD or Smagorinsky closure too: "nu_e" then answers OCN_ESTATE again); all zeros / NULL: closure = nothing */
 int ocn_model_set_closure(ocn_model_t model, double nu, const double *kappa);

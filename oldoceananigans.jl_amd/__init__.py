@@ -26,6 +26,7 @@ from .simulations import (CFL, AdvectiveCFL, DiffusiveCFL, Callback, IterationIn
                           cell_diffusion_timescale, default_nan_checker, hasnan, new_time_step, reset, run, stop_iteration_exceeded,
                           stop_time_exceeded, wall_time_limit_exceeded)
 from .stokes_drifts import StokesDrift, UniformStokesDrift
+from .particles import DroguedParticleDynamics, LagrangianParticles, no_dynamics
 from . import kernels
 
 __all__ = [n for n in dir() if not n.startswith("_")]

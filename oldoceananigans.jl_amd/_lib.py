@@ -138,6 +138,15 @@ SYMBOLS = {
     "ocn_add_cartesian_coriolis": (C.c_int, [_vp, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _ip]),
     "ocn_add_stokes_drift": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _ip]),
     "ocn_model_set_stokes_drift": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ocn_grid_set_nodes": (C.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
+    "ocn_interpolate_at": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _ip, _vp]),
+    "ocn_advect_particles": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "ocn_particle_indices_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _dp, C.c_int, _dp, _ip, _dp]),
+    "ocn_model_set_particles": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_double, _dp]),
+    "ocn_model_track_particle_field": (C.c_int, [_vp, C.c_char_p, C.c_char_p]),
+    "ocn_model_particle_property": (C.c_int, [_vp, C.c_char_p, _dp]),
+    "ocn_model_set_particle_property": (C.c_int, [_vp, C.c_char_p, _dp]),
+    "ocn_model_particle_count": (C.c_int, [_vp, _ip]),
     "ocn_add_buoyancy_acceleration": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _ip]),
     "ocn_update_hydrostatic_pressure_tilted": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, _vp]),
     "ocn_model_set_cartesian_coriolis": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double]),

@@ -9,6 +9,8 @@ open) -- while the CONTENT follows the reference's layout: one entry per address
     NonhydrostaticModel/timestepper/G⁻/<field>/data
     NonhydrostaticModel/clock/{time, iteration, stage, last_Δt, last_stage_Δt}
     NonhydrostaticModel/grid/{size, halo}                (validated on restore)
+    NonhydrostaticModel/particles/<property>             every property of the model's LagrangianParticles (the checkpointed properties
+                                                         name :particles, checkpointer.jl:60-66); absent for particles = nothing
 
 `set_from_checkpoint` is `set!(model, filepath)`: copy the arrays, set the clock; the next time-step continues bit for bit where the
 checkpointed run would have gone (tests/test_gpu_parity.py::test_checkpoint_and_restore_continue_bit_identically).
@@ -41,6 +43,9 @@ def write_checkpoint(model, filepath):
     grid = model.grid.local if hasattr(model.grid, "local") else model.grid
     out[f"{ADDRESS}/grid/size"] = np.asarray(grid.size, dtype=np.int64)
     out[f"{ADDRESS}/grid/halo"] = np.asarray(grid.halo_size, dtype=np.int64)
+    if getattr(model, "particles", None) is not None:
+        for name in model.particles.property_names:
+            out[f"{ADDRESS}/particles/{name}"] = getattr(model.particles, name)
     np.savez(filepath, **out)
     return filepath if str(filepath).endswith(".npz") else str(filepath) + ".npz"
 
@@ -64,5 +69,12 @@ def set_from_checkpoint(model, filepath):
         _lib.check(_lib.lib().ocn_model_set_clock(model.handle, float(file[f"{ADDRESS}/clock/time"]), int(file[f"{ADDRESS}/clock/iteration"]),
                                                   int(file[f"{ADDRESS}/clock/stage"]), float(file[f"{ADDRESS}/clock/last_Δt"]),
                                                   float(file[f"{ADDRESS}/clock/last_stage_Δt"])))
+        if getattr(model, "particles", None) is not None:
+            for name in model.particles.property_names:
+                key = f"{ADDRESS}/particles/{name}"
+                if key in file:
+                    if file[key].shape != (len(model.particles),):
+                        raise ValueError("the checkpointed particles do not match the model's particles")
+                    model.particles.set(**{name: file[key]})
     # auxiliary state (halos, eddy diffusivities, hydrostatic pressure, the tendencies themselves) follows from the prognostic fields
     update_state(model, True)

@@ -10,6 +10,7 @@
 #include "ocn_epilogue_march.h"
 #include "ocn_forcing.h"
 #include "ocn_implicit_z.h"
+#include "ocn_particles.h"
 #include <hipfft/hipfft.h>
 #include <array>
 #include <cfloat>
@@ -170,6 +171,11 @@ struct ocn_grid_s {
     std::string advection_error;
     // scratch t of the vertically implicit solve (ocn_implicit_z.h), Nx Ny Nz, allocated on first use
     double *ivd_scratch = nullptr;
+    // node coordinates for particles and point interpolation (ocn_grid_set_nodes): the geometry the index computation reads; `znodes` holds
+    // the Nz + 1 face and Nz centre nodes of a stretched z on the device
+    PGeom pg = {};
+    bool has_nodes = false;
+    double *znodes = nullptr;
 };
 
 static void parent_size(const DGrid &g, const int loc[3], int P[3]) {
@@ -285,7 +291,43 @@ extern "C" int ocn_grid_destroy(ocn_grid_t grid) {
     if (!grid) return OCN_OK;
     hipFree(grid->tables);
     hipFree(grid->ivd_scratch);
+    hipFree(grid->znodes);
     delete grid;
+    return OCN_OK;
+}
+
+// the node coordinates of the grid (grid.xᶠᵃᵃ[1], grid.xᶜᵃᵃ[1], grid.xᶠᵃᵃ[Nx + 1] and so on per direction): what fractional_x_index / xnode
+// read (Fields/interpolate.jl:67-83,137-188). The grid is created from spacings; its origin arrives here. zf / zc: HOST arrays of the
+// Nz + 1 face and Nz centre nodes, needed for a stretched z and ignored for a regular one.
+extern "C" int ocn_grid_set_nodes(ocn_grid_t grid, const double first_face[3], const double first_center[3], const double last_face[3],
+                                  const double *zf, const double *zc) {
+    NEED_INIT();
+    if (!grid || !first_face || !first_center || !last_face) return fail(OCN_EINVAL, "NULL argument");
+    const DGrid &D = grid->d;
+    if (!grid->z_regular && (!zf || !zc)) return fail(OCN_EINVAL, "a stretched z needs its face and centre nodes");
+    PGeom pg = {};
+    const int N[3] = {D.Nx, D.Ny, D.Nz}, H[3] = {D.Hx, D.Hy, D.Hz}, T[3] = {D.tx, D.ty, D.tz};
+    const double d[3] = {D.dx, D.dy, grid->h_dzc[D.Hz]};
+    for (int q = 0; q < 3; ++q) {
+        pg.N[q] = N[q]; pg.H[q] = H[q]; pg.T[q] = T[q];
+        pg.f0[q] = first_face[q]; pg.c0[q] = first_center[q]; pg.d[q] = d[q];
+        pg.xL[q] = first_face[q]; pg.xR[q] = last_face[q];
+    }
+    double *zn = nullptr;
+    if (!grid->z_regular) {
+        const size_t nf = (size_t)D.Nz + 1, nc = (size_t)D.Nz;
+        hipError_t e = dev_alloc((void **)&zn, (nf + nc) * sizeof(double));
+        if (e != hipSuccess) return fail((int)e, "dev_alloc(z nodes): %s", hipGetErrorString(e));
+        e = hipMemcpy(zn, zf, nf * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(zn + nf, zc, nc * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(zn); return fail((int)e, "hipMemcpy(z nodes): %s", hipGetErrorString(e)); }
+        pg.zf = zn; pg.zc = zn + nf;
+    }
+    HIP_TRY(hipStreamSynchronize(g_stream));          // a launch already queued may still read the old table
+    hipFree(grid->znodes);
+    grid->znodes = zn;
+    grid->pg = pg;
+    grid->has_nodes = true;
     return OCN_OK;
 }
 
@@ -821,6 +863,63 @@ extern "C" int ocn_add_stokes_drift(ocn_grid_t grid, const double *dzu_c, const 
     NEED_INIT();
     if (!grid || !u || !v || !w || !Gu || !Gv || !Gw) return fail(OCN_EINVAL, "NULL argument");
     return add_stokes_drift(grid->d, StokesTables{dzu_c, dzu_f, dzv_c, dzv_f, dtu_c, dtv_c}, u, v, w, Gu, Gv, Gw, range_u, range_v, range_w);
+}
+
+// particles: one launch of particle_step_kernel (ocn_particles.h), one thread per particle, 256 per block
+static int launch_particles(const PGeom &pg, const ParticleStepArgs &a) {
+    if (a.n <= 0) return OCN_OK;
+    hipLaunchKernelGGL(particle_step_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, g_stream, pg, a);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+static int loc_bits(const int loc[3]) { return (loc[0] == OCN_FACE ? 1 : 0) | (loc[1] == OCN_FACE ? 2 : 0) | (loc[2] == OCN_FACE ? 4 : 0); }
+
+// interpolate(X, field, (ℓx, ℓy, ℓz), grid) (Fields/interpolate.jl:272-282) at n points; everything a DEVICE pointer
+extern "C" int ocn_interpolate_at(ocn_grid_t grid, int n, const double *x, const double *y, const double *z, const double *field,
+                                  const int loc[3], double *out) {
+    NEED_INIT();
+    if (!grid || !x || !y || !z || !field || !loc || !out) return fail(OCN_EINVAL, "NULL argument");
+    if (n < 0) return fail(OCN_EINVAL, "n must not be negative");
+    if (!grid->has_nodes) return fail(OCN_ESTATE, "the grid has no node coordinates: call ocn_grid_set_nodes");
+    for (int d = 0; d < 3; ++d)
+        if (loc[d] != OCN_CENTER && loc[d] != OCN_FACE) return fail(OCN_EINVAL, "loc[%d] must be OCN_CENTER or OCN_FACE", d);
+    ParticleStepArgs a = {};
+    a.n = n;
+    a.x = const_cast<double *>(x); a.y = const_cast<double *>(y); a.z = const_cast<double *>(z);        // advect = 0: read only
+    a.ntracked = 1;
+    a.tracked[0] = TrackedField{make_view(grid->d, field, loc), loc_bits(loc), out};
+    return launch_particles(grid->pg, a);
+}
+
+// advect_lagrangian_particles! (lagrangian_particle_advection.jl:195-223; drogued_dynamics.jl:45-72 with depths): x, y, z move in place
+// with velocities u, v, w (filled halos); with depths the velocities are taken at (x, y, depths[p]) and z stays
+extern "C" int ocn_advect_particles(ocn_grid_t grid, int n, double *x, double *y, double *z, const double *depths, double restitution,
+                                    double dt, const double *u, const double *v, const double *w) {
+    NEED_INIT();
+    if (!grid || !x || !y || !z || !u || !v || !w) return fail(OCN_EINVAL, "NULL argument");
+    if (n < 0) return fail(OCN_EINVAL, "n must not be negative");
+    if (!grid->has_nodes) return fail(OCN_ESTATE, "the grid has no node coordinates: call ocn_grid_set_nodes");
+    ParticleStepArgs a = {};
+    a.n = n; a.x = x; a.y = y; a.z = z; a.depths = depths; a.restitution = restitution; a.dt = dt; a.advect = 1;
+    a.u = make_view(grid->d, u, LOC_U); a.v = make_view(grid->d, v, LOC_V); a.w = make_view(grid->d, w, LOC_W);
+    return launch_particles(grid->pg, a);
+}
+
+// The index computation of the particle kernel on the HOST (the same function, particle_interpolator): no device, no ocn_init. For n
+// coordinates along direction `dir` of a direction with N cells, halo H and topology `topo`, at a Face (face != 0) or a Center: idx[2 p],
+// idx[2 p + 1] = the clamped corner indices i⁻, i⁺ and w[p] = ξ. first_node: the first node at that location; spacing: Δ; nodes: the node
+// table of a stretched direction (N + 1 faces or N centres) or NULL.
+extern "C" int ocn_particle_indices_host(int N, int H, int topo, int face, double first_node, double spacing, const double *nodes, int n,
+                                         const double *coordinate, int *idx, double *w) {
+    if (!coordinate || !idx || !w || n < 0 || N < 1 || H < 0) return fail(OCN_EINVAL, "invalid argument");
+    PGeom pg = {};
+    pg.N[2] = N; pg.H[2] = H; pg.T[2] = topo; pg.f0[2] = pg.c0[2] = first_node; pg.d[2] = spacing;
+    pg.zf = pg.zc = nodes;
+    for (int p = 0; p < n; ++p) {
+        const PInterp r = particle_interpolator(pg, 2, face != 0, coordinate[p]);
+        idx[2 * p] = r.lo; idx[2 * p + 1] = r.hi; w[p] = r.w;
+    }
+    return OCN_OK;
 }
 
 // buoyancy = BuoyancyForce(formulation; gravity_unit_vector): G_u += x_dot_g_b, G_v += y_dot_g_b (buoyancy_acceleration_kernel)
@@ -2676,6 +2775,16 @@ struct StokesDrift {
     double *block = nullptr;
     StokesTables tables = {};
 };
+struct Particles {
+    // nothing | LagrangianParticles: x | y | z | depths in ONE device block owned by the model, n doubles each (`depths` NULL without a
+    // DroguedParticleDynamics); per tracked property the particles' values (owned) and the slot of the model field it samples
+    bool on = false;
+    int n = 0;
+    double restitution = 1.0;
+    double *block = nullptr, *x = nullptr, *y = nullptr, *z = nullptr, *depths = nullptr;
+    int ntracked = 0;
+    struct Tracked { char property[48]; char field[16]; double **slot; const int *loc; double *values; } tracked[OCN_MAX_TRACKED] = {};
+};
 struct ocn_model_s {
     ocn_grid_t grid;
     OcnOptions opt;                         // this model's options: the library defaults when it was created, then ocn_model_set_option
@@ -2704,6 +2813,7 @@ struct ocn_model_s {
     Buoyancy buoyancy;
     Closure closure;
     StokesDrift stokes;
+    Particles particles;
     double *nu_e = nullptr, *kappa_e[OCN_MAX_FIELDS] = {};   // diffusivity_fields.νₑ, .κₑ (ccc, with halos): allocated by the setters, kept
     // forcing = (name = F,) (ocn_forcing.h): host copy of the descriptors, the device-resident table the kernels read, the device copies
     // of the tables (per field and term: mask, target)
@@ -2736,6 +2846,8 @@ extern "C" int ocn_model_destroy(ocn_model_t m) {
     for (int f = 0; f < m->nf; ++f) { hipFree(m->U[f]); hipFree(m->U2[f]); hipFree(m->Gn[f]); hipFree(m->Gm[f]); }
     hipFree(m->pHY);
     hipFree(m->stokes.block);
+    hipFree(m->particles.block);
+    for (int q = 0; q < m->particles.ntracked; ++q) hipFree(m->particles.tracked[q].values);
     for (int c = 0; c < 3; ++c) hipFree(m->tot[c]);
     hipFree(m->forcing_d);
     for (auto &f : m->forcing_tables)
@@ -3236,6 +3348,8 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     // stokes_drift = nothing (0) | UniformStokesDrift (1); which pass adds its terms: none (0), stokes_drift_kernel (1), the per-value epilogue (2)
     if (!strcmp(key, "stokes_drift")) { *value = p.stokes ? 1 : 0; return OCN_OK; }
     if (!strcmp(key, "stokes_path")) { *value = p.stokes_path; return OCN_OK; }
+    // particles = nothing (0) | LagrangianParticles: their number
+    if (!strcmp(key, "particles")) { *value = m->particles.on ? m->particles.n : 0; return OCN_OK; }
     // which epilogue adds the closure terms: the z-marching one (1) or the per-value one (0) -- the explicit part of a vertically implicit
     // discretisation exists in the per-value epilogue only
     if (!strcmp(key, "epilogue_march_active")) { *value = p.march ? 1 : 0; return OCN_OK; }
@@ -3562,6 +3676,128 @@ extern "C" int ocn_model_set_stokes_drift(ocn_model_t m, int enabled, const doub
     return OCN_OK;
 }
 
+// particles = LagrangianParticles(x, y, z; restitution, dynamics = DroguedParticleDynamics(depths) | no_dynamics) (LagrangianParticleTracking.jl:
+// 60-102) from HOST arrays of n values, copied into one device block of the model on the library stream; replaces the earlier particles
+// whole, their tracked properties included. n = 0 with arrays: zero particles (the model steps and launches nothing for them); n = 0 with
+// x = y = z = NULL: particles = nothing. A refused call leaves the model untouched.
+extern "C" int ocn_model_set_particles(ocn_model_t m, int n, const double *x, const double *y, const double *z, double restitution,
+                                       const double *depths) {
+    NEED_INIT();
+    if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (m->dm) return fail(OCN_ENOTSUP, "particles are not served on a partitioned model (they would have to migrate between ranks)");
+    if (n < 0) return fail(OCN_EINVAL, "the number of particles must not be negative");
+    const bool clear = n == 0 && !x && !y && !z && !depths;
+    if (!clear && (!x || !y || !z)) return fail(OCN_EINVAL, "NULL argument: x, y and z are arrays of n values");
+    if (!clear && !m->grid->has_nodes) return fail(OCN_ESTATE, "the grid has no node coordinates: call ocn_grid_set_nodes");
+    Particles P;
+    if (!clear) {
+        const size_t len = (size_t)n, arrays = depths ? 4 : 3;
+        hipError_t e = dev_alloc((void **)&P.block, (len * arrays + 1) * sizeof(double));
+        if (e != hipSuccess) return fail((int)e, "dev_alloc(particles): %s", hipGetErrorString(e));
+        const double *src[4] = {x, y, z, depths};
+        for (size_t q = 0; q < arrays && e == hipSuccess && len; ++q)
+            e = hipMemcpyAsync(P.block + q * len, src[q], len * sizeof(double), hipMemcpyHostToDevice, g_stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);          // the host arrays are the caller's; queued work may still read the old block
+        if (e != hipSuccess) { hipFree(P.block); return fail((int)e, "particles: %s", hipGetErrorString(e)); }
+        P.x = P.block; P.y = P.block + len; P.z = P.block + 2 * len; P.depths = depths ? P.block + 3 * len : nullptr;
+        P.on = true; P.n = n; P.restitution = restitution;
+    } else {
+        hipError_t e = hipStreamSynchronize(g_stream);
+        if (e != hipSuccess) return fail((int)e, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    }
+    hipFree(m->particles.block);
+    for (int q = 0; q < m->particles.ntracked; ++q) hipFree(m->particles.tracked[q].values);
+    m->particles = P;
+    m->epoch += 1;
+    return OCN_OK;
+}
+
+// tracked_fields = (property = field,) (LagrangianParticleTracking.jl:89-102): before every move the particles' `property` is set to the
+// model field `field_name` interpolated at them. field_name: "u", "v", "w", "c<n>", "p", "pHY" or "nu_e", looked up like ocn_model_field.
+// At most OCN_MAX_TRACKED (8) properties; naming a property again replaces its field.
+extern "C" int ocn_model_track_particle_field(ocn_model_t m, const char *property, const char *field_name) {
+    NEED_INIT();
+    if (!m || !property || !field_name) return fail(OCN_EINVAL, "NULL argument");
+    Particles &P = m->particles;
+    if (!P.on) return fail(OCN_ESTATE, "the model has no particles");
+    if (!property[0] || strlen(property) >= sizeof P.tracked[0].property || strlen(field_name) >= sizeof P.tracked[0].field)
+        return fail(OCN_EINVAL, "property or field name is empty or too long");
+    if (!strcmp(property, "x") || !strcmp(property, "y") || !strcmp(property, "z"))
+        return fail(OCN_EINVAL, "x, y and z are the particles' position, not tracked properties");
+    const bool served = field_index(m, field_name) >= 0 || !strcmp(field_name, "p") || !strcmp(field_name, "pHY") || !strcmp(field_name, "nu_e");
+    if (!served) return fail(OCN_EINVAL, "a tracked field is a velocity, a tracer c<n>, p, pHY or nu_e; got '%s'", field_name);
+    double **slot;
+    int *loc;
+    const int rc = field_lookup(m, field_name, &slot, &loc);
+    if (rc) return rc;
+    int q = 0;
+    while (q < P.ntracked && strcmp(P.tracked[q].property, property)) ++q;
+    if (q == OCN_MAX_TRACKED) return fail(OCN_EINVAL, "at most %d tracked properties", OCN_MAX_TRACKED);
+    if (q == P.ntracked) {
+        double *values = nullptr;
+        const size_t bytes = ((size_t)P.n + 1) * sizeof(double);
+        hipError_t e = dev_alloc((void **)&values, bytes);
+        if (e != hipSuccess) return fail((int)e, "dev_alloc(tracked property): %s", hipGetErrorString(e));
+        e = hipMemsetAsync(values, 0, bytes, g_stream);
+        if (e != hipSuccess) { hipFree(values); return fail((int)e, "hipMemset(tracked property): %s", hipGetErrorString(e)); }
+        P.tracked[q].values = values;
+        strcpy(P.tracked[q].property, property);
+        P.ntracked += 1;
+    }
+    strcpy(P.tracked[q].field, field_name);
+    P.tracked[q].slot = slot;
+    P.tracked[q].loc = loc;
+    m->epoch += 1;
+    return OCN_OK;
+}
+
+// "x" | "y" | "z" | "depths" | a tracked property -> the device array of n values
+static int particle_array(ocn_model_s *m, const char *name, double **ptr) {
+    Particles &P = m->particles;
+    if (!P.on) return fail(OCN_ESTATE, "the model has no particles");
+    *ptr = nullptr;
+    if (!strcmp(name, "x")) *ptr = P.x;
+    else if (!strcmp(name, "y")) *ptr = P.y;
+    else if (!strcmp(name, "z")) *ptr = P.z;
+    else if (!strcmp(name, "depths")) *ptr = P.depths;
+    else
+        for (int q = 0; q < P.ntracked; ++q)
+            if (!strcmp(P.tracked[q].property, name)) *ptr = P.tracked[q].values;
+    if (!*ptr) return fail(OCN_EINVAL, "the particles have no property '%s' on the device", name);
+    return OCN_OK;
+}
+
+// particles.properties.<name> -> host_out (n doubles), after everything queued on the library stream
+extern "C" int ocn_model_particle_property(ocn_model_t m, const char *name, double *host_out) {
+    NEED_INIT();
+    if (!m || !name || !host_out) return fail(OCN_EINVAL, "NULL argument");
+    double *src;
+    const int rc = particle_array(m, name, &src);
+    if (rc) return rc;
+    if (m->particles.n) HIP_TRY(hipMemcpyAsync(host_out, src, (size_t)m->particles.n * sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return OCN_OK;
+}
+
+extern "C" int ocn_model_set_particle_property(ocn_model_t m, const char *name, const double *host_in) {
+    NEED_INIT();
+    if (!m || !name || !host_in) return fail(OCN_EINVAL, "NULL argument");
+    double *dst;
+    const int rc = particle_array(m, name, &dst);
+    if (rc) return rc;
+    if (m->particles.n) HIP_TRY(hipMemcpyAsync(dst, host_in, (size_t)m->particles.n * sizeof(double), hipMemcpyHostToDevice, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    m->epoch += 1;
+    return OCN_OK;
+}
+
+// length(particles); 0 for particles = nothing
+extern "C" int ocn_model_particle_count(ocn_model_t m, int *count) {
+    if (!m || !count) return fail(OCN_EINVAL, "NULL argument");
+    *count = m->particles.on ? m->particles.n : 0;
+    return OCN_OK;
+}
+
 // closure = ScalarDiffusivity(ν = nu, κ = kappa[tracer]); replaces any other closure, and with all zeros it is closure = nothing
 extern "C" int ocn_model_set_closure(ocn_model_t m, double nu, const double *kappa) {
     if (m) m->epoch += 1;
@@ -3863,6 +4099,25 @@ static int cache_previous_tendencies(ocn_model_s *m) {
     return OCN_OK;
 }
 
+// step_lagrangian_particles!(model, Δt) (LagrangianParticleTracking.jl:138-149), after a stage's update_state!: one launch, none without
+// particles. It reads m->U -- the stage's corrected, halo-filled fields -- so where the next substep rode in the tendency launch (it wrote
+// U2) the call comes BEFORE the two sets swap. The total velocities are the ones update_state! has just formed.
+static int step_particles(ocn_model_s *m, double dt) {
+    const Particles &P = m->particles;
+    if (!P.on || P.n == 0) return OCN_OK;
+    const DGrid &g = m->grid->d;
+    ParticleStepArgs a = {};
+    a.n = P.n; a.x = P.x; a.y = P.y; a.z = P.z; a.depths = P.depths; a.restitution = P.restitution; a.dt = dt; a.advect = 1;
+    a.u = make_view(g, total_velocity(m, 0), LOC_U); a.v = make_view(g, total_velocity(m, 1), LOC_V); a.w = make_view(g, total_velocity(m, 2), LOC_W);
+    a.ntracked = P.ntracked;
+    for (int q = 0; q < P.ntracked; ++q) {
+        const double *field = *P.tracked[q].slot;
+        if (!field) return fail(OCN_ESTATE, "the tracked field %s does not exist any more", P.tracked[q].field);
+        a.tracked[q] = TrackedField{make_view(g, field, P.tracked[q].loc), loc_bits(P.tracked[q].loc), P.tracked[q].values};
+    }
+    return launch_particles(m->grid->pg, a);
+}
+
 // time_step!(model::AbstractModel{<:RungeKutta3TimeStepper}, Δt) (TimeSteppers/runge_kutta_3.jl:93-170)
 static int rk3_time_step(ocn_model_s *m, double dt) {
     const DGrid &g = m->grid->d;
@@ -3902,9 +4157,13 @@ static int rk3_time_step(ocn_model_s *m, double dt) {
             FusedSubstep sub{m->U2, m->Gm, dt, gam[stage + 1], zet[stage + 1], 1};
             sub.store_G = stage != 1 || !m->opt.skip_dead_tendency_store;        // G(U²): read by the third stage's substep only
             if ((rc = update_state(m, true, &sub, fold))) return rc;
+            if ((rc = step_particles(m, sdt[stage]))) return rc;         // before the swap: the particles see this stage's fields
             for (int f = 0; f < m->nf; ++f) std::swap(m->U[f], m->U2[f]);
             substep_done = true;
-        } else if ((rc = update_state(m, true, nullptr, fold))) return rc;
+        } else {
+            if ((rc = update_state(m, true, nullptr, fold))) return rc;
+            if ((rc = step_particles(m, sdt[stage]))) return rc;         // runge_kutta_3.jl:128,144,167: the third with (γ³ + ζ³)Δt
+        }
     }
     return OCN_OK;
 }
@@ -3993,7 +4252,8 @@ extern "C" int ocn_model_time_step_ab2(ocn_model_t m, double dt, double chi, int
     m->halo_fill_folded = fold;
     if ((rc = pressure_step(m, dt, true, true, nullptr, fold))) return rc;
     if ((rc = cache_previous_tendencies(m))) return rc;
-    return update_state(m, true, nullptr, fold);
+    if ((rc = update_state(m, true, nullptr, fold))) return rc;
+    return step_particles(m, dt);                                                          // quasi_adams_bashforth_2.jl:108
 }
 
 // reset!(model.clock) + reset!(model.timestepper) (TimeSteppers/clock.jl reset!, runge_kutta_3.jl / quasi_adams_bashforth_2.jl reset!):

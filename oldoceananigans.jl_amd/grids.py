@@ -309,6 +309,18 @@ class RectilinearGrid:
                 C.byref(h), _lib.i3(self.size), _lib.i3(self.halo_size), _lib.i3([_topo_code(t) for t in self.topology]),
                 (C.c_double * 3)(self.Lx, self.Ly, self.Lz), self.Δxᶜᵃᵃ, self.Δyᵃᶜᵃ, self._dz, zc, zf))
             self._handle = h
+            # the node coordinates (the library's grid is made of spacings): what interpolation and particles read
+            H, N = self.halo_size, self.size
+            F, Cn = (self.xᶠᵃᵃ, self.yᵃᶠᵃ, self.zᵃᵃᶠ), (self.xᶜᵃᵃ, self.yᵃᶜᵃ, self.zᵃᵃᶜ)
+            flat = [t is Flat for t in self.topology]
+            d3 = lambda v: (C.c_double * 3)(*[float(a) for a in v])                        # noqa: E731
+            zf = zc = None
+            if not self.z_regular:
+                self._znodes = (np.ascontiguousarray(self.zᵃᵃᶠ[self.Hz:self.Hz + self.Nz + 1]), np.ascontiguousarray(self.zᵃᵃᶜ[self.Hz:self.Hz + self.Nz]))
+                zf, zc = (a.ctypes.data_as(dp) for a in self._znodes)
+            _lib.check(_lib.lib().ocn_grid_set_nodes(
+                h, d3(F[d][0 if flat[d] else H[d]] for d in range(3)), d3(Cn[d][0 if flat[d] else H[d]] for d in range(3)),
+                d3(F[d][0 if flat[d] else H[d] + N[d]] for d in range(3)), zf, zc))
         return self._handle
 
     @property

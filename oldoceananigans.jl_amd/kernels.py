@@ -2,6 +2,8 @@
 hot-path kernel of the reference."""
 import ctypes as C
 
+import numpy as np
+
 from . import _lib
 from .fields import _loc_array, _ptr_array
 
@@ -163,6 +165,61 @@ def add_stokes_drift(grid, stokes_drift, u, v, w, Gu, Gv, Gw, kernel_parameters=
         _lib.check(L.ocn_sync())
     finally:
         L.ocn_free(block)
+
+
+class _DeviceVectors:
+    """host vectors in one device block for the length of a raw launch"""
+
+    def __init__(self, arrays):
+        self.arrays = [None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in arrays]
+        self.block, self.ptrs = C.c_void_p(), []
+        L = _lib.lib()
+        _lib.check(L.ocn_malloc(C.byref(self.block), sum(a.nbytes for a in self.arrays if a is not None) + 8))
+        off = 0
+        try:
+            for a in self.arrays:
+                if a is None:
+                    self.ptrs.append(None)
+                    continue
+                self.ptrs.append(C.c_void_p(self.block.value + off))
+                if a.nbytes:
+                    _lib.check(L.ocn_memcpy_h2d(self.ptrs[-1], a.ctypes.data_as(C.c_void_p), a.nbytes))
+                off += a.nbytes
+        except Exception:
+            self.free()
+            raise
+
+    def read(self, q):
+        out = np.empty_like(self.arrays[q])
+        if out.nbytes:
+            _lib.check(_lib.lib().ocn_memcpy_d2h(out.ctypes.data_as(C.c_void_p), self.ptrs[q], out.nbytes))
+        return out
+
+    def free(self):
+        _lib.lib().ocn_free(self.block)
+
+
+def interpolate(grid, field, x, y, z):
+    """interpolate((x, y, z), field, location(field), grid) (Fields/interpolate.jl:272-336) at the points x[p], y[p], z[p] -> numpy array;
+    the field with filled halos"""
+    x = np.asarray(x, dtype=np.float64)
+    d = _DeviceVectors([x, y, z, np.zeros_like(x)])
+    try:
+        _lib.check(_lib.lib().ocn_interpolate_at(grid.handle, x.size, *d.ptrs[:3], field.data, _lib.i3(field.loc_codes), d.ptrs[3]))
+        return d.read(3)
+    finally:
+        d.free()
+
+
+def advect_particles(grid, x, y, z, u, v, w, Δt, restitution=1.0, depths=None):
+    """advect_lagrangian_particles! (lagrangian_particle_advection.jl:195-223; with depths: drogued_dynamics.jl:45-72) -> the new (x, y, z)"""
+    x = np.asarray(x, dtype=np.float64)
+    d = _DeviceVectors([x, y, z, depths])
+    try:
+        _lib.check(_lib.lib().ocn_advect_particles(grid.handle, x.size, *d.ptrs, float(restitution), float(Δt), u.data, v.data, w.data))
+        return d.read(0), d.read(1), d.read(2)
+    finally:
+        d.free()
 
 
 def _buoyancy_arguments(buoyancy, tracers_by_name):

@@ -36,13 +36,13 @@ class Clock:
 
 class NonhydrostaticModel:
     """NonhydrostaticModel(; grid, advection=WENO(), tracers=(:T, :S), timestepper=:RungeKutta3, coriolis, buoyancy, closure, forcing,
-    boundary_conditions, background_fields, stokes_drift); BASELINE.json benchmarks the configuration with all of them = nothing. `forcing`
+    boundary_conditions, background_fields, stokes_drift, particles); BASELINE.json benchmarks the configuration with all of them = nothing. `forcing`
     takes the closure-free forcings of forcings.py (Relaxation, Forcing(array), MultipleForcings / tuples); `background_fields` a dict or a
     BackgroundFields of time-independent backgrounds (background_fields.py); `stokes_drift` a time-independent UniformStokesDrift
-    (stokes_drifts.py)."""
+    (stokes_drifts.py); `particles` a LagrangianParticles (particles.py): model.particles is then the model's own bound copy."""
 
     def __init__(self, grid, advection=None, tracers=("T", "S"), timestepper="RungeKutta3", buoyancy=None, coriolis=None,
-                 closure=None, forcing=None, boundary_conditions=None, background_fields=None, stokes_drift=None):
+                 closure=None, forcing=None, boundary_conditions=None, background_fields=None, stokes_drift=None, particles=None):
         if advection is None:
             advection = WENO()
         if not (isinstance(advection, WENO) and advection.order == 5 and advection.bounds is None):
@@ -106,6 +106,11 @@ class NonhydrostaticModel:
         # stokes_drift = UniformStokesDrift(...) (nonhydrostatic_model.jl:115-130): its per-level tables, settled on the host as well
         self.stokes_drift = stokes_drift
         self._stokes_tables = _stokes.regularize_stokes_drift(stokes_drift, grid, 0.0)
+        # particles = LagrangianParticles(...) (nonhydrostatic_model.jl:115-130): validated here, uploaded once the closure is set
+        from . import particles as _particles
+        from .closures import AnisotropicMinimumDissipation as _AMD, Smagorinsky as _Smag
+        tracked = _particles.validate_particles(particles, grid, self.tracer_names, buoyancy is not None, isinstance(closure, (_AMD, _Smag)))
+        self.particles = None
         self.handle = self._create_handle(grid, len(self.tracer_names))
         self.clock = Clock(self)
         V = namedtuple("Velocities", "u v w")
@@ -207,6 +212,8 @@ class NonhydrostaticModel:
                     continue
                 _lib.check(_lib.lib().ocn_model_set_boundary_condition(self.handle, cname.encode(), SIDES.index(side),
                                                                        KINDS[bc.classification], bc.condition))
+        if particles is not None:
+            self.particles = particles._bind(self, tracked)
 
     def _create_handle(self, grid, ntracers):
         h = C.c_void_p()
