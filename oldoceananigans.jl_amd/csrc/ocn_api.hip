@@ -1337,1399 +1337,8 @@ extern "C" int ocn_divide_interior(ocn_grid_t grid, double *p, double divisor) {
     return divide_interior(grid->d, p, divisor);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Poisson solvers
-// ---------------------------------------------------------------------------------------------------------------------
-// line-FFT kernels (ocn_kernels.h): lines per workgroup by line length, see strided_line_fft_kernel; the longest line they take: 1024
-// points x 4 lines x 16 B = the 64 KB of LDS a workgroup may ask for
-#ifndef OCN_LINE_MAX
-#define OCN_LINE_MAX 1024
-#endif
-static inline int line_zl(const OcnOptions &o, int n) { return n >= 1024 ? 4 : (n >= 512 ? o.line_zl512 : 8); }
-static inline void launch_strided_line_fft(const OcnOptions &o, double2 *data, const double2 *tw, long C, long ncols, unsigned batches, int N, int logn, int inverse,
-                                           double scale, long plane_stride = 0) {
-    const int zl = line_zl(o, N);
-    const dim3 grd((unsigned)((ncols + zl - 1) / zl), batches);
-    const size_t lds = (size_t)N * zl * sizeof(double2);
-    if (zl == 4) hipLaunchKernelGGL(strided_line_fft_kernel<4>, grd, dim3(256), lds, g_stream, data, tw, C, N, logn, inverse, scale, plane_stride);
-    else         hipLaunchKernelGGL(strided_line_fft_kernel<8>, grd, dim3(256), lds, g_stream, data, tw, C, N, logn, inverse, scale, plane_stride);
-}
-static inline void launch_paired_zline(const OcnOptions &o, bool forward, const double2 *in, double2 *out, const double2 *tw, long C, int N, int logn, double scale) {
-    const int zl = line_zl(o, N);
-    const dim3 grd((unsigned)((C + zl - 1) / zl));
-    const size_t lds = (size_t)N * zl * sizeof(double2);
-    if (forward) {
-        if (zl == 4) hipLaunchKernelGGL(paired_zline_r2c_kernel<4>, grd, dim3(256), lds, g_stream, in, out, tw, C, N, logn);
-        else         hipLaunchKernelGGL(paired_zline_r2c_kernel<8>, grd, dim3(256), lds, g_stream, in, out, tw, C, N, logn);
-    } else {
-        if (zl == 4) hipLaunchKernelGGL(paired_zline_c2r_kernel<4>, grd, dim3(256), lds, g_stream, in, out, tw, C, N, logn, scale);
-        else         hipLaunchKernelGGL(paired_zline_c2r_kernel<8>, grd, dim3(256), lds, g_stream, in, out, tw, C, N, logn, scale);
-    }
-}
-// short lines (thin slabs) take the grouped Thomas kernels: 4 elements per lane and N / 4 lanes per line -- 2, 4 or 8 lines per wave
-static inline bool xline_grouped(const OcnOptions &o, int N) { return o.dist_xline_group && (N == 32 || N == 64 || N == 128); }
-template <bool SOLVE>
-static inline void launch_xline_thomas(const OcnOptions &o, int E, double2 *S, const double *rden, long M, int N, double a, double2 *payload, const double2 *iface, double scale) {
-    const dim3 blk(256);
-    if (xline_grouped(o, N)) {
-        const int lpw = 256 / N;
-        const dim3 grp((unsigned)((M + 4 * lpw - 1) / (4 * lpw)));
-        if (N == 32)       hipLaunchKernelGGL((xline_thomas_kernel<4, SOLVE, 8>), grp, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale);
-        else if (N == 64)  hipLaunchKernelGGL((xline_thomas_kernel<4, SOLVE, 16>), grp, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale);
-        else               hipLaunchKernelGGL((xline_thomas_kernel<4, SOLVE, 32>), grp, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale);
-        return;
-    }
-    const dim3 grd((unsigned)((M + 3) / 4));
-    switch (E) {
-        case 1: hipLaunchKernelGGL((xline_thomas_kernel<1, SOLVE>), grd, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale); break;
-        case 2: hipLaunchKernelGGL((xline_thomas_kernel<2, SOLVE>), grd, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale); break;
-        case 4: hipLaunchKernelGGL((xline_thomas_kernel<4, SOLVE>), grd, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale); break;
-        case 8: hipLaunchKernelGGL((xline_thomas_kernel<8, SOLVE>), grd, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale); break;
-        default: hipLaunchKernelGGL((xline_thomas_kernel<16, SOLVE>), grd, blk, 0, g_stream, S, rden, M, N, a, payload, iface, scale); break;
-    }
-}
-static inline void launch_zline_solve(const OcnOptions &o, double2 *hc, const double2 *tw, const double *lx, const double *ly, const double *lz, int Nxs, int Ny, int Nz,
-                                      int logn, double scale, int pitch = 0) {
-    const int zl = line_zl(o, Nz);
-    const dim3 grd((unsigned)((Nxs + zl - 1) / zl), (unsigned)Ny);
-    const size_t lds = (size_t)Nz * zl * sizeof(double2);
-    if (zl == 4) hipLaunchKernelGGL(zline_solve_kernel<4>, grd, dim3(256), lds, g_stream, hc, tw, lx, ly, lz, Nxs, Ny, Nz, logn, scale, pitch);
-    else         hipLaunchKernelGGL(zline_solve_kernel<8>, grd, dim3(256), lds, g_stream, hc, tw, lx, ly, lz, Nxs, Ny, Nz, logn, scale, pitch);
-}
-struct ocn_poisson_s {
-    ocn_grid_t grid;
-    const OcnOptions *opt = nullptr;        // the owning model's options (standalone solvers: the library defaults)
-    int kind;
-    size_t n;                   // Nx*Ny*Nz
-    double2 *storage = nullptr; // kind 0: rhs + solution; kind 1: solution
-    double2 *source = nullptr;  // kind 1: rhs
-    double *lam[3] = {nullptr, nullptr, nullptr};
-    double *D = nullptr, *lower = nullptr, *t = nullptr;
-    double2 *partial = nullptr, *mean = nullptr;
-    hipfftHandle plan = 0;
-    bool has_plan = false;
-    // real-transform fast path used by solve_for_pressure! (the source term is real by construction): D2Z of a dense real
-    // rhs into the Hermitian half spectrum (Nx/2+1, Ny, Nz), Z2D straight into the interior of the haloed pressure field
-    int Nxh = 0;
-    size_t nh = 0;
-    double *rrhs = nullptr;      // dense real right-hand side / fallback real output
-    double2 *hc = nullptr;       // half spectrum
-    double2 *hc2 = nullptr;      // kind 1: tridiagonal solution (separate from the rhs like the reference's storage)
-    hipfftHandle plan_r2c = 0, plan_c2r = 0;
-    bool has_r2c = false, has_c2r = false, c2r_strided = false;
-    bool zfused = false;         // kind 0: 2-D (x, y) plans + zline_solve_kernel instead of 3-D plans + divide kernel
-    // split form of the 2-D (x, y) transforms for the model's time-step (Ny = 2^m <= 1024): 1-D R2C / C2R plans along x and the y
-    // pass by strided_line_fft_kernel (61 us against the 82 us of the 2-D plan's column kernel); the inverse lands in the dense
-    // real array, which pressure_correction_dense_kernel reads directly
-    bool split = false;
-    int Nxp = 0;                 // row pitch (complex elements) of hc / hc2 on the split path: Nxh rounded up to a multiple of 8
-    hipfftHandle plan_xr2c = 0, plan_xc2r = 0;
-    int logn_y = 0;
-    double2 *ytw = nullptr;
-    int logn_z = 0;
-    double2 *ztw = nullptr;      // exp(-2πi m / Nz), m < Nz/2
-    // grids with Bounded transformed directions: per-direction line transforms (see ocn_kernels.h, line_gather_kernel)
-    bool general = false;
-    hipfftHandle plan_line[3] = {0, 0, 0};
-    bool has_line[3] = {false, false, false};   // owns the handle (directions of equal length share one plan)
-    double2 *buffer = nullptr;
-};
-
-// Solvers/poisson_eigenvalues.jl:8-23
-static void poisson_eigenvalues(int N, double L, int topo, std::vector<double> &lam) {
-    lam.resize(N);
-    if (topo == OCN_FLAT) { for (double &x : lam) x = 0.0; return; }      // poisson_eigenvalues(N, L, dim, ::Flat) = zeros
-    for (int i = 1; i <= N; ++i) {
-        double arg = topo == OCN_PERIODIC ? ((double)(i - 1) * M_PI) / (double)N : ((double)(i - 1) * M_PI) / (double)(2 * N);
-        double s = 2.0 * sin(arg) / (L / (double)N);
-        lam[i - 1] = s * s;
-    }
-}
-
-extern "C" int ocn_poisson_destroy(ocn_poisson_t s) {
-    if (!s) return OCN_OK;
-    if (s->has_plan) hipfftDestroy(s->plan);
-    if (s->split) { hipfftDestroy(s->plan_xr2c); hipfftDestroy(s->plan_xc2r); }
-    hipFree(s->ytw);
-    if (s->has_r2c) hipfftDestroy(s->plan_r2c);
-    if (s->has_c2r) hipfftDestroy(s->plan_c2r);
-    for (int d = 0; d < 3; ++d)
-        if (s->has_line[d]) hipfftDestroy(s->plan_line[d]);
-    hipFree(s->buffer);
-    hipFree(s->ztw);
-    hipFree(s->rrhs); hipFree(s->hc); hipFree(s->hc2);
-    hipFree(s->storage); hipFree(s->source); hipFree(s->D); hipFree(s->lower); hipFree(s->t);
-    hipFree(s->partial); hipFree(s->mean);
-    for (int d = 0; d < 3; ++d) hipFree(s->lam[d]);
-    delete s;
-    return OCN_OK;
-}
-
-// ---- FFT plan self-checks -------------------------------------------------------------------------------------------
-// rocFFT (7.0 and 7.2 tested) can return WRONG transforms from a freshly created plan while plans of other sizes are alive
-// in the process (tools/fft_real_test2.hip reproduces it without this library: e.g. a 64x16x8 real 3-D plan created while
-// 32^3 / 16^3 plans exist). Every plan set is therefore verified once, at creation, by a round trip on a pseudo-random
-// pattern; a solver whose plans fail the check is refused (OCN_EFFT) instead of silently producing wrong pressure.
-static int reduce_blockmax(double *d_blockmax, int nb, double *out) {
-    std::vector<double> h(nb);
-    HIP_TRY(hipMemcpyAsync(h.data(), d_blockmax, nb * sizeof(double), hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(hipStreamSynchronize(g_stream));
-    double m = 0;
-    for (double x : h) m = (x > m || x != x) ? x : m;
-    *out = m;
-    return OCN_OK;
-}
-
-static int verify_real_plans(ocn_poisson_s *s) {
-    const DGrid &g = s->grid->d;
-    const int Px = g.Nx + 2 * g.Hx, Py = g.Ny + 2 * g.Hy, Pz = g.Nz + 2 * g.Hz;
-    const long n = (long)s->n;
-    const int nb = 256;
-    double *tmp = nullptr, *bm = nullptr;
-    HIP_TRY(dev_alloc((void **)&bm, nb * sizeof(double)));
-    hipLaunchKernelGGL(selfcheck_fill_real, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, s->rrhs, n);
-    hipfftResult r = hipfftExecD2Z(s->plan_r2c, s->rrhs, (hipfftDoubleComplex *)s->hc);
-    const double scale = (s->kind == 0 && !s->zfused) ? 1.0 / ((double)g.Nx * g.Ny * g.Nz) : 1.0 / ((double)g.Nx * g.Ny);
-    if (r == HIPFFT_SUCCESS) {
-        if (s->c2r_strided) {
-            hipError_t e = dev_alloc((void **)&tmp, (size_t)Px * Py * Pz * sizeof(double));
-            if (e != hipSuccess) { hipFree(bm); return fail((int)e, "self-check allocation: %s", hipGetErrorString(e)); }
-            r = hipfftExecZ2D(s->plan_c2r, (hipfftDoubleComplex *)s->hc, tmp + g.Hx + (size_t)Px * (g.Hy + (size_t)Py * g.Hz));
-            hipLaunchKernelGGL(selfcheck_compare_real, dim3(nb), dim3(256), 0, g_stream, tmp, g.Nx, g.Ny, g.Nz, Px, Py, g.Hx, g.Hy, g.Hz, scale, bm);
-        } else {
-            r = hipfftExecZ2D(s->plan_c2r, (hipfftDoubleComplex *)s->hc, s->rrhs);
-            hipLaunchKernelGGL(selfcheck_compare_real, dim3(nb), dim3(256), 0, g_stream, s->rrhs, g.Nx, g.Ny, g.Nz, g.Nx, g.Ny, 0, 0, 0, scale, bm);
-        }
-    }
-    double err = 0;
-    int rc = r == HIPFFT_SUCCESS ? reduce_blockmax(bm, nb, &err) : fail(1000 + (int)r, "hipFFT exec failed in the plan self-check (%d)", (int)r);
-    hipFree(tmp); hipFree(bm);
-    if (rc) return rc;
-    if (!(err < 1e-10))
-        return fail(OCN_EFFT, "rocFFT self-check failed for the %dx%dx%d real transform pair (round-trip error %.3g): rocFFT returns wrong "
-                              "results from this plan while plans of other sizes are alive in the process; destroy the other "
-                              "models/solvers first", g.Nx, g.Ny, g.Nz, err);
-    return OCN_OK;
-}
-
-static int verify_complex_plan(hipfftHandle plan, double2 *buf, long n, double scale, const char *what) {
-    const int nb = 256;
-    double *bm = nullptr;
-    HIP_TRY(dev_alloc((void **)&bm, nb * sizeof(double)));
-    hipLaunchKernelGGL(selfcheck_fill_complex, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, buf, n);
-    hipfftResult r = hipfftExecZ2Z(plan, (hipfftDoubleComplex *)buf, (hipfftDoubleComplex *)buf, HIPFFT_FORWARD);
-    if (r == HIPFFT_SUCCESS) r = hipfftExecZ2Z(plan, (hipfftDoubleComplex *)buf, (hipfftDoubleComplex *)buf, HIPFFT_BACKWARD);
-    hipLaunchKernelGGL(selfcheck_compare_complex, dim3(nb), dim3(256), 0, g_stream, buf, n, scale, bm);
-    double err = 0;
-    int rc = r == HIPFFT_SUCCESS ? reduce_blockmax(bm, nb, &err) : fail(1000 + (int)r, "hipFFT exec failed in the plan self-check (%d)", (int)r);
-    hipFree(bm);
-    if (rc) return rc;
-    if (!(err < 1e-10))
-        return fail(OCN_EFFT, "rocFFT self-check failed for the %s plan (round-trip error %.3g): rocFFT returns wrong results from this "
-                              "plan while plans of other sizes are alive in the process; destroy the other models/solvers first", what, err);
-    HIP_TRY(hipMemsetAsync(buf, 0, n * sizeof(double2), g_stream));
-    return OCN_OK;
-}
-
-// FFT plans capture a stream at creation; re-point them when the library stream changed (ocn_set_stream)
-static int plan_set_stream(hipfftHandle plan) {
-    FFT_TRY(hipfftSetStream(plan, g_stream));
-    return OCN_OK;
-}
-
-// complex-to-complex resources of the reference's API (solve!(ϕ, solver, b) with a complex b): created on first use so
-// that the model fast path keeps only its two real plans alive
-// rocFFT hazard (tools/fft_real_test2.hip): a multi-dimensional plan created while plans of OTHER sizes are alive in
-// the process can return wrong transforms (e.g. the 64x16x8 real 3-D pair after 32x16x8, 8x16x32 and 32^3; exact again once the older
-// plans are destroyed -- an internal cache of rocFFT keyed too coarsely). Triage on MI355X: the embedded (strided) Z2D plans and the
-// unit-stride batched 1-D complex plans stay exact in exactly that situation. A solver whose multi-dimensional plans fail their
-// creation-time self-check therefore switches to the per-direction path (gather -> unit-stride batched 1-D Z2Z -> scatter, the path
-// of the cosine-transform topologies), which is verified in turn; only if that fails too is the solver refused (OCN_EFFT).
-static int g_fft_fallbacks = 0;
-static int ensure_complex(ocn_poisson_s *s);
-static int poisson_fall_back(ocn_poisson_s *s) {
-    (void)hipGetLastError();
-    s->general = true;
-    s->split = false;
-    ++g_fft_fallbacks;
-    return ensure_complex(s);
-}
-extern "C" int ocn_debug_fft_fallbacks(void) { return g_fft_fallbacks; }
-
-static int ensure_complex(ocn_poisson_s *s) {
-    if (s->has_plan || s->buffer) return OCN_OK;
-    const DGrid &g = s->grid->d;
-    if (!s->storage) HIP_TRY(dev_alloc((void **)&s->storage, s->n * sizeof(double2)));
-    HIP_TRY(hipMemsetAsync(s->storage, 0, s->n * sizeof(double2), g_stream));
-    if (s->kind == 1 && !s->source) {
-        HIP_TRY(dev_alloc((void **)&s->source, s->n * sizeof(double2)));
-        HIP_TRY(hipMemsetAsync(s->source, 0, s->n * sizeof(double2), g_stream));
-        HIP_TRY(dev_alloc((void **)&s->partial, 1024 * sizeof(double2)));
-        HIP_TRY(dev_alloc((void **)&s->mean, sizeof(double2)));
-    }
-    if (s->general) {
-        HIP_TRY(dev_alloc((void **)&s->buffer, s->n * sizeof(double2)));
-        const int N[3] = {g.Nx, g.Ny, g.Nz};
-        const int ndims = s->kind == 0 ? 3 : 2;
-        const int T[3] = {g.tx, g.ty, g.tz};
-        for (int d = 0; d < ndims; ++d) {
-            if (T[d] == OCN_FLAT) continue;
-            int shared = -1;
-            for (int e = 0; e < d; ++e)
-                if (N[e] == N[d] && T[e] != OCN_FLAT) shared = e;
-            if (shared >= 0) { s->plan_line[d] = s->plan_line[shared]; continue; }
-            int nn[1] = {N[d]};
-            hipfftResult r = hipfftPlanMany(&s->plan_line[d], 1, nn, nullptr, 1, N[d], nullptr, 1, N[d], HIPFFT_Z2Z, (int)(s->n / N[d]));
-            if (r != HIPFFT_SUCCESS) return fail(1000 + (int)r, "hipfftPlanMany(line, dim %d) failed (%d)", d, (int)r);
-            s->has_line[d] = true;
-            FFT_TRY(hipfftSetStream(s->plan_line[d], g_stream));
-            int rc = verify_complex_plan(s->plan_line[d], s->buffer, (long)s->n, 1.0 / (double)N[d], "line transform");
-            if (rc) return rc;
-        }
-        return OCN_OK;
-    }
-    hipfftResult r;
-    if (s->kind == 0) {
-        r = hipfftPlan3d(&s->plan, g.Nz, g.Ny, g.Nx, HIPFFT_Z2Z);
-    } else {
-        int nfft[2] = {g.Ny, g.Nx};
-        r = hipfftPlanMany(&s->plan, 2, nfft, nullptr, 1, g.Nx * g.Ny, nullptr, 1, g.Nx * g.Ny, HIPFFT_Z2Z, g.Nz);
-    }
-    if (r != HIPFFT_SUCCESS) return fail(1000 + (int)r, "hipfftPlan (Z2Z) failed (%d)", (int)r);
-    s->has_plan = true;
-    FFT_TRY(hipfftSetStream(s->plan, g_stream));
-    const double scale = s->kind == 0 ? 1.0 / ((double)g.Nx * g.Ny * g.Nz) : 1.0 / ((double)g.Nx * g.Ny);
-    int rc = verify_complex_plan(s->plan, s->storage, (long)s->n, scale, "complex-to-complex");
-    if (rc != OCN_EFFT) return rc;
-    // the multi-dimensional plan came out wrong (see poisson_fall_back): per-direction transforms on unit-stride 1-D plans instead
-    hipfftDestroy(s->plan);
-    s->has_plan = false;
-    return poisson_fall_back(s);
-}
-
-// one direction of the transform on a grid with Bounded directions (forward: physical -> spectral)
-static int transform_dim(ocn_poisson_s *s, double2 *A, int d, bool forward) {
-    const DGrid &g = s->grid->d;
-    const int T[3] = {g.tx, g.ty, g.tz};
-    if (T[d] == OCN_FLAT) return OCN_OK;
-    const int mode = T[d] == OCN_BOUNDED ? (forward ? 1 : 2) : 0;
-    { int rc_ = plan_set_stream(s->plan_line[d]); if (rc_) return rc_; }
-    const int dir = forward ? HIPFFT_FORWARD : HIPFFT_BACKWARD;
-    if (mode == 0 && d == 0) {          // x lines are contiguous already
-        FFT_TRY(hipfftExecZ2Z(s->plan_line[d], (hipfftDoubleComplex *)A, (hipfftDoubleComplex *)A, dir));
-        return OCN_OK;
-    }
-    hipLaunchKernelGGL(line_gather_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, A, s->buffer, g.Nx, g.Ny, g.Nz, d, mode);
-    FFT_TRY(hipfftExecZ2Z(s->plan_line[d], (hipfftDoubleComplex *)s->buffer, (hipfftDoubleComplex *)s->buffer, dir));
-    hipLaunchKernelGGL(line_scatter_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, s->buffer, A, g.Nx, g.Ny, g.Nz, d, mode);
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-// Bounded directions first on the way in, last on the way out (plan_transforms.jl:44-65)
-static int transform_all(ocn_poisson_s *s, double2 *A, bool forward) {
-    const DGrid &g = s->grid->d;
-    const int T[3] = {g.tx, g.ty, g.tz};
-    const int ndims = s->kind == 0 ? 3 : 2;
-    for (int pass = 0; pass < 2; ++pass)
-        for (int d = 0; d < ndims; ++d) {
-            const bool bounded = T[d] == OCN_BOUNDED;
-            if ((pass == 0) == (bounded == forward)) {
-                int rc = transform_dim(s, A, d, forward);
-                if (rc) return rc;
-            }
-        }
-    return OCN_OK;
-}
-
-static int poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int kind, const OcnOptions *opt) {
-    NEED_INIT();
-    if (!solver || !grid) return fail(OCN_EINVAL, "NULL argument");
-    const DGrid &g = grid->d;
-    for (int t : {g.tx, g.ty, g.tz})
-        if (t != OCN_PERIODIC && t != OCN_BOUNDED && t != OCN_FLAT)
-            return fail(OCN_ENOTSUP, "Poisson solvers need Periodic or Bounded directions (a FullyConnected x belongs to ocn_dist_poisson_create)");
-    if (kind == -1) kind = (g.tz == OCN_BOUNDED) ? 1 : 0;   // see DESIGN.md: z-Bounded takes the tridiagonal path by default
-    if (kind == 0 && !grid->z_regular) return fail(OCN_EINVAL, "FFTBasedPoissonSolver requires a regular grid");
-    if (kind == 1 && g.tz != OCN_BOUNDED)
-        return fail(OCN_EINVAL, "`FourierTridiagonalPoissonSolver` can only be used when the stretched direction's topology is `Bounded`.");
-    if (kind != 0 && kind != 1) return fail(OCN_EINVAL, "unknown solver kind %d", kind);
-    ocn_poisson_s *s = new ocn_poisson_s();
-    s->grid = grid; s->opt = opt; s->kind = kind;
-    s->n = (size_t)g.Nx * g.Ny * g.Nz;
-    s->general = g.tx == OCN_BOUNDED || g.ty == OCN_BOUNDED || (kind == 0 && g.tz == OCN_BOUNDED) ||
-                 g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT;      // Flat directions are not transformed
-    int rc = OCN_OK;
-#define TRY_OR_FREE(expr)                                                                                  \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) { rc = fail((int)e_, "%s: %s", #expr, hipGetErrorString(e_)); goto bad; }   \
-    } while (0)
-    {
-        const int N[3] = {g.Nx, g.Ny, g.Nz}, T[3] = {g.tx, g.ty, g.tz};
-        std::vector<double> lam[3];
-        for (int d = 0; d < 3; ++d) {
-            poisson_eigenvalues(N[d], grid->L[d], T[d], lam[d]);
-            TRY_OR_FREE(dev_alloc((void **)&s->lam[d], N[d] * sizeof(double)));
-            TRY_OR_FREE(hipMemcpy(s->lam[d], lam[d].data(), N[d] * sizeof(double), hipMemcpyHostToDevice));
-        }
-        if (kind == 1) {
-            // fourier_tridiagonal_poisson_solver.jl:75-134; diagonals :180-210 (HomogeneousZFormulation), host-built
-            TRY_OR_FREE(dev_alloc((void **)&s->D, s->n * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->t, s->n * sizeof(double)));
-            TRY_OR_FREE(hipMemset(s->t, 0, s->n * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->lower, std::max(1, g.Nz - 1) * sizeof(double)));
-            const int Nx = g.Nx, Ny = g.Ny, Nz = g.Nz, Hz = g.Hz;
-            auto dzf = [&](int k) { return grid->h_dzf[k - 1 + Hz]; };
-            auto dzc = [&](int k) { return grid->h_dzc[k - 1 + Hz]; };
-            std::vector<double> D(s->n), lower(std::max(1, Nz - 1));
-            for (int j = 0; j < Ny; ++j)
-                for (int i = 0; i < Nx; ++i) {
-                    double lxy = lam[0][i] + lam[1][j];
-                    auto at = [&](int k) -> double & { return D[(size_t)i + (size_t)Nx * (j + (size_t)Ny * (k - 1))]; };
-                    at(1) = -1.0 / dzf(2) - dzc(1) * lxy;
-                    at(Nz) = -1.0 / dzf(Nz) - dzc(Nz) * lxy;
-                    for (int k = 2; k <= Nz - 1; ++k) at(k) = -(1.0 / dzf(k + 1) + 1.0 / dzf(k)) - dzc(k) * lxy;
-                }
-            for (int q = 1; q <= Nz - 1; ++q) lower[q - 1] = 1.0 / dzf(q + 1);
-            TRY_OR_FREE(hipMemcpy(s->D, D.data(), s->n * sizeof(double), hipMemcpyHostToDevice));
-            TRY_OR_FREE(hipMemcpy(s->lower, lower.data(), lower.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        hipfftResult r;
-        if (s->general) {   // cosine transforms: complex storage + per-direction line transforms, created (and verified) now
-            if ((rc = ensure_complex(s))) goto bad;
-            *solver = s;
-            return OCN_OK;
-        }
-        // ---- real-transform path (the complex-to-complex resources of the reference API are created on first use) ----
-        s->Nxh = g.Nx / 2 + 1;
-        s->nh = (size_t)s->Nxh * g.Ny * g.Nz;
-        s->Nxp = (s->Nxh + 7) & ~7;                          // row pitch of the split path: whole 128-B rows
-        const size_t nh_alloc = (size_t)s->Nxp * g.Ny * g.Nz;
-        TRY_OR_FREE(dev_alloc((void **)&s->rrhs, s->n * sizeof(double)));
-        TRY_OR_FREE(dev_alloc((void **)&s->hc, nh_alloc * sizeof(double2)));
-        TRY_OR_FREE(hipMemset(s->hc, 0, nh_alloc * sizeof(double2)));
-        if (kind == 1) {
-            TRY_OR_FREE(dev_alloc((void **)&s->hc2, nh_alloc * sizeof(double2)));
-            TRY_OR_FREE(hipMemset(s->hc2, 0, nh_alloc * sizeof(double2)));
-            TRY_OR_FREE(hipMemset(s->hc2, 0, s->nh * sizeof(double2)));
-        }
-        const int Px = g.Nx + 2 * g.Hx, Py = g.Ny + 2 * g.Hy, Pz = g.Nz + 2 * g.Hz;
-        if (kind == 0 && opt->fused_zfft && g.Nz >= 8 && g.Nz <= OCN_LINE_MAX && (g.Nz & (g.Nz - 1)) == 0) {
-            s->zfused = true;
-            while ((1 << s->logn_z) < g.Nz) ++s->logn_z;
-            std::vector<double2> tw(g.Nz / 2);
-            for (int m = 0; m < g.Nz / 2; ++m) {
-                const double a = -2.0 * M_PI * (double)m / (double)g.Nz;
-                tw[m] = make_double2(cos(a), sin(a));
-            }
-            TRY_OR_FREE(dev_alloc((void **)&s->ztw, tw.size() * sizeof(double2)));
-            TRY_OR_FREE(hipMemcpy(s->ztw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
-        }
-        if (kind == 0 && !s->zfused) {
-            int n3[3] = {g.Nz, g.Ny, g.Nx};
-            r = hipfftPlanMany(&s->plan_r2c, 3, n3, nullptr, 1, 0, nullptr, 1, 0, HIPFFT_D2Z, 1);
-            if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(D2Z 3-D) failed (%d)", (int)r); goto bad; }
-            s->has_r2c = true;
-            int inembed[3] = {g.Nz, g.Ny, s->Nxh}, onembed[3] = {Pz, Py, Px};
-            r = opt->c2r_strided ? hipfftPlanMany(&s->plan_c2r, 3, n3, inembed, 1, (int)s->nh, onembed, 1, Px * Py * Pz, HIPFFT_Z2D, 1) : HIPFFT_NOT_SUPPORTED;
-            s->c2r_strided = r == HIPFFT_SUCCESS && opt->c2r_strided;
-            if (!s->c2r_strided) r = hipfftPlanMany(&s->plan_c2r, 3, n3, nullptr, 1, 0, nullptr, 1, 0, HIPFFT_Z2D, 1);
-            if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(Z2D 3-D) failed (%d)", (int)r); goto bad; }
-            s->has_c2r = true;
-        } else {
-            int n2[2] = {g.Ny, g.Nx};
-            int rin[2] = {g.Ny, g.Nx}, cemb[2] = {g.Ny, s->Nxh}, pemb[2] = {Py, Px};
-            r = hipfftPlanMany(&s->plan_r2c, 2, n2, rin, 1, g.Nx * g.Ny, cemb, 1, s->Nxh * g.Ny, HIPFFT_D2Z, g.Nz);
-            if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(D2Z 2-D) failed (%d)", (int)r); goto bad; }
-            s->has_r2c = true;
-            r = opt->c2r_strided ? hipfftPlanMany(&s->plan_c2r, 2, n2, cemb, 1, s->Nxh * g.Ny, pemb, 1, Px * Py, HIPFFT_Z2D, g.Nz) : HIPFFT_NOT_SUPPORTED;
-            s->c2r_strided = r == HIPFFT_SUCCESS;
-            if (!s->c2r_strided) r = hipfftPlanMany(&s->plan_c2r, 2, n2, cemb, 1, s->Nxh * g.Ny, rin, 1, g.Nx * g.Ny, HIPFFT_Z2D, g.Nz);
-            if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(Z2D 2-D) failed (%d)", (int)r); goto bad; }
-            s->has_c2r = true;
-        }
-        if ((r = hipfftSetStream(s->plan_r2c, g_stream)) != HIPFFT_SUCCESS || (r = hipfftSetStream(s->plan_c2r, g_stream)) != HIPFFT_SUCCESS) {
-            rc = fail(1000 + (int)r, "hipfftSetStream failed (%d)", (int)r);
-            goto bad;
-        }
-        if ((rc = verify_real_plans(s))) {
-            if (rc != OCN_EFFT) goto bad;
-            hipfftDestroy(s->plan_r2c); hipfftDestroy(s->plan_c2r);
-            s->has_r2c = s->has_c2r = false;
-            if ((rc = poisson_fall_back(s))) goto bad;
-            *solver = s;
-            return OCN_OK;
-        }
-        if (opt->split_solve && (kind == 1 || s->zfused) && g.Ny >= 8 && g.Ny <= OCN_LINE_MAX && (g.Ny & (g.Ny - 1)) == 0 && g.tx == OCN_PERIODIC &&
-            g.ty == OCN_PERIODIC) {
-            int nx1[1] = {g.Nx};
-            int rembx[1] = {g.Nx}, cembx[1] = {s->Nxp};
-            hipfftResult r1 = hipfftPlanMany(&s->plan_xr2c, 1, nx1, rembx, 1, g.Nx, cembx, 1, s->Nxp, HIPFFT_D2Z, g.Ny * g.Nz);
-            hipfftResult r2 = r1 == HIPFFT_SUCCESS ? hipfftPlanMany(&s->plan_xc2r, 1, nx1, cembx, 1, s->Nxp, rembx, 1, g.Nx, HIPFFT_Z2D, g.Ny * g.Nz) : r1;
-            if (r1 == HIPFFT_SUCCESS && r2 != HIPFFT_SUCCESS) hipfftDestroy(s->plan_xr2c);
-            if (r1 == HIPFFT_SUCCESS && r2 == HIPFFT_SUCCESS) {
-                hipfftSetStream(s->plan_xr2c, g_stream); hipfftSetStream(s->plan_xc2r, g_stream);
-                while ((1 << s->logn_y) < g.Ny) ++s->logn_y;
-                std::vector<double2> tw(g.Ny / 2);
-                for (int m = 0; m < g.Ny / 2; ++m) {
-                    const double ang = -2.0 * M_PI * (double)m / (double)g.Ny;
-                    tw[m] = make_double2(cos(ang), sin(ang));
-                }
-                double2 *ref = nullptr;
-                double *bm = nullptr;
-                bool ok = dev_alloc((void **)&s->ytw, tw.size() * sizeof(double2)) == hipSuccess &&
-                          hipMemcpy(s->ytw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice) == hipSuccess &&
-                          dev_alloc((void **)&ref, s->nh * sizeof(double2)) == hipSuccess && dev_alloc((void **)&bm, 256 * sizeof(double)) == hipSuccess;
-                double e_fwd = -1.0, e_rt = -1.0;
-                if (ok) {
-                    // forward: the split form against the library's 2-D plan on pseudo-random data; inverse: round trip of the split form
-                    const long n = (long)s->n;
-                    hipLaunchKernelGGL(selfcheck_fill_real, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, s->rrhs, n);
-                    ok = hipfftExecD2Z(s->plan_r2c, s->rrhs, (hipfftDoubleComplex *)ref) == HIPFFT_SUCCESS &&
-                         hipfftExecD2Z(s->plan_xr2c, s->rrhs, (hipfftDoubleComplex *)s->hc) == HIPFFT_SUCCESS;
-                    launch_strided_line_fft(*s->opt, s->hc, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 0, 1.0, (long)s->Nxp * g.Ny);
-                    hipLaunchKernelGGL(max_abs_diff_pitched_kernel, dim3(256), dim3(256), 0, g_stream, (const double2 *)ref, s->Nxh,
-                                       (const double2 *)s->hc, s->Nxp, s->Nxh, (long)g.Ny * g.Nz, bm);
-                    ok = ok && reduce_blockmax(bm, 256, &e_fwd) == OCN_OK;
-                    launch_strided_line_fft(*s->opt, s->hc, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 1, 1.0, (long)s->Nxp * g.Ny);
-                    ok = ok && hipfftExecZ2D(s->plan_xc2r, (hipfftDoubleComplex *)s->hc, s->rrhs) == HIPFFT_SUCCESS;
-                    hipLaunchKernelGGL(selfcheck_compare_real, dim3(256), dim3(256), 0, g_stream, s->rrhs, g.Nx, g.Ny, g.Nz, g.Nx, g.Ny, 0, 0, 0,
-                                       1.0 / ((double)g.Nx * g.Ny), bm);
-                    ok = ok && reduce_blockmax(bm, 256, &e_rt) == OCN_OK;
-                }
-                hipFree(ref); hipFree(bm);
-                s->split = ok && e_fwd >= 0 && e_fwd < 1e-10 * g.Nx * g.Ny && e_rt >= 0 && e_rt < 1e-10;
-                if (!s->split) { hipfftDestroy(s->plan_xr2c); hipfftDestroy(s->plan_xc2r); }
-                (void)hipGetLastError();
-            }
-        }
-    }
-    *solver = s;
-    return OCN_OK;
-bad:
-    ocn_poisson_destroy(s);
-    return rc;
-#undef TRY_OR_FREE
-}
-extern "C" int ocn_poisson_create(ocn_poisson_t *solver, ocn_grid_t grid, int kind) { return poisson_create(solver, grid, kind, &g_defaults); }
-
-extern "C" int ocn_poisson_kind(ocn_poisson_t s) { return s ? s->kind : OCN_EINVAL; }
-
-extern "C" int ocn_poisson_rhs(ocn_poisson_t s, double **rhs_complex) {
-    if (!s || !rhs_complex) return fail(OCN_EINVAL, "NULL argument");
-    NEED_INIT();
-    { int rc_ = ensure_complex(s); if (rc_) return rc_; }
-    *rhs_complex = (double *)(s->kind == 0 ? s->storage : s->source);
-    return OCN_OK;
-}
-
-static int poisson_solve(ocn_poisson_s *s, double *phi) {
-    const DGrid &g = s->grid->d;
-    { int rc_ = ensure_complex(s); if (rc_) return rc_; }
-    FView vphi = make_view(g, phi, LOC_C);
-    if (s->general) {
-        int rc;
-        double2 *sol = s->storage;
-        if (s->kind == 0) {
-            if ((rc = transform_all(s, s->storage, true))) return rc;
-            hipLaunchKernelGGL(spectral_divide_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, s->storage, s->lam[0],
-                               s->lam[1], s->lam[2], g.Nx, g.Ny, g.Nz, 1.0, false);
-        } else {
-            if ((rc = transform_all(s, s->source, true))) return rc;
-            hipLaunchKernelGGL(tridiagonal_z_kernel, dim3((g.Nx + 63) / 64, g.Ny), dim3(64), 0, g_stream, g.Nx, g.Nx, g.Ny, g.Nz, s->lower,
-                               s->D, s->lower, s->source, s->t, s->storage, 1.0, false);
-        }
-        if ((rc = transform_all(s, sol, false))) return rc;
-        const double scale = s->kind == 0 ? 1.0 / ((double)g.Nx * (double)g.Ny * (double)g.Nz) : 1.0 / ((double)g.Nx * (double)g.Ny);
-        const double2 *mean = nullptr;
-        if (s->kind == 1) {
-            const int nb = 1024;
-            hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(256), 0, g_stream, s->storage, (long)s->n, s->partial);
-            hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, g_stream, s->partial, nb, 1.0 / (double)s->n, scale, s->mean);
-            mean = s->mean;
-        }
-        hipLaunchKernelGGL(copy_real_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, vphi, s->storage, scale, true, mean);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    { int rc_ = plan_set_stream(s->plan); if (rc_) return rc_; }
-    if (s->kind == 0) {
-        // fft_based_poisson_solver.jl:95-125
-        FFT_TRY(hipfftExecZ2Z(s->plan, (hipfftDoubleComplex *)s->storage, (hipfftDoubleComplex *)s->storage, HIPFFT_FORWARD));
-        hipLaunchKernelGGL(spectral_divide_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, s->storage, s->lam[0],
-                           s->lam[1], s->lam[2], g.Nx, g.Ny, g.Nz, 1.0, false);
-        FFT_TRY(hipfftExecZ2Z(s->plan, (hipfftDoubleComplex *)s->storage, (hipfftDoubleComplex *)s->storage, HIPFFT_BACKWARD));
-        const double scale = 1.0 / ((double)g.Nx * (double)g.Ny * (double)g.Nz);
-        hipLaunchKernelGGL(copy_real_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, vphi, s->storage, scale, true,
-                           (const double2 *)nullptr);
-    } else {
-        // fourier_tridiagonal_poisson_solver.jl:212-239
-        FFT_TRY(hipfftExecZ2Z(s->plan, (hipfftDoubleComplex *)s->source, (hipfftDoubleComplex *)s->source, HIPFFT_FORWARD));
-        hipLaunchKernelGGL(tridiagonal_z_kernel, dim3((g.Nx + 63) / 64, g.Ny), dim3(64), 0, g_stream, g.Nx, g.Nx, g.Ny, g.Nz, s->lower,
-                           s->D, s->lower, s->source, s->t, s->storage, 1.0, false);
-        FFT_TRY(hipfftExecZ2Z(s->plan, (hipfftDoubleComplex *)s->storage, (hipfftDoubleComplex *)s->storage, HIPFFT_BACKWARD));
-        const double scale = 1.0 / ((double)g.Nx * (double)g.Ny);
-        const int nb = 1024;
-        hipLaunchKernelGGL(sum_partial_kernel, dim3(nb), dim3(256), 0, g_stream, s->storage, (long)s->n, s->partial);
-        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, g_stream, s->partial, nb, 1.0 / (double)s->n, scale, s->mean);
-        hipLaunchKernelGGL(copy_real_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, vphi, s->storage, scale, true,
-                           (const double2 *)s->mean);
-        // the reference keeps the (normalised, mean-free) solution in `storage` between solves; the guarded update of the
-        // singular column re-reads it (batched_tridiagonal_solver.jl:234-237). The read value only shifts the solution
-        // by a constant that the mean removal deletes, so `storage` keeps the unnormalised field here.
-    }
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-// solve_for_pressure! on the real-transform path: rrhs (dense real, already filled by the source-term kernel) -> phi
-static int poisson_solve_real(ocn_poisson_s *s, double *phi) {
-    const DGrid &g = s->grid->d;
-    const int Px = g.Nx + 2 * g.Hx, Py = g.Ny + 2 * g.Hy;
-    double *interior = phi + g.Hx + (size_t)Px * (g.Hy + (size_t)Py * g.Hz);
-    { int rc_; if ((rc_ = plan_set_stream(s->plan_r2c)) || (rc_ = plan_set_stream(s->plan_c2r))) return rc_; }
-    FFT_TRY(hipfftExecD2Z(s->plan_r2c, s->rrhs, (hipfftDoubleComplex *)s->hc));
-    double2 *sol = s->hc;
-    if (s->kind == 0 && s->zfused) {
-        const double scale = 1.0 / ((double)g.Nx * (double)g.Ny * (double)g.Nz);
-        launch_zline_solve(*s->opt, s->hc, s->ztw, s->lam[0], s->lam[1], s->lam[2], s->Nxh, g.Ny, g.Nz, s->logn_z, scale);
-    } else if (s->kind == 0) {
-        const double scale = 1.0 / ((double)g.Nx * (double)g.Ny * (double)g.Nz);
-        hipLaunchKernelGGL(spectral_divide_kernel, grid3(s->Nxh, g.Ny, g.Nz, BLK), BLK, 0, g_stream, s->hc, s->lam[0], s->lam[1],
-                           s->lam[2], s->Nxh, g.Ny, g.Nz, scale, true);
-    } else {
-        const double scale = 1.0 / ((double)g.Nx * (double)g.Ny);
-        hipLaunchKernelGGL(tridiagonal_z_kernel, dim3((s->Nxh + 63) / 64, g.Ny), dim3(64), 0, g_stream, s->Nxh, g.Nx, g.Ny, g.Nz,
-                           s->lower, s->D, s->lower, s->hc, s->t, s->hc2, scale, true);
-        hipLaunchKernelGGL(remove_mean_mode_kernel, dim3(1), dim3(256), 0, g_stream, s->hc2, (long)s->Nxh * g.Ny, g.Nz);
-        sol = s->hc2;
-    }
-    if (s->c2r_strided) {
-        FFT_TRY(hipfftExecZ2D(s->plan_c2r, (hipfftDoubleComplex *)sol, interior));
-    } else {
-        FFT_TRY(hipfftExecZ2D(s->plan_c2r, (hipfftDoubleComplex *)sol, s->rrhs));
-        hipLaunchKernelGGL(copy_dense_real_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, phi, LOC_C), s->rrhs);
-    }
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-
-
-// the same solve in split form: rrhs (dense real source term) -> rrhs (dense real solution, not yet divided by anything)
-static int poisson_solve_real_split(ocn_poisson_s *s) {
-    const DGrid &g = s->grid->d;
-    { int rc_; if ((rc_ = plan_set_stream(s->plan_xr2c)) || (rc_ = plan_set_stream(s->plan_xc2r))) return rc_; }
-    // rows of pitch Nxp: whole, 128-B aligned groups of lines
-    FFT_TRY(hipfftExecD2Z(s->plan_xr2c, s->rrhs, (hipfftDoubleComplex *)s->hc));
-    launch_strided_line_fft(*s->opt, s->hc, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 0, 1.0, (long)s->Nxp * g.Ny);
-    double2 *sol = s->hc;
-    if (s->kind == 0) {
-        const double scale = 1.0 / ((double)g.Nx * (double)g.Ny * (double)g.Nz);
-        launch_zline_solve(*s->opt, s->hc, s->ztw, s->lam[0], s->lam[1], s->lam[2], s->Nxh, g.Ny, g.Nz, s->logn_z, scale, s->Nxp);
-    } else {
-        const double scale = 1.0 / ((double)g.Nx * (double)g.Ny);
-        hipLaunchKernelGGL(tridiagonal_z_kernel, dim3((s->Nxh + 63) / 64, g.Ny), dim3(64), 0, g_stream, s->Nxh, g.Nx, g.Ny, g.Nz,
-                           s->lower, s->D, s->lower, s->hc, s->t, s->hc2, scale, true, s->Nxp);
-        hipLaunchKernelGGL(remove_mean_mode_kernel, dim3(1), dim3(256), 0, g_stream, s->hc2, (long)s->Nxp * g.Ny, g.Nz);
-        sol = s->hc2;
-    }
-    launch_strided_line_fft(*s->opt, sol, s->ytw, (long)s->Nxp, (long)s->Nxp, (unsigned)g.Nz, g.Ny, s->logn_y, 1, 1.0, (long)s->Nxp * g.Ny);
-    FFT_TRY(hipfftExecZ2D(s->plan_xc2r, (hipfftDoubleComplex *)sol, s->rrhs));
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-static int solve_for_pressure(ocn_poisson_s *s, const double *u, const double *v, const double *w, double *p) {
-    const DGrid &g = s->grid->d;
-    int rc;
-    if (s->opt->real_fft && !s->general) {
-        if ((rc = source_term(g, u, v, w, s->rrhs, s->kind == 1, true))) return rc;
-        return poisson_solve_real(s, p);
-    }
-    if ((rc = ensure_complex(s))) return rc;
-    if ((rc = source_term(g, u, v, w, s->kind == 0 ? s->storage : s->source, s->kind == 1))) return rc;
-    return poisson_solve(s, p);
-}
-
-extern "C" int ocn_poisson_solve(ocn_poisson_t s, double *phi) {
-    NEED_INIT();
-    if (!s || !phi) return fail(OCN_EINVAL, "NULL argument");
-    return poisson_solve(s, phi);
-}
-
-extern "C" int ocn_solve_for_pressure(ocn_poisson_t s, const double *u, const double *v, const double *w, double *p) {
-    NEED_INIT();
-    if (!s || !u || !v || !w || !p) return fail(OCN_EINVAL, "NULL argument");
-    return solve_for_pressure(s, u, v, w, p);
-}
-
-extern "C" int ocn_batched_tridiagonal_solve_z(int Nx, int Ny, int Nz, const double *a, const double *b, const double *c,
-                                               const double *f_complex, double *t, double *phi_complex) {
-    NEED_INIT();
-    if (Nx < 1 || Ny < 1 || Nz < 1 || !a || !b || !c || !f_complex || !t || !phi_complex) return fail(OCN_EINVAL, "invalid argument");
-    if ((const void *)f_complex == (const void *)phi_complex || (const void *)t == (const void *)b)
-        return fail(OCN_EINVAL, "the right-hand side and the solution (and the scratch and the diagonal) must be distinct arrays");
-    hipLaunchKernelGGL(tridiagonal_z_kernel, dim3((Nx + 63) / 64, Ny), dim3(64), 0, g_stream, Nx, Nx, Ny, Nz, a, b, c,
-                       (const double2 *)f_complex, t, (double2 *)phi_complex, 1.0, false);
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// distributed x-slab pieces (src/DistributedComputations): the collectives themselves (RCCL send/recv, all-to-all) are
-// issued by the host layer through torch.distributed on buffers it owns; the library packs / unpacks / transforms.
-// ---------------------------------------------------------------------------------------------------------------------
-static int x_halo_buffers(const DGrid &g, double *const *fields, const int (*locs)[3], int n, double *west, double *east, bool pack,
-                          int depth = 0) {
-    // a wall side has no neighbour: nothing is unpacked there (what was packed for it is ignored by the other end of the ring)
-    const bool do_west = pack || !wall_lo(g.tx), do_east = pack || !wall_hi(g.tx);
-    if (n <= 0) return OCN_OK;
-    if (depth <= 0) depth = g.Hx;
-    if (depth > g.Hx || depth > g.Nx) return fail(OCN_EINVAL, "exchange depth %d exceeds the halo (%d) or the local interior (%d)", depth, g.Hx, g.Nx);
-    if (n > OCN_MAX_FIELDS) return fail(OCN_EINVAL, "at most %d fields per call", OCN_MAX_FIELDS);
-    FieldList fl;
-    SlabList sl;
-    fl.n = n;
-    int P0 = 0;
-    long off = 0, maxrows = 0;
-    for (int f = 0; f < n; ++f) {
-        int P[3];
-        parent_size(g, locs[f], P);
-        P0 = std::max(P0, P[0]);
-        sl.p0[f] = P[0];                            // Face-in-x fields of a LeftConnected rank are one column longer
-        fl.p[f] = fields[f];
-        sl.off[f] = off;
-        sl.rows[f] = (long)P[1] * P[2];
-        off += (long)depth * sl.rows[f];
-        maxrows = std::max(maxrows, sl.rows[f]);
-    }
-    const long threads = (long)depth * maxrows;
-    const int nb = (int)((threads + 255) / 256);
-    (void)P0;
-    if (pack) hipLaunchKernelGGL(x_halo_buffer_kernel<true>, dim3(nb), dim3(256), 0, g_stream, fl, sl, g.Nx, g.Hx, depth, west, east, true, true);
-    else      hipLaunchKernelGGL(x_halo_buffer_kernel<false>, dim3(nb), dim3(256), 0, g_stream, fl, sl, g.Nx, g.Hx, depth, west, east, do_west, do_east);
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-extern "C" int ocn_pack_x_halos(ocn_grid_t grid, double *const *fields, const int (*locs)[3], int nfields, double *west_send,
-                                double *east_send) {
-    NEED_INIT();
-    if (!grid || !fields || !locs || !west_send || !east_send) return fail(OCN_EINVAL, "NULL argument");
-    return x_halo_buffers(grid->d, fields, locs, nfields, west_send, east_send, true);
-}
-
-extern "C" int ocn_unpack_x_halos(ocn_grid_t grid, double *const *fields, const int (*locs)[3], int nfields,
-                                  const double *west_recv, const double *east_recv) {
-    NEED_INIT();
-    if (!grid || !fields || !locs || !west_recv || !east_recv) return fail(OCN_EINVAL, "NULL argument");
-    return x_halo_buffers(grid->d, fields, locs, nfields, const_cast<double *>(west_recv), const_cast<double *>(east_recv), false);
-}
-
-extern "C" int ocn_pack_x_halos_depth(ocn_grid_t grid, double *const *fields, const int (*locs)[3], int nfields, int depth,
-                                      double *west_send, double *east_send) {
-    NEED_INIT();
-    if (!grid || !fields || !locs || !west_send || !east_send) return fail(OCN_EINVAL, "NULL argument");
-    if (depth < 1) return fail(OCN_EINVAL, "depth must be >= 1");
-    return x_halo_buffers(grid->d, fields, locs, nfields, west_send, east_send, true, depth);
-}
-
-extern "C" int ocn_unpack_x_halos_depth(ocn_grid_t grid, double *const *fields, const int (*locs)[3], int nfields, int depth,
-                                        const double *west_recv, const double *east_recv) {
-    NEED_INIT();
-    if (!grid || !fields || !locs || !west_recv || !east_recv) return fail(OCN_EINVAL, "NULL argument");
-    if (depth < 1) return fail(OCN_EINVAL, "depth must be >= 1");
-    return x_halo_buffers(grid->d, fields, locs, nfields, const_cast<double *>(west_recv), const_cast<double *>(east_recv), false, depth);
-}
-
-// DistributedFFTBasedPoissonSolver (distributed_fft_based_poisson_solver.jl:92-188) and
-// DistributedFourierTridiagonalPoissonSolver (distributed_fft_tridiagonal_solver.jl:153-293) for Partition(R, 1, 1).
-// z is never partitioned on an x-slab decomposition, so both solvers share one pipeline:
-//   local complex transform in (y, z) [z Periodic] or y only [z Bounded] of the PAIRED real columns (see ocn_kernels.h)
-//   -> separate + pack half the y modes -> all-to-all -> x transform -> spectral divide | z-tridiagonal solve
-//   -> inverse x transform -> pack -> all-to-all -> rebuild full spectrum -> inverse local transform -> haloed pressure.
-struct ocn_dist_poisson_s {
-    ocn_grid_t grid;            // LOCAL grid (Nxl, Ny, Nz)
-    const OcnOptions *opt = nullptr;        // the owning model's options (standalone solvers: the library defaults)
-    int R, rank, zmode;         // zmode 0: z Periodic (FFT); 1: z Bounded (tridiagonal solve in the x-local layout)
-    int Nxl, Nxe, Nxh, Nxg, Ny, Nyh, Nyc, Nyp, Nz;
-    size_t nz_c;                // complex elements of the local paired array  Nxh*Ny*Nz
-    size_t nbuf;                // complex elements of xfield / send / recv    Nxl*Nyp*Nz == Nxg*Nyc*Nz
-    double2 *zfield = nullptr;  // (Nxh, Nz, Ny) complex == dense real rhs (Nxe, Nz, Ny)
-    double2 *xfield = nullptr, *xsol = nullptr;   // (Nxg, Nyc, Nz)
-    double2 *send = nullptr, *recv = nullptr;     // borrowed (host layer owns them: torch tensors)
-    double *lam[3] = {nullptr, nullptr, nullptr};
-    double *D = nullptr, *lower = nullptr, *t = nullptr;
-    hipfftHandle plan_loc = 0, plan_x = 0;
-    bool has_loc = false, has_x = false;
-    // zmode 0, Nxg = 2^m <= 4096: the x stage (unpack, FFT, divide, inverse FFT, pack) is one LDS pass (xline_solve_kernel)
-    bool xfused = false;
-    int logn_x = 0, xlines = 1;
-    double2 *xtw = nullptr;
-    // substructured x solve (see ocn_kernels.h): modes M = Nyh*Nz, spectral slab Y (M, Nxl), Thomas factors, s = T⁻¹e₀
-    bool sub = false;
-    long M = 0;
-    double2 *Y = nullptr, *iface = nullptr;
-    double *rden = nullptr, *cpf = nullptr, *svec = nullptr;
-    double2 *payload = nullptr, *gathered = nullptr;     // borrowed (host layer: torch tensors): 2M+1 and R*(2M+1) complex
-    // z-fastest variant of the substructured solve (option dist_zfirst): source term written z-fastest, unit-stride R2C along z, strided
-    // y transform whose output is already in the order the Thomas sweeps want -- no Hermitian separation / re-pairing passes
-    bool zfirst = false;
-    int Nzh = 0, Nzp = 0;       // modes along z (Nz/2 + 1) and the row pitch they are stored with (multiple of 8: whole 128-B lines)
-    double *rreal = nullptr;    // (Nz, Nxl, Ny) real
-    double2 *spec = nullptr;    // (Nzp, Nxl, Ny) complex, modes m = kz + Nzh*ky at [kz + Nzp*(i + Nxl*ky)]
-    hipfftHandle plan_zr2c = 0, plan_zc2r = 0;       // 2-D (y, z) D2Z / Z2D, batched over the local x index (zf_2d) ...
-    hipfftHandle plan_y = 0;                         // ... or 1-D along z plus this strided 1-D y transform
-    // z Bounded, Ny = 2^m <= 1024: the local y transform by strided_line_fft_kernel instead of rocFFT's 1-D strided plan
-    bool yline = false;
-    int logn_y = 0;
-    double2 *ytw = nullptr;
-    bool zf_2d = false;
-    bool has_zf = false;
-    // x-fastest variant of the substructured solve (ocn_kernels.h, "xfast"): dense real array rx (Nx, Ny, Nz), spectrum xs (Nx, Ny, Nz/2 + 1),
-    // Thomas factors rden_x in the spectrum's layout, first / last entry of s = T⁻¹e₀ per mode
-    bool xfast = false;
-    bool src_in_spectrum = false;   // the fused source-term + z transform already filled xs: forward_local skips its z transform
-    int xE = 0, logn_z = 0;
-    double *rx = nullptr, *rden_x = nullptr, *s_first = nullptr, *s_last = nullptr;
-    double2 *xs = nullptr, *ztw = nullptr;
-};
-
-extern "C" int ocn_dist_poisson_destroy(ocn_dist_poisson_t s) {
-    if (!s) return OCN_OK;
-    if (s->has_loc) hipfftDestroy(s->plan_loc);
-    if (s->has_x) hipfftDestroy(s->plan_x);
-    hipFree(s->zfield); hipFree(s->xfield); hipFree(s->xsol); hipFree(s->xtw);
-    hipFree(s->Y); hipFree(s->iface); hipFree(s->rden); hipFree(s->cpf); hipFree(s->svec);
-    hipFree(s->D); hipFree(s->lower); hipFree(s->t);
-    for (int d = 0; d < 3; ++d) hipFree(s->lam[d]);
-    if (s->has_zf) { hipfftDestroy(s->plan_zr2c); hipfftDestroy(s->plan_zc2r); if (!s->zf_2d) hipfftDestroy(s->plan_y); }
-    hipFree(s->rreal); hipFree(s->spec); hipFree(s->ytw);
-    hipFree(s->rx); hipFree(s->rden_x); hipFree(s->s_first); hipFree(s->s_last); hipFree(s->xs); hipFree(s->ztw);
-    delete s;
-    return OCN_OK;
-}
-
-static int dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t local_grid, int R, int rank, double Lx_global, const OcnOptions *opt) {
-    NEED_INIT();
-    if (!solver || !local_grid) return fail(OCN_EINVAL, "NULL argument");
-    const DGrid &g = local_grid->d;
-    if (R < 1 || rank < 0 || rank >= R) return fail(OCN_EINVAL, "invalid rank %d of %d", rank, R);
-    // (one rank with a FullyConnected x is its own neighbour on both sides: the N > 1 code path measured on one GPU)
-    if (g.ty != OCN_PERIODIC || (R > 1 && g.tx != OCN_CONNECTED) || (R == 1 && g.tx != OCN_PERIODIC && g.tx != OCN_CONNECTED))
-        return fail(OCN_ENOTSUP, "the distributed Poisson solvers are accelerated for (Periodic, Periodic, Periodic | Bounded) x-slab partitions");
-    // validate_poisson_solver_distributed_grid (:194-229): Ny must be divisible by Rx
-    if (g.Ny % R != 0) return fail(OCN_EINVAL, "Ny = %d must be divisible by the number of ranks %d (transpose y -> x)", g.Ny, R);
-    const int zmode = g.tz == OCN_BOUNDED ? 1 : 0;
-    if (zmode == 0 && !local_grid->z_regular) return fail(OCN_EINVAL, "DistributedFFTBasedPoissonSolver requires a regular grid");
-    ocn_dist_poisson_s *s = new ocn_dist_poisson_s();
-    s->grid = local_grid; s->opt = opt; s->R = R; s->rank = rank; s->zmode = zmode;
-    s->Nxl = g.Nx; s->Nxe = g.Nx + (g.Nx & 1); s->Nxh = s->Nxe / 2; s->Nxg = g.Nx * R;
-    s->Ny = g.Ny; s->Nyh = g.Ny / 2 + 1; s->Nyc = (s->Nyh + R - 1) / R; s->Nyp = s->Nyc * R; s->Nz = g.Nz;
-    s->nz_c = (size_t)s->Nxh * s->Ny * s->Nz;
-    s->nbuf = (size_t)s->Nxg * s->Nyc * s->Nz;
-    int rc = OCN_OK;
-#define TRY_OR_FREE(expr)                                                                                  \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) { rc = fail((int)e_, "%s: %s", #expr, hipGetErrorString(e_)); goto bad; }   \
-    } while (0)
-    {
-        TRY_OR_FREE(dev_alloc((void **)&s->zfield, s->nz_c * sizeof(double2)));
-        TRY_OR_FREE(dev_alloc((void **)&s->xfield, s->nbuf * sizeof(double2)));
-        TRY_OR_FREE(hipMemset(s->zfield, 0, s->nz_c * sizeof(double2)));
-        TRY_OR_FREE(hipMemset(s->xfield, 0, s->nbuf * sizeof(double2)));
-        const int N[3] = {s->Nxg, s->Ny, s->Nz};
-        const double L[3] = {Lx_global, local_grid->L[1], local_grid->L[2]};
-        std::vector<double> lam[3];
-        for (int d = 0; d < 3; ++d) {
-            poisson_eigenvalues(N[d], L[d], d == 2 ? g.tz : OCN_PERIODIC, lam[d]);
-            TRY_OR_FREE(dev_alloc((void **)&s->lam[d], N[d] * sizeof(double)));
-            TRY_OR_FREE(hipMemcpy(s->lam[d], lam[d].data(), N[d] * sizeof(double), hipMemcpyHostToDevice));
-        }
-        if (zmode == 1) {
-            // diagonals as in the serial solver (fourier_tridiagonal_poisson_solver.jl:180-210), on this rank's modes
-            TRY_OR_FREE(dev_alloc((void **)&s->xsol, s->nbuf * sizeof(double2)));
-            TRY_OR_FREE(hipMemset(s->xsol, 0, s->nbuf * sizeof(double2)));
-            TRY_OR_FREE(dev_alloc((void **)&s->D, s->nbuf * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->t, s->nbuf * sizeof(double)));
-            TRY_OR_FREE(hipMemset(s->t, 0, s->nbuf * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->lower, std::max(1, g.Nz - 1) * sizeof(double)));
-            const int Nz = g.Nz, Hz = g.Hz;
-            auto dzf = [&](int k) { return local_grid->h_dzf[k - 1 + Hz]; };
-            auto dzc = [&](int k) { return local_grid->h_dzc[k - 1 + Hz]; };
-            std::vector<double> D(s->nbuf), lower(std::max(1, Nz - 1));
-            for (int jl = 0; jl < s->Nyc; ++jl) {
-                const int jg = std::min(rank * s->Nyc + jl, s->Ny - 1);
-                for (int i = 0; i < s->Nxg; ++i) {
-                    double lxy = lam[0][i] + lam[1][jg];
-                    auto at = [&](int k) -> double & { return D[(size_t)i + (size_t)s->Nxg * (jl + (size_t)s->Nyc * (k - 1))]; };
-                    if (Nz == 1) { at(1) = -dzc(1) * lxy; continue; }
-                    at(1) = -1.0 / dzf(2) - dzc(1) * lxy;
-                    at(Nz) = -1.0 / dzf(Nz) - dzc(Nz) * lxy;
-                    for (int k = 2; k <= Nz - 1; ++k) at(k) = -(1.0 / dzf(k + 1) + 1.0 / dzf(k)) - dzc(k) * lxy;
-                }
-            }
-            for (int q = 1; q <= Nz - 1; ++q) lower[q - 1] = 1.0 / dzf(q + 1);
-            TRY_OR_FREE(hipMemcpy(s->D, D.data(), s->nbuf * sizeof(double), hipMemcpyHostToDevice));
-            TRY_OR_FREE(hipMemcpy(s->lower, lower.data(), lower.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        hipfftResult r;
-        if (zmode == 0) {
-            // (y, z) transform of (Nxh, Nz, Ny): z stride Nxh, y stride Nxh*Nz, one batch entry per column pair
-            int nyz[2] = {s->Ny, s->Nz};
-            r = hipfftPlanMany(&s->plan_loc, 2, nyz, nyz, s->Nxh, 1, nyz, s->Nxh, 1, HIPFFT_Z2Z, s->Nxh);
-        } else {
-            int ny[1] = {s->Ny};
-            r = hipfftPlanMany(&s->plan_loc, 1, ny, ny, s->Nxh * s->Nz, 1, ny, s->Nxh * s->Nz, 1, HIPFFT_Z2Z, s->Nxh * s->Nz);
-        }
-        if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(local y/z) failed (%d)", (int)r); goto bad; }
-        s->has_loc = true;
-        auto pow2_line = [](int n) { return n >= 8 && n <= OCN_LINE_MAX && (n & (n - 1)) == 0; };
-        if (zmode == 0 && opt->dist_substructured && opt->dist_xfast && (s->Nxl % 2) == 0 && s->Nxl <= 1024 && pow2_line(s->Ny) && pow2_line(s->Nz)) {
-            // ---- x-fastest variant (ocn_kernels.h "xfast") ----
-            s->sub = true; s->xfast = true;
-            s->Nzh = s->Nz / 2 + 1;
-            s->M = (long)s->Ny * s->Nzh;                                     // mode m = ky + Ny kz
-            while ((1 << s->logn_y) < s->Ny) ++s->logn_y;
-            while ((1 << s->logn_z) < s->Nz) ++s->logn_z;
-            s->xE = 1;
-            while (s->xE * 64 < s->Nxl) s->xE *= 2;
-            const size_t nreal = (size_t)s->Nxl * s->Ny * s->Nz, nspec = (size_t)s->Nxl * s->M;
-            TRY_OR_FREE(dev_alloc((void **)&s->rx, nreal * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->xs, nspec * sizeof(double2)));
-            TRY_OR_FREE(dev_alloc((void **)&s->rden_x, nspec * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->s_first, (size_t)s->M * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->s_last, (size_t)s->M * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->iface, (2 * (size_t)s->M + 2) * sizeof(double2)));
-            auto twiddles = [&](int n, double2 **dst) -> hipError_t {
-                std::vector<double2> tw(n / 2);
-                for (int q = 0; q < n / 2; ++q) {
-                    const double ang = -2.0 * M_PI * (double)q / (double)n;
-                    tw[q] = make_double2(cos(ang), sin(ang));
-                }
-                hipError_t e_ = dev_alloc((void **)dst, tw.size() * sizeof(double2));
-                return e_ != hipSuccess ? e_ : hipMemcpy(*dst, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice);
-            };
-            TRY_OR_FREE(twiddles(s->Ny, &s->ytw));
-            TRY_OR_FREE(twiddles(s->Nz, &s->ztw));
-            const double a = 1.0 / (g.dx * g.dx);
-            // mode m = ky + Ny kz: first eigenvalue array indexed with m % Ny, second with m / Ny; the spectrum buffer is the scratch of s
-            hipLaunchKernelGGL(sub_setup_xfast_kernel, dim3((unsigned)((s->M + 255) / 256)), dim3(256), 0, g_stream, s->M, s->Ny, s->Nxl, a, s->lam[1],
-                               s->lam[2], s->rden_x, s->s_first, s->s_last, (double *)(s->iface + 2 * s->M + 1), (double *)s->xs);
-            TRY_OR_FREE(hipGetLastError());
-            // known-answer check of the paired z transform (a round trip cannot tell a mis-read layout from the right one): column 2c
-            // carries cos(2 pi k / N), column 2c + 1 carries sin(2 pi 3 k / N): X_even[1] = N/2, X_odd[3] = -i N/2, everything else 0;
-            // then the way back reproduces the input
-            {
-                const long C = (long)s->Nxl * s->Ny / 2;
-                double *bm = nullptr;
-                TRY_OR_FREE(dev_alloc((void **)&bm, 2 * sizeof(double)));
-                hipLaunchKernelGGL(xfast_kat_fill_kernel, dim3((unsigned)((nreal / 2 + 255) / 256)), dim3(256), 0, g_stream, (double2 *)s->rx, C, s->Nz);
-                launch_paired_zline(*s->opt, true, (const double2 *)s->rx, s->xs, s->ztw, C, s->Nz, s->logn_z, 1.0);
-                hipLaunchKernelGGL(xfast_kat_check_kernel, dim3(1), dim3(256), 0, g_stream, (const double2 *)s->xs, C, s->Nz, bm);
-                launch_paired_zline(*s->opt, false, s->xs, (double2 *)s->rx, s->ztw, C, s->Nz, s->logn_z, 1.0 / (double)s->Nz);
-                hipLaunchKernelGGL(xfast_kat_check_real_kernel, dim3(1), dim3(256), 0, g_stream, (const double2 *)s->rx, C, s->Nz, bm + 1);
-                double err[2] = {1.0, 1.0};
-                hipError_t e_ = hipMemcpyAsync(err, bm, sizeof(err), hipMemcpyDeviceToHost, g_stream);
-                if (e_ == hipSuccess) e_ = hipStreamSynchronize(g_stream);
-                hipFree(bm);
-                if (e_ != hipSuccess) { rc = fail((int)e_, "x-fastest solver self-check: %s", hipGetErrorString(e_)); goto bad; }
-                if (!(err[0] < 1e-10 * s->Nz) || !(err[1] < 1e-12 * s->Nz)) {
-                    rc = fail(OCN_EFFT, "the paired z line transform failed its known-answer check (spectrum %.3g, round trip %.3g)", err[0], err[1]);
-                    goto bad;
-                }
-            }
-        } else if (zmode == 0 && opt->dist_substructured && opt->dist_zfirst) {
-            s->sub = true; s->zfirst = true;
-            s->Nzh = s->Nz / 2 + 1;
-            s->Nzp = (s->Nzh + 7) & ~7;
-            s->M = (long)s->Nzh * s->Ny;
-            const size_t slab = (size_t)s->M * s->Nxl;                       // factor arrays: mode-fastest, unpadded
-            const size_t pslab = (size_t)s->Nzp * s->Nxl * s->Ny;            // the spectrum itself: padded rows
-            TRY_OR_FREE(dev_alloc((void **)&s->rreal, (size_t)s->Nz * s->Nxl * s->Ny * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->spec, pslab * sizeof(double2)));
-            TRY_OR_FREE(hipMemset(s->spec, 0, pslab * sizeof(double2)));
-            TRY_OR_FREE(dev_alloc((void **)&s->rden, slab * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->cpf, slab * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->svec, slab * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->iface, (2 * (size_t)s->M + 2) * sizeof(double2)));
-            const double a = 1.0 / (g.dx * g.dx);
-            // mode m = kz + Nzh*ky: the setup kernel indexes its first eigenvalue array with m % n and the second with m / n
-            hipLaunchKernelGGL(sub_setup_kernel, dim3((unsigned)((s->M + 255) / 256)), dim3(256), 0, g_stream, (int)s->M, s->Nzh, s->Nxl, a,
-                               s->lam[2], s->lam[1], s->rden, s->cpf, s->svec, (double *)(s->iface + 2 * s->M + 1));
-            TRY_OR_FREE(hipGetLastError());
-            // ONE 2-D real plan over (y, z) per direction, the local x index as the batch in the middle of the layout: row pitch
-            // Nz*Nxl (Nzh*Nxl on the complex side), batch distance Nz (Nzh). As a 2-D plan rocFFT runs the strided y pass with its
-            // column kernel; the same pass as a 1-D strided plan gets the 3x slower row kernel (measured: 280 vs 90 us).
-            int nyz[2] = {s->Ny, s->Nz};
-            int remb[2] = {s->Ny, s->Nz * s->Nxl}, cemb[2] = {s->Ny, s->Nzp * s->Nxl};
-            // ... unless Ny = 2^m <= 1024: then the y pass is strided_line_fft_kernel (3x faster again than the column kernel of the 2-D
-            // plan) next to plain 1-D plans along z
-            const bool want_yline = opt->dist_yline && s->Ny >= 8 && s->Ny <= OCN_LINE_MAX && (s->Ny & (s->Ny - 1)) == 0;
-            hipfftResult rz = want_yline ? HIPFFT_NOT_SUPPORTED
-                                         : hipfftPlanMany(&s->plan_zr2c, 2, nyz, remb, 1, s->Nz, cemb, 1, s->Nzp, HIPFFT_D2Z, s->Nxl);
-            if (rz == HIPFFT_SUCCESS) {
-                rz = hipfftPlanMany(&s->plan_zc2r, 2, nyz, cemb, 1, s->Nzp, remb, 1, s->Nz, HIPFFT_Z2D, s->Nxl);
-                if (rz != HIPFFT_SUCCESS) { hipfftDestroy(s->plan_zr2c); s->plan_zr2c = 0; }
-            }
-            s->zf_2d = rz == HIPFFT_SUCCESS;
-            if (!s->zf_2d) {
-                // rocFFT refuses the interleaved-batch 2-D layout for some (small) sizes: 1-D R2C along z + 1-D strided y transform
-                (void)hipGetLastError();
-                int nz1[1] = {s->Nz}, ny1[1] = {s->Ny}, rez[1] = {s->Nz}, cez[1] = {s->Nzp};
-                rz = hipfftPlanMany(&s->plan_zr2c, 1, nz1, rez, 1, s->Nz, cez, 1, s->Nzp, HIPFFT_D2Z, s->Nxl * s->Ny);
-                if (rz == HIPFFT_SUCCESS) rz = hipfftPlanMany(&s->plan_zc2r, 1, nz1, cez, 1, s->Nzp, rez, 1, s->Nz, HIPFFT_Z2D, s->Nxl * s->Ny);
-                if (rz == HIPFFT_SUCCESS)
-                    rz = hipfftPlanMany(&s->plan_y, 1, ny1, ny1, s->Nzp * s->Nxl, 1, ny1, s->Nzp * s->Nxl, 1, HIPFFT_Z2Z, s->Nzp * s->Nxl);
-                if (rz != HIPFFT_SUCCESS) { rc = fail(1000 + (int)rz, "hipfftPlanMany(z-fastest local transforms) failed (%d)", (int)rz); goto bad; }
-                if ((rc = plan_set_stream(s->plan_y))) goto bad;
-                if ((rc = verify_complex_plan(s->plan_y, s->spec, (long)pslab, 1.0 / (double)s->Ny, "distributed y (z-fastest layout)"))) goto bad;
-                if (want_yline) {
-                    while ((1 << s->logn_y) < s->Ny) ++s->logn_y;
-                    std::vector<double2> tw(s->Ny / 2);
-                    for (int m = 0; m < s->Ny / 2; ++m) {
-                        const double ang = -2.0 * M_PI * (double)m / (double)s->Ny;
-                        tw[m] = make_double2(cos(ang), sin(ang));
-                    }
-                    TRY_OR_FREE(dev_alloc((void **)&s->ytw, tw.size() * sizeof(double2)));
-                    TRY_OR_FREE(hipMemcpy(s->ytw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
-                    double2 *ref = nullptr;
-                    double *bm = nullptr;
-                    TRY_OR_FREE(dev_alloc((void **)&ref, pslab * sizeof(double2)));
-                    TRY_OR_FREE(dev_alloc((void **)&bm, 256 * sizeof(double)));
-                    const long C = (long)s->Nzp * s->Nxl;
-                    double err[2] = {-1.0, -1.0};
-                    bool ok = true;
-                    for (int dir = 0; dir < 2 && ok; ++dir) {      // accept the kernel only if it reproduces the library transform
-                        hipLaunchKernelGGL(selfcheck_fill_complex, dim3((unsigned)((pslab + 255) / 256)), dim3(256), 0, g_stream, s->spec, (long)pslab);
-                        ok = hipMemcpyAsync(ref, s->spec, pslab * sizeof(double2), hipMemcpyDeviceToDevice, g_stream) == hipSuccess &&
-                             hipfftExecZ2Z(s->plan_y, (hipfftDoubleComplex *)ref, (hipfftDoubleComplex *)ref, dir ? HIPFFT_BACKWARD : HIPFFT_FORWARD) == HIPFFT_SUCCESS;
-                        launch_strided_line_fft(*s->opt, s->spec, s->ytw, C, C, 1, s->Ny, s->logn_y, dir, 1.0);
-                        hipLaunchKernelGGL(max_abs_diff_kernel, dim3(256), dim3(256), 0, g_stream, (const double *)ref, (const double *)s->spec,
-                                           2 * (long)pslab, bm);
-                        ok = ok && reduce_blockmax(bm, 256, &err[dir]) == OCN_OK;
-                    }
-                    hipFree(ref); hipFree(bm);
-                    s->yline = ok && err[0] >= 0 && err[1] >= 0 && err[0] < 1e-10 * s->Ny && err[1] < 1e-10 * s->Ny;
-                    (void)hipGetLastError();
-                }
-            }
-            TRY_OR_FREE(hipMemsetAsync(s->spec, 0, pslab * sizeof(double2), g_stream));     // the self-checks wrote into the padding
-            s->has_zf = true;
-            if ((rc = plan_set_stream(s->plan_zr2c)) || (rc = plan_set_stream(s->plan_zc2r))) goto bad;
-            if (s->zf_2d) {
-                // a round trip cannot tell a transform of a mis-read layout from the right one: check the 2-D plan's spectrum against
-                // plain 1-D plans once (pseudo-random data), then drop them
-                hipfftHandle pz = 0, py = 0;
-                int nz1[1] = {s->Nz}, ny1[1] = {s->Ny}, rez2[1] = {s->Nz}, cez2[1] = {s->Nzp};
-                double2 *ref = nullptr;
-                double *bm = nullptr;
-                const long nreal = (long)s->Nz * s->Nxl * s->Ny;
-                hipfftResult r1 = hipfftPlanMany(&pz, 1, nz1, rez2, 1, s->Nz, cez2, 1, s->Nzp, HIPFFT_D2Z, s->Nxl * s->Ny);
-                hipfftResult r2 = r1 == HIPFFT_SUCCESS ? hipfftPlanMany(&py, 1, ny1, ny1, s->Nzp * s->Nxl, 1, ny1, s->Nzp * s->Nxl, 1, HIPFFT_Z2Z, s->Nzp * s->Nxl) : r1;
-                bool ok = r1 == HIPFFT_SUCCESS && r2 == HIPFFT_SUCCESS && dev_alloc((void **)&ref, pslab * sizeof(double2)) == hipSuccess &&
-                          dev_alloc((void **)&bm, 256 * sizeof(double)) == hipSuccess;
-                double err = -1.0;
-                if (ok) {
-                    hipfftSetStream(pz, g_stream); hipfftSetStream(py, g_stream);
-                    hipLaunchKernelGGL(selfcheck_fill_real, dim3((unsigned)((nreal + 255) / 256)), dim3(256), 0, g_stream, s->rreal, nreal);
-                    ok = hipMemsetAsync(ref, 0, pslab * sizeof(double2), g_stream) == hipSuccess && hipfftExecD2Z(pz, s->rreal, (hipfftDoubleComplex *)ref) == HIPFFT_SUCCESS &&
-                         hipfftExecZ2Z(py, (hipfftDoubleComplex *)ref, (hipfftDoubleComplex *)ref, HIPFFT_FORWARD) == HIPFFT_SUCCESS &&
-                         hipfftExecD2Z(s->plan_zr2c, s->rreal, (hipfftDoubleComplex *)s->spec) == HIPFFT_SUCCESS;
-                    if (ok) {
-                        hipLaunchKernelGGL(max_abs_diff_kernel, dim3(256), dim3(256), 0, g_stream, (const double *)ref, (const double *)s->spec,
-                                           2 * (long)pslab, bm);
-                        ok = reduce_blockmax(bm, 256, &err) == OCN_OK;
-                    }
-                }
-                if (pz) hipfftDestroy(pz);
-                if (py) hipfftDestroy(py);
-                hipFree(ref); hipFree(bm);
-                if (!ok || !(err >= 0.0 && err < 1e-9 * (double)s->Ny * (double)s->Nz)) {
-                    rc = fail(OCN_EFFT, "the 2-D (y, z) real plan disagrees with 1-D plans (max difference %.3g): refusing it", err);
-                    goto bad;
-                }
-            }
-            {   // real pair: fill, R2C, C2R, compare
-                const long n = (long)s->Nz * s->Nxl * s->Ny;
-                const int nb = 256;
-                double *bm = nullptr;
-                TRY_OR_FREE(dev_alloc((void **)&bm, nb * sizeof(double)));
-                hipLaunchKernelGGL(selfcheck_fill_real, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, s->rreal, n);
-                hipfftResult r1 = hipfftExecD2Z(s->plan_zr2c, s->rreal, (hipfftDoubleComplex *)s->spec);
-                if (r1 == HIPFFT_SUCCESS) r1 = hipfftExecZ2D(s->plan_zc2r, (hipfftDoubleComplex *)s->spec, s->rreal);
-                hipLaunchKernelGGL(selfcheck_compare_real, dim3(nb), dim3(256), 0, g_stream, s->rreal, s->Nz, s->Nxl, s->Ny, s->Nz, s->Nxl, 0, 0, 0,
-                                   s->zf_2d ? 1.0 / ((double)s->Nz * (double)s->Ny) : 1.0 / (double)s->Nz, bm);
-                double err = 0;
-                rc = r1 == HIPFFT_SUCCESS ? reduce_blockmax(bm, nb, &err) : fail(1000 + (int)r1, "hipFFT exec failed in the plan self-check (%d)", (int)r1);
-                hipFree(bm);
-                if (rc) goto bad;
-                if (!(err < 1e-10)) { rc = fail(OCN_EFFT, "rocFFT self-check failed for the (y, z) real transform pair (round-trip error %.3g)", err); goto bad; }
-            }
-        } else if (zmode == 0 && opt->dist_substructured) {
-            s->sub = true;
-            s->M = (long)s->Nyh * s->Nz;
-            const size_t slab = (size_t)s->M * s->Nxl;
-            TRY_OR_FREE(dev_alloc((void **)&s->Y, slab * sizeof(double2)));
-            TRY_OR_FREE(dev_alloc((void **)&s->rden, slab * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->cpf, slab * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->svec, slab * sizeof(double)));
-            TRY_OR_FREE(dev_alloc((void **)&s->iface, (2 * (size_t)s->M + 2) * sizeof(double2)));      // + one slot: Σ s of the null mode
-            const double a = 1.0 / (g.dx * g.dx);
-            hipLaunchKernelGGL(sub_setup_kernel, dim3((unsigned)((s->M + 255) / 256)), dim3(256), 0, g_stream, (int)s->M, s->Nyh, s->Nxl, a,
-                               s->lam[1], s->lam[2], s->rden, s->cpf, s->svec, (double *)(s->iface + 2 * s->M + 1));
-            TRY_OR_FREE(hipGetLastError());
-        }
-        if (!s->sub && zmode == 0 && opt->fused_zfft && s->Nxg >= 8 && s->Nxg <= 4096 && (s->Nxg & (s->Nxg - 1)) == 0) {
-            s->xfused = true;
-            while ((1 << s->logn_x) < s->Nxg) ++s->logn_x;
-            s->xlines = std::max(1, 4096 / s->Nxg);           // 64 KB of LDS per workgroup
-            std::vector<double2> tw(s->Nxg / 2);
-            for (int m = 0; m < s->Nxg / 2; ++m) {
-                const double a = -2.0 * M_PI * (double)m / (double)s->Nxg;
-                tw[m] = make_double2(cos(a), sin(a));
-            }
-            TRY_OR_FREE(dev_alloc((void **)&s->xtw, tw.size() * sizeof(double2)));
-            TRY_OR_FREE(hipMemcpy(s->xtw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
-        }
-        if ((rc = plan_set_stream(s->plan_loc))) goto bad;
-        const double sc = zmode == 0 ? 1.0 / ((double)s->Ny * s->Nz) : 1.0 / (double)s->Ny;
-        if ((rc = verify_complex_plan(s->plan_loc, s->zfield, (long)s->nz_c, sc, "distributed local (y, z)"))) goto bad;
-        if (zmode == 1 && opt->dist_yline && s->Ny >= 8 && s->Ny <= OCN_LINE_MAX && (s->Ny & (s->Ny - 1)) == 0) {
-            while ((1 << s->logn_y) < s->Ny) ++s->logn_y;
-            std::vector<double2> tw(s->Ny / 2);
-            for (int m = 0; m < s->Ny / 2; ++m) {
-                const double ang = -2.0 * M_PI * (double)m / (double)s->Ny;
-                tw[m] = make_double2(cos(ang), sin(ang));
-            }
-            TRY_OR_FREE(dev_alloc((void **)&s->ytw, tw.size() * sizeof(double2)));
-            TRY_OR_FREE(hipMemcpy(s->ytw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
-            // accept the kernel only if it reproduces the library transform on pseudo-random data (both directions)
-            double2 *ref = nullptr;
-            double *bm = nullptr;
-            TRY_OR_FREE(dev_alloc((void **)&ref, s->nz_c * sizeof(double2)));
-            TRY_OR_FREE(dev_alloc((void **)&bm, 256 * sizeof(double)));
-            const long C = (long)s->Nxh * s->Nz;
-            double err[2] = {-1.0, -1.0};
-            bool ok = true;
-            for (int dir = 0; dir < 2 && ok; ++dir) {
-                hipLaunchKernelGGL(selfcheck_fill_complex, dim3((unsigned)((s->nz_c + 255) / 256)), dim3(256), 0, g_stream, s->zfield, (long)s->nz_c);
-                ok = hipMemcpyAsync(ref, s->zfield, s->nz_c * sizeof(double2), hipMemcpyDeviceToDevice, g_stream) == hipSuccess &&
-                     hipfftExecZ2Z(s->plan_loc, (hipfftDoubleComplex *)ref, (hipfftDoubleComplex *)ref, dir ? HIPFFT_BACKWARD : HIPFFT_FORWARD) == HIPFFT_SUCCESS;
-                launch_strided_line_fft(*s->opt, s->zfield, s->ytw, C, C, 1, s->Ny, s->logn_y, dir, 1.0);
-                hipLaunchKernelGGL(max_abs_diff_kernel, dim3(256), dim3(256), 0, g_stream, (const double *)ref, (const double *)s->zfield,
-                                   2 * (long)s->nz_c, bm);
-                ok = ok && reduce_blockmax(bm, 256, &err[dir]) == OCN_OK;
-            }
-            hipFree(ref); hipFree(bm);
-            s->yline = ok && err[0] >= 0 && err[1] >= 0 && err[0] < 1e-10 * s->Ny && err[1] < 1e-10 * s->Ny;
-            (void)hipGetLastError();
-        }
-        if (!s->xfused && !s->sub) {
-            int nx[1] = {s->Nxg};
-            r = hipfftPlanMany(&s->plan_x, 1, nx, nullptr, 1, s->Nxg, nullptr, 1, s->Nxg, HIPFFT_Z2Z, s->Nyc * s->Nz);
-            if (r != HIPFFT_SUCCESS) { rc = fail(1000 + (int)r, "hipfftPlanMany(x) failed (%d)", (int)r); goto bad; }
-            s->has_x = true;
-            if ((rc = plan_set_stream(s->plan_x))) goto bad;
-            if ((rc = verify_complex_plan(s->plan_x, s->xfield, (long)s->nbuf, 1.0 / (double)s->Nxg, "distributed x"))) goto bad;
-        }
-    }
-    *solver = s;
-    return OCN_OK;
-bad:
-    ocn_dist_poisson_destroy(s);
-    return rc;
-#undef TRY_OR_FREE
-}
-extern "C" int ocn_dist_poisson_create(ocn_dist_poisson_t *solver, ocn_grid_t local_grid, int R, int rank, double Lx_global) {
-    return dist_poisson_create(solver, local_grid, R, rank, Lx_global, &g_defaults);
-}
-
-extern "C" int ocn_dist_poisson_buffer_size(ocn_dist_poisson_t s, size_t *complex_elements) {
-    if (!s || !complex_elements) return fail(OCN_EINVAL, "NULL argument");
-    *complex_elements = s->nbuf;
-    return OCN_OK;
-}
-
-// 0: paired-column layout; 1: z-fastest layout with 1-D plans; 2: z-fastest layout with the 2-D (y, z) real plans; 3: z-fastest with the LDS
-// y-line kernel; 4: x-fastest layout (paired z transform in LDS, Thomas scans); -1 transposing solver
-extern "C" int ocn_dist_poisson_layout(ocn_dist_poisson_t s, int *layout) {
-    if (!s || !layout) return fail(OCN_EINVAL, "NULL argument");
-    *layout = !s->sub ? -1 : (s->xfast ? 4 : (!s->zfirst ? 0 : (s->yline ? 3 : (s->zf_2d ? 2 : 1))));
-    return OCN_OK;
-}
-
-// substructured mode: complex elements of the per-rank payload (first / last value per mode + the null mode's sum); 0 otherwise
-extern "C" int ocn_dist_poisson_payload_size(ocn_dist_poisson_t s, size_t *complex_elements) {
-    if (!s || !complex_elements) return fail(OCN_EINVAL, "NULL argument");
-    *complex_elements = s->sub ? 2 * (size_t)s->M + 1 : 0;
-    return OCN_OK;
-}
-
-extern "C" int ocn_dist_poisson_set_gather_buffers(ocn_dist_poisson_t s, double *payload_complex, double *gathered_complex) {
-    if (!s || !payload_complex || !gathered_complex) return fail(OCN_EINVAL, "NULL argument");
-    if (!s->sub) return fail(OCN_ESTATE, "this solver transposes (all-to-all); it has no gather buffers");
-    s->payload = (double2 *)payload_complex; s->gathered = (double2 *)gathered_complex;
-    return OCN_OK;
-}
-
-// substructured mode, stage 1: local (y, z) transform, column separation, Thomas sweeps along x, payload. Afterwards the host layer
-// runs all_gather(gathered, payload).
-extern "C" int ocn_dist_poisson_forward_local(ocn_dist_poisson_t s) {
-    NEED_INIT();
-    if (!s || !s->sub || !s->payload) return fail(OCN_EINVAL, "substructured solver / gather buffers not set");
-    int rc;
-    const double a = 1.0 / (s->grid->d.dx * s->grid->d.dx);
-    if (s->xfast) {
-        const long C = (long)s->Nxl * s->Ny / 2, P = (long)s->Nxl * s->Ny;
-        if (!s->src_in_spectrum) launch_paired_zline(*s->opt, true, (const double2 *)s->rx, s->xs, s->ztw, C, s->Nz, s->logn_z, 1.0);
-        s->src_in_spectrum = false;
-        launch_strided_line_fft(*s->opt, s->xs, s->ytw, (long)s->Nxl, (long)s->Nxl, (unsigned)s->Nzh, s->Ny, s->logn_y, 0, 1.0, P);
-        launch_xline_thomas<false>(*s->opt, s->xE, s->xs, s->rden_x, s->M, s->Nxl, a, s->payload, nullptr, 1.0);      // reads only: the payload
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    if (s->zfirst) {
-        if ((rc = plan_set_stream(s->plan_zr2c))) return rc;
-        FFT_TRY(hipfftExecD2Z(s->plan_zr2c, s->rreal, (hipfftDoubleComplex *)s->spec));
-        if (s->yline) {
-            const long C = (long)s->Nzp * s->Nxl;
-            launch_strided_line_fft(*s->opt, s->spec, s->ytw, C, C, 1, s->Ny, s->logn_y, 0, 1.0);
-        } else if (!s->zf_2d) {
-            if ((rc = plan_set_stream(s->plan_y))) return rc;
-            FFT_TRY(hipfftExecZ2Z(s->plan_y, (hipfftDoubleComplex *)s->spec, (hipfftDoubleComplex *)s->spec, HIPFFT_FORWARD));
-        }
-        hipLaunchKernelGGL(sub_thomas_kernel<true>, dim3((unsigned)((s->M + 63) / 64)), dim3(64), 0, g_stream, s->M, s->Nxl, a, s->rden, s->cpf,
-                           s->spec, s->payload, s->Nzh, s->Nzp);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    if ((rc = plan_set_stream(s->plan_loc))) return rc;
-    FFT_TRY(hipfftExecZ2Z(s->plan_loc, (hipfftDoubleComplex *)s->zfield, (hipfftDoubleComplex *)s->zfield, HIPFFT_FORWARD));
-    const dim3 blk(16, 16), grd((s->Nxh + 15) / 16, (s->Nyh + 15) / 16, s->Nz);
-    hipLaunchKernelGGL(sub_separate_kernel, grd, blk, 0, g_stream, s->zfield, s->Y, s->Nxl, s->Nxh, s->Ny, s->Nyh, s->Nz);
-    hipLaunchKernelGGL(sub_thomas_kernel<false>, dim3((unsigned)((s->M + 63) / 64)), dim3(64), 0, g_stream, s->M, s->Nxl, a, s->rden, s->cpf, s->Y,
-                       s->payload, 1, 1);
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-// substructured mode, stage 2: interface unknowns from the gathered payloads, slab correction, rebuild the paired spectrum,
-// inverse local transform, copy into the haloed pressure
-static int dist_poisson_backward_local(ocn_dist_poisson_t s, double *phi, bool keep_zfast);
-extern "C" int ocn_dist_poisson_backward_local(ocn_dist_poisson_t s, double *phi) {
-    NEED_INIT();
-    if (!s || !s->sub || !s->gathered || !phi) return fail(OCN_EINVAL, "substructured solver / gather buffers not set");
-    return dist_poisson_backward_local(s, phi, false);
-}
-// keep_zfast (z-fastest layout only): leave the solution in the solver's dense z-fastest real array (s->rreal) instead of copying it
-// into a haloed field -- the partitioned model's pressure correction reads it there (pressure_correction_zfast_kernel)
-static int dist_poisson_backward_local(ocn_dist_poisson_t s, double *phi, bool keep_zfast) {
-    const DGrid &g = s->grid->d;
-    const double a = 1.0 / (g.dx * g.dx);
-    const double scale = 1.0 / ((double)s->Ny * (double)s->Nz);
-    if (s->xfast) {
-        // interface unknowns, then the SAME line solve on the right-hand side that carries them in its two end entries: the final solution
-        hipLaunchKernelGGL(sub_interface_kernel, dim3((unsigned)((s->M + 255) / 256)), dim3(256), 0, g_stream, s->M, s->Ny, s->Nxl, s->R, s->rank,
-                           a, s->lam[1], s->lam[2], s->s_first, s->s_last, (const double *)(s->iface + 2 * s->M + 1), s->gathered, s->iface);
-        launch_xline_thomas<true>(*s->opt, s->xE, s->xs, s->rden_x, s->M, s->Nxl, a, nullptr, s->iface, scale);
-        const long C = (long)s->Nxl * s->Ny / 2, P = (long)s->Nxl * s->Ny;
-        launch_strided_line_fft(*s->opt, s->xs, s->ytw, (long)s->Nxl, (long)s->Nxl, (unsigned)s->Nzh, s->Ny, s->logn_y, 1, 1.0, P);
-        launch_paired_zline(*s->opt, false, s->xs, (double2 *)s->rx, s->ztw, C, s->Nz, s->logn_z, 1.0);
-        if (!keep_zfast && !phi) return fail(OCN_EINVAL, "NULL pressure field");
-        if (!keep_zfast)           // (here: keep the dense x-fastest solution in s->rx)
-            hipLaunchKernelGGL(copy_dense_to_field_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, phi, LOC_C), (const double *)s->rx);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    hipLaunchKernelGGL(sub_interface_kernel, dim3((unsigned)((s->M + 255) / 256)), dim3(256), 0, g_stream, s->M, s->Nyh, s->Nxl, s->R, s->rank,
-                       a, s->lam[1], s->lam[2], s->svec, s->svec + s->M * (long)(s->Nxl - 1), (const double *)(s->iface + 2 * s->M + 1), s->gathered, s->iface);
-    if (s->zfirst) {
-        const long total = (long)s->Nzp * s->Nxl * s->Ny;
-        hipLaunchKernelGGL(sub_correct_zfast_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g_stream, s->spec, s->svec, s->iface,
-                           s->M, s->Nxl, s->Nzh, s->Ny, a, scale, s->Nzp);
-        int rcz;
-        if (s->yline) {
-            const long C = (long)s->Nzp * s->Nxl;
-            launch_strided_line_fft(*s->opt, s->spec, s->ytw, C, C, 1, s->Ny, s->logn_y, 1, 1.0);
-        } else if (!s->zf_2d) {
-            if ((rcz = plan_set_stream(s->plan_y))) return rcz;
-            FFT_TRY(hipfftExecZ2Z(s->plan_y, (hipfftDoubleComplex *)s->spec, (hipfftDoubleComplex *)s->spec, HIPFFT_BACKWARD));
-        }
-        if ((rcz = plan_set_stream(s->plan_zc2r))) return rcz;
-        FFT_TRY(hipfftExecZ2D(s->plan_zc2r, (hipfftDoubleComplex *)s->spec, s->rreal));
-        if (!keep_zfast && !phi) return fail(OCN_EINVAL, "NULL pressure field");
-        if (!keep_zfast)
-            hipLaunchKernelGGL(copy_real_zfast_kernel, dim3((g.Nx + 31) / 32, (g.Nz + 31) / 32, g.Ny), dim3(32, 8), 0, g_stream, g,
-                               make_view(g, phi, LOC_C), s->rreal);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    const dim3 blk(16, 16), grd((s->Nxh + 15) / 16, (s->Nyh + 15) / 16, s->Nz);
-    hipLaunchKernelGGL(sub_correct_combine_kernel, grd, blk, 0, g_stream, s->Y, s->svec, s->iface, s->zfield, s->Nxl, s->Nxh, s->Ny, s->Nyh,
-                       s->Nz, a, scale);
-    int rc;
-    if ((rc = plan_set_stream(s->plan_loc))) return rc;
-    FFT_TRY(hipfftExecZ2Z(s->plan_loc, (hipfftDoubleComplex *)s->zfield, (hipfftDoubleComplex *)s->zfield, HIPFFT_BACKWARD));
-    if (!phi) return fail(OCN_EINVAL, "this layout of the substructured solver writes the haloed pressure field: NULL given");
-    hipLaunchKernelGGL(dist_copy_real_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, phi, LOC_C),
-                       (const double *)s->zfield, s->Nxe);
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-extern "C" int ocn_dist_poisson_set_buffers(ocn_dist_poisson_t s, double *send_complex, double *recv_complex) {
-    if (!s || !send_complex || !recv_complex) return fail(OCN_EINVAL, "NULL argument");
-    s->send = (double2 *)send_complex; s->recv = (double2 *)recv_complex;
-    return OCN_OK;
-}
-
-// compute_source_term! into the solver's paired-column real storage (solve_for_pressure.jl:12-84; weighted by Δzᶜ for the
-// tridiagonal solver)
-extern "C" int ocn_dist_poisson_source_term(ocn_dist_poisson_t s, const double *u, const double *v, const double *w) {
-    NEED_INIT();
-    if (!s || !u || !v || !w) return fail(OCN_EINVAL, "NULL argument");
-    if (s->xfast) return source_term(s->grid->d, u, v, w, s->rx, false, true);
-    if (s->zfirst) {
-        const DGrid &g = s->grid->d;
-        hipLaunchKernelGGL(source_term_zfast_kernel, dim3((g.Nx + 31) / 32, (g.Nz + 31) / 32, g.Ny), dim3(32, 8), 0, g_stream, g,
-                           make_view(g, u, LOC_U), make_view(g, v, LOC_V), make_view(g, w, LOC_W), s->rreal);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    return source_term(s->grid->d, u, v, w, s->zfield, s->zmode == 1, true, (long)s->Nxe * s->Nz, (long)s->Nxe, s->Nxe != s->Nxl);
-}
-
-// the partitioned model's form (z-fastest layout): no halo is read -- y / z neighbours at wrapped interior indices, u[Nx+1] from `u_east`, the
-// (Ny, Nz) column received by the one-column exchange
-static int dist_poisson_source_term_wrapped(ocn_dist_poisson_t s, const double *u, const double *v, const double *w, const double *u_east) {
-    const DGrid &g = s->grid->d;
-    if (s->xfast && s->opt->dist_fuse_source) {
-        const long C = (long)s->Nxl * s->Ny / 2;
-        const int zl = line_zl(*s->opt, s->Nz);
-        const dim3 grd((unsigned)((C + zl - 1) / zl));
-        const size_t lds = (size_t)s->Nz * zl * sizeof(double2);
-        const FView fu = make_view(g, u, LOC_U), fv = make_view(g, v, LOC_V), fw = make_view(g, w, LOC_W);
-        if (zl == 4) hipLaunchKernelGGL(source_paired_zline_r2c_kernel<4>, grd, dim3(256), lds, g_stream, g, fu, fv, fw, u_east, s->xs, s->ztw, C, s->Nz, s->logn_z);
-        else         hipLaunchKernelGGL(source_paired_zline_r2c_kernel<8>, grd, dim3(256), lds, g_stream, g, fu, fv, fw, u_east, s->xs, s->ztw, C, s->Nz, s->logn_z);
-        KERNEL_CHECK();
-        s->src_in_spectrum = true;
-        return OCN_OK;
-    }
-    if (s->xfast) {
-        hipLaunchKernelGGL(source_term_dense_wrapped_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, u, LOC_U), make_view(g, v, LOC_V),
-                           make_view(g, w, LOC_W), u_east, s->rx);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    if (!s->zfirst)     // transposing solvers (paired-column layout): y wraps (Periodic), z wraps when Periodic; a Bounded z reads its wall faces
-        return source_term(g, u, v, w, s->zfield, s->zmode == 1, true, (long)s->Nxe * s->Nz, (long)s->Nxe, s->Nxe != s->Nxl, false,
-                           2 | (s->zmode == 0 ? 4 : 0), u_east);
-    hipLaunchKernelGGL(source_term_zfast_wrapped_kernel, dim3((g.Nx + 31) / 32, (g.Nz + 31) / 32, g.Ny), dim3(32, 8), 0, g_stream, g,
-                       make_view(g, u, LOC_U), make_view(g, v, LOC_V), make_view(g, w, LOC_W), u_east, s->rreal);
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-static int transpose_stage(ocn_dist_poisson_s *s, int dir, const double2 *src, double2 *dst) {
-    const long total = (long)s->nbuf;
-    hipLaunchKernelGGL(transpose_stage_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g_stream, dir, s->R, s->Nxl, s->Nyc,
-                       s->Nz, src, dst);
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-// stage 1: local forward transform (:148-151), separate the column pairs and pack for transpose_y_to_x!. Afterwards the
-// host layer runs all_to_all(recv, send).
-extern "C" int ocn_dist_poisson_forward_yz(ocn_dist_poisson_t s) {
-    NEED_INIT();
-    if (!s || !s->send) return fail(OCN_EINVAL, "solver / buffers not set");
-    int rc;
-    if (s->yline) {
-        const long C = (long)s->Nxh * s->Nz;
-        launch_strided_line_fft(*s->opt, s->zfield, s->ytw, C, C, 1, s->Ny, s->logn_y, 0, 1.0);
-    } else {
-        if ((rc = plan_set_stream(s->plan_loc))) return rc;
-        FFT_TRY(hipfftExecZ2Z(s->plan_loc, (hipfftDoubleComplex *)s->zfield, (hipfftDoubleComplex *)s->zfield, HIPFFT_FORWARD));
-    }
-    hipLaunchKernelGGL(dist_pack_forward_kernel, grid3(s->Nxh, s->Nyp, s->Nz, BLK), BLK, 0, g_stream, s->zfield, s->send, s->Nxl, s->Nxh,
-                       s->Ny, s->Nyh, s->Nyc, s->Nyp, s->Nz, s->zmode == 0);
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-// stage 2: unpack into the x-local layout, forward FFT in x, spectral divide | tridiagonal solve, backward FFT in x
-// (:152-166), pack for transpose_x_to_y!. Afterwards the host layer runs all_to_all(recv, send) again.
-extern "C" int ocn_dist_poisson_solve_x(ocn_dist_poisson_t s) {
-    NEED_INIT();
-    if (!s || !s->send) return fail(OCN_EINVAL, "solver / buffers not set");
-    int rc;
-    if (s->xfused) {
-        // send may alias recv (one rank): a workgroup reads all of its lines before it writes them back
-        const double scale = 1.0 / ((double)s->Nxg * (double)s->Ny * (double)s->Nz);
-        const long nlines = (long)s->Nyc * s->Nz;
-        const unsigned nb = (unsigned)((nlines + s->xlines - 1) / s->xlines);
-        hipLaunchKernelGGL(xline_solve_kernel, dim3(nb), dim3(256), (size_t)s->xlines * s->Nxg * sizeof(double2), g_stream, s->recv, s->send,
-                           s->xtw, s->lam[0], s->lam[1], s->lam[2], s->R, s->Nxl, s->Nyc, s->Nz, s->logn_x, s->xlines, s->rank * s->Nyc,
-                           s->Ny, scale);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    if ((rc = transpose_stage(s, 1, s->recv, s->xfield))) return rc;
-    if ((rc = plan_set_stream(s->plan_x))) return rc;
-    FFT_TRY(hipfftExecZ2Z(s->plan_x, (hipfftDoubleComplex *)s->xfield, (hipfftDoubleComplex *)s->xfield, HIPFFT_FORWARD));
-    double2 *sol = s->xfield;
-    if (s->zmode == 0) {
-        const double scale = 1.0 / ((double)s->Nxg * (double)s->Ny * (double)s->Nz);
-        hipLaunchKernelGGL(dist_spectral_divide_kernel, grid3(s->Nxg, s->Nyc, s->Nz, BLK), BLK, 0, g_stream, s->xfield, s->lam[0],
-                           s->lam[1], s->lam[2], s->Nxg, s->Nyc, s->Nz, s->rank * s->Nyc, s->Ny, scale);
-    } else {
-        const double scale = 1.0 / ((double)s->Nxg * (double)s->Ny);
-        hipLaunchKernelGGL(tridiagonal_z_kernel, dim3((s->Nxg + 63) / 64, s->Nyc), dim3(64), 0, g_stream, s->Nxg, s->Nxg, s->Nyc, s->Nz,
-                           s->lower, s->D, s->lower, s->xfield, s->t, s->xsol, scale, true);
-        // the serial solver subtracts the mean (fourier_tridiagonal_poisson_solver.jl:233); the reference's distributed
-        // solver does not -- the difference is a constant in p, which only its gradient uses. Kept identical to the
-        // single-GPU path: the (0, 0) column lives on rank 0.
-        if (s->rank == 0)
-            hipLaunchKernelGGL(remove_mean_mode_kernel, dim3(1), dim3(256), 0, g_stream, s->xsol, (long)s->Nxg * s->Nyc, s->Nz);
-        sol = s->xsol;
-    }
-    FFT_TRY(hipfftExecZ2Z(s->plan_x, (hipfftDoubleComplex *)sol, (hipfftDoubleComplex *)sol, HIPFFT_BACKWARD));
-    return transpose_stage(s, 2, sol, s->send);
-}
-
-// stage 3: rebuild the paired spectrum, local backward transform, copy into the haloed pressure (:167-178)
-static int dist_poisson_backward_yz(ocn_dist_poisson_t s, double *phi, bool keep_dense);
-extern "C" int ocn_dist_poisson_backward_yz(ocn_dist_poisson_t s, double *phi) {
-    NEED_INIT();
-    if (!s || !s->recv || !phi) return fail(OCN_EINVAL, "solver / buffers not set");
-    return dist_poisson_backward_yz(s, phi, false);
-}
-// keep_dense: leave the solution in the paired-column real array (element (i, j, k) at (i-1) + Nxe ((k-1) + Nz (j-1)) of s->zfield) for the
-// partitioned model's dense pressure correction instead of copying it into a haloed field
-static int dist_poisson_backward_yz(ocn_dist_poisson_t s, double *phi, bool keep_dense) {
-    const DGrid &g = s->grid->d;
-    int rc;
-    hipLaunchKernelGGL(dist_combine_backward_kernel, grid3(s->Nxh, s->Ny, s->Nz, BLK), BLK, 0, g_stream, s->recv, s->zfield, s->Nxl, s->Nxh,
-                       s->Ny, s->Nyh, s->Nyc, s->Nz, s->zmode == 0);
-    if (s->yline) {
-        const long C = (long)s->Nxh * s->Nz;
-        launch_strided_line_fft(*s->opt, s->zfield, s->ytw, C, C, 1, s->Ny, s->logn_y, 1, 1.0);
-    } else {
-        if ((rc = plan_set_stream(s->plan_loc))) return rc;
-        FFT_TRY(hipfftExecZ2Z(s->plan_loc, (hipfftDoubleComplex *)s->zfield, (hipfftDoubleComplex *)s->zfield, HIPFFT_BACKWARD));
-    }
-    if (!keep_dense) {
-        if (!phi) return fail(OCN_EINVAL, "NULL pressure field");
-        hipLaunchKernelGGL(dist_copy_real_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, phi, LOC_C),
-                           (const double *)s->zfield, s->Nxe);
-    }
-    KERNEL_CHECK();
-    return OCN_OK;
-}
+#include "ocn_poisson.h"
+#include "ocn_dist_poisson.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // model
