@@ -122,6 +122,28 @@ int ocn_compute_flux_bcs(ocn_grid_t grid, double *G, const int loc[3], const ocn
  * (identity interpolation). examples/ocean_wind_mixing_and_convection.jl:125-136: a = 0, b = -evaporation_rate, φ = S. General
  * callables cannot cross a C ABI; this family covers relaxation / evaporation / linear-drag conditions. */
 int ocn_compute_linear_flux_bc(ocn_grid_t grid, double *G, const int loc[3], int side, double a, double b, const double *dep);
+/* One boundary step of OpenBoundaryCondition(value; scheme = PerturbationAdvection(inflow_timescale, outflow_timescale)) on `side`
+ * (0 west .. 5 top) of the wall-normal velocity `field` at `loc`: _fill_west_halo! .. _fill_top_halo! for a PAOBC
+ * (BoundaryConditions/perturbation_advection.jl:119-180) with step_left_boundary! / step_right_boundary! (:71-117), operation for
+ * operation: Δt = isinf(last_stage_dt) ? 0 : last_stage_dt, U = max(0, min(1, Δt / ΔX ū)) on right sides and min(0, max(-1, .)) on left
+ * ones, τ by the sign of ū, the quotient (uᴮ ± U uᴬ + ū Δt/τ) / (1 + Δt/τ ± U), ū where τ == 0. ΔX = Δxᶠᶜᶜ, Δyᶜᶠᶜ or Δzᶜᶜᶠ at the boundary
+ * index. ū is `value`, or value_array (see ocn_bc_t) when it is not NULL. One launch, one thread per face point. OCN_EINVAL: a side that is
+ * not the wall of a Bounded direction, a field that is not the wall-normal velocity of the side, a negative or NaN timescale. */
+int ocn_step_open_boundary(ocn_grid_t grid, double *field, const int loc[3], int side, double value, const double *value_array,
+                           double inflow_timescale, double outflow_timescale, double last_stage_dt);
+/* open_boundary_mass_inflow (Models/NonhydrostaticModels/boundary_mass_fluxes.jl:47-55,181-198) over the sides of sides_mask (bit s = side
+ * s, 0 west .. 5 top): Σ u Axᶠᶜᶜ + Σ v Ayᶜᶠᶜ + Σ w Azᶜᶜᶠ over the left faces minus the same over the right ones, summed on the device in a
+ * fixed order (two runs give the same bits). u, v, w: haloed fields, NULL where no side of the mask needs one. Synchronous; a diagnostic.
+ * OCN_EINVAL: a side of the mask that is not the wall of a Bounded direction, or whose velocity is NULL. */
+int ocn_open_boundary_mass_inflow(ocn_grid_t grid, const double *u, const double *v, const double *w, int sides_mask, double *value);
+/* enforce_open_boundary_mass_conservation! (boundary_mass_fluxes.jl:224-239). sides[s]: the condition of the wall-normal velocity on side
+ * s -- OCN_BC_OPEN or OCN_BC_DEFAULT --, scheme_mask: the sides whose Open condition carries a scheme. The total is the flux through the
+ * scheme faces and the array-valued imposed faces (integrated on the device) plus condition * area of the constant imposed faces
+ * (initialize_boundary_mass_flux, :57-79); A is the area of the scheme faces alone, and A⁻¹ ∮u dA is subtracted on left scheme faces and
+ * added on right ones (:200-214). Two launches, no atomics, a fixed summation order. Nothing is launched without a scheme side (:216).
+ * OCN_EINVAL: another kind of condition, an Open side that is no wall, a scheme bit on a side that is not Open, a NULL velocity a face
+ * needs. */
+int ocn_enforce_open_boundary_mass_conservation(ocn_grid_t grid, double *u, double *v, double *w, const ocn_bc_t sides[6], int scheme_mask);
 
 /* ---------------------------------------------------------------- tendencies ------------------------------------ */
 /* compute_Gu!/Gv!/Gw!/Gc! (Models/NonhydrostaticModels/compute_nonhydrostatic_tendencies.jl:138-163) for
@@ -520,6 +542,20 @@ int ocn_model_set_smagorinsky(ocn_model_t model, double C, double Cb, int lilly,
 int ocn_model_set_boundary_condition(ocn_model_t model, const char *name, int side, int kind, double value);
 /* the same with an array-valued condition (see ocn_bc_t; borrowed device pointer, valid for the model's lifetime) */
 int ocn_model_set_boundary_condition_array(ocn_model_t model, const char *name, int side, int kind, const double *device_array);
+/* name.side = OpenBoundaryCondition(value; scheme = PerturbationAdvection(inflow_timescale, outflow_timescale))
+ * (BoundaryConditions/perturbation_advection.jl:57-63) for a side whose condition is OCN_BC_OPEN already (number or array; set it first);
+ * enabled = 0: scheme = nothing, the imposed form. The velocity fill of compute_pressure_correction! and of set! then leaves such a side
+ * alone and ONE launch steps every scheme side with the clock's last_stage_Δt (ocn_step_open_boundary); update_state! never touches the
+ * boundary value, which is the scheme's state. enforce_open_boundary_mass_conservation! (pressure_correction.jl:14) follows the fill
+ * in every pressure step, two launches (ocn_enforce_open_boundary_mass_conservation); a time-step stays free of synchronisation. A model
+ * with a scheme side does not replay a captured time-step (option use_graph): the step's arguments follow the clock. Replacing the
+ * side's condition by another Open one keeps the scheme, by any other kind drops it. OCN_EINVAL: a side that is not the wall-normal one
+ * of a Bounded direction (u west / east, v south / north, w bottom / top), a side whose condition is not Open, a negative or NaN
+ * timescale; OCN_ENOTSUP: a partitioned model. ocn_model_get_option answers "open_boundary_scheme_sides" (their number) and
+ * "open_boundary_launches" (the launches they add to a pressure step: 3, or 0 without a scheme side; where an RK3 substep rides in the
+ * tendency launch and the model's two sets of arrays swap, one more small launch carries the boundary values over). */
+int ocn_model_set_open_boundary_scheme(ocn_model_t model, const char *name, int side, int enabled, double inflow_timescale,
+                                       double outflow_timescale);
 /* name.side = FluxBoundaryCondition((ξ, η, t, φ, p) -> a + b φ, field_dependencies = dep); dep at the location of `name` */
 int ocn_model_set_linear_flux_bc(ocn_model_t model, const char *name, int side, double a, double b, const char *dep);
 /* forcing = (name = F,) of the model constructor (Forcings/model_forcing.jl; nonhydrostatic_tendency_kernel_functions.jl:81-93, the last

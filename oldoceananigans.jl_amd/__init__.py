@@ -8,7 +8,8 @@ from .advection import (Centered, FluxFormAdvection, UpwindBiased, WENO, adapt_a
                         required_halo_size_x, required_halo_size_y, required_halo_size_z)
 from .architectures import GPU, architecture, ndevices, own_stream, set_option, synchronize
 from .boundary_conditions import (BoundaryCondition, FieldBoundaryConditions, FluxBoundaryCondition,
-                                  GradientBoundaryCondition, LinearFieldFlux, OpenBoundaryCondition, ValueBoundaryCondition, compute_flux_bcs)
+                                  GradientBoundaryCondition, LinearFieldFlux, OpenBoundaryCondition, PerturbationAdvection, ValueBoundaryCondition,
+                                  compute_flux_bcs)
 from .background_fields import BackgroundField, BackgroundFields
 from .buoyancy import BuoyancyForce, BuoyancyTracer, ConstantCartesianCoriolis, FPlane, LinearEquationOfState, SeawaterBuoyancy
 from .checkpointer import set_from_checkpoint, write_checkpoint

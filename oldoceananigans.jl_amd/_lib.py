@@ -99,6 +99,10 @@ SYMBOLS = {
     "ocn_pack_x_halos": (C.c_int, [_vp, _pp, _vp, C.c_int, _vp, _vp]),
     "ocn_unpack_x_halos": (C.c_int, [_vp, _pp, _vp, C.c_int, _vp, _vp]),
     "ocn_compute_linear_flux_bc": (C.c_int, [_vp, _vp, _ip, C.c_int, C.c_double, C.c_double, _vp]),
+    "ocn_step_open_boundary": (C.c_int, [_vp, _vp, _ip, C.c_int, C.c_double, _vp, C.c_double, C.c_double, C.c_double]),
+    "ocn_open_boundary_mass_inflow": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _dp]),
+    "ocn_enforce_open_boundary_mass_conservation": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "ocn_model_set_open_boundary_scheme": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_double]),
     "ocn_model_set_linear_flux_bc": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_double, C.c_double, C.c_char_p]),
     "ocn_model_set_forcing": (C.c_int, [_vp, C.c_int, C.POINTER(Forcing), C.c_int]),
     "ocn_compute_advective_tendency": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _ip, C.c_int]),

@@ -20,12 +20,40 @@ class LinearFieldFlux:
         self.a, self.b = float(a), float(b)
 
 
-class BoundaryCondition:
-    """BoundaryCondition(classification, condition::Number); Flux conditions also take a LinearFieldFlux with field_dependencies"""
+class PerturbationAdvection:
+    """PerturbationAdvection(; inflow_timescale = 0, outflow_timescale = Inf) (perturbation_advection.jl:4-7,57-63): the scheme of a
+    radiating OpenBoundaryCondition -- the boundary value is advected out with the exterior value ū and relaxed to it over
+    inflow_timescale where ū points into the domain and over outflow_timescale where it points out. Positionally the fields come in the
+    struct's order, inflow before outflow."""
 
-    def __init__(self, classification, condition=0.0, field_dependencies=None):
+    def __init__(self, inflow_timescale=0, outflow_timescale=float("inf")):
+        self.inflow_timescale, self.outflow_timescale = float(inflow_timescale), float(outflow_timescale)          # convert(FT, ...)
+        if not (self.inflow_timescale >= 0 and self.outflow_timescale >= 0):
+            raise ValueError("PerturbationAdvection timescales must be non-negative")
+
+    def __repr__(self):
+        from .forcings import _jl
+        return f"PerturbationAdvection{{Float64}}({_jl(self.inflow_timescale)}, {_jl(self.outflow_timescale)})"
+
+    def __eq__(self, other):
+        return (isinstance(other, PerturbationAdvection) and
+                (self.inflow_timescale, self.outflow_timescale) == (other.inflow_timescale, other.outflow_timescale))
+
+    __hash__ = None
+
+
+class BoundaryCondition:
+    """BoundaryCondition(classification, condition::Number); Flux conditions also take a LinearFieldFlux with field_dependencies; Open
+    conditions a scheme (Open(scheme), boundary_condition_classifications.jl:70-72)"""
+
+    def __init__(self, classification, condition=0.0, field_dependencies=None, scheme=None):
         if classification not in KINDS:
             raise ValueError(f"unknown boundary condition classification {classification}")
+        if scheme is not None and classification != "Open":
+            raise ValueError("only an Open boundary condition carries a scheme")
+        if scheme is not None and not isinstance(scheme, PerturbationAdvection):
+            raise NotImplementedError("scheme must be nothing or PerturbationAdvection(inflow_timescale, outflow_timescale)")
+        self.scheme = scheme
         self.linear = None
         if isinstance(condition, LinearFieldFlux):
             deps = (field_dependencies,) if isinstance(field_dependencies, str) else tuple(field_dependencies or ())
@@ -67,6 +95,8 @@ class BoundaryCondition:
             pass
 
     def __repr__(self):
+        if self.scheme is not None:
+            return f"OpenBoundaryCondition: {self.condition if self.array is None else 'Array'} with {self.scheme!r}"
         if self.linear:
             return f"FluxBoundaryCondition: {self.linear[0]} + {self.linear[1]} * {self.linear[2]}"
         if self.array is not None:
@@ -87,8 +117,33 @@ def GradientBoundaryCondition(value):
     return BoundaryCondition("Gradient", value)
 
 
-def OpenBoundaryCondition(value):
-    return BoundaryCondition("Open", value)
+def OpenBoundaryCondition(value, scheme=None):
+    """OpenBoundaryCondition(val; scheme = nothing) (boundary_condition.jl:108)"""
+    return BoundaryCondition("Open", value, scheme=scheme)
+
+
+def scheme_sides(fbcs):
+    """the sides of a FieldBoundaryConditions (or None) whose Open condition carries a scheme"""
+    return [s for s, bc in fbcs.sides.items() if bc.scheme is not None] if fbcs is not None else []
+
+
+def validate_open_boundary_schemes(boundary_conditions, grid):
+    """a scheme is accepted where the reference has a method for it: on the wall-normal velocity of a Bounded direction (_fill_west_halo!
+    .. _fill_top_halo! for a PAOBC, perturbation_advection.jl:119-180: u west / east, v south / north, w bottom / top), on one device.
+    Raises NotImplementedError otherwise -- called before anything touches the device."""
+    from .grids import Bounded
+    normal = {"u": ("west", "east"), "v": ("south", "north"), "w": ("bottom", "top")}
+    for name, fbcs in dict(boundary_conditions or {}).items():
+        if not isinstance(fbcs, FieldBoundaryConditions):
+            continue
+        for side in scheme_sides(fbcs):
+            if hasattr(grid, "local"):
+                raise NotImplementedError("an OpenBoundaryCondition with a scheme is not served on partitioned grids")
+            if side not in normal.get(name, ()):
+                raise NotImplementedError(f"a scheme belongs to the wall-normal velocity of its side (u west / east, v south / north, "
+                                          f"w bottom / top); got {name}.{side}")
+            if grid.topology[SIDES.index(side) // 2] is not Bounded:
+                raise NotImplementedError(f"a scheme needs a Bounded direction; {name}.{side} is not on one")
 
 
 class FieldBoundaryConditions:
@@ -105,6 +160,10 @@ class FieldBoundaryConditions:
 
     def c_array(self, grid=None):
         arr = (_lib.BC * 6)()
+        if scheme_sides(self):
+            # step_left_boundary! / step_right_boundary! read clock.last_stage_Δt: a fill without a model has no clock
+            raise NotImplementedError("an OpenBoundaryCondition with a scheme is stepped with the model's clock: it is a model boundary "
+                                      "condition, not one of a free-standing fill or flux computation")
         for s, bc in self.sides.items():
             q = SIDES.index(s)
             arr[q].kind = KINDS[bc.classification]

@@ -11,6 +11,7 @@
 #include "ocn_forcing.h"
 #include "ocn_implicit_z.h"
 #include "ocn_particles.h"
+#include "ocn_open_boundary.h"
 #include <hipfft/hipfft.h>
 #include <array>
 #include <cfloat>
@@ -171,6 +172,8 @@ struct ocn_grid_s {
     std::string advection_error;
     // scratch t of the vertically implicit solve (ocn_implicit_z.h), Nx Ny Nz, allocated on first use
     double *ivd_scratch = nullptr;
+    // partial sums of the open-boundary mass flux (ocn_open_boundary.h): one per block of all six faces and one total, allocated on first use
+    double *ob_partial = nullptr;
     // node coordinates for particles and point interpolation (ocn_grid_set_nodes): the geometry the index computation reads; `znodes` holds
     // the Nz + 1 face and Nz centre nodes of a stretched z on the device
     PGeom pg = {};
@@ -291,6 +294,7 @@ extern "C" int ocn_grid_destroy(ocn_grid_t grid) {
     if (!grid) return OCN_OK;
     hipFree(grid->tables);
     hipFree(grid->ivd_scratch);
+    hipFree(grid->ob_partial);
     hipFree(grid->znodes);
     delete grid;
     return OCN_OK;
@@ -380,8 +384,12 @@ static int fill_halo_group(const OcnOptions &o, const ocn_grid_s *grid, double *
     parent_size(g, loc, P);
     const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz}, T[3] = {g.tx, g.ty, g.tz};
     FView view = make_view(g, nullptr, loc);
+    // a side with a scheme (bottom / top of w) is skipped by the bounded fill; the fused kernel below has no such case
+    bool scheme_side = false;
+    for (int f = 0; bcs && f < n; ++f)
+        for (int sd = 0; sd < 6; ++sd) scheme_side = scheme_side || bcs[f][sd].kind == OCN_BC_OPEN_SCHEME;
     // (Periodic | FullyConnected, Periodic, Bounded): bounded z fill + periodic y and x fills as one launch
-    if (o.fused_halo && (T[0] == OCN_PERIODIC || T[0] == OCN_CONNECTED) && T[1] == OCN_PERIODIC && T[2] == OCN_BOUNDED &&
+    if (!scheme_side && o.fused_halo && (T[0] == OCN_PERIODIC || T[0] == OCN_CONNECTED) && T[1] == OCN_PERIODIC && T[2] == OCN_BOUNDED &&
         (T[0] == OCN_CONNECTED || N[0] >= H[0]) && N[1] >= H[1]) {
         const bool face = loc[2] == OCN_FACE, zfill = !face || fill_open;
         BcSides bc;
@@ -1418,6 +1426,11 @@ struct ocn_model_s {
     bool any_bc = false, any_flux_bc = false;
     struct LinBC { bool on = false; int dep = 0; double a = 0.0, b = 0.0; } lin[OCN_MAX_FIELDS][6];   // linear field-dependent Flux
     bool any_linear_flux = false;
+    // OpenBoundaryCondition(value; scheme = PerturbationAdvection(...)) per side (0 west .. 5 top) of the wall-normal velocity; the areas of
+    // the six faces (the partial sums of the mass-flux correction are the grid's)
+    OpenScheme ob[6];
+    int n_scheme = 0;
+    double ob_area[6] = {};
     Coriolis coriolis;
     Buoyancy buoyancy;
     Closure closure;
@@ -1959,6 +1972,10 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     if (!strcmp(key, "stokes_path")) { *value = p.stokes_path; return OCN_OK; }
     // particles = nothing (0) | LagrangianParticles: their number
     if (!strcmp(key, "particles")) { *value = m->particles.on ? m->particles.n : 0; return OCN_OK; }
+    // sides with OpenBoundaryCondition(value; scheme = PerturbationAdvection(...)), and the launches they add to a pressure step: the
+    // boundary step and the two of the mass-flux correction, or none
+    if (!strcmp(key, "open_boundary_scheme_sides")) { *value = m->n_scheme; return OCN_OK; }
+    if (!strcmp(key, "open_boundary_launches")) { *value = m->n_scheme ? 3 : 0; return OCN_OK; }
     // which epilogue adds the closure terms: the z-marching one (1) or the per-value one (0) -- the explicit part of a vertically implicit
     // discretisation exists in the per-value epilogue only
     if (!strcmp(key, "epilogue_march_active")) { *value = p.march ? 1 : 0; return OCN_OK; }
@@ -2106,9 +2123,200 @@ static int compute_flux_bc_tendencies(ocn_model_s *m) {
     return rc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// open boundaries with a scheme (ocn_open_boundary.h)
+// ---------------------------------------------------------------------------------------------------------------------
+// face `side` (0 west .. 5 top) of its wall-normal velocity `p`
+static ObFace ob_face(const ocn_grid_s *grid, double *p, int side, double value, const double *arr, const OpenScheme &sc) {
+    const DGrid &g = grid->d;
+    const int d = side / 2, right = side & 1;
+    const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz};
+    int P[3];
+    parent_size(g, d == 0 ? LOC_U : (d == 1 ? LOC_V : LOC_W), P);
+    const long s[3] = {1, P[0], (long)P[0] * P[1]};
+    const long base = H[0] + s[1] * H[1] + s[2] * H[2];            // parent index of the point (1, 1, 1)
+    const int ta = d == 0 ? 1 : 0, tb = d == 2 ? 1 : 2;
+    ObFace f = {};
+    f.p = p; f.from = p; f.dir = d; f.right = right;
+    f.sa = s[ta]; f.sb = s[tb]; f.Na = N[ta]; f.Nb = N[tb];
+    f.iB = base + (right ? N[d] : 0) * s[d];
+    f.iA = base + (right ? N[d] - 1 : 1) * s[d];
+    // Δxᶠᶜᶜ, Δyᶜᶠᶜ, Δzᶜᶜᶠ at the boundary index (perturbation_advection.jl:124,134,145,155,166,176)
+    f.dX = d == 0 ? g.dx : (d == 1 ? g.dy : grid->h_dzf[(right ? g.Nz : 0) + g.Hz]);
+    f.value = value; f.arr = arr; f.tin = sc.tin; f.tout = sc.tout;
+    return f;
+}
+static void ob_add(ObFaces &S, const ObFace &f) {
+    S.f[S.n] = f;
+    S.f[S.n].first_block = S.nblocks;
+    S.nblocks += (int)(((long)f.Na * f.Nb + OB_THREADS - 1) / OB_THREADS);
+    S.n += 1;
+}
+static bool ob_wall(const DGrid &g, int side) {
+    const int T[3] = {g.tx, g.ty, g.tz};
+    return (side & 1) ? wall_hi(T[side / 2]) : wall_lo(T[side / 2]);
+}
+// get_west_area .. get_top_area (boundary_mass_fluxes.jl:11-45): Σ Axᶠᶜᶜ, Σ Ayᶜᶠᶜ, Σ Azᶜᶜᶠ over the face
+static double ob_face_area(const ocn_grid_s *grid, int side) {
+    const DGrid &g = grid->d;
+    const int d = side / 2;
+    double sum = 0.0;
+    if (d == 2) for (long q = 0; q < (long)g.Nx * g.Ny; ++q) sum += g.dx * g.dy;
+    else
+        for (int k = 1; k <= g.Nz; ++k)
+            for (int a = 0; a < (d == 0 ? g.Ny : g.Nx); ++a) sum += (d == 0 ? g.dy : g.dx) * grid->h_dzc[k - 1 + g.Hz];
+    return sum;
+}
+// the grid's buffer of partial sums: the blocks of all six faces, and the total of ocn_open_boundary_mass_inflow after them
+static int ob_blocks_of_all_faces(const DGrid &g) {
+    const long n[3] = {(long)g.Ny * g.Nz, (long)g.Nx * g.Nz, (long)g.Nx * g.Ny};
+    int b = 0;
+    for (int d = 0; d < 3; ++d) b += 2 * (int)((n[d] + OB_THREADS - 1) / OB_THREADS);
+    return b;
+}
+static int ob_partial_buffer(ocn_grid_s *grid) {
+    if (!grid->ob_partial) HIP_TRY(dev_alloc((void **)&grid->ob_partial, (size_t)(ob_blocks_of_all_faces(grid->d) + 1) * sizeof(double)));
+    return OCN_OK;
+}
+
+static int ob_step(const ObFaces &S, double last_stage_dt) {
+    if (S.n == 0) return OCN_OK;
+    const double dt = std::isinf(last_stage_dt) ? 0.0 : last_stage_dt;          // perturbation_advection.jl:76,100
+    hipLaunchKernelGGL(open_boundary_step_kernel, dim3(S.nblocks), dim3(OB_THREADS), 0, g_stream, S, dt);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+// the faces of open_boundary_mass_inflow (boundary_mass_fluxes.jl:57-79,181-198) and of the correction (:200-238) from the wall-normal
+// conditions wn[side] of u (west, east), v (south, north), w (bottom, top): scheme faces and array-valued imposed faces are integrated on
+// the device, constant imposed faces contribute condition * area here, anything else nothing; only scheme faces are corrected
+struct ObPlan { ObFaces flux = {}, corr = {}; double host_flux = 0.0, scheme_area = 0.0; };
+static ObPlan ob_plan(const ocn_grid_s *grid, double *const U[3], const ocn_bc_t wn[6], const OpenScheme sc[6], const double area[6]) {
+    ObPlan P;
+    for (int side = 0; side < 6; ++side) {
+        if (!ob_wall(grid->d, side) || wn[side].kind != OCN_BC_OPEN) continue;
+        const ObFace f = ob_face(grid, U[side / 2], side, wn[side].value, wn[side].array, sc[side]);
+        if (sc[side].on) { ob_add(P.flux, f); ob_add(P.corr, f); P.scheme_area += area[side]; }
+        else if (wn[side].array) ob_add(P.flux, f);
+        else P.host_flux += (side & 1) ? -(wn[side].value * area[side]) : wn[side].value * area[side];
+    }
+    return P;
+}
+// enforce_open_boundary_mass_conservation! (boundary_mass_fluxes.jl:224-239): launch A, launch B; nothing without a scheme face (:216)
+static int ob_enforce(const ocn_grid_s *grid, const ObPlan &P, double *partial) {
+    if (P.corr.n == 0) return OCN_OK;
+    hipLaunchKernelGGL(open_boundary_flux_kernel, dim3(P.flux.nblocks), dim3(OB_THREADS), 0, g_stream, P.flux, grid->d, partial);
+    hipLaunchKernelGGL(open_boundary_correct_kernel, dim3(P.corr.nblocks), dim3(OB_THREADS), 0, g_stream, P.corr, (const double *)partial,
+                       P.flux.nblocks, P.host_flux, P.scheme_area, (double *)nullptr);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+extern "C" int ocn_step_open_boundary(ocn_grid_t grid, double *field, const int loc[3], int side, double value, const double *value_array,
+                                      double inflow_timescale, double outflow_timescale, double last_stage_dt) {
+    NEED_INIT();
+    if (!grid || !field || !loc) return fail(OCN_EINVAL, "NULL argument");
+    if (side < 0 || side > 5) return fail(OCN_EINVAL, "side %d out of range (0..5 = west, east, south, north, bottom, top)", side);
+    const int d = side / 2;
+    for (int q = 0; q < 3; ++q)
+        if (loc[q] != (q == d ? OCN_FACE : OCN_CENTER)) return fail(OCN_EINVAL, "a scheme steps the wall-normal velocity of its side");
+    if (!ob_wall(grid->d, side)) return fail(OCN_EINVAL, "side %d is not the wall of a Bounded direction", side);
+    if (!(inflow_timescale >= 0) || !(outflow_timescale >= 0)) return fail(OCN_EINVAL, "the timescales must be non-negative");
+    OpenScheme sc;
+    sc.on = true; sc.tin = inflow_timescale; sc.tout = outflow_timescale;
+    ObFaces S = {};
+    ob_add(S, ob_face(grid, field, side, value, value_array, sc));
+    return ob_step(S, last_stage_dt);
+}
+
+extern "C" int ocn_open_boundary_mass_inflow(ocn_grid_t grid, const double *u, const double *v, const double *w, int sides_mask, double *value) {
+    NEED_INIT();
+    if (!grid || !value) return fail(OCN_EINVAL, "NULL argument");
+    if (sides_mask < 0 || sides_mask > 63) return fail(OCN_EINVAL, "sides_mask is a mask of the bits 0 (west) .. 5 (top)");
+    double *const U[3] = {const_cast<double *>(u), const_cast<double *>(v), const_cast<double *>(w)};
+    ObFaces S = {};
+    for (int side = 0; side < 6; ++side) {
+        if (!(sides_mask >> side & 1)) continue;
+        if (!ob_wall(grid->d, side)) return fail(OCN_EINVAL, "side %d is not the wall of a Bounded direction", side);
+        if (!U[side / 2]) return fail(OCN_EINVAL, "NULL velocity for side %d", side);
+        ob_add(S, ob_face(grid, U[side / 2], side, 0.0, nullptr, OpenScheme()));
+    }
+    *value = 0.0;
+    if (S.n == 0) return OCN_OK;
+    int rc = ob_partial_buffer(grid);
+    if (rc) return rc;
+    double *partial = grid->ob_partial, *total = partial + ob_blocks_of_all_faces(grid->d);
+    hipLaunchKernelGGL(open_boundary_flux_kernel, dim3(S.nblocks), dim3(OB_THREADS), 0, g_stream, S, grid->d, partial);
+    ObFaces none = {};
+    hipLaunchKernelGGL(open_boundary_correct_kernel, dim3(1), dim3(OB_THREADS), 0, g_stream, none, (const double *)partial, S.nblocks, 0.0, 1.0,
+                       total);
+    KERNEL_CHECK();
+    HIP_TRY(hipMemcpyAsync(value, total, sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return OCN_OK;
+}
+
+extern "C" int ocn_enforce_open_boundary_mass_conservation(ocn_grid_t grid, double *u, double *v, double *w, const ocn_bc_t sides[6],
+                                                           int scheme_mask) {
+    NEED_INIT();
+    if (!grid || !sides) return fail(OCN_EINVAL, "NULL argument");
+    if (scheme_mask < 0 || scheme_mask > 63) return fail(OCN_EINVAL, "scheme_mask is a mask of the bits 0 (west) .. 5 (top)");
+    double *const U[3] = {u, v, w};
+    OpenScheme sc[6];
+    double area[6];
+    for (int side = 0; side < 6; ++side) {
+        sc[side].on = (scheme_mask >> side & 1) != 0;
+        if (sides[side].kind != OCN_BC_DEFAULT && sides[side].kind != OCN_BC_OPEN)
+            return fail(OCN_EINVAL, "the wall-normal velocity of a side takes an Open condition or the default");
+        if (sides[side].kind == OCN_BC_OPEN && !ob_wall(grid->d, side)) return fail(OCN_EINVAL, "side %d is not the wall of a Bounded direction", side);
+        if (sc[side].on && sides[side].kind != OCN_BC_OPEN) return fail(OCN_EINVAL, "a scheme belongs to an Open condition (side %d)", side);
+        if (sides[side].kind == OCN_BC_OPEN && (sc[side].on || sides[side].array) && !U[side / 2]) return fail(OCN_EINVAL, "NULL velocity for side %d", side);
+        area[side] = ob_wall(grid->d, side) ? ob_face_area(grid, side) : 0.0;
+    }
+    const ObPlan P = ob_plan(grid, U, sides, sc, area);
+    if (P.corr.n == 0) return OCN_OK;
+    int rc = ob_partial_buffer(grid);
+    if (rc) return rc;
+    return ob_enforce(grid, P, grid->ob_partial);
+}
+
+// fill_halo_regions!(fields, clock, fields(model)) with fill_open_bcs = true on the first `nfields` prognostic fields: the sides with a scheme
+// are skipped by the fill and stepped by ONE launch (perturbation_advection.jl:119-180); enforce: enforce_open_boundary_mass_conservation!
+// follows (pressure_correction.jl:12-14). A model without scheme sides makes the fill call it always made.
+static int fill_open_boundaries(ocn_model_s *m, int nfields, bool enforce) {
+    if (!m->n_scheme) return fill_halo_regions(m->opt, m->grid, m->U, m->loc, nfields, true, m->any_bc ? m->bcs : nullptr);
+    ocn_bc_t bcs[OCN_MAX_FIELDS][6], wn[6];
+    memcpy(bcs, m->bcs, sizeof bcs);
+    for (int side = 0; side < 6; ++side) {
+        wn[side] = m->bcs[side / 2][side];
+        if (m->ob[side].on) bcs[side / 2][side].kind = OCN_BC_OPEN_SCHEME;
+    }
+    int rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, nfields, true, bcs);
+    if (rc) return rc;
+    const ObPlan P = ob_plan(m->grid, m->U, wn, m->ob, m->ob_area);
+    if ((rc = ob_step(P.corr, m->last_stage_dt))) return rc;
+    return enforce ? ob_enforce(m->grid, P, m->grid->ob_partial) : OCN_OK;
+}
+
+// after the two sets of prognostic arrays have swapped (rk3_time_step): the scheme sides' boundary values, which the substep that wrote the
+// new set never touches, follow the fields -- implicit_step! and the boundary step read them there. One launch, only with scheme sides.
+static int carry_open_boundaries(ocn_model_s *m) {
+    ObFaces S = {};
+    for (int side = 0; side < 6; ++side) {
+        if (!m->ob[side].on) continue;
+        ObFace f = ob_face(m->grid, m->U[side / 2], side, 0.0, nullptr, m->ob[side]);
+        f.from = m->U2[side / 2];
+        ob_add(S, f);
+    }
+    if (S.n == 0) return OCN_OK;
+    hipLaunchKernelGGL(open_boundary_carry_kernel, dim3(S.nblocks), dim3(OB_THREADS), 0, g_stream, S);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
 // compute_pressure_correction! (pressure_correction.jl:8-20)
 static int compute_pressure_correction(ocn_model_s *m) {
-    int rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr);
+    int rc = fill_open_boundaries(m, 3, true);
     if (rc) return rc;
     if ((rc = solve_for_pressure(m->solver, m->U[0], m->U[1], m->U[2], m->p))) return rc;
     double *pp[1] = {m->p};
@@ -2165,7 +2373,7 @@ static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = tru
     // triply periodic: the divergence reads its upper neighbours at the wrapped interior index, so fill_halo_regions!(velocities)
     // (pressure_correction.jl:10) is not needed here -- update_state! fills every halo again before anything else reads one
     const bool ppp = g.tx == OCN_PERIODIC && g.ty == OCN_PERIODIC && g.tz == OCN_PERIODIC;
-    if (!ppp && (rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, 3, true, m->any_bc ? m->bcs : nullptr))) return rc;
+    if (!ppp && (rc = fill_open_boundaries(m, 3, true))) return rc;
     if (pending) {
         SubstepArgs a;
         int nx, ny, nz;
@@ -2643,6 +2851,7 @@ static int model_set_bc(ocn_model_t m, const char *name, int side, int kind, dou
     m->bcs[f][side].kind = kind;
     m->bcs[f][side].value = value;
     m->bcs[f][side].array = array;
+    if (kind != OCN_BC_OPEN && f < 3 && side / 2 == f && m->ob[side].on) { m->ob[side].on = false; m->n_scheme -= 1; }   // the scheme belongs to an Open condition
     m->lin[f][side].on = false;                 // a plain condition replaces a field-dependent one on this side
     m->any_linear_flux = false;
     for (int q = 0; q < m->nf; ++q)
@@ -2666,6 +2875,31 @@ extern "C" int ocn_model_set_boundary_condition_array(ocn_model_t m, const char 
     return model_set_bc(m, name, side, kind, 0.0, device_array);
 }
 
+// name.side = OpenBoundaryCondition(value; scheme = PerturbationAdvection(inflow_timescale, outflow_timescale)) (perturbation_advection.jl:57-63)
+extern "C" int ocn_model_set_open_boundary_scheme(ocn_model_t m, const char *name, int side, int enabled, double inflow_timescale,
+                                                  double outflow_timescale) {
+    if (m) m->epoch += 1;
+    NEED_INIT();
+    if (!m || !name) return fail(OCN_EINVAL, "NULL argument");
+    if (m->dm) return fail(OCN_ENOTSUP, "open boundaries with a scheme are not served on a partitioned model");
+    const int f = field_index(m, name);
+    if (side < 0 || side > 5 || f < 0 || f > 2 || side / 2 != f || !ob_wall(m->grid->d, side))
+        return fail(OCN_EINVAL, "a scheme belongs to the wall-normal velocity of a Bounded direction (u west / east, v south / north, w bottom / top)");
+    if (m->bcs[f][side].kind != OCN_BC_OPEN) return fail(OCN_EINVAL, "a scheme belongs to an Open condition: set the side's condition first");
+    if (enabled && (!(inflow_timescale >= 0) || !(outflow_timescale >= 0))) return fail(OCN_EINVAL, "the timescales must be non-negative");
+    if (enabled) {
+        int rc = ob_partial_buffer(m->grid);
+        if (rc) return rc;
+        for (int sd = 0; sd < 6; ++sd) m->ob_area[sd] = ob_wall(m->grid->d, sd) ? ob_face_area(m->grid, sd) : 0.0;
+    }
+    m->ob[side].on = enabled != 0;
+    m->ob[side].tin = inflow_timescale;
+    m->ob[side].tout = outflow_timescale;
+    m->n_scheme = 0;
+    for (int sd = 0; sd < 6; ++sd) m->n_scheme += m->ob[sd].on ? 1 : 0;
+    return OCN_OK;
+}
+
 extern "C" int ocn_model_update_state(ocn_model_t m, int compute_tendencies_flag) {
     NEED_INIT();
     if (!m) return fail(OCN_EINVAL, "NULL argument");
@@ -2675,7 +2909,7 @@ extern "C" int ocn_model_update_state(ocn_model_t m, int compute_tendencies_flag
 extern "C" int ocn_model_set_finalize(ocn_model_t m, int enforce_incompressibility) {
     NEED_INIT();
     if (!m) return fail(OCN_EINVAL, "NULL argument");
-    int rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, true, m->any_bc ? m->bcs : nullptr);     // set!(ϕ, value); fill_halo_regions!(ϕ) per field
+    int rc = fill_open_boundaries(m, m->nf, false);     // set!(ϕ, value); fill_halo_regions!(ϕ, model.clock, fields(model)) per field
     if (rc) return rc;
     if ((rc = update_state(m, false))) return rc;
     if (enforce_incompressibility) {
@@ -2768,6 +3002,7 @@ static int rk3_time_step(ocn_model_s *m, double dt) {
             if ((rc = update_state(m, true, &sub, fold))) return rc;
             if ((rc = step_particles(m, sdt[stage]))) return rc;         // before the swap: the particles see this stage's fields
             for (int f = 0; f < m->nf; ++f) std::swap(m->U[f], m->U2[f]);
+            if (m->n_scheme && (rc = carry_open_boundaries(m))) return rc;
             substep_done = true;
         } else {
             if ((rc = update_state(m, true, nullptr, fold))) return rc;
@@ -2795,7 +3030,8 @@ extern "C" int ocn_model_time_step(ocn_model_t m, double dt) {
         if (rc) dist_abandon_exchange(m);
         return rc;
     }
-    if (!m->opt.use_graph || m->profile || m->iteration == 0 || !g_stream_owned) return rk3_time_step(m, dt);
+    // ... and not with a scheme side: the boundary step takes last_stage_Δt, whose corrected third-stage value changes from step to step
+    if (!m->opt.use_graph || m->profile || m->iteration == 0 || !g_stream_owned || m->n_scheme) return rk3_time_step(m, dt);
     if (m->graph_exec && m->graph_dt == dt && m->graph_epoch == m->epoch * 1000003ull + g_epoch) {
         hipError_t e = hipGraphLaunch(m->graph_exec, g_stream);
         if (e != hipSuccess) return fail((int)e, "hipGraphLaunch: %s", hipGetErrorString(e));

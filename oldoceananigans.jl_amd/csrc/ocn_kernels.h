@@ -1279,6 +1279,7 @@ __global__ void __launch_bounds__(256) fill_periodic_xyz_kernel(FieldList fl, in
 // other dims. Center fields: Flux / default -> mirror (fill_halo_regions_flux.jl:9-27); Value / Gradient -> linear
 // extrapolation through the boundary face (fill_halo_regions_value_gradient.jl:7-119). Face fields: Open wall value
 // (fill_halo_regions_open.jl:2-7; impenetrable = 0), skipped when fill_open_bcs = false.
+#define OCN_BC_OPEN_SCHEME 5          // internal: an Open side that carries a scheme (ocn_open_boundary.h); never crosses the C ABI
 struct BcSides {
     int kind[OCN_MAX_FIELDS][2];      // [field][lo | hi], OCN_BC_*
     double value[OCN_MAX_FIELDS][2];
@@ -1319,8 +1320,9 @@ __global__ void __launch_bounds__(256) fill_bounded_kernel(FieldList fl, BcSides
             if (do_lo) p[lo] = h0;
             if (do_hi) p[hi] = h1;
         } else if (fill_open) {
-            if (do_lo) p[lo] = bc.kind[f][0] == OCN_BC_OPEN ? bc.get(f, 0, ab) : 0.0;
-            if (do_hi) p[hi] = bc.kind[f][1] == OCN_BC_OPEN ? bc.get(f, 1, ab) : 0.0;
+            // a side with a scheme is left alone: its boundary value is the scheme's state, stepped by open_boundary_step_kernel
+            if (do_lo && bc.kind[f][0] != OCN_BC_OPEN_SCHEME) p[lo] = bc.kind[f][0] == OCN_BC_OPEN ? bc.get(f, 0, ab) : 0.0;
+            if (do_hi && bc.kind[f][1] != OCN_BC_OPEN_SCHEME) p[hi] = bc.kind[f][1] == OCN_BC_OPEN ? bc.get(f, 1, ab) : 0.0;
         }
     }
 }

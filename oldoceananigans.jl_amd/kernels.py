@@ -272,3 +272,55 @@ def make_pressure_correction(grid, u, v, w, p):
 
 def divide_interior(grid, p, divisor):
     _lib.check(_lib.lib().ocn_divide_interior(grid.handle, p.data, float(divisor)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# open boundaries with a scheme, piece by piece (the model runs them inside its pressure step)
+# ---------------------------------------------------------------------------------------------------------------------
+def _side_conditions(grid, conditions):
+    """{side: OpenBoundaryCondition} of the wall-normal velocities -> (ocn_bc_t[6], scheme mask)"""
+    from .boundary_conditions import KINDS, SIDES, _tangential_shape
+    arr, mask = (_lib.BC * 6)(), 0
+    arr._keep = dict(conditions)                       # the device arrays live as long as the conditions
+    for side, bc in conditions.items():
+        q = SIDES.index(side)
+        arr[q].kind, arr[q].value = KINDS[bc.classification], bc.condition
+        if bc.array is not None:
+            arr[q].array = bc.device_array(_tangential_shape(grid, q))
+        if bc.scheme is not None:
+            mask |= 1 << q
+    return arr, mask
+
+
+def step_open_boundary(field, side, condition, last_stage_Δt):
+    """_fill_<side>_halo!(..., bc::PAOBC, ...) (perturbation_advection.jl:119-180) on the wall-normal velocity `field` for condition =
+    OpenBoundaryCondition(value; scheme = PerturbationAdvection(...)) and clock.last_stage_Δt"""
+    from .boundary_conditions import SIDES, _tangential_shape
+    q = SIDES.index(side)
+    if condition.scheme is None:
+        raise ValueError("step_open_boundary steps a condition with a scheme")
+    dev = condition.device_array(_tangential_shape(field.grid, q)) if condition.array is not None else None
+    _lib.check(_lib.lib().ocn_step_open_boundary(field.grid.handle, field.data, _lib.i3(field.loc_codes), q, condition.condition, dev,
+                                                 condition.scheme.inflow_timescale, condition.scheme.outflow_timescale, float(last_stage_Δt)))
+
+
+def open_boundary_mass_inflow(grid, u, v, w, sides):
+    """Σ u Ax + Σ v Ay + Σ w Az over the left faces among `sides` minus the same over the right ones (open_boundary_mass_inflow,
+    boundary_mass_fluxes.jl:181-198, every listed face integrated); synchronous"""
+    from .boundary_conditions import SIDES
+    mask = 0
+    for s in sides:
+        mask |= 1 << SIDES.index(s)
+    out = C.c_double()
+    _lib.check(_lib.lib().ocn_open_boundary_mass_inflow(grid.handle, u.data if u is not None else None, v.data if v is not None else None,
+                                                        w.data if w is not None else None, mask, C.byref(out)))
+    return out.value
+
+
+def enforce_open_boundary_mass_conservation(grid, u, v, w, conditions):
+    """enforce_open_boundary_mass_conservation! (boundary_mass_fluxes.jl:224-239) for conditions = {side: OpenBoundaryCondition} of the
+    wall-normal velocities: the sides with a scheme are corrected, the imposed ones only enter the total"""
+    arr, mask = _side_conditions(grid, conditions)
+    _lib.check(_lib.lib().ocn_enforce_open_boundary_mass_conservation(grid.handle, u.data if u is not None else None,
+                                                                      v.data if v is not None else None, w.data if w is not None else None,
+                                                                      arr, mask))

@@ -77,6 +77,9 @@ class NonhydrostaticModel:
             # implicit_diffusion_solver (vertically_implicit_diffusion_solver.jl:149-153)
             raise ValueError("VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.")
         self.closure = closure
+        # OpenBoundaryCondition(value; scheme = PerturbationAdvection(...)): refused here where the reference has no method for it
+        from .boundary_conditions import validate_open_boundary_schemes
+        validate_open_boundary_schemes(boundary_conditions, grid)
         # "Adjust advection scheme to be valid on a particular grid size" and "Adjust halos when the advection scheme or turbulence
         # closure requires it" (nonhydrostatic_model.jl:176-184). The library derives the same per-direction schemes from the grid
         # size (ocn_grid_create), so only the descriptor and the halo are settled here.
@@ -209,9 +212,12 @@ class NonhydrostaticModel:
                     dev = bc.device_array(_tangential_shape(self.grid, SIDES.index(side)))      # borrowed by the library: `bc` is kept
                     _lib.check(_lib.lib().ocn_model_set_boundary_condition_array(self.handle, cname.encode(), SIDES.index(side),
                                                                                  KINDS[bc.classification], dev))
-                    continue
-                _lib.check(_lib.lib().ocn_model_set_boundary_condition(self.handle, cname.encode(), SIDES.index(side),
-                                                                       KINDS[bc.classification], bc.condition))
+                else:
+                    _lib.check(_lib.lib().ocn_model_set_boundary_condition(self.handle, cname.encode(), SIDES.index(side),
+                                                                           KINDS[bc.classification], bc.condition))
+                if getattr(bc, "scheme", None) is not None:
+                    _lib.check(_lib.lib().ocn_model_set_open_boundary_scheme(self.handle, cname.encode(), SIDES.index(side), 1,
+                                                                             bc.scheme.inflow_timescale, bc.scheme.outflow_timescale))
         if particles is not None:
             self.particles = particles._bind(self, tracked)
 
