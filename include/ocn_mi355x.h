@@ -794,6 +794,47 @@ int ocn_transpose_x_to_y(ocn_transposable_t field);
 int ocn_transpose_y_to_z(ocn_transposable_t field);
 int ocn_dist_model_max_abs_divergence(ocn_model_t model, double *value);    /* global maximum; synchronous */
 
+/* ---------------------------------------------------------------- diagnostics (AbstractOperations/, Fields/scans.jl) ----------------
+ * One operation node: op(▶a(a), ▶b(b)) at `loc` (BinaryOperation, AbstractOperations/binary_operations.jl:5-25,38-43). a / b: BORROWED device
+ * parent arrays with filled halos at loc_a / loc_b, or NULL for the number ca / cb. `loc` is the location of the first field operand
+ * (binary_operations.jl:109-135); the other field is interpolated to it by the operator interpolation_operator(from, to) names
+ * (Operators/interpolation_utils.jl:55-69): 0.5 (f[i] + f[i+1]) to a Center, 0.5 (f[i-1] + f[i]) to a Face, nested z of y of x for two
+ * directions and x of y of z for three (Operators/interpolation_operators.jl:8-15,45-71), the identity in a Flat direction (:87-110).
+ * OCN_OP_IDENTITY: the field a itself. Partitioned grids (connected topologies) answer OCN_ENOTSUP. */
+#define OCN_OP_IDENTITY 0
+#define OCN_OP_ADD 1
+#define OCN_OP_SUB 2
+#define OCN_OP_MUL 3
+#define OCN_OP_DIV 4
+typedef struct {
+    int op;
+    const double *a, *b;
+    double ca, cb;
+    int loc_a[3], loc_b[3];
+    int loc[3];
+} ocn_operand_t;
+/* compute_computed_field! / _compute! (AbstractOperations/computed_field.jl:92-103): out[i, j, k] = operand[i, j, k] over the interior of
+ * `out`, a parent array at operand->loc; the halos of `out` are the caller's (fill_halo_regions!, :87, is the next call) */
+int ocn_compute_operation(ocn_grid_t grid, const ocn_operand_t *operand, double *out);
+/* sum! / maximum! / minimum! of the operand into a reduced field (Fields/field.jl:735-767) and average! (AbstractOperations/
+ * metric_field_reductions.jl:34-47) over the operand's interior -- all N + 1 points of a Face field on a Bounded direction.
+ * dims_mask: bit d set = direction d + 1 is reduced (1..7). use_metric: the summand is operand * metric with the metric
+ * reduction_grid_metric(dims) names (metric_field_reductions.jl:12-21: Δx, Δy, Δz, Az = Δx Δy, Ay = Δx Δz, Ax = Δy Δz, V = Az Δz,
+ * Operators/spacings_and_areas_and_volumes.jl:309-311,326-333) at the operand's location -- Integral (:144-150); OCN_REDUCE_AVERAGE then
+ * divides by the sum of the metric over the same points (:75-92), and without use_metric by the number of points (conditional_length,
+ * Fields/field.jl:722-732). absolute: f = abs (maximum(abs, c)). `out`: the parent array of the reduced field (reduced_location,
+ * field.jl:673-687: size 1 and no halo in the reduced directions, the halos of the kept ones untouched).
+ * No atomics: block partial sums in a slab of the grid, combined in a fixed order that depends on the grid size and dims_mask only. */
+#define OCN_REDUCE_SUM 0
+#define OCN_REDUCE_MAXIMUM 1
+#define OCN_REDUCE_MINIMUM 2
+#define OCN_REDUCE_AVERAGE 3
+int ocn_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute, double *out);
+/* cumsum! / reverse_cumsum! (directional_accumulate!, accumulate_x / _y / _z, Fields/scans.jl:225-306) along direction dim (0, 1, 2):
+ * B[start] = A[start], B[i] = B[i ∓ 1] + A[i] in that sequential order; use_metric: A = operand * Δ of the direction (CumulativeIntegral,
+ * metric_field_reductions.jl:206-212). `out`: a parent array at operand->loc, interior written. */
+int ocn_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ from .simulations import (CFL, AdvectiveCFL, DiffusiveCFL, Callback, IterationIn
                           stop_time_exceeded, wall_time_limit_exceeded)
 from .stokes_drifts import StokesDrift, UniformStokesDrift
 from .particles import DroguedParticleDynamics, LagrangianParticles, no_dynamics
-from . import kernels
+from . import diagnostics, kernels
+from .diagnostics import (Accumulation, Average, BinaryOperation, CumulativeIntegral, FieldStatus, Integral, Reduction, compute, compute_at)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -39,6 +39,12 @@ class Forcing(C.Structure):
                 ("rate_mask", C.c_double), ("target_dir", C.c_int), ("target_table", C.POINTER(C.c_double)), ("target", C.c_double)]
 
 
+class Operand(C.Structure):
+    """ocn_operand_t"""
+    _fields_ = [("op", C.c_int), ("a", C.c_void_p), ("b", C.c_void_p), ("ca", C.c_double), ("cb", C.c_double),
+                ("loc_a", C.c_int * 3), ("loc_b", C.c_int * 3), ("loc", C.c_int * 3)]
+
+
 class Transport(C.Structure):
     """ocn_transport_t: caller-supplied collectives (device addresses as integers)"""
     EXCHANGE_START = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -82,6 +88,9 @@ SYMBOLS = {
     "ocn_transpose_y_to_x": (C.c_int, [_vp]),
     "ocn_transpose_x_to_y": (C.c_int, [_vp]),
     "ocn_transpose_y_to_z": (C.c_int, [_vp]),
+    "ocn_compute_operation": (C.c_int, [_vp, C.POINTER(Operand), _vp]),
+    "ocn_reduce_operation": (C.c_int, [_vp, C.POINTER(Operand), C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "ocn_accumulate_operation": (C.c_int, [_vp, C.POINTER(Operand), C.c_int, C.c_int, C.c_int, _vp]),
     "ocn_init": (C.c_int, [C.c_int]),
     "ocn_device_count": (C.c_int, [_ip]),
     "ocn_sync": (C.c_int, []),

@@ -12,6 +12,7 @@
 #include "ocn_implicit_z.h"
 #include "ocn_particles.h"
 #include "ocn_open_boundary.h"
+#include "ocn_diagnostics.h"
 #include <hipfft/hipfft.h>
 #include <array>
 #include <cfloat>
@@ -179,6 +180,9 @@ struct ocn_grid_s {
     PGeom pg = {};
     bool has_nodes = false;
     double *znodes = nullptr;
+    // partial results of the diagnostics' reductions (ocn_diagnostics.h): grow-only, allocated on first use
+    double *diag_slab = nullptr;
+    size_t diag_slab_n = 0;
 };
 
 static void parent_size(const DGrid &g, const int loc[3], int P[3]) {
@@ -296,6 +300,7 @@ extern "C" int ocn_grid_destroy(ocn_grid_t grid) {
     hipFree(grid->ivd_scratch);
     hipFree(grid->ob_partial);
     hipFree(grid->znodes);
+    hipFree(grid->diag_slab);
     delete grid;
     return OCN_OK;
 }
@@ -757,6 +762,184 @@ extern "C" int ocn_sum_parent(ocn_grid_t grid, const double *a, const double *b,
     for (int d = 0; d < 3; ++d)
         if (loc[d] != OCN_CENTER && loc[d] != OCN_FACE) return fail(OCN_EINVAL, "loc[%d] is OCN_CENTER or OCN_FACE", d);
     return sum_parent(grid->d, a, b, loc, out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// diagnostics (ocn_diagnostics.h): computed fields, reductions, accumulations of one operation node
+// ---------------------------------------------------------------------------------------------------------------------
+static void dg_interior_size(const DGrid &g, const int loc[3], int n[3]) {
+    const int N[3] = {g.Nx, g.Ny, g.Nz}, T[3] = {g.tx, g.ty, g.tz};
+    for (int d = 0; d < 3; ++d) n[d] = N[d] + ((loc[d] == OCN_FACE && wall_hi(T[d])) ? 1 : 0);
+}
+
+// a field at `from` read at `to`: interpolation_operator(from, to) (interpolation_utils.jl:55-69) as a stencil corner and strides
+static DgLeaf dg_make_leaf(const DGrid &g, const double *p, double c, const int from[3], const int to[3]) {
+    DgLeaf l = {};
+    l.p = p;
+    l.c = c;
+    if (!p) return l;
+    const int H[3] = {g.Hx, g.Hy, g.Hz}, T[3] = {g.tx, g.ty, g.tz};
+    int P[3];
+    parent_size(g, from, P);
+    const long st[3] = {1L, (long)P[0], (long)P[0] * P[1]};
+    l.s1 = P[0];
+    l.s2 = st[2];
+    l.off = H[0] + st[1] * H[1] + st[2] * H[2];
+    long dirs[3];
+    for (int d = 0; d < 3; ++d) {
+        if (T[d] == OCN_FLAT || from[d] == to[d]) continue;           // identity (interpolation_operators.jl:87-110)
+        if (to[d] == OCN_FACE) l.off -= st[d];                        // ℑᶠ: f[i-1], f[i]; ℑᶜ: f[i], f[i+1]
+        dirs[l.n++] = st[d];
+    }
+    // two directions nest as z of y of x (the lower direction innermost), three as x of y of z (interpolation_operators.jl:45-71)
+    for (int q = 0; q < l.n; ++q) l.st[q] = l.n == 3 ? dirs[2 - q] : dirs[q];
+    return l;
+}
+
+static int dg_make_operand(const ocn_grid_s *grid, const ocn_operand_t *op, DgOperand *o) {
+    if (!grid || !op) return fail(OCN_EINVAL, "NULL argument");
+    const DGrid &g = grid->d;
+    const int T[3] = {g.tx, g.ty, g.tz};
+    for (int d = 0; d < 3; ++d)
+        if (T[d] == OCN_CONNECTED || T[d] == OCN_RIGHT_CONNECTED || T[d] == OCN_LEFT_CONNECTED)
+            return fail(OCN_ENOTSUP, "diagnostics on a partitioned grid (connected topology in dimension %d) are not built", d);
+    if (op->op < OCN_OP_IDENTITY || op->op > OCN_OP_DIV) return fail(OCN_EINVAL, "unknown operation code %d", op->op);
+    const bool binary = op->op != OCN_OP_IDENTITY;
+    if (!op->a && !(binary && op->b)) return fail(OCN_EINVAL, "the operation has no field operand (a%s NULL)", binary ? " and b are" : " is");
+    const int *first = op->a ? op->loc_a : op->loc_b;
+    for (int d = 0; d < 3; ++d) {
+        if (op->loc[d] != OCN_CENTER && op->loc[d] != OCN_FACE) return fail(OCN_EINVAL, "loc[%d] is OCN_CENTER or OCN_FACE", d);
+        if (op->a && op->loc_a[d] != OCN_CENTER && op->loc_a[d] != OCN_FACE) return fail(OCN_EINVAL, "loc_a[%d] is OCN_CENTER or OCN_FACE", d);
+        if (binary && op->b && op->loc_b[d] != OCN_CENTER && op->loc_b[d] != OCN_FACE)
+            return fail(OCN_EINVAL, "loc_b[%d] is OCN_CENTER or OCN_FACE", d);
+        if (op->loc[d] != first[d])
+            return fail(OCN_EINVAL, "the operation's location is that of its first field operand (dimension %d: %d != %d)", d, op->loc[d], first[d]);
+    }
+    *o = DgOperand{};
+    o->op = op->op;
+    o->a = dg_make_leaf(g, op->a, op->ca, op->loc_a, op->loc);
+    if (binary) o->b = dg_make_leaf(g, op->b, op->cb, op->loc_b, op->loc);
+    o->dz = op->loc[2] == OCN_FACE ? g.dzf : g.dzc;
+    o->Hz = g.Hz;
+    return OCN_OK;
+}
+
+// the metric of the directions in `mask` (reduction_grid_metric, metric_field_reductions.jl:12-21)
+static void dg_set_metric(const DGrid &g, int mask, DgOperand *o) {
+    const bool x = mask & 1, y = mask & 2, z = mask & 4;
+    o->mc = (x && y) ? g.az : (x ? g.dx : g.dy);
+    o->mmode = (x || y) ? (z ? 3 : 1) : 2;
+}
+
+static DgOut dg_make_out(const DGrid &g, const int loc[3], int reduced_mask, double *out) {
+    const int H[3] = {g.Hx, g.Hy, g.Hz};
+    int P[3];
+    parent_size(g, loc, P);
+    DgOut w = {};
+    w.p = out;
+    long stride = 1;
+    for (int d = 0; d < 3; ++d) {
+        const bool reduced = (reduced_mask >> d) & 1;
+        w.s[d] = reduced ? 0 : stride;
+        w.off += reduced ? 0 : H[d] * stride;
+        stride *= reduced ? 1 : P[d];
+    }
+    return w;
+}
+
+extern "C" int ocn_compute_operation(ocn_grid_t grid, const ocn_operand_t *operand, double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    DgOperand o;
+    int rc = dg_make_operand(grid, operand, &o);
+    if (rc) return rc;
+    int n[3];
+    dg_interior_size(grid->d, operand->loc, n);
+    hipLaunchKernelGGL(dg_compute_kernel, grid3(n[0], n[1], n[2], BLK), BLK, 0, g_stream, o, dg_make_out(grid->d, operand->loc, 0, out), n[0], n[1]);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+template <int KIND>
+static int dg_reduce(ocn_grid_s *grid, const DgOperand &o, const int n[3], int mask, const DgOut &out) {
+    const bool rj = mask & 2, rk = mask & 4;
+    const double count = (double)((mask & 1) ? n[0] : 1) * (rj ? n[1] : 1) * (rk ? n[2] : 1);
+    const int e1 = rj ? 1 : n[1], e2 = rk ? 1 : n[2];
+    if (!(mask & 1)) {
+        hipLaunchKernelGGL(dg_reduce_cols_kernel<KIND>, grid3(n[0], e1, e2, BLK), BLK, 0, g_stream, o, out, n[0], e1, rj ? n[1] : 1, rk ? n[2] : 1, count);
+        KERNEL_CHECK();
+        return OCN_OK;
+    }
+    DgRows R;
+    R.n0 = n[0]; R.n1 = n[1]; R.n2 = n[2]; R.rj = rj; R.rk = rk;
+    R.rows = (rj ? n[1] : 1) * (rk ? n[2] : 1);
+    R.nch = (R.rows + DG_ROWS - 1) / DG_ROWS;
+    R.count = count;
+    const long nout = (long)e1 * e2, nslab = nout * R.nch;
+    if (nslab > 0x7fffffffL) return fail(OCN_ENOTSUP, "reduction over %ld blocks", nslab);
+    if (R.nch > 1 && grid->diag_slab_n < (size_t)(2 * nslab)) {
+        HIP_TRY(hipStreamSynchronize(g_stream));              // a launch already queued may still read the old slab
+        hipFree(grid->diag_slab);
+        grid->diag_slab = nullptr;
+        grid->diag_slab_n = 0;
+        HIP_TRY(dev_alloc((void **)&grid->diag_slab, (size_t)(2 * nslab) * sizeof(double)));
+        grid->diag_slab_n = (size_t)(2 * nslab);
+    }
+    hipLaunchKernelGGL(dg_reduce_rows_kernel<KIND>, dim3((unsigned)nslab), dim3(DG_THREADS), 0, g_stream, o, R, out, grid->diag_slab, nslab);
+    KERNEL_CHECK();
+    if (R.nch > 1) {
+        hipLaunchKernelGGL(dg_combine_kernel<KIND>, dim3((unsigned)nout), dim3(DG_THREADS), 0, g_stream, R, out, grid->diag_slab, nslab,
+                           (int)(KIND == OCN_REDUCE_AVERAGE && o.mmode != 0));
+        KERNEL_CHECK();
+    }
+    return OCN_OK;
+}
+
+extern "C" int ocn_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
+                                    double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    if (kind < OCN_REDUCE_SUM || kind > OCN_REDUCE_AVERAGE) return fail(OCN_EINVAL, "unknown reduction kind %d", kind);
+    if (dims_mask < 1 || dims_mask > 7) return fail(OCN_EINVAL, "dims_mask %d: bits 0..2 name the reduced directions, at least one", dims_mask);
+    if (use_metric && (kind == OCN_REDUCE_MAXIMUM || kind == OCN_REDUCE_MINIMUM)) return fail(OCN_EINVAL, "maximum and minimum take no metric");
+    DgOperand o;
+    int rc = dg_make_operand(grid, operand, &o);
+    if (rc) return rc;
+    o.absolute = absolute != 0;
+    if (use_metric) dg_set_metric(grid->d, dims_mask, &o);
+    int n[3];
+    dg_interior_size(grid->d, operand->loc, n);
+    const DgOut w = dg_make_out(grid->d, operand->loc, dims_mask, out);
+    switch (kind) {
+    case OCN_REDUCE_SUM:     return dg_reduce<OCN_REDUCE_SUM>(grid, o, n, dims_mask, w);
+    case OCN_REDUCE_MAXIMUM: return dg_reduce<OCN_REDUCE_MAXIMUM>(grid, o, n, dims_mask, w);
+    case OCN_REDUCE_MINIMUM: return dg_reduce<OCN_REDUCE_MINIMUM>(grid, o, n, dims_mask, w);
+    default:                 return dg_reduce<OCN_REDUCE_AVERAGE>(grid, o, n, dims_mask, w);
+    }
+}
+
+extern "C" int ocn_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric, double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    if (dim < 0 || dim > 2) return fail(OCN_EINVAL, "dim %d: 0 (x), 1 (y) or 2 (z)", dim);
+    DgOperand o;
+    int rc = dg_make_operand(grid, operand, &o);
+    if (rc) return rc;
+    if (use_metric) dg_set_metric(grid->d, 1 << dim, &o);
+    int n[3];
+    dg_interior_size(grid->d, operand->loc, n);
+    const DgOut w = dg_make_out(grid->d, operand->loc, 0, out);
+    const dim3 blk(64, 4, 1);
+    if (dim == 0) {
+        const long nrows = (long)n[1] * n[2];
+        hipLaunchKernelGGL(dg_accumulate_rows_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(DG_THREADS), 0, g_stream, o, w, n[0], n[1], nrows,
+                           reverse != 0);
+    } else if (dim == 1)
+        hipLaunchKernelGGL(dg_accumulate_cols_kernel<1>, dim3((n[0] + 63) / 64, (n[2] + 3) / 4), blk, 0, g_stream, o, w, n[0], n[2], n[1], reverse != 0);
+    else
+        hipLaunchKernelGGL(dg_accumulate_cols_kernel<2>, dim3((n[0] + 63) / 64, (n[1] + 3) / 4), blk, 0, g_stream, o, w, n[0], n[1], n[2], reverse != 0);
+    KERNEL_CHECK();
+    return OCN_OK;
 }
 
 static int update_hydrostatic_pressure(const DGrid &g, int kind, const double *bT, const double *S, double grav, double alpha, double beta,

@@ -13,12 +13,27 @@ _LOC_CODE = {Center: 0, Face: 1}
 
 
 class Field:
-    def __init__(self, loc, grid, data=None, owner=None):
+    """Field(loc, grid, data=None) -- or Field(operand, compute=True) for a BinaryOperation or a scan (Average, Integral, Reduction,
+    CumulativeIntegral, Accumulation): the computed field of AbstractOperations/computed_field.jl:42-72 and Fields/scans.jl:45-72,
+    whose `operand` ocn.compute(field) evaluates (diagnostics.py)"""
+
+    __array_ufunc__ = None    # a numpy scalar on the left of an operation defers to the reflected method
+
+    def __init__(self, loc, grid=None, data=None, owner=None, compute=True):
+        operand = None
+        if not isinstance(loc, (tuple, list)):
+            from . import diagnostics
+            operand = diagnostics.as_field_operand(loc)
+            if grid is not None or data is not None:
+                raise NotImplementedError("Field(operand): the computed field allocates its own data on the operand's grid")
+            loc, grid = operand.location, operand.grid
         self.grid = grid
         self.loc = tuple(loc)
         self.shape = grid.total_size(self.loc)
         self.nbytes = int(np.prod(self.shape)) * 8
         self._owner = None   # views into a model's memory do NOT keep the model alive (no reference cycles)
+        self.operand = operand
+        self.status = None
         if data is None:
             p = C.c_void_p()
             _lib.check(_lib.lib().ocn_malloc(C.byref(p), self.nbytes))   # zeros(arch, FT, sz...)
@@ -27,6 +42,11 @@ class Field:
         else:
             self.data = data if isinstance(data, C.c_void_p) else C.c_void_p(data)
             self._owns = False
+        if operand is not None:
+            from . import diagnostics
+            self.status = diagnostics.FieldStatus()
+            if compute:
+                diagnostics.compute(self)
 
     @property
     def architecture(self):
@@ -51,7 +71,7 @@ class Field:
 
     def _interior_slices(self):
         g = self.grid
-        return tuple(slice(h, h + n) for h, n in zip(g.halo_size, g.interior_size(self.loc)))
+        return tuple(slice(0, 1) if l is None else slice(h, h + n) for h, n, l in zip(g.halo_size, g.interior_size(self.loc), self.loc))
 
     def interior(self):
         """Array(interior(field)) (field.jl: interior)"""
@@ -69,12 +89,44 @@ class Field:
         self.set_parent(a)
         return self
 
+    # ---- operations and reductions (diagnostics.py): descriptors, no device work until Field(op) / compute; see _add_operations below ----
+
     def __del__(self):
         if getattr(self, "_owns", False):
             try:
                 _lib.lib().ocn_free(self.data)
             except Exception:
                 pass
+
+
+def _add_operations():
+    """the operators (a BinaryOperation descriptor each) and the allocating reductions of Field, forwarded to diagnostics.py"""
+    def binary(symbol, reflected):
+        def method(self, other):
+            from .diagnostics import binary_operation
+            return binary_operation(symbol, other, self) if reflected else binary_operation(symbol, self, other)
+        return method
+
+    def reduction(name):
+        def method(self, dims=None, **kw):
+            from . import diagnostics
+            return getattr(diagnostics, name)(self, dims=dims, **kw)
+        method.__name__ = name
+        return method
+
+    def power(self, exponent):
+        from .diagnostics import power
+        return power(self, exponent)
+
+    for name, symbol in (("add", "+"), ("sub", "-"), ("mul", "*"), ("truediv", "/")):
+        setattr(Field, f"__{name}__", binary(symbol, False))
+        setattr(Field, f"__r{name}__", binary(symbol, True))
+    Field.__pow__ = power
+    for name in ("sum", "mean", "maximum", "minimum"):       # maximum / minimum also take f = None | abs
+        setattr(Field, name, reduction(name))
+
+
+_add_operations()
 
 
 def CenterField(grid):

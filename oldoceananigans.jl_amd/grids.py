@@ -332,12 +332,14 @@ class RectilinearGrid:
         return (self.Hx, self.Hy, self.Hz)
 
     def total_size(self, loc):
-        """total_size(loc, topo, N, H) (grid_utils.jl:138-169)"""
-        return tuple(n + 2 * h + (1 if (l is Face and t in (Bounded, LeftConnected)) else 0)
+        """total_size(loc, topo, N, H) (grid_utils.jl:138-169); a `None` location (a reduced direction, field.jl:673-687) has one point
+        and no halo (total_length(::Nothing, ...) = 1, grid_utils.jl:66-72)"""
+        return tuple(1 if l is None else n + 2 * h + (1 if (l is Face and t in (Bounded, LeftConnected)) else 0)
                      for n, h, l, t in zip(self.size, self.halo_size, loc, self.topology))
 
     def interior_size(self, loc):
-        return tuple(n + (1 if (l is Face and t in (Bounded, LeftConnected)) else 0) for n, l, t in zip(self.size, loc, self.topology))
+        return tuple(1 if l is None else n + (1 if (l is Face and t in (Bounded, LeftConnected)) else 0)
+                     for n, l, t in zip(self.size, loc, self.topology))
 
     def nodes(self, loc):
         """interior node coordinates (xnodes, ynodes, znodes) as broadcastable arrays"""

@@ -49,6 +49,30 @@ def sum_parent(grid, a, b, out):
     _lib.check(_lib.lib().ocn_sum_parent(grid.handle, a.data, b.data, _lib.i3(out.loc_codes), out.data))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# diagnostics: one operation node (a Field or a BinaryOperation, diagnostics.py) evaluated, reduced or accumulated on the device
+# ---------------------------------------------------------------------------------------------------------------------
+def compute_operation(grid, operand, out):
+    """_compute!(data, operand) (computed_field.jl:100-103): out[i, j, k] = operand[i, j, k] over the interior of `out`"""
+    from .diagnostics import operand_struct
+    _lib.check(_lib.lib().ocn_compute_operation(grid.handle, C.byref(operand_struct(operand)), out.data))
+
+
+def reduce_operation(grid, operand, kind, dims, use_metric, absolute, out):
+    """sum! / maximum! / minimum! / average! of the operand over the 1-based directions `dims` into the reduced field `out`; kind: "sum" |
+    "maximum" | "minimum" | "average"; use_metric: the summand is operand * metric (Integral; Average over a stretched z)"""
+    from .diagnostics import _KIND_CODE, dims_mask, operand_struct
+    _lib.check(_lib.lib().ocn_reduce_operation(grid.handle, C.byref(operand_struct(operand)), _KIND_CODE[kind], dims_mask(dims), int(use_metric),
+                                               int(absolute), out.data))
+
+
+def accumulate_operation(grid, operand, dim, reverse, use_metric, out):
+    """cumsum! / reverse_cumsum! of the operand along the 1-based direction `dim` into `out`; use_metric: operand * Δ (CumulativeIntegral)"""
+    from .diagnostics import operand_struct
+    _lib.check(_lib.lib().ocn_accumulate_operation(grid.handle, C.byref(operand_struct(operand)), int(dim) - 1, int(reverse), int(use_metric),
+                                                   out.data))
+
+
 def compute_tendencies_and_substep(grid, fields, Gn, next_fields, Gm, Δt, γ, ζ, kernel_parameters=None):
     """tendencies of all prognostic fields (u, v, w, tracers...) + the rk3_substep! of the next stage into `next_fields`"""
     _lib.check(_lib.lib().ocn_compute_tendencies_and_substep(

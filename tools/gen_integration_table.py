@@ -26,6 +26,8 @@ def jl_type(t):
         return "Ptr{OcnForcing}"
     if base == "ocn_transport_t":
         return "Ptr{OcnTransport}"
+    if base == "ocn_operand_t":
+        return "Ptr{OcnOperand}"
     if base == "char":
         return "Cstring"
     if base == "void":
@@ -52,7 +54,9 @@ table = [MARK, "",
          "`pointer(parent(field.data))`, arrays of device pointers as `Ptr{Ptr{Cdouble}}` built on the host; `OcnBC` / `OcnTransport` mirror",
          "`ocn_bc_t` / `ocn_transport_t` field by field (`struct OcnBC; kind::Cint; value::Cdouble; array::Ptr{Cdouble}; end`). Every `Cint`",
          "return is a status: `check(rc)` of §1. `OcnForcing` mirrors `ocn_forcing_t` the same way; its mask and target tables are host",
-         "`Vector{Float64}`s the binder fills with the reference's own `GaussianMask` / `PiecewiseLinearMask` / `LinearTarget` at the field's nodes.", "", "| entry point | binding |", "|---|---|"] + rows
+         "`Vector{Float64}`s the binder fills with the reference's own `GaussianMask` / `PiecewiseLinearMask` / `LinearTarget` at the field's nodes.",
+         "`OcnOperand` mirrors `ocn_operand_t` (`op::Cint; a::Ptr{Cdouble}; b::Ptr{Cdouble}; ca::Cdouble; cb::Cdouble; loc_a, loc_b, loc::NTuple{3, Cint}`),",
+         "filled from a `BinaryOperation`'s `op`, `a`, `b` and the locations of the three.", "", "| entry point | binding |", "|---|---|"] + rows
 p = os.path.join(ROOT, "INTEGRATION.md")
 s = open(p).read()
 if MARK in s:
