@@ -87,6 +87,11 @@ int ocn_grid_parent_size(ocn_grid_t grid, const int loc[3], int P[3]);    /* tot
  * ocn_model_set_particles (OCN_ESTATE without it). */
 int ocn_grid_set_nodes(ocn_grid_t grid, const double first_face[3], const double first_center[3], const double last_face[3],
                        const double *zf, const double *zc);
+/* The node TABLES of the grid: per direction HOST arrays of the N + 1 face nodes grid.xᶠᵃᵃ[1 .. N + 1] and the N centre nodes
+ * grid.xᶜᵃᵃ[1 .. N] (one of each in a Flat direction), copied to the device. The reference's nodes are elements of Julia ranges, not
+ * x₀ + (i - 1) Δ in floating point, so a kernel that hands coordinates to a user's function reads them from here: needed by
+ * ocn_evaluate_boundary_function and ocn_model_set_flux_bc_function (OCN_ESTATE without it). */
+int ocn_grid_set_node_tables(ocn_grid_t grid, const double *const faces[3], const double *const centers[3]);
 
 /* ---------------------------------------------------------------- halo fills (BoundaryConditions/) -------------- */
 /* fill_halo_regions!(field) with the default boundary conditions of field_boundary_conditions.jl:15-25
@@ -558,6 +563,75 @@ int ocn_model_set_open_boundary_scheme(ocn_model_t model, const char *name, int 
                                        double outflow_timescale);
 /* name.side = FluxBoundaryCondition((ξ, η, t, φ, p) -> a + b φ, field_dependencies = dep); dep at the location of `name` */
 int ocn_model_set_linear_flux_bc(ocn_model_t model, const char *name, int side, double a, double b, const char *dep);
+/* FluxBoundaryCondition(func, field_dependencies = ..., parameters = ...) for ANY function built from the operations below
+ * (BoundaryConditions/continuous_boundary_function.jl:104-154, Utils/user_function_arguments.jl:22-39): func(X..., t, deps..., [p]). A
+ * closure cannot cross a C ABI; a program can. The caller evaluates func once with symbolic arguments and hands over the operations it
+ * performed, in the order it performed them, as a list in SSA form: instruction n defines value n, the operands a, b, c name EARLIER
+ * values, the last value is the flux. Every instruction is one IEEE double operation (no contraction, no reassociation; sqrt and / are
+ * correctly rounded; exp .. pow are the device math library's).
+ *   OCN_EXPR_CONST   imm
+ *   OCN_EXPR_COORD   a = 0 / 1: the node coordinate along the first / second tangential direction of the side (x before y before z) at the
+ *                    condition's location there -- ξ / η / r nodes with Face in the normal direction (x_boundary_node .. z_boundary_node, :104-117)
+ *   OCN_EXPR_TIME    clock.time of the moment of evaluation
+ *   OCN_EXPR_FIELD   a = dependency slot: the dependency at boundary-normal index 1 (left sides) or N (right sides), interpolated from its
+ *                    location to the condition's in the two tangential directions by the operator interpolation_operator(from, to) names
+ *                    (interpolation_utils.jl:55-69; see ocn_operand_t), never in the normal direction (its location there is Nothing)
+ *   OCN_EXPR_ADD SUB MUL DIV MIN MAX POW   a op b (min / max as Julia's: NaN propagates)
+ *   OCN_EXPR_NEG ABS SQRT EXP LOG SIN COS TANH   op a
+ *   OCN_EXPR_LT LE GT GE   a op b ? 1.0 : 0.0
+ *   OCN_EXPR_SELECT  a != 0 ? b : c  (ifelse)
+ * Operand fields an instruction does not use are 0. */
+#define OCN_EXPR_CONST 0
+#define OCN_EXPR_COORD 1
+#define OCN_EXPR_TIME 2
+#define OCN_EXPR_FIELD 3
+#define OCN_EXPR_ADD 4
+#define OCN_EXPR_SUB 5
+#define OCN_EXPR_MUL 6
+#define OCN_EXPR_DIV 7
+#define OCN_EXPR_NEG 8
+#define OCN_EXPR_ABS 9
+#define OCN_EXPR_MIN 10
+#define OCN_EXPR_MAX 11
+#define OCN_EXPR_SQRT 12
+#define OCN_EXPR_EXP 13
+#define OCN_EXPR_LOG 14
+#define OCN_EXPR_SIN 15
+#define OCN_EXPR_COS 16
+#define OCN_EXPR_TANH 17
+#define OCN_EXPR_POW 18
+#define OCN_EXPR_LT 19
+#define OCN_EXPR_LE 20
+#define OCN_EXPR_GT 21
+#define OCN_EXPR_GE 22
+#define OCN_EXPR_SELECT 23
+#define OCN_EXPR_MAX_INSTRUCTIONS 64
+#define OCN_EXPR_MAX_DEPENDENCIES 8
+typedef struct { int op, a, b, c; double imm; } ocn_expr_ins_t;
+/* The program at every point of `side` (0 west .. 5 top) for a condition of a field at `loc` (the entry along the normal direction is
+ * ignored): out[a, b] over the interior extents of the two tangential directions, the dense column-major layout ocn_bc_t::array documents.
+ * deps[s]: BORROWED haloed device arrays with current halos, at dep_locs[s]. ONE launch on ocn_stream(), one thread per boundary point.
+ * OCN_EINVAL, before any launch: n outside 1..OCN_EXPR_MAX_INSTRUCTIONS, an operand index that is not smaller than the instruction's own,
+ * an unknown op, a coordinate other than 0 / 1, a dependency slot >= ndeps, ndeps outside 0..OCN_EXPR_MAX_DEPENDENCIES, a NULL that is
+ * needed, a side that is not a wall of the grid. OCN_ENOTSUP on a connected topology; OCN_ESTATE without ocn_grid_set_node_tables. */
+int ocn_evaluate_boundary_function(ocn_grid_t grid, const ocn_expr_ins_t *program, int n, const int loc[3], int side,
+                                   const double *const *deps, const int (*dep_locs)[3], int ndeps, double time, double *out);
+/* name.side = FluxBoundaryCondition(func, ...) with the program of func; dep_names: the model fields ("u", "v", "w", "c0" ..) of the
+ * dependency slots, read at their own locations (assumed_field_location). The model owns the (Na, Nb) array, sets the side's condition to
+ * {OCN_BC_FLUX, 0, array} and keeps the program in a device-resident table. ONE launch evaluates all functions of the model into their
+ * arrays (blockIdx.z selects the function) at the two moments the Flux conditions are consumed -- before the epilogue launch a substep
+ * rides in, and at the top of compute_flux_bc_tendencies in the steppers -- with the fields, their halos and clock.time of that moment:
+ * the stage times of runge_kutta_3.jl. A model without functions launches nothing more than before. A model whose programs read
+ * OCN_EXPR_TIME steps without the captured graph (the time is a kernel argument); others keep it and the launch is captured with the rest.
+ * A later ocn_model_set_boundary_condition[_array] or ocn_model_set_linear_flux_bc on that side removes the function and frees the array.
+ * At most 16 functions per model. OCN_ENOTSUP on a partitioned model; OCN_EINVAL for unknown names, a side where a Flux condition cannot
+ * sit, a seventeenth function and the program errors of ocn_evaluate_boundary_function; OCN_ESTATE without ocn_grid_set_node_tables.
+ * ocn_model_get_option answers "boundary_functions" (their number), "boundary_function_launches" (launches per evaluation moment: 1 or 0)
+ * and "boundary_functions_read_time" (whether some program holds OCN_EXPR_TIME). */
+int ocn_model_set_flux_bc_function(ocn_model_t model, const char *name, int side, const ocn_expr_ins_t *program, int n,
+                                   const char *const *dep_names, int ndeps);
+/* the function's array as last evaluated, copied to host_out (Na * Nb doubles); synchronous. OCN_EINVAL when the side carries no function */
+int ocn_model_boundary_function_values(ocn_model_t model, const char *name, int side, double *host_out);
 /* forcing = (name = F,) of the model constructor (Forcings/model_forcing.jl; nonhydrostatic_tendency_kernel_functions.jl:81-93, the last
  * term `+ forcing(i, j, k, grid, clock, model_fields)`) for the closure-free forcings of src/Forcings/:
  *   OCN_FORCING_ARRAY       Forcing(array) / forcing = (T = array,): F = array[i, j, k] (forcing.jl:165-177, model_forcing.jl:29)

@@ -10,6 +10,7 @@ from .architectures import GPU, architecture, ndevices, own_stream, set_option, 
 from .boundary_conditions import (BoundaryCondition, FieldBoundaryConditions, FluxBoundaryCondition,
                                   GradientBoundaryCondition, LinearFieldFlux, OpenBoundaryCondition, PerturbationAdvection, ValueBoundaryCondition,
                                   compute_flux_bcs)
+from .boundary_functions import ContinuousBoundaryFunction, cos, exp, ifelse, log, max_, min_, sin, sqrt, tanh
 from .background_fields import BackgroundField, BackgroundFields
 from .buoyancy import BuoyancyForce, BuoyancyTracer, ConstantCartesianCoriolis, FPlane, LinearEquationOfState, SeawaterBuoyancy
 from .checkpointer import set_from_checkpoint, write_checkpoint

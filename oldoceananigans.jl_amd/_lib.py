@@ -45,6 +45,11 @@ class Operand(C.Structure):
                 ("loc_a", C.c_int * 3), ("loc_b", C.c_int * 3), ("loc", C.c_int * 3)]
 
 
+class ExprIns(C.Structure):
+    """ocn_expr_ins_t"""
+    _fields_ = [("op", C.c_int), ("a", C.c_int), ("b", C.c_int), ("c", C.c_int), ("imm", C.c_double)]
+
+
 class Transport(C.Structure):
     """ocn_transport_t: caller-supplied collectives (device addresses as integers)"""
     EXCHANGE_START = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -113,6 +118,10 @@ SYMBOLS = {
     "ocn_enforce_open_boundary_mass_conservation": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
     "ocn_model_set_open_boundary_scheme": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_double]),
     "ocn_model_set_linear_flux_bc": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_double, C.c_double, C.c_char_p]),
+    "ocn_grid_set_node_tables": (C.c_int, [_vp, C.POINTER(_dp), C.POINTER(_dp)]),
+    "ocn_evaluate_boundary_function": (C.c_int, [_vp, C.POINTER(ExprIns), C.c_int, _ip, C.c_int, _pp, _vp, C.c_int, C.c_double, _vp]),
+    "ocn_model_set_flux_bc_function": (C.c_int, [_vp, C.c_char_p, C.c_int, C.POINTER(ExprIns), C.c_int, C.POINTER(C.c_char_p), C.c_int]),
+    "ocn_model_boundary_function_values": (C.c_int, [_vp, C.c_char_p, C.c_int, _dp]),
     "ocn_model_set_forcing": (C.c_int, [_vp, C.c_int, C.POINTER(Forcing), C.c_int]),
     "ocn_compute_advective_tendency": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _ip, C.c_int]),
     "ocn_sum_parent": (C.c_int, [_vp, _vp, _vp, _ip, _vp]),

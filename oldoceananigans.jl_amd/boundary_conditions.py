@@ -1,6 +1,9 @@
-"""Boundary conditions with constant or array values (reference: src/BoundaryConditions/boundary_condition.jl,
-boundary_condition_classifications.jl, field_boundary_conditions.jl). Function- and field-valued conditions are outside the
-accelerated path."""
+"""Boundary conditions (reference: src/BoundaryConditions/boundary_condition.jl, boundary_condition_classifications.jl,
+field_boundary_conditions.jl, continuous_boundary_function.jl). A condition is a number, a 2-D array over the boundary, a LinearFieldFlux,
+or -- Flux conditions only -- a function: FluxBoundaryCondition(func, field_dependencies=..., parameters=...) with the reference's
+signature func(X..., t, deps..., [parameters]). The model records the function's operations once and evaluates them on the device at every
+boundary point before each use of the Flux conditions (boundary_functions.py). Functions in Value / Gradient / Open conditions,
+discrete_form=True, functions on diffusivity fields, on partitioned grids and in a free-standing fill are refused by name."""
 import ctypes as C
 
 import numpy as np
@@ -46,7 +49,7 @@ class BoundaryCondition:
     """BoundaryCondition(classification, condition::Number); Flux conditions also take a LinearFieldFlux with field_dependencies; Open
     conditions a scheme (Open(scheme), boundary_condition_classifications.jl:70-72)"""
 
-    def __init__(self, classification, condition=0.0, field_dependencies=None, scheme=None):
+    def __init__(self, classification, condition=0.0, field_dependencies=None, scheme=None, parameters=None, discrete_form=False):
         if classification not in KINDS:
             raise ValueError(f"unknown boundary condition classification {classification}")
         if scheme is not None and classification != "Open":
@@ -55,6 +58,14 @@ class BoundaryCondition:
             raise NotImplementedError("scheme must be nothing or PerturbationAdvection(inflow_timescale, outflow_timescale)")
         self.scheme = scheme
         self.linear = None
+        self.function = None
+        if discrete_form:
+            raise NotImplementedError("discrete_form=True (a DiscreteBoundaryFunction indexes the fields itself) is not built: write the "
+                                      "condition in the continuous form func(X..., t, deps..., [parameters])")
+        if callable(condition) and not isinstance(condition, LinearFieldFlux) and classification == "Flux":
+            from .boundary_functions import ContinuousBoundaryFunction
+            self.function = ContinuousBoundaryFunction(condition, parameters, field_dependencies)
+            condition = 0.0
         if isinstance(condition, LinearFieldFlux):
             deps = (field_dependencies,) if isinstance(field_dependencies, str) else tuple(field_dependencies or ())
             if classification != "Flux" or len(deps) != 1:
@@ -70,8 +81,12 @@ class BoundaryCondition:
                 raise ValueError("an array-valued boundary condition is a 2-D array over the two tangential directions")
             self._device = None
             condition = 0.0
-        if callable(condition) or not isinstance(condition, (int, float)):
-            raise NotImplementedError("only constant (Number) or array boundary conditions and LinearFieldFlux are on the accelerated path")
+        if callable(condition):
+            raise NotImplementedError(f"a function in a {classification} condition is not built (it would have to be evaluated before every "
+                                      "halo fill): only constant (Number) or array boundary conditions are on the accelerated path there; "
+                                      "Flux conditions take functions")
+        if not isinstance(condition, (int, float)):
+            raise NotImplementedError("only constant (Number) or array boundary conditions, LinearFieldFlux and (Flux) functions are on the accelerated path")
         self.classification, self.condition = classification, float(condition)
 
     def device_array(self, expected_shape=None):
@@ -99,14 +114,17 @@ class BoundaryCondition:
             return f"OpenBoundaryCondition: {self.condition if self.array is None else 'Array'} with {self.scheme!r}"
         if self.linear:
             return f"FluxBoundaryCondition: {self.linear[0]} + {self.linear[1]} * {self.linear[2]}"
+        if self.function is not None:
+            return f"FluxBoundaryCondition: {self.function!r}"
         if self.array is not None:
             return f"{self.classification}BoundaryCondition: {self.array.shape[0]}×{self.array.shape[1]} Array{{Float64, 2}}"
         return f"{self.classification}BoundaryCondition: {self.condition}"
 
 
-def FluxBoundaryCondition(value, field_dependencies=None, parameters=None):
-    """FluxBoundaryCondition(Number) | FluxBoundaryCondition(LinearFieldFlux(a, b), field_dependencies = :φ)"""
-    return BoundaryCondition("Flux", value, field_dependencies)
+def FluxBoundaryCondition(value, field_dependencies=None, parameters=None, discrete_form=False):
+    """FluxBoundaryCondition(Number | array) | FluxBoundaryCondition(LinearFieldFlux(a, b), field_dependencies = :φ) |
+    FluxBoundaryCondition(func, field_dependencies = (...), parameters = p) with func(X..., t, deps..., [p]) (boundary_functions.py)"""
+    return BoundaryCondition("Flux", value, field_dependencies, parameters=parameters, discrete_form=discrete_form)
 
 
 def ValueBoundaryCondition(value):
@@ -146,6 +164,27 @@ def validate_open_boundary_schemes(boundary_conditions, grid):
                 raise NotImplementedError(f"a scheme needs a Bounded direction; {name}.{side} is not on one")
 
 
+def function_sides(fbcs):
+    """the sides of a FieldBoundaryConditions (or None) whose Flux condition is a function"""
+    return [s for s, bc in fbcs.sides.items() if bc.function is not None] if isinstance(fbcs, FieldBoundaryConditions) else []
+
+
+def validate_boundary_functions(boundary_conditions, grid):
+    """function-valued Flux conditions are served for the velocities and tracers of a model on one device. Raises NotImplementedError
+    otherwise -- called before anything touches the device."""
+    import unicodedata
+    for name, fbcs in dict(boundary_conditions or {}).items():
+        diffusivity = unicodedata.normalize("NFKC", name) in ("νe", "nu_e", "κe", "kappa_e")
+        nested = list(dict(fbcs).values()) if diffusivity and not isinstance(fbcs, FieldBoundaryConditions) else [fbcs]
+        for entry in nested:
+            if not function_sides(entry):
+                continue
+            if diffusivity:
+                raise NotImplementedError(f"a function-valued condition of the diffusivity field {name} is not built")
+            if hasattr(grid, "local"):
+                raise NotImplementedError("a function-valued boundary condition is not served on partitioned grids")
+
+
 class FieldBoundaryConditions:
     """FieldBoundaryConditions(; west, east, south, north, bottom, top): unspecified sides keep the defaults of
     field_boundary_conditions.jl:15-25 (Periodic -> periodic, Bounded + Center -> no flux, Bounded + Face -> impenetrable)"""
@@ -165,6 +204,10 @@ class FieldBoundaryConditions:
             raise NotImplementedError("an OpenBoundaryCondition with a scheme is stepped with the model's clock: it is a model boundary "
                                       "condition, not one of a free-standing fill or flux computation")
         for s, bc in self.sides.items():
+            if bc.function is not None:
+                # getbc(::ContinuousBoundaryFunction, ..., clock, model_fields): a fill without a model has neither
+                raise NotImplementedError("a function-valued boundary condition is evaluated with the model's clock and fields: it is a model "
+                                          "boundary condition, not one of a free-standing fill or flux computation")
             q = SIDES.index(s)
             arr[q].kind = KINDS[bc.classification]
             arr[q].value = bc.condition

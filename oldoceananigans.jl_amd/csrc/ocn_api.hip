@@ -13,6 +13,7 @@
 #include "ocn_particles.h"
 #include "ocn_open_boundary.h"
 #include "ocn_diagnostics.h"
+#include "ocn_boundary_function.h"
 #include <hipfft/hipfft.h>
 #include <array>
 #include <cfloat>
@@ -183,6 +184,9 @@ struct ocn_grid_s {
     // partial results of the diagnostics' reductions (ocn_diagnostics.h): grow-only, allocated on first use
     double *diag_slab = nullptr;
     size_t diag_slab_n = 0;
+    // node tables for functions of the coordinates (ocn_grid_set_node_tables): per direction N + 1 face and N centre nodes, one device block
+    double *node_tables = nullptr;
+    const double *nodes_f[3] = {}, *nodes_c[3] = {};
 };
 
 static void parent_size(const DGrid &g, const int loc[3], int P[3]) {
@@ -301,6 +305,7 @@ extern "C" int ocn_grid_destroy(ocn_grid_t grid) {
     hipFree(grid->ob_partial);
     hipFree(grid->znodes);
     hipFree(grid->diag_slab);
+    hipFree(grid->node_tables);
     delete grid;
     return OCN_OK;
 }
@@ -337,6 +342,33 @@ extern "C" int ocn_grid_set_nodes(ocn_grid_t grid, const double first_face[3], c
     grid->znodes = zn;
     grid->pg = pg;
     grid->has_nodes = true;
+    return OCN_OK;
+}
+
+// the node tables (grid.xᶠᵃᵃ[1 .. N + 1], grid.xᶜᵃᵃ[1 .. N] per direction; one node each in a Flat direction): elements of Julia ranges on the
+// reference's side, so they are copied, not recomputed
+extern "C" int ocn_grid_set_node_tables(ocn_grid_t grid, const double *const faces[3], const double *const centers[3]) {
+    NEED_INIT();
+    if (!grid || !faces || !centers) return fail(OCN_EINVAL, "NULL argument");
+    const DGrid &D = grid->d;
+    const int N[3] = {D.Nx, D.Ny, D.Nz}, T[3] = {D.tx, D.ty, D.tz};
+    std::vector<double> h;
+    size_t at_f[3], at_c[3];
+    for (int d = 0; d < 3; ++d) {
+        if (!faces[d] || !centers[d]) return fail(OCN_EINVAL, "NULL node table in dimension %d", d);
+        const int nf = T[d] == OCN_FLAT ? 1 : N[d] + 1, nc = T[d] == OCN_FLAT ? 1 : N[d];
+        at_f[d] = h.size(); h.insert(h.end(), faces[d], faces[d] + nf);
+        at_c[d] = h.size(); h.insert(h.end(), centers[d], centers[d] + nc);
+    }
+    double *dev = nullptr;
+    hipError_t e = dev_alloc((void **)&dev, h.size() * sizeof(double));
+    if (e != hipSuccess) return fail((int)e, "dev_alloc(node tables): %s", hipGetErrorString(e));
+    e = hipMemcpy(dev, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(dev); return fail((int)e, "hipMemcpy(node tables): %s", hipGetErrorString(e)); }
+    HIP_TRY(hipStreamSynchronize(g_stream));          // a launch already queued may still read the old tables
+    hipFree(grid->node_tables);
+    grid->node_tables = dev;
+    for (int d = 0; d < 3; ++d) { grid->nodes_f[d] = dev + at_f[d]; grid->nodes_c[d] = dev + at_c[d]; }
     return OCN_OK;
 }
 
@@ -845,6 +877,125 @@ static DgOut dg_make_out(const DGrid &g, const int loc[3], int reduced_mask, dou
         stride *= reduced ? 1 : P[d];
     }
     return w;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// boundary functions (ocn_boundary_function.h): programs of FluxBoundaryCondition(func, field_dependencies, parameters)
+// ---------------------------------------------------------------------------------------------------------------------
+// every operand of every instruction names an earlier value (or is 0 where unused): nothing the kernel indexes with is left unchecked
+static int bf_validate_program(const ocn_expr_ins_t *program, int n, int ndeps, bool *reads_time) {
+    if (n < 1 || n > BF_MAX_INS) return fail(OCN_EINVAL, "a boundary function has 1..%d instructions; got %d", BF_MAX_INS, n);
+    if (ndeps < 0 || ndeps > BF_MAX_DEPS) return fail(OCN_EINVAL, "a boundary function has 0..%d field dependencies; got %d", BF_MAX_DEPS, ndeps);
+    if (!program) return fail(OCN_EINVAL, "NULL program");
+    if (reads_time) *reads_time = false;
+    for (int q = 0; q < n; ++q) {
+        const ocn_expr_ins_t &I = program[q];
+        int values = 0;                 // how many of a, b, c are value operands
+        switch (I.op) {
+        case OCN_EXPR_CONST: break;
+        case OCN_EXPR_TIME: if (reads_time) *reads_time = true; break;
+        case OCN_EXPR_COORD:
+            if (I.a != 0 && I.a != 1) return fail(OCN_EINVAL, "instruction %d: coordinate %d is not 0 or 1", q, I.a);
+            break;
+        case OCN_EXPR_FIELD:
+            if (I.a < 0 || I.a >= ndeps) return fail(OCN_EINVAL, "instruction %d: dependency slot %d outside 0..%d", q, I.a, ndeps - 1);
+            break;
+        case OCN_EXPR_NEG: case OCN_EXPR_ABS: case OCN_EXPR_SQRT: case OCN_EXPR_EXP: case OCN_EXPR_LOG: case OCN_EXPR_SIN: case OCN_EXPR_COS:
+        case OCN_EXPR_TANH: values = 1; break;
+        case OCN_EXPR_ADD: case OCN_EXPR_SUB: case OCN_EXPR_MUL: case OCN_EXPR_DIV: case OCN_EXPR_MIN: case OCN_EXPR_MAX: case OCN_EXPR_POW:
+        case OCN_EXPR_LT: case OCN_EXPR_LE: case OCN_EXPR_GT: case OCN_EXPR_GE: values = 2; break;
+        case OCN_EXPR_SELECT: values = 3; break;
+        default: return fail(OCN_EINVAL, "instruction %d: unknown op %d", q, I.op);
+        }
+        const int operand[3] = {I.a, I.b, I.c};
+        for (int w = 0; w < 3; ++w) {
+            if (w < values) {
+                if (operand[w] < 0 || operand[w] >= q) return fail(OCN_EINVAL, "instruction %d: operand %d is not an earlier value", q, operand[w]);
+            } else if (operand[w] != 0 && !(w == 0 && (I.op == OCN_EXPR_COORD || I.op == OCN_EXPR_FIELD)))
+                return fail(OCN_EINVAL, "instruction %d: an unused operand field is not 0", q);
+        }
+    }
+    return OCN_OK;
+}
+
+// the function of a condition at `loc` on `side`: extents, coordinate tables, the stencils of its dependencies (dep_field[s]: slot of
+// BfFields, at dep_locs[s]) and a copy of the validated program
+static int bf_make_function(const ocn_grid_s *grid, const ocn_expr_ins_t *program, int n, const int loc[3], int side, const int *dep_field,
+                            const int (*dep_locs)[3], int ndeps, double *out, BfFunction *fn) {
+    const DGrid &g = grid->d;
+    const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz}, T[3] = {g.tx, g.ty, g.tz};
+    for (int d = 0; d < 3; ++d)
+        if (T[d] == OCN_CONNECTED || T[d] == OCN_RIGHT_CONNECTED || T[d] == OCN_LEFT_CONNECTED)
+            return fail(OCN_ENOTSUP, "boundary functions on a partitioned grid (connected topology in dimension %d) are not built", d);
+    if (side < 0 || side > 5) return fail(OCN_EINVAL, "side %d out of range (0..5 = west, east, south, north, bottom, top)", side);
+    const int d = side / 2, right = side & 1;
+    if (!(right ? wall_hi(T[d]) : wall_lo(T[d]))) return fail(OCN_EINVAL, "side %d is not a wall of the grid (Bounded direction)", side);
+    if (!grid->node_tables) return fail(OCN_ESTATE, "the grid has no node tables: call ocn_grid_set_node_tables");
+    const int ta = d == 0 ? 1 : 0, tb = d == 2 ? 1 : 2;
+    for (int q = 0; q < 3; ++q)
+        if (q != d && loc[q] != OCN_CENTER && loc[q] != OCN_FACE) return fail(OCN_EINVAL, "loc[%d] is OCN_CENTER or OCN_FACE", q);
+    *fn = BfFunction{};
+    fn->n = n; fn->ndeps = ndeps;
+    fn->Na = N[ta]; fn->Nb = N[tb];
+    fn->out = out;
+    fn->xa = loc[ta] == OCN_FACE ? grid->nodes_f[ta] : grid->nodes_c[ta];
+    fn->xb = loc[tb] == OCN_FACE ? grid->nodes_f[tb] : grid->nodes_c[tb];
+    for (int s = 0; s < ndeps; ++s) {
+        const int *from = dep_locs[s];
+        for (int q = 0; q < 3; ++q)
+            if (from[q] != OCN_CENTER && from[q] != OCN_FACE) return fail(OCN_EINVAL, "dependency %d: loc[%d] is OCN_CENTER or OCN_FACE", s, q);
+        int P[3];
+        parent_size(g, from, P);
+        const long st[3] = {1L, (long)P[0], (long)P[0] * P[1]};
+        BfDep &D = fn->dep[s];
+        D.field = dep_field[s];
+        // interior point (1, 1, 1), moved to the boundary-normal index 1 / N (domain_boundary_indices): no interpolation along the normal
+        D.off = H[0] + st[1] * H[1] + st[2] * H[2] + (right ? N[d] - 1 : 0) * st[d];
+        D.sa = st[ta]; D.sb = st[tb];
+        const int tang[2] = {ta, tb};
+        for (int w = 0; w < 2; ++w) {
+            const int q = tang[w];
+            if (T[q] == OCN_FLAT || from[q] == loc[q]) continue;          // identity (interpolation_operators.jl:87-110)
+            if (loc[q] == OCN_FACE) D.off -= st[q];                       // ℑᶠ: f[i-1], f[i]; ℑᶜ: f[i], f[i+1]
+            D.st[D.n++] = st[q];                                          // the lower direction innermost (:45-71)
+        }
+    }
+    memcpy(fn->ins, program, sizeof(ocn_expr_ins_t) * (size_t)n);
+    return OCN_OK;
+}
+
+static void bf_launch(const BfFunction *table_d, int nfun, int na, int nb, const BfFields &fields, double time) {
+    hipLaunchKernelGGL(boundary_function_kernel, dim3((na + BF_LANES - 1) / BF_LANES, (nb + BF_ROWS - 1) / BF_ROWS, nfun), dim3(BF_LANES, BF_ROWS), 0,
+                       g_stream, table_d, fields, time);
+}
+
+extern "C" int ocn_evaluate_boundary_function(ocn_grid_t grid, const ocn_expr_ins_t *program, int n, const int loc[3], int side,
+                                              const double *const *deps, const int (*dep_locs)[3], int ndeps, double time, double *out) {
+    NEED_INIT();
+    if (!grid || !loc || !out) return fail(OCN_EINVAL, "NULL argument");
+    int rc = bf_validate_program(program, n, ndeps, nullptr);
+    if (rc) return rc;
+    if (ndeps > 0 && (!deps || !dep_locs)) return fail(OCN_EINVAL, "NULL dependencies");
+    BfFields fields = {};
+    int slots[BF_MAX_DEPS];
+    for (int s = 0; s < ndeps; ++s) {
+        if (!deps[s]) return fail(OCN_EINVAL, "dependency %d is NULL", s);
+        fields.p[s] = deps[s];
+        slots[s] = s;
+    }
+    BfFunction fn;
+    if ((rc = bf_make_function(grid, program, n, loc, side, slots, dep_locs, ndeps, out, &fn))) return rc;
+    BfFunction *table_d = nullptr;
+    HIP_TRY(dev_alloc((void **)&table_d, sizeof(BfFunction)));
+    hipError_t e = hipMemcpy(table_d, &fn, sizeof(BfFunction), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        bf_launch(table_d, 1, fn.Na, fn.Nb, fields, time);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);          // the table is this call's
+    hipFree(table_d);
+    if (e != hipSuccess) return fail((int)e, "boundary_function_kernel: %s", hipGetErrorString(e));
+    return OCN_OK;
 }
 
 extern "C" int ocn_compute_operation(ocn_grid_t grid, const ocn_operand_t *operand, double *out) {
@@ -1609,6 +1760,14 @@ struct ocn_model_s {
     bool any_bc = false, any_flux_bc = false;
     struct LinBC { bool on = false; int dep = 0; double a = 0.0, b = 0.0; } lin[OCN_MAX_FIELDS][6];   // linear field-dependent Flux
     bool any_linear_flux = false;
+    // FluxBoundaryCondition(func, ...) (ocn_boundary_function.h): per function its field, side and the array it is evaluated into (owned; the
+    // side's condition is {OCN_BC_FLUX, 0, array}); the device-resident table of the programs, rewritten by the setters
+    struct BoundaryFunctions {
+        int n = 0;
+        struct Slot { int f, side; BfFunction fn; } slot[BF_MAX_FUNCTIONS];
+        BfFunction *table_d = nullptr;
+        bool reads_time = false;
+    } bf;
     // OpenBoundaryCondition(value; scheme = PerturbationAdvection(...)) per side (0 west .. 5 top) of the wall-normal velocity; the areas of
     // the six faces (the partial sums of the mass-flux correction are the grid's)
     OpenScheme ob[6];
@@ -1650,6 +1809,8 @@ extern "C" int ocn_model_destroy(ocn_model_t m) {
     if (m->graph_exec) hipGraphExecDestroy(m->graph_exec);
     for (int f = 0; f < m->nf; ++f) { hipFree(m->U[f]); hipFree(m->U2[f]); hipFree(m->Gn[f]); hipFree(m->Gm[f]); }
     hipFree(m->pHY);
+    for (int q = 0; q < m->bf.n; ++q) hipFree(m->bf.slot[q].fn.out);
+    hipFree(m->bf.table_d);
     hipFree(m->stokes.block);
     hipFree(m->particles.block);
     for (int q = 0; q < m->particles.ntracked; ++q) hipFree(m->particles.tracked[q].values);
@@ -1907,6 +2068,19 @@ static bool has_forcing(const ocn_model_s *m) {
         if (m->forcing_h.nterms[f] > 0) return true;
     return false;
 }
+// getbc of every function-valued Flux condition with the fields, their halos and the clock of this moment, into the conditions' arrays:
+// ONE launch for all of them, none without one
+static int evaluate_boundary_functions(ocn_model_s *m) {
+    if (m->bf.n == 0) return OCN_OK;
+    BfFields fields = {};
+    for (int f = 0; f < m->nf; ++f) fields.p[f] = m->U[f];
+    int na = 1, nb = 1;
+    for (int q = 0; q < m->bf.n; ++q) { na = std::max(na, m->bf.slot[q].fn.Na); nb = std::max(nb, m->bf.slot[q].fn.Nb); }
+    bf_launch(m->bf.table_d, m->bf.n, na, nb, fields, m->time);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
 static int count_linear_flux(const ocn_model_s *m) {
     int n = 0;
     for (int f = 0; f < m->nf; ++f)
@@ -2061,6 +2235,10 @@ static int tendency_epilogue(ocn_model_s *m, const StepPlan &p, const FusedSubst
     // update_state!: the conditions are folded in only when that stage's substep rides along; otherwise G stays without them and the
     // stepper adds them when the stage begins (compute_flux_bc_tendencies below) -- with the conditions' values of THAT moment
     const bool with_flux = sub != nullptr;
+    if (with_flux) {                      // the function-valued conditions of that stage: m->U and the clock are already its own
+        const int rc = evaluate_boundary_functions(m);
+        if (rc) return rc;
+    }
     a.any_flux = m->any_flux_bc && with_flux;
     a.nlin = 0;
     for (int f = 0; f < m->nf; ++f)
@@ -2159,6 +2337,10 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     // boundary step and the two of the mass-flux correction, or none
     if (!strcmp(key, "open_boundary_scheme_sides")) { *value = m->n_scheme; return OCN_OK; }
     if (!strcmp(key, "open_boundary_launches")) { *value = m->n_scheme ? 3 : 0; return OCN_OK; }
+    // function-valued Flux conditions: their number, the launches they add to each moment the conditions are consumed, whether a program reads t
+    if (!strcmp(key, "boundary_functions")) { *value = m->bf.n; return OCN_OK; }
+    if (!strcmp(key, "boundary_function_launches")) { *value = m->bf.n ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "boundary_functions_read_time")) { *value = m->bf.reads_time ? 1 : 0; return OCN_OK; }
     // which epilogue adds the closure terms: the z-marching one (1) or the per-value one (0) -- the explicit part of a vertically implicit
     // discretisation exists in the per-value epilogue only
     if (!strcmp(key, "epilogue_march_active")) { *value = p.march ? 1 : 0; return OCN_OK; }
@@ -2295,7 +2477,7 @@ static int update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *s
 // the conditions folded into that pass (tendency_epilogue); every other substep calls this first.
 static int compute_flux_bc_tendencies(ocn_model_s *m) {
     const DGrid &g = m->grid->d;
-    int rc = OCN_OK;
+    int rc = evaluate_boundary_functions(m);
     if (m->any_flux_bc)
         for (int f = 0; f < m->nf && !rc; ++f) rc = compute_flux_bcs(g, m->Gn[f], m->loc[f], m->bcs[f]);
     if (m->any_linear_flux)
@@ -2850,6 +3032,7 @@ static int implicit_step(ocn_model_s *m, double dt) {
     return OCN_OK;
 }
 
+static int bf_remove(ocn_model_s *m, int f, int side);
 // name.side = FluxBoundaryCondition((ξ, η, t, φ, p) -> a + b φ, field_dependencies = dep) (continuous_boundary_function.jl:128-161)
 extern "C" int ocn_model_set_linear_flux_bc(ocn_model_t m, const char *name, int side, double a, double b, const char *dep) {
     if (!m || !name || !dep) return fail(OCN_EINVAL, "NULL argument");
@@ -2861,6 +3044,7 @@ extern "C" int ocn_model_set_linear_flux_bc(ocn_model_t m, const char *name, int
     for (int q = 0; q < 3; ++q)
         if (m->loc[fd][q] != m->loc[f][q])
             return fail(OCN_ENOTSUP, "the field dependency %s must sit at the location of %s (identity interpolation to the boundary)", dep, name);
+    if ((rc = bf_remove(m, f, side))) return rc;         // the linear family replaces a function on this side
     m->bcs[f][side].kind = OCN_BC_FLUX; m->bcs[f][side].value = 0.0; m->bcs[f][side].array = nullptr;   // halos of a Flux side: zero gradient
     m->any_bc = true;
     m->lin[f][side].on = true; m->lin[f][side].dep = fd; m->lin[f][side].a = a; m->lin[f][side].b = b;
@@ -3005,6 +3189,91 @@ extern "C" int ocn_model_set_smagorinsky(ocn_model_t m, double C, double Cb, int
     return OCN_OK;
 }
 
+// the device-resident table of the model's programs, after the host copy changed (never inside a captured step)
+static int bf_upload(ocn_model_s *m) {
+    auto &B = m->bf;
+    B.reads_time = false;
+    for (int q = 0; q < B.n; ++q)
+        for (int w = 0; w < B.slot[q].fn.n; ++w) B.reads_time = B.reads_time || B.slot[q].fn.ins[w].op == OCN_EXPR_TIME;
+    if (B.n == 0) return OCN_OK;
+    HIP_TRY(hipStreamSynchronize(g_stream));          // a launch already queued still reads the table as it was
+    if (!B.table_d) HIP_TRY(dev_alloc((void **)&B.table_d, sizeof(BfFunction) * BF_MAX_FUNCTIONS));
+    BfFunction h[BF_MAX_FUNCTIONS];
+    for (int q = 0; q < B.n; ++q) h[q] = B.slot[q].fn;
+    HIP_TRY(hipMemcpy(B.table_d, h, sizeof(BfFunction) * (size_t)B.n, hipMemcpyHostToDevice));
+    return OCN_OK;
+}
+
+// the function of side `side` of field f leaves (another condition replaces it): its array is freed; the caller sets the side's condition
+static int bf_remove(ocn_model_s *m, int f, int side) {
+    auto &B = m->bf;
+    for (int q = 0; q < B.n; ++q)
+        if (B.slot[q].f == f && B.slot[q].side == side) {
+            HIP_TRY(hipStreamSynchronize(g_stream));
+            hipFree(B.slot[q].fn.out);
+            for (int w = q; w + 1 < B.n; ++w) B.slot[w] = B.slot[w + 1];
+            B.n -= 1;
+            if (m->bcs[f][side].kind == OCN_BC_FLUX) m->bcs[f][side].array = nullptr;
+            return bf_upload(m);
+        }
+    return OCN_OK;
+}
+
+// name.side = FluxBoundaryCondition(func, field_dependencies = dep_names, ...) with the program of func
+extern "C" int ocn_model_set_flux_bc_function(ocn_model_t m, const char *name, int side, const ocn_expr_ins_t *program, int n,
+                                              const char *const *dep_names, int ndeps) {
+    NEED_INIT();
+    if (m) m->epoch += 1;
+    if (!m || !name) return fail(OCN_EINVAL, "NULL argument");
+    if (m->dm) return fail(OCN_ENOTSUP, "boundary functions are not served on a partitioned model");
+    const int f = field_index(m, name);
+    if (f < 0) return fail(OCN_EINVAL, "name %s not found in model.velocities or model.tracers.", name);
+    bool reads_time;
+    int rc = bf_validate_program(program, n, ndeps, &reads_time);
+    if (rc) return rc;
+    if (ndeps > 0 && !dep_names) return fail(OCN_EINVAL, "NULL dependency names");
+    int dep_field[BF_MAX_DEPS], dep_locs[BF_MAX_DEPS][3];
+    for (int s = 0; s < ndeps; ++s) {
+        dep_field[s] = dep_names[s] ? field_index(m, dep_names[s]) : -1;
+        if (dep_field[s] < 0) return fail(OCN_EINVAL, "name %s not found in model.velocities or model.tracers.", dep_names[s] ? dep_names[s] : "(NULL)");
+        memcpy(dep_locs[s], m->loc[dep_field[s]], sizeof(int) * 3);
+    }
+    if ((rc = validate_bc(m->grid->d, m->loc[f], side, OCN_BC_FLUX))) return rc;
+    BfFunction fn;
+    if ((rc = bf_make_function(m->grid, program, n, m->loc[f], side, dep_field, dep_locs, ndeps, nullptr, &fn))) return rc;
+    auto &B = m->bf;
+    int q = 0;
+    while (q < B.n && !(B.slot[q].f == f && B.slot[q].side == side)) ++q;
+    if (q == BF_MAX_FUNCTIONS) return fail(OCN_EINVAL, "a model carries at most %d boundary functions", BF_MAX_FUNCTIONS);
+    if (q < B.n) fn.out = B.slot[q].fn.out;          // the side had a function: its array stays (the extents are the side's)
+    else {
+        const size_t bytes = sizeof(double) * (size_t)fn.Na * fn.Nb;
+        HIP_TRY(dev_alloc((void **)&fn.out, bytes));
+        HIP_TRY(hipMemsetAsync(fn.out, 0, bytes, g_stream));
+        B.n += 1;
+    }
+    B.slot[q].f = f; B.slot[q].side = side; B.slot[q].fn = fn;
+    m->bcs[f][side].kind = OCN_BC_FLUX; m->bcs[f][side].value = 0.0; m->bcs[f][side].array = fn.out;
+    m->any_bc = m->any_flux_bc = true;
+    m->lin[f][side].on = false;                 // the function replaces a linear field-dependent condition on this side
+    m->any_linear_flux = false;
+    for (int a = 0; a < m->nf; ++a)
+        for (int sd = 0; sd < 6; ++sd) m->any_linear_flux = m->any_linear_flux || m->lin[a][sd].on;
+    return bf_upload(m);
+}
+
+extern "C" int ocn_model_boundary_function_values(ocn_model_t m, const char *name, int side, double *host_out) {
+    NEED_INIT();
+    if (!m || !name || !host_out) return fail(OCN_EINVAL, "NULL argument");
+    const int f = field_index(m, name);
+    for (int q = 0; q < m->bf.n; ++q)
+        if (m->bf.slot[q].f == f && m->bf.slot[q].side == side) {
+            const BfFunction &fn = m->bf.slot[q].fn;
+            return ocn_memcpy_d2h(host_out, fn.out, sizeof(double) * (size_t)fn.Na * fn.Nb);
+        }
+    return fail(OCN_EINVAL, "%s carries no boundary function on side %d", name, side);
+}
+
 static int model_set_bc(ocn_model_t m, const char *name, int side, int kind, double value, const double *array) {
     if (m) m->epoch += 1;
     if (!m || !name) return fail(OCN_EINVAL, "NULL argument");
@@ -3031,6 +3300,7 @@ static int model_set_bc(ocn_model_t m, const char *name, int side, int kind, dou
     int rc = validate_bc(m->grid->d, m->loc[f], side, kind);
     if (rc) return rc;
     if (array && kind == OCN_BC_DEFAULT) return fail(OCN_EINVAL, "an array-valued condition needs a classification (Flux, Value, Gradient, Open)");
+    if ((rc = bf_remove(m, f, side))) return rc;        // a plain condition replaces a function on this side
     m->bcs[f][side].kind = kind;
     m->bcs[f][side].value = value;
     m->bcs[f][side].array = array;
@@ -3214,7 +3484,8 @@ extern "C" int ocn_model_time_step(ocn_model_t m, double dt) {
         return rc;
     }
     // ... and not with a scheme side: the boundary step takes last_stage_Δt, whose corrected third-stage value changes from step to step
-    if (!m->opt.use_graph || m->profile || m->iteration == 0 || !g_stream_owned || m->n_scheme) return rk3_time_step(m, dt);
+    // ... nor with a boundary function that reads t: the time is an argument of its launch
+    if (!m->opt.use_graph || m->profile || m->iteration == 0 || !g_stream_owned || m->n_scheme || m->bf.reads_time) return rk3_time_step(m, dt);
     if (m->graph_exec && m->graph_dt == dt && m->graph_epoch == m->epoch * 1000003ull + g_epoch) {
         hipError_t e = hipGraphLaunch(m->graph_exec, g_stream);
         if (e != hipSuccess) return fail((int)e, "hipGraphLaunch: %s", hipGetErrorString(e));

@@ -321,6 +321,11 @@ class RectilinearGrid:
             _lib.check(_lib.lib().ocn_grid_set_nodes(
                 h, d3(F[d][0 if flat[d] else H[d]] for d in range(3)), d3(Cn[d][0 if flat[d] else H[d]] for d in range(3)),
                 d3(F[d][0 if flat[d] else H[d] + N[d]] for d in range(3)), zf, zc))
+            # ... and the node tables (elements of Julia ranges, copied rather than recomputed): what boundary functions read
+            self._node_tables = ([np.ascontiguousarray(F[d][:1] if flat[d] else F[d][H[d]:H[d] + N[d] + 1], dtype=np.float64) for d in range(3)],
+                                 [np.ascontiguousarray(Cn[d][:1] if flat[d] else Cn[d][H[d]:H[d] + N[d]], dtype=np.float64) for d in range(3)])
+            tables = [(dp * 3)(*[a.ctypes.data_as(dp) for a in t]) for t in self._node_tables]
+            _lib.check(_lib.lib().ocn_grid_set_node_tables(h, tables[0], tables[1]))
         return self._handle
 
     @property

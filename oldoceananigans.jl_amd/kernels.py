@@ -73,6 +73,35 @@ def accumulate_operation(grid, operand, dim, reverse, use_metric, out):
                                                    out.data))
 
 
+def evaluate_boundary_function(grid, program, loc, side, deps, time, out=None):
+    """getbc of a traced boundary function (boundary_functions.py: a list of instruction tuples (op, a, b, c, imm)) at every point of
+    `side` ("west" .. "top" or 0..5) for a condition of a field at `loc`: `deps` are Fields with current halos, one per dependency slot;
+    returns the host array (Na, Nb). `out`: a device pointer to evaluate into instead (then nothing is copied back)"""
+    from .boundary_conditions import SIDES, _tangential_shape
+    from .boundary_functions import program_array
+    side = SIDES.index(side) if isinstance(side, str) else int(side)
+    codes = [0 if l is None else l.code for l in loc]
+    deps = list(deps)
+    ptrs = _ptr_array(deps) if deps else None
+    locs = _loc_array(deps) if deps else None
+    arr, n = program_array(program)
+    shape = _tangential_shape(grid, side) if 0 <= side <= 5 else (1, 1)
+    dev = out
+    if out is None:
+        dev = C.c_void_p()
+        _lib.check(_lib.lib().ocn_malloc(C.byref(dev), 8 * shape[0] * shape[1]))
+    try:
+        _lib.check(_lib.lib().ocn_evaluate_boundary_function(grid.handle, arr, n, _lib.i3(codes), side, ptrs, locs, len(deps), float(time), dev))
+        if out is not None:
+            return None
+        host = np.empty(shape, dtype=np.float64, order="F")
+        _lib.check(_lib.lib().ocn_memcpy_d2h(host.ctypes.data, dev, host.nbytes))
+        return host
+    finally:
+        if out is None:
+            _lib.lib().ocn_free(dev)
+
+
 def compute_tendencies_and_substep(grid, fields, Gn, next_fields, Gm, Δt, γ, ζ, kernel_parameters=None):
     """tendencies of all prognostic fields (u, v, w, tracers...) + the rk3_substep! of the next stage into `next_fields`"""
     _lib.check(_lib.lib().ocn_compute_tendencies_and_substep(

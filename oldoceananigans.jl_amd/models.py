@@ -80,6 +80,9 @@ class NonhydrostaticModel:
         # OpenBoundaryCondition(value; scheme = PerturbationAdvection(...)): refused here where the reference has no method for it
         from .boundary_conditions import validate_open_boundary_schemes
         validate_open_boundary_schemes(boundary_conditions, grid)
+        # FluxBoundaryCondition(func, ...): refused here on partitioned grids and on diffusivity fields
+        from .boundary_conditions import validate_boundary_functions
+        validate_boundary_functions(boundary_conditions, grid)
         # "Adjust advection scheme to be valid on a particular grid size" and "Adjust halos when the advection scheme or turbulence
         # closure requires it" (nonhydrostatic_model.jl:176-184). The library derives the same per-direction schemes from the grid
         # size (ocn_grid_create), so only the descriptor and the halo are settled here.
@@ -200,8 +203,22 @@ class NonhydrostaticModel:
             if name not in ("u", "v", "w") + self.tracer_names:
                 raise ValueError(f"boundary conditions given for {name}, which is not a velocity or tracer of the model")
             targets.append((self._cname(name), fbcs))
+        self.boundary_functions = {}                     # (field name, side) -> RegularizedBoundaryFunction
+        names = {self._cname(n): n for n in ("u", "v", "w") + self.tracer_names}
         for cname, fbcs in targets:
             for side, bc in fbcs.sides.items():
+                if getattr(bc, "function", None) is not None:
+                    # regularize_boundary_condition (continuous_boundary_function.jl:76-92): the function is recorded once, here
+                    from .boundary_functions import RegularizedBoundaryFunction, program_array
+                    if cname not in names:
+                        raise NotImplementedError(f"a function-valued condition of the diffusivity field {cname} is not built")
+                    rbf = RegularizedBoundaryFunction(bc.function, self.grid, locations[names[cname]], SIDES.index(side), tuple(names.values()))
+                    program, n = program_array(rbf.program)
+                    deps = (C.c_char_p * max(len(rbf.field_dependencies), 1))(*[self._cname(d).encode() for d in rbf.field_dependencies])
+                    _lib.check(_lib.lib().ocn_model_set_flux_bc_function(self.handle, cname.encode(), SIDES.index(side), program, n, deps,
+                                                                         len(rbf.field_dependencies)))
+                    self.boundary_functions[(names[cname], side)] = rbf
+                    continue
                 if bc.linear is not None:
                     a, b, dep = bc.linear
                     _lib.check(_lib.lib().ocn_model_set_linear_flux_bc(self.handle, cname.encode(), SIDES.index(side), a, b,
@@ -260,6 +277,16 @@ class NonhydrostaticModel:
         v = C.c_int()
         _lib.check(_lib.lib().ocn_model_get_option(self.handle, key.encode(), C.byref(v)))
         return v.value
+
+    def boundary_function_values(self, name, side):
+        """the array of the function-valued Flux condition name.side as the library last evaluated it: (Na, Nb) over the two tangential
+        directions"""
+        import numpy as np
+        from .boundary_conditions import SIDES, _tangential_shape
+        out = np.empty(_tangential_shape(self.grid, SIDES.index(side)), dtype=np.float64, order="F")
+        _lib.check(_lib.lib().ocn_model_boundary_function_values(self.handle, self._cname(name).encode(), SIDES.index(side),
+                                                                 out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
 
     def profile_read(self):
         """(total ms, count) of the event-timed tendency evaluations since the last read"""

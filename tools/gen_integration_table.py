@@ -28,8 +28,10 @@ def jl_type(t):
         return "Ptr{OcnTransport}"
     if base == "ocn_operand_t":
         return "Ptr{OcnOperand}"
+    if base == "ocn_expr_ins_t":
+        return "Ptr{OcnExprIns}"
     if base == "char":
-        return "Cstring"
+        return "Ptr{Cstring}" if ptr > 1 else "Cstring"
     if base == "void":
         return "Ptr{Ptr{Cvoid}}" if ptr > 1 else "Ptr{Cvoid}"
     scalar = {"int": "Cint", "double": "Cdouble", "size_t": "Csize_t", "long": "Clong", "int64_t": "Int64", "unsigned": "Cuint"}.get(base, base)
@@ -56,7 +58,8 @@ table = [MARK, "",
          "return is a status: `check(rc)` of §1. `OcnForcing` mirrors `ocn_forcing_t` the same way; its mask and target tables are host",
          "`Vector{Float64}`s the binder fills with the reference's own `GaussianMask` / `PiecewiseLinearMask` / `LinearTarget` at the field's nodes.",
          "`OcnOperand` mirrors `ocn_operand_t` (`op::Cint; a::Ptr{Cdouble}; b::Ptr{Cdouble}; ca::Cdouble; cb::Cdouble; loc_a, loc_b, loc::NTuple{3, Cint}`),",
-         "filled from a `BinaryOperation`'s `op`, `a`, `b` and the locations of the three.", "", "| entry point | binding |", "|---|---|"] + rows
+         "filled from a `BinaryOperation`'s `op`, `a`, `b` and the locations of the three. `OcnExprIns` mirrors `ocn_expr_ins_t`",
+         "(`op::Cint; a::Cint; b::Cint; c::Cint; imm::Cdouble`): one recorded operation of a boundary function.", "", "| entry point | binding |", "|---|---|"] + rows
 p = os.path.join(ROOT, "INTEGRATION.md")
 s = open(p).read()
 if MARK in s:
