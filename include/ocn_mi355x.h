@@ -90,7 +90,9 @@ int ocn_grid_set_nodes(ocn_grid_t grid, const double first_face[3], const double
 /* The node TABLES of the grid: per direction HOST arrays of the N + 1 face nodes grid.xᶠᵃᵃ[1 .. N + 1] and the N centre nodes
  * grid.xᶜᵃᵃ[1 .. N] (one of each in a Flat direction), copied to the device. The reference's nodes are elements of Julia ranges, not
  * x₀ + (i - 1) Δ in floating point, so a kernel that hands coordinates to a user's function reads them from here: needed by
- * ocn_evaluate_boundary_function and ocn_model_set_flux_bc_function (OCN_ESTATE without it). */
+ * ocn_evaluate_boundary_function, ocn_model_set_flux_bc_function, ocn_evaluate_forcing_function and OCN_FORCING_FUNCTION terms
+ * (OCN_ESTATE without it). The device block is allocated by the first call and rewritten in place by later ones: the programs a model
+ * keeps hold addresses inside it. */
 int ocn_grid_set_node_tables(ocn_grid_t grid, const double *const faces[3], const double *const centers[3]);
 
 /* ---------------------------------------------------------------- halo fills (BoundaryConditions/) -------------- */
@@ -646,9 +648,29 @@ int ocn_model_boundary_function_values(ocn_model_t model, const char *name, int 
  * an array stays BORROWED while it is set. A partitioned model takes its rank-local tables and arrays. Model option "forcing_path"
  * reports which pass adds the term: 0 none; 1 the role tendency kernel (no physics terms, no Flux condition, Periodic z, single GPU: the
  * RK3 substep stays fused); 3 a standalone pass after the tendency launches (every other configuration; the substeps then run as their
- * own launches); 2 (inside the physics epilogue) is reserved and never reported. "fused_forcing" = 0 forces the standalone pass. */
+ * own launches); 2 (inside the physics epilogue) is reserved and never reported. "fused_forcing" = 0 forces the standalone pass.
+ *   OCN_FORCING_FUNCTION    F = program(x, y, z, t, deps...) at the forced field's (i, j, k) (Forcings/continuous_forcing.jl:119-142;
+ *                           Relaxation with a function mask or target, relaxation.jl:80-101): a recorded program as above, in which
+ *                           OCN_EXPR_COORD a = 0 / 1 / 2 is the x / y / z node of the field's own location, OCN_EXPR_TIME the clock of
+ *                           the tendency evaluation (the stage times of runge_kutta_3.jl; tⁿ in AB2) and OCN_EXPR_FIELD a = slot the
+ *                           model field dep_names[slot], read at its own location (assumed_field_location) and interpolated to the
+ *                           forced field's by the operator interpolation_operator(from, to) names: the lower direction innermost, none
+ *                           along a Flat direction. A Relaxation is the program rate * mask(X...) * (target(X..., t) - φ) with φ as
+ *                           dependency slot 0; a binder passes every ContinuousForcing this way.
+ * The term takes its place in the sum like any other. A field with a function term is completed by forcing_function_kernel (all its terms,
+ * in sum order, one launch for all such fields); "forcing_path" then answers 3. Values that depend on no coordinate and no field, or on
+ * one coordinate only, are evaluated once per evaluation moment into 1-D tables (one more launch, and only when a program reads
+ * OCN_EXPR_TIME: the others' tables are filled when the forcing is set); per cell only the remaining instructions run, on the same
+ * operand bits, so the result does not depend on "forcing_function_hoist" (ocn_model_set_option on the model, default 1; 0: the recorded program at every cell).
+ * A model whose forcing programs read OCN_EXPR_TIME steps without the captured graph. At most 16 function terms per model.
+ * OCN_EINVAL: the program errors of ocn_evaluate_boundary_function (coordinates 0 .. 2 here), a coordinate along a Flat direction, an
+ * unknown dependency name, a seventeenth function; OCN_ENOTSUP on a partitioned model; OCN_ESTATE without ocn_grid_set_node_tables.
+ * ocn_model_get_option answers "forcing_functions" (their number), "forcing_function_cell_instructions" (the longest per-cell program),
+ * "forcing_functions_read_time" and "forcing_function_arithmetic_only" (1: no per-cell program holds EXP .. POW, and the instantiation
+ * of the kernel without them runs -- twice the waves per SIMD). */
 #define OCN_FORCING_ARRAY 1
 #define OCN_FORCING_RELAXATION 2
+#define OCN_FORCING_FUNCTION 3
 #define OCN_MAX_FORCING_TERMS 8
 typedef struct {
     int kind;
@@ -661,8 +683,26 @@ typedef struct {
     int target_dir;             /* -1: constant target `target` (zerofunction: 0.0); 0 / 1 / 2: the table along x / y / z */
     const double *target_table; /* HOST, target(node), same layout */
     double target;
+    /* OCN_FORCING_FUNCTION (all zero for the other kinds): the recorded program, F = program(x, y, z, t, deps...), and the model fields
+       ("u", "v", "w", "c0" ..) of its dependency slots; both are copied */
+    const ocn_expr_ins_t *program;
+    int n;
+    const char *const *dep_names;
+    int ndeps;
 } ocn_forcing_t;
 int ocn_model_set_forcing(ocn_model_t model, int field, const ocn_forcing_t *terms, int nterms);
+/* A forcing program at every interior point of a field at `loc`, into the interior of `out`, a parent-shaped DEVICE array at `loc`
+ * (ocn_grid_parent_size; halos untouched): what an OCN_FORCING_FUNCTION term adds, without a model. deps[s]: BORROWED haloed device arrays
+ * with current halos, at dep_locs[s]. hoist: 1 tables + per-cell program (two launches), 0 the recorded program per cell (one); the bits
+ * are the same. Synchronous. With Forcing(array), which is borrowed, a caller can refresh an arbitrary forcing between time-steps.
+ * Errors as OCN_FORCING_FUNCTION above. */
+int ocn_evaluate_forcing_function(ocn_grid_t grid, const ocn_expr_ins_t *program, int n, const int loc[3], const double *const *deps,
+                                  const int (*dep_locs)[3], int ndeps, double time, int hoist, double *out);
+/* Host arithmetic only (callable before ocn_init): how a forcing program is split. value_class[q] (n ints, may be NULL) is the class of
+ * value q: 0 uniform (depends on no coordinate and no field), 1 / 2 / 3 a line value of x / y / z (that coordinate only), 4 a cell value
+ * (two coordinates, or a field). *n_cell: the length of the per-cell program -- the cell instructions plus one table load per distinct
+ * uniform or line value they consume (one load when the result itself is no cell value). OCN_EINVAL: the program errors above. */
+int ocn_forcing_function_plan(const ocn_expr_ins_t *program, int n, int ndeps, int *value_class, int *n_cell);
 /* background_fields = (name = B,) of the model constructor (Models/NonhydrostaticModels/background_fields.jl:97-116, BackgroundFields{false}):
  * name is "u", "v", "w" or "c<n>"; parent is a haloed device array at that field's location, BORROWED for the model's lifetime, whose
  * halos hold what the background is there (a function's analytic continuation, not a periodic wrap); NULL removes it (ZeroField).

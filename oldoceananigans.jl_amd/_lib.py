@@ -36,7 +36,8 @@ class BC(C.Structure):
 class Forcing(C.Structure):
     """ocn_forcing_t"""
     _fields_ = [("kind", C.c_int), ("array", C.c_void_p), ("mask_dir", C.c_int), ("mask_table", C.POINTER(C.c_double)),
-                ("rate_mask", C.c_double), ("target_dir", C.c_int), ("target_table", C.POINTER(C.c_double)), ("target", C.c_double)]
+                ("rate_mask", C.c_double), ("target_dir", C.c_int), ("target_table", C.POINTER(C.c_double)), ("target", C.c_double),
+                ("program", C.c_void_p), ("n", C.c_int), ("dep_names", C.c_void_p), ("ndeps", C.c_int)]
 
 
 class Operand(C.Structure):
@@ -123,6 +124,8 @@ SYMBOLS = {
     "ocn_model_set_flux_bc_function": (C.c_int, [_vp, C.c_char_p, C.c_int, C.POINTER(ExprIns), C.c_int, C.POINTER(C.c_char_p), C.c_int]),
     "ocn_model_boundary_function_values": (C.c_int, [_vp, C.c_char_p, C.c_int, _dp]),
     "ocn_model_set_forcing": (C.c_int, [_vp, C.c_int, C.POINTER(Forcing), C.c_int]),
+    "ocn_evaluate_forcing_function": (C.c_int, [_vp, C.POINTER(ExprIns), C.c_int, _ip, _pp, _vp, C.c_int, C.c_double, C.c_int, _vp]),
+    "ocn_forcing_function_plan": (C.c_int, [C.POINTER(ExprIns), C.c_int, C.c_int, _ip, _ip]),
     "ocn_compute_advective_tendency": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _ip, C.c_int]),
     "ocn_sum_parent": (C.c_int, [_vp, _vp, _vp, _ip, _vp]),
     "ocn_model_set_background_field": (C.c_int, [_vp, C.c_char_p, _vp]),

@@ -36,8 +36,8 @@ class _Trace:
 
     def emit(self, op, a=0, b=0, c=0, imm=0.0):
         if len(self.instructions) == MAX_INSTRUCTIONS:
-            raise ValueError(f"the boundary function performs more than {MAX_INSTRUCTIONS} operations: the limit of a traced boundary "
-                             f"function is {MAX_INSTRUCTIONS} instructions")
+            raise ValueError(f"the function performs more than {MAX_INSTRUCTIONS} operations: the limit of a traced function is "
+                             f"{MAX_INSTRUCTIONS} instructions")
         self.instructions.append((OPS[op], int(a), int(b), int(c), float(imm)))
         return len(self.instructions) - 1
 
@@ -45,14 +45,14 @@ class _Trace:
         """the index of the value of x: a symbol's own (a leaf is emitted on first use), or a new constant"""
         if isinstance(x, Symbol):
             if x.trace is not self:
-                raise ValueError("a symbol of another boundary function")
+                raise ValueError("a symbol of another function")
             if x.index is None:
                 x.index = self.emit(*x.leaf)
             return x.index
         if isinstance(x, (bool, np.bool_)):
             x = 1.0 if x else 0.0
         if not isinstance(x, (numbers.Real, np.floating, np.integer)):
-            raise TypeError(f"{type(x).__name__} in a boundary function: symbols and real numbers can be recorded")
+            raise TypeError(f"{type(x).__name__} in a function: symbols and real numbers can be recorded")
         return self.emit("const", imm=float(x))
 
 
@@ -214,10 +214,11 @@ class RegularizedBoundaryFunction:
 
 
 def trace(func, coordinates, ndeps, parameters=None):
-    """call func(X..., t, deps..., [parameters]) once with symbols; `coordinates`: for every X the tangential direction (0 / 1) it is the
-    node of. Returns the program, a list of (op, a, b, c, imm)."""
+    """call func(X..., t, deps..., [parameters]) once with symbols; `coordinates`: for every X the direction it is the node of -- the
+    tangential direction 0 / 1 of a boundary function, x / y / z = 0 / 1 / 2 of a function in the volume (forcings.py). Returns the
+    program, a list of (op, a, b, c, imm)."""
     if ndeps > MAX_DEPENDENCIES:
-        raise ValueError(f"{ndeps} field dependencies: the limit of a boundary function is {MAX_DEPENDENCIES} dependencies")
+        raise ValueError(f"{ndeps} field dependencies: the limit of a traced function is {MAX_DEPENDENCIES} dependencies")
     tr = _Trace()
     args = [Symbol(tr, leaf=("coord", c)) for c in coordinates] + [Symbol(tr, leaf=("time",))] + [Symbol(tr, leaf=("field", s)) for s in range(ndeps)]
     if parameters is not None:
@@ -231,6 +232,35 @@ def trace(func, coordinates, ndeps, parameters=None):
         tr.value(result)                        # a plain number: a one-instruction program (anything else: TypeError)
         tr.instructions = tr.instructions[-1:]
     return tr.instructions
+
+
+def interpret(program, coordinates, time, deps):
+    """a program on numpy arrays, operation by operation (host twin of the device interpreters): coordinates[a] and deps[slot] are
+    arrays that broadcast against each other"""
+    with np.errstate(all="ignore"):
+        v = []
+        for op, a, b, c, imm in program:
+            k = OP_NAMES[op]
+            if k == "const":
+                r = np.float64(imm)
+            elif k == "coord":
+                r = coordinates[a]
+            elif k == "time":
+                r = np.float64(time)
+            elif k == "field":
+                r = deps[a]
+            elif k in ("<", "<=", ">", ">="):
+                r = {"<": np.less, "<=": np.less_equal, ">": np.greater, ">=": np.greater_equal}[k](v[a], v[b]).astype(np.float64)
+            elif k == "select":
+                r = np.where(v[a] != 0.0, v[b], v[c])
+            elif k in ("+", "-", "*", "/", "min", "max", "pow"):
+                r = {"+": np.add, "-": np.subtract, "*": np.multiply, "/": np.divide, "min": np.minimum, "max": np.maximum,
+                     "pow": np.power}[k](v[a], v[b])
+            else:
+                r = {"neg": np.negative, "abs": np.abs, "sqrt": np.sqrt, "exp": np.exp, "log": np.log, "sin": np.sin, "cos": np.cos,
+                     "tanh": np.tanh}[k](v[a])
+            v.append(r)
+        return v[-1]
 
 
 def program_array(program):

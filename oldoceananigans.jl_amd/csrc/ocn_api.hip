@@ -14,6 +14,7 @@
 #include "ocn_open_boundary.h"
 #include "ocn_diagnostics.h"
 #include "ocn_boundary_function.h"
+#include "ocn_forcing_function.h"
 #include <hipfft/hipfft.h>
 #include <array>
 #include <cfloat>
@@ -22,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -360,13 +362,16 @@ extern "C" int ocn_grid_set_node_tables(ocn_grid_t grid, const double *const fac
         at_f[d] = h.size(); h.insert(h.end(), faces[d], faces[d] + nf);
         at_c[d] = h.size(); h.insert(h.end(), centers[d], centers[d] + nc);
     }
-    double *dev = nullptr;
-    hipError_t e = dev_alloc((void **)&dev, h.size() * sizeof(double));
-    if (e != hipSuccess) return fail((int)e, "dev_alloc(node tables): %s", hipGetErrorString(e));
-    e = hipMemcpy(dev, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { hipFree(dev); return fail((int)e, "hipMemcpy(node tables): %s", hipGetErrorString(e)); }
-    HIP_TRY(hipStreamSynchronize(g_stream));          // a launch already queued may still read the old tables
-    hipFree(grid->node_tables);
+    // The block is allocated once per grid and rewritten IN PLACE by a later call (its size depends on the grid only): the programs of
+    // boundary and forcing functions hold addresses inside it (BfFunction::xa, FfFunction::x) for as long as their model lives.
+    double *dev = grid->node_tables;
+    if (!dev) {
+        hipError_t e = dev_alloc((void **)&dev, h.size() * sizeof(double));
+        if (e != hipSuccess) return fail((int)e, "dev_alloc(node tables): %s", hipGetErrorString(e));
+    }
+    HIP_TRY(hipStreamSynchronize(g_stream));          // a launch already queued may still read the old nodes
+    hipError_t e = hipMemcpy(dev, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { if (!grid->node_tables) hipFree(dev); return fail((int)e, "hipMemcpy(node tables): %s", hipGetErrorString(e)); }
     grid->node_tables = dev;
     for (int d = 0; d < 3; ++d) { grid->nodes_f[d] = dev + at_f[d]; grid->nodes_c[d] = dev + at_c[d]; }
     return OCN_OK;
@@ -882,31 +887,43 @@ static DgOut dg_make_out(const DGrid &g, const int loc[3], int reduced_mask, dou
 // ---------------------------------------------------------------------------------------------------------------------
 // boundary functions (ocn_boundary_function.h): programs of FluxBoundaryCondition(func, field_dependencies, parameters)
 // ---------------------------------------------------------------------------------------------------------------------
+// the ONE table of the ops on the host: value operands of an instruction (the leaves have none), -1 for an unknown op
+static int expr_arity(int op) {
+    switch (op) {
+    case OCN_EXPR_CONST: case OCN_EXPR_COORD: case OCN_EXPR_TIME: case OCN_EXPR_FIELD: return 0;
+    case OCN_EXPR_NEG: case OCN_EXPR_ABS: case OCN_EXPR_SQRT: case OCN_EXPR_EXP: case OCN_EXPR_LOG: case OCN_EXPR_SIN: case OCN_EXPR_COS:
+    case OCN_EXPR_TANH: return 1;
+    case OCN_EXPR_ADD: case OCN_EXPR_SUB: case OCN_EXPR_MUL: case OCN_EXPR_DIV: case OCN_EXPR_MIN: case OCN_EXPR_MAX: case OCN_EXPR_POW:
+    case OCN_EXPR_LT: case OCN_EXPR_LE: case OCN_EXPR_GT: case OCN_EXPR_GE: return 2;
+    case OCN_EXPR_SELECT: return 3;
+    default: return -1;          // no op of the public enum
+    }
+}
+
+static int no_connected_topology(const DGrid &g, const char *what) {
+    const int T[3] = {g.tx, g.ty, g.tz};
+    for (int d = 0; d < 3; ++d)
+        if (T[d] == OCN_CONNECTED || T[d] == OCN_RIGHT_CONNECTED || T[d] == OCN_LEFT_CONNECTED)
+            return fail(OCN_ENOTSUP, "%s on a partitioned grid (connected topology in dimension %d) are not built", what, d);
+    return OCN_OK;
+}
+
 // every operand of every instruction names an earlier value (or is 0 where unused): nothing the kernel indexes with is left unchecked
-static int bf_validate_program(const ocn_expr_ins_t *program, int n, int ndeps, bool *reads_time) {
-    if (n < 1 || n > BF_MAX_INS) return fail(OCN_EINVAL, "a boundary function has 1..%d instructions; got %d", BF_MAX_INS, n);
-    if (ndeps < 0 || ndeps > BF_MAX_DEPS) return fail(OCN_EINVAL, "a boundary function has 0..%d field dependencies; got %d", BF_MAX_DEPS, ndeps);
+// max_coord: the largest coordinate index (1 on a boundary: two tangential directions; 2 in the volume: x / y / z)
+static int bf_validate_program(const ocn_expr_ins_t *program, int n, int ndeps, bool *reads_time, int max_coord = 1) {
+    if (n < 1 || n > BF_MAX_INS) return fail(OCN_EINVAL, "a function program has 1..%d instructions; got %d", BF_MAX_INS, n);
+    if (ndeps < 0 || ndeps > BF_MAX_DEPS) return fail(OCN_EINVAL, "a function program has 0..%d field dependencies; got %d", BF_MAX_DEPS, ndeps);
     if (!program) return fail(OCN_EINVAL, "NULL program");
     if (reads_time) *reads_time = false;
     for (int q = 0; q < n; ++q) {
         const ocn_expr_ins_t &I = program[q];
-        int values = 0;                 // how many of a, b, c are value operands
-        switch (I.op) {
-        case OCN_EXPR_CONST: break;
-        case OCN_EXPR_TIME: if (reads_time) *reads_time = true; break;
-        case OCN_EXPR_COORD:
-            if (I.a != 0 && I.a != 1) return fail(OCN_EINVAL, "instruction %d: coordinate %d is not 0 or 1", q, I.a);
-            break;
-        case OCN_EXPR_FIELD:
-            if (I.a < 0 || I.a >= ndeps) return fail(OCN_EINVAL, "instruction %d: dependency slot %d outside 0..%d", q, I.a, ndeps - 1);
-            break;
-        case OCN_EXPR_NEG: case OCN_EXPR_ABS: case OCN_EXPR_SQRT: case OCN_EXPR_EXP: case OCN_EXPR_LOG: case OCN_EXPR_SIN: case OCN_EXPR_COS:
-        case OCN_EXPR_TANH: values = 1; break;
-        case OCN_EXPR_ADD: case OCN_EXPR_SUB: case OCN_EXPR_MUL: case OCN_EXPR_DIV: case OCN_EXPR_MIN: case OCN_EXPR_MAX: case OCN_EXPR_POW:
-        case OCN_EXPR_LT: case OCN_EXPR_LE: case OCN_EXPR_GT: case OCN_EXPR_GE: values = 2; break;
-        case OCN_EXPR_SELECT: values = 3; break;
-        default: return fail(OCN_EINVAL, "instruction %d: unknown op %d", q, I.op);
-        }
+        const int values = expr_arity(I.op);          // how many of a, b, c are value operands
+        if (values < 0) return fail(OCN_EINVAL, "instruction %d: unknown op %d", q, I.op);
+        if (I.op == OCN_EXPR_TIME && reads_time) *reads_time = true;
+        if (I.op == OCN_EXPR_COORD && (I.a < 0 || I.a > max_coord))
+            return fail(OCN_EINVAL, "instruction %d: coordinate %d is not 0 %s", q, I.a, max_coord == 1 ? "or 1" : ".. 2");
+        if (I.op == OCN_EXPR_FIELD && (I.a < 0 || I.a >= ndeps))
+            return fail(OCN_EINVAL, "instruction %d: dependency slot %d outside 0..%d", q, I.a, ndeps - 1);
         const int operand[3] = {I.a, I.b, I.c};
         for (int w = 0; w < 3; ++w) {
             if (w < values) {
@@ -924,9 +941,7 @@ static int bf_make_function(const ocn_grid_s *grid, const ocn_expr_ins_t *progra
                             const int (*dep_locs)[3], int ndeps, double *out, BfFunction *fn) {
     const DGrid &g = grid->d;
     const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz}, T[3] = {g.tx, g.ty, g.tz};
-    for (int d = 0; d < 3; ++d)
-        if (T[d] == OCN_CONNECTED || T[d] == OCN_RIGHT_CONNECTED || T[d] == OCN_LEFT_CONNECTED)
-            return fail(OCN_ENOTSUP, "boundary functions on a partitioned grid (connected topology in dimension %d) are not built", d);
+    if (const int rc = no_connected_topology(g, "boundary functions")) return rc;
     if (side < 0 || side > 5) return fail(OCN_EINVAL, "side %d out of range (0..5 = west, east, south, north, bottom, top)", side);
     const int d = side / 2, right = side & 1;
     if (!(right ? wall_hi(T[d]) : wall_lo(T[d]))) return fail(OCN_EINVAL, "side %d is not a wall of the grid (Bounded direction)", side);
@@ -995,6 +1010,190 @@ extern "C" int ocn_evaluate_boundary_function(ocn_grid_t grid, const ocn_expr_in
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream);          // the table is this call's
     hipFree(table_d);
     if (e != hipSuccess) return fail((int)e, "boundary_function_kernel: %s", hipGetErrorString(e));
+    return OCN_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// forcing functions (ocn_forcing_function.h): programs evaluated in the volume, their line and uniform values hoisted into tables
+// ---------------------------------------------------------------------------------------------------------------------
+// Host arithmetic only. Every value gets the set of inputs it depends on out of {x, y, z, field} (constants and t add nothing) and from it
+// its class: FF_UNIFORM (none), FF_LINE + d (coordinate d only), FF_CELL (two coordinates, or a field). A uniform or line value that a
+// cell instruction consumes, or that is the result, is a ROOT: it gets a table. The per-cell program is the cell instructions in their
+// recorded order, each root operand replaced by ONE table load (FF_OP_TABLE, a = the root's value index until ff_make_function knows the
+// tables' offsets). Nothing else changes: the same operations on the same operands.
+struct FfPlan {
+    int cls[BF_MAX_INS];
+    bool root[BF_MAX_INS];
+    int n_cell;
+    ocn_expr_ins_t cell[BF_MAX_INS];
+};
+static void ff_make_plan(const ocn_expr_ins_t *program, int n, FfPlan *P) {
+    int mask[BF_MAX_INS];
+    for (int q = 0; q < n; ++q) {
+        const ocn_expr_ins_t &I = program[q];
+        const int operand[3] = {I.a, I.b, I.c};
+        mask[q] = I.op == OCN_EXPR_COORD ? 1 << I.a : (I.op == OCN_EXPR_FIELD ? 8 : 0);
+        for (int w = 0; w < expr_arity(I.op); ++w) mask[q] |= mask[operand[w]];
+        P->cls[q] = mask[q] == 0 ? FF_UNIFORM : (mask[q] == 1 ? FF_LINE : (mask[q] == 2 ? FF_LINE + 1 : (mask[q] == 4 ? FF_LINE + 2 : FF_CELL)));
+        P->root[q] = false;
+    }
+    int at[BF_MAX_INS], load[BF_MAX_INS];          // where a cell value / the load of a root sits in the per-cell program
+    for (int q = 0; q < n; ++q) at[q] = load[q] = -1;
+    int nc = 0;
+    auto table_load = [&](int v) {
+        if (load[v] < 0) {
+            P->root[v] = true;
+            load[v] = nc;
+            P->cell[nc++] = ocn_expr_ins_t{FF_OP_TABLE, v, P->cls[v] == FF_UNIFORM ? 3 : P->cls[v] - FF_LINE, 0, 0.0};
+        }
+        return load[v];
+    };
+    for (int q = 0; q < n; ++q) {
+        if (P->cls[q] != FF_CELL) continue;
+        ocn_expr_ins_t I = program[q];
+        int *operand[3] = {&I.a, &I.b, &I.c};
+        for (int w = 0; w < expr_arity(I.op); ++w) {
+            const int v = *operand[w];
+            *operand[w] = P->cls[v] == FF_CELL ? at[v] : table_load(v);
+        }
+        at[q] = nc;
+        P->cell[nc++] = I;
+    }
+    if (P->cls[n - 1] != FF_CELL) { nc = 0; load[n - 1] = -1; table_load(n - 1); }      // the result is a line or uniform value: one load per cell
+    P->n_cell = nc;
+}
+
+extern "C" int ocn_forcing_function_plan(const ocn_expr_ins_t *program, int n, int ndeps, int *value_class, int *n_cell) {
+    int rc = bf_validate_program(program, n, ndeps, nullptr, 2);
+    if (rc) return rc;
+    FfPlan P;
+    ff_make_plan(program, n, &P);
+    if (value_class) for (int q = 0; q < n; ++q) value_class[q] = P.cls[q];
+    if (n_cell) *n_cell = P.n_cell;
+    return OCN_OK;
+}
+
+// the function of a forcing of a field at `loc`: the plan, the coordinate tables, the stencils of its dependencies (dep_field[s]: slot of
+// BfFields, at dep_locs[s]), a copy of the validated program and the device block of its root tables (the caller owns fn->tab)
+static int ff_make_function(const ocn_grid_s *grid, const ocn_expr_ins_t *program, int n, const int loc[3], const int *dep_field,
+                            const int (*dep_locs)[3], int ndeps, FfFunction *fn) {
+    const DGrid &g = grid->d;
+    const int H[3] = {g.Hx, g.Hy, g.Hz}, T[3] = {g.tx, g.ty, g.tz};
+    int rc = no_connected_topology(g, "forcing functions");
+    if (rc) return rc;
+    if (!grid->node_tables) return fail(OCN_ESTATE, "the grid has no node tables: call ocn_grid_set_node_tables");
+    for (int q = 0; q < 3; ++q)
+        if (loc[q] != OCN_CENTER && loc[q] != OCN_FACE) return fail(OCN_EINVAL, "loc[%d] is OCN_CENTER or OCN_FACE", q);
+    *fn = FfFunction{};
+    fn->n = n; fn->ndeps = ndeps;
+    for (int q = 0; q < n; ++q) {
+        if (program[q].op == OCN_EXPR_COORD && T[program[q].a] == OCN_FLAT)
+            return fail(OCN_EINVAL, "instruction %d: a coordinate along %c, which is Flat (the function takes the remaining coordinates only)", q, "xyz"[program[q].a]);
+        fn->reads_time |= program[q].op == OCN_EXPR_TIME;
+    }
+    dg_interior_size(g, loc, fn->L);
+    for (int d = 0; d < 3; ++d) fn->x[d] = loc[d] == OCN_FACE ? grid->nodes_f[d] : grid->nodes_c[d];
+    for (int s = 0; s < ndeps; ++s) {
+        const int *from = dep_locs[s];
+        for (int q = 0; q < 3; ++q)
+            if (from[q] != OCN_CENTER && from[q] != OCN_FACE) return fail(OCN_EINVAL, "dependency %d: loc[%d] is OCN_CENTER or OCN_FACE", s, q);
+        int P[3];
+        parent_size(g, from, P);
+        const long st[3] = {1L, (long)P[0], (long)P[0] * P[1]};
+        FfDep &D = fn->dep[s];
+        D.field = dep_field[s];
+        D.off = H[0] + st[1] * H[1] + st[2] * H[2];                        // interior point (1, 1, 1)
+        D.s1 = st[1]; D.s2 = st[2];
+        for (int q = 0; q < 3; ++q) {
+            if (T[q] == OCN_FLAT || from[q] == loc[q]) continue;          // identity (interpolation_operators.jl:87-110)
+            if (loc[q] == OCN_FACE) D.off -= st[q];                       // ℑᶠ: f[i-1], f[i]; ℑᶜ: f[i], f[i+1]
+            D.st[D.n++] = st[q];                                          // the lower direction innermost (:45-71)
+        }
+    }
+    memcpy(fn->ins, program, sizeof(ocn_expr_ins_t) * (size_t)n);
+    FfPlan P;
+    ff_make_plan(program, n, &P);
+    long words = 0;
+    for (int q = 0; q < n; ++q) {
+        fn->cls[q] = (signed char)P.cls[q];
+        fn->root[q] = -1;
+        if (!P.root[q]) continue;
+        fn->root[q] = (int)words;
+        words += P.cls[q] == FF_UNIFORM ? 1 : fn->L[P.cls[q] - FF_LINE];
+    }
+    fn->n_cell = P.n_cell;
+    for (int q = 0; q < P.n_cell; ++q) {
+        fn->cell[q] = P.cell[q];
+        if (P.cell[q].op == FF_OP_TABLE) fn->cell[q].a = fn->root[P.cell[q].a];
+    }
+    HIP_TRY(dev_alloc((void **)&fn->tab, sizeof(double) * (size_t)std::max(words, 1L)));
+    return OCN_OK;
+}
+
+// the tables of functions [0, n) of `table_d` (time_only: of those that read t); Lmax: the longest line among them
+static void ff_launch_lines(const FfTable *table_d, int n, int Lmax, double time, bool time_only) {
+    hipLaunchKernelGGL(forcing_line_kernel, dim3((Lmax + FF_THREADS - 1) / FF_THREADS, 4, n), dim3(FF_THREADS), 0, g_stream, table_d, time,
+                       time_only ? 1 : 0);
+}
+// whether a program holds none of exp, log, sin, cos, tanh, pow: its cells can take the arithmetic-only instantiation
+static bool ff_arithmetic_only(const ocn_expr_ins_t *program, int n) {
+    for (int q = 0; q < n; ++q)
+        if (program[q].op >= OCN_EXPR_EXP && program[q].op <= OCN_EXPR_POW) return false;
+    return true;
+}
+static void ff_launch_cells(const DGrid &g, const ForcingTable *tab_d, const FfTable *table_d, const ForcingLaunch &L, const BfFields &fields, int nx,
+                            int ny, int nz, int slots, double time, bool hoist, bool assign, bool arithmetic) {
+    hipLaunchKernelGGL(arithmetic ? forcing_function_kernel<true> : forcing_function_kernel<false>, dim3((nx + FF_LANES - 1) / FF_LANES, (ny + FF_ROWS - 1) / FF_ROWS, nz * L.n), dim3(FF_LANES, FF_ROWS),
+                       sizeof(double) * FF_THREADS * (size_t)std::max(slots, 1), g_stream, g, tab_d, table_d, L, fields, nz, time, hoist ? 1 : 0,
+                       assign ? 1 : 0);
+}
+
+extern "C" int ocn_evaluate_forcing_function(ocn_grid_t grid, const ocn_expr_ins_t *program, int n, const int loc[3], const double *const *deps,
+                                             const int (*dep_locs)[3], int ndeps, double time, int hoist, double *out) {
+    NEED_INIT();
+    if (!grid || !loc || !out) return fail(OCN_EINVAL, "NULL argument");
+    int rc = bf_validate_program(program, n, ndeps, nullptr, 2);
+    if (rc) return rc;
+    if (ndeps > 0 && (!deps || !dep_locs)) return fail(OCN_EINVAL, "NULL dependencies");
+    BfFields fields = {};
+    int slots[BF_MAX_DEPS];
+    for (int s = 0; s < ndeps; ++s) {
+        if (!deps[s]) return fail(OCN_EINVAL, "dependency %d is NULL", s);
+        fields.p[s] = deps[s];
+        slots[s] = s;
+    }
+    // one field (slot 0) with one function term over the interior of `loc`: the tables of a model, made for this call
+    auto ft = std::make_unique<FfTable>();
+    auto tab = std::make_unique<ForcingTable>();
+    *ft = FfTable{}; *tab = ForcingTable{};
+    FfFunction &fn = ft->fn[0];
+    if ((rc = ff_make_function(grid, program, n, loc, slots, dep_locs, ndeps, &fn))) return rc;
+    ft->n = 1;
+    memset(ft->fn_of, -1, sizeof(ft->fn_of));
+    ft->fn_of[0][0] = 0;
+    tab->nterms[0] = 1;
+    tab->t[0][0].kind = OCN_FORCING_KIND_FUNCTION;
+    tab->r[0] = Range6{1, fn.L[0], 1, fn.L[1], 1, fn.L[2]};
+    const FView v = make_view(grid->d, nullptr, loc);
+    tab->s1[0] = v.s1; tab->s2[0] = v.s2; tab->off[0] = v.off;
+    ForcingLaunch L = {};
+    L.n = 1; L.f[0] = 0; L.U[0] = out; L.G[0] = out;
+    FfTable *ft_d = nullptr;
+    ForcingTable *tab_d = nullptr;
+    hipError_t e = dev_alloc((void **)&ft_d, sizeof(FfTable));
+    if (e == hipSuccess) e = dev_alloc((void **)&tab_d, sizeof(ForcingTable));
+    if (e == hipSuccess) e = hipMemcpy(ft_d, ft.get(), sizeof(FfTable), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(tab_d, tab.get(), sizeof(ForcingTable), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (hoist) ff_launch_lines(ft_d, 1, std::max(fn.L[0], std::max(fn.L[1], fn.L[2])), time, false);
+        ff_launch_cells(grid->d, tab_d, ft_d, L, fields, fn.L[0], fn.L[1], fn.L[2], hoist ? fn.n_cell : fn.n, time, hoist != 0, true,
+                        hoist ? ff_arithmetic_only(fn.cell, fn.n_cell) : ff_arithmetic_only(fn.ins, fn.n));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(g_stream);          // the tables are this call's
+    hipFree(ft_d); hipFree(tab_d); hipFree(fn.tab);
+    if (e != hipSuccess) return fail((int)e, "forcing_function_kernel: %s", hipGetErrorString(e));
     return OCN_OK;
 }
 
@@ -1784,6 +1983,16 @@ struct ocn_model_s {
     ForcingTable forcing_h = {};
     ForcingTable *forcing_d = nullptr;
     double *forcing_tables[OCN_MAX_FIELDS][OCN_MAX_FORCING_TERMS][2] = {};
+    // OCN_FORCING_FUNCTION terms (ocn_forcing_function.h): the host copy of their table (it owns every FfFunction::tab), the device-resident
+    // one, whether some program reads t, the longest per-cell program and line
+    struct ForcingFunctions {
+        FfTable h = {};
+        FfTable *d = nullptr;
+        bool reads_time = false;
+        bool hoist = true;              // model option "forcing_function_hoist": tables + per-cell programs (0: the recorded programs per cell)
+        int cell_max = 0, ins_max = 0, Lmax = 1;
+        bool cell_arith = true, ins_arith = true;       // no per-cell / recorded program holds exp .. pow: the arithmetic-only kernel serves
+    } ff;
     double *pHY = nullptr;                  // hydrostatic pressure anomaly (only with buoyancy)
     // background_fields = (u = Ū, b = B̄, ...) (background_fields.jl): borrowed haloed arrays at their field's location (NULL: ZeroField),
     // and the total velocities U + Ū update_state! forms for the components that have one (owned; allocated by the setter)
@@ -1816,6 +2025,8 @@ extern "C" int ocn_model_destroy(ocn_model_t m) {
     for (int q = 0; q < m->particles.ntracked; ++q) hipFree(m->particles.tracked[q].values);
     for (int c = 0; c < 3; ++c) hipFree(m->tot[c]);
     hipFree(m->forcing_d);
+    for (int q = 0; q < m->ff.h.n; ++q) hipFree(m->ff.h.fn[q].tab);
+    hipFree(m->ff.d);
     for (auto &f : m->forcing_tables)
         for (auto &t : f) { hipFree(t[0]); hipFree(t[1]); }
     hipFree(m->nu_e);
@@ -2030,6 +2241,11 @@ extern "C" int ocn_model_set_option(ocn_model_t m, const char *key, int value) {
     if (!m || !key) return fail(OCN_EINVAL, "NULL argument");
     m->epoch += 1;
     if (!strcmp(key, "profile")) { m->profile = value; m->events_used = 0; return OCN_OK; }
+    if (!strcmp(key, "forcing_function_hoist")) {          // a model's own switch, like "profile": not a tuning option of the table
+        if (value != 0 && value != 1) return fail(OCN_EINVAL, "forcing_function_hoist is 0 or 1");
+        m->ff.hoist = value != 0;
+        return OCN_OK;
+    }
     const OptionRow *r = option_row(key, value);
     if (!r) return OCN_EINVAL;
     if (r->scope == OPT_CREATION)
@@ -2131,7 +2347,7 @@ static StepPlan plan(const ocn_model_s *m) {
     const bool forcing = has_forcing(m), background = has_background(m);
     const bool forcing_in_role = forcing && !background && o.fused_forcing && !m->dm && !p.physics && !flux && !p.epilogue && o.tendency_impl == 2 &&
                                  o.arithmetic == 0 && g.tz == OCN_PERIODIC && fused_path(o, g, nullptr, m->ntr, 2) && role_tendency_supported(o, g);
-    p.forcing_path = forcing ? (forcing_in_role ? 1 : 3) : 0;
+    p.forcing_path = forcing ? ((forcing_in_role && m->ff.h.n == 0) ? 1 : 3) : 0;      // a function term: always the standalone passes
     p.background_path = !background ? 0 : (split_role_path(o, g, o.tendency_impl) ? 2 : 1);
     // without extra physics the substep rides in the fused advection kernel; with Coriolis / buoyancy / closure terms it rides in
     // the epilogue pass that completes the tendencies (any advection path); a valued Flux condition is added after both
@@ -2147,19 +2363,38 @@ static bool has_physics(const ocn_model_s *m) { return plan(m).physics; }
 
 // G = G_rest + F of every forced field (ocn_forcing.h), one launch after the tendency evaluation is complete (advection, physics
 // epilogue) and before the Flux-condition terms (compute_flux_bc_tendencies, which the steppers call when the next stage begins)
+static bool has_function_term(const ocn_model_s *m, int f) {
+    for (int q = 0; q < m->forcing_h.nterms[f]; ++q)
+        if (m->forcing_h.t[f][q].kind == OCN_FORCING_KIND_FUNCTION) return true;
+    return false;
+}
+// Fields with a function term (ocn_forcing_function.h) go to forcing_function_kernel, all their terms in sum order, with m->U, their halos
+// and the clock of this tendency evaluation; the tables of programs that read t are refilled first. The other fields stay with
+// add_forcing_kernel.
 static int add_forcing(ocn_model_s *m) {
-    ForcingLaunch L = {};
-    int nx = 0, ny = 0, nz = 0;
-    for (int f = 0; f < m->nf; ++f) {
-        if (m->forcing_h.nterms[f] <= 0) continue;
-        const Range6 &r = m->forcing_h.r[f];
-        if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) continue;
-        L.f[L.n] = f; L.U[L.n] = m->U[f]; L.G[L.n] = m->Gn[f]; ++L.n;
-        nx = std::max(nx, r.i1 - r.i0 + 1); ny = std::max(ny, r.j1 - r.j0 + 1); nz = std::max(nz, r.k1 - r.k0 + 1);
+    for (int functions = 0; functions < 2; ++functions) {
+        ForcingLaunch L = {};
+        int nx = 0, ny = 0, nz = 0;
+        for (int f = 0; f < m->nf; ++f) {
+            if (m->forcing_h.nterms[f] <= 0 || has_function_term(m, f) != (functions == 1)) continue;
+            const Range6 &r = m->forcing_h.r[f];
+            if (r.i1 < r.i0 || r.j1 < r.j0 || r.k1 < r.k0) continue;
+            L.f[L.n] = f; L.U[L.n] = m->U[f]; L.G[L.n] = m->Gn[f]; ++L.n;
+            nx = std::max(nx, r.i1 - r.i0 + 1); ny = std::max(ny, r.j1 - r.j0 + 1); nz = std::max(nz, r.k1 - r.k0 + 1);
+        }
+        if (L.n == 0) continue;
+        if (!functions) {
+            hipLaunchKernelGGL(add_forcing_kernel, grid3(nx, ny, nz * L.n, BLK), BLK, 0, g_stream, m->grid->d, (const ForcingTable *)m->forcing_d, L, nz);
+        } else {
+            const bool hoist = m->ff.hoist;
+            BfFields fields = {};
+            for (int f = 0; f < m->nf; ++f) fields.p[f] = m->U[f];
+            if (hoist && m->ff.reads_time) ff_launch_lines(m->ff.d, m->ff.h.n, m->ff.Lmax, m->time, true);
+            ff_launch_cells(m->grid->d, m->forcing_d, m->ff.d, L, fields, nx, ny, nz, hoist ? m->ff.cell_max : m->ff.ins_max, m->time, hoist, false,
+                            hoist ? m->ff.cell_arith : m->ff.ins_arith);
+        }
+        KERNEL_CHECK();
     }
-    if (L.n == 0) return OCN_OK;
-    hipLaunchKernelGGL(add_forcing_kernel, grid3(nx, ny, nz * L.n, BLK), BLK, 0, g_stream, m->grid->d, (const ForcingTable *)m->forcing_d, L, nz);
-    KERNEL_CHECK();
     return OCN_OK;
 }
 
@@ -2341,6 +2576,14 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     if (!strcmp(key, "boundary_functions")) { *value = m->bf.n; return OCN_OK; }
     if (!strcmp(key, "boundary_function_launches")) { *value = m->bf.n ? 1 : 0; return OCN_OK; }
     if (!strcmp(key, "boundary_functions_read_time")) { *value = m->bf.reads_time ? 1 : 0; return OCN_OK; }
+    // function-valued forcing terms: their number, the longest per-cell program (the recorded ones with forcing_function_hoist = 0), whether a
+    // program reads t
+    if (!strcmp(key, "forcing_functions")) { *value = m->ff.h.n; return OCN_OK; }
+    if (!strcmp(key, "forcing_function_cell_instructions")) { *value = m->ff.hoist ? m->ff.cell_max : m->ff.ins_max; return OCN_OK; }
+    if (!strcmp(key, "forcing_function_hoist")) { *value = m->ff.hoist ? 1 : 0; return OCN_OK; }
+    // which instantiation of forcing_function_kernel runs: 1 the arithmetic-only one (no exp .. pow per cell), 0 the full one
+    if (!strcmp(key, "forcing_function_arithmetic_only")) { *value = m->ff.h.n > 0 && (m->ff.hoist ? m->ff.cell_arith : m->ff.ins_arith) ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "forcing_functions_read_time")) { *value = m->ff.reads_time ? 1 : 0; return OCN_OK; }
     // which epilogue adds the closure terms: the z-marching one (1) or the per-value one (0) -- the explicit part of a vertically implicit
     // discretisation exists in the per-value epilogue only
     if (!strcmp(key, "epilogue_march_active")) { *value = p.march ? 1 : 0; return OCN_OK; }
@@ -3092,11 +3335,36 @@ extern "C" int ocn_model_set_forcing(ocn_model_t m, int field, const ocn_forcing
                 if (dirs[w] >= 0 && T[dirs[w]] == OCN_FLAT)
                     return fail(OCN_EINVAL, "term %d: a %s along %c, which is Flat (relaxation.jl has no method for it)", q, w ? "target" : "mask", "xyz"[dirs[w]]);
             }
+        } else if (t.kind == OCN_FORCING_FUNCTION) {
+            if (m->dm) return fail(OCN_ENOTSUP, "term %d: forcing functions are not served on a partitioned model", q);
+            const int rc = bf_validate_program(t.program, t.n, t.ndeps, nullptr, 2);
+            if (rc) return rc;
+            if (t.ndeps > 0 && !t.dep_names) return fail(OCN_EINVAL, "term %d: NULL dependency names", q);
         } else return fail(OCN_EINVAL, "term %d: unknown forcing kind %d", q, t.kind);
+    }
+    // function terms (ocn_forcing_function.h): built, their tables allocated, before anything of the previous forcing changes
+    FfFunction made[OCN_MAX_FORCING_TERMS];
+    int nmade = 0, kept = 0;
+    auto release_made = [&]() { for (int q = 0; q < nmade; ++q) hipFree(made[q].tab); };
+    for (int q = 0; q < m->ff.h.n; ++q) kept += m->ff.h.fn[q].field != field ? 1 : 0;
+    for (int q = 0; q < nterms; ++q) {
+        const ocn_forcing_t &t = terms[q];
+        if (t.kind != OCN_FORCING_FUNCTION) continue;
+        if (kept + nmade == FF_MAX_FUNCTIONS) { release_made(); return fail(OCN_EINVAL, "a model carries at most %d forcing functions", FF_MAX_FUNCTIONS); }
+        int dep_field[BF_MAX_DEPS], dep_locs[BF_MAX_DEPS][3], rc = OCN_OK;
+        for (int s = 0; s < t.ndeps && !rc; ++s) {
+            dep_field[s] = t.dep_names[s] ? field_index(m, t.dep_names[s]) : -1;
+            if (dep_field[s] < 0) rc = fail(OCN_EINVAL, "name %s not found in model.velocities or model.tracers.", t.dep_names[s] ? t.dep_names[s] : "(NULL)");
+            else memcpy(dep_locs[s], m->loc[dep_field[s]], sizeof(int) * 3);
+        }
+        if (!rc) rc = ff_make_function(m->grid, t.program, t.n, m->loc[field], dep_field, dep_locs, t.ndeps, &made[nmade]);
+        if (rc) { release_made(); return rc; }
+        made[nmade].field = field; made[nmade].term = q;
+        ++nmade;
     }
     // device copies of the tables first: nothing of the previous forcing is released before the new one is complete
     double *dev[OCN_MAX_FORCING_TERMS][2] = {};
-    auto release = [&]() { for (auto &d : dev) { hipFree(d[0]); hipFree(d[1]); } };
+    auto release = [&]() { for (auto &d : dev) { hipFree(d[0]); hipFree(d[1]); } release_made(); };
     for (int q = 0; q < nterms; ++q)
         for (int w = 0; w < 2; ++w) {
             const int dir = w ? terms[q].target_dir : terms[q].mask_dir;
@@ -3121,7 +3389,7 @@ extern "C" int ocn_model_set_forcing(ocn_model_t m, int field, const ocn_forcing
         d = ForcingTerm{};
         if (q >= nterms) continue;
         const ocn_forcing_t &t = terms[q];
-        d.kind = t.kind;
+        d.kind = t.kind;                                    // OCN_FORCING_FUNCTION: the function is FfTable::fn_of[field][q]
         d.array = t.kind == OCN_FORCING_ARRAY ? t.array : nullptr;
         d.mask_dir = t.kind == OCN_FORCING_RELAXATION ? t.mask_dir : -1;
         d.target_dir = t.kind == OCN_FORCING_RELAXATION ? t.target_dir : -1;
@@ -3135,17 +3403,47 @@ extern "C" int ocn_model_set_forcing(ocn_model_t m, int field, const ocn_forcing
     }
     const FView a = make_view(g, nullptr, LOC_C);
     h.as1 = a.s1; h.as2 = a.s2; h.aoff = a.off;
-    e = hipMemcpy(m->forcing_d, &h, sizeof(ForcingTable), hipMemcpyHostToDevice);
+    // the functions of the other fields stay, this field's are replaced by the new ones; fn_of follows
+    auto nf = std::make_unique<FfTable>();
+    *nf = FfTable{};
+    for (int q = 0; q < m->ff.h.n; ++q)
+        if (m->ff.h.fn[q].field != field) nf->fn[nf->n++] = m->ff.h.fn[q];
+    for (int q = 0; q < nmade; ++q) nf->fn[nf->n++] = made[q];
+    memset(nf->fn_of, -1, sizeof(nf->fn_of));
+    for (int q = 0; q < nf->n; ++q) nf->fn_of[nf->fn[q].field][nf->fn[q].term] = (signed char)q;
+    if (nf->n > 0 && !m->ff.d) {
+        e = dev_alloc((void **)&m->ff.d, sizeof(FfTable));
+        if (e != hipSuccess) { m->ff.d = nullptr; release(); return fail((int)e, "dev_alloc(forcing function table): %s", hipGetErrorString(e)); }
+    }
+    if (m->ff.d) e = hipMemcpy(m->ff.d, nf.get(), sizeof(FfTable), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m->forcing_d, &h, sizeof(ForcingTable), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        // the device copy may be partial: try to restore the previous table (whose tables are still allocated) before reporting
+        // the device copies may be partial: try to restore the previous tables (whose tables are still allocated) before reporting
         (void)hipMemcpy(m->forcing_d, &m->forcing_h, sizeof(ForcingTable), hipMemcpyHostToDevice);
+        if (m->ff.d) (void)hipMemcpy(m->ff.d, &m->ff.h, sizeof(FfTable), hipMemcpyHostToDevice);
         release();
         return fail((int)e, "forcing table: %s", hipGetErrorString(e));
     }
     m->forcing_h = h;
+    for (int q = 0; q < m->ff.h.n; ++q)
+        if (m->ff.h.fn[q].field == field) hipFree(m->ff.h.fn[q].tab);
+    m->ff.h = *nf;
+    m->ff.reads_time = false; m->ff.cell_max = m->ff.ins_max = 0; m->ff.Lmax = 1; m->ff.cell_arith = m->ff.ins_arith = true;
+    for (int q = 0; q < nf->n; ++q) {
+        const FfFunction &fn = nf->fn[q];
+        m->ff.reads_time = m->ff.reads_time || fn.reads_time;
+        m->ff.cell_arith = m->ff.cell_arith && ff_arithmetic_only(fn.cell, fn.n_cell); m->ff.ins_arith = m->ff.ins_arith && ff_arithmetic_only(fn.ins, fn.n);
+        m->ff.cell_max = std::max(m->ff.cell_max, fn.n_cell); m->ff.ins_max = std::max(m->ff.ins_max, fn.n);
+        m->ff.Lmax = std::max(m->ff.Lmax, std::max(fn.L[0], std::max(fn.L[1], fn.L[2])));
+    }
     for (int q = 0; q < OCN_MAX_FORCING_TERMS; ++q)
         for (int w = 0; w < 2; ++w) { hipFree(m->forcing_tables[field][q][w]); m->forcing_tables[field][q][w] = dev[q][w]; }
     m->epoch += 1;                  // a captured time-step graph launches other kernels now
+    // the tables of the new functions, once everything above is settled: those of programs that do not read t are filled here and never again
+    if (nmade > 0) {
+        ff_launch_lines(m->ff.d, m->ff.h.n, m->ff.Lmax, m->time, false);
+        KERNEL_CHECK();
+    }
     return OCN_OK;
 }
 
@@ -3484,8 +3782,9 @@ extern "C" int ocn_model_time_step(ocn_model_t m, double dt) {
         return rc;
     }
     // ... and not with a scheme side: the boundary step takes last_stage_Δt, whose corrected third-stage value changes from step to step
-    // ... nor with a boundary function that reads t: the time is an argument of its launch
-    if (!m->opt.use_graph || m->profile || m->iteration == 0 || !g_stream_owned || m->n_scheme || m->bf.reads_time) return rk3_time_step(m, dt);
+    // ... nor with a boundary function or a forcing function that reads t: the time is an argument of its launch
+    if (!m->opt.use_graph || m->profile || m->iteration == 0 || !g_stream_owned || m->n_scheme || m->bf.reads_time || m->ff.reads_time)
+        return rk3_time_step(m, dt);
     if (m->graph_exec && m->graph_dt == dt && m->graph_epoch == m->epoch * 1000003ull + g_epoch) {
         hipError_t e = hipGraphLaunch(m->graph_exec, g_stream);
         if (e != hipSuccess) return fail((int)e, "hipGraphLaunch: %s", hipGetErrorString(e));

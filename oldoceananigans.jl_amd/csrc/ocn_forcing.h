@@ -1,16 +1,19 @@
 // ocn_forcing.h -- the forcing term of the tendencies: `+ forcing(i, j, k, grid, clock, model_fields)`, the last term of
 // u_velocity_tendency and its v / w / tracer siblings (Models/NonhydrostaticModels/nonhydrostatic_tendency_kernel_functions.jl:81-93).
 //
-// Closure-free forcings of src/Forcings/ only (a Julia closure cannot cross the C ABI):
+// The forcings of src/Forcings/ that cross the C ABI:
 //   Forcing(array)       F = array[i, j, k]                                  (forcing.jl:165-177, model_forcing.jl:29)
 //   Relaxation           F = rate * mask(x, y, z) * (target(x, y, z, t) - φ)  (relaxation.jl:75-90)
+//   a function           F = program(x, y, z, t, deps...), a recorded program  (continuous_forcing.jl:119-142; ocn_forcing_function.h)
 //   MultipleForcings     F = F₁ + F₂ + ...                                    (multiple_forcings.jl)
-// Every mask and target of relaxation.jl depends on ONE coordinate and not on time, so the host evaluates `rate * mask(node)` and
-// `target(node)` at the forced field's own location over the haloed index range of that direction (a binder does it with the
-// reference's own functions, `exp` included) and the device does only the `*` and `-` the reference does per cell:
+// The built-in masks and targets of relaxation.jl (GaussianMask, PiecewiseLinearMask, LinearTarget) depend on ONE coordinate and not on
+// time, so the host evaluates `rate * mask(node)` and `target(node)` at the forced field's own location over the haloed index range of
+// that direction (a binder does it with the reference's own functions, `exp` included) and the device does only the `*` and `-` the
+// reference does per cell:
 //   F = (rate·mask)[ξ_m] * (target[ξ_t] - φ)
 // with the zero target as `0.0 - φ` (Julia's `0 - φ`: φ = +0.0 gives +0.0, not -0.0) and the constant mask as the bare rate
-// (`rate * 1` is the rate).
+// (`rate * 1` is the rate). A Relaxation whose mask or target is any other function is one function term (kind 3): this header's
+// kernels never see it -- a field that has one is completed by forcing_function_kernel, which calls forcing_one for its other terms.
 //
 // Association order of a sum: N <= 4 terms are the explicit left-to-right sums of multiple_forcings.jl (F₁ + F₂ + F₃ + F₄); N > 4
 // is its generated loop `total = zero(grid); total += Fₙ`, i.e. ((0.0 + F₁) + F₂) + ... The tendency is completed as

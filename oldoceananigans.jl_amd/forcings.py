@@ -2,8 +2,13 @@
 PiecewiseLinearMask / LinearTarget, Forcing(array) and MultipleForcings -- and `model_forcing`, which regularises the `forcing = (...)`
 of the model constructor into the per-field term descriptors of ocn_model_set_forcing (include/ocn_mi355x.h).
 
-Masks and targets depend on one coordinate and not on time, so they are evaluated HERE, on the host, at the forced field's own nodes
-(the grid's node arrays with halos, `xᶠᵃᵃ / xᶜᵃᵃ / ...`); the device does the `*` and `-` of relaxation.jl per cell (ocn_forcing.h)."""
+The built-in masks and targets depend on one coordinate and not on time, so they are evaluated HERE, on the host, at the forced field's own
+nodes (the grid's node arrays with halos, `xᶠᵃᵃ / xᶜᵃᵃ / ...`); the device does the `*` and `-` of relaxation.jl per cell (ocn_forcing.h).
+
+A `mask(x, y, z)` or `target(x, y, z, t)` that is a function of the user's makes the whole relaxation ONE recorded program
+(boundary_functions.py), `rate * mask(X...) * (target(X..., t) - φ)`, evaluated on the device at every cell (ocn_forcing_function.h):
+
+    sponge = Relaxation(rate=1 / 60, mask=lambda x, y, z: ocn.max_(west(x), bottom(z)), target=lambda x, y, z, t: T0 + A * ocn.sin(ω * t))"""
 import ctypes as C
 
 import numpy as np
@@ -248,15 +253,77 @@ def _node_table(grid, loc, D, fn, what):
 
 
 class Term:
-    """one ocn_forcing_t: kind 1 (array) or 2 (relaxation), with the host tables it points to"""
+    """one ocn_forcing_t: kind 1 (array), 2 (relaxation) with the host tables it points to, or 3 (function) with its recorded program
+    and the model fields of its dependency slots"""
 
-    def __init__(self, kind, array=None, mask_dir=-1, mask_table=None, rate_mask=0.0, target_dir=-1, target_table=None, target=0.0):
+    def __init__(self, kind, array=None, mask_dir=-1, mask_table=None, rate_mask=0.0, target_dir=-1, target_table=None, target=0.0,
+                 program=None, dep_names=()):
         self.kind, self.array = kind, array
         self.mask_dir, self.mask_table, self.rate_mask = mask_dir, mask_table, float(rate_mask)
         self.target_dir, self.target_table, self.target = target_dir, target_table, float(target)
+        self.program, self.dep_names = program, tuple(dep_names)
 
 
-def _relaxation_term(r, grid, loc):
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+def _is_function(f):
+    """a mask or target that is the user's own function: recorded, not tabulated"""
+    return (callable(f) and not isinstance(f, type) and f is not onefunction and f is not zerofunction
+            and not isinstance(f, (GaussianMask, PiecewiseLinearMask, LinearTarget)))
+
+
+def _recorded_builtin(f, coordinate, what):
+    """a built-in mask or target next to a function: its reference formula (relaxation.jl), recorded on the symbol of its coordinate"""
+    from . import boundary_functions as bf
+    if f.D not in coordinate:
+        raise ValueError(f"a {what} along {f.D}, which is Flat: the reference has no method for it (relaxation.jl Flat methods take the "
+                         "remaining coordinates only)")
+    xi = coordinate[f.D]
+    if isinstance(f, GaussianMask):
+        return bf.exp(-(xi - f.center) ** 2 / (2 * (f.width * f.width)))
+    if isinstance(f, PiecewiseLinearMask):
+        return bf.max_(0.0, 1.0 - abs(xi - f.center) / f.width)
+    return f.intercept + f.gradient * xi
+
+
+def _function_relaxation_term(r, grid, loc, name):
+    """Relaxation with a function mask or target: rate * mask(X...) * (target(X..., t) - φ) as the reference evaluates it
+    (relaxation.jl:80-101), recorded once. X: the nodes of the forced field's location, Flat directions dropped; φ: dependency slot 0"""
+    from .boundary_functions import trace
+    dims = [d for d in range(3) if grid.topology[d] is not Flat]
+
+    def known(f, what):
+        if not (_is_function(f) or isinstance(f, (GaussianMask, PiecewiseLinearMask, LinearTarget))):
+            raise _unsupported(f)
+        return f
+
+    def relaxation(*args):
+        X, t, phi = args[:len(dims)], args[len(dims)], args[len(dims) + 1]
+        coordinate = {_DIRS[d]: x for d, x in zip(dims, X)}
+        if r.mask is onefunction:
+            a = r.rate                                                  # rate * 1
+        elif _is_function(r.mask):
+            a = r.rate * r.mask(*X)
+        else:
+            a = r.rate * _recorded_builtin(known(r.mask, "mask"), coordinate, "mask")
+        if r.target is zerofunction:
+            b = 0.0                                                     # `0 - φ`
+        elif _is_number(r.target):
+            b = float(r.target)
+        elif _is_function(r.target):
+            b = r.target(*X, t)
+        else:
+            b = _recorded_builtin(known(r.target, "target"), coordinate, "target")
+        return a * (b - phi)
+
+    return Term(3, program=trace(relaxation, dims, 1), dep_names=(name,))
+
+
+def _relaxation_term(r, grid, loc, name=None):
+    if _is_function(r.mask) or _is_function(r.target):
+        return _function_relaxation_term(r, grid, loc, name)
     if r.mask is onefunction:
         mask_dir, mask_table, rate_mask = -1, None, r.rate             # rate * 1
     elif isinstance(r.mask, (GaussianMask, PiecewiseLinearMask)):
@@ -291,8 +358,9 @@ def _array_term(a, grid):
     return Term(1, array=np.asarray(a, dtype=np.float64))
 
 
-def regularize_forcing(f, grid, loc):
-    """regularize_forcing (model_forcing.jl, multiple_forcings.jl): a forcing -> list of Terms, in summation order"""
+def regularize_forcing(f, grid, loc, name=None):
+    """regularize_forcing (model_forcing.jl, multiple_forcings.jl): a forcing -> list of Terms, in summation order; `name`: the forced
+    field, the dependency of a recorded relaxation"""
     from .fields import Field
     if isinstance(f, MultipleForcings):
         f = f.forcings
@@ -301,10 +369,10 @@ def regularize_forcing(f, grid, loc):
         for g in f:
             if isinstance(g, (tuple, list, MultipleForcings)):
                 raise _unsupported(g)             # the reference sums a flat tuple; a nested one is not a forcing
-            terms += regularize_forcing(g, grid, loc)
+            terms += regularize_forcing(g, grid, loc, name)
         return terms
     if isinstance(f, Relaxation):
-        return [_relaxation_term(f, grid, loc)]
+        return [_relaxation_term(f, grid, loc, name)]
     if isinstance(f, ArrayForcing):
         return [_array_term(f.array, grid)]
     if isinstance(f, (np.ndarray, Field)):
@@ -322,18 +390,29 @@ def model_forcing(grid, field_locations, forcing):
                                       f"({', '.join(field_locations)})")
         if f is None:
             continue
-        terms = regularize_forcing(f, grid, field_locations[name])
+        terms = regularize_forcing(f, grid, field_locations[name], name)
         if len(terms) > _MAX_TERMS:
             raise ValueError(f"{len(terms)} forcing terms for {name}: at most {_MAX_TERMS}")
         out[name] = terms
+    functions = sum(t.kind == 3 for terms in out.values() for t in terms)
+    if functions > _MAX_FUNCTIONS:
+        raise ValueError(f"{functions} function-valued forcing terms: the limit of a model is {_MAX_FUNCTIONS} function terms")
     return out
 
 
 _MAX_TERMS = 8          # OCN_MAX_FORCING_TERMS
+_MAX_FUNCTIONS = 16     # function terms of one model (ocn_forcing_function.h)
 
 
-def set_forcing(handle, field_index, terms, grid, keep):
-    """ocn_model_set_forcing for one field. Arrays become device buffers (numpy: owned, appended to `keep`; Field: borrowed)."""
+def refuse_functions_on_partitions(terms_by_field, grid):
+    """function terms are served on one device. Raises NotImplementedError otherwise -- called before anything touches the device."""
+    if hasattr(grid, "local") and any(t.kind == 3 for terms in terms_by_field.values() for t in terms):
+        raise NotImplementedError("a Relaxation with a function mask or target is not served on partitioned grids")
+
+
+def set_forcing(handle, field_index, terms, grid, keep, cname=None):
+    """ocn_model_set_forcing for one field. Arrays become device buffers (numpy: owned, appended to `keep`; Field: borrowed). cname: model
+    field name -> the library's ("u", "v", "w", "c0" ..), for the dependencies of function terms"""
     from .fields import CenterField
     arr = (_lib.Forcing * max(1, len(terms)))()
     host = []
@@ -350,6 +429,12 @@ def set_forcing(handle, field_index, terms, grid, keep):
             else:
                 keep.append(fld)
             e.array = fld.data
+        if t.kind == 3:
+            from .boundary_functions import program_array
+            program, e.n = program_array(t.program)
+            names = (C.c_char_p * max(len(t.dep_names), 1))(*[(cname(d) if cname else d).encode() for d in t.dep_names])
+            host += [program, names]
+            e.program, e.dep_names, e.ndeps = C.cast(program, C.c_void_p), C.cast(names, C.c_void_p), len(t.dep_names)
         e.mask_dir, e.rate_mask, e.target_dir, e.target = t.mask_dir, t.rate_mask, t.target_dir, t.target
         if t.mask_table is not None:
             host.append(t.mask_table)
@@ -360,11 +445,29 @@ def set_forcing(handle, field_index, terms, grid, keep):
     _lib.check(_lib.lib().ocn_model_set_forcing(handle, int(field_index), arr, len(terms)))
 
 
-def evaluate(terms, grid, loc, phi):
-    """host twin of ocn_forcing.h's forcing_sum over the interior of `loc` (tests): φ is the field's interior array"""
+def node_coordinates(grid, loc):
+    """the node coordinates over the interior of `loc`, shaped to broadcast as (x, y, z); None along a Flat direction"""
+    n, H = grid.interior_size(loc), grid.halo_size
+    nodes = ((grid.xᶠᵃᵃ, grid.xᶜᵃᵃ), (grid.yᵃᶠᵃ, grid.yᵃᶜᵃ), (grid.zᵃᵃᶠ, grid.zᵃᵃᶜ))
+    out = []
+    for d in range(3):
+        if grid.topology[d] is Flat:
+            out.append(None)
+            continue
+        shape = [1, 1, 1]
+        shape[d] = n[d]
+        out.append(np.asarray(nodes[d][0] if loc[d] is Face else nodes[d][1], dtype=np.float64)[H[d]:H[d] + n[d]].reshape(shape))
+    return out
+
+
+def evaluate(terms, grid, loc, phi, t=0.0):
+    """host twin of ocn_forcing.h's forcing_sum over the interior of `loc` (tests): φ is the field's interior array, t the clock's time.
+    A function term is interpreted with numpy; its one dependency is φ (a recorded relaxation)"""
     from .fields import Field
     nx, ny, nz = grid.interior_size(loc)
     H = grid.halo_size
+
+    time = t
 
     def tab(t, d):
         sl = slice(H[d], H[d] + (nx, ny, nz)[d])
@@ -379,6 +482,9 @@ def evaluate(terms, grid, loc, phi):
             mx, my, mz = min(nx, a.shape[0]), min(ny, a.shape[1]), min(nz, a.shape[2])
             out[:mx, :my, :mz] = a[:mx, :my, :mz]
             return out
+        if t.kind == 3:
+            from .boundary_functions import interpret
+            return np.array(np.broadcast_to(interpret(t.program, node_coordinates(grid, loc), time, [phi] * len(t.dep_names)), (nx, ny, nz)))
         a = t.rate_mask if t.mask_dir < 0 else tab(t.mask_table, t.mask_dir)
         b = t.target if t.target_dir < 0 else tab(t.target_table, t.target_dir)
         return a * (b - phi)

@@ -102,6 +102,24 @@ def evaluate_boundary_function(grid, program, loc, side, deps, time, out=None):
             _lib.lib().ocn_free(dev)
 
 
+def evaluate_forcing_function(grid, program, loc, deps, time, hoist=True, out=None):
+    """a traced function of (X..., t, deps...) (boundary_functions.trace with coordinates x / y / z = 0 / 1 / 2) at every interior point of
+    a field at `loc`: what a function-valued forcing term adds. `deps` are Fields with current halos, one per dependency slot, each
+    interpolated from its own location to `loc`. Returns the host interior array; with `out`, a Field at `loc`, evaluates into its interior
+    and returns nothing -- Forcing(out) is borrowed, so this refreshes an arbitrary forcing between time-steps. hoist=False evaluates the
+    whole program at every cell (the bits are the same)."""
+    from .boundary_functions import program_array
+    from .fields import Field
+    deps = list(deps)
+    ptrs = _ptr_array(deps) if deps else None
+    locs = _loc_array(deps) if deps else None
+    arr, n = program_array(program)
+    field = out if out is not None else Field(loc, grid)
+    _lib.check(_lib.lib().ocn_evaluate_forcing_function(grid.handle, arr, n, _lib.i3(field.loc_codes), ptrs, locs, len(deps), float(time),
+                                                        int(bool(hoist)), field.data))
+    return None if out is not None else field.interior()
+
+
 def compute_tendencies_and_substep(grid, fields, Gn, next_fields, Gm, Δt, γ, ζ, kernel_parameters=None):
     """tendencies of all prognostic fields (u, v, w, tracers...) + the rk3_substep! of the next stage into `next_fields`"""
     _lib.check(_lib.lib().ocn_compute_tendencies_and_substep(

@@ -102,6 +102,7 @@ class NonhydrostaticModel:
         locations = {"u": (Face, Center, Center), "v": (Center, Face, Center), "w": (Center, Center, Face)}
         locations.update({t: (Center, Center, Center) for t in self.tracer_names})
         self._forcing_terms = _forcings.model_forcing(getattr(grid, "local", grid), locations, forcing)
+        _forcings.refuse_functions_on_partitions(self._forcing_terms, grid)
         self.forcing = dict(forcing or {})
         # background_fields = (u = U, b = B) (nonhydrostatic_model.jl:196-197): regularised on the host for the same reason
         from . import background_fields as _background
@@ -176,7 +177,7 @@ class NonhydrostaticModel:
         self._forcing_keep = []                          # device arrays of Forcing(array): owned (numpy) or borrowed (Field)
         for name, terms in self._forcing_terms.items():
             _forcings.set_forcing(self.handle, ("u", "v", "w").index(name) if name in ("u", "v", "w") else 3 + self.tracer_names.index(name),
-                                  terms, getattr(grid, "local", grid), self._forcing_keep)
+                                  terms, getattr(grid, "local", grid), self._forcing_keep, self._cname)
         # boundary_conditions = (u = FieldBoundaryConditions(top = FluxBoundaryCondition(Q)), ...) (nonhydrostatic_model.jl:
         # 163-190): constant Flux / Value / Gradient / Open conditions on Bounded sides
         self.boundary_conditions = dict(boundary_conditions or {})
