@@ -640,11 +640,12 @@ static int dist_make_pressure_correction(ocn_model_s *m, double dt, bool start_h
             return e == hipSuccess ? OCN_OK : fail((int)e, "pressure correction (partitioned slab): %s", hipGetErrorString(e));
         };
         if (!early) return pcz(1, g.Nx);
+        const unsigned sbx = (2 * g.Hx + 7) / 8;          // the two strips hold 2 Hx columns: one block of 8 up to Hx = 4
         if (!zf)
-            hipLaunchKernelGGL(pressure_correction_dense_strips_kernel, dim3(1, (g.Ny + 31) / 32, g.Nz), dim3(8, 32), 0, g_stream, g, vu, vv, vw, pd, pw, vp, dtp, g.Hx,
+            hipLaunchKernelGGL(pressure_correction_dense_strips_kernel, dim3(sbx, (g.Ny + 31) / 32, g.Nz), dim3(8, 32), 0, g_stream, g, vu, vv, vw, pd, pw, vp, dtp, g.Hx,
                                d.sj, d.sk, zb, keep_p);
         else
-            hipLaunchKernelGGL(pressure_correction_zfast_strips_kernel, dim3(1, (g.Ny + 31) / 32, g.Nz), dim3(8, 32), 0, g_stream, g, vu, vv, vw, pd, pw, vp, dtp, g.Hx);
+            hipLaunchKernelGGL(pressure_correction_zfast_strips_kernel, dim3(sbx, (g.Ny + 31) / 32, g.Nz), dim3(8, 32), 0, g_stream, g, vu, vv, vw, pd, pw, vp, dtp, g.Hx);
         KERNEL_CHECK();
         if (zb) {            // a Bounded z: the strips' z halos come from their boundary conditions -- local fill, then the plain pack
             if ((rc = fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, false, m->any_bc ? m->bcs : nullptr))) return rc;

@@ -2587,10 +2587,11 @@ __global__ void __launch_bounds__(256) pressure_correction_zfast_kernel(DGrid g,
 
 // the same for the two Hx-wide boundary strips (columns 1 .. H and Nx - H + 1 .. Nx) in one launch: a tile kernel would leave 29 of 32
 // lanes idle, so here a thread owns one cell and reads its four pressure values from the z-fastest array directly -- threads along
-// (column, y) like pressure_correction_kernel on a strip range; the lines of pd are shared by 16 consecutive levels (L2)
+// (column, y) like pressure_correction_kernel on a strip range (8 columns per block: ceil(2 H / 8) blocks along x); the lines of pd are
+// shared by 16 consecutive levels (L2)
 __global__ void __launch_bounds__(256) pressure_correction_zfast_strips_kernel(DGrid g, FView u, FView v, FView w, const double *pd, const double *pw,
                                                                                FView p, double divisor, int H) {
-    const int c = threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
+    const int c = blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
     if (c >= 2 * H || j > g.Ny || k > g.Nz) return;
     const int i = c < H ? 1 + c : g.Nx - 2 * H + 1 + c;
     const long sNz = g.Nz, sNx = g.Nx;
@@ -3014,7 +3015,7 @@ __global__ void __launch_bounds__(256) pressure_correction_dense_slab_kernel(DGr
 // ... and on the two Hx-wide boundary strips in one launch (threads along (column, y))
 __global__ void __launch_bounds__(256) pressure_correction_dense_strips_kernel(DGrid g, FView u, FView v, FView w, const double *pd, const double *pw,
                                                                                FView p, double divisor, int H, long sj, long sk, bool zbounded, bool store_p) {
-    const int c = threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
+    const int c = blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
     if (c >= 2 * H || j > g.Ny || k > g.Nz) return;
     const int i = c < H ? 1 + c : g.Nx - 2 * H + 1 + c;
     const long sx = sj, sxy = sk;
