@@ -949,6 +949,59 @@ int ocn_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operand, int kind
  * metric_field_reductions.jl:206-212). `out`: a parent array at operand->loc, interior written. */
 int ocn_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric, double *out);
 
+/* ---------------------------------------------------------------- stencil programs ---------------------------------------------------
+ * KernelFunctionOperation{LX, LY, LZ}(kernel_function, grid, arguments...) (AbstractOperations/kernel_function_operation.jl:58-70), and
+ * what Derivative (derivatives.jl), UnaryOperation (unary_operations.jl) and @at (at.jl) lower to. A closure cannot cross this ABI: the
+ * host calls kernel_function(i, j, k, grid, args...) ONCE with symbols and records a straight-line program in SSA form -- instruction n
+ * defines value n, operands name earlier values, the LAST value is the operand at (i, j, k). The arithmetic ops are the OCN_EXPR_* codes
+ * with their meanings (Julia's min / max, correctly rounded sqrt and /, one IEEE operation each, no contraction); the leaves are
+ *   OCN_EXPR_CONST       imm
+ *   OCN_STENCIL_LOAD     a = argument slot: args[a] at (i + di, j + dj, k + dk)                (getindex of a field)
+ *   OCN_STENCIL_SPACING  a = direction 0 / 1 / 2, b = OCN_CENTER / OCN_FACE: Δx, Δy or Δz at that location and at the index shifted by
+ *                        the direction's own offset (Operators/spacings_and_areas_and_volumes.jl:44-145); 1 in a Flat direction
+ *   OCN_STENCIL_NODE     a = direction, b = location: xnode / ynode / znode at the shifted index (Grids/nodes_and_spacings.jl), from the
+ *                        tables of ocn_grid_set_node_tables (OCN_ESTATE without them)
+ * OCN_EXPR_COORD, OCN_EXPR_TIME and OCN_EXPR_FIELD are no ops of a stencil program.
+ * args: BORROWED device parent arrays with filled halos, arg_locs[3 s + d] their locations; loc: where the operation lives -- its
+ * interior (N + 1 points for a Face on a Bounded direction) is what is computed, reduced or accumulated.
+ *
+ * OCN_EINVAL, before any launch: n outside 1..OCN_STENCIL_MAX_INSTRUCTIONS, nargs outside 0..OCN_STENCIL_MAX_ARGUMENTS, an operand that is
+ * no earlier value, an unknown op, a slot >= nargs, an unused field that is not 0, more than OCN_STENCIL_MAX_SLOTS values alive at once,
+ * a NULL that is needed, an offset along a Flat direction, and the REACH RULE: with n_out the interior extent of `loc` and n_arg that of
+ * the argument along a non-Flat direction d, every LOAD needs off >= -H_d and n_out + off <= n_arg + H_d (a Center argument read from
+ * a Face output on a Bounded direction has one point less of room); Δz tables and node tables are checked the same way against their
+ * lengths. The message names the argument, the direction and the halo it would need. Connected topologies answer OCN_ENOTSUP.
+ *
+ * Limits: values live in LDS, one 8-byte word per thread and LIVE value; the kernels have 256 threads, so a slot is 2 KiB and 64 slots
+ * are 128 KiB of the 160 KiB of a CU. Slots are reused (ocn_stencil_plan), so the budget is values alive at once, not instructions. */
+#define OCN_STENCIL_LOAD 25
+#define OCN_STENCIL_SPACING 26
+#define OCN_STENCIL_NODE 27
+#define OCN_STENCIL_MAX_INSTRUCTIONS 256
+#define OCN_STENCIL_MAX_SLOTS 64
+#define OCN_STENCIL_MAX_ARGUMENTS 8
+typedef struct { int op, a, b, c, di, dj, dk; double imm; } ocn_stencil_ins_t;
+typedef struct {
+    const ocn_stencil_ins_t *program;
+    int n;
+    const double *const *args;
+    const int *arg_locs;          /* 3 per argument */
+    int nargs;
+    int loc[3];
+} ocn_stencil_operand_t;
+/* _compute!(data, operand) (computed_field.jl:100-103) of a stencil operand; see ocn_compute_operation */
+int ocn_compute_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, double *out);
+/* sum! / maximum! / minimum! / average! (Fields/field.jl:735-767, metric_field_reductions.jl:34-47) of a stencil operand: the splits,
+ * the combine order, the metric and `absolute` are those of ocn_reduce_operation -- the same kernels with another evaluator */
+int ocn_reduce_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute, double *out);
+/* cumsum! / reverse_cumsum! (Fields/scans.jl:225-306) of a stencil operand; see ocn_accumulate_operation */
+int ocn_accumulate_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int dim, int reverse, int use_metric, double *out);
+/* the LDS slot of every value: a linear scan over the program -- a value's slot is free again at its last use (the instruction that uses
+ * it last may take it for its own result: operands are read before the result is written), a value takes the lowest free slot, the
+ * last value stays alive. slot_of_value: n ints; nslots: how many slots the program needs. Host arithmetic only, callable before
+ * ocn_init. OCN_EINVAL for the program errors above that need no grid (slot limit included). */
+int ocn_stencil_plan(const ocn_stencil_ins_t *program, int n, int nargs, int *slot_of_value, int *nslots);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,8 @@ from .simulations import (CFL, AdvectiveCFL, DiffusiveCFL, Callback, IterationIn
                           stop_time_exceeded, wall_time_limit_exceeded)
 from .stokes_drifts import StokesDrift, UniformStokesDrift
 from .particles import DroguedParticleDynamics, LagrangianParticles, no_dynamics
-from . import diagnostics, kernels
-from .diagnostics import (Accumulation, Average, BinaryOperation, CumulativeIntegral, FieldStatus, Integral, Reduction, compute, compute_at)
+from . import diagnostics, kernels, operators
+from .diagnostics import (Accumulation, Average, BinaryOperation, CumulativeIntegral, Derivative, FieldStatus, Integral, KernelFunctionOperation,
+                          Reduction, UnaryOperation, at, compute, compute_at, dx, dy, dz)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -51,6 +51,18 @@ class ExprIns(C.Structure):
     _fields_ = [("op", C.c_int), ("a", C.c_int), ("b", C.c_int), ("c", C.c_int), ("imm", C.c_double)]
 
 
+class StencilIns(C.Structure):
+    """ocn_stencil_ins_t"""
+    _fields_ = [("op", C.c_int), ("a", C.c_int), ("b", C.c_int), ("c", C.c_int), ("di", C.c_int), ("dj", C.c_int), ("dk", C.c_int),
+                ("imm", C.c_double)]
+
+
+class StencilOperand(C.Structure):
+    """ocn_stencil_operand_t"""
+    _fields_ = [("program", C.POINTER(StencilIns)), ("n", C.c_int), ("args", C.POINTER(C.c_void_p)), ("arg_locs", C.POINTER(C.c_int)),
+                ("nargs", C.c_int), ("loc", C.c_int * 3)]
+
+
 class Transport(C.Structure):
     """ocn_transport_t: caller-supplied collectives (device addresses as integers)"""
     EXCHANGE_START = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -97,6 +109,10 @@ SYMBOLS = {
     "ocn_compute_operation": (C.c_int, [_vp, C.POINTER(Operand), _vp]),
     "ocn_reduce_operation": (C.c_int, [_vp, C.POINTER(Operand), C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "ocn_accumulate_operation": (C.c_int, [_vp, C.POINTER(Operand), C.c_int, C.c_int, C.c_int, _vp]),
+    "ocn_compute_stencil": (C.c_int, [_vp, C.POINTER(StencilOperand), _vp]),
+    "ocn_reduce_stencil": (C.c_int, [_vp, C.POINTER(StencilOperand), C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
+    "ocn_accumulate_stencil": (C.c_int, [_vp, C.POINTER(StencilOperand), C.c_int, C.c_int, C.c_int, _vp]),
+    "ocn_stencil_plan": (C.c_int, [C.POINTER(StencilIns), C.c_int, C.c_int, _ip, _ip]),
     "ocn_init": (C.c_int, [C.c_int]),
     "ocn_device_count": (C.c_int, [_ip]),
     "ocn_sync": (C.c_int, []),

@@ -121,9 +121,13 @@ def _symbolic(*xs):
 def _unary(name, on_numbers):
     def f(x):
         s = _symbolic(x)
+        if s is None and hasattr(x, "grid"):          # a Field or an operation: the UnaryOperation of diagnostics.py
+            from .diagnostics import unary_operation
+            return unary_operation(name, x)
         return s._op(name, x) if s is not None else on_numbers(x)
     f.__name__ = name
-    f.__doc__ = f"{name}(x): one recorded instruction on a symbol of a boundary function, numpy's {name} on numbers and arrays"
+    f.__doc__ = (f"{name}(x): one recorded instruction on a symbol of a traced function, a UnaryOperation on a Field or an operation, numpy's "
+                 f"{name} on numbers and arrays")
     return f
 
 

@@ -186,6 +186,11 @@ struct ocn_grid_s {
     // partial results of the diagnostics' reductions (ocn_diagnostics.h): grow-only, allocated on first use
     double *diag_slab = nullptr;
     size_t diag_slab_n = 0;
+    // the lowered stencil program of the diagnostic being launched (ocn_diagnostics.h): DG_ST_MAX_INS instructions, allocated on first use
+    DgStIns *diag_program = nullptr;
+    // ... its host copy, which the queued transfer reads, and the event that says the transfer has read it
+    std::vector<DgStIns> diag_program_h;
+    hipEvent_t diag_program_copied = nullptr;
     // node tables for functions of the coordinates (ocn_grid_set_node_tables): per direction N + 1 face and N centre nodes, one device block
     double *node_tables = nullptr;
     const double *nodes_f[3] = {}, *nodes_c[3] = {};
@@ -307,6 +312,8 @@ extern "C" int ocn_grid_destroy(ocn_grid_t grid) {
     hipFree(grid->ob_partial);
     hipFree(grid->znodes);
     hipFree(grid->diag_slab);
+    hipFree(grid->diag_program);
+    if (grid->diag_program_copied) hipEventDestroy(grid->diag_program_copied);
     hipFree(grid->node_tables);
     delete grid;
     return OCN_OK;
@@ -1197,6 +1204,22 @@ extern "C" int ocn_evaluate_forcing_function(ocn_grid_t grid, const ocn_expr_ins
     return OCN_OK;
 }
 
+// the launches below serve both evaluators: O = DgOperand with lds = 0, O = DgStencil<..> with the bytes of its slots
+// more dynamic LDS than the runtime grants by default (a CU has 160 KiB; 64 slots of a stencil program are 128 KiB)
+#define DG_ALLOW_LDS(kernel, lds)                                                                                       \
+    do {                                                                                                                \
+        if ((lds) > 48 * 1024)                                                                                          \
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds))); \
+    } while (0)
+
+template <class O>
+static int dg_compute(ocn_grid_s *grid, const O &o, const int n[3], const DgOut &out, size_t lds) {
+    DG_ALLOW_LDS(dg_compute_kernel<O>, lds);
+    hipLaunchKernelGGL(dg_compute_kernel<O>, grid3(n[0], n[1], n[2], BLK), BLK, lds, g_stream, o, out, n[0], n[1]);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
 extern "C" int ocn_compute_operation(ocn_grid_t grid, const ocn_operand_t *operand, double *out) {
     NEED_INIT();
     if (!out) return fail(OCN_EINVAL, "NULL argument");
@@ -1205,18 +1228,17 @@ extern "C" int ocn_compute_operation(ocn_grid_t grid, const ocn_operand_t *opera
     if (rc) return rc;
     int n[3];
     dg_interior_size(grid->d, operand->loc, n);
-    hipLaunchKernelGGL(dg_compute_kernel, grid3(n[0], n[1], n[2], BLK), BLK, 0, g_stream, o, dg_make_out(grid->d, operand->loc, 0, out), n[0], n[1]);
-    KERNEL_CHECK();
-    return OCN_OK;
+    return dg_compute(grid, o, n, dg_make_out(grid->d, operand->loc, 0, out), 0);
 }
 
-template <int KIND>
-static int dg_reduce(ocn_grid_s *grid, const DgOperand &o, const int n[3], int mask, const DgOut &out) {
+template <int KIND, class O>
+static int dg_reduce(ocn_grid_s *grid, const O &o, const int n[3], int mask, const DgOut &out, size_t lds) {
     const bool rj = mask & 2, rk = mask & 4;
     const double count = (double)((mask & 1) ? n[0] : 1) * (rj ? n[1] : 1) * (rk ? n[2] : 1);
     const int e1 = rj ? 1 : n[1], e2 = rk ? 1 : n[2];
     if (!(mask & 1)) {
-        hipLaunchKernelGGL(dg_reduce_cols_kernel<KIND>, grid3(n[0], e1, e2, BLK), BLK, 0, g_stream, o, out, n[0], e1, rj ? n[1] : 1, rk ? n[2] : 1, count);
+        DG_ALLOW_LDS((dg_reduce_cols_kernel<KIND, O>), lds);
+        hipLaunchKernelGGL((dg_reduce_cols_kernel<KIND, O>), grid3(n[0], e1, e2, BLK), BLK, lds, g_stream, o, out, n[0], e1, rj ? n[1] : 1, rk ? n[2] : 1, count);
         KERNEL_CHECK();
         return OCN_OK;
     }
@@ -1235,13 +1257,44 @@ static int dg_reduce(ocn_grid_s *grid, const DgOperand &o, const int n[3], int m
         HIP_TRY(dev_alloc((void **)&grid->diag_slab, (size_t)(2 * nslab) * sizeof(double)));
         grid->diag_slab_n = (size_t)(2 * nslab);
     }
-    hipLaunchKernelGGL(dg_reduce_rows_kernel<KIND>, dim3((unsigned)nslab), dim3(DG_THREADS), 0, g_stream, o, R, out, grid->diag_slab, nslab);
+    DG_ALLOW_LDS((dg_reduce_rows_kernel<KIND, O>), lds);
+    hipLaunchKernelGGL((dg_reduce_rows_kernel<KIND, O>), dim3((unsigned)nslab), dim3(DG_THREADS), lds, g_stream, o, R, out, grid->diag_slab, nslab);
     KERNEL_CHECK();
     if (R.nch > 1) {
         hipLaunchKernelGGL(dg_combine_kernel<KIND>, dim3((unsigned)nout), dim3(DG_THREADS), 0, g_stream, R, out, grid->diag_slab, nslab,
                            (int)(KIND == OCN_REDUCE_AVERAGE && o.mmode != 0));
         KERNEL_CHECK();
     }
+    return OCN_OK;
+}
+
+template <class O>
+static int dg_reduce_kind(ocn_grid_s *grid, const O &o, int kind, const int n[3], int mask, const DgOut &out, size_t lds) {
+    switch (kind) {
+    case OCN_REDUCE_SUM:     return dg_reduce<OCN_REDUCE_SUM>(grid, o, n, mask, out, lds);
+    case OCN_REDUCE_MAXIMUM: return dg_reduce<OCN_REDUCE_MAXIMUM>(grid, o, n, mask, out, lds);
+    case OCN_REDUCE_MINIMUM: return dg_reduce<OCN_REDUCE_MINIMUM>(grid, o, n, mask, out, lds);
+    default:                 return dg_reduce<OCN_REDUCE_AVERAGE>(grid, o, n, mask, out, lds);
+    }
+}
+
+// cumsum along direction dim of the operand's interior n
+template <class O>
+static int dg_accumulate(const O &o, const int n[3], int dim, int reverse, const DgOut &w, size_t lds) {
+    const dim3 blk(64, 4, 1);
+    if (dim == 0) {
+        const long nrows = (long)n[1] * n[2];
+        DG_ALLOW_LDS(dg_accumulate_rows_kernel<O>, lds);
+        hipLaunchKernelGGL(dg_accumulate_rows_kernel<O>, dim3((unsigned)((nrows + 3) / 4)), dim3(DG_THREADS), lds, g_stream, o, w, n[0], n[1], nrows,
+                           reverse != 0);
+    } else if (dim == 1) {
+        DG_ALLOW_LDS((dg_accumulate_cols_kernel<1, O>), lds);
+        hipLaunchKernelGGL((dg_accumulate_cols_kernel<1, O>), dim3((n[0] + 63) / 64, (n[2] + 3) / 4), blk, lds, g_stream, o, w, n[0], n[2], n[1], reverse != 0);
+    } else {
+        DG_ALLOW_LDS((dg_accumulate_cols_kernel<2, O>), lds);
+        hipLaunchKernelGGL((dg_accumulate_cols_kernel<2, O>), dim3((n[0] + 63) / 64, (n[1] + 3) / 4), blk, lds, g_stream, o, w, n[0], n[1], n[2], reverse != 0);
+    }
+    KERNEL_CHECK();
     return OCN_OK;
 }
 
@@ -1260,12 +1313,7 @@ extern "C" int ocn_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operan
     int n[3];
     dg_interior_size(grid->d, operand->loc, n);
     const DgOut w = dg_make_out(grid->d, operand->loc, dims_mask, out);
-    switch (kind) {
-    case OCN_REDUCE_SUM:     return dg_reduce<OCN_REDUCE_SUM>(grid, o, n, dims_mask, w);
-    case OCN_REDUCE_MAXIMUM: return dg_reduce<OCN_REDUCE_MAXIMUM>(grid, o, n, dims_mask, w);
-    case OCN_REDUCE_MINIMUM: return dg_reduce<OCN_REDUCE_MINIMUM>(grid, o, n, dims_mask, w);
-    default:                 return dg_reduce<OCN_REDUCE_AVERAGE>(grid, o, n, dims_mask, w);
-    }
+    return dg_reduce_kind(grid, o, kind, n, dims_mask, w, 0);
 }
 
 extern "C" int ocn_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric, double *out) {
@@ -1278,18 +1326,273 @@ extern "C" int ocn_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *op
     if (use_metric) dg_set_metric(grid->d, 1 << dim, &o);
     int n[3];
     dg_interior_size(grid->d, operand->loc, n);
-    const DgOut w = dg_make_out(grid->d, operand->loc, 0, out);
-    const dim3 blk(64, 4, 1);
-    if (dim == 0) {
-        const long nrows = (long)n[1] * n[2];
-        hipLaunchKernelGGL(dg_accumulate_rows_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(DG_THREADS), 0, g_stream, o, w, n[0], n[1], nrows,
-                           reverse != 0);
-    } else if (dim == 1)
-        hipLaunchKernelGGL(dg_accumulate_cols_kernel<1>, dim3((n[0] + 63) / 64, (n[2] + 3) / 4), blk, 0, g_stream, o, w, n[0], n[2], n[1], reverse != 0);
-    else
-        hipLaunchKernelGGL(dg_accumulate_cols_kernel<2>, dim3((n[0] + 63) / 64, (n[1] + 3) / 4), blk, 0, g_stream, o, w, n[0], n[1], n[2], reverse != 0);
-    KERNEL_CHECK();
+    return dg_accumulate(o, n, dim, reverse, dg_make_out(grid->d, operand->loc, 0, out), 0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// stencil programs (ocn_diagnostics.h): KernelFunctionOperation, Derivative, UnaryOperation as recorded programs
+// ---------------------------------------------------------------------------------------------------------------------
+// value operands of a stencil instruction (the leaves have none), -1 for what is no op of a stencil program
+static int st_arity(int op) {
+    if (op == OCN_EXPR_CONST || op == OCN_STENCIL_LOAD || op == OCN_STENCIL_SPACING || op == OCN_STENCIL_NODE) return 0;
+    if (op < OCN_EXPR_ADD || op > OCN_EXPR_SELECT) return -1;          // COORD, TIME, FIELD, the planner's table load, anything else
+    return expr_arity(op);
+}
+
+// what can be checked without a grid: every operand names an earlier value, every field the kernel or the lowering reads is in range
+static int st_validate_program(const ocn_stencil_ins_t *program, int n, int nargs) {
+    if (n < 1 || n > DG_ST_MAX_INS) return fail(OCN_EINVAL, "a stencil program has 1..%d instructions; got %d", DG_ST_MAX_INS, n);
+    if (nargs < 0 || nargs > DG_ST_MAX_ARGS) return fail(OCN_EINVAL, "a stencil program has 0..%d field arguments; got %d", DG_ST_MAX_ARGS, nargs);
+    if (!program) return fail(OCN_EINVAL, "NULL program");
+    for (int q = 0; q < n; ++q) {
+        const ocn_stencil_ins_t &I = program[q];
+        const int values = st_arity(I.op);
+        if (values < 0) return fail(OCN_EINVAL, "instruction %d: unknown op %d", q, I.op);
+        const bool load = I.op == OCN_STENCIL_LOAD, line = I.op == OCN_STENCIL_SPACING || I.op == OCN_STENCIL_NODE;
+        if (load && (I.a < 0 || I.a >= nargs)) return fail(OCN_EINVAL, "instruction %d: argument slot %d outside 0..%d", q, I.a, nargs - 1);
+        if (line && (I.a < 0 || I.a > 2)) return fail(OCN_EINVAL, "instruction %d: direction %d is not 0 .. 2", q, I.a);
+        if (line && I.b != OCN_CENTER && I.b != OCN_FACE) return fail(OCN_EINVAL, "instruction %d: location %d is not OCN_CENTER or OCN_FACE", q, I.b);
+        const int operand[3] = {I.a, I.b, I.c}, off[3] = {I.di, I.dj, I.dk};
+        for (int w = 0; w < 3; ++w) {
+            if (w < values) {
+                if (operand[w] < 0 || operand[w] >= q) return fail(OCN_EINVAL, "instruction %d: operand %d is not an earlier value", q, operand[w]);
+            } else if (operand[w] != 0 && !((load && w == 0) || (line && w < 2)))
+                return fail(OCN_EINVAL, "instruction %d: an unused operand field is not 0", q);
+            if (off[w] != 0 && !(load || (line && w == I.a)))
+                return fail(OCN_EINVAL, "instruction %d: an offset where the op takes none (d%c = %d)", q, "ijk"[w], off[w]);
+        }
+    }
     return OCN_OK;
+}
+
+// the slot of every value: a linear scan by last use. At instruction q the slots of the operands that are not used later are freed FIRST
+// (the kernel reads the operands before it writes the result), then q takes the lowest free slot; a value nobody uses frees its slot at
+// once; the last value is the result and stays. Returns the number of slots.
+static int st_plan(const ocn_stencil_ins_t *program, int n, int *slot) {
+    std::vector<int> last(n);
+    for (int q = 0; q < n; ++q) {
+        last[q] = q;
+        const int operand[3] = {program[q].a, program[q].b, program[q].c};
+        for (int w = 0; w < st_arity(program[q].op); ++w) last[operand[w]] = q;
+    }
+    last[n - 1] = n;
+    std::vector<char> used(n + 1, 0);
+    int nslots = 0;
+    for (int q = 0; q < n; ++q) {
+        const int operand[3] = {program[q].a, program[q].b, program[q].c};
+        for (int w = 0; w < st_arity(program[q].op); ++w)
+            if (last[operand[w]] == q) used[slot[operand[w]]] = 0;
+        int s = 0;
+        while (used[s]) ++s;
+        slot[q] = s;
+        used[s] = 1;
+        nslots = std::max(nslots, s + 1);
+        if (last[q] == q) used[s] = 0;
+    }
+    return nslots;
+}
+
+extern "C" int ocn_stencil_plan(const ocn_stencil_ins_t *program, int n, int nargs, int *slot_of_value, int *nslots) {
+    const int rc = st_validate_program(program, n, nargs);
+    if (rc) return rc;
+    std::vector<int> slot(n);
+    const int ns = st_plan(program, n, slot.data());
+    if (slot_of_value) for (int q = 0; q < n; ++q) slot_of_value[q] = slot[q];
+    if (nslots) *nslots = ns;
+    if (ns > DG_ST_MAX_SLOTS)
+        return fail(OCN_EINVAL, "the program keeps %d values alive at once: the limit of a stencil program is %d live values (LDS slots)", ns, DG_ST_MAX_SLOTS);
+    return OCN_OK;
+}
+
+struct StLowered { int n, nslots; bool arith; };
+
+// validate the operand against the grid, lower its program (slots for values, pointers for leaves) and queue the copy into the grid's
+// program block: nothing the kernel indexes with is left unchecked
+static int dg_lower_stencil(ocn_grid_s *grid, const ocn_stencil_operand_t *op, StLowered *S) {
+    if (!grid || !op) return fail(OCN_EINVAL, "NULL argument");
+    const DGrid &g = grid->d;
+    int rc = no_connected_topology(g, "diagnostics");
+    if (rc) return rc;
+    if ((rc = st_validate_program(op->program, op->n, op->nargs))) return rc;
+    if (op->nargs > 0 && (!op->args || !op->arg_locs)) return fail(OCN_EINVAL, "NULL arguments");
+    for (int d = 0; d < 3; ++d)
+        if (op->loc[d] != OCN_CENTER && op->loc[d] != OCN_FACE) return fail(OCN_EINVAL, "loc[%d] is OCN_CENTER or OCN_FACE", d);
+    for (int s = 0; s < op->nargs; ++s) {
+        if (!op->args[s]) return fail(OCN_EINVAL, "argument %d is NULL", s);
+        for (int d = 0; d < 3; ++d)
+            if (op->arg_locs[3 * s + d] != OCN_CENTER && op->arg_locs[3 * s + d] != OCN_FACE)
+                return fail(OCN_EINVAL, "argument %d: loc[%d] is OCN_CENTER or OCN_FACE", s, d);
+    }
+    const int n = op->n;
+    std::vector<int> slot(n);
+    S->n = n;
+    S->nslots = st_plan(op->program, n, slot.data());
+    S->arith = true;
+    if (S->nslots > DG_ST_MAX_SLOTS)
+        return fail(OCN_EINVAL, "the program keeps %d values alive at once: the limit of a stencil program is %d live values (LDS slots)", S->nslots,
+                    DG_ST_MAX_SLOTS);
+    const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz}, T[3] = {g.tx, g.ty, g.tz};
+    int nout[3];
+    dg_interior_size(g, op->loc, nout);
+    std::vector<DgStIns> low(n);
+    for (int q = 0; q < n; ++q) {
+        const ocn_stencil_ins_t &I = op->program[q];
+        const int off[3] = {I.di, I.dj, I.dk};
+        DgStIns &L = low[q];
+        L = DgStIns{};
+        L.dst = slot[q];
+        if (I.op == OCN_EXPR_CONST) {
+            L.op = OCN_EXPR_CONST;
+            L.imm = I.imm;
+        } else if (I.op == OCN_STENCIL_LOAD) {
+            const int *from = op->arg_locs + 3 * I.a;
+            int narg[3], P[3];
+            dg_interior_size(g, from, narg);
+            parent_size(g, from, P);
+            for (int d = 0; d < 3; ++d) {
+                if (T[d] == OCN_FLAT) {
+                    if (off[d] != 0) return fail(OCN_EINVAL, "instruction %d: argument %d is read at offset %+d along %c, which is Flat", q, I.a, off[d], "xyz"[d]);
+                    continue;
+                }
+                // parent index H + i + off, i = 0 .. nout - 1, inside 0 .. narg + 2 H - 1
+                const int need = std::max(-off[d], nout[d] + off[d] - narg[d]);
+                if (need > H[d])
+                    return fail(OCN_EINVAL, "instruction %d: argument %d read at offset %+d along %c (%d output points, %d of the argument) needs a halo of %d; "
+                                "the grid has %d", q, I.a, off[d], "xyz"[d], nout[d], narg[d], need, H[d]);
+            }
+            const long st1 = P[0], st2 = (long)P[0] * P[1];
+            L.op = DG_ST_LOAD;
+            L.s1 = P[0];
+            L.s2 = st2;
+            L.p = op->args[I.a] + ((H[0] + off[0]) + st1 * (H[1] + off[1]) + st2 * (H[2] + off[2]));
+        } else if (I.op == OCN_STENCIL_SPACING) {
+            const int d = I.a;
+            if (d < 2 || T[2] == OCN_FLAT) {                              // x and y are regular (Δᶜ = Δᶠ); a Flat direction has Δ = 1
+                if (T[d] == OCN_FLAT && off[d] != 0) return fail(OCN_EINVAL, "instruction %d: a spacing at offset %+d along %c, which is Flat", q, off[d], "xyz"[d]);
+                L.op = OCN_EXPR_CONST;
+                L.imm = d == 0 ? g.dx : (d == 1 ? g.dy : 1.0);
+            } else {                                                      // tables of Nz + 2 Hz + 1 levels, level k (1-based) at k - 1 + Hz
+                const int need = std::max(-off[2], nout[2] + off[2] - (N[2] + 1));
+                if (need > H[2])
+                    return fail(OCN_EINVAL, "instruction %d: Δz read at offset %+d along z (%d output points) needs a halo of %d; the grid has %d", q, off[2],
+                                nout[2], need, H[2]);
+                L.op = DG_ST_LINE;
+                L.c = 2;
+                L.p = (I.b == OCN_FACE ? g.dzf : g.dzc) + (H[2] + off[2]);
+            }
+        } else if (I.op == OCN_STENCIL_NODE) {
+            const int d = I.a;
+            if (!grid->node_tables) return fail(OCN_ESTATE, "the grid has no node tables: call ocn_grid_set_node_tables");
+            const int len = T[d] == OCN_FLAT ? 1 : N[d] + (I.b == OCN_FACE ? 1 : 0);          // nodes of interior points only
+            if (off[d] < 0 || nout[d] + off[d] > len)
+                return fail(OCN_EINVAL, "instruction %d: the %c node at offset %+d (%d output points) lies outside the %d interior nodes of the table", q,
+                            "xyz"[d], off[d], nout[d], len);
+            L.op = DG_ST_LINE;
+            L.c = d;
+            L.p = (I.b == OCN_FACE ? grid->nodes_f[d] : grid->nodes_c[d]) + off[d];
+        } else {
+            L.op = I.op;
+            const int values = st_arity(I.op);
+            L.a = slot[I.a];
+            if (values > 1) L.b = slot[I.b];
+            if (values > 2) L.c = slot[I.c];
+            if (I.op >= OCN_EXPR_EXP && I.op <= OCN_EXPR_POW) S->arith = false;
+        }
+    }
+    // the program the device block already holds (a diagnostic computed again): nothing to transfer
+    static_assert(sizeof(DgStIns) == 48, "no padding: the comparison below is of whole instructions");
+    std::vector<DgStIns> &held = grid->diag_program_h;
+    if (grid->diag_program && held.size() == low.size() && memcmp(held.data(), low.data(), sizeof(DgStIns) * (size_t)n) == 0) return OCN_OK;
+    if (!grid->diag_program) HIP_TRY(dev_alloc((void **)&grid->diag_program, sizeof(DgStIns) * DG_ST_MAX_INS));
+    // the host copy belongs to the grid and outlives this call; the transfer queued by an earlier call must have read it before it changes
+    if (grid->diag_program_copied) HIP_TRY(hipEventSynchronize(grid->diag_program_copied));
+    else HIP_TRY(hipEventCreateWithFlags(&grid->diag_program_copied, hipEventDisableTiming));
+    held = low;
+    // stream-ordered after the launch that read the previous program
+    hipError_t e = hipMemcpyAsync(grid->diag_program, held.data(), sizeof(DgStIns) * (size_t)n, hipMemcpyHostToDevice, g_stream);
+    if (e == hipSuccess) e = hipEventRecord(grid->diag_program_copied, g_stream);
+    if (e != hipSuccess) { held.clear(); return fail((int)e, "stencil program transfer: %s", hipGetErrorString(e)); }
+    return OCN_OK;
+}
+
+template <bool ARITH>
+static DgStencil<ARITH> dg_stencil_operand(const ocn_grid_s *grid, const ocn_stencil_operand_t *op, const StLowered &S) {
+    DgStencil<ARITH> o = {};
+    o.ins = grid->diag_program;
+    o.n = S.n;
+    o.dz = op->loc[2] == OCN_FACE ? grid->d.dzf : grid->d.dzc;
+    o.Hz = grid->d.Hz;
+    return o;
+}
+template <class O> static void dg_set_metric_of(const DGrid &g, int mask, O *o) {
+    DgOperand m = {};
+    dg_set_metric(g, mask, &m);
+    o->mc = m.mc;
+    o->mmode = m.mmode;
+}
+// DG_ST_MIN_LDS_SLOTS (an A/B build, OCN_EXTRA_FLAGS): ask for at least that many slots of LDS, to time a program at the occupancy a
+// larger one would have -- 32 slots are two blocks per CU, 64 one
+#ifndef DG_ST_MIN_LDS_SLOTS
+#define DG_ST_MIN_LDS_SLOTS 0
+#endif
+static size_t st_lds_bytes(const StLowered &S) { return sizeof(double) * DG_THREADS * (size_t)std::max(S.nslots, DG_ST_MIN_LDS_SLOTS); }
+
+extern "C" int ocn_compute_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    StLowered S;
+    const int rc = dg_lower_stencil(grid, operand, &S);
+    if (rc) return rc;
+    int n[3];
+    dg_interior_size(grid->d, operand->loc, n);
+    const DgOut w = dg_make_out(grid->d, operand->loc, 0, out);
+    return S.arith ? dg_compute(grid, dg_stencil_operand<true>(grid, operand, S), n, w, st_lds_bytes(S))
+                   : dg_compute(grid, dg_stencil_operand<false>(grid, operand, S), n, w, st_lds_bytes(S));
+}
+
+template <bool ARITH>
+static int st_reduce(ocn_grid_s *grid, const ocn_stencil_operand_t *operand, const StLowered &S, int kind, int dims_mask, int use_metric,
+                     int absolute, double *out) {
+    DgStencil<ARITH> o = dg_stencil_operand<ARITH>(grid, operand, S);
+    o.absolute = absolute != 0;
+    if (use_metric) dg_set_metric_of(grid->d, dims_mask, &o);
+    int n[3];
+    dg_interior_size(grid->d, operand->loc, n);
+    return dg_reduce_kind(grid, o, kind, n, dims_mask, dg_make_out(grid->d, operand->loc, dims_mask, out), st_lds_bytes(S));
+}
+
+extern "C" int ocn_reduce_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
+                                  double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    if (kind < OCN_REDUCE_SUM || kind > OCN_REDUCE_AVERAGE) return fail(OCN_EINVAL, "unknown reduction kind %d", kind);
+    if (dims_mask < 1 || dims_mask > 7) return fail(OCN_EINVAL, "dims_mask %d: bits 0..2 name the reduced directions, at least one", dims_mask);
+    if (use_metric && (kind == OCN_REDUCE_MAXIMUM || kind == OCN_REDUCE_MINIMUM)) return fail(OCN_EINVAL, "maximum and minimum take no metric");
+    StLowered S;
+    const int rc = dg_lower_stencil(grid, operand, &S);
+    if (rc) return rc;
+    return S.arith ? st_reduce<true>(grid, operand, S, kind, dims_mask, use_metric, absolute, out)
+                   : st_reduce<false>(grid, operand, S, kind, dims_mask, use_metric, absolute, out);
+}
+
+template <bool ARITH>
+static int st_accumulate(ocn_grid_s *grid, const ocn_stencil_operand_t *operand, const StLowered &S, int dim, int reverse, int use_metric, double *out) {
+    DgStencil<ARITH> o = dg_stencil_operand<ARITH>(grid, operand, S);
+    if (use_metric) dg_set_metric_of(grid->d, 1 << dim, &o);
+    int n[3];
+    dg_interior_size(grid->d, operand->loc, n);
+    return dg_accumulate(o, n, dim, reverse, dg_make_out(grid->d, operand->loc, 0, out), st_lds_bytes(S));
+}
+
+extern "C" int ocn_accumulate_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int dim, int reverse, int use_metric, double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    if (dim < 0 || dim > 2) return fail(OCN_EINVAL, "dim %d: 0 (x), 1 (y) or 2 (z)", dim);
+    StLowered S;
+    const int rc = dg_lower_stencil(grid, operand, &S);
+    if (rc) return rc;
+    return S.arith ? st_accumulate<true>(grid, operand, S, dim, reverse, use_metric, out)
+                   : st_accumulate<false>(grid, operand, S, dim, reverse, use_metric, out);
 }
 
 static int update_hydrostatic_pressure(const DGrid &g, int kind, const double *bT, const double *S, double grav, double alpha, double beta,

@@ -4,7 +4,9 @@
 //
 // One evaluator, dg_eval, forms the operand at (i, j, k): loads, interpolation (Operators/interpolation_operators.jl), operation, metric,
 // in that order -- the computed-field kernel, the reducing kernels and the accumulating kernels all call it, so what is summed is exactly
-// what the computed field holds. The translation unit is compiled with -ffp-contract=off: separate IEEE multiplies and adds.
+// what the computed field holds. It has two overloads and every kernel is a template on the operand type: DgOperand, the one fixed
+// operation node, and DgStencil, a recorded stencil program (KernelFunctionOperation, Derivative, UnaryOperation) run by an interpreter.
+// The translation unit is compiled with -ffp-contract=off: separate IEEE multiplies and adds.
 //
 // Reductions use no atomics. How the points are split into partial results depends on the grid size and the reduced directions only:
 //   x reduced (dg_reduce_rows_kernel)  the (j, k) rows of one output element are cut into chunks of DG_ROWS rows, one 256-thread block per
@@ -68,7 +70,7 @@ __device__ __forceinline__ double dg_leaf(const DgLeaf &l, int i, int j, int k) 
 }
 
 // the metric at level k (0-based interior index)
-__device__ __forceinline__ double dg_metric(const DgOperand &o, int k) {
+template <class O> __device__ __forceinline__ double dg_metric(const O &o, int k) {
     if (o.mmode == 1) return o.mc;
     const double dz = o.dz[k + o.Hz];
     return o.mmode == 2 ? dz : o.mc * dz;
@@ -92,9 +94,91 @@ __device__ __forceinline__ double dg_eval(const DgOperand &o, int i, int j, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// stencil programs: KernelFunctionOperation (AbstractOperations/kernel_function_operation.jl:58-70), Derivative, UnaryOperation
+// ---------------------------------------------------------------------------------------------------------------------
+// The host records kernel_function(i, j, k, grid, args...) once as a straight-line program (ocn_stencil_ins_t) and lowers it for the
+// device: every value has an LDS slot (ocn_stencil_plan: linear scan by last use), every leaf its pointer. dg_eval (the DgStencil
+// overload, "dg_eval_stencil") is the ONE evaluator of such programs: the kernels below call it exactly where they call the fixed one.
+// The instruction words are the same for every thread (scalar loads, a switch on a wave-uniform value); the values of a thread are
+// indexed at run time, so they live in dynamic LDS, slot-major: vals[slot][thread], nslots x 256 threads x 8 B, consecutive lanes in
+// consecutive banks (ocn_boundary_function.h). A thread only touches its own column: no barrier. Every instruction is ONE IEEE operation.
+#define DG_ST_MAX_INS 256        // OCN_STENCIL_MAX_INSTRUCTIONS
+#define DG_ST_MAX_SLOTS 64       // OCN_STENCIL_MAX_SLOTS: 64 x 2 KiB = 128 KiB of the 160 KiB of a CU
+#define DG_ST_MAX_ARGS 8         // OCN_STENCIL_MAX_ARGUMENTS
+#define DG_ST_LOAD 25            // p[i + s1 j + s2 k]: an argument at a constant offset (folded into p)
+#define DG_ST_LINE 26            // p[i], p[j] or p[k] (c = 0, 1, 2): Δz or a node table (the offset folded into p)
+
+struct DgStIns {
+    int op;                   // OCN_EXPR_CONST, OCN_EXPR_ADD .. OCN_EXPR_SELECT, DG_ST_LOAD, DG_ST_LINE
+    int a, b, c;              // SLOTS of the operands (0 where unused; DG_ST_LINE: c = the direction)
+    int dst;                  // slot of the result
+    int s1;
+    long s2;                  // parent strides of the argument along y and z
+    const double *p;
+    double imm;
+};
+
+// ARITH: the program holds none of exp, log, sin, cos, tanh, pow -- an instantiation without their code (ocn_forcing_function.h)
+template <bool ARITH> struct DgStencil {
+    const DgStIns *ins;       // device copy of the lowered program
+    int n;
+    int absolute, mmode;      // as DgOperand
+    double mc;
+    const double *dz;
+    int Hz;
+};
+
+extern __shared__ double dg_vals[];
+
+template <bool ARITH>
+__device__ __forceinline__ double dg_eval(const DgStencil<ARITH> &o, int i, int j, int k, double &metric) {
+    double *vals = dg_vals + (threadIdx.y * blockDim.x + threadIdx.x);
+    double r = 0.0;
+    for (int q = 0; q < o.n; ++q) {
+        const DgStIns I = o.ins[q];
+        const double x = vals[I.a * DG_THREADS], y = vals[I.b * DG_THREADS];
+        switch (I.op) {
+        case OCN_EXPR_CONST: r = I.imm; break;
+        case DG_ST_LOAD: r = I.p[i + (long)I.s1 * j + I.s2 * k]; break;
+        case DG_ST_LINE: r = I.p[I.c == 0 ? i : (I.c == 1 ? j : k)]; break;
+        case OCN_EXPR_ADD: r = x + y; break;
+        case OCN_EXPR_SUB: r = x - y; break;
+        case OCN_EXPR_MUL: r = x * y; break;
+        case OCN_EXPR_DIV: r = x / y; break;
+        case OCN_EXPR_NEG: r = -x; break;
+        case OCN_EXPR_ABS: r = fabs(x); break;
+        case OCN_EXPR_MIN: r = jl_min(x, y); break;
+        case OCN_EXPR_MAX: r = jl_max(x, y); break;
+        case OCN_EXPR_SQRT: r = sqrt(x); break;
+        case OCN_EXPR_EXP: if (!ARITH) r = exp(x); break;
+        case OCN_EXPR_LOG: if (!ARITH) r = log(x); break;
+        case OCN_EXPR_SIN: if (!ARITH) r = sin(x); break;
+        case OCN_EXPR_COS: if (!ARITH) r = cos(x); break;
+        case OCN_EXPR_TANH: if (!ARITH) r = tanh(x); break;
+        case OCN_EXPR_POW: if (!ARITH) r = pow(x, y); break;
+        case OCN_EXPR_LT: r = x < y ? 1.0 : 0.0; break;
+        case OCN_EXPR_LE: r = x <= y ? 1.0 : 0.0; break;
+        case OCN_EXPR_GT: r = x > y ? 1.0 : 0.0; break;
+        case OCN_EXPR_GE: r = x >= y ? 1.0 : 0.0; break;
+        default: r = x != 0.0 ? y : vals[I.c * DG_THREADS]; break;          // OCN_EXPR_SELECT
+        }
+        vals[I.dst * DG_THREADS] = r;
+    }
+    double v = r;                                                          // the result is the LAST value
+    if (o.absolute) v = fabs(v);
+    metric = 1.0;
+    if (o.mmode) {
+        metric = dg_metric(o, k);
+        v = v * metric;
+    }
+    return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // computed field: _compute! (computed_field.jl:100-103)
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) dg_compute_kernel(DgOperand o, DgOut out, int n0, int n1) {
+template <class O>
+__global__ void __launch_bounds__(256) dg_compute_kernel(O o, DgOut out, int n0, int n1) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y, k = blockIdx.z;
     if (i >= n0 || j >= n1) return;
     double m;
@@ -131,8 +215,8 @@ struct DgRows {
 
 // x reduced. Block b: output element b / nch, chunk b % nch. slab: [0, nout * nch) the partial results, [nout * nch, 2 nout nch) the
 // partial metric sums (average with a metric)
-template <int KIND>
-__global__ void __launch_bounds__(DG_THREADS) dg_reduce_rows_kernel(DgOperand o, DgRows R, DgOut out, double *slab, long nslab) {
+template <int KIND, class O>
+__global__ void __launch_bounds__(DG_THREADS) dg_reduce_rows_kernel(O o, DgRows R, DgOut out, double *slab, long nslab) {
     __shared__ double lds[2][DG_THREADS / 64];
     const long b = blockIdx.x;
     const int e = (int)(b / R.nch), c = (int)(b % R.nch);
@@ -193,8 +277,8 @@ __global__ void __launch_bounds__(DG_THREADS) dg_combine_kernel(DgRows R, DgOut 
 }
 
 // x kept: thread (i, jo, ko) loops over the reduced y (inner) and z (outer) extents lj, lk (1 where the direction is kept)
-template <int KIND>
-__global__ void __launch_bounds__(256) dg_reduce_cols_kernel(DgOperand o, DgOut out, int n0, int e1, int lj, int lk, double count) {
+template <int KIND, class O>
+__global__ void __launch_bounds__(256) dg_reduce_cols_kernel(O o, DgOut out, int n0, int e1, int lj, int lk, double count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, jo = blockIdx.y * blockDim.y + threadIdx.y, ko = blockIdx.z;
     if (i >= n0 || jo >= e1) return;
     const bool with_metric = KIND == OCN_REDUCE_AVERAGE && o.mmode != 0;
@@ -212,8 +296,8 @@ __global__ void __launch_bounds__(256) dg_reduce_cols_kernel(DgOperand o, DgOut 
 // accumulations: B[start] = A[start]; B[i] = B[i ∓ 1] + A[i] (accumulate_x / _y / _z, scans.jl:272-306)
 // ---------------------------------------------------------------------------------------------------------------------
 // along y (DIM 1) or z (DIM 2): thread (i, q), q the other of j, k; nd points along the march
-template <int DIM>
-__global__ void __launch_bounds__(256) dg_accumulate_cols_kernel(DgOperand o, DgOut out, int n0, int nq, int nd, int reverse) {
+template <int DIM, class O>
+__global__ void __launch_bounds__(256) dg_accumulate_cols_kernel(O o, DgOut out, int n0, int nq, int nd, int reverse) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, q = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= n0 || q >= nq) return;
     double run = 0.0;
@@ -228,7 +312,8 @@ __global__ void __launch_bounds__(256) dg_accumulate_cols_kernel(DgOperand o, Dg
 }
 
 // along x: one wave per (j, k) row, 64 points per step; every lane forms the running sum of the step's values in index order
-__global__ void __launch_bounds__(DG_THREADS) dg_accumulate_rows_kernel(DgOperand o, DgOut out, int n0, int n1, long nrows, int reverse) {
+template <class O>
+__global__ void __launch_bounds__(DG_THREADS) dg_accumulate_rows_kernel(O o, DgOut out, int n0, int n1, long nrows, int reverse) {
     const long row = (long)blockIdx.x * (DG_THREADS / 64) + (threadIdx.x >> 6);
     if (row >= nrows) return;                                // whole waves leave: the shuffles below see full waves
     const int lane = threadIdx.x & 63;

@@ -8,9 +8,15 @@ A BinaryOperation (`a + b`, `a - b`, `a * b`, `a / b`, `a ** 2` of a Field and a
 CumulativeIntegral, Reduction, Accumulation) are descriptors: no device work happens until `Field(operand)` / `compute(field)`, which run
 the kernels of csrc/ocn_diagnostics.h on the library's stream, after whatever step came before.
 
-Served: ONE operation node over fields of one grid. Refused by name (NotImplementedError, before any device call): condition= / mask=,
-derivative and unary operands, nested operations (materialise the inner one with Field(op) first), reduced fields as operands,
-partitioned grids; fields of different grids are a ValueError."""
+Two evaluators serve them. ONE operation node over fields and numbers keeps the fixed one (ocn_operand_t). Everything deeper is a
+stencil program (operators.py): KernelFunctionOperation(location, kernel_function, grid, *arguments) records a kernel function written
+with the operators of ocn.operators; Derivative (ocn.dx / dy / dz), UnaryOperation (ocn.sqrt .. tanh of a field, abs(f), -f), ocn.at and a
+BinaryOperation with such operands are lowered to the same programs as the reference's getindex evaluates them
+(AbstractOperations/derivatives.jl:23, unary_operations.jl:21, binary_operations.jl:25).
+
+Refused by name (NotImplementedError, before any device call): condition= / mask=, arithmetic on a BinaryOperation (materialise it with
+Field(op) first, or write a KernelFunctionOperation), functions, strings and arrays as operands, reduced fields as operands, partitioned
+grids; fields of different grids are a ValueError."""
 import numbers
 
 from . import _lib
@@ -38,8 +44,8 @@ def _check_grid(grid):
 
 def _check_field(f):
     if not isinstance(f, Field):
-        raise NotImplementedError(f"{type(f).__name__} as an operand: a Field or one BinaryOperation of Fields and numbers is served; "
-                                  "derivatives, unary operations and functions are not built")
+        raise NotImplementedError(f"{type(f).__name__} as an operand: a Field, a Derivative, a UnaryOperation, a KernelFunctionOperation or one "
+                                  "BinaryOperation of those and numbers is served; functions, strings and arrays are not")
     if any(l is None for l in f.loc):
         raise NotImplementedError("a reduced field as an operand is not built")
     _check_grid(f.grid)
@@ -57,25 +63,33 @@ class BinaryOperation:
     """op(▶a(a), ▶b(b)) at `location` (binary_operations.jl:5-25): the location of the first field operand (:109-135), the other field
     interpolated to it by the operator `interp_a` / `interp_b` names (:38-43)"""
 
-    def __init__(self, op, a, b):
+    def __init__(self, op, a, b, location=None):
         fields = [x for x in (a, b) if not isinstance(x, numbers.Real)]
         for x in fields:
-            if isinstance(x, (BinaryOperation, Scan)):
+            if isinstance(x, (BinaryOperation, Scan, KernelFunctionOperation)):
                 raise NotImplementedError("nested operations are not built: materialise the inner one first with Field(op) and use that "
-                                          "field as the operand")
-            _check_field(x)
+                                          "field as the operand (KernelFunctionOperation is the route for deeper expressions)")
+            if not isinstance(x, (Derivative, UnaryOperation)):
+                _check_field(x)
         if not fields:
             raise TypeError("an operation needs a Field operand")
         if len(fields) == 2 and fields[0].grid is not fields[1].grid:
             raise ValueError("the operands live on different grids")          # validate_grid (AbstractOperations/AbstractOperations.jl)
         self.op, self.a, self.b = op, a, b
         self.grid = fields[0].grid
-        self.location = fields[0].loc
-        self.interp_a = interpolation_operator(a.loc, self.location) if isinstance(a, Field) else "identity"
-        self.interp_b = interpolation_operator(b.loc, self.location) if isinstance(b, Field) else "identity"
+        self.location = _location(fields[0]) if location is None else _as_location(location)
+        self.interp_a = "identity" if isinstance(a, numbers.Real) else interpolation_operator(_location(a), self.location)
+        self.interp_b = "identity" if isinstance(b, numbers.Real) else interpolation_operator(_location(b), self.location)
+
+    @property
+    def fixed(self):
+        """whether the fixed evaluator (ocn_operand_t) serves this node: fields and numbers at the first field's location"""
+        operands = [x for x in (self.a, self.b) if not isinstance(x, numbers.Real)]
+        return all(isinstance(x, Field) for x in operands) and self.location == operands[0].loc
 
     def _nested(self, *_):
-        raise NotImplementedError("nested operations are not built: materialise this one first with Field(op) and use that field as the operand")
+        raise NotImplementedError("nested operations are not built: materialise this one first with Field(op) and use that field as the operand "
+                                  "(KernelFunctionOperation is the route for deeper expressions)")
 
     __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = __pow__ = _nested
 
@@ -86,7 +100,7 @@ class BinaryOperation:
 
 def binary_operation(op, a, b):
     for x in (a, b):
-        if isinstance(x, bool) or not isinstance(x, (numbers.Real, Field, BinaryOperation, Scan)):
+        if isinstance(x, bool) or not isinstance(x, (numbers.Real, Field, BinaryOperation, Scan, Derivative, UnaryOperation, KernelFunctionOperation)):
             raise NotImplementedError(f"{type(x).__name__} as an operand: a Field or a number is served")
     return BinaryOperation(op, a, b)
 
@@ -96,6 +110,231 @@ def power(a, exponent):
     if isinstance(exponent, bool) or not isinstance(exponent, numbers.Real) or exponent != 2:
         raise NotImplementedError(f"a ** {exponent!r}: only the exponent 2 is built (as a * a)")
     return BinaryOperation("*", a, a)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# nodes that are lowered to stencil programs (operators.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def _as_location(loc):
+    loc = tuple(l if isinstance(l, type) else type(l) for l in loc)
+    if len(loc) != 3 or any(l not in (Center, Face) for l in loc):
+        raise ValueError(f"location {loc!r}: a 3-tuple of Center / Face")
+    return loc
+
+
+def _location(x):
+    return x.loc if isinstance(x, Field) else x.location
+
+
+def _flip(l):
+    """flip (derivatives.jl:42-43)"""
+    return Face if l is Center else Center
+
+
+class _Node:
+    """what the tree nodes below share: arithmetic that builds a BinaryOperation / UnaryOperation, and the cached lowering"""
+
+    __array_ufunc__ = None
+
+    def __add__(self, o): return binary_operation("+", self, o)
+    def __radd__(self, o): return binary_operation("+", o, self)
+    def __sub__(self, o): return binary_operation("-", self, o)
+    def __rsub__(self, o): return binary_operation("-", o, self)
+    def __mul__(self, o): return binary_operation("*", self, o)
+    def __rmul__(self, o): return binary_operation("*", o, self)
+    def __truediv__(self, o): return binary_operation("/", self, o)
+    def __rtruediv__(self, o): return binary_operation("/", o, self)
+    def __pow__(self, e): return power(self, e)
+    def __neg__(self): return UnaryOperation("neg", self)
+    def __abs__(self): return UnaryOperation("abs", self)
+
+
+def _check_argument(arg, what):
+    if isinstance(arg, (Scan, KernelFunctionOperation)):
+        raise NotImplementedError(f"{type(arg).__name__} as the argument of a {what}: materialise it first with Field(...)")
+    if not isinstance(arg, (Derivative, UnaryOperation, BinaryOperation)):
+        _check_field(arg)
+    _check_grid(arg.grid)
+    return arg
+
+
+class Derivative(_Node):
+    """Derivative{LX, LY, LZ}(∂, arg, ▶, grid) (derivatives.jl:3-34): ∂ along `direction` (0, 1, 2) of `arg` where it lands -- arg's location
+    with the direction flipped -- then interpolated to `location` by the operator `interp` names; getindex is ▶(i, j, k, grid, ∂, arg) (:23)"""
+
+    def __init__(self, direction, arg, location=None):
+        self.direction, self.arg = int(direction), _check_argument(arg, "Derivative")
+        self.grid = arg.grid
+        La = _location(arg)
+        self.derivative_location = tuple(_flip(l) if d == self.direction else l for d, l in enumerate(La))
+        self.location = self.derivative_location if location is None else _as_location(location)
+        # ∂x(LX, LY, LZ) (derivatives.jl:48-54): the operator named for where the derivative lands
+        self.operator = "d" + "xyz"[self.direction] + "".join(_SUP[l] for l in self.derivative_location)
+        self.interp = interpolation_operator(self.derivative_location, self.location)
+
+    def __repr__(self):
+        return f"Derivative at ({', '.join(l.__name__ for l in self.location)}): ∂{'xyz'[self.direction]} via {self.interp}"
+
+
+UNARY_OPERATORS = ("identity", "neg", "abs", "sqrt", "exp", "log", "sin", "cos", "tanh")
+
+
+class UnaryOperation(_Node):
+    """UnaryOperation{LX, LY, LZ}(op, arg, ▶, grid) (unary_operations.jl:3-34): op at arg's location, then interpolated to `location`;
+    getindex is ▶(i, j, k, grid, op, arg) (:21). op: one of UNARY_OPERATORS ("identity" is at.jl's interpolate_identity, :28-37)"""
+
+    def __init__(self, op, arg, location=None):
+        if op in ("log10", "tan", "sinh", "cosh"):
+            raise NotImplementedError(f"{op}(field): the reference's {op} has no instruction in a stencil program")
+        if op not in UNARY_OPERATORS:
+            raise NotImplementedError(f"{op}(field): the unary operations with an instruction are {', '.join(UNARY_OPERATORS[1:])}")
+        self.op, self.arg = op, _check_argument(arg, "UnaryOperation")
+        self.grid = arg.grid
+        self.location = _location(arg) if location is None else _as_location(location)
+        self.interp = interpolation_operator(_location(arg), self.location)
+
+    def __repr__(self):
+        return f"UnaryOperation at ({', '.join(l.__name__ for l in self.location)}): {self.op} via {self.interp}"
+
+
+class KernelFunctionOperation:
+    """KernelFunctionOperation{LX, LY, LZ}(kernel_function, grid, arguments...) (kernel_function_operation.jl:58-70) as
+    KernelFunctionOperation(location, kernel_function, grid, *arguments). The function is called ONCE, here, as
+    kernel_function(i, j, k, grid, *arguments) with index symbols and, for every Field among the arguments, a field symbol
+    (operators.record); anything else is handed over untouched. ValueError: a limit, or the reach rule -- an offset the grid's halo does
+    not cover; TypeError: a misused symbol."""
+
+    def __init__(self, location, kernel_function, grid, *arguments):
+        from . import operators
+        if not callable(kernel_function):
+            raise TypeError("kernel_function must be callable")
+        self.location = _as_location(location)
+        _check_grid(grid)
+        for a in arguments:
+            if isinstance(a, Field):
+                _check_field(a)
+                if a.grid is not grid:
+                    raise ValueError("the operands live on different grids")
+            elif isinstance(a, _NODES + (Scan,)):
+                raise NotImplementedError(f"{type(a).__name__} as an argument of a KernelFunctionOperation: materialise it first with Field(...)")
+        self.kernel_function, self.grid, self.arguments = kernel_function, grid, tuple(arguments)
+        self.stencil = operators.record(kernel_function, grid, self.location, self.arguments)
+
+    __array_ufunc__ = None
+
+    def _nested(self, *_):
+        raise NotImplementedError("arithmetic on a KernelFunctionOperation is not built: write it inside the kernel function, or materialise "
+                                  "this one first with Field(op)")
+
+    __add__ = __radd__ = __sub__ = __rsub__ = __mul__ = __rmul__ = __truediv__ = __rtruediv__ = __pow__ = _nested
+
+    def __repr__(self):
+        # Base.show (kernel_function_operation.jl:83-96)
+        loc = ", ".join(l.__name__ for l in self.location)
+        args = "()" if not self.arguments else "(" + ", ".join('"Field"' if isinstance(a, Field) else repr(a) for a in self.arguments) + ")"
+        return (f"KernelFunctionOperation at ({loc})\n├── grid: {self.grid!r}\n"
+                f"├── kernel_function: {getattr(self.kernel_function, '__name__', repr(self.kernel_function))}\n└── arguments: {args}")
+
+
+_NODES = (BinaryOperation, Derivative, UnaryOperation, KernelFunctionOperation)
+
+
+def _derivative(direction):
+    def d(*args):
+        if len(args) == 1:
+            return Derivative(direction, args[0])
+        if len(args) == 2:
+            return Derivative(direction, args[1], args[0])
+        raise TypeError(f"d{'xyz'[direction]}(f) or d{'xyz'[direction]}(location, f)")
+    d.__name__ = "d" + "xyz"[direction]
+    d.__doc__ = (f"∂{'xyz'[direction]}(arg) / ∂{'xyz'[direction]}(L, arg) (derivatives.jl:65-107): the derivative of a Field or an operation, by "
+                 "default where it lands (arg's location with the direction flipped), else interpolated to L")
+    return d
+
+
+dx, dy, dz = _derivative(0), _derivative(1), _derivative(2)
+
+
+def unary_operation(op, arg):
+    """what ocn.sqrt .. ocn.tanh answer for a Field or an operation"""
+    return UnaryOperation(op, arg)
+
+
+def at(location, node):
+    """@at location node (at.jl:45-55) through the reference's at(loc, ·) methods: a BinaryOperation is rebuilt at `location` with both
+    operands relocated (binary_operations.jl:32), a UnaryOperation likewise (unary_operations.jl:37), a Derivative is taken where it lands
+    and interpolated to `location` with its argument as it is (derivatives.jl:39); a Field elsewhere is interpolated
+    (interpolate_identity, at.jl:28-37), a Field at `location` and a number stay"""
+    location = _as_location(location)
+    relocated = _at(location, node)
+    if isinstance(relocated, Field) and relocated.loc != location:
+        return UnaryOperation("identity", relocated, location)
+    return relocated
+
+
+def _at(location, node):
+    if isinstance(node, BinaryOperation):
+        return BinaryOperation(node.op, _at(location, node.a), _at(location, node.b), location)
+    if isinstance(node, UnaryOperation):
+        return UnaryOperation(node.op, _at(location, node.arg), location)
+    if isinstance(node, Derivative):
+        return Derivative(node.direction, node.arg, location)
+    if isinstance(node, (Field, numbers.Real)):
+        return node                                            # at(loc, f) = f (AbstractOperations.jl:48)
+    raise NotImplementedError(f"at(location, {type(node).__name__}): a Field or a tree of BinaryOperation, UnaryOperation and Derivative")
+
+
+def lower(node):
+    """the StencilProgram of a Field, a BinaryOperation, a Derivative, a UnaryOperation or a KernelFunctionOperation (cached on the node):
+    the tree is evaluated once with symbols, each node as the reference's getindex evaluates it"""
+    from . import boundary_functions as bf
+    from . import operators
+    if isinstance(node, KernelFunctionOperation):
+        return node.stencil
+    cached = None if isinstance(node, Field) else getattr(node, "_stencil", None)
+    if cached is not None:
+        return cached
+    fields = []
+
+    def collect(x):
+        if isinstance(x, Field):
+            if not any(x is f for f in fields):
+                fields.append(x)
+        elif isinstance(x, BinaryOperation):
+            collect(x.a), collect(x.b)
+        elif isinstance(x, (Derivative, UnaryOperation)):
+            collect(x.arg)
+    collect(node)
+    if any(f.grid is not fields[0].grid for f in fields):
+        raise ValueError("the operands live on different grids")
+    unary = {"identity": lambda x: x, "neg": lambda x: -x, "abs": abs, "sqrt": bf.sqrt, "exp": bf.exp, "log": bf.log, "sin": bf.sin,
+             "cos": bf.cos, "tanh": bf.tanh}
+    binary = {"+": lambda x, y: x + y, "-": lambda x, y: x - y, "*": lambda x, y: x * y, "/": lambda x, y: x / y}
+
+    def kernel_function(i, j, k, grid, *symbols):
+        def operand(x):
+            """what an operator takes: a field symbol, a number, or the function that evaluates the node"""
+            if isinstance(x, Field):
+                return symbols[next(q for q, f in enumerate(fields) if f is x)]
+            if isinstance(x, numbers.Real):
+                return float(x)
+            return lambda i, j, k, grid: evaluate(x, i, j, k)
+
+        def evaluate(x, i, j, k):
+            if isinstance(x, BinaryOperation):
+                a = operators.interpolation(x.interp_a)(i, j, k, grid, operand(x.a))
+                b = operators.interpolation(x.interp_b)(i, j, k, grid, operand(x.b))
+                return binary[x.op](a, b)
+            if isinstance(x, Derivative):
+                return operators.interpolation(x.interp)(i, j, k, grid, getattr(operators, x.operator), operand(x.arg))
+            op = unary[x.op]
+            return operators.interpolation(x.interp)(i, j, k, grid, lambda i, j, k, grid, a: op(operators.identity(i, j, k, grid, a)), operand(x.arg))
+        return operators.identity(i, j, k, grid, operand(node))
+
+    stencil = operators.record(kernel_function, node.grid, _location(node), fields)
+    if not isinstance(node, Field):
+        node._stencil = stencil
+    return stencil
 
 
 def _filter_dims(dims):
@@ -119,7 +358,7 @@ def _refuse_conditions(kw):
 def _check_operand(operand):
     if isinstance(operand, Scan):
         raise NotImplementedError("nested operations are not built: materialise the inner scan first with Field(scan)")
-    if not isinstance(operand, BinaryOperation):
+    if not isinstance(operand, _NODES):
         _check_field(operand)
     return operand
 
@@ -138,7 +377,7 @@ class Scan:
         self.kind, self.operand, self.dims = kind, _check_operand(operand), dims
         self.use_metric, self.absolute, self.reverse = bool(use_metric), bool(absolute), bool(reverse)
         self.grid = operand.grid
-        operand_location = operand.location if isinstance(operand, BinaryOperation) else operand.loc
+        operand_location = _location(operand)
         self.location = reduced_location(operand_location, dims) if self.reducing else tuple(operand_location)
 
     def __repr__(self):
@@ -207,10 +446,11 @@ class Accumulation(_Accumulating):
 
 def as_field_operand(x):
     """what Field(x) may be computed from"""
-    if isinstance(x, (BinaryOperation, Scan)):
+    if isinstance(x, _NODES + (Scan,)):
         _check_grid(x.grid)
         return x
-    raise TypeError(f"Field({type(x).__name__}): a location tuple, a BinaryOperation or a scan")
+    raise TypeError(f"Field({type(x).__name__}): a location tuple, an operation (BinaryOperation, Derivative, UnaryOperation, "
+                    "KernelFunctionOperation) or a scan")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -252,13 +492,17 @@ def compute(field):
     if operand is None:
         return field                                           # compute!(field) of a plain field is a no-op (field.jl)
     grid = field.grid
-    if isinstance(operand, BinaryOperation):
-        kernels.compute_operation(grid, operand, field)
+    inner = operand.operand if isinstance(operand, Scan) else operand
+    stencil = not (isinstance(inner, Field) or (isinstance(inner, BinaryOperation) and inner.fixed))      # which evaluator
+    if not isinstance(operand, Scan):
+        (kernels.compute_stencil if stencil else kernels.compute_operation)(grid, operand, field)
         fill_halo_regions(field)
     elif operand.reducing:
-        kernels.reduce_operation(grid, operand.operand, operand.kind, operand.dims, operand.use_metric, operand.absolute, field)
+        (kernels.reduce_stencil if stencil else kernels.reduce_operation)(grid, inner, operand.kind, operand.dims, operand.use_metric,
+                                                                           operand.absolute, field)
     else:
-        kernels.accumulate_operation(grid, operand.operand, operand.dims[0], operand.reverse, operand.use_metric, field)
+        (kernels.accumulate_stencil if stencil else kernels.accumulate_operation)(grid, inner, operand.dims[0], operand.reverse,
+                                                                                   operand.use_metric, field)
     return field
 
 

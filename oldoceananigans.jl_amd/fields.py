@@ -122,6 +122,13 @@ def _add_operations():
         setattr(Field, f"__{name}__", binary(symbol, False))
         setattr(Field, f"__r{name}__", binary(symbol, True))
     Field.__pow__ = power
+
+    def unary(name):
+        def method(self):
+            from .diagnostics import unary_operation
+            return unary_operation(name, self)
+        return method
+    Field.__neg__, Field.__abs__ = unary("neg"), unary("abs")
     for name in ("sum", "mean", "maximum", "minimum"):       # maximum / minimum also take f = None | abs
         setattr(Field, name, reduction(name))
 

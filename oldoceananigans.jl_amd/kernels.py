@@ -73,6 +73,48 @@ def accumulate_operation(grid, operand, dim, reverse, use_metric, out):
                                                    out.data))
 
 
+def _stencil_struct(operand):
+    """the ocn_stencil_operand_t of a Field, an operation (lowered by diagnostics.lower) or an operators.StencilProgram, with what it
+    points to (pass it while both exist)"""
+    from .diagnostics import lower
+    from .operators import StencilProgram, program_array
+    st = operand if isinstance(operand, StencilProgram) else lower(operand)
+    if getattr(st, "_struct", None) is not None:              # the program is packed once; the device pointers are read every time
+        s, keep = st._struct
+        for q, f in enumerate(st.fields):
+            keep[1][q] = f.data
+        return st._struct
+    s = _lib.StencilOperand()
+    arr, s.n = program_array(st.program)
+    s.program = arr
+    ptrs = _ptr_array(st.fields) if st.fields else None
+    locs = (C.c_int * (3 * max(len(st.fields), 1)))(*[c for f in st.fields for c in f.loc_codes])
+    s.args, s.arg_locs, s.nargs = ptrs, locs, len(st.fields)
+    s.loc[:] = [l.code for l in st.location]
+    st._struct = (s, (arr, ptrs, locs))
+    return st._struct
+
+
+def compute_stencil(grid, operand, out):
+    """_compute!(data, operand) of a stencil program -- a KernelFunctionOperation, a Derivative, a UnaryOperation, or ANY operand (a Field,
+    a one-node BinaryOperation) forced through the interpreter: out[i, j, k] = operand[i, j, k] over the interior of `out`"""
+    s, keep = _stencil_struct(operand)
+    _lib.check(_lib.lib().ocn_compute_stencil(grid.handle, C.byref(s), out.data))
+
+
+def reduce_stencil(grid, operand, kind, dims, use_metric, absolute, out):
+    """reduce_operation with the operand as a stencil program: the same kernels, the interpreter as the evaluator"""
+    from .diagnostics import _KIND_CODE, dims_mask
+    s, keep = _stencil_struct(operand)
+    _lib.check(_lib.lib().ocn_reduce_stencil(grid.handle, C.byref(s), _KIND_CODE[kind], dims_mask(dims), int(use_metric), int(absolute), out.data))
+
+
+def accumulate_stencil(grid, operand, dim, reverse, use_metric, out):
+    """accumulate_operation with the operand as a stencil program"""
+    s, keep = _stencil_struct(operand)
+    _lib.check(_lib.lib().ocn_accumulate_stencil(grid.handle, C.byref(s), int(dim) - 1, int(reverse), int(use_metric), out.data))
+
+
 def evaluate_boundary_function(grid, program, loc, side, deps, time, out=None):
     """getbc of a traced boundary function (boundary_functions.py: a list of instruction tuples (op, a, b, c, imm)) at every point of
     `side` ("west" .. "top" or 0..5) for a condition of a field at `loc`: `deps` are Fields with current halos, one per dependency slot;

@@ -30,6 +30,10 @@ def jl_type(t):
         return "Ptr{OcnOperand}"
     if base == "ocn_expr_ins_t":
         return "Ptr{OcnExprIns}"
+    if base == "ocn_stencil_ins_t":
+        return "Ptr{OcnStencilIns}"
+    if base == "ocn_stencil_operand_t":
+        return "Ptr{OcnStencilOperand}"
     if base == "char":
         return "Ptr{Cstring}" if ptr > 1 else "Cstring"
     if base == "void":
@@ -59,7 +63,10 @@ table = [MARK, "",
          "`Vector{Float64}`s the binder fills with the reference's own `GaussianMask` / `PiecewiseLinearMask` / `LinearTarget` at the field's nodes.",
          "`OcnOperand` mirrors `ocn_operand_t` (`op::Cint; a::Ptr{Cdouble}; b::Ptr{Cdouble}; ca::Cdouble; cb::Cdouble; loc_a, loc_b, loc::NTuple{3, Cint}`),",
          "filled from a `BinaryOperation`'s `op`, `a`, `b` and the locations of the three. `OcnExprIns` mirrors `ocn_expr_ins_t`",
-         "(`op::Cint; a::Cint; b::Cint; c::Cint; imm::Cdouble`): one recorded operation of a boundary function.", "", "| entry point | binding |", "|---|---|"] + rows
+         "(`op::Cint; a::Cint; b::Cint; c::Cint; imm::Cdouble`): one recorded operation of a boundary function. `OcnStencilIns` mirrors",
+         "`ocn_stencil_ins_t` (`op, a, b, c, di, dj, dk::Cint; imm::Cdouble`): one recorded operation of a kernel function, and",
+         "`OcnStencilOperand` mirrors `ocn_stencil_operand_t` (`program::Ptr{OcnStencilIns}; n::Cint; args::Ptr{Ptr{Cdouble}};",
+         "arg_locs::Ptr{Cint}; nargs::Cint; loc::NTuple{3, Cint}`), filled from a `KernelFunctionOperation`'s recorded program and arguments.", "", "| entry point | binding |", "|---|---|"] + rows
 p = os.path.join(ROOT, "INTEGRATION.md")
 s = open(p).read()
 if MARK in s:
