@@ -8,6 +8,14 @@ def tanh_faces(Nz, S=1.3, Lz=1.0):
     return -Lz + Lz * (np.tanh(S * (2 * k / Nz - 1)) / np.tanh(S) + 1) / 2
 
 
+def order_one_stokes_drift(ocn):
+    """the UniformStokesDrift of test_gpu_stokes.py, test_gpu_epilogue_dispatch.py and test_gpu_physics_combinations.py. O(1), so the terms
+    matter: ∂z_uˢ = 0.7 e^{z / 0.3}, ∂z_vˢ = -0.4 e^{z / 0.5}, ∂t_uˢ = 0.05 e^{z / 0.3}, ∂t_vˢ = 0.02 (1 + z): all four nonzero at every level"""
+    import math
+    return ocn.UniformStokesDrift(dz_us=lambda z, t: 0.7 * math.exp(z / 0.3), dz_vs=lambda z, t: -0.4 * math.exp(z / 0.5),
+                                  dt_us=lambda z, t: 0.05 * math.exp(z / 0.3), dt_vs=lambda z, t: 0.02 * (1 + z))
+
+
 def random_state(shapes, seed=1234, amp=1.0):
     rng = np.random.default_rng(seed)
     return {name: amp * rng.standard_normal(shape) for name, shape in shapes.items()}

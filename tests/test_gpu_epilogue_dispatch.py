@@ -1,5 +1,5 @@
 """Which tendency epilogue a model runs, for every combination of physics the setters can reach: the selection is checked, not the kernels'
-interiors (those are pinned by test_gpu_parity.py, test_gpu_tilted.py, test_gpu_smagorinsky.py, ...).
+interiors (those are pinned by test_gpu_parity.py, test_gpu_tilted.py, test_gpu_smagorinsky.py, test_gpu_stokes.py, ...).
 
 One model per (ntracers, closure) on the (Periodic, Periodic, Bounded) 8 x 6 x 10 tanh-stretched grid of test_gpu_tilted.py with
 helpers.smooth_state. Within the model the setters walk coriolis in {nothing, FPlane(0.7), ConstantCartesianCoriolis(0.3, -1.1, 0.7)} x
@@ -11,13 +11,35 @@ kernels, which the epilogue's dispatch does not touch) -- and
   * "epilogue_march_active", "coriolis_kind", "tilted_gravity" and "vertically_implicit" answer the rule of include/ocn_mi355x.h: marching
     iff there is a closure, it is not vertically implicit, ntracers <= 2, no ConstantCartesianCoriolis and no tilted buoyancy;
   * G differs from the G of the same state without physics whenever a term is on (an epilogue that did nothing fails).
-No combination is exempt: every one is bit-identical across the three paths."""
+
+The STOKES axis. At the same combination ocn_model_set_stokes_drift switches helpers.order_one_stokes_drift on ("stokes_drift" 1,
+"stokes_path" 2, "epilogue_march_active" 0 whatever the closure): the default path is then the STOKES instantiation of the per-value
+epilogue, and
+  * Gu, Gv, Gw are np.array_equal over the whole parent array to stokes_reference.add_stokes_drift applied to the drift-free tendencies of
+    the comparison above -- (G + curl) + ∂t on a tendency that holds everything up to the closure term, the order of
+    nonhydrostatic_tendency_kernel_functions.jl:99-102 -- and every tracer tendency keeps the bits of its drift-free one;
+  * fused_epilogue = 0 ("stokes_path" 1: the stand-alone physics kernels, then stokes_drift_kernel) gives the same bits;
+  * Gu, Gv, Gw differ from the drift-free ones (an epilogue that skipped the Stokes terms fails);
+  * ocn_model_set_stokes_drift(model, 0, NULLs) brings back the old answer of "epilogue_march_active" and the drift-free bits.
+
+The substep that rides along (a.Gm, a.Un are run-time arguments: an update_state! alone never reaches that code). At the second and the
+last entry of every Coriolis walk -- each (gravity, buoyancy) pair once with a Coriolis and once without -- one RK3 step is taken from the
+saved state (fields and pressure restored, update_state!) by the model on its default path ("fuse_substep_active" 1) and by a twin that
+got the same setters and has fused_epilogue = 0 ("fuse_substep_active" 0): fields, Gⁿ, G⁻ and pNHS are np.array_equal and finite. With the drift on at every such entry, with the drift off
+where the plan marches; scalar_vi included (its implicit solve follows the substep on both paths).
+
+No combination is exempt: every one is bit-identical across the paths, with and without the drift. The walk launches all 60 STOKES
+instantiations, 59 of the 60 without the terms (the all-off one runs only for a model that has Flux conditions and nothing else:
+test_gpu_boundary_function.py) and the 28 marching ones a model can reach -- the other 8 are BUOY or CLO 3 without a tracer (DESIGN.md 13
+derives the counts from epilogue_slot and epilogue_march_slot)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from helpers import smooth_state, tanh_faces
+from helpers import order_one_stokes_drift, smooth_state, tanh_faces
+import stokes_reference as S
+import vertically_implicit_reference as R
 
 pytestmark = pytest.mark.gpu
 
@@ -92,26 +114,78 @@ def _same(a, b):
     return all(np.array_equal(x, y) for x, y in zip(a, b))
 
 
+def _set_drift(L, model, tables):
+    dp = C.POINTER(C.c_double)
+    args = [t.ctypes.data_as(dp) for t in tables] if tables is not None else [None] * 6
+    assert L.ocn_model_set_stokes_drift(model.handle, int(tables is not None), *args) == 0
+
+
+def _state_names(model):
+    return ["u", "v", "w"] + ["c%d" % t for t in range(len(model.tracer_names))]
+
+
+def _save(model):
+    """the prognostic fields and the pressure: whole parent arrays"""
+    return {n: model._field(n).parent() for n in _state_names(model) + ["p"]}
+
+
+def _step_from(ocn, model, saved, dt):
+    """one RK3 step from the saved state -> fields, Gⁿ, G⁻, pNHS"""
+    for n, a in saved.items():
+        model._field(n).set_parent(a)
+    ocn.update_state(model, True)
+    ocn.time_step(model, dt)
+    names = _state_names(model)
+    return [model._field(pre + n).parent() for pre in ("", "G", "M") for n in names] + [model._field("p").parent()]
+
+
+def _stepped_the_same(ocn, model, twin, saved, dt, combo):
+    """the default path, where the substep of stages 2 and 3 rides in the epilogue, against fused_epilogue = 0, where it is its own launch.
+    Two models in lockstep, not one model stepped twice: on a Bounded z the pressure solver re-reads its previous solution in the singular
+    column (ocn_poisson.h), which shifts the next one by round-off -- the two models have solved the same systems in the same order"""
+    assert model.get_option("fuse_substep_active") == 1 and twin.get_option("fuse_substep_active") == 0, combo
+    assert model.get_option("stokes_path") == 2 * model.get_option("stokes_drift") and twin.get_option("stokes_path") == twin.get_option("stokes_drift"), combo
+    fused, plain = _step_from(ocn, model, saved, dt), _step_from(ocn, twin, saved, dt)
+    assert all(np.all(np.isfinite(a)) for a in fused + plain), combo
+    worst = max(float(np.abs(a - b).max()) for a, b in zip(fused, plain))
+    assert _same(fused, plain), (combo, worst)
+    # the step moved the fields: the comparison is not one of untouched arrays
+    assert not np.array_equal(fused[0], saved["u"]), combo
+    for n, a in saved.items():
+        model._field(n).set_parent(a)
+
+
 @pytest.mark.parametrize("closure", CLOSURES)
 @pytest.mark.parametrize("ntr", [0, 1, 2, 3])
 def test_every_physics_combination_takes_the_same_bits_on_all_three_paths(ocn, arch, ntr, closure):
     from oldoceananigans_jl_amd import _lib
     L = _lib.lib()
     grid, model = _model(ocn, arch, ntr)
+    _, twin = _model(ocn, arch, ntr)              # the same setters in lockstep, fused_epilogue = 0 throughout: it only steps (_stepped_the_same)
+    twin.set_option("fused_epilogue", 0)
+    both = (model, twin)
     bare = _tendencies(ocn, model)
     assert all(np.all(np.isfinite(g)) for g in bare)
-    _set_closure(L, model, closure, ntr)
+    for m in both:
+        _set_closure(L, m, closure, ntr)
     has_closure, vi = closure != "none", closure == "scalar_vi"
+    metrics = R.Metrics.of_grid(grid)
+    tables = order_one_stokes_drift(ocn).tables(grid)
+    assert all(np.all(t != 0.0) and 0.01 < np.abs(t).max() < 1.0 for t in tables)          # all of ∂z_uˢ, ∂z_vˢ, ∂t_uˢ, ∂t_vˢ act at every level
+    saved, dt = _save(model), 0.05 / grid.Nx
     visited, coriolis, walk = set(), 0, 0
     for tilt in (0, 1):
-        if tilt:
-            assert L.ocn_model_set_gravity_unit_vector(model.handle, 1, *GVEC) == 0
-        else:
-            assert L.ocn_model_set_gravity_unit_vector(model.handle, 0, 0.0, 0.0, 0.0) == 0
+        for m in both:
+            if tilt:
+                assert L.ocn_model_set_gravity_unit_vector(m.handle, 1, *GVEC) == 0
+            else:
+                assert L.ocn_model_set_gravity_unit_vector(m.handle, 0, 0.0, 0.0, 0.0) == 0
         for buoyancy in (0, 1, 2)[:min(ntr, 2) + 1]:
-            _set_buoyancy(L, model, buoyancy)
-            for kind in WALKS[walk % 2]:
-                _set_coriolis(L, model, kind, coriolis)
+            for m in both:
+                _set_buoyancy(L, m, buoyancy)
+            for entry, kind in enumerate(WALKS[walk % 2]):
+                for m in both:
+                    _set_coriolis(L, m, kind, coriolis)
                 visited.add((coriolis, kind))
                 coriolis = kind
                 combo = (ntr, closure, "tilt" if tilt else "vertical", buoyancy, coriolis)
@@ -141,10 +215,40 @@ def test_every_physics_combination_takes_the_same_bits_on_all_three_paths(ocn, a
                     assert changed[0] and changed[1] and changed[2] == (coriolis == 2) and not any(changed[3:]), combo
                 else:
                     assert not any(changed), combo
+                stepping = entry in (1, 3)
+                if stepping and march:                # the marching epilogue with the substep riding along
+                    _stepped_the_same(ocn, model, twin, saved, dt, combo + ("no drift",))
+                # the STOKES instantiation of the same coordinates: G == the restatement's (G0 + curl) + ∂t, bit for bit
+                U = {n: model._field(n).parent() for n in "uvw"}
+                for m in both:
+                    _set_drift(L, m, tables)
+                got = {k: model.get_option(k) for k in ("stokes_drift", "stokes_path", "epilogue_march_active")}
+                assert got == {"stokes_drift": 1, "stokes_path": 2, "epilogue_march_active": 0}, combo
+                with_drift = _tendencies(ocn, model)
+                model.set_option("fused_epilogue", 0)
+                assert model.get_option("stokes_path") == 1, combo
+                drift_standalone = _tendencies(ocn, model)
+                model.set_option("fused_epilogue", 1)
+                want = S.add_stokes_drift(metrics, tables, U, {n: default[q].copy(order="F") for q, n in enumerate("uvw")})
+                assert all(np.all(np.isfinite(g)) for g in with_drift + drift_standalone), combo
+                for q, n in enumerate("uvw"):
+                    assert np.array_equal(with_drift[q], want[n]), (combo, "G" + n, float(np.abs(with_drift[q] - want[n]).max()))
+                    assert not np.array_equal(with_drift[q], default[q]), (combo, "G" + n)
+                assert _same(with_drift[3:], default[3:]), combo
+                worst = max(float(np.abs(a - b).max()) for a, b in zip(with_drift, drift_standalone))
+                assert _same(with_drift, drift_standalone), (combo, worst)
+                if stepping:
+                    _stepped_the_same(ocn, model, twin, saved, dt, combo + ("drift",))
+                for m in both:
+                    _set_drift(L, m, None)
+                got = {k: model.get_option(k) for k in ("stokes_drift", "stokes_path", "epilogue_march_active")}
+                assert got == {"stokes_drift": 0, "stokes_path": 0, "epilogue_march_active": int(march)}, combo
+                assert _same(_tendencies(ocn, model), default), combo
             walk += 1
     # every replacement of one Coriolis by another (or by nothing) was made (without tracers: one walk per gravity vector, both kinds)
     assert visited == {(0, 1), (1, 2), (2, 1), (1, 0), (0, 2), (2, 0)}
     model.close()
+    twin.close()
 
 
 def test_set_closure_replaces_an_eddy_viscosity_closure(ocn, arch):

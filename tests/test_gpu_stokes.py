@@ -14,7 +14,7 @@ import math
 import numpy as np
 import pytest
 
-from helpers import rel_err, smooth_state, tanh_faces
+from helpers import order_one_stokes_drift, rel_err, smooth_state, tanh_faces
 import stokes_reference as S
 import vertically_implicit_reference as R
 
@@ -29,12 +29,6 @@ CASES = {
     "ppp": dict(size=(8, 8, 8), topo=("Periodic", "Periodic", "Periodic"), stretched=False),
 }
 TRIMMED = (2, 7, 2, 5, 3, 9)                              # a launch range on ppb_stretched
-
-
-def _drift(ocn):
-    """O(1), so the terms matter: ∂z_uˢ = 0.7 e^{z / 0.3}, ∂z_vˢ = -0.4 e^{z / 0.5}, ∂t_uˢ = 0.05 e^{z / 0.3}, ∂t_vˢ = 0.02 (1 + z)"""
-    return ocn.UniformStokesDrift(dz_us=lambda z, t: 0.7 * math.exp(z / 0.3), dz_vs=lambda z, t: -0.4 * math.exp(z / 0.5),
-                                  dt_us=lambda z, t: 0.05 * math.exp(z / 0.3), dt_vs=lambda z, t: 0.02 * (1 + z))
 
 
 def _grids(ocn, oracle, arch, name):
@@ -76,7 +70,7 @@ def test_raw_kernel_is_the_restatement(ocn, arch, name):
     Periodic one), the rest of the parent arrays keeping their bits; on ppb_stretched once more over a launch range"""
     grid, _ = _grids(ocn, None, arch, name)
     m = R.Metrics.of_grid(grid)
-    drift = _drift(ocn)
+    drift = order_one_stokes_drift(ocn)
     tables = drift.tables(grid)
     U, P = _smooth_fields(ocn, grid, 3, "uvw")
     for rng in [None] + ([TRIMMED] if name == "ppb_stretched" else []):
@@ -101,7 +95,7 @@ def test_uniform_velocities_give_exact_products_on_the_device(ocn, arch):
     the restatement to the same)"""
     grid, _ = _grids(ocn, None, arch, "ppb_stretched")
     m = R.Metrics.of_grid(grid)
-    full = _drift(ocn)
+    full = order_one_stokes_drift(ocn)
     dzu_c, dzu_f, dzv_c, dzv_f, dtu_c, dtv_c = full.tables(grid)
     make = {"u": ocn.XFaceField, "v": ocn.YFaceField, "w": ocn.ZFaceField}
 
@@ -146,7 +140,7 @@ STEPS = 3
 def _model_pair(ocn, oracle, arch, case, options=None, yardstick=True, drift="default", closure=None):
     name, timestepper, langmuir, forced, background = MODEL_CASES[case]
     grid, g_cpu = _grids(ocn, oracle if yardstick else None, arch, name)
-    drift = _drift(ocn) if drift == "default" else drift
+    drift = order_one_stokes_drift(ocn) if drift == "default" else drift
     forcing = 0.3 * np.random.default_rng(4).standard_normal(grid.interior_size((ocn.Face, ocn.Center, ocn.Center))) if forced else None
     bg = {"b": lambda x, y, z: 0.8 * z + 0 * x + 0 * y} if background else None
     if closure is None and langmuir:
@@ -266,7 +260,7 @@ def test_setting_and_clearing_the_drift_on_a_live_model(ocn, arch):
         assert np.all(np.isfinite(a)) and np.array_equal(a, b), (n, np.abs(a - b).max())
     # set between steps: a second call replaces the first whole -- the full drift, then ∂t_uˢ alone == a model that only ever got ∂t_uˢ
     dp = C.POINTER(C.c_double)
-    tables = _drift(ocn).tables(grid)
+    tables = order_one_stokes_drift(ocn).tables(grid)
     _, only, _, _ = _model_pair(ocn, None, arch, "langmuir_rk3", yardstick=False, closure=amd(), drift=None)
     ocn.time_step(only, dt)
     assert L.ocn_model_set_stokes_drift(model.handle, 1, *[t.ctypes.data_as(dp) for t in tables]) == 0
@@ -383,7 +377,7 @@ def test_setter_refusals_leave_the_model_untouched(ocn, arch):
     assert L.ocn_model_set_stokes_drift(part.handle, 1, *none) == -2 and b"partitioned" in L.ocn_last_error()
     assert part.get_option("stokes_drift") == 0
     with pytest.raises(NotImplementedError, match="partitioned"):
-        dist.LibraryDistributedModel(grid=grid, tracers=(), stokes_drift=_drift(ocn))
+        dist.LibraryDistributedModel(grid=grid, tracers=(), stokes_drift=order_one_stokes_drift(ocn))
     part.close()
     ctx.close()
     # a live drift survives a refused ... there is no refusable call on a valid single-GPU model with a z direction: the raw kernel's instead
