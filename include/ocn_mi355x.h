@@ -1002,6 +1002,38 @@ int ocn_accumulate_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand
  * ocn_init. OCN_EINVAL for the program errors above that need no grid (slot limit included). */
 int ocn_stencil_plan(const ocn_stencil_ins_t *program, int n, int nargs, int *slot_of_value, int *nslots);
 
+/* ---------------------------------------------------------------- time averages (OutputWriters/windowed_time_average.jl) -------------
+ * accumulate_result! (:216-230): result = (result * T_previous + integrand * dt) / T_current, element by element -- two IEEE multiplies,
+ * one add, one correctly rounded divide, in that association, no contraction. The integrand is never stored: each entry point below is
+ * its plain counterpart above (same operand rules, same kernels, same splits, chunks and combine orders, so the integrand has the bits
+ * the counterpart would have written) with the fold at the store, in the thread that formed the value. `result` is what `out` is for
+ * the counterpart and must not be one of the operand's arrays. The three times travel by value: no device-to-host copy, no
+ * stream synchronisation.
+ * first != 0: the first sample of a window, where advance_time_average! (:236-249) has just zeroed the result and T_previous is 0 --
+ * `result` is neither read nor cleared beforehand and becomes (0.0 * 0.0 + integrand * dt) / T_current, the reference's bits: an
+ * integrand of -0.0 gives +0.0, and in general the value is not the integrand.
+ * ocn_time_average_operation with OCN_OP_IDENTITY (a plain field) folds the WHOLE parent array, halos included, as `@.` on
+ * parent(result) does; every other operand is folded over the interior of its location and leaves the halos of `result` alone.
+ * OCN_EINVAL before any launch: a NULL result or fold, a non-finite time, T_current <= 0, T_previous < 0, first with T_previous != 0,
+ * and every operand error of the counterpart. Connected topologies answer OCN_ENOTSUP. */
+typedef struct {
+    double T_previous, dt, T_current;
+    int first;
+} ocn_time_fold_t;
+int ocn_time_average_operation(ocn_grid_t grid, const ocn_operand_t *operand, const ocn_time_fold_t *fold, double *result);
+/* the fold of n doubles: a materialised integrand of any shape -- a reduced field, which has no location code for an operand -- over its
+ * whole parent array; `integrand` and `result` are device arrays of n elements */
+int ocn_time_average_parent(const double *integrand, size_t n, const ocn_time_fold_t *fold, double *result);
+int ocn_time_average_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, const ocn_time_fold_t *fold, double *result);
+int ocn_time_average_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
+                                      const ocn_time_fold_t *fold, double *result);
+int ocn_time_average_reduce_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
+                                    const ocn_time_fold_t *fold, double *result);
+int ocn_time_average_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric,
+                                          const ocn_time_fold_t *fold, double *result);
+int ocn_time_average_accumulate_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int dim, int reverse, int use_metric,
+                                        const ocn_time_fold_t *fold, double *result);
+
 #ifdef __cplusplus
 }
 #endif

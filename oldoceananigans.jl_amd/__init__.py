@@ -29,8 +29,9 @@ from .simulations import (CFL, AdvectiveCFL, DiffusiveCFL, Callback, IterationIn
                           stop_time_exceeded, wall_time_limit_exceeded)
 from .stokes_drifts import StokesDrift, UniformStokesDrift
 from .particles import DroguedParticleDynamics, LagrangianParticles, no_dynamics
-from . import diagnostics, kernels, operators
+from . import diagnostics, kernels, operators, time_averages, units
 from .diagnostics import (Accumulation, Average, BinaryOperation, CumulativeIntegral, Derivative, FieldStatus, Integral, KernelFunctionOperation,
                           Reduction, UnaryOperation, at, compute, compute_at, dx, dy, dz)
+from .time_averages import AveragedTimeInterval, WindowedTimeAverage, advance_time_average, prettytime, run_diagnostic
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -63,6 +63,11 @@ class StencilOperand(C.Structure):
                 ("nargs", C.c_int), ("loc", C.c_int * 3)]
 
 
+class TimeFold(C.Structure):
+    """ocn_time_fold_t"""
+    _fields_ = [("T_previous", C.c_double), ("dt", C.c_double), ("T_current", C.c_double), ("first", C.c_int)]
+
+
 class Transport(C.Structure):
     """ocn_transport_t: caller-supplied collectives (device addresses as integers)"""
     EXCHANGE_START = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -113,6 +118,13 @@ SYMBOLS = {
     "ocn_reduce_stencil": (C.c_int, [_vp, C.POINTER(StencilOperand), C.c_int, C.c_int, C.c_int, C.c_int, _vp]),
     "ocn_accumulate_stencil": (C.c_int, [_vp, C.POINTER(StencilOperand), C.c_int, C.c_int, C.c_int, _vp]),
     "ocn_stencil_plan": (C.c_int, [C.POINTER(StencilIns), C.c_int, C.c_int, _ip, _ip]),
+    "ocn_time_average_operation": (C.c_int, [_vp, C.POINTER(Operand), C.POINTER(TimeFold), _vp]),
+    "ocn_time_average_parent": (C.c_int, [_vp, C.c_size_t, C.POINTER(TimeFold), _vp]),
+    "ocn_time_average_stencil": (C.c_int, [_vp, C.POINTER(StencilOperand), C.POINTER(TimeFold), _vp]),
+    "ocn_time_average_reduce_operation": (C.c_int, [_vp, C.POINTER(Operand), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TimeFold), _vp]),
+    "ocn_time_average_reduce_stencil": (C.c_int, [_vp, C.POINTER(StencilOperand), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(TimeFold), _vp]),
+    "ocn_time_average_accumulate_operation": (C.c_int, [_vp, C.POINTER(Operand), C.c_int, C.c_int, C.c_int, C.POINTER(TimeFold), _vp]),
+    "ocn_time_average_accumulate_stencil": (C.c_int, [_vp, C.POINTER(StencilOperand), C.c_int, C.c_int, C.c_int, C.POINTER(TimeFold), _vp]),
     "ocn_init": (C.c_int, [C.c_int]),
     "ocn_device_count": (C.c_int, [_ip]),
     "ocn_sync": (C.c_int, []),

@@ -1212,33 +1212,96 @@ extern "C" int ocn_evaluate_forcing_function(ocn_grid_t grid, const ocn_expr_ins
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds))); \
     } while (0)
 
-template <class O>
-static int dg_compute(ocn_grid_s *grid, const O &o, const int n[3], const DgOut &out, size_t lds) {
-    DG_ALLOW_LDS(dg_compute_kernel<O>, lds);
-    hipLaunchKernelGGL(dg_compute_kernel<O>, grid3(n[0], n[1], n[2], BLK), BLK, lds, g_stream, o, out, n[0], n[1]);
+// The launches are templates on where they write as well: W = DgOut, the plain store, or DgOutFold, the running time average
+// (ocn_time_average_*). dg_with_out hands `launch` the one the call asks for: `fold` is NULL for the plain entry points.
+static int dg_check_fold(const ocn_time_fold_t *fold) {
+    if (!fold) return fail(OCN_EINVAL, "NULL argument");
+    if (!std::isfinite(fold->T_previous) || !std::isfinite(fold->dt) || !std::isfinite(fold->T_current))
+        return fail(OCN_EINVAL, "time fold: T_previous = %g, dt = %g, T_current = %g must be finite", fold->T_previous, fold->dt, fold->T_current);
+    if (fold->T_current <= 0) return fail(OCN_EINVAL, "time fold: T_current = %g must be positive", fold->T_current);
+    if (fold->T_previous < 0) return fail(OCN_EINVAL, "time fold: T_previous = %g must not be negative", fold->T_previous);
+    if (fold->first && fold->T_previous != 0) return fail(OCN_EINVAL, "time fold: the first sample of a window has T_previous = 0, not %g", fold->T_previous);
+    return OCN_OK;
+}
+
+static DgOutFold dg_fold_out(const DgOut &w, const ocn_time_fold_t &fold) {
+    DgOutFold f = {};
+    static_cast<DgOut &>(f) = w;
+    f.Tp = fold.T_previous;
+    f.dt = fold.dt;
+    f.Tc = fold.T_current;
+    f.first = fold.first != 0;
+    return f;
+}
+
+template <class F> static int dg_with_out(const DgOut &w, const ocn_time_fold_t *fold, F &&launch) {
+    return fold ? launch(dg_fold_out(w, *fold)) : launch(w);
+}
+
+template <class O, class W>
+static int dg_compute(ocn_grid_s *grid, const O &o, const int n[3], const W &out, size_t lds) {
+    DG_ALLOW_LDS((dg_compute_kernel<O, W>), lds);
+    hipLaunchKernelGGL((dg_compute_kernel<O, W>), grid3(n[0], n[1], n[2], BLK), BLK, lds, g_stream, o, out, n[0], n[1]);
     KERNEL_CHECK();
     return OCN_OK;
 }
 
-extern "C" int ocn_compute_operation(ocn_grid_t grid, const ocn_operand_t *operand, double *out) {
-    NEED_INIT();
-    if (!out) return fail(OCN_EINVAL, "NULL argument");
+static int dg_compute_operation(ocn_grid_t grid, const ocn_operand_t *operand, const ocn_time_fold_t *fold, double *out) {
     DgOperand o;
     int rc = dg_make_operand(grid, operand, &o);
     if (rc) return rc;
     int n[3];
     dg_interior_size(grid->d, operand->loc, n);
-    return dg_compute(grid, o, n, dg_make_out(grid->d, operand->loc, 0, out), 0);
+    if (fold && operand->op == OCN_OP_IDENTITY) {
+        // a plain field: the whole parent array of the result, halos included (windowed_time_average.jl:224 broadcasts over parent)
+        int P[3];
+        parent_size(grid->d, operand->loc, P);
+        const long np = (long)P[0] * P[1] * P[2];
+        DgOut whole = {};
+        whole.p = out;
+        hipLaunchKernelGGL(dg_fold_parent_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, g_stream, operand->a, dg_fold_out(whole, *fold), np);
+        KERNEL_CHECK();
+        return OCN_OK;
+    }
+    return dg_with_out(dg_make_out(grid->d, operand->loc, 0, out), fold, [&](const auto &w) { return dg_compute(grid, o, n, w, 0); });
 }
 
-template <int KIND, class O>
-static int dg_reduce(ocn_grid_s *grid, const O &o, const int n[3], int mask, const DgOut &out, size_t lds) {
+extern "C" int ocn_compute_operation(ocn_grid_t grid, const ocn_operand_t *operand, double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    return dg_compute_operation(grid, operand, nullptr, out);
+}
+
+extern "C" int ocn_time_average_operation(ocn_grid_t grid, const ocn_operand_t *operand, const ocn_time_fold_t *fold, double *result) {
+    NEED_INIT();
+    if (!result) return fail(OCN_EINVAL, "NULL argument");
+    const int rc = dg_check_fold(fold);
+    if (rc) return rc;
+    return dg_compute_operation(grid, operand, fold, result);
+}
+
+// a field of any shape as the integrand (a reduced field has no location code): n doubles of its parent array
+extern "C" int ocn_time_average_parent(const double *integrand, size_t n, const ocn_time_fold_t *fold, double *result) {
+    NEED_INIT();
+    if (!integrand || !result) return fail(OCN_EINVAL, "NULL argument");
+    const int rc = dg_check_fold(fold);
+    if (rc) return rc;
+    if (n == 0 || n > 0x7fffffffL * 256L) return fail(OCN_EINVAL, "n = %zu: between 1 and 2^39", n);
+    DgOut whole = {};
+    whole.p = result;
+    hipLaunchKernelGGL(dg_fold_parent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, integrand, dg_fold_out(whole, *fold), (long)n);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+template <int KIND, class O, class W>
+static int dg_reduce(ocn_grid_s *grid, const O &o, const int n[3], int mask, const W &out, size_t lds) {
     const bool rj = mask & 2, rk = mask & 4;
     const double count = (double)((mask & 1) ? n[0] : 1) * (rj ? n[1] : 1) * (rk ? n[2] : 1);
     const int e1 = rj ? 1 : n[1], e2 = rk ? 1 : n[2];
     if (!(mask & 1)) {
-        DG_ALLOW_LDS((dg_reduce_cols_kernel<KIND, O>), lds);
-        hipLaunchKernelGGL((dg_reduce_cols_kernel<KIND, O>), grid3(n[0], e1, e2, BLK), BLK, lds, g_stream, o, out, n[0], e1, rj ? n[1] : 1, rk ? n[2] : 1, count);
+        DG_ALLOW_LDS((dg_reduce_cols_kernel<KIND, O, W>), lds);
+        hipLaunchKernelGGL((dg_reduce_cols_kernel<KIND, O, W>), grid3(n[0], e1, e2, BLK), BLK, lds, g_stream, o, out, n[0], e1, rj ? n[1] : 1, rk ? n[2] : 1, count);
         KERNEL_CHECK();
         return OCN_OK;
     }
@@ -1257,19 +1320,19 @@ static int dg_reduce(ocn_grid_s *grid, const O &o, const int n[3], int mask, con
         HIP_TRY(dev_alloc((void **)&grid->diag_slab, (size_t)(2 * nslab) * sizeof(double)));
         grid->diag_slab_n = (size_t)(2 * nslab);
     }
-    DG_ALLOW_LDS((dg_reduce_rows_kernel<KIND, O>), lds);
-    hipLaunchKernelGGL((dg_reduce_rows_kernel<KIND, O>), dim3((unsigned)nslab), dim3(DG_THREADS), lds, g_stream, o, R, out, grid->diag_slab, nslab);
+    DG_ALLOW_LDS((dg_reduce_rows_kernel<KIND, O, W>), lds);
+    hipLaunchKernelGGL((dg_reduce_rows_kernel<KIND, O, W>), dim3((unsigned)nslab), dim3(DG_THREADS), lds, g_stream, o, R, out, grid->diag_slab, nslab);
     KERNEL_CHECK();
     if (R.nch > 1) {
-        hipLaunchKernelGGL(dg_combine_kernel<KIND>, dim3((unsigned)nout), dim3(DG_THREADS), 0, g_stream, R, out, grid->diag_slab, nslab,
+        hipLaunchKernelGGL((dg_combine_kernel<KIND, W>), dim3((unsigned)nout), dim3(DG_THREADS), 0, g_stream, R, out, grid->diag_slab, nslab,
                            (int)(KIND == OCN_REDUCE_AVERAGE && o.mmode != 0));
         KERNEL_CHECK();
     }
     return OCN_OK;
 }
 
-template <class O>
-static int dg_reduce_kind(ocn_grid_s *grid, const O &o, int kind, const int n[3], int mask, const DgOut &out, size_t lds) {
+template <class O, class W>
+static int dg_reduce_kind(ocn_grid_s *grid, const O &o, int kind, const int n[3], int mask, const W &out, size_t lds) {
     switch (kind) {
     case OCN_REDUCE_SUM:     return dg_reduce<OCN_REDUCE_SUM>(grid, o, n, mask, out, lds);
     case OCN_REDUCE_MAXIMUM: return dg_reduce<OCN_REDUCE_MAXIMUM>(grid, o, n, mask, out, lds);
@@ -1279,29 +1342,27 @@ static int dg_reduce_kind(ocn_grid_s *grid, const O &o, int kind, const int n[3]
 }
 
 // cumsum along direction dim of the operand's interior n
-template <class O>
-static int dg_accumulate(const O &o, const int n[3], int dim, int reverse, const DgOut &w, size_t lds) {
+template <class O, class W>
+static int dg_accumulate(const O &o, const int n[3], int dim, int reverse, const W &w, size_t lds) {
     const dim3 blk(64, 4, 1);
     if (dim == 0) {
         const long nrows = (long)n[1] * n[2];
-        DG_ALLOW_LDS(dg_accumulate_rows_kernel<O>, lds);
-        hipLaunchKernelGGL(dg_accumulate_rows_kernel<O>, dim3((unsigned)((nrows + 3) / 4)), dim3(DG_THREADS), lds, g_stream, o, w, n[0], n[1], nrows,
+        DG_ALLOW_LDS((dg_accumulate_rows_kernel<O, W>), lds);
+        hipLaunchKernelGGL((dg_accumulate_rows_kernel<O, W>), dim3((unsigned)((nrows + 3) / 4)), dim3(DG_THREADS), lds, g_stream, o, w, n[0], n[1], nrows,
                            reverse != 0);
     } else if (dim == 1) {
-        DG_ALLOW_LDS((dg_accumulate_cols_kernel<1, O>), lds);
-        hipLaunchKernelGGL((dg_accumulate_cols_kernel<1, O>), dim3((n[0] + 63) / 64, (n[2] + 3) / 4), blk, lds, g_stream, o, w, n[0], n[2], n[1], reverse != 0);
+        DG_ALLOW_LDS((dg_accumulate_cols_kernel<1, O, W>), lds);
+        hipLaunchKernelGGL((dg_accumulate_cols_kernel<1, O, W>), dim3((n[0] + 63) / 64, (n[2] + 3) / 4), blk, lds, g_stream, o, w, n[0], n[2], n[1], reverse != 0);
     } else {
-        DG_ALLOW_LDS((dg_accumulate_cols_kernel<2, O>), lds);
-        hipLaunchKernelGGL((dg_accumulate_cols_kernel<2, O>), dim3((n[0] + 63) / 64, (n[1] + 3) / 4), blk, lds, g_stream, o, w, n[0], n[1], n[2], reverse != 0);
+        DG_ALLOW_LDS((dg_accumulate_cols_kernel<2, O, W>), lds);
+        hipLaunchKernelGGL((dg_accumulate_cols_kernel<2, O, W>), dim3((n[0] + 63) / 64, (n[1] + 3) / 4), blk, lds, g_stream, o, w, n[0], n[1], n[2], reverse != 0);
     }
     KERNEL_CHECK();
     return OCN_OK;
 }
 
-extern "C" int ocn_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
-                                    double *out) {
-    NEED_INIT();
-    if (!out) return fail(OCN_EINVAL, "NULL argument");
+static int dg_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
+                               const ocn_time_fold_t *fold, double *out) {
     if (kind < OCN_REDUCE_SUM || kind > OCN_REDUCE_AVERAGE) return fail(OCN_EINVAL, "unknown reduction kind %d", kind);
     if (dims_mask < 1 || dims_mask > 7) return fail(OCN_EINVAL, "dims_mask %d: bits 0..2 name the reduced directions, at least one", dims_mask);
     if (use_metric && (kind == OCN_REDUCE_MAXIMUM || kind == OCN_REDUCE_MINIMUM)) return fail(OCN_EINVAL, "maximum and minimum take no metric");
@@ -1312,13 +1373,28 @@ extern "C" int ocn_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operan
     if (use_metric) dg_set_metric(grid->d, dims_mask, &o);
     int n[3];
     dg_interior_size(grid->d, operand->loc, n);
-    const DgOut w = dg_make_out(grid->d, operand->loc, dims_mask, out);
-    return dg_reduce_kind(grid, o, kind, n, dims_mask, w, 0);
+    return dg_with_out(dg_make_out(grid->d, operand->loc, dims_mask, out), fold,
+                       [&](const auto &w) { return dg_reduce_kind(grid, o, kind, n, dims_mask, w, 0); });
 }
 
-extern "C" int ocn_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric, double *out) {
+extern "C" int ocn_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
+                                    double *out) {
     NEED_INIT();
     if (!out) return fail(OCN_EINVAL, "NULL argument");
+    return dg_reduce_operation(grid, operand, kind, dims_mask, use_metric, absolute, nullptr, out);
+}
+
+extern "C" int ocn_time_average_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operand, int kind, int dims_mask, int use_metric,
+                                                 int absolute, const ocn_time_fold_t *fold, double *result) {
+    NEED_INIT();
+    if (!result) return fail(OCN_EINVAL, "NULL argument");
+    const int rc = dg_check_fold(fold);
+    if (rc) return rc;
+    return dg_reduce_operation(grid, operand, kind, dims_mask, use_metric, absolute, fold, result);
+}
+
+static int dg_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric,
+                                   const ocn_time_fold_t *fold, double *out) {
     if (dim < 0 || dim > 2) return fail(OCN_EINVAL, "dim %d: 0 (x), 1 (y) or 2 (z)", dim);
     DgOperand o;
     int rc = dg_make_operand(grid, operand, &o);
@@ -1326,7 +1402,22 @@ extern "C" int ocn_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *op
     if (use_metric) dg_set_metric(grid->d, 1 << dim, &o);
     int n[3];
     dg_interior_size(grid->d, operand->loc, n);
-    return dg_accumulate(o, n, dim, reverse, dg_make_out(grid->d, operand->loc, 0, out), 0);
+    return dg_with_out(dg_make_out(grid->d, operand->loc, 0, out), fold, [&](const auto &w) { return dg_accumulate(o, n, dim, reverse, w, 0); });
+}
+
+extern "C" int ocn_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric, double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    return dg_accumulate_operation(grid, operand, dim, reverse, use_metric, nullptr, out);
+}
+
+extern "C" int ocn_time_average_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric,
+                                                     const ocn_time_fold_t *fold, double *result) {
+    NEED_INIT();
+    if (!result) return fail(OCN_EINVAL, "NULL argument");
+    const int rc = dg_check_fold(fold);
+    if (rc) return rc;
+    return dg_accumulate_operation(grid, operand, dim, reverse, use_metric, fold, result);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1537,62 +1628,107 @@ template <class O> static void dg_set_metric_of(const DGrid &g, int mask, O *o) 
 #endif
 static size_t st_lds_bytes(const StLowered &S) { return sizeof(double) * DG_THREADS * (size_t)std::max(S.nslots, DG_ST_MIN_LDS_SLOTS); }
 
-extern "C" int ocn_compute_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, double *out) {
-    NEED_INIT();
-    if (!out) return fail(OCN_EINVAL, "NULL argument");
+static int st_compute(ocn_grid_t grid, const ocn_stencil_operand_t *operand, const ocn_time_fold_t *fold, double *out) {
     StLowered S;
     const int rc = dg_lower_stencil(grid, operand, &S);
     if (rc) return rc;
     int n[3];
     dg_interior_size(grid->d, operand->loc, n);
-    const DgOut w = dg_make_out(grid->d, operand->loc, 0, out);
-    return S.arith ? dg_compute(grid, dg_stencil_operand<true>(grid, operand, S), n, w, st_lds_bytes(S))
-                   : dg_compute(grid, dg_stencil_operand<false>(grid, operand, S), n, w, st_lds_bytes(S));
+    return dg_with_out(dg_make_out(grid->d, operand->loc, 0, out), fold, [&](const auto &w) {
+        return S.arith ? dg_compute(grid, dg_stencil_operand<true>(grid, operand, S), n, w, st_lds_bytes(S))
+                       : dg_compute(grid, dg_stencil_operand<false>(grid, operand, S), n, w, st_lds_bytes(S));
+    });
+}
+
+extern "C" int ocn_compute_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    return st_compute(grid, operand, nullptr, out);
+}
+
+// a stencil operand has no whole-parent form: a program that is one LOAD of a field is folded over the interior like any other
+extern "C" int ocn_time_average_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, const ocn_time_fold_t *fold, double *result) {
+    NEED_INIT();
+    if (!result) return fail(OCN_EINVAL, "NULL argument");
+    const int rc = dg_check_fold(fold);
+    if (rc) return rc;
+    return st_compute(grid, operand, fold, result);
 }
 
 template <bool ARITH>
 static int st_reduce(ocn_grid_s *grid, const ocn_stencil_operand_t *operand, const StLowered &S, int kind, int dims_mask, int use_metric,
-                     int absolute, double *out) {
+                     int absolute, const ocn_time_fold_t *fold, double *out) {
     DgStencil<ARITH> o = dg_stencil_operand<ARITH>(grid, operand, S);
     o.absolute = absolute != 0;
     if (use_metric) dg_set_metric_of(grid->d, dims_mask, &o);
     int n[3];
     dg_interior_size(grid->d, operand->loc, n);
-    return dg_reduce_kind(grid, o, kind, n, dims_mask, dg_make_out(grid->d, operand->loc, dims_mask, out), st_lds_bytes(S));
+    return dg_with_out(dg_make_out(grid->d, operand->loc, dims_mask, out), fold,
+                       [&](const auto &w) { return dg_reduce_kind(grid, o, kind, n, dims_mask, w, st_lds_bytes(S)); });
 }
 
-extern "C" int ocn_reduce_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
-                                  double *out) {
-    NEED_INIT();
-    if (!out) return fail(OCN_EINVAL, "NULL argument");
+static int st_reduce_any(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
+                         const ocn_time_fold_t *fold, double *out) {
     if (kind < OCN_REDUCE_SUM || kind > OCN_REDUCE_AVERAGE) return fail(OCN_EINVAL, "unknown reduction kind %d", kind);
     if (dims_mask < 1 || dims_mask > 7) return fail(OCN_EINVAL, "dims_mask %d: bits 0..2 name the reduced directions, at least one", dims_mask);
     if (use_metric && (kind == OCN_REDUCE_MAXIMUM || kind == OCN_REDUCE_MINIMUM)) return fail(OCN_EINVAL, "maximum and minimum take no metric");
     StLowered S;
     const int rc = dg_lower_stencil(grid, operand, &S);
     if (rc) return rc;
-    return S.arith ? st_reduce<true>(grid, operand, S, kind, dims_mask, use_metric, absolute, out)
-                   : st_reduce<false>(grid, operand, S, kind, dims_mask, use_metric, absolute, out);
+    return S.arith ? st_reduce<true>(grid, operand, S, kind, dims_mask, use_metric, absolute, fold, out)
+                   : st_reduce<false>(grid, operand, S, kind, dims_mask, use_metric, absolute, fold, out);
+}
+
+extern "C" int ocn_reduce_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
+                                  double *out) {
+    NEED_INIT();
+    if (!out) return fail(OCN_EINVAL, "NULL argument");
+    return st_reduce_any(grid, operand, kind, dims_mask, use_metric, absolute, nullptr, out);
+}
+
+extern "C" int ocn_time_average_reduce_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int kind, int dims_mask, int use_metric,
+                                               int absolute, const ocn_time_fold_t *fold, double *result) {
+    NEED_INIT();
+    if (!result) return fail(OCN_EINVAL, "NULL argument");
+    const int rc = dg_check_fold(fold);
+    if (rc) return rc;
+    return st_reduce_any(grid, operand, kind, dims_mask, use_metric, absolute, fold, result);
 }
 
 template <bool ARITH>
-static int st_accumulate(ocn_grid_s *grid, const ocn_stencil_operand_t *operand, const StLowered &S, int dim, int reverse, int use_metric, double *out) {
+static int st_accumulate(ocn_grid_s *grid, const ocn_stencil_operand_t *operand, const StLowered &S, int dim, int reverse, int use_metric,
+                         const ocn_time_fold_t *fold, double *out) {
     DgStencil<ARITH> o = dg_stencil_operand<ARITH>(grid, operand, S);
     if (use_metric) dg_set_metric_of(grid->d, 1 << dim, &o);
     int n[3];
     dg_interior_size(grid->d, operand->loc, n);
-    return dg_accumulate(o, n, dim, reverse, dg_make_out(grid->d, operand->loc, 0, out), st_lds_bytes(S));
+    return dg_with_out(dg_make_out(grid->d, operand->loc, 0, out), fold,
+                       [&](const auto &w) { return dg_accumulate(o, n, dim, reverse, w, st_lds_bytes(S)); });
+}
+
+static int st_accumulate_any(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int dim, int reverse, int use_metric,
+                             const ocn_time_fold_t *fold, double *out) {
+    if (dim < 0 || dim > 2) return fail(OCN_EINVAL, "dim %d: 0 (x), 1 (y) or 2 (z)", dim);
+    StLowered S;
+    const int rc = dg_lower_stencil(grid, operand, &S);
+    if (rc) return rc;
+    return S.arith ? st_accumulate<true>(grid, operand, S, dim, reverse, use_metric, fold, out)
+                   : st_accumulate<false>(grid, operand, S, dim, reverse, use_metric, fold, out);
 }
 
 extern "C" int ocn_accumulate_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int dim, int reverse, int use_metric, double *out) {
     NEED_INIT();
     if (!out) return fail(OCN_EINVAL, "NULL argument");
-    if (dim < 0 || dim > 2) return fail(OCN_EINVAL, "dim %d: 0 (x), 1 (y) or 2 (z)", dim);
-    StLowered S;
-    const int rc = dg_lower_stencil(grid, operand, &S);
+    return st_accumulate_any(grid, operand, dim, reverse, use_metric, nullptr, out);
+}
+
+extern "C" int ocn_time_average_accumulate_stencil(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int dim, int reverse, int use_metric,
+                                                   const ocn_time_fold_t *fold, double *result) {
+    NEED_INIT();
+    if (!result) return fail(OCN_EINVAL, "NULL argument");
+    const int rc = dg_check_fold(fold);
     if (rc) return rc;
-    return S.arith ? st_accumulate<true>(grid, operand, S, dim, reverse, use_metric, out)
-                   : st_accumulate<false>(grid, operand, S, dim, reverse, use_metric, out);
+    return st_accumulate_any(grid, operand, dim, reverse, use_metric, fold, result);
 }
 
 static int update_hydrostatic_pressure(const DGrid &g, int kind, const double *bT, const double *S, double grav, double alpha, double beta,

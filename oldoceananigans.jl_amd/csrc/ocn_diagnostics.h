@@ -19,6 +19,10 @@
 // Accumulations keep the reference's sequential order: along y and z a march per column with x across the lanes
 // (dg_accumulate_cols_kernel); along x a wave per row reads 64 points at a time and every lane forms the same running sum from the lanes'
 // values in index order (dg_accumulate_rows_kernel).
+//
+// Every kernel is also a template on WHERE it writes: DgOut, a plain store, or DgOutFold, the running time average of
+// accumulate_result! (OutputWriters/windowed_time_average.jl:216-230) -- the value the plain store would write is folded into the
+// element it would overwrite, in the thread that formed it (dg_store). Splits, chunks and combine orders do not depend on it.
 #pragma once
 #include "ocn_device.h"
 #include "ocn_open_boundary.h"   // jl_min, jl_max
@@ -53,6 +57,23 @@ struct DgOut {
     double *p;
     long off, s[3];
 };
+
+// the same place as the running average of a WindowedTimeAverage: result = (result * T_previous + integrand * Δt) / T_current
+// (windowed_time_average.jl:224), the three times by value. first: the first sample of a window, for which advance_time_average!
+// (:236-249) has just zeroed the result and T_previous is 0 -- the result is not read (no memset either) and is
+// (0.0 * 0.0 + integrand * Δt) / T_current = (0.0 + integrand * Δt) / T_current, so an integrand of -0.0 gives +0.0 as it does there
+struct DgOutFold : DgOut {
+    double Tp, dt, Tc;
+    int first;
+};
+
+__device__ __forceinline__ void dg_store(const DgOut &w, long idx, double v) { w.p[idx] = v; }
+// two multiplies, one add, one correctly rounded divide, in the reference's association (-ffp-contract=off: no fma)
+__device__ __forceinline__ void dg_store(const DgOutFold &w, long idx, double v) {
+    const double s = v * w.dt;
+    const double r = w.first ? 0.0 : w.p[idx] * w.Tp;
+    w.p[idx] = (r + s) / w.Tc;
+}
 
 // ℑ of a field: 0.5 (f[low] + f[low + 1]) per direction, nested with st[0] innermost
 __device__ __forceinline__ double dg_leaf(const DgLeaf &l, int i, int j, int k) {
@@ -177,12 +198,19 @@ __device__ __forceinline__ double dg_eval(const DgStencil<ARITH> &o, int i, int 
 // ---------------------------------------------------------------------------------------------------------------------
 // computed field: _compute! (computed_field.jl:100-103)
 // ---------------------------------------------------------------------------------------------------------------------
-template <class O>
-__global__ void __launch_bounds__(256) dg_compute_kernel(O o, DgOut out, int n0, int n1) {
+template <class O, class W>
+__global__ void __launch_bounds__(256) dg_compute_kernel(O o, W out, int n0, int n1) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y * blockDim.y + threadIdx.y, k = blockIdx.z;
     if (i >= n0 || j >= n1) return;
     double m;
-    out.p[out.off + i * out.s[0] + j * out.s[1] + k * out.s[2]] = dg_eval(o, i, j, k, m);
+    dg_store(out, out.off + i * out.s[0] + j * out.s[1] + k * out.s[2], dg_eval(o, i, j, k, m));
+}
+
+// a plain field as the integrand: the whole parent array, halos included, as `@.` on parent(result) folds it
+// (windowed_time_average.jl:224)
+__global__ void __launch_bounds__(256) dg_fold_parent_kernel(const double *a, DgOutFold out, long n) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n) dg_store(out, q, a[q]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -215,8 +243,8 @@ struct DgRows {
 
 // x reduced. Block b: output element b / nch, chunk b % nch. slab: [0, nout * nch) the partial results, [nout * nch, 2 nout nch) the
 // partial metric sums (average with a metric)
-template <int KIND, class O>
-__global__ void __launch_bounds__(DG_THREADS) dg_reduce_rows_kernel(O o, DgRows R, DgOut out, double *slab, long nslab) {
+template <int KIND, class O, class W>
+__global__ void __launch_bounds__(DG_THREADS) dg_reduce_rows_kernel(O o, DgRows R, W out, double *slab, long nslab) {
     __shared__ double lds[2][DG_THREADS / 64];
     const long b = blockIdx.x;
     const int e = (int)(b / R.nch), c = (int)(b % R.nch);
@@ -244,7 +272,7 @@ __global__ void __launch_bounds__(DG_THREADS) dg_reduce_rows_kernel(O o, DgRows 
         s = dg_combine<KIND>(s, lds[0][w]);
         if (with_metric) ms = ms + lds[1][w];
     }
-    if (R.nch == 1) out.p[out.off + jo * out.s[1] + ko * out.s[2]] = dg_finish<KIND>(s, ms, with_metric, R.count);
+    if (R.nch == 1) dg_store(out, out.off + jo * out.s[1] + ko * out.s[2], dg_finish<KIND>(s, ms, with_metric, R.count));
     else {
         slab[b] = s;
         if (with_metric) slab[nslab + b] = ms;
@@ -252,8 +280,8 @@ __global__ void __launch_bounds__(DG_THREADS) dg_reduce_rows_kernel(O o, DgRows 
 }
 
 // the chunks of one output element per block: thread t adds chunks t, t + 256, ... in order, the threads combine in a fixed tree
-template <int KIND>
-__global__ void __launch_bounds__(DG_THREADS) dg_combine_kernel(DgRows R, DgOut out, const double *slab, long nslab, int with_metric) {
+template <int KIND, class W>
+__global__ void __launch_bounds__(DG_THREADS) dg_combine_kernel(DgRows R, W out, const double *slab, long nslab, int with_metric) {
     __shared__ double lds[2][DG_THREADS];
     const int e = blockIdx.x;
     const int ej = R.rj ? 1 : R.n1;
@@ -273,12 +301,12 @@ __global__ void __launch_bounds__(DG_THREADS) dg_combine_kernel(DgRows R, DgOut 
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) out.p[out.off + jo * out.s[1] + ko * out.s[2]] = dg_finish<KIND>(lds[0][0], lds[1][0], with_metric != 0, R.count);
+    if (threadIdx.x == 0) dg_store(out, out.off + jo * out.s[1] + ko * out.s[2], dg_finish<KIND>(lds[0][0], lds[1][0], with_metric != 0, R.count));
 }
 
 // x kept: thread (i, jo, ko) loops over the reduced y (inner) and z (outer) extents lj, lk (1 where the direction is kept)
-template <int KIND, class O>
-__global__ void __launch_bounds__(256) dg_reduce_cols_kernel(O o, DgOut out, int n0, int e1, int lj, int lk, double count) {
+template <int KIND, class O, class W>
+__global__ void __launch_bounds__(256) dg_reduce_cols_kernel(O o, W out, int n0, int e1, int lj, int lk, double count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, jo = blockIdx.y * blockDim.y + threadIdx.y, ko = blockIdx.z;
     if (i >= n0 || jo >= e1) return;
     const bool with_metric = KIND == OCN_REDUCE_AVERAGE && o.mmode != 0;
@@ -289,15 +317,16 @@ __global__ void __launch_bounds__(256) dg_reduce_cols_kernel(O o, DgOut out, int
             s = dg_combine<KIND>(s, dg_eval(o, i, jo + jr, ko + kr, m));
             if (with_metric) ms = ms + m;
         }
-    out.p[out.off + i * out.s[0] + jo * out.s[1] + ko * out.s[2]] = dg_finish<KIND>(s, ms, with_metric, count);
+    dg_store(out, out.off + i * out.s[0] + jo * out.s[1] + ko * out.s[2], dg_finish<KIND>(s, ms, with_metric, count));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // accumulations: B[start] = A[start]; B[i] = B[i ∓ 1] + A[i] (accumulate_x / _y / _z, scans.jl:272-306)
 // ---------------------------------------------------------------------------------------------------------------------
 // along y (DIM 1) or z (DIM 2): thread (i, q), q the other of j, k; nd points along the march
-template <int DIM, class O>
-__global__ void __launch_bounds__(256) dg_accumulate_cols_kernel(O o, DgOut out, int n0, int nq, int nd, int reverse) {
+// (a time average folds only what is stored: the running sum stays in registers)
+template <int DIM, class O, class W>
+__global__ void __launch_bounds__(256) dg_accumulate_cols_kernel(O o, W out, int n0, int nq, int nd, int reverse) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, q = blockIdx.y * blockDim.y + threadIdx.y;
     if (i >= n0 || q >= nq) return;
     double run = 0.0;
@@ -307,13 +336,13 @@ __global__ void __launch_bounds__(256) dg_accumulate_cols_kernel(O o, DgOut out,
         double m;
         const double a = dg_eval(o, i, j, k, m);
         run = t == 0 ? a : run + a;
-        out.p[out.off + i * out.s[0] + j * out.s[1] + k * out.s[2]] = run;
+        dg_store(out, out.off + i * out.s[0] + j * out.s[1] + k * out.s[2], run);
     }
 }
 
 // along x: one wave per (j, k) row, 64 points per step; every lane forms the running sum of the step's values in index order
-template <class O>
-__global__ void __launch_bounds__(DG_THREADS) dg_accumulate_rows_kernel(O o, DgOut out, int n0, int n1, long nrows, int reverse) {
+template <class O, class W>
+__global__ void __launch_bounds__(DG_THREADS) dg_accumulate_rows_kernel(O o, W out, int n0, int n1, long nrows, int reverse) {
     const long row = (long)blockIdx.x * (DG_THREADS / 64) + (threadIdx.x >> 6);
     if (row >= nrows) return;                                // whole waves leave: the shuffles below see full waves
     const int lane = threadIdx.x & 63;
@@ -331,6 +360,6 @@ __global__ void __launch_bounds__(DG_THREADS) dg_accumulate_rows_kernel(O o, DgO
             run = (base == 0 && l == 0) ? al : run + al;
             if (l == lane) mine = run;
         }
-        if (t < n0) out.p[out.off + i * out.s[0] + j * out.s[1] + k * out.s[2]] = mine;
+        if (t < n0) dg_store(out, out.off + i * out.s[0] + j * out.s[1] + k * out.s[2], mine);
     }
 }

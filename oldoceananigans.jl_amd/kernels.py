@@ -115,6 +115,62 @@ def accumulate_stencil(grid, operand, dim, reverse, use_metric, out):
     _lib.check(_lib.lib().ocn_accumulate_stencil(grid.handle, C.byref(s), int(dim) - 1, int(reverse), int(use_metric), out.data))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# time averages: the six calls above with the fold of accumulate_result! (OutputWriters/windowed_time_average.jl:216-230) at the store.
+# times: (T_previous, Δt, T_current, first) -- first: the first sample of a window, `result` is not read
+# ---------------------------------------------------------------------------------------------------------------------
+def _time_fold(times):
+    T_previous, Δt, T_current, first = times
+    return C.byref(_lib.TimeFold(float(T_previous), float(Δt), float(T_current), int(bool(first))))
+
+
+def time_average_operation(grid, operand, times, result):
+    """result = (result * T_previous + operand * Δt) / T_current: a Field over its whole parent array, halos included; a BinaryOperation
+    over the interior of its location"""
+    from .diagnostics import operand_struct
+    _lib.check(_lib.lib().ocn_time_average_operation(grid.handle, C.byref(operand_struct(operand)), _time_fold(times), result.data))
+
+
+def time_average_parent(field, times, result):
+    """the fold of a materialised field of any shape (a reduced field has no operand form) over its whole parent array"""
+    if field.shape != result.shape:
+        raise ValueError(f"parent shape {field.shape} != {result.shape}")
+    _lib.check(_lib.lib().ocn_time_average_parent(field.data, field.nbytes // 8, _time_fold(times), result.data))
+
+
+def time_average_stencil(grid, operand, times, result):
+    """time_average_operation with the operand as a stencil program, over the interior of its location"""
+    s, keep = _stencil_struct(operand)
+    _lib.check(_lib.lib().ocn_time_average_stencil(grid.handle, C.byref(s), _time_fold(times), result.data))
+
+
+def time_average_reduce_operation(grid, operand, kind, dims, use_metric, absolute, times, result):
+    """the fold of what reduce_operation would write, into the reduced field `result`"""
+    from .diagnostics import _KIND_CODE, dims_mask, operand_struct
+    _lib.check(_lib.lib().ocn_time_average_reduce_operation(grid.handle, C.byref(operand_struct(operand)), _KIND_CODE[kind], dims_mask(dims),
+                                                            int(use_metric), int(absolute), _time_fold(times), result.data))
+
+
+def time_average_reduce_stencil(grid, operand, kind, dims, use_metric, absolute, times, result):
+    from .diagnostics import _KIND_CODE, dims_mask
+    s, keep = _stencil_struct(operand)
+    _lib.check(_lib.lib().ocn_time_average_reduce_stencil(grid.handle, C.byref(s), _KIND_CODE[kind], dims_mask(dims), int(use_metric), int(absolute),
+                                                          _time_fold(times), result.data))
+
+
+def time_average_accumulate_operation(grid, operand, dim, reverse, use_metric, times, result):
+    """the fold of what accumulate_operation would write: the running sum stays in registers"""
+    from .diagnostics import operand_struct
+    _lib.check(_lib.lib().ocn_time_average_accumulate_operation(grid.handle, C.byref(operand_struct(operand)), int(dim) - 1, int(reverse),
+                                                                int(use_metric), _time_fold(times), result.data))
+
+
+def time_average_accumulate_stencil(grid, operand, dim, reverse, use_metric, times, result):
+    s, keep = _stencil_struct(operand)
+    _lib.check(_lib.lib().ocn_time_average_accumulate_stencil(grid.handle, C.byref(s), int(dim) - 1, int(reverse), int(use_metric),
+                                                              _time_fold(times), result.data))
+
+
 def evaluate_boundary_function(grid, program, loc, side, deps, time, out=None):
     """getbc of a traced boundary function (boundary_functions.py: a list of instruction tuples (op, a, b, c, imm)) at every point of
     `side` ("west" .. "top" or 0..5) for a condition of a field at `loc`: `deps` are Fields with current halos, one per dependency slot;

@@ -184,9 +184,17 @@ class TimeInterval:
 
 
 class Callback:
-    """Callback(func, schedule = IterationInterval(1); parameters = nothing): func(sim) or func(sim, parameters) (callback.jl)"""
+    """Callback(func, schedule = IterationInterval(1); parameters = nothing): func(sim) or func(sim, parameters) (callback.jl).
+    Callback(wta) of a WindowedTimeAverage advances it on its own schedule (callback.jl:81-88); naming a schedule as well is an error
+    (:90-92)"""
 
     def __init__(self, func, schedule=None, parameters=None):
+        from .time_averages import WindowedTimeAverage, advance_time_average
+        if isinstance(func, WindowedTimeAverage):
+            if schedule is not None:
+                raise ValueError("Schedule must be inferred from WindowedTimeAverage. Use Callback(windowed_time_average)")
+            wta = func
+            func, schedule = (lambda sim: advance_time_average(wta, sim.model)), wta.schedule
         self.func, self.schedule, self.parameters = func, schedule or IterationInterval(1), parameters
 
     def __call__(self, sim):
@@ -211,7 +219,8 @@ def wall_time_limit_exceeded(sim):
 class Simulation:
     """Simulation(model; Δt, stop_iteration = Inf, stop_time = Inf, wall_time_limit = Inf, align_time_step = true,
     minimum_relative_step = 0) (Simulations/simulation.jl:67-121). `callbacks` is an ordered dict of Callback; the three stop
-    criteria and the default NaN checker (every 100 iterations) are installed like the reference does."""
+    criteria and the default NaN checker (every 100 iterations) are installed like the reference does. `diagnostics` is an ordered dict
+    of diagnostics (a WindowedTimeAverage: time_averages.py), run after the time-step and before the callbacks (run.jl:153-154)."""
 
     def __init__(self, model, Δt, stop_iteration=math.inf, stop_time=math.inf, wall_time_limit=math.inf, align_time_step=True,
                  minimum_relative_step=0.0, verbose=False):
@@ -219,6 +228,7 @@ class Simulation:
         self.stop_iteration, self.stop_time, self.wall_time_limit = float(stop_iteration), float(stop_time), float(wall_time_limit)
         self.align_time_step, self.minimum_relative_step, self.verbose = bool(align_time_step), float(minimum_relative_step), verbose
         self.run_wall_time, self.initialized, self.running = 0.0, False, False
+        self.diagnostics = OrderedDict()
         self.callbacks = OrderedDict()
         self.callbacks["stop_time_exceeded"] = Callback(stop_time_exceeded)
         self.callbacks["stop_iteration_exceeded"] = Callback(stop_iteration_exceeded)
@@ -240,9 +250,12 @@ class Simulation:
         from .models import update_state
         if hasattr(self.model, "handle"):
             update_state(self.model, True)
-        for cb in self.callbacks.values():
-            cb.schedule.initialize(self.model)
+        from .time_averages import run_diagnostic
+        for activity in list(self.diagnostics.values()) + list(self.callbacks.values()):
+            activity.schedule.initialize(self.model)
         if self.model.clock.iteration == 0:
+            for diag in self.diagnostics.values():               # run.jl:232-235
+                run_diagnostic(diag, self.model)
             for cb in self.callbacks.values():
                 cb(self)
         self.initialized = True
@@ -259,6 +272,11 @@ class Simulation:
         if Δt < self.minimum_relative_step * self.Δt:
             raise NotImplementedError("skipping a tiny aligned time step needs a writable clock (minimum_relative_step > 0)")
         model_time_step(self.model, Δt)
+        if self.diagnostics:
+            from .time_averages import run_diagnostic
+            for diag in self.diagnostics.values():               # run.jl:153-154
+                if diag.schedule(self.model):
+                    run_diagnostic(diag, self.model)
         for cb in self.callbacks.values():
             if cb.schedule(self.model):
                 cb(self)

@@ -34,6 +34,8 @@ def jl_type(t):
         return "Ptr{OcnStencilIns}"
     if base == "ocn_stencil_operand_t":
         return "Ptr{OcnStencilOperand}"
+    if base == "ocn_time_fold_t":
+        return "Ptr{OcnTimeFold}"
     if base == "char":
         return "Ptr{Cstring}" if ptr > 1 else "Cstring"
     if base == "void":
@@ -66,7 +68,9 @@ table = [MARK, "",
          "(`op::Cint; a::Cint; b::Cint; c::Cint; imm::Cdouble`): one recorded operation of a boundary function. `OcnStencilIns` mirrors",
          "`ocn_stencil_ins_t` (`op, a, b, c, di, dj, dk::Cint; imm::Cdouble`): one recorded operation of a kernel function, and",
          "`OcnStencilOperand` mirrors `ocn_stencil_operand_t` (`program::Ptr{OcnStencilIns}; n::Cint; args::Ptr{Ptr{Cdouble}};",
-         "arg_locs::Ptr{Cint}; nargs::Cint; loc::NTuple{3, Cint}`), filled from a `KernelFunctionOperation`'s recorded program and arguments.", "", "| entry point | binding |", "|---|---|"] + rows
+         "arg_locs::Ptr{Cint}; nargs::Cint; loc::NTuple{3, Cint}`), filled from a `KernelFunctionOperation`'s recorded program and arguments.",
+         "`OcnTimeFold` mirrors `ocn_time_fold_t` (`T_previous::Cdouble; dt::Cdouble; T_current::Cdouble; first::Cint`): the three times of",
+         "`accumulate_result!` and whether the sample is the first of its window.", "", "| entry point | binding |", "|---|---|"] + rows
 p = os.path.join(ROOT, "INTEGRATION.md")
 s = open(p).read()
 if MARK in s:
