@@ -467,7 +467,10 @@ int ocn_model_set_option(ocn_model_t model, const char *key, int value);
  * "graph_replays", "graph_failures" (option "use_graph"), which conditional path the model's pressure solver took -- "fused_zfft_active"
  * (1 when solve_for_pressure! runs the z transform, the divide and the inverse z transform as one pass: options "real_fft" and
  * "fused_zfft", FFT solver, Nz = 2^m in 8 .. 1024), "c2r_strided_active" (1 when the Z2D plan writes into the haloed pressure field:
- * options "real_fft" and "c2r_strided" AND rocFFT accepted the plan); both 0 on a partitioned model -- and, on a partitioned model,
+ * options "real_fft" and "c2r_strided" AND rocFFT accepted the plan), "split_solve_active" (1 when the model's pressure step runs the
+ * split form -- 1-D x plans on padded rows, the LDS line kernel along y, the correction taken from the dense solution: options
+ * "split_solve" and "real_fft", x and y Periodic, Ny = 2^m in 8 .. 1024, Fourier-tridiagonal solver or fused z transform, AND the split
+ * form passed its self-check at creation; the 2-D plans run otherwise); all three 0 on a partitioned model -- and, on a partitioned model,
  * "dist_poisson_layout", "dist_yline_active" (1 when the local y transform runs in the LDS line kernel: option "dist_yline", z Bounded,
  * Ny = 2^m in 8 .. 1024 and the kernel passed its check at creation) and "dist_xline_group_active" (1 when the Thomas scans of the
  * x-fastest solve run several lines per wave: option "dist_xline_group", local Nx 32, 64 or 128); both 0 on a single-GPU model */

@@ -3044,6 +3044,14 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
         *value = !real_path ? 0 : (key[0] == 'f' ? (s->kind == 0 && s->zfused) : s->c2r_strided) ? 1 : 0;
         return OCN_OK;
     }
+    // whether the model's pressure step runs the split form (1-D x plans on padded rows, strided_line_fft_kernel along y, the correction from
+    // the dense solution): the solver's self-check accepted it at creation (poisson_accept_split keeps the 2-D plans otherwise, without a
+    // word) and the options still ask for it -- the condition pressure_step itself tests. 0 on the complex path and on a partitioned model
+    if (!strcmp(key, "split_solve_active")) {
+        const ocn_poisson_s *s = m->solver;
+        *value = !m->dm && s && s->split && m->opt.split_solve && m->opt.real_fft && !s->general ? 1 : 0;
+        return OCN_OK;
+    }
     if (!strcmp(key, "fused_tendency_active")) { *value = fused_path(m->opt, m->grid->d, nullptr, m->ntr, m->opt.tendency_impl) ? 1 : 0; return OCN_OK; }
     return fail(OCN_EINVAL, "unknown model option '%s'", key);
 }
