@@ -298,6 +298,27 @@ int ocn_compute_amd_diffusivities(ocn_grid_t grid, double Cnu, const double *Cka
 int ocn_compute_smagorinsky_viscosity(ocn_grid_t grid, double C, double Cb, int lilly, int buoyancy_kind, const double *b_or_T,
                                       const double *S, double g, double alpha, double beta, const double *u, const double *v,
                                       const double *w, double *nu_e, const int *range);
+/* ONE coefficient update of a dynamic Smagorinsky closure on caller arrays: compute_coefficient_fields! once its schedule has fired
+ * (Smagorinskys/dynamic_coefficient.jl:194-217 for a DirectionallyAveragedCoefficient, :292-330 for LagrangianAveraging), that is
+ * _compute_Σ!, _compute_Σ̄! (:142-158), _compute_LM_MM! (:160-188; the operators of scale_invariant_operators.jl:47-188) and then
+ *   averaging_mask 1..7 (bit d = direction d + 1): J_LM = Average(LM, dims), J_MM = Average(MM, dims) as ocn_reduce_operation forms them
+ *                    (the metric where a stretched z is averaged); J_LM, J_MM are reduced fields (no halo and one point along an
+ *                    averaged direction). J_LM_prev, J_MM_prev are not read (NULL).
+ *   averaging_mask 0 (LagrangianAveraging): parent(J_prev) <- parent(J); initialising != 0: J <- LM, MM, then the WHOLE parent
+ *                    <- max(mean(J_LM), minimum_numerator) and mean(J_MM) (:318-321); else _lagrangian_average_LM_MM! (:241-290) with
+ *                    Δt = dt writes the interior of J. LM, MM are not written (NULL). Needs ocn_grid_set_nodes / _node_tables
+ *                    (OCN_ESTATE).
+ * u, v, w: parent arrays with filled halos. Sigma, Sigma_bar, LM, MM: ccc parent arrays whose interior is written; the halo of Sigma is
+ * never read (the reference never fills it: a neighbour outside the interior counts as 0). OCN_EINVAL on a Flat direction, halos
+ * below 2 or a missing array; OCN_ENOTSUP on a connected topology. */
+int ocn_dynamic_smagorinsky_update(ocn_grid_t grid, const double *u, const double *v, const double *w, int averaging_mask,
+                                   double minimum_numerator, double dt, int initialising, double *Sigma, double *Sigma_bar, double *LM,
+                                   double *MM, double *J_LM, double *J_MM, double *J_LM_prev, double *J_MM_prev);
+/* _compute_smagorinsky_viscosity! (smagorinsky.jl:92-106) with square_smagorinsky_coefficient of a dynamic closure
+ * (dynamic_coefficient.jl:129-140): νₑ = (cs² Δᶠ²) sqrt(2 Σ²), cs² = J_MM > 0 ? max(J_LM, minimum_numerator) / J_MM : 0, over the
+ * interior. J_LM, J_MM laid out as ocn_dynamic_smagorinsky_update leaves them for averaging_mask. */
+int ocn_compute_dynamic_smagorinsky_viscosity(ocn_grid_t grid, int averaging_mask, double minimum_numerator, const double *J_LM,
+                                              const double *J_MM, const double *u, const double *v, const double *w, double *nu_e);
 /* ocn_compute_closure_tendencies_field for a Smagorinsky closure: the momentum terms with νₑ, tracer t's with κ = ℑ(νₑ) / Pr[t] at its
  * flux points -- interpolate, then divide (κᶠᶜᶜ, κᶜᶠᶜ, κᶜᶜᶠ, smagorinsky.jl:141-143) */
 int ocn_compute_closure_tendencies_smagorinsky(ocn_grid_t grid, const double *u, const double *v, const double *w,
@@ -434,7 +455,9 @@ int ocn_model_clock(ocn_model_t model, double *time, int64_t *iteration, int *st
                     double *last_stage_dt);
 /* set!(model, checkpointed_clock) (OutputWriters/checkpointer.jl:199-231): restore the clock of a checkpointed state; the fields and
  * the tendencies Gⁿ, G⁻ are restored by copying the checkpointed parent arrays (halos included, like the reference's files) into the
- * arrays ocn_model_field returns, followed by ocn_model_update_state */
+ * arrays ocn_model_field returns, followed by ocn_model_update_state. The coefficient fields of a dynamic Smagorinsky closure are not
+ * part of a checkpoint: this call (and ocn_model_reset) sets previous_compute_time to `time` and marks the 𝒥 fields as holding nothing,
+ * so the first coefficient update that fires afterwards takes the initialising branch from the restored velocities */
 int ocn_model_set_clock(ocn_model_t model, double time, int64_t iteration, int stage, double last_dt, double last_stage_dt);
 /* max |∇·u| over the interior (test helper: test/test_time_stepping.jl:124-160); synchronous */
 int ocn_model_max_abs_divergence(ocn_model_t model, double *value);
@@ -549,6 +572,19 @@ int ocn_model_set_amd(ocn_model_t model, double Cnu, const double *Ckappa);
  * ocn_model_set_buoyancy names at that moment and fills its halos before the tendencies. OCN_EINVAL on a grid with a Flat
  * direction, for C < 0 and for Pr <= 0. */
 int ocn_model_set_smagorinsky(ocn_model_t model, double C, double Cb, int lilly, const double *Pr);
+/* closure = Smagorinsky(coefficient = DynamicCoefficient(averaging, schedule = IterationInterval(interval, offset), minimum_numerator), Pr)
+ * (Smagorinskys/dynamic_coefficient.jl:5-9,114-117; DynamicSmagorinsky, :20-26). averaging_mask: bit d set = direction d + 1 averaged
+ * (1..7, DirectionallyAveragedCoefficient), 0 = LagrangianAveraging. Replaces any other closure as ocn_model_set_smagorinsky does. Every
+ * update_state! then runs compute_coefficient_fields! (:194-217, :292-330) -- the schedule is (iteration - offset) % interval == 0 on the
+ * clock as it stands -- and _compute_smagorinsky_viscosity! with square_smagorinsky_coefficient (:129-140). The model carries "nu_e",
+ * "Sigma", "Sigma_bar", "J_LM", "J_MM" and "LM", "MM" (directional; J_LM, J_MM are then reduced fields: one point and no halo along
+ * every averaged direction, the parent extent along the others) or "J_LM_prev", "J_MM_prev" (Lagrangian); the names of the other
+ * averaging answer OCN_ESTATE. The first update that fires after this call initialises the 𝒥 fields (LagrangianAveraging: the
+ * first-time-step branch), also on a model whose clock is past 0. A model with a dynamic coefficient steps without the captured graph. OCN_EINVAL on a grid with a Flat
+ * direction or halos below 2, for a mask outside 0..7, interval < 1, a NaN minimum_numerator and Pr <= 0; OCN_ENOTSUP on a partitioned
+ * model; OCN_ESTATE for LagrangianAveraging without ocn_grid_set_nodes and ocn_grid_set_node_tables. */
+int ocn_model_set_dynamic_smagorinsky(ocn_model_t model, int averaging_mask, double minimum_numerator, int64_t interval, int64_t offset,
+                                      const double *Pr);
 int ocn_model_set_boundary_condition(ocn_model_t model, const char *name, int side, int kind, double value);
 /* the same with an array-valued condition (see ocn_bc_t; borrowed device pointer, valid for the model's lifetime) */
 int ocn_model_set_boundary_condition_array(ocn_model_t model, const char *name, int side, int kind, const double *device_array);

@@ -14,8 +14,9 @@ from .boundary_functions import ContinuousBoundaryFunction, cos, exp, ifelse, lo
 from .background_fields import BackgroundField, BackgroundFields
 from .buoyancy import BuoyancyForce, BuoyancyTracer, ConstantCartesianCoriolis, FPlane, LinearEquationOfState, SeawaterBuoyancy
 from .checkpointer import set_from_checkpoint, write_checkpoint
-from .closures import (AnisotropicMinimumDissipation, DynamicCoefficient, ExplicitTimeDiscretization, ScalarDiffusivity, Smagorinsky,
-                       SmagorinskyLilly, VerticalScalarDiffusivity, VerticallyImplicitTimeDiscretization)
+from .closures import (AnisotropicMinimumDissipation, Colon, DynamicCoefficient, DynamicSmagorinsky, ExplicitTimeDiscretization,
+                       LagrangianAveraging, ScalarDiffusivity, Smagorinsky, SmagorinskyLilly, VerticalScalarDiffusivity,
+                       VerticallyImplicitTimeDiscretization)
 from .forcings import (AdvectiveForcing, ContinuousForcing, DiscreteForcing, Forcing, GaussianMask, LinearTarget, MultipleForcings,
                        PiecewiseLinearMask, Relaxation)
 from .fields import (CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions, interior, set_)

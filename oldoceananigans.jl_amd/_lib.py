@@ -178,6 +178,9 @@ SYMBOLS = {
     "ocn_compute_closure_tendencies_field": (C.c_int, [_vp, _vp, _vp, _vp, _pp, C.c_int, _vp, _pp, _vp, _vp, _vp, _pp, _ip]),
     "ocn_compute_amd_diffusivities": (C.c_int, [_vp, C.c_double, _dp, _vp, _vp, _vp, _pp, C.c_int, _vp, _pp, _ip]),
     "ocn_model_set_smagorinsky": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, _dp]),
+    "ocn_model_set_dynamic_smagorinsky": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int64, C.c_int64, _dp]),
+    "ocn_dynamic_smagorinsky_update": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_int] + [_vp] * 8),
+    "ocn_compute_dynamic_smagorinsky_viscosity": (C.c_int, [_vp, C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ocn_compute_smagorinsky_viscosity": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _vp, C.c_double, C.c_double, C.c_double,
                                                     _vp, _vp, _vp, _vp, _ip]),
     "ocn_compute_closure_tendencies_smagorinsky": (C.c_int, [_vp, _vp, _vp, _vp, _pp, C.c_int, _vp, _dp, _vp, _vp, _vp, _pp, _ip]),

@@ -136,11 +136,79 @@ class AnisotropicMinimumDissipation:
         return f"AnisotropicMinimumDissipation{{ExplicitTimeDiscretization}}(Cν={self.Cν}, Cκ={self.Cκ}, Cb=nothing)"
 
 
-class DynamicCoefficient:
-    """DynamicCoefficient(; averaging, ...) (Smagorinskys/dynamic_coefficient.jl): named so that it can be refused; not on the accelerated path."""
+class _Colon:
+    """Julia's `:` as an averaging: all three directions. ocn.Colon (also spelt ":")"""
 
-    def __init__(self, *args, **kwargs):
+    def __repr__(self):
+        return "Colon()"
+
+
+Colon = _Colon()
+
+
+class LagrangianAveraging:
+    """LagrangianAveraging() (Smagorinskys/dynamic_coefficient.jl:32): 𝒥ᴸᴹ and 𝒥ᴹᴹ are averaged along fluid-parcel trajectories"""
+
+    def __repr__(self):
+        return "LagrangianAveraging()"
+
+    def __eq__(self, other):
+        return type(other) is type(self)
+
+    __hash__ = object.__hash__
+
+
+def _averaging(averaging):
+    """the averaging as the reference holds it -- an Int, a tuple of Ints, Colon or LagrangianAveraging() -- and the library's mask of the
+    averaged directions (bit d: direction d + 1; 0: Lagrangian)"""
+    if isinstance(averaging, LagrangianAveraging) or averaging is LagrangianAveraging:
+        return LagrangianAveraging(), 0
+    if averaging is Colon or (isinstance(averaging, str) and averaging == ":"):
+        return Colon, 7
+    if isinstance(averaging, bool):
+        raise TypeError("averaging is an Int, a tuple of Ints out of (1, 2, 3), Colon or LagrangianAveraging()")
+    if isinstance(averaging, (int, np.integer)):
+        dims, kept = (int(averaging),), int(averaging)
+    elif isinstance(averaging, (tuple, list)) and averaging and all(isinstance(d, (int, np.integer)) and not isinstance(d, bool) for d in averaging):
+        dims = tuple(int(d) for d in averaging)
+        kept = dims
+    else:
+        raise TypeError("averaging is an Int, a tuple of Ints out of (1, 2, 3), Colon or LagrangianAveraging()")
+    if any(d not in (1, 2, 3) for d in dims) or len(set(dims)) != len(dims):
+        raise ValueError(f"averaging = {averaging}: the directions are distinct and out of (1, 2, 3)")
+    return kept, sum(1 << (d - 1) for d in dims)
+
+
+class DynamicCoefficient:
+    """DynamicCoefficient(; averaging, schedule = IterationInterval(1), minimum_numerator = 1e-32) (Smagorinskys/dynamic_coefficient.jl:
+    39-117): the scale-invariant dynamic Smagorinsky coefficient of Bou-Zeid et al. (2005). `averaging`: an Int or a tuple of Ints out of
+    (1, 2, 3), Colon (all three), or LagrangianAveraging(). `schedule`: an IterationInterval. A DynamicCoefficient without `averaging` can be
+    written down (the reference's keyword is required) but no closure takes it."""
+
+    def __init__(self, *args, averaging=None, schedule=None, minimum_numerator=1e-32, **kwargs):
         self.args, self.kwargs = args, kwargs
+        self.averaging, self.averaging_mask = (None, None) if averaging is None else _averaging(averaging)
+        from .simulations import IterationInterval
+        self.schedule = IterationInterval(1) if schedule is None else schedule
+        if callable(minimum_numerator):
+            raise NotImplementedError("minimum_numerator is a number")
+        self.minimum_numerator = float(minimum_numerator)
+
+    def _schedule_text(self):
+        s = self.schedule
+        return f"IterationInterval({s.interval}, {s.offset})" if hasattr(s, "interval") and hasattr(s, "offset") else repr(s)
+
+    def summary(self):
+        """Base.summary (dynamic_coefficient.jl:119)"""
+        return f"DynamicCoefficient(averaging = {self.averaging!r}, schedule = {self._schedule_text()})"
+
+    def __repr__(self):
+        """Base.show (dynamic_coefficient.jl:120-123)"""
+        from .forcings import _jl
+        return ("DynamicCoefficient with\n"
+                f"├── averaging = {self.averaging!r}\n"
+                f"├── schedule = {self._schedule_text()}\n"
+                f"└── minimum_numerator = {_jl(self.minimum_numerator)}")
 
 
 class Smagorinsky:
@@ -156,13 +224,25 @@ class Smagorinsky:
         if _is_time_discretization(coefficient):        # Smagorinsky(time_discretization; coefficient, Pr) (smagorinsky.jl:62)
             coefficient, time_discretization = 0.16, coefficient
         _refuse_vertically_implicit(type(self).__name__, time_discretization)
-        if isinstance(coefficient, DynamicCoefficient) or callable(coefficient):
-            raise NotImplementedError("only a constant (Number) Smagorinsky coefficient is on the accelerated path")
+        self.dynamic = isinstance(coefficient, DynamicCoefficient)
+        if self.dynamic:
+            if self.lilly:
+                raise NotImplementedError("the Lilly stability function with a DynamicCoefficient is not a closure of the reference")
+            if coefficient.averaging is None:
+                raise NotImplementedError("DynamicCoefficient: the keyword `averaging` is required (an Int, a tuple of Ints, Colon or "
+                                          "LagrangianAveraging())")
+            from .simulations import IterationInterval
+            if not isinstance(coefficient.schedule, IterationInterval):
+                raise NotImplementedError("the schedule of a DynamicCoefficient on the accelerated path is an IterationInterval")
+            if coefficient.schedule.interval < 1:
+                raise ValueError("the interval of the schedule must be positive")
+        elif callable(coefficient):
+            raise NotImplementedError("only a constant (Number) or a DynamicCoefficient Smagorinsky coefficient is on the accelerated path")
         if callable(Pr) or (isinstance(Pr, dict) and any(callable(x) for x in Pr.values())):
             raise NotImplementedError("only constant (Number) Prandtl numbers are on the accelerated path")
-        self.coefficient = float(coefficient)
+        self.coefficient = coefficient if self.dynamic else float(coefficient)
         self.Pr = {n: float(v) for n, v in Pr.items()} if isinstance(Pr, dict) else float(Pr)
-        if self.coefficient < 0:
+        if not self.dynamic and self.coefficient < 0:
             raise ValueError("the Smagorinsky coefficient must be non-negative")
         if any(not v > 0 for v in (self.Pr.values() if isinstance(self.Pr, dict) else [self.Pr])):
             raise ValueError("the Prandtl number must be positive")
@@ -178,8 +258,24 @@ class Smagorinsky:
         arr = np.ascontiguousarray(vals if vals else [1.0], dtype=np.float64)
         return arr, arr.ctypes.data_as(C.POINTER(C.c_double))
 
+    def summary(self):
+        """Base.summary (smagorinsky.jl:145)"""
+        coefficient = self.coefficient.summary() if self.dynamic else self.coefficient
+        return f"Smagorinsky with coefficient = {coefficient}, Pr={self.Pr}"
+
     def __repr__(self):
+        if self.dynamic:                # Base.show (smagorinsky.jl:146-151)
+            return f"Smagorinsky closure with\n├── coefficient = {self.coefficient.summary()}\n└── Pr = {self.Pr}"
         return f"Smagorinsky closure with coefficient = {self.coefficient}, Pr = {self.Pr}"
+
+
+def DynamicSmagorinsky(time_discretization=None, averaging=None, Pr=1.0, schedule=None, minimum_numerator=1e-32):
+    """DynamicSmagorinsky(; averaging, Pr = 1.0, schedule = IterationInterval(1), minimum_numerator = 1e-32) (Smagorinskys/
+    dynamic_coefficient.jl:20-26): Smagorinsky(coefficient = DynamicCoefficient(averaging, schedule, minimum_numerator), Pr)"""
+    if averaging is None:
+        raise TypeError("DynamicSmagorinsky: the keyword `averaging` is required")
+    return Smagorinsky(coefficient=DynamicCoefficient(averaging=averaging, schedule=schedule, minimum_numerator=minimum_numerator), Pr=Pr,
+                       time_discretization=time_discretization)
 
 
 class SmagorinskyLilly(Smagorinsky):

@@ -15,6 +15,7 @@
 #include "ocn_diagnostics.h"
 #include "ocn_boundary_function.h"
 #include "ocn_forcing_function.h"
+#include "ocn_dynamic_smagorinsky.h"
 #include <hipfft/hipfft.h>
 #include <array>
 #include <cfloat>
@@ -167,8 +168,9 @@ struct ocn_grid_s {
     DGrid d;
     double L[3];
     bool z_regular;
-    double *tables;   // one device allocation holding dzc, dzf, ax, ay, vinv_c, vinv_f, rdzf, rdzc, df2
+    double *tables;   // one device allocation holding dzc, dzf, ax, ay, vinv_c, vinv_f, rdzf, rdzc, df2, df
     const double *df2; // Δf² = cbrt((Δx Δy) Δzᶜ)² per level: the Smagorinsky filter width (smagorinsky.jl:99-100), formed on the host
+    const double *df;  // Δf itself: the time scale of the Lagrangian-averaged dynamic coefficient (dynamic_coefficient.jl:253)
     std::vector<double> h_dzc, h_dzf;
     // why the advection scheme cannot be evaluated on this grid (empty: it can). A grid whose halo is smaller than the scheme needs
     // -- RectilinearGrid(halo = (1, 1, 1)), what test/test_halo_regions.jl fills -- serves fields, halo fills and the Poisson
@@ -279,7 +281,7 @@ extern "C" int ocn_grid_create(ocn_grid_t *grid, const int N[3], const int H[3],
     }
     for (int k = 1; k <= N[2]; ++k)
         if (g->h_dzc[k - 1 + H[2]] != g->h_dzc[H[2]] || g->h_dzf[k - 1 + H[2]] != g->h_dzc[H[2]]) g->z_regular = false;
-    std::vector<double> tab(9 * (size_t)n);
+    std::vector<double> tab(10 * (size_t)n);
     for (int q = 0; q < n; ++q) {
         const double zc = g->h_dzc[q], zf = g->h_dzf[q];
         tab[0 * n + q] = zc;
@@ -292,6 +294,7 @@ extern "C" int ocn_grid_create(ocn_grid_t *grid, const int N[3], const int H[3],
         tab[7 * n + q] = 1.0 / zc;
         const double df = std::cbrt((dx * dy) * zc);
         tab[8 * n + q] = df * df;
+        tab[9 * n + q] = df;
     }
     hipError_t e = dev_alloc((void **)&g->tables, tab.size() * sizeof(double));
     if (e != hipSuccess) { delete g; return fail((int)e, "dev_alloc(grid tables): %s", hipGetErrorString(e)); }
@@ -301,6 +304,7 @@ extern "C" int ocn_grid_create(ocn_grid_t *grid, const int N[3], const int H[3],
     D.vinv_c = g->tables + 4 * n; D.vinv_f = g->tables + 5 * n; D.rdzf = g->tables + 6 * n;
     D.rdzc = g->tables + 7 * n;
     g->df2 = g->tables + 8 * n;
+    g->df = g->tables + 9 * n;
     *grid = g;
     return OCN_OK;
 }
@@ -2162,6 +2166,136 @@ extern "C" int ocn_compute_smagorinsky_viscosity(ocn_grid_t grid, double C, doub
     return smagorinsky_viscosity(g_defaults, grid, C, Cb, lilly != 0, buoyancy_kind, b_or_T, S, g, alpha, beta, u, v, w, nu_e, range);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Smagorinsky(coefficient = DynamicCoefficient(...)) (ocn_dynamic_smagorinsky.h)
+// ---------------------------------------------------------------------------------------------------------------------
+// the fields of one coefficient update. mask: the averaged directions (bit d), 0 = LagrangianAveraging. LM, MM: directional only;
+// J_LM_prev, J_MM_prev: Lagrangian only. ub, vb, wb: scratch for the filtered velocities at the velocities' locations; mean: two doubles
+struct DynFields {
+    double *Sigma, *Sigma_bar, *LM, *MM, *J_LM, *J_MM, *J_LM_prev, *J_MM_prev;
+    double *ub, *vb, *wb, *mean;
+};
+static int alloc_parent_zeroed(ocn_grid_t grid, const int loc[3], double **p);
+
+static int dynamic_smagorinsky_check_grid(const ocn_grid_s *grid, int mask) {
+    const DGrid &g = grid->d;
+    if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT) return fail(OCN_EINVAL, "Smagorinsky needs a grid without Flat directions");
+    if (no_connected_topology(g, "a dynamic Smagorinsky coefficient")) return OCN_ENOTSUP;
+    if (g.Hx < 2 || g.Hy < 2 || g.Hz < 2) return fail(OCN_EINVAL, "a dynamic Smagorinsky coefficient needs halos of at least 2 (the filtered velocities read u, v, w to ±2)");
+    if (mask == 0 && (!grid->has_nodes || !grid->nodes_c[0]))
+        return fail(OCN_ESTATE, "LagrangianAveraging interpolates at displaced nodes: call ocn_grid_set_nodes and ocn_grid_set_node_tables first");
+    return OCN_OK;
+}
+
+// Average(field, dims = mask) of a ccc field as the diagnostics compute it: the metric where the stretched z is reduced
+static int dynamic_average(ocn_grid_t grid, const double *field, int mask, bool metric, double *out) {
+    ocn_operand_t op = {};
+    op.op = OCN_OP_IDENTITY;
+    op.a = field;
+    return dg_reduce_operation(grid, &op, OCN_REDUCE_AVERAGE, mask, metric && (mask & 4) && !grid->z_regular, 0, nullptr, out);
+}
+
+// compute_coefficient_fields! (dynamic_coefficient.jl:194-217 directional, :292-330 Lagrangian) once the schedule has fired
+static int dynamic_coefficient_update(ocn_grid_t grid, const DynFields &F, int mask, double jmin, const double *u, const double *v, const double *w,
+                                      double dt, bool initialising) {
+    const DGrid &g = grid->d;
+    const bool lagr = mask == 0;
+    DynArgs a = {};
+    a.u = make_view(g, u, LOC_U); a.v = make_view(g, v, LOC_V); a.w = make_view(g, w, LOC_W);
+    a.ub = make_view(g, F.ub, LOC_U); a.vb = make_view(g, F.vb, LOC_V); a.wb = make_view(g, F.wb, LOC_W);
+    a.Sig = make_view(g, F.Sigma, LOC_C); a.Sigb = make_view(g, F.Sigma_bar, LOC_C);
+    a.LM = make_view(g, lagr ? F.J_LM : F.LM, LOC_C); a.MM = make_view(g, lagr ? F.J_MM : F.MM, LOC_C);
+    a.JLMp = make_view(g, lagr ? F.J_LM_prev : F.J_LM, LOC_C); a.JMMp = make_view(g, lagr ? F.J_MM_prev : F.J_MM, LOC_C);
+    a.df2 = grid->df2; a.df = grid->df;
+    a.xc = grid->nodes_c[0]; a.yc = grid->nodes_c[1]; a.zc = grid->nodes_c[2];
+    a.jmin = jmin; a.dt = dt;
+    hipLaunchKernelGGL(dyn_filter_sigma_kernel, grid3(g.Nx + 2, g.Ny + 2, g.Nz + 2, BLK), BLK, 0, g_stream, g, a);
+    KERNEL_CHECK();
+    const dim3 grd = grid3(g.Nx, g.Ny, g.Nz, BLK);
+    hipLaunchKernelGGL(dyn_sigma_bar_kernel, grd, BLK, 0, g_stream, g, a);
+    KERNEL_CHECK();
+    if (!lagr) {
+        hipLaunchKernelGGL(dyn_lm_mm_kernel<false>, grd, BLK, 0, g_stream, g, a, grid->pg);
+        KERNEL_CHECK();
+        int rc = dynamic_average(grid, F.LM, mask, true, F.J_LM);
+        if (!rc) rc = dynamic_average(grid, F.MM, mask, true, F.J_MM);
+        return rc;
+    }
+    int P[3];
+    parent_size(g, LOC_C, P);
+    const long n = (long)P[0] * P[1] * P[2];
+    HIP_TRY(hipMemcpyAsync(F.J_LM_prev, F.J_LM, n * sizeof(double), hipMemcpyDeviceToDevice, g_stream));
+    HIP_TRY(hipMemcpyAsync(F.J_MM_prev, F.J_MM, n * sizeof(double), hipMemcpyDeviceToDevice, g_stream));
+    if (!initialising) {
+        hipLaunchKernelGGL(dyn_lm_mm_kernel<true>, grd, BLK, 0, g_stream, g, a, grid->pg);
+        KERNEL_CHECK();
+        return OCN_OK;
+    }
+    // the first updates: 𝒥 <- LM, MM, then the whole parent <- mean(𝒥) (Statistics.mean: the sum over the number of points, no metric)
+    hipLaunchKernelGGL(dyn_lm_mm_kernel<false>, grd, BLK, 0, g_stream, g, a, grid->pg);
+    KERNEL_CHECK();
+    int rc = dynamic_average(grid, F.J_LM, 7, false, F.mean);
+    if (!rc) rc = dynamic_average(grid, F.J_MM, 7, false, F.mean + 1);
+    if (rc) return rc;
+    const dim3 fg((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(dyn_fill_mean_kernel, fg, dim3(256), 0, g_stream, F.J_LM, n, F.mean, 1, jmin);
+    hipLaunchKernelGGL(dyn_fill_mean_kernel, fg, dim3(256), 0, g_stream, F.J_MM, n, F.mean + 1, 0, jmin);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+// _compute_smagorinsky_viscosity! with the coefficient of the 𝒥 fields over the interior
+static int dynamic_smagorinsky_viscosity(ocn_grid_t grid, int mask, double jmin, const double *J_LM, const double *J_MM, const double *u, const double *v,
+                                         const double *w, double *nu_e) {
+    const DGrid &g = grid->d;
+    SmagArgs a = {};
+    a.r = Range6{1, g.Nx, 1, g.Ny, 1, g.Nz};
+    a.u = make_view(g, u, LOC_U); a.v = make_view(g, v, LOC_V); a.w = make_view(g, w, LOC_W);
+    a.bT = a.u; a.S = a.u;
+    a.nu_e = make_view(g, nu_e, LOC_C);
+    a.df2 = grid->df2;
+    const DgOut where = dg_make_out(g, LOC_C, mask, nullptr);
+    DynCoefficient d = {};
+    d.jlm = J_LM; d.jmm = J_MM; d.off = where.off; d.jmin = jmin;
+    for (int q = 0; q < 3; ++q) d.s[q] = where.s[q];
+    hipLaunchKernelGGL(smagorinsky_viscosity_dynamic_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, a, d);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+extern "C" int ocn_dynamic_smagorinsky_update(ocn_grid_t grid, const double *u, const double *v, const double *w, int averaging_mask,
+                                              double minimum_numerator, double dt, int initialising, double *Sigma, double *Sigma_bar,
+                                              double *LM, double *MM, double *J_LM, double *J_MM, double *J_LM_prev, double *J_MM_prev) {
+    NEED_INIT();
+    if (!grid || !u || !v || !w || !Sigma || !Sigma_bar || !J_LM || !J_MM || averaging_mask < 0 || averaging_mask > 7)
+        return fail(OCN_EINVAL, "invalid argument");
+    if (averaging_mask != 0 && (!LM || !MM)) return fail(OCN_EINVAL, "directional averaging needs the LM and MM fields");
+    if (averaging_mask == 0 && (!J_LM_prev || !J_MM_prev)) return fail(OCN_EINVAL, "LagrangianAveraging needs the previous J fields");
+    if (averaging_mask == 0 && !initialising && !std::isfinite(dt)) return fail(OCN_EINVAL, "dt must be finite");
+    int rc = dynamic_smagorinsky_check_grid(grid, averaging_mask);
+    if (rc) return rc;
+    DynFields F = {Sigma, Sigma_bar, LM, MM, J_LM, J_MM, J_LM_prev, J_MM_prev, nullptr, nullptr, nullptr, nullptr};
+    const int *locs[3] = {LOC_U, LOC_V, LOC_W};
+    double **scratch[3] = {&F.ub, &F.vb, &F.wb};
+    for (int c = 0; c < 3 && !rc; ++c) rc = alloc_parent_zeroed(grid, locs[c], scratch[c]);
+    if (!rc && dev_alloc((void **)&F.mean, 2 * sizeof(double)) != hipSuccess) rc = fail(OCN_ESTATE, "dev_alloc(means)");
+    if (!rc) rc = dynamic_coefficient_update(grid, F, averaging_mask, minimum_numerator, u, v, w, dt, initialising != 0);
+    const hipError_t e = hipStreamSynchronize(g_stream);        // the scratch is this call's
+    hipFree(F.ub); hipFree(F.vb); hipFree(F.wb); hipFree(F.mean);
+    if (!rc && e != hipSuccess) rc = fail((int)e, "hipStreamSynchronize: %s", hipGetErrorString(e));
+    return rc;
+}
+
+extern "C" int ocn_compute_dynamic_smagorinsky_viscosity(ocn_grid_t grid, int averaging_mask, double minimum_numerator, const double *J_LM,
+                                                         const double *J_MM, const double *u, const double *v, const double *w, double *nu_e) {
+    NEED_INIT();
+    if (!grid || !u || !v || !w || !nu_e || !J_LM || !J_MM || averaging_mask < 0 || averaging_mask > 7) return fail(OCN_EINVAL, "invalid argument");
+    const DGrid &g = grid->d;
+    if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT) return fail(OCN_EINVAL, "Smagorinsky needs a grid without Flat directions");
+    if (no_connected_topology(g, "a dynamic Smagorinsky coefficient")) return OCN_ENOTSUP;
+    return dynamic_smagorinsky_viscosity(grid, averaging_mask, minimum_numerator, J_LM, J_MM, u, v, w, nu_e);
+}
+
 extern "C" int ocn_compute_tendencies_and_substep(ocn_grid_t grid, const double *const *fields, int ntracers, double *const *Gn,
                                                   const int *range, double *const *next, const double *const *Gm, double dt,
                                                   double gamma, double zeta, int has_zeta) {
@@ -2349,6 +2483,12 @@ struct Closure {
     double Cnu = 0.0, Ckappa[OCN_MAX_FIELDS] = {};
     double C = 0.0, Cb = 0.0, Pr[OCN_MAX_FIELDS] = {};
     bool lilly = false;
+    // Smagorinsky(coefficient = DynamicCoefficient(averaging, schedule = IterationInterval(interval, offset), minimum_numerator)): kind
+    // SMAGORINSKY with `dynamic`; averaging_mask bit d = direction d + 1 averaged, 0 = LagrangianAveraging
+    bool dynamic = false;
+    int averaging_mask = 0;
+    double minimum_numerator = 0.0;
+    int64_t interval = 1, offset = 0;
     bool eddy() const { return kind == AMD || kind == SMAGORINSKY; }      // the closures with diffusivity fields (Smagorinsky: νₑ only, smagorinsky.jl:131-139)
     // the CLO coordinate of the epilogue kernels (ocn_kernels.h): 0 none, 1 constant ν, κ, 2 coefficient arrays, 3 the same with the tracers'
     // coefficient divided by a Prandtl number (Smagorinsky with some Pr ≠ 1), 4 the explicit part of a vertically implicit ScalarDiffusivity
@@ -2417,6 +2557,13 @@ struct ocn_model_s {
     StokesDrift stokes;
     Particles particles;
     double *nu_e = nullptr, *kappa_e[OCN_MAX_FIELDS] = {};   // diffusivity_fields.νₑ, .κₑ (ccc, with halos): allocated by the setters, kept
+    // the coefficient fields and scratch of a dynamic Smagorinsky closure (allocated by ocn_model_set_dynamic_smagorinsky, freed when another
+    // averaging replaces them and with the model) and diffusivity_fields.previous_compute_time (dynamic_coefficient.jl:342)
+    DynFields dyn = {};
+    double dyn_previous_time = 0.0;
+    // the 𝒥 fields hold nothing yet: set by ocn_model_set_dynamic_smagorinsky and by ocn_model_set_clock (a restored model's 𝒥 are not
+    // checkpointed), cleared by the first update that fires, which takes the initialising branch whatever the clock says
+    bool dyn_uninitialised = true;
     // forcing = (name = F,) (ocn_forcing.h): host copy of the descriptors, the device-resident table the kernels read, the device copies
     // of the tables (per field and term: mask, target)
     ForcingTable forcing_h = {};
@@ -2451,8 +2598,15 @@ struct ocn_model_s {
     size_t events_used = 0;
 };
 
+static void dynamic_fields_free(DynFields &F) {
+    double *all[] = {F.Sigma, F.Sigma_bar, F.LM, F.MM, F.J_LM, F.J_MM, F.J_LM_prev, F.J_MM_prev, F.ub, F.vb, F.wb, F.mean};
+    for (double *p : all) hipFree(p);
+    F = DynFields{};
+}
+
 extern "C" int ocn_model_destroy(ocn_model_t m) {
     if (!m) return OCN_OK;
+    dynamic_fields_free(m->dyn);
     for (auto &e : m->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (m->graph_exec) hipGraphExecDestroy(m->graph_exec);
     for (int f = 0; f < m->nf; ++f) { hipFree(m->U[f]); hipFree(m->U2[f]); hipFree(m->Gn[f]); hipFree(m->Gm[f]); }
@@ -2556,6 +2710,19 @@ static int field_lookup(ocn_model_s *m, const char *name, double ***slot, int **
         if (name[7] < '0' || name[7] > '9' || name[8] || t >= m->ntr) return fail(OCN_EINVAL, "no eddy diffusivity field %s", name);
         *slot = &m->kappa_e[t];
         return OCN_OK;
+    }
+    // the coefficient fields of a dynamic Smagorinsky closure (allocate_coefficient_fields, dynamic_coefficient.jl:219-230,332-345). J_LM and
+    // J_MM of a directional average are REDUCED fields: one point and no halo along every averaged direction
+    {
+        static const char *const names[8] = {"Sigma", "Sigma_bar", "LM", "MM", "J_LM", "J_MM", "J_LM_prev", "J_MM_prev"};
+        double **const slots[8] = {&m->dyn.Sigma, &m->dyn.Sigma_bar, &m->dyn.LM, &m->dyn.MM, &m->dyn.J_LM, &m->dyn.J_MM, &m->dyn.J_LM_prev, &m->dyn.J_MM_prev};
+        for (int q = 0; q < 8; ++q)
+            if (!strcmp(name, names[q])) {
+                if (!m->closure.dynamic) return fail(OCN_ESTATE, "the model has no dynamic Smagorinsky coefficient (no field %s)", name);
+                if (!*slots[q]) return fail(OCN_ESTATE, "%s averaging has no field %s", m->closure.averaging_mask ? "directional" : "Lagrangian", name);
+                *slot = slots[q]; *loc = const_cast<int *>(LOC_C);
+                return OCN_OK;
+            }
     }
     // background_fields: "bg_<name>" is the caller's array, "total_<name>" a velocity component's U + Ū as of the last update_state!
     if (!strncmp(name, "bg_", 3) || !strncmp(name, "total_", 6)) {
@@ -3071,7 +3238,22 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
         // Smagorinsky: the buoyancy is the model's at this moment (nothing: N² = 0), and νₑ is the only field
         if (c.kind == Closure::AMD)
             rc = amd_diffusivities(m->opt, g, c.Cnu, c.Ckappa, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->nu_e, m->kappa_e, amd_range);
-        else
+        else if (c.dynamic) {
+            // compute_coefficient_fields! (dynamic_coefficient.jl:194-217,292-330): previous_compute_time moves on EVERY call, the fields
+            // only where the schedule fires -- (iteration - offset) % interval == 0 with the clock as it stands; the Lagrangian average
+            // initialises while last_Δt is not finite (until the third tick!) or no time has passed -- and, beyond the reference, at the first
+            // update that fires after the closure or the clock was set: the averaging branch would blend with 𝒥⁻ = 0 (T⁻ = Inf, ε = 0) and
+            // leave 𝒥ᴹᴹ = 0, νₑ = 0 for the rest of the run
+            const double dt = m->time - m->dyn_previous_time;
+            m->dyn_previous_time = m->time;
+            rc = OCN_OK;
+            if ((m->iteration - c.offset) % c.interval == 0) {
+                rc = dynamic_coefficient_update(m->grid, m->dyn, c.averaging_mask, c.minimum_numerator, m->U[0], m->U[1], m->U[2], dt,
+                                                m->dyn_uninitialised || !std::isfinite(m->last_dt) || dt == 0);
+                m->dyn_uninitialised = false;
+            }
+            if (!rc) rc = dynamic_smagorinsky_viscosity(m->grid, c.averaging_mask, c.minimum_numerator, m->dyn.J_LM, m->dyn.J_MM, m->U[0], m->U[1], m->U[2], m->nu_e);
+        } else
             rc = smagorinsky_viscosity(m->opt, m->grid, c.C, c.Cb, c.lilly, b.kind, b.kind ? m->U[3 + b.bT] : nullptr, b.kind == 2 ? m->U[3 + b.S] : nullptr,
                                        b.grav, b.alpha, b.beta, m->U[0], m->U[1], m->U[2], m->nu_e, amd_range);
         if (rc) return rc;
@@ -3934,6 +4116,71 @@ extern "C" int ocn_model_set_smagorinsky(ocn_model_t m, double C, double Cb, int
     return OCN_OK;
 }
 
+// closure = Smagorinsky(coefficient = DynamicCoefficient(averaging, schedule = IterationInterval(interval, offset), minimum_numerator), Pr)
+// (dynamic_coefficient.jl:114-117, smagorinsky.jl:62-66); replaces any other closure. Every coefficient field and the scratch of the filtered
+// velocities is allocated here, and the reductions' partial-result slab is grown here, so that a step allocates nothing.
+extern "C" int ocn_model_set_dynamic_smagorinsky(ocn_model_t m, int averaging_mask, double minimum_numerator, int64_t interval, int64_t offset,
+                                                 const double *Pr) {
+    if (m) m->epoch += 1;
+    NEED_INIT();
+    if (!m || (m->ntr > 0 && !Pr)) return fail(OCN_EINVAL, "NULL argument");
+    if (m->dm) return fail(OCN_ENOTSUP, "a dynamic Smagorinsky coefficient is not built for a partitioned model");
+    if (averaging_mask < 0 || averaging_mask > 7) return fail(OCN_EINVAL, "averaging_mask %d: bits 0..2 name the averaged directions, 0 is LagrangianAveraging", averaging_mask);
+    if (interval < 1) return fail(OCN_EINVAL, "the interval of the schedule must be positive");
+    if (minimum_numerator != minimum_numerator) return fail(OCN_EINVAL, "minimum_numerator is NaN");
+    for (int t = 0; t < m->ntr; ++t)
+        if (!(Pr[t] > 0)) return fail(OCN_EINVAL, "the Prandtl number must be positive");
+    int rc = dynamic_smagorinsky_check_grid(m->grid, averaging_mask);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(g_stream));          // a launch already queued may still read the fields of the closure that leaves
+    dynamic_fields_free(m->dyn);
+    DynFields &F = m->dyn;
+    rc = alloc_parent_zeroed(m->grid, LOC_C, &m->nu_e);
+    double **full[] = {&F.Sigma, &F.Sigma_bar};
+    for (double **p : full)
+        if (!rc) rc = alloc_parent_zeroed(m->grid, LOC_C, p);
+    if (!rc) rc = alloc_parent_zeroed(m->grid, LOC_U, &F.ub);
+    if (!rc) rc = alloc_parent_zeroed(m->grid, LOC_V, &F.vb);
+    if (!rc) rc = alloc_parent_zeroed(m->grid, LOC_W, &F.wb);
+    if (!rc && averaging_mask == 0) {
+        double **lag[] = {&F.J_LM, &F.J_MM, &F.J_LM_prev, &F.J_MM_prev};
+        for (double **p : lag)
+            if (!rc) rc = alloc_parent_zeroed(m->grid, LOC_C, p);
+        if (!rc && dev_alloc((void **)&F.mean, 2 * sizeof(double)) != hipSuccess) rc = fail(OCN_ESTATE, "dev_alloc(means)");
+        // (the slab of the two full means)
+        if (!rc) rc = dynamic_average(m->grid, F.J_LM, 7, false, F.mean);
+    } else if (!rc) {
+        rc = alloc_parent_zeroed(m->grid, LOC_C, &F.LM);
+        if (!rc) rc = alloc_parent_zeroed(m->grid, LOC_C, &F.MM);
+        // the reduced fields: the parent extent along every kept direction, one point along an averaged one
+        int P[3];
+        parent_size(m->grid->d, LOC_C, P);
+        size_t n = 1;
+        for (int d = 0; d < 3; ++d) n *= ((averaging_mask >> d) & 1) ? 1 : (size_t)P[d];
+        double **red[] = {&F.J_LM, &F.J_MM};
+        for (double **p : red) {
+            if (rc) break;
+            if (dev_alloc((void **)p, n * sizeof(double)) != hipSuccess) { *p = nullptr; rc = fail(OCN_ESTATE, "dev_alloc(reduced field)"); }
+            else if (hipMemsetAsync(*p, 0, n * sizeof(double), g_stream) != hipSuccess) rc = fail(OCN_ESTATE, "hipMemset(reduced field)");
+        }
+        if (!rc) rc = dynamic_average(m->grid, F.LM, averaging_mask, true, F.J_LM);
+    }
+    if (rc) {
+        dynamic_fields_free(m->dyn);
+        if (m->closure.dynamic) m->closure = Closure();          // its fields are gone
+        return rc;
+    }
+    Closure c;
+    c.kind = Closure::SMAGORINSKY;
+    c.dynamic = true;
+    c.averaging_mask = averaging_mask; c.minimum_numerator = minimum_numerator; c.interval = interval; c.offset = offset;
+    for (int t = 0; t < m->ntr; ++t) c.Pr[t] = Pr[t];
+    m->closure = c;
+    m->dyn_previous_time = m->time;
+    m->dyn_uninitialised = true;
+    return OCN_OK;
+}
+
 // the device-resident table of the model's programs, after the host copy changed (never inside a captured step)
 static int bf_upload(ocn_model_s *m) {
     auto &B = m->bf;
@@ -4230,7 +4477,9 @@ extern "C" int ocn_model_time_step(ocn_model_t m, double dt) {
     }
     // ... and not with a scheme side: the boundary step takes last_stage_Δt, whose corrected third-stage value changes from step to step
     // ... nor with a boundary function or a forcing function that reads t: the time is an argument of its launch
-    if (!m->opt.use_graph || m->profile || m->iteration == 0 || !g_stream_owned || m->n_scheme || m->bf.reads_time || m->ff.reads_time)
+    // ... nor with a dynamic Smagorinsky coefficient: whether an update runs, which branch it takes and its Δt are decided on the host
+    if (!m->opt.use_graph || m->profile || m->iteration == 0 || !g_stream_owned || m->n_scheme || m->bf.reads_time || m->ff.reads_time ||
+        m->closure.dynamic)
         return rk3_time_step(m, dt);
     if (m->graph_exec && m->graph_dt == dt && m->graph_epoch == m->epoch * 1000003ull + g_epoch) {
         hipError_t e = hipGraphLaunch(m->graph_exec, g_stream);
@@ -4307,6 +4556,8 @@ extern "C" int ocn_model_reset(ocn_model_t m) {
     NEED_INIT();
     if (!m) return fail(OCN_EINVAL, "NULL argument");
     m->time = 0; m->iteration = 0; m->stage = 1; m->last_dt = INFINITY; m->last_stage_dt = INFINITY;
+    m->dyn_previous_time = 0.0;            // (a dynamic Smagorinsky coefficient starts again, as after ocn_model_set_clock)
+    m->dyn_uninitialised = true;
     const DGrid &g = m->grid->d;
     for (int f = 0; f < m->nf; ++f) {
         int P[3];
@@ -4335,6 +4586,10 @@ extern "C" int ocn_model_set_clock(ocn_model_t m, double time, int64_t iteration
     if (iteration < 0 || stage < 1 || stage > 3) return fail(OCN_EINVAL, "invalid clock (iteration %lld, stage %d)", (long long)iteration, stage);
     m->epoch += 1;
     m->time = time; m->iteration = iteration; m->stage = stage; m->last_dt = last_dt; m->last_stage_dt = last_stage_dt;
+    // a dynamic Smagorinsky coefficient starts again from the fields the caller restores: no time has passed since "the previous call", and
+    // the 𝒥 fields (not part of a checkpoint) are initialised by the next update that fires
+    m->dyn_previous_time = time;
+    m->dyn_uninitialised = true;
     return OCN_OK;
 }
 

@@ -657,13 +657,20 @@ template <int BK> __device__ __forceinline__ double smag_dzb(const SmagArgs &a, 
 // what a cell is assembled from: the three diagonal strain components, the three interpolated squares and ∂z_b below and above the cell
 struct SmagCell { double s11, s22, s33, ixy12, ixz13, iyz23, dzb_k, dzb_k1; };
 
-// the one assembly of a cell, shared by the per-cell and the marching kernel (=> bit-identical)
-template <bool LILLY>
-__device__ __forceinline__ double smagorinsky_viscosity(const SmagCell &c, const SmagArgs &a, double df2) {
+// Σ² of a cell: ΣᵢⱼΣᵢⱼᶜᶜᶜ (scale_invariant_operators.jl:10-13), also of the filtered velocities (Σ̄ᵢⱼΣ̄ᵢⱼᶜᶜᶜ, :119-122; ocn_dynamic_smagorinsky.h)
+__device__ __forceinline__ double smag_strain_squared(const SmagCell &c) {
     double s2 = c.s11 * c.s11 + c.s22 * c.s22;
     s2 = s2 + c.s33 * c.s33;
     s2 = s2 + 2 * c.ixy12; s2 = s2 + 2 * c.ixz13; s2 = s2 + 2 * c.iyz23;
-    double cs2 = a.C * a.C;
+    return s2;
+}
+
+// the one assembly of a cell, shared by the per-cell and the marching kernel (=> bit-identical). DYN: cs² is the caller's `cs2_dyn`, the
+// dynamic coefficient of the cell (dynamic_coefficient.jl:129-140), instead of C C
+template <bool LILLY, bool DYN = false>
+__device__ __forceinline__ double smagorinsky_viscosity(const SmagCell &c, const SmagArgs &a, double df2, double cs2_dyn = 0.0) {
+    const double s2 = smag_strain_squared(c);
+    double cs2 = DYN ? cs2_dyn : a.C * a.C;
     if (LILLY) {
         const double N2 = 0.5 * (c.dzb_k + c.dzb_k1);
         const double N2p = fmax(0.0, N2);

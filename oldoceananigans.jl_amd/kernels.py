@@ -283,6 +283,40 @@ def compute_smagorinsky_viscosity(grid, closure, buoyancy, tracers_by_name, u, v
                                                             u.data, v.data, w.data, νₑ.data, _range(kernel_parameters)))
 
 
+def dynamic_coefficient_fields(grid, coefficient):
+    """allocate_coefficient_fields (dynamic_coefficient.jl:219-230, 332-345) as a dict of zeroed Fields under the library's names: Sigma,
+    Sigma_bar, J_LM, J_MM and LM, MM (directional; J_LM, J_MM reduced along the averaged directions) or J_LM_prev, J_MM_prev (Lagrangian)"""
+    from .fields import CenterField, Field
+    from .grids import Center
+    mask = coefficient.averaging_mask
+    reduced = tuple(None if (mask >> d) & 1 else Center for d in range(3))
+    names = ("Sigma", "Sigma_bar", "LM", "MM") if mask else ("Sigma", "Sigma_bar", "J_LM", "J_MM", "J_LM_prev", "J_MM_prev")
+    out = {n: CenterField(grid) for n in names}
+    if mask:
+        out["J_LM"], out["J_MM"] = Field(reduced, grid), Field(reduced, grid)
+    for f in out.values():
+        _lib.check(_lib.lib().ocn_memset_zero(f.data, f.nbytes))
+    return out
+
+
+def dynamic_smagorinsky_update(grid, coefficient, u, v, w, fields, Δt=0.0, initialising=True):
+    """one update of the coefficient fields of Smagorinsky(coefficient = DynamicCoefficient(...)) -- compute_coefficient_fields! once the
+    schedule has fired (dynamic_coefficient.jl:194-217, 292-330). u, v, w with filled halos; `fields` as dynamic_coefficient_fields makes
+    them. Lagrangian averaging: `initialising` takes the first-time-step branch, else the averaging step over Δt"""
+    ptr = lambda n: fields[n].data if n in fields else None                  # noqa: E731
+    _lib.check(_lib.lib().ocn_dynamic_smagorinsky_update(grid.handle, u.data, v.data, w.data, coefficient.averaging_mask,
+                                                         coefficient.minimum_numerator, float(Δt), int(bool(initialising)), ptr("Sigma"),
+                                                         ptr("Sigma_bar"), ptr("LM"), ptr("MM"), ptr("J_LM"), ptr("J_MM"), ptr("J_LM_prev"),
+                                                         ptr("J_MM_prev")))
+
+
+def compute_dynamic_smagorinsky_viscosity(grid, coefficient, fields, u, v, w, νₑ):
+    """_compute_smagorinsky_viscosity! with the coefficient of fields["J_LM"], fields["J_MM"] (smagorinsky.jl:92-106, dynamic_coefficient.jl:
+    129-140) over the interior; fill the halos of νₑ afterwards"""
+    _lib.check(_lib.lib().ocn_compute_dynamic_smagorinsky_viscosity(grid.handle, coefficient.averaging_mask, coefficient.minimum_numerator,
+                                                                    fields["J_LM"].data, fields["J_MM"].data, u.data, v.data, w.data, νₑ.data))
+
+
 def compute_closure_tendencies_smagorinsky(grid, fields, Gn, νₑ, closure, tracer_names, kernel_parameters=None):
     """adds -∂ⱼτᵢⱼ with νₑ and -∇·q with ℑ(νₑ) / Pr[tracer] (smagorinsky.jl:141-143); fields = u, v, w, tracers..., νₑ with filled halos"""
     parr, pp = closure.Pr_array(tracer_names)

@@ -71,6 +71,8 @@ class NonhydrostaticModel:
         if closure is not None and not isinstance(closure, (ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky)):
             raise NotImplementedError("only closure = nothing | ScalarDiffusivity(ν, κ) | AnisotropicMinimumDissipation(C, Cν, Cκ) | "
                                       "Smagorinsky(coefficient, Pr) | SmagorinskyLilly(C, Cb, Pr) is on the accelerated path (SURVEY.md 8f)")
+        if getattr(closure, "dynamic", False) and hasattr(grid, "local"):
+            raise NotImplementedError("Smagorinsky with a DynamicCoefficient is not served on partitioned grids")
         from .closures import is_vertically_implicit
         from .grids import Bounded
         if is_vertically_implicit(closure) and getattr(grid, "local", grid).topology[2] is not Bounded:
@@ -159,11 +161,27 @@ class NonhydrostaticModel:
             self.diffusivity_fields = D(self._field("nu_e"), K(*[self._field("kappa_e%d" % n) for n in range(len(self.tracer_names))]))
         elif isinstance(closure, Smagorinsky):
             self._kappa, pp = closure.Pr_array(self.tracer_names)
-            _lib.check(_lib.lib().ocn_model_set_smagorinsky(self.handle, closure.coefficient, closure.Cb, int(closure.lilly), pp))
-            # build_diffusivity_fields (smagorinsky.jl:131-139): νₑ only
             import unicodedata
-            D = namedtuple("DiffusivityFields", [unicodedata.normalize("NFKC", "νₑ")])
-            self.diffusivity_fields = D(self._field("nu_e"))
+            if closure.dynamic:
+                # allocate_coefficient_fields (dynamic_coefficient.jl:219-230, 332-345) merged behind νₑ (smagorinsky.jl:131-139). The
+                # reference's names come first, NFKC-normalised as Python does with identifiers; ASCII aliases are properties beside them
+                dc = closure.coefficient
+                _lib.check(_lib.lib().ocn_model_set_dynamic_smagorinsky(self.handle, dc.averaging_mask, dc.minimum_numerator,
+                                                                        dc.schedule.interval, dc.schedule.offset, pp))
+                reduced = tuple(None if (dc.averaging_mask >> d) & 1 else Center for d in range(3))
+                ccc = (Center, Center, Center)
+                if dc.averaging_mask:
+                    spec = [("Σ", "Sigma", ccc), ("Σ̄", "Sigma_bar", ccc), ("LM", "LM", ccc), ("MM", "MM", ccc),
+                            ("𝒥ᴸᴹ", "J_LM", reduced), ("𝒥ᴹᴹ", "J_MM", reduced)]
+                else:
+                    spec = [("Σ", "Sigma", ccc), ("Σ̄", "Sigma_bar", ccc), ("𝒥ᴸᴹ", "J_LM", ccc), ("𝒥ᴹᴹ", "J_MM", ccc),
+                            ("𝒥ᴸᴹ⁻", "J_LM_prev", ccc), ("𝒥ᴹᴹ⁻", "J_MM_prev", ccc)]
+                self.diffusivity_fields = _dynamic_diffusivity_fields(self, [("νₑ", "nu_e", ccc)] + spec)
+            else:
+                _lib.check(_lib.lib().ocn_model_set_smagorinsky(self.handle, closure.coefficient, closure.Cb, int(closure.lilly), pp))
+                # build_diffusivity_fields (smagorinsky.jl:131-139): νₑ only
+                D = namedtuple("DiffusivityFields", [unicodedata.normalize("NFKC", "νₑ")])
+                self.diffusivity_fields = D(self._field("nu_e"))
         elif closure is not None:
             self._kappa, kp = closure.kappa_array(self.tracer_names)
             _lib.check(_lib.lib().ocn_model_set_closure(self.handle, closure.ν, kp))
@@ -193,7 +211,7 @@ class NonhydrostaticModel:
                     raise ValueError(f"boundary conditions given for {name}, but the closure has no diffusivity fields")
                 if key in ("νe", "nu_e"):
                     targets.append(("nu_e", fbcs))
-                elif len(self.diffusivity_fields) < 2:
+                elif "κe" not in self.diffusivity_fields._fields:
                     raise ValueError(f"boundary conditions given for {name}, but the closure's diffusivity fields are νₑ only")
                 else:
                     for tracer, tb in dict(fbcs).items():
@@ -306,6 +324,26 @@ class NonhydrostaticModel:
             self.close()
         except Exception:
             pass
+
+
+def _dynamic_diffusivity_fields(model, spec):
+    """the diffusivity fields of a dynamic Smagorinsky closure as a named tuple: per entry the reference's name, the library's name and the
+    location (None along an averaged direction: one point, no halo). A name is spelt as Python spells the identifier (NFKC: 𝒥ᴸᴹ is JLM),
+    the library's ASCII name where that is no identifier (𝒥ᴸᴹ⁻); the ASCII names are attributes as well"""
+    import unicodedata
+    names = []
+    for reference, ascii_name, _ in spec:
+        n = unicodedata.normalize("NFKC", reference)
+        names.append(n if n.isidentifier() else ascii_name)
+    base = namedtuple("DiffusivityFields", names)
+    aliases = {a: q for q, ((_, a, _), n) in enumerate(zip(spec, names)) if a != n}
+    D = type("DiffusivityFields", (base,), dict({a: property(lambda self, q=q: self[q]) for a, q in aliases.items()}, __slots__=()))
+    fields = []
+    for _, ascii_name, loc in spec:
+        p = C.c_void_p()
+        _lib.check(_lib.lib().ocn_model_field(model.handle, ascii_name.encode(), C.byref(p), None))
+        fields.append(Field(loc, model.grid, data=p))
+    return D(*fields)
 
 
 def set_model(model, enforce_incompressibility=True, **kwargs):
