@@ -95,6 +95,27 @@ int ocn_grid_set_nodes(ocn_grid_t grid, const double first_face[3], const double
  * keeps hold addresses inside it. */
 int ocn_grid_set_node_tables(ocn_grid_t grid, const double *const faces[3], const double *const centers[3]);
 
+/* ---------------------------------------------------------------- immersed boundaries (ImmersedBoundaries/) ----- */
+/* ImmersedBoundaryGrid(grid, GridFittedBottom | GridFittedBoundary) (immersed_boundary_grid.jl, grid_fitted_bottom.jl:99-130,
+ * grid_fitted_boundary.jl): the grid gets a grid-fitted immersed boundary. `immersed_cell` is a HOST array, parent-shaped at (Center,
+ * Center, Center), halos filled by the caller, 1 = immersed_cell(i, j, k, ibg); NULL clears the boundary. One kernel builds the two device
+ * tables everything else reads (csrc/ocn_immersed.h: the periphery byte replaces inactive_cell / immersed_peripheral_node of
+ * immersed_boundary_interface.jl:49-54, the orders word the near_*_immersed_boundary_* tests of Advection/immersed_advective_fluxes.jl:
+ * 121-183). Needs a halo of the advection buffer + 1 in every non-Flat direction (inflate_halo_size_one_dimension(req, old, _, ::IBG),
+ * OCN_EINVAL otherwise) and must be called before a model is created on the grid (OCN_ESTATE otherwise). */
+int ocn_grid_set_immersed_boundary(ocn_grid_t grid, const uint8_t *immersed_cell);
+/* copies the periphery bytes and the orders words (parent-shaped at ccc; either pointer may be NULL) to the HOST; OCN_ESTATE on a grid
+ * without a boundary */
+int ocn_grid_get_immersed_flags(ocn_grid_t grid, uint8_t *periphery, uint16_t *orders);
+/* mask_immersed_field!(field, value) (mask_immersed_field.jl:53-64): field = value at immersed_peripheral_node of `loc` over :xyz; nothing
+ * on a grid without a boundary (the fallback of :46) */
+int ocn_mask_immersed_field(ocn_grid_t grid, double *field, const int loc[3], double value);
+/* On a grid with a boundary ocn_compute_Gu/Gv/Gw/Gc, ocn_compute_tendencies, ocn_compute_advective_tendency, ocn_add_fplane_coriolis and
+ * ocn_compute_closure_tendencies evaluate the immersed methods (conditional fluxes, the boundary-aware cascade); every other closure entry
+ * point, the diagnostics and the partitioned models answer OCN_ENOTSUP there. ocn_model_get_option: "immersed" 0 / 1 and
+ * "immersed_tendency_path" (0 no boundary, 1 one field per launch, 2 the flux-sharing role kernel: grids periodic in x and y without a Flat
+ * direction under tendency_impl 2; tendency_impl 0 forces path 1; both give the same bits). */
+
 /* ---------------------------------------------------------------- halo fills (BoundaryConditions/) -------------- */
 /* fill_halo_regions!(field) with the default boundary conditions of field_boundary_conditions.jl:15-25
  * (Periodic -> PeriodicBC copies, fill_halo_regions_periodic.jl:5-33; Bounded+Center -> no-flux one-cell mirror,

@@ -22,6 +22,8 @@ from .forcings import (AdvectiveForcing, ContinuousForcing, DiscreteForcing, For
 from .fields import (CenterField, Field, XFaceField, YFaceField, ZFaceField, fill_halo_regions, interior, set_)
 from .grids import (Bounded, Center, Face, Flat, FullyConnected, LeftConnected, NegativeZDirection, Periodic, RectilinearGrid, RightConnected,
                     ZDirection, validate_unit_vector, with_halo)
+from .immersed_boundaries import (CenterImmersedCondition, GridFittedBottom, GridFittedBoundary, ImmersedBoundaryCondition, ImmersedBoundaryGrid,
+                                  InterfaceImmersedCondition, PartialCellBottom, mask_immersed_field)
 from .models import NonhydrostaticModel, max_abs_divergence, set_model, time_step, update_state
 from .solvers import (FFTBasedPoissonSolver, FourierTridiagonalPoissonSolver, batched_tridiagonal_solve_z, solve,
                       solve_for_pressure)

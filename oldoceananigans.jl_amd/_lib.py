@@ -148,6 +148,9 @@ SYMBOLS = {
     "ocn_model_set_open_boundary_scheme": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_int, C.c_double, C.c_double]),
     "ocn_model_set_linear_flux_bc": (C.c_int, [_vp, C.c_char_p, C.c_int, C.c_double, C.c_double, C.c_char_p]),
     "ocn_grid_set_node_tables": (C.c_int, [_vp, C.POINTER(_dp), C.POINTER(_dp)]),
+    "ocn_grid_set_immersed_boundary": (C.c_int, [_vp, C.POINTER(C.c_ubyte)]),
+    "ocn_grid_get_immersed_flags": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.POINTER(C.c_ushort)]),
+    "ocn_mask_immersed_field": (C.c_int, [_vp, _vp, _ip, C.c_double]),
     "ocn_evaluate_boundary_function": (C.c_int, [_vp, C.POINTER(ExprIns), C.c_int, _ip, C.c_int, _pp, _vp, C.c_int, C.c_double, _vp]),
     "ocn_model_set_flux_bc_function": (C.c_int, [_vp, C.c_char_p, C.c_int, C.POINTER(ExprIns), C.c_int, C.POINTER(C.c_char_p), C.c_int]),
     "ocn_model_boundary_function_values": (C.c_int, [_vp, C.c_char_p, C.c_int, _dp]),

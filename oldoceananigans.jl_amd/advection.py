@@ -149,7 +149,9 @@ def inflate_halo_size(Hx, Hy, Hz, grid, *tendency_terms):
     """Grids/automatic_halo_sizing.jl:68-83"""
     from .grids import Flat
     H = [Hx, Hy, Hz]
+    # inflate_halo_size_one_dimension(req_H, old_H, _, ::ImmersedBoundaryGrid) = max(req_H + 1, old_H) (immersed_boundary_grid.jl:100-103)
+    extra = 1 if hasattr(grid, "immersed_boundary") else 0
     for term in tendency_terms:
         req = (required_halo_size_x(term), required_halo_size_y(term), required_halo_size_z(term))
-        H = [0 if t is Flat else max(r, h) for r, h, t in zip(req, H, grid.topology)]
+        H = [0 if t is Flat else max(r + extra, h) for r, h, t in zip(req, H, grid.topology)]
     return tuple(H)

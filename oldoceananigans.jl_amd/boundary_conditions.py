@@ -190,6 +190,10 @@ class FieldBoundaryConditions:
     field_boundary_conditions.jl:15-25 (Periodic -> periodic, Bounded + Center -> no flux, Bounded + Face -> impenetrable)"""
 
     def __init__(self, **sides):
+        if sides.pop("immersed", None) is not None:
+            # FieldBoundaryConditions(immersed = ...) (field_boundary_conditions.jl, immersed_boundary_condition.jl)
+            from .immersed_boundaries import refuse
+            refuse("FieldBoundaryConditions(immersed=...) (a boundary condition on the immersed boundary)")
         for s, bc in sides.items():
             if s not in SIDES:
                 raise ValueError(f"unknown side {s}; expected one of {SIDES}")

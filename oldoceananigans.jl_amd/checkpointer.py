@@ -27,8 +27,15 @@ from . import _lib
 ADDRESS = "NonhydrostaticModel"          # checkpointer_address(::NonhydrostaticModel)
 
 
+def _refuse_immersed(model):
+    if hasattr(model.grid, "immersed_boundary"):
+        from .immersed_boundaries import refuse
+        refuse("the checkpointer (the boundary is not part of a checkpoint)")
+
+
 def write_checkpoint(model, filepath):
     """write_output!(::Checkpointer, model) (checkpointer.jl:161-183) into `filepath` (.npz)"""
+    _refuse_immersed(model)
     out = {}
     for name, field in model.fields().items():
         out[f"{ADDRESS}/{name}/data"] = field.parent()
@@ -53,6 +60,7 @@ def write_checkpoint(model, filepath):
 def set_from_checkpoint(model, filepath):
     """set!(model, filepath::AbstractString) (checkpointer.jl:199-231): prognostic fields, tendencies and clock from the file"""
     from .models import update_state
+    _refuse_immersed(model)
     with np.load(filepath, allow_pickle=False) as file:
         grid = model.grid.local if hasattr(model.grid, "local") else model.grid
         if tuple(file[f"{ADDRESS}/grid/size"]) != tuple(grid.size) or tuple(file[f"{ADDRESS}/grid/halo"]) != tuple(grid.halo_size):

@@ -196,6 +196,11 @@ struct ocn_grid_s {
     // node tables for functions of the coordinates (ocn_grid_set_node_tables): per direction N + 1 face and N centre nodes, one device block
     double *node_tables = nullptr;
     const double *nodes_f[3] = {}, *nodes_c[3] = {};
+    // a grid-fitted immersed boundary (ocn_grid_set_immersed_boundary, ocn_immersed.h): the periphery bytes and the orders words, both
+    // parent-shaped at ccc (NULL: none), and the number of live models on the grid -- the boundary may not change under one
+    unsigned char *imm_periph = nullptr;
+    unsigned short *imm_orders = nullptr;
+    int models = 0;
 };
 
 static void parent_size(const DGrid &g, const int loc[3], int P[3]) {
@@ -214,6 +219,20 @@ static FView make_view(const DGrid &g, const double *p, const int loc[3]) {
     v.off = (g.Hx - 1) + (long)v.s1 * (g.Hy - 1) + v.s2 * (g.Hz - 1);
     return v;
 }
+
+// the immersed tables of a grid as the kernels read them (periph == NULL: the grid has no boundary)
+static ImmView imm_view(const ocn_grid_s *grid) {
+    const DGrid &g = grid->d;
+    ImmView v = {};
+    v.periph = grid->imm_periph; v.orders = grid->imm_orders;
+    const long P0 = g.Nx + 2 * g.Hx, P1 = g.Ny + 2 * g.Hy;
+    v.sx = g.tx == OCN_FLAT ? 0 : 1;
+    v.sy = g.ty == OCN_FLAT ? 0 : (int)P0;
+    v.sz = g.tz == OCN_FLAT ? 0 : P0 * P1;
+    v.off = (long)v.sx * (g.Hx - 1) + (long)v.sy * (g.Hy - 1) + v.sz * (g.Hz - 1);
+    return v;
+}
+static bool is_immersed(const ocn_grid_s *grid) { return grid && grid->imm_periph != nullptr; }
 
 static const int LOC_U[3] = {OCN_FACE, OCN_CENTER, OCN_CENTER};
 static const int LOC_V[3] = {OCN_CENTER, OCN_FACE, OCN_CENTER};
@@ -319,6 +338,8 @@ extern "C" int ocn_grid_destroy(ocn_grid_t grid) {
     hipFree(grid->diag_program);
     if (grid->diag_program_copied) hipEventDestroy(grid->diag_program_copied);
     hipFree(grid->node_tables);
+    hipFree(grid->imm_periph);
+    hipFree(grid->imm_orders);
     delete grid;
     return OCN_OK;
 }
@@ -639,11 +660,105 @@ extern "C" int ocn_compute_flux_bcs(ocn_grid_t grid, double *G, const int loc[3]
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// immersed boundaries (ocn_immersed.h)
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int ocn_grid_set_immersed_boundary(ocn_grid_t grid, const unsigned char *immersed_cell) {
+    NEED_INIT();
+    if (!grid) return fail(OCN_EINVAL, "NULL argument");
+    if (grid->models > 0) return fail(OCN_ESTATE, "the immersed boundary of a grid is set before a model is created on it (%d live)", grid->models);
+    const DGrid &g = grid->d;
+    HIP_TRY(hipStreamSynchronize(g_stream));          // a launch already queued may still read the old tables
+    if (!immersed_cell) {
+        hipFree(grid->imm_periph); hipFree(grid->imm_orders);
+        grid->imm_periph = nullptr; grid->imm_orders = nullptr;
+        return OCN_OK;
+    }
+    auto connected = [](int t) { return t == OCN_CONNECTED || t == OCN_RIGHT_CONNECTED || t == OCN_LEFT_CONNECTED; };
+    if (connected(g.tx) || connected(g.ty)) return fail(OCN_ENOTSUP, "ImmersedBoundaryGrid on a partitioned grid is not built");
+    ImmGeometry G = {{g.Nx, g.Ny, g.Nz}, {g.Hx, g.Hy, g.Hz}, {g.tx, g.ty, g.tz}};
+    const int B[3] = {g.Bx, g.By, g.Bz};
+    for (int d = 0; d < 3; ++d)
+        if (G.T[d] != OCN_FLAT && G.H[d] < B[d] + 1)
+            return fail(OCN_EINVAL, "halo %d < %d in dimension %d: an immersed grid needs the advection buffer + 1 "
+                                    "(inflate_halo_size_one_dimension(req, old, _, ::ImmersedBoundaryGrid) = max(req + 1, old))", G.H[d], B[d] + 1, d);
+    const size_t n = (size_t)(g.Nx + 2 * g.Hx) * (g.Ny + 2 * g.Hy) * (g.Nz + 2 * g.Hz);
+    unsigned char *cell = nullptr, *periph = grid->imm_periph;
+    unsigned short *orders = grid->imm_orders;
+    hipError_t e = dev_alloc((void **)&cell, n);
+    if (e == hipSuccess && !periph) e = dev_alloc((void **)&periph, n);
+    if (e == hipSuccess && !orders) e = dev_alloc((void **)&orders, n * sizeof(unsigned short));
+    if (e == hipSuccess) e = hipMemcpy(cell, immersed_cell, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(immersed_flags_kernel, grid3(g.Nx + 2 * g.Hx, g.Ny + 2 * g.Hy, g.Nz + 2 * g.Hz, BLK), BLK, 0, g_stream, G,
+                           (const unsigned char *)cell, periph, orders);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(g_stream);          // `cell` is released below
+    }
+    hipFree(cell);
+    if (e != hipSuccess) {
+        if (!grid->imm_periph) hipFree(periph);
+        if (!grid->imm_orders) hipFree(orders);
+        return fail((int)e, "ocn_grid_set_immersed_boundary: %s", hipGetErrorString(e));
+    }
+    grid->imm_periph = periph; grid->imm_orders = orders;
+    return OCN_OK;
+}
+
+extern "C" int ocn_grid_get_immersed_flags(ocn_grid_t grid, unsigned char *periphery, unsigned short *orders) {
+    NEED_INIT();
+    if (!grid) return fail(OCN_EINVAL, "NULL argument");
+    if (!is_immersed(grid)) return fail(OCN_ESTATE, "the grid has no immersed boundary");
+    const DGrid &g = grid->d;
+    const size_t n = (size_t)(g.Nx + 2 * g.Hx) * (g.Ny + 2 * g.Hy) * (g.Nz + 2 * g.Hz);
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    if (periphery) HIP_TRY(hipMemcpy(periphery, grid->imm_periph, n, hipMemcpyDeviceToHost));
+    if (orders) HIP_TRY(hipMemcpy(orders, grid->imm_orders, n * sizeof(unsigned short), hipMemcpyDeviceToHost));
+    return OCN_OK;
+}
+
+// the periphery bit mask_immersed_field! tests for a field at `loc`; -1: (Face, Face, Face), which no field of the model has
+static int imm_location_bit(const int loc[3]) {
+    const int faces = (loc[0] == OCN_FACE ? 1 : 0) | (loc[1] == OCN_FACE ? 2 : 0) | (loc[2] == OCN_FACE ? 4 : 0);
+    static const int bit_of[8] = {IMM_CCC, IMM_FCC, IMM_CFC, IMM_FFC, IMM_CCF, IMM_FCF, IMM_CFF, -1};
+    return bit_of[faces];
+}
+
+// mask_immersed_field! of n fields in one launch; nothing on a grid without a boundary
+static int mask_immersed_fields(const ocn_grid_s *grid, double *const *fields, const int (*locs)[3], int n, double value) {
+    if (!is_immersed(grid) || n <= 0) return OCN_OK;
+    const DGrid &g = grid->d;
+    ImmMaskList L = {};
+    L.n = n;
+    for (int q = 0; q < n; ++q) {
+        L.f[q] = make_view(g, fields[q], locs[q]);
+        L.bit[q] = imm_location_bit(locs[q]);
+        if (L.bit[q] < 0) return fail(OCN_EINVAL, "mask_immersed_field: no field lives at (Face, Face, Face)");
+    }
+    hipLaunchKernelGGL(mask_immersed_kernel, grid3(g.Nx, g.Ny, g.Nz * n, BLK), BLK, 0, g_stream, imm_view(grid), L, value, g.Nx, g.Ny, g.Nz);
+    KERNEL_CHECK();
+    return OCN_OK;
+}
+
+extern "C" int ocn_mask_immersed_field(ocn_grid_t grid, double *field, const int loc[3], double value) {
+    NEED_INIT();
+    if (!grid || !field || !loc) return fail(OCN_EINVAL, "NULL argument");
+    double *f[1] = {field};
+    const int l[1][3] = {{loc[0], loc[1], loc[2]}};
+    return mask_immersed_fields(grid, f, l, 1, value);
+}
+
+// what an immersed grid does not serve: OCN_ENOTSUP naming the grid and the feature
+static int refuse_immersed(const ocn_grid_s *grid, const char *feature) {
+    if (!is_immersed(grid)) return OCN_OK;
+    return fail(OCN_ENOTSUP, "%s is not served on an ImmersedBoundaryGrid", feature);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // tendencies
 // ---------------------------------------------------------------------------------------------------------------------
 template <int F>
 static int launch_tendency(const DGrid &g, const double *u, const double *v, const double *w, const double *c, double *G,
-                           const int *range) {
+                           const int *range, const ImmView *im = nullptr) {
     const int *loc = F == F_U ? LOC_U : (F == F_V ? LOC_V : (F == F_W ? LOC_W : LOC_C));
     Range6 r;
     int rc = check_range(g, range, &r, loc, F != F_C);
@@ -652,7 +767,10 @@ static int launch_tendency(const DGrid &g, const double *u, const double *v, con
     if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;   // "Don't launch kernels with no size" (kernel_launching.jl:370)
     FView fu = make_view(g, u, LOC_U), fv = make_view(g, v, LOC_V), fw = make_view(g, w, LOC_W);
     FView fc = make_view(g, c ? c : u, LOC_C), fG = make_view(g, G, loc);
-    hipLaunchKernelGGL(tendency_kernel<F>, grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, fu, fv, fw, fc, fG, r);
+    // on an immersed grid the advected field is u, v, w or c itself (immersed_tendency_kernel names it apart from the advecting velocities)
+    if (im) hipLaunchKernelGGL((immersed_tendency_kernel<F, false>), grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, *im, fu, fv, fw,
+                               F == F_U ? fu : (F == F_V ? fv : (F == F_W ? fw : fc)), fG, r);
+    else hipLaunchKernelGGL(tendency_kernel<F>, grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, fu, fv, fw, fc, fG, r);
     KERNEL_CHECK();
     return OCN_OK;
 }
@@ -661,26 +779,30 @@ extern "C" int ocn_compute_Gu(ocn_grid_t grid, const double *u, const double *v,
     NEED_INIT();
     if (!grid || !u || !v || !w || !Gu) return fail(OCN_EINVAL, "NULL argument");
     if (!grid->advection_error.empty()) return fail(OCN_EINVAL, "%s", grid->advection_error.c_str());
-    return launch_tendency<F_U>(grid->d, u, v, w, nullptr, Gu, range);
+    const ImmView im = imm_view(grid);
+    return launch_tendency<F_U>(grid->d, u, v, w, nullptr, Gu, range, is_immersed(grid) ? &im : nullptr);
 }
 extern "C" int ocn_compute_Gv(ocn_grid_t grid, const double *u, const double *v, const double *w, double *Gv, const int *range) {
     NEED_INIT();
     if (!grid || !u || !v || !w || !Gv) return fail(OCN_EINVAL, "NULL argument");
     if (!grid->advection_error.empty()) return fail(OCN_EINVAL, "%s", grid->advection_error.c_str());
-    return launch_tendency<F_V>(grid->d, u, v, w, nullptr, Gv, range);
+    const ImmView im = imm_view(grid);
+    return launch_tendency<F_V>(grid->d, u, v, w, nullptr, Gv, range, is_immersed(grid) ? &im : nullptr);
 }
 extern "C" int ocn_compute_Gw(ocn_grid_t grid, const double *u, const double *v, const double *w, double *Gw, const int *range) {
     NEED_INIT();
     if (!grid || !u || !v || !w || !Gw) return fail(OCN_EINVAL, "NULL argument");
     if (!grid->advection_error.empty()) return fail(OCN_EINVAL, "%s", grid->advection_error.c_str());
-    return launch_tendency<F_W>(grid->d, u, v, w, nullptr, Gw, range);
+    const ImmView im = imm_view(grid);
+    return launch_tendency<F_W>(grid->d, u, v, w, nullptr, Gw, range, is_immersed(grid) ? &im : nullptr);
 }
 extern "C" int ocn_compute_Gc(ocn_grid_t grid, const double *u, const double *v, const double *w, const double *c, double *Gc,
                               const int *range) {
     NEED_INIT();
     if (!grid || !u || !v || !w || !c || !Gc) return fail(OCN_EINVAL, "NULL argument");
     if (!grid->advection_error.empty()) return fail(OCN_EINVAL, "%s", grid->advection_error.c_str());
-    return launch_tendency<F_C>(grid->d, u, v, w, c, Gc, range);
+    const ImmView im = imm_view(grid);
+    return launch_tendency<F_C>(grid->d, u, v, w, c, Gc, range, is_immersed(grid) ? &im : nullptr);
 }
 
 static bool fused_path(const OcnOptions &o, const DGrid &g, const int *range, int ntr, int impl) {
@@ -690,9 +812,29 @@ static bool fused_path(const OcnOptions &o, const DGrid &g, const int *range, in
            ((impl == 2 && role_tendency_supported(o, g)) || fused_tendency_size_supported(g));
 }
 
+// whether an immersed grid's tendencies take the flux-sharing kernel (immersed_role_tendency_kernel): tendency_impl 2 (0 forces the per-field
+// kernels), reference arithmetic, x and y Periodic, no Flat or reduced-order direction, planes the role kernel's offsets reach
+static bool immersed_role_path(const OcnOptions &o, const DGrid &g, const int *range, int ntr, int impl) {
+    return impl == 2 && o.arithmetic == 0 && ntr <= 3 && g.tx == OCN_PERIODIC && g.ty == OCN_PERIODIC && fused_tendency_supported(g, range) &&
+           role_tendency_supported(o, g);
+}
+
 static int compute_tendencies(const OcnOptions &o, const DGrid &g, const double *u, const double *v, const double *w, const double *const *tr,
                               int ntr, double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range, int impl,
-                              const FusedSubstep *sub = nullptr, const ForcingTable *ftab = nullptr) {
+                              const FusedSubstep *sub = nullptr, const ForcingTable *ftab = nullptr, const ImmView *im = nullptr) {
+    // an immersed grid takes the immersed instantiation of the role kernel ("immersed_tendency_path" 2) where that kernel serves the grid
+    // and tendency_impl asks for it, else the per-field kernels, one field per launch (path 1); the two give the same bits
+    if (im) {
+        if (sub || ftab) return fail(OCN_ESTATE, "fused substep or forcing requested in the tendency launch of an immersed grid");
+        if (immersed_role_path(o, g, range, ntr, impl)) {
+            int rc = check_range(g, range, nullptr);
+            if (rc) return rc;
+            if ((rc = launch_role_tendency_immersed(o, g, g_stream, u, v, w, tr, ntr, Gu, Gv, Gw, Gc, range, *im))) return fail(rc, "immersed role tendency launch failed");
+            KERNEL_CHECK();
+            return OCN_OK;
+        }
+        impl = 0;
+    }
     if (sub && !fused_path(o, g, range, ntr, impl)) return fail(OCN_ESTATE, "fused substep requested on the per-field tendency path");
     if (ftab && !(impl == 2 && fused_path(o, g, range, ntr, impl) && role_tendency_supported(o, g)))
         return fail(OCN_ESTATE, "forcing term requested in a tendency launch other than the role kernel");
@@ -707,11 +849,11 @@ static int compute_tendencies(const OcnOptions &o, const DGrid &g, const double 
         return OCN_OK;
     }
     int rc;
-    if ((rc = launch_tendency<F_U>(g, u, v, w, nullptr, Gu, range))) return rc;
-    if ((rc = launch_tendency<F_V>(g, u, v, w, nullptr, Gv, range))) return rc;
-    if ((rc = launch_tendency<F_W>(g, u, v, w, nullptr, Gw, range))) return rc;
+    if ((rc = launch_tendency<F_U>(g, u, v, w, nullptr, Gu, range, im))) return rc;
+    if ((rc = launch_tendency<F_V>(g, u, v, w, nullptr, Gv, range, im))) return rc;
+    if ((rc = launch_tendency<F_W>(g, u, v, w, nullptr, Gw, range, im))) return rc;
     for (int t = 0; t < ntr; ++t)
-        if ((rc = launch_tendency<F_C>(g, u, v, w, tr[t], Gc[t], range))) return rc;
+        if ((rc = launch_tendency<F_C>(g, u, v, w, tr[t], Gc[t], range, im))) return rc;
     return OCN_OK;
 }
 
@@ -724,7 +866,9 @@ extern "C" int ocn_compute_tendencies(ocn_grid_t grid, const double *u, const do
         return fail(OCN_EINVAL, "invalid argument");
     if (!grid->advection_error.empty()) return fail(OCN_EINVAL, "%s", grid->advection_error.c_str());
     // (the raw entry points map tendency_impl 0 to the all-fields kernel)
-    int rc = compute_tendencies(g_defaults, grid->d, u, v, w, tracers, ntracers, Gu, Gv, Gw, Gc, range, g_defaults.tendency_impl ? g_defaults.tendency_impl : 1);
+    const ImmView im = imm_view(grid);
+    int rc = compute_tendencies(g_defaults, grid->d, u, v, w, tracers, ntracers, Gu, Gv, Gw, Gc, range, g_defaults.tendency_impl ? g_defaults.tendency_impl : 1,
+                                nullptr, nullptr, is_immersed(grid) ? &im : nullptr);
     if (rc) return rc;
     KERNEL_CHECK();
     return OCN_OK;
@@ -736,7 +880,8 @@ extern "C" int ocn_compute_tendencies(ocn_grid_t grid, const double *u, const do
 static const int *field_loc(int f) { return f == 0 ? LOC_U : (f == 1 ? LOC_V : (f == 2 ? LOC_W : LOC_C)); }
 
 template <int F>
-static int launch_advective_tendency(const DGrid &g, const double *const adv[3], const double *psi, double *G, const int *range, bool accumulate) {
+static int launch_advective_tendency(const DGrid &g, const double *const adv[3], const double *psi, double *G, const int *range, bool accumulate,
+                                     const ImmView *im = nullptr) {
     const int *loc = field_loc(F);
     Range6 r;
     int rc = check_range(g, range, &r, loc, F != F_C);
@@ -745,6 +890,10 @@ static int launch_advective_tendency(const DGrid &g, const double *const adv[3],
     if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
     const FView fu = make_view(g, adv[0], LOC_U), fv = make_view(g, adv[1], LOC_V), fw = make_view(g, adv[2], LOC_W);
     const FView fp = make_view(g, psi, loc), fG = make_view(g, G, loc);
+    if (im) {
+        if (accumulate) hipLaunchKernelGGL((immersed_tendency_kernel<F, true>), grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, *im, fu, fv, fw, fp, fG, r);
+        else            hipLaunchKernelGGL((immersed_tendency_kernel<F, false>), grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, *im, fu, fv, fw, fp, fG, r);
+    } else
     if (accumulate) hipLaunchKernelGGL((advective_tendency_kernel<F, true>), grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, fu, fv, fw, fp, fG, r);
     else            hipLaunchKernelGGL((advective_tendency_kernel<F, false>), grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, fu, fv, fw, fp, fG, r);
     KERNEL_CHECK();
@@ -760,9 +909,9 @@ static bool split_role_path(const OcnOptions &o, const DGrid &g, int impl) {
 // -div(advection, adv, psi[f]) of the fields `roles` into G[f] (accumulate: G[f] -= div): one role-kernel launch, or one per-field
 // launch each
 static int advective_terms(const OcnOptions &o, const DGrid &g, const double *const adv[3], const double *const *psi, double *const *G,
-                           const int *roles, int nrole, const int *range, bool accumulate, int impl) {
+                           const int *roles, int nrole, const int *range, bool accumulate, int impl, const ImmView *im = nullptr) {
     if (nrole <= 0) return OCN_OK;
-    if (split_role_path(o, g, impl)) {
+    if (!im && split_role_path(o, g, impl)) {
         int rc = check_range(g, range, nullptr);
         if (rc) return rc;
         rc = launch_role_split(o, g, g_stream, adv, psi, G, roles, nrole, range, accumulate);
@@ -772,10 +921,10 @@ static int advective_terms(const OcnOptions &o, const DGrid &g, const double *co
     }
     for (int q = 0; q < nrole; ++q) {
         const int f = roles[q];
-        int rc = f == 0 ? launch_advective_tendency<F_U>(g, adv, psi[f], G[f], range, accumulate)
-               : f == 1 ? launch_advective_tendency<F_V>(g, adv, psi[f], G[f], range, accumulate)
-               : f == 2 ? launch_advective_tendency<F_W>(g, adv, psi[f], G[f], range, accumulate)
-                        : launch_advective_tendency<F_C>(g, adv, psi[f], G[f], range, accumulate);
+        int rc = f == 0 ? launch_advective_tendency<F_U>(g, adv, psi[f], G[f], range, accumulate, im)
+               : f == 1 ? launch_advective_tendency<F_V>(g, adv, psi[f], G[f], range, accumulate, im)
+               : f == 2 ? launch_advective_tendency<F_W>(g, adv, psi[f], G[f], range, accumulate, im)
+                        : launch_advective_tendency<F_C>(g, adv, psi[f], G[f], range, accumulate, im);
         if (rc) return rc;
     }
     return OCN_OK;
@@ -791,7 +940,8 @@ extern "C" int ocn_compute_advective_tendency(ocn_grid_t grid, const double *ua,
     const double *P[OCN_MAX_FIELDS] = {};
     double *Gs[OCN_MAX_FIELDS] = {};
     P[which] = psi; Gs[which] = G;
-    return advective_terms(g_defaults, grid->d, adv, P, Gs, &which, 1, range, accumulate != 0, g_defaults.tendency_impl);
+    const ImmView im = imm_view(grid);
+    return advective_terms(g_defaults, grid->d, adv, P, Gs, &which, 1, range, accumulate != 0, g_defaults.tendency_impl, is_immersed(grid) ? &im : nullptr);
 }
 
 static int sum_parent(const DGrid &g, const double *a, const double *b, const int loc[3], double *out) {
@@ -1251,6 +1401,7 @@ static int dg_compute(ocn_grid_s *grid, const O &o, const int n[3], const W &out
 }
 
 static int dg_compute_operation(ocn_grid_t grid, const ocn_operand_t *operand, const ocn_time_fold_t *fold, double *out) {
+    if (int rc_ = refuse_immersed(grid, "a diagnostic (its reductions exclude immersed cells through a condition)")) return rc_;
     DgOperand o;
     int rc = dg_make_operand(grid, operand, &o);
     if (rc) return rc;
@@ -1367,6 +1518,7 @@ static int dg_accumulate(const O &o, const int n[3], int dim, int reverse, const
 
 static int dg_reduce_operation(ocn_grid_t grid, const ocn_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
                                const ocn_time_fold_t *fold, double *out) {
+    if (int rc_ = refuse_immersed(grid, "a diagnostic (its reductions exclude immersed cells through a condition)")) return rc_;
     if (kind < OCN_REDUCE_SUM || kind > OCN_REDUCE_AVERAGE) return fail(OCN_EINVAL, "unknown reduction kind %d", kind);
     if (dims_mask < 1 || dims_mask > 7) return fail(OCN_EINVAL, "dims_mask %d: bits 0..2 name the reduced directions, at least one", dims_mask);
     if (use_metric && (kind == OCN_REDUCE_MAXIMUM || kind == OCN_REDUCE_MINIMUM)) return fail(OCN_EINVAL, "maximum and minimum take no metric");
@@ -1399,6 +1551,7 @@ extern "C" int ocn_time_average_reduce_operation(ocn_grid_t grid, const ocn_oper
 
 static int dg_accumulate_operation(ocn_grid_t grid, const ocn_operand_t *operand, int dim, int reverse, int use_metric,
                                    const ocn_time_fold_t *fold, double *out) {
+    if (int rc_ = refuse_immersed(grid, "a diagnostic (its reductions exclude immersed cells through a condition)")) return rc_;
     if (dim < 0 || dim > 2) return fail(OCN_EINVAL, "dim %d: 0 (x), 1 (y) or 2 (z)", dim);
     DgOperand o;
     int rc = dg_make_operand(grid, operand, &o);
@@ -1633,6 +1786,7 @@ template <class O> static void dg_set_metric_of(const DGrid &g, int mask, O *o) 
 static size_t st_lds_bytes(const StLowered &S) { return sizeof(double) * DG_THREADS * (size_t)std::max(S.nslots, DG_ST_MIN_LDS_SLOTS); }
 
 static int st_compute(ocn_grid_t grid, const ocn_stencil_operand_t *operand, const ocn_time_fold_t *fold, double *out) {
+    if (int rc_ = refuse_immersed(grid, "a diagnostic (its reductions exclude immersed cells through a condition)")) return rc_;
     StLowered S;
     const int rc = dg_lower_stencil(grid, operand, &S);
     if (rc) return rc;
@@ -1673,6 +1827,7 @@ static int st_reduce(ocn_grid_s *grid, const ocn_stencil_operand_t *operand, con
 
 static int st_reduce_any(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int kind, int dims_mask, int use_metric, int absolute,
                          const ocn_time_fold_t *fold, double *out) {
+    if (int rc_ = refuse_immersed(grid, "a diagnostic (its reductions exclude immersed cells through a condition)")) return rc_;
     if (kind < OCN_REDUCE_SUM || kind > OCN_REDUCE_AVERAGE) return fail(OCN_EINVAL, "unknown reduction kind %d", kind);
     if (dims_mask < 1 || dims_mask > 7) return fail(OCN_EINVAL, "dims_mask %d: bits 0..2 name the reduced directions, at least one", dims_mask);
     if (use_metric && (kind == OCN_REDUCE_MAXIMUM || kind == OCN_REDUCE_MINIMUM)) return fail(OCN_EINVAL, "maximum and minimum take no metric");
@@ -1712,6 +1867,7 @@ static int st_accumulate(ocn_grid_s *grid, const ocn_stencil_operand_t *operand,
 
 static int st_accumulate_any(ocn_grid_t grid, const ocn_stencil_operand_t *operand, int dim, int reverse, int use_metric,
                              const ocn_time_fold_t *fold, double *out) {
+    if (int rc_ = refuse_immersed(grid, "a diagnostic (its reductions exclude immersed cells through a condition)")) return rc_;
     if (dim < 0 || dim > 2) return fail(OCN_EINVAL, "dim %d: 0 (x), 1 (y) or 2 (z)", dim);
     StLowered S;
     const int rc = dg_lower_stencil(grid, operand, &S);
@@ -1776,6 +1932,7 @@ extern "C" int ocn_update_hydrostatic_pressure(ocn_grid_t grid, int kind, const 
 extern "C" int ocn_update_hydrostatic_pressure_tilted(ocn_grid_t grid, int kind, const double *bT, const double *S, double grav, double alpha,
                                                       double beta, double ghat_z, double *pHY) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "BuoyancyForce(gravity_unit_vector)")) return rc_;
     if (!grid || !bT || !pHY || (kind != 1 && kind != 2) || (kind == 2 && !S)) return fail(OCN_EINVAL, "invalid argument");
     return update_hydrostatic_pressure(grid->d, kind, bT, S, grav, alpha, beta, pHY, true, ghat_z);
 }
@@ -1786,10 +1943,14 @@ extern "C" int ocn_add_hydrostatic_pressure_gradient(ocn_grid_t grid, const doub
     return add_hydrostatic_pressure_gradient(grid->d, pHY, Gu, Gv, range);
 }
 
-static int add_fplane_coriolis(const DGrid &g, double f, const double *u, const double *v, double *Gu, double *Gv, const int *range) {
+static int add_fplane_coriolis(const DGrid &g, double f, const double *u, const double *v, double *Gu, double *Gv, const int *range,
+                               const ImmView *im = nullptr) {
     Range6 ru, rv;
     int rc;
     if ((rc = check_range(g, range, &ru, LOC_U, true)) || (rc = check_range(g, range, &rv, LOC_V, true))) return rc;
+    if (im) hipLaunchKernelGGL(immersed_fplane_coriolis_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, *im, f, make_view(g, u, LOC_U),
+                               make_view(g, v, LOC_V), make_view(g, Gu, LOC_U), make_view(g, Gv, LOC_V), ru, rv);
+    else
     hipLaunchKernelGGL(fplane_coriolis_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, f, make_view(g, u, LOC_U),
                        make_view(g, v, LOC_V), make_view(g, Gu, LOC_U), make_view(g, Gv, LOC_V), ru, rv);
     KERNEL_CHECK();
@@ -1799,7 +1960,8 @@ static int add_fplane_coriolis(const DGrid &g, double f, const double *u, const 
 extern "C" int ocn_add_fplane_coriolis(ocn_grid_t grid, double f, const double *u, const double *v, double *Gu, double *Gv, const int *range) {
     NEED_INIT();
     if (!grid || !u || !v || !Gu || !Gv) return fail(OCN_EINVAL, "NULL argument");
-    return add_fplane_coriolis(grid->d, f, u, v, Gu, Gv, range);
+    const ImmView im = imm_view(grid);
+    return add_fplane_coriolis(grid->d, f, u, v, Gu, Gv, range, is_immersed(grid) ? &im : nullptr);
 }
 
 // coriolis = ConstantCartesianCoriolis(fx, fy, fz): G_u -= x_f_cross_U, G_v -= y_f_cross_U, G_w -= z_f_cross_U (cartesian_coriolis_kernel)
@@ -1819,6 +1981,7 @@ static int add_cartesian_coriolis(const DGrid &g, double fx, double fy, double f
 extern "C" int ocn_add_cartesian_coriolis(ocn_grid_t grid, double fx, double fy, double fz, const double *u, const double *v, const double *w,
                                           double *Gu, double *Gv, double *Gw, const int *range) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "ConstantCartesianCoriolis")) return rc_;
     if (!grid || !u || !v || !w || !Gu || !Gv || !Gw) return fail(OCN_EINVAL, "NULL argument");
     return add_cartesian_coriolis(grid->d, fx, fy, fz, u, v, w, Gu, Gv, Gw, range);
 }
@@ -1845,6 +2008,7 @@ extern "C" int ocn_add_stokes_drift(ocn_grid_t grid, const double *dzu_c, const 
                                     const double *dtu_c, const double *dtv_c, const double *u, const double *v, const double *w, double *Gu,
                                     double *Gv, double *Gw, const int *range_u, const int *range_v, const int *range_w) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "stokes_drift")) return rc_;
     if (!grid || !u || !v || !w || !Gu || !Gv || !Gw) return fail(OCN_EINVAL, "NULL argument");
     return add_stokes_drift(grid->d, StokesTables{dzu_c, dzu_f, dzv_c, dzv_f, dtu_c, dtv_c}, u, v, w, Gu, Gv, Gw, range_u, range_v, range_w);
 }
@@ -1880,6 +2044,7 @@ extern "C" int ocn_interpolate_at(ocn_grid_t grid, int n, const double *x, const
 extern "C" int ocn_advect_particles(ocn_grid_t grid, int n, double *x, double *y, double *z, const double *depths, double restitution,
                                     double dt, const double *u, const double *v, const double *w) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "particles (LagrangianParticles)")) return rc_;
     if (!grid || !x || !y || !z || !u || !v || !w) return fail(OCN_EINVAL, "NULL argument");
     if (n < 0) return fail(OCN_EINVAL, "n must not be negative");
     if (!grid->has_nodes) return fail(OCN_ESTATE, "the grid has no node coordinates: call ocn_grid_set_nodes");
@@ -1926,13 +2091,16 @@ static int add_buoyancy_acceleration(const DGrid &g, int kind, const double *bT,
 extern "C" int ocn_add_buoyancy_acceleration(ocn_grid_t grid, int kind, const double *bT, const double *S, double grav, double alpha, double beta,
                                              double ghat_x, double ghat_y, double *Gu, double *Gv, const int *range) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "BuoyancyForce(gravity_unit_vector)")) return rc_;
     if (!grid || !bT || !Gu || !Gv || (kind != 1 && kind != 2) || (kind == 2 && !S)) return fail(OCN_EINVAL, "invalid argument");
     return add_buoyancy_acceleration(grid->d, kind, bT, S, grav, alpha, beta, ghat_x, ghat_y, Gu, Gv, range);
 }
 
 static int closure_tendencies(const DGrid &g, const double *u, const double *v, const double *w, const double *const *tr, int ntr,
                               double nu, const double *kappa, double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range,
-                              const double *nu_e = nullptr, const double *const *kappa_e = nullptr, const double *Pr = nullptr, bool vi = false) {
+                              const double *nu_e = nullptr, const double *const *kappa_e = nullptr, const double *Pr = nullptr, bool vi = false,
+                              const ImmView *im = nullptr) {
+    if (im && (nu_e || kappa_e || Pr || vi)) return fail(OCN_ENOTSUP, "eddy-viscosity closures and VerticallyImplicitTimeDiscretization are not served on an ImmersedBoundaryGrid");
     // Pr (Smagorinsky): kappa_e[t] is νₑ and tracer t's coefficient is the interpolated νₑ divided by Pr[t]; Pr[t] == 1 takes the
     // plain instantiation (x / 1.0 is x)
     const FView vu = make_view(g, u, LOC_U), vv = make_view(g, v, LOC_V), vw = make_view(g, w, LOC_W);
@@ -1947,6 +2115,13 @@ static int closure_tendencies(const DGrid &g, const double *u, const double *v, 
         if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
         const FView vc = make_view(g, c ? c : u, LOC_C), vG = make_view(g, G, loc);
         const dim3 grd = grid3(nx, ny, nz, BLK);
+        if (im) {               // constant coefficients, explicit, every flux conditional (immersed_closure_tendency_kernel)
+            if (F == F_U) hipLaunchKernelGGL(immersed_closure_tendency_kernel<F_U>, grd, BLK, 0, g_stream, g, *im, vu, vv, vw, vc, vG, coef, r);
+            if (F == F_V) hipLaunchKernelGGL(immersed_closure_tendency_kernel<F_V>, grd, BLK, 0, g_stream, g, *im, vu, vv, vw, vc, vG, coef, r);
+            if (F == F_W) hipLaunchKernelGGL(immersed_closure_tendency_kernel<F_W>, grd, BLK, 0, g_stream, g, *im, vu, vv, vw, vc, vG, coef, r);
+            if (F == F_C) hipLaunchKernelGGL(immersed_closure_tendency_kernel<F_C>, grd, BLK, 0, g_stream, g, *im, vu, vv, vw, vc, vG, coef, r);
+            return OCN_OK;
+        }
         if (vi) {               // constant coefficients, the explicit part of a vertically implicit discretisation
             if (F == F_U) hipLaunchKernelGGL((closure_tendency_kernel<F_U, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
             if (F == F_V) hipLaunchKernelGGL((closure_tendency_kernel<F_V, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
@@ -1980,7 +2155,9 @@ extern "C" int ocn_compute_closure_tendencies(ocn_grid_t grid, const double *u, 
         (ntracers > 0 && (!tracers || !Gc || !kappa)))
         return fail(OCN_EINVAL, "invalid argument");
     if (nu < 0) return fail(OCN_EINVAL, "viscosity must be non-negative");
-    return closure_tendencies(grid->d, u, v, w, tracers, ntracers, nu, kappa, Gu, Gv, Gw, Gc, range);
+    const ImmView im = imm_view(grid);
+    return closure_tendencies(grid->d, u, v, w, tracers, ntracers, nu, kappa, Gu, Gv, Gw, Gc, range, nullptr, nullptr, nullptr, false,
+                              is_immersed(grid) ? &im : nullptr);
 }
 
 // the same with the z fluxes of ScalarDiffusivity(VerticallyImplicitTimeDiscretization(), ν, κ) on a vertically Bounded grid
@@ -1995,6 +2172,7 @@ extern "C" int ocn_compute_closure_tendencies_vertically_implicit(ocn_grid_t gri
     if (nu < 0) return fail(OCN_EINVAL, "viscosity must be non-negative");
     if (grid->d.tz != OCN_BOUNDED)
         return fail(OCN_EINVAL, "VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.");
+    if (int rc = refuse_immersed(grid, "VerticallyImplicitTimeDiscretization")) return rc;
     return closure_tendencies(grid->d, u, v, w, tracers, ntracers, nu, kappa, Gu, Gv, Gw, Gc, range, nullptr, nullptr, nullptr, true);
 }
 
@@ -2029,6 +2207,7 @@ static int implicit_step_z(ocn_grid_s *grid, double *field, const int loc[3], do
 
 extern "C" int ocn_implicit_step_z(ocn_grid_t grid, double *field, const int loc[3], double coef, double dt, int form) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "VerticallyImplicitTimeDiscretization")) return rc_;
     if (!grid || !field || !loc) return fail(OCN_EINVAL, "NULL argument");
     return implicit_step_z(grid, field, loc, coef, dt, form);
 }
@@ -2038,6 +2217,7 @@ extern "C" int ocn_compute_closure_tendencies_field(ocn_grid_t grid, const doubl
                                                     const double *const *kappa_e, double *Gu, double *Gv, double *Gw, double *const *Gc,
                                                     const int *range) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "a closure with diffusivity fields (AnisotropicMinimumDissipation)")) return rc_;
     if (!grid || !u || !v || !w || !nu_e || !Gu || !Gv || !Gw || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 ||
         (ntracers > 0 && (!tracers || !Gc || !kappa_e)))
         return fail(OCN_EINVAL, "invalid argument");
@@ -2092,6 +2272,7 @@ extern "C" int ocn_compute_amd_diffusivities(ocn_grid_t grid, double Cnu, const 
                                              const double *w, const double *const *tracers, int ntracers, double *nu_e,
                                              double *const *kappa_e, const int *range) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "AnisotropicMinimumDissipation")) return rc_;
     if (!grid || !u || !v || !w || !nu_e || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 || (ntracers > 0 && (!tracers || !kappa_e || !Ckappa)))
         return fail(OCN_EINVAL, "invalid argument");
     return amd_diffusivities(g_defaults, grid->d, Cnu, Ckappa, u, v, w, tracers, ntracers, nu_e, kappa_e, range);
@@ -2101,6 +2282,7 @@ extern "C" int ocn_compute_closure_tendencies_smagorinsky(ocn_grid_t grid, const
                                                           const double *const *tracers, int ntracers, const double *nu_e, const double *Pr,
                                                           double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "Smagorinsky")) return rc_;
     if (!grid || !u || !v || !w || !nu_e || !Gu || !Gv || !Gw || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 ||
         (ntracers > 0 && (!tracers || !Gc || !Pr)))
         return fail(OCN_EINVAL, "invalid argument");
@@ -2160,6 +2342,7 @@ extern "C" int ocn_compute_smagorinsky_viscosity(ocn_grid_t grid, double C, doub
                                                  const double *S, double g, double alpha, double beta, const double *u, const double *v,
                                                  const double *w, double *nu_e, const int *range) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "Smagorinsky")) return rc_;
     if (!grid || !u || !v || !w || !nu_e || buoyancy_kind < 0 || buoyancy_kind > 2 || (buoyancy_kind >= 1 && !b_or_T) || (buoyancy_kind == 2 && !S))
         return fail(OCN_EINVAL, "invalid argument");
     if (!(C >= 0)) return fail(OCN_EINVAL, "the Smagorinsky coefficient must be non-negative");
@@ -2267,6 +2450,7 @@ extern "C" int ocn_dynamic_smagorinsky_update(ocn_grid_t grid, const double *u, 
                                               double minimum_numerator, double dt, int initialising, double *Sigma, double *Sigma_bar,
                                               double *LM, double *MM, double *J_LM, double *J_MM, double *J_LM_prev, double *J_MM_prev) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "DynamicSmagorinsky")) return rc_;
     if (!grid || !u || !v || !w || !Sigma || !Sigma_bar || !J_LM || !J_MM || averaging_mask < 0 || averaging_mask > 7)
         return fail(OCN_EINVAL, "invalid argument");
     if (averaging_mask != 0 && (!LM || !MM)) return fail(OCN_EINVAL, "directional averaging needs the LM and MM fields");
@@ -2289,6 +2473,7 @@ extern "C" int ocn_dynamic_smagorinsky_update(ocn_grid_t grid, const double *u, 
 extern "C" int ocn_compute_dynamic_smagorinsky_viscosity(ocn_grid_t grid, int averaging_mask, double minimum_numerator, const double *J_LM,
                                                          const double *J_MM, const double *u, const double *v, const double *w, double *nu_e) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "DynamicSmagorinsky")) return rc_;
     if (!grid || !u || !v || !w || !nu_e || !J_LM || !J_MM || averaging_mask < 0 || averaging_mask > 7) return fail(OCN_EINVAL, "invalid argument");
     const DGrid &g = grid->d;
     if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT) return fail(OCN_EINVAL, "Smagorinsky needs a grid without Flat directions");
@@ -2300,6 +2485,7 @@ extern "C" int ocn_compute_tendencies_and_substep(ocn_grid_t grid, const double 
                                                   const int *range, double *const *next, const double *const *Gm, double dt,
                                                   double gamma, double zeta, int has_zeta) {
     NEED_INIT();
+    if (int rc_ = refuse_immersed(grid, "the fused tendency-and-substep launch")) return rc_;
     if (!grid || !fields || !Gn || !next || ntracers < 0 || ntracers > 3 || (has_zeta && !Gm)) return fail(OCN_EINVAL, "invalid argument");
     for (int f = 0; f < 3 + ntracers; ++f)
         if (!fields[f] || !Gn[f] || !next[f] || (has_zeta && !Gm[f])) return fail(OCN_EINVAL, "NULL field pointer");
@@ -2596,6 +2782,7 @@ struct ocn_model_s {
     int profile = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     size_t events_used = 0;
+    bool counted = false;                   // this model is in its grid's count of live models (ocn_grid_set_immersed_boundary)
 };
 
 static void dynamic_fields_free(DynFields &F) {
@@ -2606,6 +2793,7 @@ static void dynamic_fields_free(DynFields &F) {
 
 extern "C" int ocn_model_destroy(ocn_model_t m) {
     if (!m) return OCN_OK;
+    if (m->counted) m->grid->models -= 1;
     dynamic_fields_free(m->dyn);
     for (auto &e : m->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (m->graph_exec) hipGraphExecDestroy(m->graph_exec);
@@ -2672,6 +2860,7 @@ static int model_create(ocn_model_t *model, ocn_grid_t grid, int ntracers, bool 
     }
     if (!rc && with_solver) rc = poisson_create(&m->solver, grid, -1, &m->opt);
     if (rc) { ocn_model_destroy(m); return rc; }
+    grid->models += 1; m->counted = true;
     *model = m;
     return OCN_OK;
 }
@@ -2963,6 +3152,16 @@ static StepPlan plan(const ocn_model_s *m) {
     else if (background) p.fuse_substep = false;                     // the second advection term follows the launch the substep would ride in
     else p.fuse_substep = !p.physics && !flux && fused_path(o, g, nullptr, m->ntr, o.tendency_impl);
     p.substep_in_advection = p.fuse_substep && !p.epilogue;
+    // An immersed grid takes the plainest composition: the per-field immersed kernels complete the advective part, the stand-alone
+    // kernels add the physics terms (their immersed instantiations where a term reads the boundary), the forcing pass follows, and every
+    // substep is a launch of its own -- no epilogue, no marching form, nothing riding in another launch. The two masks then sit where
+    // the reference has them: update_state and pressure_step.
+    if (is_immersed(m->grid)) {
+        p.epilogue = p.march = p.fuse_substep = p.substep_in_advection = false;
+        p.stokes_path = p.stokes ? 1 : 0;
+        p.forcing_path = forcing ? 3 : 0;
+        p.background_path = background ? 1 : 0;
+    }
     return p;
 }
 static bool has_physics(const ocn_model_s *m) { return plan(m).physics; }
@@ -3163,6 +3362,13 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
     if (!strcmp(key, "graph_failures")) { *value = m->graph_failures; return OCN_OK; }
     const StepPlan p = plan(m);
     if (!strcmp(key, "forcing_path")) { *value = p.forcing_path; return OCN_OK; }
+    // whether the model's grid has an immersed boundary, and which kernels evaluate its tendencies: 0 none, 1 one field per launch, 2 the
+    // flux-sharing role kernel
+    if (!strcmp(key, "immersed")) { *value = is_immersed(m->grid) ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "immersed_tendency_path")) {
+        *value = !is_immersed(m->grid) ? 0 : (immersed_role_path(m->opt, m->grid->d, nullptr, m->ntr, m->opt.tendency_impl) ? 2 : 1);
+        return OCN_OK;
+    }
     if (!strcmp(key, "background_fields")) { *value = count_background(m); return OCN_OK; }
     if (!strcmp(key, "background_tendency_path")) { *value = p.background_path; return OCN_OK; }
     if (!strcmp(key, "vertically_implicit")) { *value = m->closure.vi ? 1 : 0; return OCN_OK; }
@@ -3219,7 +3425,10 @@ extern "C" int ocn_model_get_option(ocn_model_t m, const char *key, int *value) 
         *value = !m->dm && s && s->split && m->opt.split_solve && m->opt.real_fft && !s->general ? 1 : 0;
         return OCN_OK;
     }
-    if (!strcmp(key, "fused_tendency_active")) { *value = fused_path(m->opt, m->grid->d, nullptr, m->ntr, m->opt.tendency_impl) ? 1 : 0; return OCN_OK; }
+    if (!strcmp(key, "fused_tendency_active")) {
+        *value = !is_immersed(m->grid) && fused_path(m->opt, m->grid->d, nullptr, m->ntr, m->opt.tendency_impl) ? 1 : 0;
+        return OCN_OK;
+    }
     return fail(OCN_EINVAL, "unknown model option '%s'", key);
 }
 
@@ -3284,6 +3493,8 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
             HIP_TRY(hipEventRecord(ev->first, g_stream));
         }
         const bool physics = p.physics || p.epilogue;
+        const ImmView imv = imm_view(m->grid);
+        const ImmView *im = is_immersed(m->grid) ? &imv : nullptr;
         if (p.background_path) {
             // G = - div(U + Ū, φ) - div(U, Φ̄) ... (nonhydrostatic_tendency_kernel_functions.jl:86-94,148-156,213-221,276-293): term 1 is
             // today's launch when no velocity has a background (U + ZeroField is U), else the split one with the totals; term 2 accumulates
@@ -3304,7 +3515,7 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
             if (!rc) rc = advective_terms(m->opt, g, adv, m->bg, m->Gn, roles, nb, nullptr, true, m->opt.tendency_impl);
         } else
         rc = compute_tendencies(m->opt, g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
-                                m->opt.tendency_impl, physics ? nullptr : sub, p.forcing_path == 1 ? m->forcing_d : nullptr);
+                                m->opt.tendency_impl, physics ? nullptr : sub, p.forcing_path == 1 ? m->forcing_d : nullptr, im);
         if (ev) HIP_TRY(hipEventRecord(ev->second, g_stream));
         if (!rc && physics) {
             if (p.epilogue) { if (p.physics || sub) rc = tendency_epilogue(m, p, sub); }      // (Flux conditions alone and no substep: nothing to do)
@@ -3316,11 +3527,11 @@ static int update_state_tail(ocn_model_s *m, bool compute_tend, const FusedSubst
                                                    m->Gn[1], nullptr);
                 if (!rc && cor.kind == Coriolis::CARTESIAN)
                     rc = add_cartesian_coriolis(g, cor.fx, cor.fy, cor.fz, m->U[0], m->U[1], m->U[2], m->Gn[0], m->Gn[1], m->Gn[2], nullptr);
-                if (!rc && cor.kind == Coriolis::FPLANE) rc = add_fplane_coriolis(g, cor.f, m->U[0], m->U[1], m->Gn[0], m->Gn[1], nullptr);
+                if (!rc && cor.kind == Coriolis::FPLANE) rc = add_fplane_coriolis(g, cor.f, m->U[0], m->U[1], m->Gn[0], m->Gn[1], nullptr, im);
                 if (!rc && b.kind) rc = add_hydrostatic_pressure_gradient(g, m->pHY, m->Gn[0], m->Gn[1], nullptr);
                 if (!rc && c.kind == Closure::SCALAR)
                     rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, c.nu, c.kappa, m->Gn[0], m->Gn[1],
-                                            m->Gn[2], m->Gn + 3, nullptr, nullptr, nullptr, nullptr, c.vi);
+                                            m->Gn[2], m->Gn + 3, nullptr, nullptr, nullptr, nullptr, c.vi, im);
                 if (!rc && c.eddy())                  // AMD: νₑ and every κₑ; Smagorinsky: νₑ and the Prandtl numbers
                     rc = closure_tendencies(g, m->U[0], m->U[1], m->U[2], m->U + 3, m->ntr, 0.0, nullptr, m->Gn[0], m->Gn[1], m->Gn[2], m->Gn + 3, nullptr,
                                             m->nu_e, c.kind == Closure::AMD ? m->kappa_e : nullptr, c.kind == Closure::AMD ? nullptr : c.Pr);
@@ -3339,7 +3550,10 @@ static int dist_update_state(ocn_model_s *m, bool compute_tend, const FusedSubst
 // halos_current: the pressure step of the same time-step has just written every halo (pressure_step, fold_halos)
 static int update_state(ocn_model_s *m, bool compute_tend, const FusedSubstep *sub = nullptr, bool halos_current = false) {
     if (m->dm) return dist_update_state(m, compute_tend, sub);
-    int rc = halos_current ? OCN_OK : fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, /*fill_open_bcs=*/false, m->any_bc ? m->bcs : nullptr);
+    // "Mask immersed tracers" (update_nonhydrostatic_model_state.jl:22-25): first thing, before the halo fill; one launch for all of them
+    int rc = mask_immersed_fields(m->grid, m->U + 3, m->loc + 3, m->ntr, 0.0);
+    if (rc) return rc;
+    rc = halos_current ? OCN_OK : fill_halo_regions(m->opt, m->grid, m->U, m->loc, m->nf, /*fill_open_bcs=*/false, m->any_bc ? m->bcs : nullptr);
     if (rc) return rc;
     return update_state_tail(m, compute_tend, sub, nullptr);
 }
@@ -3587,8 +3801,9 @@ struct PendingSubstep { double dt, gamma; };
 static bool periodic_dense_path(const ocn_model_s *m) {
     const ocn_poisson_s *s = m->solver;
     const DGrid &g = m->grid->d;
-    return !m->dm && s && s->split && m->opt.split_solve && m->opt.real_fft && !s->general && g.tx == OCN_PERIODIC && g.ty == OCN_PERIODIC &&
-           g.tz == OCN_PERIODIC;
+    // (an immersed grid folds nothing into the pressure step: its masks run between the passes that would be folded)
+    return !m->dm && !is_immersed(m->grid) && s && s->split && m->opt.split_solve && m->opt.real_fft && !s->general && g.tx == OCN_PERIODIC &&
+           g.ty == OCN_PERIODIC && g.tz == OCN_PERIODIC;
 }
 static bool can_fold_halo_fill(const ocn_model_s *m) {                // N >= H: the fused fill's own condition
     const DGrid &g = m->grid->d;
@@ -3600,6 +3815,10 @@ static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = tru
                          bool fold_halos = false) {
     if (m->dm) return dist_pressure_step(m, dt, tendencies_follow, keep_p || !m->opt.skip_stage_pressure);
     int rc;
+    // "Mask immersed velocities" (pressure_correction.jl:10-12): first thing in compute_pressure_correction!, before the velocities' halo
+    // fill and the source term; one launch for all three. The solve is the underlying grid's (approximate near the boundary,
+    // NonhydrostaticModels.jl:42-58); the correction that follows leaves -Δt ∂p on the immersed faces until the next mask.
+    if ((rc = mask_immersed_fields(m->grid, m->U, m->loc, 3, 0.0))) return rc;
     ocn_poisson_s *s = m->solver;
     if ((pending || fold_halos) && !periodic_dense_path(m)) return fail(OCN_ESTATE, "folded pressure step off the periodic dense-solution path");
     if (!(s->split && m->opt.split_solve && m->opt.real_fft && !s->general)) {
@@ -3669,6 +3888,7 @@ extern "C" int ocn_model_set_coriolis(ocn_model_t m, int enabled, double f) {
 extern "C" int ocn_model_set_cartesian_coriolis(ocn_model_t m, int enabled, double fx, double fy, double fz) {
     if (m) m->epoch += 1;
     if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "ConstantCartesianCoriolis")) return rc_;
     if (m->dm) return fail(OCN_ENOTSUP, "ConstantCartesianCoriolis is not served on a partitioned model");
     m->coriolis = Coriolis{enabled ? Coriolis::CARTESIAN : Coriolis::NONE, 0.0, fx, fy, fz};
     return OCN_OK;
@@ -3677,6 +3897,7 @@ extern "C" int ocn_model_set_cartesian_coriolis(ocn_model_t m, int enabled, doub
 extern "C" int ocn_model_set_gravity_unit_vector(ocn_model_t m, int enabled, double gx, double gy, double gz) {
     if (m) m->epoch += 1;
     if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "BuoyancyForce(gravity_unit_vector)")) return rc_;
     if (m->dm) return fail(OCN_ENOTSUP, "gravity_unit_vector is not served on a partitioned model");
     Buoyancy &b = m->buoyancy;
     if (!enabled) { b.tilted = false; b.ghat[0] = 0.0; b.ghat[1] = 0.0; b.ghat[2] = 1.0; return OCN_OK; }      // NegativeZDirection()
@@ -3696,6 +3917,7 @@ extern "C" int ocn_model_set_stokes_drift(ocn_model_t m, int enabled, const doub
                                           const double *dzv_f, const double *dtu_c, const double *dtv_c) {
     NEED_INIT();
     if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "stokes_drift")) return rc_;
     if (m->dm) return fail(OCN_ENOTSUP, "a Stokes drift is not served on a partitioned model");
     const DGrid &g = m->grid->d;
     if (g.tz == OCN_FLAT) return fail(OCN_EINVAL, "a UniformStokesDrift varies with z: the grid needs a z direction");
@@ -3738,6 +3960,7 @@ extern "C" int ocn_model_set_particles(ocn_model_t m, int n, const double *x, co
                                        const double *depths) {
     NEED_INIT();
     if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "particles (LagrangianParticles)")) return rc_;
     if (m->dm) return fail(OCN_ENOTSUP, "particles are not served on a partitioned model (they would have to migrate between ranks)");
     if (n < 0) return fail(OCN_EINVAL, "the number of particles must not be negative");
     const bool clear = n == 0 && !x && !y && !z && !depths;
@@ -3879,6 +4102,7 @@ extern "C" int ocn_model_set_vertically_implicit(ocn_model_t m, int enabled) {
     if (m) m->epoch += 1;
     NEED_INIT();
     if (!m) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "VerticallyImplicitTimeDiscretization")) return rc_;
     if (!enabled) { m->closure.vi = false; return OCN_OK; }
     if (m->grid->d.tz != OCN_BOUNDED)
         return fail(OCN_EINVAL, "VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.");
@@ -3931,6 +4155,7 @@ extern "C" int ocn_model_set_background_field(ocn_model_t m, const char *name, c
     NEED_INIT();
     if (m) m->epoch += 1;
     if (!m || !name) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "background_fields")) return rc_;
     if (m->dm) return fail(OCN_ENOTSUP, "background fields are not served on a partitioned model");
     const int f = field_index(m, name);
     if (f < 0) return fail(OCN_EINVAL, "background fields can be set on u, v, w and the tracers c0..c%d; got '%s'", m->ntr - 1, name);
@@ -4081,6 +4306,7 @@ extern "C" int ocn_model_set_amd(ocn_model_t m, double Cnu, const double *Ckappa
     if (m) m->epoch += 1;
     NEED_INIT();
     if (!m || (m->ntr > 0 && !Ckappa)) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "AnisotropicMinimumDissipation")) return rc_;
     const DGrid &g = m->grid->d;
     if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT)
         return fail(OCN_ENOTSUP, "AnisotropicMinimumDissipation needs a grid without Flat directions");
@@ -4101,6 +4327,7 @@ extern "C" int ocn_model_set_smagorinsky(ocn_model_t m, double C, double Cb, int
     if (m) m->epoch += 1;
     NEED_INIT();
     if (!m || (m->ntr > 0 && !Pr)) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "Smagorinsky")) return rc_;
     const DGrid &g = m->grid->d;
     if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT) return fail(OCN_EINVAL, "Smagorinsky needs a grid without Flat directions");
     if (!(C >= 0)) return fail(OCN_EINVAL, "the Smagorinsky coefficient must be non-negative");
@@ -4124,6 +4351,7 @@ extern "C" int ocn_model_set_dynamic_smagorinsky(ocn_model_t m, int averaging_ma
     if (m) m->epoch += 1;
     NEED_INIT();
     if (!m || (m->ntr > 0 && !Pr)) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "DynamicSmagorinsky")) return rc_;
     if (m->dm) return fail(OCN_ENOTSUP, "a dynamic Smagorinsky coefficient is not built for a partitioned model");
     if (averaging_mask < 0 || averaging_mask > 7) return fail(OCN_EINVAL, "averaging_mask %d: bits 0..2 name the averaged directions, 0 is LagrangianAveraging", averaging_mask);
     if (interval < 1) return fail(OCN_EINVAL, "the interval of the schedule must be positive");
@@ -4326,6 +4554,7 @@ extern "C" int ocn_model_set_open_boundary_scheme(ocn_model_t m, const char *nam
     if (m) m->epoch += 1;
     NEED_INIT();
     if (!m || !name) return fail(OCN_EINVAL, "NULL argument");
+    if (int rc_ = refuse_immersed(m->grid, "an OpenBoundaryCondition with a scheme")) return rc_;
     if (m->dm) return fail(OCN_ENOTSUP, "open boundaries with a scheme are not served on a partitioned model");
     const int f = field_index(m, name);
     if (side < 0 || side > 5 || f < 0 || f > 2 || side / 2 != f || !ob_wall(m->grid->d, side))
@@ -4356,6 +4585,9 @@ extern "C" int ocn_model_set_finalize(ocn_model_t m, int enforce_incompressibili
     if (!m) return fail(OCN_EINVAL, "NULL argument");
     int rc = fill_open_boundaries(m, m->nf, false);     // set!(ϕ, value); fill_halo_regions!(ϕ, model.clock, fields(model)) per field
     if (rc) return rc;
+    // "Apply a mask" (set_nonhydrostatic_model.jl:47-49): tracers, then velocities, before update_state!
+    if ((rc = mask_immersed_fields(m->grid, m->U + 3, m->loc + 3, m->ntr, 0.0))) return rc;
+    if ((rc = mask_immersed_fields(m->grid, m->U, m->loc, 3, 0.0))) return rc;
     if ((rc = update_state(m, false))) return rc;
     if (enforce_incompressibility) {
         if ((rc = pressure_step(m, 1.0, false))) return rc;

@@ -1,6 +1,7 @@
 // ocn_kernels.h -- HIP kernels of the hot path (reference kernel inventory: SURVEY.md 2.1). gfx950 / wave64.
 #pragma once
 #include "ocn_device.h"
+#include "ocn_immersed.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // advective fluxes (src/Advection/upwind_biased_advective_fluxes.jl:23-121), evaluated straight from global memory.
@@ -17,8 +18,9 @@ template <int AQ> __device__ __forceinline__ double area_q(const DGrid &g, const
 
 // symmetric interpolation of a transport along D; CEN: ᶜ variant (stencil of face idx+1). B: buffer of the scheme of the
 // direction the FLUX points along (adapt_advection_order; 3 unless that direction has fewer than 3 cells)
-template <int AQ, int D, bool CEN>
-__device__ __forceinline__ double sym_transport(const DGrid &g, const FView &f, int i, int j, int k, int B) {
+// IM: NoImm, or the ImmView of an immersed grid (ocn_immersed.h) -- the order entry then stands where outside_symmetric_halo stood
+template <int AQ, int D, bool CEN, class IM = NoImm>
+__device__ __forceinline__ double sym_transport(const DGrid &g, const FView &f, int i, int j, int k, int B, const IM &im = IM()) {
     // interpolation along a Flat direction is the identity (flat_advective_fluxes.jl:35-50)
     if ((D == 0 ? g.tx : (D == 1 ? g.ty : g.tz)) == OCN_FLAT) return area_q<AQ>(g, f, i, j, k);
     const int idx = D == 0 ? i : (D == 1 ? j : k);
@@ -31,14 +33,15 @@ __device__ __forceinline__ double sym_transport(const DGrid &g, const FView &f, 
         q[n] = D == 0 ? area_q<AQ>(g, f, i + m, j, k) : (D == 1 ? area_q<AQ>(g, f, i, j + m, k) : area_q<AQ>(g, f, i, j, k + m));
     }
     if (B < 3) return symmetric_interp_low(q[1], q[2]);
+    if constexpr (IM::on) return symmetric_interp_order(q[0], q[1], q[2], q[3], im.template order<D, CEN>(i, j, k));
     const int T = D == 0 ? g.tx : (D == 1 ? g.ty : g.tz);
     const bool lo = wall_lo(T), hi = wall_hi(T);
     const int N = D == 0 ? g.Nx : (D == 1 ? g.Ny : g.Nz);
     return symmetric_interp(q[0], q[1], q[2], q[3], lo | hi, idx, CEN, N, lo, hi);
 }
 
-template <int D, bool CEN>
-__device__ __forceinline__ double biased_field(const DGrid &g, const FView &c, bool left, int i, int j, int k) {
+template <int D, bool CEN, class IM = NoImm>
+__device__ __forceinline__ double biased_field(const DGrid &g, const FView &c, bool left, int i, int j, int k, const IM &im = IM()) {
     const int idx = D == 0 ? i : (D == 1 ? j : k);
     const int o = CEN ? 1 : 0;
     const long st = c.stride<D>();
@@ -50,28 +53,35 @@ __device__ __forceinline__ double biased_field(const DGrid &g, const FView &c, b
     if (B < 3) {                                                         // reduced scheme: the halo may be only B cells deep
         const double s2 = p[2 * st], s3 = p[3 * st];
         const double s1 = B == 2 ? p[st] : 0.0, s4 = B == 2 ? p[4 * st] : 0.0;
+        if constexpr (IM::on) return biased_interp_order(0.0, s1, s2, s3, s4, 0.0, left, min(B, im.template order<D, CEN>(i, j, k)));
         return biased_interp_low(s1, s2, s3, s4, left, bounded, idx, CEN, N, B, lo, hi);
     }
     double s0 = p[0], s1 = p[st], s2 = p[2 * st], s3 = p[3 * st], s4 = p[4 * st], s5 = p[5 * st];
+    if constexpr (IM::on) return biased_interp_order(s0, s1, s2, s3, s4, s5, left, im.template order<D, CEN>(i, j, k));
     return biased_interp(s0, s1, s2, s3, s4, s5, left, bounded, idx, CEN, N, lo, hi);
 }
 
 // advective_momentum_flux_{U,V,W}{u,v,w}: transport AQ interpolated along DS (CS), advected field reconstructed along
 // DB (CB).
-template <int AQ, int DS, bool CS, int DB, bool CB>
-__device__ __forceinline__ double mom_flux(const DGrid &g, const FView &adv, const FView &psi, int i, int j, int k) {
+// On an immersed grid the flux is conditional_flux_{ccc,ffc,fcf,cff}(i, j, k, ibg, 0, flux) (immersed_advective_fluxes.jl:39-55).
+template <int AQ, int DS, bool CS, int DB, bool CB, class IM = NoImm>
+__device__ __forceinline__ double mom_flux(const DGrid &g, const FView &adv, const FView &psi, int i, int j, int k, const IM &im = IM()) {
     if ((DB == 0 ? g.tx : (DB == 1 ? g.ty : g.tz)) == OCN_FLAT) return 0.0;     // fluxes along a Flat direction vanish (:13-27)
-    double ut = sym_transport<AQ, DS, CS>(g, adv, i, j, k, DB == 0 ? g.Bx : (DB == 1 ? g.By : g.Bz));
-    double pr = biased_field<DB, CB>(g, psi, ut > 0, i, j, k);
+    double ut = sym_transport<AQ, DS, CS, IM>(g, adv, i, j, k, DB == 0 ? g.Bx : (DB == 1 ? g.By : g.Bz), im);
+    double pr = biased_field<DB, CB, IM>(g, psi, ut > 0, i, j, k, im);
+    if constexpr (IM::on) return im.flux(imm_momentum_flux_bit<DS, DB>(), i, j, k, ut * pr);
     return ut * pr;
 }
 
 // advective_tracer_flux_{x,y,z} (:99-121): A * U[i,j,k] * cR
-template <int D> __device__ __forceinline__ double tracer_flux(const DGrid &g, const FView &vel, const FView &c, int i, int j, int k) {
+// (on an immersed grid conditional_flux_{fcc,cfc,ccf}, immersed_advective_fluxes.jl:57-59)
+template <int D, class IM = NoImm>
+__device__ __forceinline__ double tracer_flux(const DGrid &g, const FView &vel, const FView &c, int i, int j, int k, const IM &im = IM()) {
     if ((D == 0 ? g.tx : (D == 1 ? g.ty : g.tz)) == OCN_FLAT) return 0.0;
     double ut = vel.at(i, j, k);
-    double cr = biased_field<D, false>(g, c, ut > 0, i, j, k);
+    double cr = biased_field<D, false, IM>(g, c, ut > 0, i, j, k, im);
     double a = D == 0 ? g.ax[k - 1 + g.Hz] : (D == 1 ? g.ay[k - 1 + g.Hz] : g.az);
+    if constexpr (IM::on) return im.flux(IMM_FCC + D, i, j, k, a * ut * cr);
     return a * ut * cr;
 }
 
@@ -109,6 +119,43 @@ __global__ void __launch_bounds__(256) tendency_kernel(DGrid g, FView u, FView v
     }
     double div = vinv * ((dx + dy) + dz);
     G.at(i, j, k) = -div + 0.0;   // `-div - 0 + 0 ...` of the tendency functions: only maps -0.0 to +0.0
+}
+
+// The immersed instantiation (ocn_immersed.h), with the advecting velocities apart from the advected field like advective_tendency_kernel
+// (ocn_advect_split.h): compute_Gu!/Gv!/Gw!/Gc! pass psi = u, v, w, c. Every cell of the launch range is written, immersed cells
+// included -- the reference launches without an active-cells map.
+template <int F, bool ACC>
+__global__ void __launch_bounds__(256) immersed_tendency_kernel(DGrid g, ImmView im, FView ua, FView va, FView wa, FView psi, FView G, Range6 r) {
+    const int i = r.i0 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = r.j0 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = r.k0 + blockIdx.z;
+    if (i > r.i1 || j > r.j1 || k > r.k1) return;
+    using IM = ImmView;
+    double dx, dy, dz, vinv;
+    if (F == F_U) {
+        vinv = g.vinv_c[k - 1 + g.Hz];
+        dx = mom_flux<AQ_U, 0, true, 0, true, IM>(g, ua, psi, i, j, k, im) - mom_flux<AQ_U, 0, true, 0, true, IM>(g, ua, psi, i - 1, j, k, im);
+        dy = mom_flux<AQ_V, 0, false, 1, false, IM>(g, va, psi, i, j + 1, k, im) - mom_flux<AQ_V, 0, false, 1, false, IM>(g, va, psi, i, j, k, im);
+        dz = mom_flux<AQ_W, 0, false, 2, false, IM>(g, wa, psi, i, j, k + 1, im) - mom_flux<AQ_W, 0, false, 2, false, IM>(g, wa, psi, i, j, k, im);
+    } else if (F == F_V) {
+        vinv = g.vinv_c[k - 1 + g.Hz];
+        dx = mom_flux<AQ_U, 1, false, 0, false, IM>(g, ua, psi, i + 1, j, k, im) - mom_flux<AQ_U, 1, false, 0, false, IM>(g, ua, psi, i, j, k, im);
+        dy = mom_flux<AQ_V, 1, true, 1, true, IM>(g, va, psi, i, j, k, im) - mom_flux<AQ_V, 1, true, 1, true, IM>(g, va, psi, i, j - 1, k, im);
+        dz = mom_flux<AQ_W, 1, false, 2, false, IM>(g, wa, psi, i, j, k + 1, im) - mom_flux<AQ_W, 1, false, 2, false, IM>(g, wa, psi, i, j, k, im);
+    } else if (F == F_W) {
+        vinv = g.vinv_f[k - 1 + g.Hz];
+        dx = mom_flux<AQ_U, 2, false, 0, false, IM>(g, ua, psi, i + 1, j, k, im) - mom_flux<AQ_U, 2, false, 0, false, IM>(g, ua, psi, i, j, k, im);
+        dy = mom_flux<AQ_V, 2, false, 1, false, IM>(g, va, psi, i, j + 1, k, im) - mom_flux<AQ_V, 2, false, 1, false, IM>(g, va, psi, i, j, k, im);
+        dz = mom_flux<AQ_W, 2, true, 2, true, IM>(g, wa, psi, i, j, k, im) - mom_flux<AQ_W, 2, true, 2, true, IM>(g, wa, psi, i, j, k - 1, im);
+    } else {
+        vinv = g.vinv_c[k - 1 + g.Hz];
+        dx = tracer_flux<0, IM>(g, ua, psi, i + 1, j, k, im) - tracer_flux<0, IM>(g, ua, psi, i, j, k, im);
+        dy = tracer_flux<1, IM>(g, va, psi, i, j + 1, k, im) - tracer_flux<1, IM>(g, va, psi, i, j, k, im);
+        dz = tracer_flux<2, IM>(g, wa, psi, i, j, k + 1, im) - tracer_flux<2, IM>(g, wa, psi, i, j, k, im);
+    }
+    const double div = vinv * ((dx + dy) + dz);
+    if (ACC) G.at(i, j, k) = G.at(i, j, k) - div;
+    else     G.at(i, j, k) = -div + 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -235,6 +282,60 @@ __global__ void __launch_bounds__(256) closure_tendency_kernel(DGrid g, FView u,
     const int k = r.k0 + blockIdx.z;
     if (i > r.i1 || j > r.j1 || k > r.k1) return;
     G.at(i, j, k) = (G.at(i, j, k) - closure_divergence<F, false, VI>(g, u, v, w, c, coef, i, j, k, VI ? false : var, K)) + 0.0;
+}
+
+// The explicit constant-coefficient closure on an immersed grid (ocn_immersed.h): closure_divergence<F> with every flux
+// conditional_flux_*(i, j, k, ibg, 0, flux) at its own location and index (TurbulenceClosures/immersed_diffusive_fluxes.jl:27-44) --
+// viscous ux, vy, wz at ccc, uy = vx at ffc, uz = wx at fcf, vz = wy at cff; diffusive x, y, z at fcc, cfc, ccf. Same operation sequence
+// around the fluxes; no variable coefficient, no vertically implicit part (both refused on an immersed grid).
+template <int F>
+__device__ __forceinline__ double closure_divergence_immersed(const DGrid &g, const ImmView &im, const FView &u, const FView &v, const FView &w,
+                                                              const FView &c, double coef, int i, int j, int k) {
+    const ClosureCtx X{g, u, v, w, coef, g.tx == OCN_FLAT, g.ty == OCN_FLAT, g.tz == OCN_FLAT, false, u};
+    const double dx_ = g.dx, dy_ = g.dy;
+    auto f11 = [&](int a, int b, int d) { return im.flux(IMM_CCC, a, b, d, X.vf11(a, b, d)); };
+    auto f22 = [&](int a, int b, int d) { return im.flux(IMM_CCC, a, b, d, X.vf22(a, b, d)); };
+    auto f33 = [&](int a, int b, int d) { return im.flux(IMM_CCC, a, b, d, X.vf33(a, b, d)); };
+    auto f12 = [&](int a, int b, int d) { return im.flux(IMM_FFC, a, b, d, X.vf12(a, b, d)); };
+    auto f13 = [&](int a, int b, int d) { return im.flux(IMM_FCF, a, b, d, X.vf13(a, b, d)); };
+    auto f23 = [&](int a, int b, int d) { return im.flux(IMM_CFF, a, b, d, X.vf23(a, b, d)); };
+    double dx, dy, dz, vinv;
+    if (F == F_U) {
+        vinv = g.vinv_c[k - 1 + g.Hz];
+        dx = X.fx ? 0.0 : (dy_ * X.dzc(k)) * f11(i, j, k) - (dy_ * X.dzc(k)) * f11(i - 1, j, k);
+        dy = X.fy ? 0.0 : (dx_ * X.dzc(k)) * f12(i, j + 1, k) - (dx_ * X.dzc(k)) * f12(i, j, k);
+        dz = X.fz ? 0.0 : (dx_ * dy_) * f13(i, j, k + 1) - (dx_ * dy_) * f13(i, j, k);
+    } else if (F == F_V) {
+        vinv = g.vinv_c[k - 1 + g.Hz];
+        dx = X.fx ? 0.0 : (dy_ * X.dzc(k)) * f12(i + 1, j, k) - (dy_ * X.dzc(k)) * f12(i, j, k);
+        dy = X.fy ? 0.0 : (dx_ * X.dzc(k)) * f22(i, j, k) - (dx_ * X.dzc(k)) * f22(i, j - 1, k);
+        dz = X.fz ? 0.0 : (dx_ * dy_) * f23(i, j, k + 1) - (dx_ * dy_) * f23(i, j, k);
+    } else if (F == F_W) {
+        vinv = g.vinv_f[k - 1 + g.Hz];
+        dx = X.fx ? 0.0 : (dy_ * X.dzf(k)) * f13(i + 1, j, k) - (dy_ * X.dzf(k)) * f13(i, j, k);
+        dy = X.fy ? 0.0 : (dx_ * X.dzf(k)) * f23(i, j + 1, k) - (dx_ * X.dzf(k)) * f23(i, j, k);
+        dz = X.fz ? 0.0 : (dx_ * dy_) * f33(i, j, k) - (dx_ * dy_) * f33(i, j, k - 1);
+    } else {
+        vinv = g.vinv_c[k - 1 + g.Hz];
+        const double ax = dy_ * X.dzc(k), ay = dx_ * X.dzc(k), az = dx_ * dy_;
+        auto qx = [&](int a, int b, int d) { return im.flux(IMM_FCC, a, b, d, -(coef * X.ddx_f(c, a, b, d))); };
+        auto qy = [&](int a, int b, int d) { return im.flux(IMM_CFC, a, b, d, -(coef * X.ddy_f(c, a, b, d))); };
+        auto qz = [&](int a, int b, int d) { return im.flux(IMM_CCF, a, b, d, -(coef * X.ddz_f(c, a, b, d))); };
+        dx = X.fx ? 0.0 : ax * qx(i + 1, j, k) - ax * qx(i, j, k);
+        dy = X.fy ? 0.0 : ay * qy(i, j + 1, k) - ay * qy(i, j, k);
+        dz = X.fz ? 0.0 : az * qz(i, j, k + 1) - az * qz(i, j, k);
+    }
+    return vinv * ((dx + dy) + dz);
+}
+
+template <int F>
+__global__ void __launch_bounds__(256) immersed_closure_tendency_kernel(DGrid g, ImmView im, FView u, FView v, FView w, FView c, FView G, double coef,
+                                                                        Range6 r) {
+    const int i = r.i0 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = r.j0 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = r.k0 + blockIdx.z;
+    if (i > r.i1 || j > r.j1 || k > r.k1) return;
+    G.at(i, j, k) = (G.at(i, j, k) - closure_divergence_immersed<F>(g, im, u, v, w, c, coef, i, j, k)) + 0.0;
 }
 
 // a tracer of a Smagorinsky closure with Pr ≠ 1: κ = ℑ(νₑ) / Pr at the flux points
@@ -873,6 +974,8 @@ __device__ __forceinline__ bool inactive_cell(const DGrid &g, int i, int j, int 
            (g.tz == OCN_BOUNDED && (k < 1 || k > g.Nz));
 }
 
+// (x_f_cross_U_with / y_f_cross_U_with below are the same two bodies with the inactive-cell test handed in, for immersed grids: a change
+// here is a change there.)
 // x_f_cross_U at (f, c, c) and y_f_cross_U at (c, f, c). The field is read through `q(di, dj)` = value at (i + di, j + dj, k): from memory
 // (the stand-alone kernels) or from the registers of the marching epilogue -- one body for both, so the same operations on the same values.
 template <class Q>
@@ -899,6 +1002,33 @@ __device__ __forceinline__ double y_f_cross_U_of(const DGrid &g, double f, Q q, 
     const double aw = an == 0 ? 0.0 : qa / an;
     return f * aw;
 }
+// The same two averages with inactive_cell at level k handed in as `inactive(ii, jj)`: bit 0 of the periphery byte on an immersed grid, whose
+// peripheral_node counts the immersed cells (immersed_boundary_interface.jl:49). (Bodies apart from the ones above: those are part of the
+// marching epilogue's instantiations, which keep their registers.)
+template <class Q, class IC>
+__device__ __forceinline__ double x_f_cross_U_with(const DGrid &g, double f, Q q, int i, int j, int k, IC inactive) {
+    const bool fx = g.tx == OCN_FLAT, fy = g.ty == OCN_FLAT;
+    // ℑxyᶠᶜᵃ = ℑyᵃᶜᵃ(ℑxᶠᵃᵃ ·): X(jj) = 0.5 (q[i-1, jj] + q[i, jj]); 0.5 (X(j) + X(j+1)); not_peripheral at (c, f, c)
+    auto np = [&](int ii, int jj) { return !(inactive(ii, jj) || inactive(ii, jj - 1)) ? 1.0 : 0.0; };
+    auto Xq = [&](int dj) { return fx ? q(0, dj) : 0.5 * (q(-1, dj) + q(0, dj)); };
+    auto Xn = [&](int jj) { return fx ? np(i, jj) : 0.5 * (np(i - 1, jj) + np(i, jj)); };
+    const double qa = fy ? Xq(0) : 0.5 * (Xq(0) + Xq(1));
+    const double an = fy ? Xn(j) : 0.5 * (Xn(j) + Xn(j + 1));
+    const double aw = an == 0 ? 0.0 : qa / an;
+    return -f * aw;
+}
+template <class Q, class IC>
+__device__ __forceinline__ double y_f_cross_U_with(const DGrid &g, double f, Q q, int i, int j, int k, IC inactive) {
+    const bool fx = g.tx == OCN_FLAT, fy = g.ty == OCN_FLAT;
+    // ℑxyᶜᶠᵃ = ℑyᵃᶠᵃ(ℑxᶜᵃᵃ ·): X(jj) = 0.5 (q[i, jj] + q[i+1, jj]); 0.5 (X(j-1) + X(j)); not_peripheral at (f, c, c)
+    auto np = [&](int ii, int jj) { return !(inactive(ii, jj) || inactive(ii - 1, jj)) ? 1.0 : 0.0; };
+    auto Xq = [&](int dj) { return fx ? q(0, dj) : 0.5 * (q(0, dj) + q(1, dj)); };
+    auto Xn = [&](int jj) { return fx ? np(i, jj) : 0.5 * (np(i, jj) + np(i + 1, jj)); };
+    const double qa = fy ? Xq(0) : 0.5 * (Xq(-1) + Xq(0));
+    const double an = fy ? Xn(j) : 0.5 * (Xn(j - 1) + Xn(j));
+    const double aw = an == 0 ? 0.0 : qa / an;
+    return f * aw;
+}
 __device__ __forceinline__ double x_f_cross_U(const DGrid &g, double f, const FView &v, int i, int j, int k) {
     return x_f_cross_U_of(g, f, [&](int di, int dj) { return v.at(i + di, j + dj, k); }, i, j, k);
 }
@@ -915,6 +1045,20 @@ __global__ void __launch_bounds__(256) fplane_coriolis_kernel(DGrid g, double f,
         Gu.at(i, j, k) = Gu.at(i, j, k) - x_f_cross_U(g, f, v, i, j, k);
     if (i >= rv.i0 && i <= rv.i1 && j >= rv.j0 && j <= rv.j1 && k >= rv.k0 && k <= rv.k1)
         Gv.at(i, j, k) = Gv.at(i, j, k) - y_f_cross_U(g, f, u, i, j, k);
+}
+
+// the same on an immersed grid: not_peripheral read from the periphery byte (ocn_immersed.h)
+__global__ void __launch_bounds__(256) immersed_fplane_coriolis_kernel(DGrid g, ImmView im, double f, FView u, FView v, FView Gu, FView Gv, Range6 ru,
+                                                                       Range6 rv) {
+    const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = 1 + blockIdx.y * blockDim.y + threadIdx.y;
+    const int k = 1 + blockIdx.z;
+    if (i > g.Nx || j > g.Ny || k > g.Nz) return;
+    auto inactive = [&](int ii, int jj) { return im.bit(IMM_INACTIVE, ii, jj, k); };
+    if (i >= ru.i0 && i <= ru.i1 && j >= ru.j0 && j <= ru.j1 && k >= ru.k0 && k <= ru.k1)
+        Gu.at(i, j, k) = Gu.at(i, j, k) - x_f_cross_U_with(g, f, [&](int di, int dj) { return v.at(i + di, j + dj, k); }, i, j, k, inactive);
+    if (i >= rv.i0 && i <= rv.i1 && j >= rv.j0 && j <= rv.j1 && k >= rv.k0 && k <= rv.k1)
+        Gv.at(i, j, k) = Gv.at(i, j, k) - y_f_cross_U_with(g, f, [&](int di, int dj) { return u.at(i + di, j + dj, k); }, i, j, k, inactive);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -147,8 +147,38 @@ template <int ROLE, bool SPLIT = false> __device__ __forceinline__ Win6 load_zin
     if (ROLE == ROLE_C) w.s[3] = ldb<24>(p.w, o.c, so);
     return w;
 }
-template <int ROLE, int ARITH, bool SPLIT = false>
-__device__ __forceinline__ double z_flux(const DGrid &g, const Win6 &zin, int i, int j, int k, const Win6 &qz) {
+// The immersed instantiation (IM = ImmView, ocn_immersed.h; reference arithmetic, no SPLIT): the same windows and the same operation
+// sequence per flux, the reconstruction chosen by the grid's order entry at the index the _interpolate function is called with instead
+// of the topological test, the flux conditional on the periphery bit of its own location. The flag words of a plane are loaded where
+// the plane's windows are: one byte / one 16-bit word per lane, consecutive along x.
+__device__ __forceinline__ double sym4_im(const Win6 &q, double a, int order) {
+    return symmetric_interp_order(a * q.s[1], a * q.s[2], a * q.s[3], a * q.s[4], order);
+}
+__device__ __forceinline__ double sym4z_im(const Win6 &q, const double *a, int order) {
+    return symmetric_interp_order(a[0] * q.s[1], a[1] * q.s[2], a[2] * q.s[3], a[3] * q.s[4], order);
+}
+__device__ __forceinline__ double bias6_im(const Win6 &s, bool left, int order) {
+    return biased_interp_order(s.s[0], s.s[1], s.s[2], s.s[3], s.s[4], s.s[5], left, order);
+}
+template <int ROLE, int ARITH, bool SPLIT = false, class IM = NoImm>
+__device__ __forceinline__ double z_flux(const DGrid &g, const Win6 &zin, int i, int j, int k, const Win6 &qz, const IM &im = IM()) {
+    if constexpr (IM::on) {
+        const double az = g.az;
+        if (ROLE == ROLE_U) {
+            const double wt = sym4_im(zin, az, im.template order<0, false>(i, j, k));
+            return im.flux(IMM_FCF, i, j, k, wt * bias6_im(qz, wt > 0, im.template order<2, false>(i, j, k)));
+        } else if (ROLE == ROLE_V) {
+            const double wt = sym4_im(zin, az, im.template order<1, false>(i, j, k));
+            return im.flux(IMM_CFF, i, j, k, wt * bias6_im(qz, wt > 0, im.template order<2, false>(i, j, k)));
+        } else if (ROLE == ROLE_W) {
+            const int o = im.template order<2, true>(i, j, k - 1);
+            const double wt = sym4_im(qz, az, o);
+            return im.flux(IMM_CCC, i, j, k - 1, wt * bias6_im(qz, wt > 0, o));
+        } else {
+            const double w0 = zin.s[3];
+            return im.flux(IMM_CCF, i, j, k, az * w0 * bias6_im(qz, w0 > 0, im.template order<2, false>(i, j, k)));
+        }
+    }
     const bool bx = g.tx != 0, by = g.ty != 0, bz = g.tz != 0;
     const double az = g.az;
     if (ROLE == ROLE_U) {
@@ -175,8 +205,24 @@ template <int ROLE, bool SPLIT = false> __device__ __forceinline__ Win6 load_xau
     if (ROLE == ROLE_C) w.s[3] = ldb<24>(p.u, o.c, p.so);
     return w;
 }
-template <int ROLE, int ARITH, bool SPLIT = false>
-__device__ __forceinline__ double x_flux(const DGrid &g, const PlaneCtx &p, const Win6 &qx, const Win6 &aux, int i, int j, int k) {
+template <int ROLE, int ARITH, bool SPLIT = false, class IM = NoImm>
+__device__ __forceinline__ double x_flux(const DGrid &g, const PlaneCtx &p, const Win6 &qx, const Win6 &aux, int i, int j, int k, const IM &im = IM()) {
+    if constexpr (IM::on) {
+        if (ROLE == ROLE_U) {
+            const int o = im.template order<0, true>(i - 1, j, k);
+            const double ut = sym4_im(qx, p.axk, o);
+            return im.flux(IMM_CCC, i - 1, j, k, ut * bias6_im(qx, ut > 0, o));
+        } else if (ROLE == ROLE_V) {
+            const double ut = sym4_im(aux, p.axk, im.template order<1, false>(i, j, k));
+            return im.flux(IMM_FFC, i, j, k, ut * bias6_im(qx, ut > 0, im.template order<0, false>(i, j, k)));
+        } else if (ROLE == ROLE_W) {
+            const double ut = sym4z_im(aux, p.axz, im.template order<2, false>(i, j, k));
+            return im.flux(IMM_FCF, i, j, k, ut * bias6_im(qx, ut > 0, im.template order<0, false>(i, j, k)));
+        } else {
+            const double u0 = aux.s[3];
+            return im.flux(IMM_FCC, i, j, k, p.axk * u0 * bias6_im(qx, u0 > 0, im.template order<0, false>(i, j, k)));
+        }
+    }
     const bool bx = g.tx != 0, by = g.ty != 0, bz = g.tz != 0;
     if (ROLE == ROLE_U) {
         const double ut = sym4<ARITH>(SPLIT ? aux : qx, p.axk, bx, i - 1, true, g.Nx);                    // advective_momentum_flux_Uu :23-29
@@ -202,8 +248,24 @@ template <int ROLE, bool SPLIT = false> __device__ __forceinline__ Win6 load_yau
     if (ROLE == ROLE_C) w.s[3] = ldb<24>(p.v, o.c, p.so);
     return w;
 }
-template <int ROLE, int ARITH, bool SPLIT = false>
-__device__ __forceinline__ double y_flux(const DGrid &g, const PlaneCtx &p, const Win6 &qy, const Win6 &aux, int i, int j, int k) {
+template <int ROLE, int ARITH, bool SPLIT = false, class IM = NoImm>
+__device__ __forceinline__ double y_flux(const DGrid &g, const PlaneCtx &p, const Win6 &qy, const Win6 &aux, int i, int j, int k, const IM &im = IM()) {
+    if constexpr (IM::on) {
+        if (ROLE == ROLE_U) {
+            const double vt = sym4_im(aux, p.ayk, im.template order<0, false>(i, j, k));
+            return im.flux(IMM_FFC, i, j, k, vt * bias6_im(qy, vt > 0, im.template order<1, false>(i, j, k)));
+        } else if (ROLE == ROLE_V) {
+            const int o = im.template order<1, true>(i, j - 1, k);
+            const double vt = sym4_im(qy, p.ayk, o);
+            return im.flux(IMM_CCC, i, j - 1, k, vt * bias6_im(qy, vt > 0, o));
+        } else if (ROLE == ROLE_W) {
+            const double vt = sym4z_im(aux, p.ayz, im.template order<2, false>(i, j, k));
+            return im.flux(IMM_CFF, i, j, k, vt * bias6_im(qy, vt > 0, im.template order<1, false>(i, j, k)));
+        } else {
+            const double v0 = aux.s[3];
+            return im.flux(IMM_CFC, i, j, k, p.ayk * v0 * bias6_im(qy, v0 > 0, im.template order<1, false>(i, j, k)));
+        }
+    }
     const bool bx = g.tx != 0, by = g.ty != 0, bz = g.tz != 0;
     if (ROLE == ROLE_U) {
         const double vt = sym4<ARITH>(aux, p.ayk, bx, i, false, g.Nx);                      // advective_momentum_flux_Vu :31-37
@@ -245,7 +307,12 @@ template <bool SPLIT, typename Args> __device__ __forceinline__ const double *ro
 
 // SPLIT: advecting (a.A) and advected (a.U[fidx]) arrays differ. ACC: the tendency array already holds earlier terms, G = G - div (the
 // previous value of a cell arrives through the stream the fused substep uses for G⁻, one plane ahead of its use).
-template <int ROLE, int TY, bool SUB, bool BZ, int ARITH, bool FORCE, typename Args, bool SPLIT = false, bool ACC = false>
+template <class IM, typename Args> __device__ __forceinline__ IM role_immersed(const Args &a) {
+    if constexpr (IM::on) return a.im; else return IM();
+}
+
+// IM = ImmView (immersed_role_tendency_kernel): the launch's arguments carry the grid's flag tables
+template <int ROLE, int TY, bool SUB, bool BZ, int ARITH, bool FORCE, typename Args, bool SPLIT = false, bool ACC = false, class IM = NoImm>
 __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const int fidx, const int i0, const int j0, const int kc0,
                                            const int kc1, double (*FX)[TY][66], double (*FY)[TY + 1][64]) {
     // Bounded z: only the planes within reach of a wall need the fallback logic of the scheme (every z-stencil test of
@@ -254,7 +321,9 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
     // loop of a Bounded-z launch is the Periodic one (it was 6.5 % slower per cell: more code in the loop, conditions per plane).
     DGrid gP = g, gB = g;
     gP.tz = 0; gB.tz = BZ ? 1 : 0;
-    auto near_wall = [&](int k) { return BZ && (k < 4 || k > g.Nz - 2); };
+    // (an immersed launch has no wall planes: the order entries decide at every level, the topology of the copy is never read)
+    auto near_wall = [&](int k) { return !IM::on && BZ && (k < 4 || k > g.Nz - 2); };
+    const IM im = role_immersed<IM>(a);
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const bool edge = wave == TY;
@@ -265,6 +334,9 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
     const bool edge_y = edge && i <= a.r.i1 && j <= a.r.j1 + 1;
     const int ie = i0 + 64, je = j0 + lane;
     const bool edge_x = edge && lane < TY && ie <= a.r.i1 + 1 && je <= a.r.j1;
+    // the index the flags are read at: lanes right of the range compute fluxes nobody reads from zeros (ROLE_OOB below), but a flag load
+    // is a plain load and stays inside the tables
+    const int fi = IM::on ? min(i, a.r.i1 + 1) : i, fj = IM::on ? min(j, a.r.j1 + 1) : j;
 
     const unsigned s2 = 8u * a.s2;                    // plane stride in bytes
     const int Hz = g.Hz;
@@ -317,13 +389,13 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
                 if (edge_y && !(OCN_ROLE_ABLATE & 32)) {
                     const Win6 qy = ywin6<false>(p.q, p.so, o, 0.0);
                     const Win6 aux = ROLE == ROLE_W ? zwin4(p.v, p.so, o, s2) : load_yaux<ROLE, SPLIT>(p, o);
-                    FY[buf][TY][lane] = y_flux<ROLE, ARITH, SPLIT>(gg, p, qy, aux, i, j, k);
+                    FY[buf][TY][lane] = y_flux<ROLE, ARITH, SPLIT, IM>(gg, p, qy, aux, i, j, k, im);
                 }
                 if (edge_x && !(OCN_ROLE_ABLATE & 32)) {
                     asm volatile("" : "+v"(e.c));
                     const Win6 qxe = xwin6<false>(p.q, p.so, e, 0.0);
                     const Win6 aux = ROLE == ROLE_W ? zwin4(p.u, p.so, e, s2) : load_xaux<ROLE, SPLIT>(p, e);
-                    FX[buf][lane][64] = x_flux<ROLE, ARITH, SPLIT>(gg, p, qxe, aux, ie, je, k);
+                    FX[buf][lane][64] = x_flux<ROLE, ARITH, SPLIT, IM>(gg, p, qxe, aux, ie, je, k, im);
                 }
             };
             if (ROLE == ROLE_W && near_wall(k)) edge_plane(gB); else edge_plane(gP);     // only role w interpolates along z here
@@ -359,7 +431,7 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
         zin = load_zin<ROLE, SPLIT>(p, p.so, o);
     };
     auto z_compute = [&](const DGrid &gg, const int k, const int buf, const long pk) {
-        const double fz = z_flux<ROLE, ARITH, SPLIT>(gg, zin, i, j, k, qz);
+        const double fz = z_flux<ROLE, ARITH, SPLIT, IM>(gg, zin, fi, fj, k, qz, im);
         const int pb = buf ^ 1;
         const long pkm = pk - 1;
         const double vinv = ROLE == ROLE_W ? ktab(g.vinv_f)[pkm] : ktab(g.vinv_c)[pkm];
@@ -426,12 +498,12 @@ __device__ __forceinline__ void role_march(const DGrid &g, const Args &a, const 
             x_loads();
             stores();
             __builtin_amdgcn_sched_barrier(0);
-            FX[buf][row0][lane] = x_flux<ROLE, ARITH, SPLIT>(gg, p, qx, xaux, i, j, k);
+            FX[buf][row0][lane] = x_flux<ROLE, ARITH, SPLIT, IM>(gg, p, qx, xaux, fi, fj, k, im);
             __builtin_amdgcn_sched_barrier(0);
             y_loads();
             prefetches();
             __builtin_amdgcn_sched_barrier(0);
-            FY[buf][row0][lane] = y_flux<ROLE, ARITH, SPLIT>(gg, p, qy, yaux, i, j, k);
+            FY[buf][row0][lane] = y_flux<ROLE, ARITH, SPLIT, IM>(gg, p, qy, yaux, fi, fj, k, im);
         };
         if (near_wall(k)) plane(gB); else plane(gP);
         p.so += s2;
@@ -469,6 +541,35 @@ __global__ void __launch_bounds__(64 * (TY + 1), OCN_ROLE_WAVES) role_tendency_k
     else if (role == 1) role_march<ROLE_V, TY, SUB, BZ, ARITH, FORCE>(g, a, 1, i0, j0, kc0, kc1, FX, FY);
     else if (role == 2) role_march<ROLE_W, TY, SUB, BZ, ARITH, FORCE>(g, a, 2, i0, j0, kc0, kc1, FX, FY);
     else role_march<ROLE_C, TY, SUB, BZ, ARITH, FORCE>(g, a, (int)role, i0, j0, kc0, kc1, FX, FY);
+}
+
+// The flux-sharing tendency kernel of an immersed grid ("immersed_tendency_path" 2): the role kernel's march with IM = ImmView, for grids
+// periodic in x and y without a Flat or reduced-order direction; no substep, no forcing, reference arithmetic (an immersed model takes the
+// plainest composition). Bounded and Periodic z share one instantiation: the order entries hold the walls. Four waves per SIMD are asked
+// for instead of six: the flag loads and the selects need registers the six-wave budget does not have.
+template <int NF>
+struct RoleImmArgs : RoleArgs<NF> {
+    ImmView im;
+};
+template <int NTR, int TY>
+__global__ void __launch_bounds__(64 * (TY + 1), 4) immersed_role_tendency_kernel(DGrid gin, RoleImmArgs<3 + NTR> a) {
+    constexpr int NF = 3 + NTR;
+    __shared__ double FX[2][TY][66];
+    __shared__ double FY[2][TY + 1][64];
+    DGrid g = gin;
+    g.tx = 0; g.ty = 0; g.tz = 0;
+    const unsigned d = blockIdx.x, xcd = d & 7u, slot = d >> 3;
+    const unsigned role = slot % NF, pair = xcd * (unsigned)a.band + slot / NF;
+    if (slot / NF >= (unsigned)a.band || pair >= (unsigned)a.npair) return;
+    const unsigned tile = pair % (unsigned)a.ntile, chunk = pair / (unsigned)a.ntile;
+    const int i0 = a.r.i0 + (int)(tile % (unsigned)a.ntile_x) * 64, j0 = a.r.j0 + (int)(tile / (unsigned)a.ntile_x) * TY;
+    const int kc0 = a.r.k0 + (int)chunk * a.kchunk;
+    const int kc1 = min(kc0 + a.kchunk - 1, a.r.k1);
+    using A = RoleImmArgs<NF>;
+    if (role == 0) role_march<ROLE_U, TY, false, false, 0, false, A, false, false, ImmView>(g, a, 0, i0, j0, kc0, kc1, FX, FY);
+    else if (role == 1) role_march<ROLE_V, TY, false, false, 0, false, A, false, false, ImmView>(g, a, 1, i0, j0, kc0, kc1, FX, FY);
+    else if (role == 2) role_march<ROLE_W, TY, false, false, 0, false, A, false, false, ImmView>(g, a, 2, i0, j0, kc0, kc1, FX, FY);
+    else role_march<ROLE_C, TY, false, false, 0, false, A, false, false, ImmView>(g, a, (int)role, i0, j0, kc0, kc1, FX, FY);
 }
 
 // The role kernel addresses memory with a 31-bit byte offset (bit 31 is the out-of-range flag of its buffer descriptors, whose num_records
@@ -565,6 +666,52 @@ static inline int launch_role_tendency(const OcnOptions &o, const DGrid &g, hipS
         case 1: return launch_roles_n<1>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
         case 2: return launch_roles_n<2>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
         case 3: return launch_roles_n<3>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, sub, ftab);
+        default: return -2;
+    }
+}
+
+template <int NTR>
+static int launch_roles_immersed_n(const OcnOptions &o, const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w,
+                                   const double *const *tr, double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range, const ImmView &im) {
+    constexpr int NF = 3 + NTR, TY = OCN_ROLE_TY;
+    RoleImmArgs<NF> a;
+    a.im = im;
+    a.ftab = nullptr;
+    a.U[0] = u; a.U[1] = v; a.U[2] = w; a.G[0] = Gu; a.G[1] = Gv; a.G[2] = Gw;
+    for (int t = 0; t < NTR; ++t) { a.U[3 + t] = tr[t]; a.G[3 + t] = Gc[t]; }
+    a.has_zeta = 0; a.store_G = 1; a.dt = a.gamma = a.zeta = 0.0;
+    for (int f = 0; f < NF; ++f) { a.Un[f] = nullptr; a.Gm[f] = nullptr; }
+    const int Px = g.Nx + 2 * g.Hx, Py = g.Ny + 2 * g.Hy;
+    a.s1 = Px;
+    a.s2 = (unsigned)((long)Px * Py);
+    a.off = (g.Hx - 1) + (long)Px * (g.Hy - 1);
+    if (range) {
+        a.r = Range6{range[0], range[1], range[2], range[3], range[4], range[5]};
+        a.wk0 = a.r.k0;
+    } else {
+        a.r = Range6{1, g.Nx, 1, g.Ny, 1, g.Nz};
+        a.wk0 = (g.tz != 0 && g.Nz > 1) ? 2 : 1;
+    }
+    const int nx = a.r.i1 - a.r.i0 + 1, ny = a.r.j1 - a.r.j0 + 1, nz = a.r.k1 - a.r.k0 + 1;
+    if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
+    a.ntile_x = (nx + 63) / 64;
+    a.ntile = a.ntile_x * ((ny + TY - 1) / TY);
+    a.kchunk = o.role_kchunk > 0 ? o.role_kchunk : pick_role_kchunk((long)a.ntile * NF, nz);
+    const int nchunk = (nz + a.kchunk - 1) / a.kchunk;
+    a.npair = a.ntile * nchunk;
+    a.band = (a.npair + 7) / 8;
+    hipLaunchKernelGGL((immersed_role_tendency_kernel<NTR, TY>), dim3((unsigned)a.band * 8u * NF), dim3(64 * (TY + 1)), (size_t)o.role_ldspad, stream, g, a);
+    return 0;
+}
+
+static inline int launch_role_tendency_immersed(const OcnOptions &o, const DGrid &g, hipStream_t stream, const double *u, const double *v, const double *w,
+                                                const double *const *tr, int ntr, double *Gu, double *Gv, double *Gw, double *const *Gc,
+                                                const int *range, const ImmView &im) {
+    switch (ntr) {
+        case 0: return launch_roles_immersed_n<0>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, im);
+        case 1: return launch_roles_immersed_n<1>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, im);
+        case 2: return launch_roles_immersed_n<2>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, im);
+        case 3: return launch_roles_immersed_n<3>(o, g, stream, u, v, w, tr, Gu, Gv, Gw, Gc, range, im);
         default: return -2;
     }
 }

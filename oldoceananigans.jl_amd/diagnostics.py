@@ -37,6 +37,11 @@ class FieldStatus:
 
 
 def _check_grid(grid):
+    if hasattr(grid, "immersed_boundary"):
+        # the reference's reductions and operations on an immersed grid exclude the immersed cells through a condition
+        # (immersed_reductions.jl), which this library does not have
+        from .immersed_boundaries import refuse
+        refuse("a diagnostic (operation, reduction, scan or time average; the reference excludes immersed cells through a condition)")
     if any(t in (FullyConnected, RightConnected, LeftConnected) for t in grid.topology):
         raise NotImplementedError("diagnostics on a partitioned grid are not built: gather the fields of the ranks (or reduce per rank and "
                                   "combine on the host)")

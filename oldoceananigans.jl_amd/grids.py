@@ -380,4 +380,6 @@ class RectilinearGrid:
 
 def with_halo(halo, grid):
     """with_halo(halo, grid::RectilinearGrid) (rectilinear_grid.jl:442-449): the same grid with another halo"""
+    if hasattr(grid, "_with_halo"):              # an ImmersedBoundaryGrid materialises its boundary again (immersed_boundary_grid.jl:93-98)
+        return grid._with_halo(tuple(halo))
     return type(grid)(grid.architecture, halo=tuple(halo), **grid._constructor_arguments)

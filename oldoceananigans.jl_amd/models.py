@@ -63,6 +63,10 @@ class NonhydrostaticModel:
             raise NotImplementedError("buoyancy must be nothing, BuoyancyTracer(), SeawaterBuoyancy(LinearEquationOfState) or a BuoyancyForce of one")
         self.buoyancy = buoyancy
         tilted = force is not None and force.tilted
+        from . import immersed_boundaries as _immersed
+        immersed = _immersed.is_immersed(grid)
+        if immersed:                                     # refused here, before any handle exists
+            _immersed.validate_model(grid, closure, force, coriolis, background_fields, stokes_drift, particles, boundary_conditions)
         if hasattr(grid, "local") and (tilted or isinstance(coriolis, ConstantCartesianCoriolis)):
             raise NotImplementedError("ConstantCartesianCoriolis and BuoyancyForce(gravity_unit_vector) are not served on partitioned grids")
         from . import stokes_drifts as _stokes
@@ -94,7 +98,9 @@ class NonhydrostaticModel:
         required = inflate_halo_size(*grid.halo_size, grid, advection, closure)
         if any(u < r for u, r in zip(grid.halo_size, required)):
             import warnings
-            warnings.warn(f"Inflating model grid halo size to {required} and recreating grid. The model grid will be different from the "
+            note = ("Note that an ImmersedBoundaryGrid requires an extra halo point in all non-flat directions compared to a non-immersed "
+                    "boundary grid. ") if immersed else ""             # (nonhydrostatic_model.jl:252-256)
+            warnings.warn(f"Inflating model grid halo size to {required} and recreating grid. {note}The model grid will be different from the "
                           f"input grid. To avoid this warning, pass halo={required} when constructing the grid.")
             grid = with_halo(required, grid)
         self.grid, self.advection = grid, advection
@@ -120,6 +126,10 @@ class NonhydrostaticModel:
         from .closures import AnisotropicMinimumDissipation as _AMD, Smagorinsky as _Smag
         tracked = _particles.validate_particles(particles, grid, self.tracer_names, buoyancy is not None, isinstance(closure, (_AMD, _Smag)))
         self.particles = None
+        if immersed:
+            # nonhydrostatic_pressure_solver(arch, ibg::IBGWithFFTSolver) (NonhydrostaticModels.jl:42-58): the underlying grid's solver
+            import warnings
+            warnings.warn(_immersed.FFT_WARNING)
         self.handle = self._create_handle(grid, len(self.tracer_names))
         self.clock = Clock(self)
         V = namedtuple("Velocities", "u v w")

@@ -40,7 +40,7 @@ def jl_type(t):
         return "Ptr{Cstring}" if ptr > 1 else "Cstring"
     if base == "void":
         return "Ptr{Ptr{Cvoid}}" if ptr > 1 else "Ptr{Cvoid}"
-    scalar = {"int": "Cint", "double": "Cdouble", "size_t": "Csize_t", "long": "Clong", "int64_t": "Int64", "unsigned": "Cuint"}.get(base, base)
+    scalar = {"int": "Cint", "double": "Cdouble", "size_t": "Csize_t", "long": "Clong", "int64_t": "Int64", "unsigned": "Cuint", "uint8_t": "UInt8", "uint16_t": "UInt16"}.get(base, base)
     if ptr >= 2:
         return "Ptr{Ptr{%s}}" % scalar
     if ptr == 1:
