@@ -2053,6 +2053,198 @@ __global__ void __launch_bounds__(256) line_scatter_kernel(const double2 *B, dou
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The LDS line kernels below (zline_solve_kernel, strided_line_fft_kernel) at a line length known when they are compiled: NC points,
+// E = NC / KQ = 1, 2, 4, 8 or 16 of them per thread (KQ = 256 / ZL k-rows per pass). The generic loops have run-time trip counts, and the
+// compiler serialises them: one global_load_dwordx4, s_waitcnt vmcnt(0), one ds_write_b128 per iteration -- E HBM round trips one after
+// the other with 16 B per lane in flight --, and every butterfly waits for its own twiddle loads. Here
+//  * a thread issues ALL E loads of its part of the line back to back, and only then writes them to LDS; a lane past the last column
+//    loads its workgroup's first column instead (a clamped address, no branch between the loads) and stores zeros;
+//  * the twiddles of a butterfly stage are in registers before the stage starts: those of the first stage are loaded behind the data
+//    loads, those of every later stage in front of the LDS reads of the stage before it (LDS stays at NC x ZL x 16 B: the same
+//    workgroups per CU, and 1024 x 4 lines already take the 64 KB a workgroup may ask for).
+// Same values, same operations in the same order as the generic loops (the build has -ffp-contract=off): bit-identical results.
+// OCN_LINE_IN_FLIGHT=0 sends every line length back to the generic loops -- for A/B timing only (tools/ab_build.sh).
+// ---------------------------------------------------------------------------------------------------------------------
+#ifndef OCN_LINE_IN_FLIGHT
+#define OCN_LINE_IN_FLIGHT 1
+#endif
+constexpr int line_ilog2(int n) { return n <= 1 ? 0 : 1 + line_ilog2(n >> 1); }
+// waves per SIMD the fixed-length kernels must leave room for: a 32 KB line buffer fits five times into a CU's 160 KB of LDS, and five
+// workgroups of four waves are five waves per SIMD (<= 96 VGPRs); every other shape is left to the compiler
+constexpr int line_min_waves(int zl, int nc) { return nc * zl * (int)sizeof(double2) == 32768 ? 5 : 1; }
+__device__ __forceinline__ double2 line_add(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ double2 line_sub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ double2 line_cmul(double2 v, double2 w) { return make_double2(v.x * w.x - v.y * w.y, v.x * w.y + v.y * w.x); }     // v * w
+__device__ __forceinline__ double2 line_cmulc(double2 v, double2 w) { return make_double2(v.x * w.x + v.y * w.y, v.y * w.x - v.x * w.y); }    // v * conj(w)
+
+template <int ZL, int NC>
+struct LineFFT {
+    static constexpr int KQ = 256 / ZL, E = NC / KQ, HALF = NC >> 1, QUARTER = NC >> 2, LOGN = line_ilog2(NC);
+    static constexpr int ODD = LOGN & 1, NS4 = LOGN >> 1;                         // one radix-2 stage when log2 NC is odd, NS4 radix-4 stages
+    static constexpr int I2 = (HALF + KQ - 1) / KQ, I4 = (QUARTER + KQ - 1) / KQ; // butterflies per thread and stage
+    static_assert(NC == E * KQ && (NC & (NC - 1)) == 0 && E >= 1 && E <= 16, "line length: 1, 2, 4, 8 or 16 points per thread");
+    struct Tw2 { double2 w[I2]; };
+    struct Tw4 { double2 a[I4], b[I4], c[I4]; };
+
+    // thread (il, kq) holds points kq, kq + KQ, ...: E loads back to back from p (point kq of its column), `stride` elements apart
+    static __device__ __forceinline__ void load(const double2 *p, long stride, double2 (&r)[E]) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) r[e] = p[stride * (e * KQ)];
+    }
+    // every twiddle index below stays under NC / 2 for any q, so the loads of a thread without a butterfly (q past the loop's end) are in bounds
+    // forward = decimation in frequency: [radix-2 at span NC/2,] radix-4 stage s at h = (NC/2 >> ODD) >> 2s, twiddle stride st = (1 << ODD) << 2s
+    static __device__ __forceinline__ void dif_tw2(const double2 *tw, int kq, Tw2 &t) {
+#pragma unroll
+        for (int it = 0; it < I2; ++it) t.w[it] = tw[(kq + it * KQ) & (HALF - 1)];
+    }
+    static __device__ __forceinline__ void dif_stage2(double2 *zbuf, int il, int kq, const Tw2 &t) {
+#pragma unroll
+        for (int it = 0; it < I2; ++it) {
+            const int q = kq + it * KQ;
+            if (HALF % KQ == 0 || q < HALF) {
+                const int jj = q & (HALF - 1), a = ((q - jj) << 1) + jj, b = a + HALF;
+                const double2 xa = zbuf[a * ZL + il], xb = zbuf[b * ZL + il];
+                zbuf[a * ZL + il] = line_add(xa, xb);
+                zbuf[b * ZL + il] = line_cmul(line_sub(xa, xb), t.w[it]);
+            }
+        }
+    }
+    static __device__ __forceinline__ void dif_tw4(const double2 *tw, int kq, int s, Tw4 &t) {
+        const int h = (HALF >> ODD) >> (2 * s), st = (1 << ODD) << (2 * s), h2 = h >> 1;
+#pragma unroll
+        for (int it = 0; it < I4; ++it) {
+            const int jj = (kq + it * KQ) & (h2 - 1);
+            t.a[it] = tw[jj * st];
+            t.b[it] = tw[(jj + h2) * st];
+            t.c[it] = tw[jj * 2 * st];
+        }
+    }
+    // one radix-4 butterfly on x = the points a, a + h/2, a + h, a + 3h/2 (in this order), in place
+    static __device__ __forceinline__ void dif_butterfly4(double2 (&x)[4], double2 wa, double2 wb, double2 wc) {
+        const double2 y0 = line_add(x[0], x[2]), y2 = line_cmul(line_sub(x[0], x[2]), wa);
+        const double2 y1 = line_add(x[1], x[3]), y3 = line_cmul(line_sub(x[1], x[3]), wb);
+        x[0] = line_add(y0, y1);
+        x[1] = line_cmul(line_sub(y0, y1), wc);
+        x[2] = line_add(y2, y3);
+        x[3] = line_cmul(line_sub(y2, y3), wc);
+    }
+    static __device__ __forceinline__ void dif_stage4(double2 *zbuf, int il, int kq, int s, const Tw4 &t) {
+        const int h = (HALF >> ODD) >> (2 * s), h2 = h >> 1;
+#pragma unroll
+        for (int it = 0; it < I4; ++it) {
+            const int q = kq + it * KQ;
+            if (QUARTER % KQ == 0 || q < QUARTER) {
+                const int jj = q & (h2 - 1), a = ((q - jj) << 2) + jj;
+                double2 x[4] = {zbuf[a * ZL + il], zbuf[(a + h2) * ZL + il], zbuf[(a + h) * ZL + il], zbuf[(a + h + h2) * ZL + il]};
+                dif_butterfly4(x, t.a[it], t.b[it], t.c[it]);
+                zbuf[a * ZL + il] = x[0];
+                zbuf[(a + h2) * ZL + il] = x[1];
+                zbuf[(a + h) * ZL + il] = x[2];
+                zbuf[(a + h + h2) * ZL + il] = x[3];
+            }
+        }
+    }
+    // twiddles of the first forward stage(s): call behind the data loads
+    static __device__ __forceinline__ void dif_first_tw(const double2 *tw, int kq, Tw2 &t2, Tw4 &t4) {
+        if (ODD) dif_tw2(tw, kq, t2);
+        dif_tw4(tw, kq, 0, t4);
+    }
+    // the line is in LDS (barrier passed) -> the line after the radix-4 stages [0, S_END) (barrier passed); S_END = NS4: the whole transform,
+    // the line in bit-reversed order. t: the twiddles of stage 0 on entry, those of stage S_END on return (if there is one). `before_last`
+    // runs in front of the LDS reads of the last stage done here: the place for loads the caller needs right after it
+    template <int S_END, class F>
+    static __device__ __forceinline__ void forward_to(double2 *zbuf, const double2 *tw, int il, int kq, const Tw2 &t2, Tw4 &t, F &&before_last) {
+        if (ODD) {
+            dif_stage2(zbuf, il, kq, t2);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int s = 0; s < S_END; ++s) {
+            Tw4 next;
+            if (s + 1 < NS4) dif_tw4(tw, kq, s + 1, next);
+            if (s + 1 == S_END) before_last();
+            dif_stage4(zbuf, il, kq, s, t);
+            __syncthreads();
+            if (s + 1 < NS4) t = next;
+        }
+    }
+    static __device__ __forceinline__ void forward(double2 *zbuf, const double2 *tw, int il, int kq, const Tw2 &t2, Tw4 t) {
+        forward_to<NS4>(zbuf, tw, il, kq, t2, t, [] {});
+    }
+    // inverse = decimation in time, conjugate twiddles: radix-4 stage s at h = 1 << 2s, st = NC/2 >> 2s [, radix-2 at span NC/2, st = 1]
+    static __device__ __forceinline__ void dit_tw4(const double2 *tw, int kq, int s, Tw4 &t) {
+        const int h = 1 << (2 * s), st = HALF >> (2 * s);
+#pragma unroll
+        for (int it = 0; it < I4; ++it) {
+            const int jj = (kq + it * KQ) & (h - 1);
+            t.a[it] = tw[jj * st];
+            t.b[it] = tw[jj * (st >> 1)];
+            t.c[it] = tw[(jj + h) * (st >> 1)];
+        }
+    }
+    // one radix-4 butterfly on x = the points a, a + h, a + 2h, a + 3h (in this order), in place
+    static __device__ __forceinline__ void dit_butterfly4(double2 (&x)[4], double2 wa, double2 wb, double2 wc) {
+        const double2 t1 = line_cmulc(x[1], wa), t3 = line_cmulc(x[3], wa);
+        const double2 y0 = line_add(x[0], t1), y1 = line_sub(x[0], t1);
+        const double2 y2 = line_add(x[2], t3), y3 = line_sub(x[2], t3);
+        const double2 u2 = line_cmulc(y2, wb), u3 = line_cmulc(y3, wc);
+        x[0] = line_add(y0, u2);
+        x[2] = line_sub(y0, u2);
+        x[1] = line_add(y1, u3);
+        x[3] = line_sub(y1, u3);
+    }
+    static __device__ __forceinline__ void dit_stage4(double2 *zbuf, int il, int kq, int s, const Tw4 &t) {
+        const int h = 1 << (2 * s);
+#pragma unroll
+        for (int it = 0; it < I4; ++it) {
+            const int q = kq + it * KQ;
+            if (QUARTER % KQ == 0 || q < QUARTER) {
+                const int jj = q & (h - 1), a = ((q - jj) << 2) + jj;
+                double2 x[4] = {zbuf[a * ZL + il], zbuf[(a + h) * ZL + il], zbuf[(a + 2 * h) * ZL + il], zbuf[(a + 3 * h) * ZL + il]};
+                dit_butterfly4(x, t.a[it], t.b[it], t.c[it]);
+                zbuf[a * ZL + il] = x[0];
+                zbuf[(a + h) * ZL + il] = x[1];
+                zbuf[(a + 2 * h) * ZL + il] = x[2];
+                zbuf[(a + 3 * h) * ZL + il] = x[3];
+            }
+        }
+    }
+    static __device__ __forceinline__ void dit_tw2(const double2 *tw, int kq, Tw2 &t) { dif_tw2(tw, kq, t); }      // h = NC/2, st = 1 again
+    static __device__ __forceinline__ void dit_stage2(double2 *zbuf, int il, int kq, const Tw2 &t) {
+#pragma unroll
+        for (int it = 0; it < I2; ++it) {
+            const int q = kq + it * KQ;
+            if (HALF % KQ == 0 || q < HALF) {
+                const int jj = q & (HALF - 1), a = ((q - jj) << 1) + jj, b = a + HALF;
+                const double2 xa = zbuf[a * ZL + il], u = line_cmulc(zbuf[b * ZL + il], t.w[it]);
+                zbuf[a * ZL + il] = line_add(xa, u);
+                zbuf[b * ZL + il] = line_sub(xa, u);
+            }
+        }
+    }
+    // the line after the radix-4 stages [0, S_BEGIN) is in LDS (barrier passed; S_BEGIN = 0: the bit-reversed line), t = dit_tw4 of stage
+    // S_BEGIN -> the line in natural order (barrier passed)
+    template <int S_BEGIN = 0>
+    static __device__ __forceinline__ void inverse(double2 *zbuf, const double2 *tw, int il, int kq, Tw4 t) {
+        Tw2 t2;
+        if (ODD && S_BEGIN == NS4) dit_tw2(tw, kq, t2);
+#pragma unroll
+        for (int s = S_BEGIN; s < NS4; ++s) {
+            Tw4 next;
+            if (s + 1 < NS4) dit_tw4(tw, kq, s + 1, next);
+            else if (ODD) dit_tw2(tw, kq, t2);
+            dit_stage4(zbuf, il, kq, s, t);
+            __syncthreads();
+            if (s + 1 < NS4) t = next;
+        }
+        if (ODD) {
+            dit_stage2(zbuf, il, kq, t2);
+            __syncthreads();
+        }
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Fused z pass of the FFT-based Poisson solve on the Hermitian half spectrum (Nxs, Ny, Nz), z Periodic, Nz a power of two:
 // forward FFT along z, ϕ̂ = -b̂ / (λx + λy + λz) (fft_based_poisson_solver.jl:108-118), inverse FFT along z -- ONE pass over the
 // array instead of three (rocFFT column transform, divide kernel, rocFFT column transform). A workgroup holds ZL z-lines
@@ -2060,8 +2252,9 @@ __global__ void __launch_bounds__(256) line_scatter_kernel(const double2 *B, dou
 // runs in bit-reversed order, inverse = radix-2 decimation in time (bit-reversed -> natural): in place, no reordering pass.
 // tw[m] = exp(-2πi m / Nz), m < Nz/2 (host-computed). `scale` folds the normalisation of the whole 3-D inverse transform.
 // ---------------------------------------------------------------------------------------------------------------------
-template <int ZL>
-__global__ void __launch_bounds__(256) zline_solve_kernel(double2 *hc, const double2 *tw, const double *lx, const double *ly,
+// NC > 0: Nz = NC at compile time (LineFFT above); NC = 0: any Nz = 2^logn, the generic loops.
+template <int ZL, int NC = 0>
+__global__ void __launch_bounds__(256, line_min_waves(ZL, NC)) zline_solve_kernel(double2 *hc, const double2 *tw, const double *lx, const double *ly,
                                                           const double *lz, int Nxs, int Ny, int Nz, int logn, double scale, int pitch = 0) {
     extern __shared__ double2 zbuf[];                 // [Nz][ZL]
     const int il = threadIdx.x % ZL, kq = threadIdx.x / ZL;       // 32 k-rows per pass
@@ -2070,6 +2263,66 @@ __global__ void __launch_bounds__(256) zline_solve_kernel(double2 *hc, const dou
     const bool live = i < Nxs;
     const int ldx = pitch > 0 ? pitch : Nxs;          // row pitch of the spectrum (>= Nxs: padded to whole 128-B rows on the split path)
     const long plane = (long)ldx * Ny, base = (long)i + (long)ldx * j;
+    if constexpr (NC > 0) {
+        using LF = LineFFT<ZL, NC>;
+        constexpr int KQ = LF::KQ, E = LF::E, LOGN = LF::LOGN;
+        double2 r[E];
+        LF::load(hc + ((long)(live ? i : i0) + (long)ldx * j) + plane * kq, plane, r);
+        typename LF::Tw2 t2;
+        typename LF::Tw4 t4;
+        LF::dif_first_tw(tw, kq, t2, t4);
+#pragma unroll
+        for (int e = 0; e < E; ++e) zbuf[(kq + e * KQ) * ZL + il] = live ? r[e] : make_double2(0.0, 0.0);
+        __syncthreads();
+        // The last forward stage (span 2), the divide and the first inverse stage (span 1) of a thread work on the same four consecutive
+        // points 4q .. 4q + 3: they stay in registers in between -- two LDS round trips and two barriers fewer than stage by stage, the
+        // same operations on the same values. The eigenvalues of the divide and the twiddles of the two inverse stages that follow are
+        // on their way while the forward stage before runs.
+        static_assert(LF::NS4 >= 2, "the fused middle stages need two radix-4 stages");
+        constexpr int I4 = LF::I4, QUARTER = LF::QUARTER;
+        double lam[I4][4], lxy = 0.0;
+        typename LF::Tw4 ti0, ti1;
+        LF::template forward_to<LF::NS4 - 1>(zbuf, tw, il, kq, t2, t4, [&] {
+            lxy = lx[live ? i : i0] + ly[j];
+#pragma unroll
+            for (int it = 0; it < I4; ++it)
+#pragma unroll
+                for (int m = 0; m < 4; ++m) lam[it][m] = lz[(int)(__brev((unsigned)(4 * (kq + it * KQ) + m) & (unsigned)(NC - 1)) >> (32 - LOGN))];
+            LF::dit_tw4(tw, kq, 0, ti0);
+            LF::dit_tw4(tw, kq, 1, ti1);
+        });
+#pragma unroll
+        for (int it = 0; it < I4; ++it) {
+            const int q = kq + it * KQ;
+            if (QUARTER % KQ == 0 || q < QUARTER) {
+                const int a = q << 2;
+                double2 x[4] = {zbuf[a * ZL + il], zbuf[(a + 1) * ZL + il], zbuf[(a + 2) * ZL + il], zbuf[(a + 3) * ZL + il]};
+                LF::dif_butterfly4(x, t4.a[it], t4.b[it], t4.c[it]);
+                if (live) {
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) {
+                        const int k = (int)(__brev((unsigned)(a + m)) >> (32 - LOGN));
+                        const double l = lxy + lam[it][m] - 0.0;
+                        x[m].x = -(x[m].x * scale) / l;
+                        x[m].y = -(x[m].y * scale) / l;
+                        if (i == 0 && j == 0 && k == 0) x[m] = make_double2(0.0, 0.0);
+                    }
+                }
+                LF::dit_butterfly4(x, ti0.a[it], ti0.b[it], ti0.c[it]);
+#pragma unroll
+                for (int m = 0; m < 4; ++m) zbuf[(a + m) * ZL + il] = x[m];
+            }
+        }
+        __syncthreads();
+        LF::template inverse<1>(zbuf, tw, il, kq, ti1);
+        if (live) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) r[e] = zbuf[(kq + e * KQ) * ZL + il];
+#pragma unroll
+            for (int e = 0; e < E; ++e) hc[base + plane * (kq + e * KQ)] = r[e];
+        }
+        return;
+    }
     for (int k = kq; k < Nz; k += 256 / ZL) zbuf[k * ZL + il] = live ? hc[base + plane * k] : make_double2(0.0, 0.0);
     __syncthreads();
     const int half = Nz >> 1, quarter = Nz >> 2, KQ = 256 / ZL;
@@ -2158,14 +2411,50 @@ __global__ void __launch_bounds__(256) zline_solve_kernel(double2 *hc, const dou
 // whose 64 KB of LDS per 8 lines leave two workgroups per CU -- measured at 512^3: 54.0 -> 51.9 ms/step with 4, 54.1 with 2; at 256^3 8 wins).
 // forward: natural -> radix-4 DIF -> stored through the bit-reversal; inverse: loaded through the bit-reversal -> DIT -> natural,
 // times `scale`. Same arithmetic as rocFFT's to round-off, not bitwise.
-template <int ZL>
-__global__ void __launch_bounds__(256) strided_line_fft_kernel(double2 *data, const double2 *tw, long C, int N, int logn, int inverse,
+// NC > 0: N = NC at compile time (LineFFT above); NC = 0: any N = 2^logn, the generic loops.
+template <int ZL, int NC = 0>
+__global__ void __launch_bounds__(256, line_min_waves(ZL, NC)) strided_line_fft_kernel(double2 *data, const double2 *tw, long C, int N, int logn, int inverse,
                                                                double scale, long plane_stride = 0) {
     extern __shared__ double2 zbuf[];                 // [N][ZL]
     data += plane_stride * blockIdx.y;                // gridDim.y independent (C, N) arrays `plane_stride` elements apart
     const int il = threadIdx.x % ZL, kq = threadIdx.x / ZL;
     const long c = (long)blockIdx.x * ZL + il;
     const bool live = c < C;
+    if constexpr (NC > 0) {
+        using LF = LineFFT<ZL, NC>;
+        constexpr int KQ = LF::KQ, E = LF::E, LOGN = LF::LOGN;
+        double2 r[E];
+        LF::load(data + (live ? c : (long)blockIdx.x * ZL) + C * kq, C, r);
+        typename LF::Tw2 t2;
+        typename LF::Tw4 t4;
+        if (!inverse) {
+            LF::dif_first_tw(tw, kq, t2, t4);
+#pragma unroll
+            for (int e = 0; e < E; ++e) zbuf[(kq + e * KQ) * ZL + il] = live ? r[e] : make_double2(0.0, 0.0);
+            __syncthreads();
+            LF::forward(zbuf, tw, il, kq, t2, t4);
+            if (live) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) r[e] = zbuf[(kq + e * KQ) * ZL + il];
+#pragma unroll
+                for (int e = 0; e < E; ++e) data[c + C * (long)(__brev((unsigned)(kq + e * KQ)) >> (32 - LOGN))] = r[e];
+            }
+        } else {
+            LF::dit_tw4(tw, kq, 0, t4);
+#pragma unroll
+            for (int e = 0; e < E; ++e)
+                zbuf[(int)(__brev((unsigned)(kq + e * KQ)) >> (32 - LOGN)) * ZL + il] = live ? r[e] : make_double2(0.0, 0.0);
+            __syncthreads();
+            LF::template inverse<0>(zbuf, tw, il, kq, t4);
+            if (live) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) r[e] = zbuf[(kq + e * KQ) * ZL + il];
+#pragma unroll
+                for (int e = 0; e < E; ++e) data[c + C * (kq + e * KQ)] = make_double2(r[e].x * scale, r[e].y * scale);
+            }
+        }
+        return;
+    }
     const int half = N >> 1, quarter = N >> 2, KQ = 256 / ZL;
 #define ZB(n) zbuf[(n) * ZL + il]
 #define CMUL(ar, ai, w) make_double2((ar) * (w).x - (ai) * (w).y, (ar) * (w).y + (ai) * (w).x)

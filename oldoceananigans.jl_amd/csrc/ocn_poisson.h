@@ -15,13 +15,32 @@ static inline void with_line_count(int lines, F &&launch) {
     if (lines == 4) launch(std::integral_constant<int, 4>{});
     else            launch(std::integral_constant<int, 8>{});
 }
+// ... and for these line lengths at compile time (1, 2, 4, 8 or 16 points per thread: all of a thread's loads in flight at once, see LineFFT);
+// every other length -- fewer points than the 256 / lines k-rows of a pass -- takes the generic loops: `launch` receives (lines, length or 0)
+template <class F>
+static inline void with_line_shape(int lines, int n, F &&launch) {
+    using std::integral_constant;
+#if OCN_LINE_IN_FLIGHT
+    if (lines == 4) {
+        if (n == 512)  return launch(integral_constant<int, 4>{}, integral_constant<int, 512>{});
+        if (n == 1024) return launch(integral_constant<int, 4>{}, integral_constant<int, 1024>{});
+    } else {
+        if (n == 32)  return launch(integral_constant<int, 8>{}, integral_constant<int, 32>{});
+        if (n == 64)  return launch(integral_constant<int, 8>{}, integral_constant<int, 64>{});
+        if (n == 128) return launch(integral_constant<int, 8>{}, integral_constant<int, 128>{});
+        if (n == 256) return launch(integral_constant<int, 8>{}, integral_constant<int, 256>{});
+        if (n == 512) return launch(integral_constant<int, 8>{}, integral_constant<int, 512>{});
+    }
+#endif
+    with_line_count(lines, [&](auto ZL) { launch(ZL, integral_constant<int, 0>{}); });
+}
 static inline void launch_strided_line_fft(const OcnOptions &o, double2 *data, const double2 *tw, long C, long ncols, unsigned batches, int N, int logn, int inverse,
                                            double scale, long plane_stride = 0) {
     const int zl = line_zl(o, N);
     const dim3 grd((unsigned)((ncols + zl - 1) / zl), batches);
     const size_t lds = (size_t)N * zl * sizeof(double2);
-    with_line_count(zl, [&](auto ZL) {
-        hipLaunchKernelGGL(strided_line_fft_kernel<decltype(ZL)::value>, grd, dim3(256), lds, g_stream, data, tw, C, N, logn, inverse, scale, plane_stride);
+    with_line_shape(zl, N, [&](auto ZL, auto NC) {
+        hipLaunchKernelGGL((strided_line_fft_kernel<decltype(ZL)::value, decltype(NC)::value>), grd, dim3(256), lds, g_stream, data, tw, C, N, logn, inverse, scale, plane_stride);
     });
 }
 static inline void launch_paired_zline(const OcnOptions &o, bool forward, const double2 *in, double2 *out, const double2 *tw, long C, int N, int logn, double scale) {
@@ -62,8 +81,8 @@ static inline void launch_zline_solve(const OcnOptions &o, double2 *hc, const do
     const int zl = line_zl(o, Nz);
     const dim3 grd((unsigned)((Nxs + zl - 1) / zl), (unsigned)Ny);
     const size_t lds = (size_t)Nz * zl * sizeof(double2);
-    with_line_count(zl, [&](auto ZL) {
-        hipLaunchKernelGGL(zline_solve_kernel<decltype(ZL)::value>, grd, dim3(256), lds, g_stream, hc, tw, lx, ly, lz, Nxs, Ny, Nz, logn, scale, pitch);
+    with_line_shape(zl, Nz, [&](auto ZL, auto NC) {
+        hipLaunchKernelGGL((zline_solve_kernel<decltype(ZL)::value, decltype(NC)::value>), grd, dim3(256), lds, g_stream, hc, tw, lx, ly, lz, Nxs, Ny, Nz, logn, scale, pitch);
     });
 }
 
