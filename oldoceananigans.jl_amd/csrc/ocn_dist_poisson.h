@@ -84,7 +84,7 @@ struct ocn_dist_poisson_s {
     double *D = nullptr, *lower = nullptr, *t = nullptr;
     hipfftHandle plan_loc = 0, plan_x = 0;
     bool has_loc = false, has_x = false;
-    // zmode 0, Nxg = 2^m <= 4096: the x stage (unpack, FFT, divide, inverse FFT, pack) is one LDS pass (xline_solve_kernel)
+    // zmode 0, Nxg = 2^m <= 4096: the x stage (unpack, FFT, divide, inverse FFT, pack) is one LDS pass (xline_solve_kernel, ocn_line_fft.h)
     bool xfused = false;
     int logn_x = 0, xlines = 1;
     double2 *xtw = nullptr;
@@ -102,7 +102,7 @@ struct ocn_dist_poisson_s {
     double2 *spec = nullptr;    // (Nzp, Nxl, Ny) complex, modes m = kz + Nzh*ky at [kz + Nzp*(i + Nxl*ky)]
     hipfftHandle plan_zr2c = 0, plan_zc2r = 0;       // 2-D (y, z) D2Z / Z2D, batched over the local x index (zf_2d) ...
     hipfftHandle plan_y = 0;                         // ... or 1-D along z plus this strided 1-D y transform
-    // z Bounded, Ny = 2^m <= 1024: the local y transform by strided_line_fft_kernel instead of rocFFT's 1-D strided plan
+    // z Bounded, Ny = 2^m <= 1024: the local y transform by strided_line_fft_kernel (ocn_line_fft.h) instead of rocFFT's 1-D strided plan
     bool yline = false;
     int logn_y = 0;
     double2 *ytw = nullptr;
@@ -196,7 +196,7 @@ static int dist_verify_local_plan(ocn_dist_poisson_s *s) {
     return OCN_OK;
 }
 
-// ---- x-fastest layout (ocn_kernels.h "xfast") ----
+// ---- x-fastest layout (ocn_kernels.h "xfast"; its paired z transforms: ocn_line_fft.h) ----
 static int setup_xfast(ocn_dist_poisson_s *s) {
     const DGrid &g = s->grid->d;
     s->sub = true; s->xfast = true;

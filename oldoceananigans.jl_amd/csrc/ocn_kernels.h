@@ -2,6 +2,7 @@
 #pragma once
 #include "ocn_device.h"
 #include "ocn_immersed.h"
+#include "ocn_line_fft.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // advective fluxes (src/Advection/upwind_biased_advective_fluxes.jl:23-121), evaluated straight from global memory.
@@ -2053,592 +2054,6 @@ __global__ void __launch_bounds__(256) line_scatter_kernel(const double2 *B, dou
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The LDS line kernels below (zline_solve_kernel, strided_line_fft_kernel) at a line length known when they are compiled: NC points,
-// E = NC / KQ = 1, 2, 4, 8 or 16 of them per thread (KQ = 256 / ZL k-rows per pass). The generic loops have run-time trip counts, and the
-// compiler serialises them: one global_load_dwordx4, s_waitcnt vmcnt(0), one ds_write_b128 per iteration -- E HBM round trips one after
-// the other with 16 B per lane in flight --, and every butterfly waits for its own twiddle loads. Here
-//  * a thread issues ALL E loads of its part of the line back to back, and only then writes them to LDS; a lane past the last column
-//    loads its workgroup's first column instead (a clamped address, no branch between the loads) and stores zeros;
-//  * the twiddles of a butterfly stage are in registers before the stage starts: those of the first stage are loaded behind the data
-//    loads, those of every later stage in front of the LDS reads of the stage before it (LDS stays at NC x ZL x 16 B: the same
-//    workgroups per CU, and 1024 x 4 lines already take the 64 KB a workgroup may ask for).
-// Same values, same operations in the same order as the generic loops (the build has -ffp-contract=off): bit-identical results.
-// OCN_LINE_IN_FLIGHT=0 sends every line length back to the generic loops -- for A/B timing only (tools/ab_build.sh).
-// ---------------------------------------------------------------------------------------------------------------------
-#ifndef OCN_LINE_IN_FLIGHT
-#define OCN_LINE_IN_FLIGHT 1
-#endif
-constexpr int line_ilog2(int n) { return n <= 1 ? 0 : 1 + line_ilog2(n >> 1); }
-// waves per SIMD the fixed-length kernels must leave room for: a 32 KB line buffer fits five times into a CU's 160 KB of LDS, and five
-// workgroups of four waves are five waves per SIMD (<= 96 VGPRs); every other shape is left to the compiler
-constexpr int line_min_waves(int zl, int nc) { return nc * zl * (int)sizeof(double2) == 32768 ? 5 : 1; }
-__device__ __forceinline__ double2 line_add(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 line_sub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 line_cmul(double2 v, double2 w) { return make_double2(v.x * w.x - v.y * w.y, v.x * w.y + v.y * w.x); }     // v * w
-__device__ __forceinline__ double2 line_cmulc(double2 v, double2 w) { return make_double2(v.x * w.x + v.y * w.y, v.y * w.x - v.x * w.y); }    // v * conj(w)
-
-template <int ZL, int NC>
-struct LineFFT {
-    static constexpr int KQ = 256 / ZL, E = NC / KQ, HALF = NC >> 1, QUARTER = NC >> 2, LOGN = line_ilog2(NC);
-    static constexpr int ODD = LOGN & 1, NS4 = LOGN >> 1;                         // one radix-2 stage when log2 NC is odd, NS4 radix-4 stages
-    static constexpr int I2 = (HALF + KQ - 1) / KQ, I4 = (QUARTER + KQ - 1) / KQ; // butterflies per thread and stage
-    static_assert(NC == E * KQ && (NC & (NC - 1)) == 0 && E >= 1 && E <= 16, "line length: 1, 2, 4, 8 or 16 points per thread");
-    struct Tw2 { double2 w[I2]; };
-    struct Tw4 { double2 a[I4], b[I4], c[I4]; };
-
-    // thread (il, kq) holds points kq, kq + KQ, ...: E loads back to back from p (point kq of its column), `stride` elements apart
-    static __device__ __forceinline__ void load(const double2 *p, long stride, double2 (&r)[E]) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) r[e] = p[stride * (e * KQ)];
-    }
-    // every twiddle index below stays under NC / 2 for any q, so the loads of a thread without a butterfly (q past the loop's end) are in bounds
-    // forward = decimation in frequency: [radix-2 at span NC/2,] radix-4 stage s at h = (NC/2 >> ODD) >> 2s, twiddle stride st = (1 << ODD) << 2s
-    static __device__ __forceinline__ void dif_tw2(const double2 *tw, int kq, Tw2 &t) {
-#pragma unroll
-        for (int it = 0; it < I2; ++it) t.w[it] = tw[(kq + it * KQ) & (HALF - 1)];
-    }
-    static __device__ __forceinline__ void dif_stage2(double2 *zbuf, int il, int kq, const Tw2 &t) {
-#pragma unroll
-        for (int it = 0; it < I2; ++it) {
-            const int q = kq + it * KQ;
-            if (HALF % KQ == 0 || q < HALF) {
-                const int jj = q & (HALF - 1), a = ((q - jj) << 1) + jj, b = a + HALF;
-                const double2 xa = zbuf[a * ZL + il], xb = zbuf[b * ZL + il];
-                zbuf[a * ZL + il] = line_add(xa, xb);
-                zbuf[b * ZL + il] = line_cmul(line_sub(xa, xb), t.w[it]);
-            }
-        }
-    }
-    static __device__ __forceinline__ void dif_tw4(const double2 *tw, int kq, int s, Tw4 &t) {
-        const int h = (HALF >> ODD) >> (2 * s), st = (1 << ODD) << (2 * s), h2 = h >> 1;
-#pragma unroll
-        for (int it = 0; it < I4; ++it) {
-            const int jj = (kq + it * KQ) & (h2 - 1);
-            t.a[it] = tw[jj * st];
-            t.b[it] = tw[(jj + h2) * st];
-            t.c[it] = tw[jj * 2 * st];
-        }
-    }
-    // one radix-4 butterfly on x = the points a, a + h/2, a + h, a + 3h/2 (in this order), in place
-    static __device__ __forceinline__ void dif_butterfly4(double2 (&x)[4], double2 wa, double2 wb, double2 wc) {
-        const double2 y0 = line_add(x[0], x[2]), y2 = line_cmul(line_sub(x[0], x[2]), wa);
-        const double2 y1 = line_add(x[1], x[3]), y3 = line_cmul(line_sub(x[1], x[3]), wb);
-        x[0] = line_add(y0, y1);
-        x[1] = line_cmul(line_sub(y0, y1), wc);
-        x[2] = line_add(y2, y3);
-        x[3] = line_cmul(line_sub(y2, y3), wc);
-    }
-    static __device__ __forceinline__ void dif_stage4(double2 *zbuf, int il, int kq, int s, const Tw4 &t) {
-        const int h = (HALF >> ODD) >> (2 * s), h2 = h >> 1;
-#pragma unroll
-        for (int it = 0; it < I4; ++it) {
-            const int q = kq + it * KQ;
-            if (QUARTER % KQ == 0 || q < QUARTER) {
-                const int jj = q & (h2 - 1), a = ((q - jj) << 2) + jj;
-                double2 x[4] = {zbuf[a * ZL + il], zbuf[(a + h2) * ZL + il], zbuf[(a + h) * ZL + il], zbuf[(a + h + h2) * ZL + il]};
-                dif_butterfly4(x, t.a[it], t.b[it], t.c[it]);
-                zbuf[a * ZL + il] = x[0];
-                zbuf[(a + h2) * ZL + il] = x[1];
-                zbuf[(a + h) * ZL + il] = x[2];
-                zbuf[(a + h + h2) * ZL + il] = x[3];
-            }
-        }
-    }
-    // twiddles of the first forward stage(s): call behind the data loads
-    static __device__ __forceinline__ void dif_first_tw(const double2 *tw, int kq, Tw2 &t2, Tw4 &t4) {
-        if (ODD) dif_tw2(tw, kq, t2);
-        dif_tw4(tw, kq, 0, t4);
-    }
-    // the line is in LDS (barrier passed) -> the line after the radix-4 stages [0, S_END) (barrier passed); S_END = NS4: the whole transform,
-    // the line in bit-reversed order. t: the twiddles of stage 0 on entry, those of stage S_END on return (if there is one). `before_last`
-    // runs in front of the LDS reads of the last stage done here: the place for loads the caller needs right after it
-    template <int S_END, class F>
-    static __device__ __forceinline__ void forward_to(double2 *zbuf, const double2 *tw, int il, int kq, const Tw2 &t2, Tw4 &t, F &&before_last) {
-        if (ODD) {
-            dif_stage2(zbuf, il, kq, t2);
-            __syncthreads();
-        }
-#pragma unroll
-        for (int s = 0; s < S_END; ++s) {
-            Tw4 next;
-            if (s + 1 < NS4) dif_tw4(tw, kq, s + 1, next);
-            if (s + 1 == S_END) before_last();
-            dif_stage4(zbuf, il, kq, s, t);
-            __syncthreads();
-            if (s + 1 < NS4) t = next;
-        }
-    }
-    static __device__ __forceinline__ void forward(double2 *zbuf, const double2 *tw, int il, int kq, const Tw2 &t2, Tw4 t) {
-        forward_to<NS4>(zbuf, tw, il, kq, t2, t, [] {});
-    }
-    // inverse = decimation in time, conjugate twiddles: radix-4 stage s at h = 1 << 2s, st = NC/2 >> 2s [, radix-2 at span NC/2, st = 1]
-    static __device__ __forceinline__ void dit_tw4(const double2 *tw, int kq, int s, Tw4 &t) {
-        const int h = 1 << (2 * s), st = HALF >> (2 * s);
-#pragma unroll
-        for (int it = 0; it < I4; ++it) {
-            const int jj = (kq + it * KQ) & (h - 1);
-            t.a[it] = tw[jj * st];
-            t.b[it] = tw[jj * (st >> 1)];
-            t.c[it] = tw[(jj + h) * (st >> 1)];
-        }
-    }
-    // one radix-4 butterfly on x = the points a, a + h, a + 2h, a + 3h (in this order), in place
-    static __device__ __forceinline__ void dit_butterfly4(double2 (&x)[4], double2 wa, double2 wb, double2 wc) {
-        const double2 t1 = line_cmulc(x[1], wa), t3 = line_cmulc(x[3], wa);
-        const double2 y0 = line_add(x[0], t1), y1 = line_sub(x[0], t1);
-        const double2 y2 = line_add(x[2], t3), y3 = line_sub(x[2], t3);
-        const double2 u2 = line_cmulc(y2, wb), u3 = line_cmulc(y3, wc);
-        x[0] = line_add(y0, u2);
-        x[2] = line_sub(y0, u2);
-        x[1] = line_add(y1, u3);
-        x[3] = line_sub(y1, u3);
-    }
-    static __device__ __forceinline__ void dit_stage4(double2 *zbuf, int il, int kq, int s, const Tw4 &t) {
-        const int h = 1 << (2 * s);
-#pragma unroll
-        for (int it = 0; it < I4; ++it) {
-            const int q = kq + it * KQ;
-            if (QUARTER % KQ == 0 || q < QUARTER) {
-                const int jj = q & (h - 1), a = ((q - jj) << 2) + jj;
-                double2 x[4] = {zbuf[a * ZL + il], zbuf[(a + h) * ZL + il], zbuf[(a + 2 * h) * ZL + il], zbuf[(a + 3 * h) * ZL + il]};
-                dit_butterfly4(x, t.a[it], t.b[it], t.c[it]);
-                zbuf[a * ZL + il] = x[0];
-                zbuf[(a + h) * ZL + il] = x[1];
-                zbuf[(a + 2 * h) * ZL + il] = x[2];
-                zbuf[(a + 3 * h) * ZL + il] = x[3];
-            }
-        }
-    }
-    static __device__ __forceinline__ void dit_tw2(const double2 *tw, int kq, Tw2 &t) { dif_tw2(tw, kq, t); }      // h = NC/2, st = 1 again
-    static __device__ __forceinline__ void dit_stage2(double2 *zbuf, int il, int kq, const Tw2 &t) {
-#pragma unroll
-        for (int it = 0; it < I2; ++it) {
-            const int q = kq + it * KQ;
-            if (HALF % KQ == 0 || q < HALF) {
-                const int jj = q & (HALF - 1), a = ((q - jj) << 1) + jj, b = a + HALF;
-                const double2 xa = zbuf[a * ZL + il], u = line_cmulc(zbuf[b * ZL + il], t.w[it]);
-                zbuf[a * ZL + il] = line_add(xa, u);
-                zbuf[b * ZL + il] = line_sub(xa, u);
-            }
-        }
-    }
-    // the line after the radix-4 stages [0, S_BEGIN) is in LDS (barrier passed; S_BEGIN = 0: the bit-reversed line), t = dit_tw4 of stage
-    // S_BEGIN -> the line in natural order (barrier passed)
-    template <int S_BEGIN = 0>
-    static __device__ __forceinline__ void inverse(double2 *zbuf, const double2 *tw, int il, int kq, Tw4 t) {
-        Tw2 t2;
-        if (ODD && S_BEGIN == NS4) dit_tw2(tw, kq, t2);
-#pragma unroll
-        for (int s = S_BEGIN; s < NS4; ++s) {
-            Tw4 next;
-            if (s + 1 < NS4) dit_tw4(tw, kq, s + 1, next);
-            else if (ODD) dit_tw2(tw, kq, t2);
-            dit_stage4(zbuf, il, kq, s, t);
-            __syncthreads();
-            if (s + 1 < NS4) t = next;
-        }
-        if (ODD) {
-            dit_stage2(zbuf, il, kq, t2);
-            __syncthreads();
-        }
-    }
-};
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Fused z pass of the FFT-based Poisson solve on the Hermitian half spectrum (Nxs, Ny, Nz), z Periodic, Nz a power of two:
-// forward FFT along z, ϕ̂ = -b̂ / (λx + λy + λz) (fft_based_poisson_solver.jl:108-118), inverse FFT along z -- ONE pass over the
-// array instead of three (rocFFT column transform, divide kernel, rocFFT column transform). A workgroup holds ZL z-lines
-// (consecutive in x: 128-B rows) in LDS. Forward = radix-2 decimation in frequency (natural -> bit-reversed order), the divide
-// runs in bit-reversed order, inverse = radix-2 decimation in time (bit-reversed -> natural): in place, no reordering pass.
-// tw[m] = exp(-2πi m / Nz), m < Nz/2 (host-computed). `scale` folds the normalisation of the whole 3-D inverse transform.
-// ---------------------------------------------------------------------------------------------------------------------
-// NC > 0: Nz = NC at compile time (LineFFT above); NC = 0: any Nz = 2^logn, the generic loops.
-template <int ZL, int NC = 0>
-__global__ void __launch_bounds__(256, line_min_waves(ZL, NC)) zline_solve_kernel(double2 *hc, const double2 *tw, const double *lx, const double *ly,
-                                                          const double *lz, int Nxs, int Ny, int Nz, int logn, double scale, int pitch = 0) {
-    extern __shared__ double2 zbuf[];                 // [Nz][ZL]
-    const int il = threadIdx.x % ZL, kq = threadIdx.x / ZL;       // 32 k-rows per pass
-    const int i0 = blockIdx.x * ZL, j = blockIdx.y;
-    const int i = i0 + il;
-    const bool live = i < Nxs;
-    const int ldx = pitch > 0 ? pitch : Nxs;          // row pitch of the spectrum (>= Nxs: padded to whole 128-B rows on the split path)
-    const long plane = (long)ldx * Ny, base = (long)i + (long)ldx * j;
-    if constexpr (NC > 0) {
-        using LF = LineFFT<ZL, NC>;
-        constexpr int KQ = LF::KQ, E = LF::E, LOGN = LF::LOGN;
-        double2 r[E];
-        LF::load(hc + ((long)(live ? i : i0) + (long)ldx * j) + plane * kq, plane, r);
-        typename LF::Tw2 t2;
-        typename LF::Tw4 t4;
-        LF::dif_first_tw(tw, kq, t2, t4);
-#pragma unroll
-        for (int e = 0; e < E; ++e) zbuf[(kq + e * KQ) * ZL + il] = live ? r[e] : make_double2(0.0, 0.0);
-        __syncthreads();
-        // The last forward stage (span 2), the divide and the first inverse stage (span 1) of a thread work on the same four consecutive
-        // points 4q .. 4q + 3: they stay in registers in between -- two LDS round trips and two barriers fewer than stage by stage, the
-        // same operations on the same values. The eigenvalues of the divide and the twiddles of the two inverse stages that follow are
-        // on their way while the forward stage before runs.
-        static_assert(LF::NS4 >= 2, "the fused middle stages need two radix-4 stages");
-        constexpr int I4 = LF::I4, QUARTER = LF::QUARTER;
-        double lam[I4][4], lxy = 0.0;
-        typename LF::Tw4 ti0, ti1;
-        LF::template forward_to<LF::NS4 - 1>(zbuf, tw, il, kq, t2, t4, [&] {
-            lxy = lx[live ? i : i0] + ly[j];
-#pragma unroll
-            for (int it = 0; it < I4; ++it)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) lam[it][m] = lz[(int)(__brev((unsigned)(4 * (kq + it * KQ) + m) & (unsigned)(NC - 1)) >> (32 - LOGN))];
-            LF::dit_tw4(tw, kq, 0, ti0);
-            LF::dit_tw4(tw, kq, 1, ti1);
-        });
-#pragma unroll
-        for (int it = 0; it < I4; ++it) {
-            const int q = kq + it * KQ;
-            if (QUARTER % KQ == 0 || q < QUARTER) {
-                const int a = q << 2;
-                double2 x[4] = {zbuf[a * ZL + il], zbuf[(a + 1) * ZL + il], zbuf[(a + 2) * ZL + il], zbuf[(a + 3) * ZL + il]};
-                LF::dif_butterfly4(x, t4.a[it], t4.b[it], t4.c[it]);
-                if (live) {
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        const int k = (int)(__brev((unsigned)(a + m)) >> (32 - LOGN));
-                        const double l = lxy + lam[it][m] - 0.0;
-                        x[m].x = -(x[m].x * scale) / l;
-                        x[m].y = -(x[m].y * scale) / l;
-                        if (i == 0 && j == 0 && k == 0) x[m] = make_double2(0.0, 0.0);
-                    }
-                }
-                LF::dit_butterfly4(x, ti0.a[it], ti0.b[it], ti0.c[it]);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) zbuf[(a + m) * ZL + il] = x[m];
-            }
-        }
-        __syncthreads();
-        LF::template inverse<1>(zbuf, tw, il, kq, ti1);
-        if (live) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) r[e] = zbuf[(kq + e * KQ) * ZL + il];
-#pragma unroll
-            for (int e = 0; e < E; ++e) hc[base + plane * (kq + e * KQ)] = r[e];
-        }
-        return;
-    }
-    for (int k = kq; k < Nz; k += 256 / ZL) zbuf[k * ZL + il] = live ? hc[base + plane * k] : make_double2(0.0, 0.0);
-    __syncthreads();
-    const int half = Nz >> 1, quarter = Nz >> 2, KQ = 256 / ZL;
-#define ZB(n) zbuf[(n) * ZL + il]
-#define CMUL(ar, ai, w) make_double2((ar) * (w).x - (ai) * (w).y, (ar) * (w).y + (ai) * (w).x)        /* (ar + i ai) * w       */
-#define CMULC(v, w) make_double2((v).x * (w).x + (v).y * (w).y, (v).y * (w).x - (v).x * (w).y)       /* v * conj(w)           */
-    // forward, decimation in frequency (natural -> bit-reversed): spans Nz/2, Nz/4, ..., 1; two radix-2 stages are fused in
-    // registers (radix-4 butterflies: half the LDS traffic and barriers), preceded by one radix-2 stage when log2 Nz is odd
-    int h = half, st = 1;
-    if (logn & 1) {
-        for (int q = kq; q < half; q += KQ) {
-            const int jj = q & (h - 1), a = ((q - jj) << 1) + jj, b = a + h;
-            const double2 xa = ZB(a), xb = ZB(b), w = tw[jj * st];
-            ZB(a) = make_double2(xa.x + xb.x, xa.y + xb.y);
-            ZB(b) = CMUL(xa.x - xb.x, xa.y - xb.y, w);
-        }
-        __syncthreads();
-        h >>= 1; st <<= 1;
-    }
-    for (; h >= 2; h >>= 2, st <<= 2) {
-        const int h2 = h >> 1;
-        for (int q = kq; q < quarter; q += KQ) {
-            const int jj = q & (h2 - 1), a = ((q - jj) << 2) + jj;             // blocks of 2h elements, jj < h/2
-            const double2 x0 = ZB(a), x1 = ZB(a + h2), x2 = ZB(a + h), x3 = ZB(a + h + h2);
-            const double2 wa = tw[jj * st], wb = tw[(jj + h2) * st], wc = tw[jj * 2 * st];
-            const double2 y0 = make_double2(x0.x + x2.x, x0.y + x2.y), y2 = CMUL(x0.x - x2.x, x0.y - x2.y, wa);
-            const double2 y1 = make_double2(x1.x + x3.x, x1.y + x3.y), y3 = CMUL(x1.x - x3.x, x1.y - x3.y, wb);
-            ZB(a) = make_double2(y0.x + y1.x, y0.y + y1.y);
-            ZB(a + h2) = CMUL(y0.x - y1.x, y0.y - y1.y, wc);
-            ZB(a + h) = make_double2(y2.x + y3.x, y2.y + y3.y);
-            ZB(a + h + h2) = CMUL(y2.x - y3.x, y2.y - y3.y, wc);
-        }
-        __syncthreads();
-    }
-    // spectral divide in bit-reversed order
-    if (live) {
-        const double lxy = lx[i] + ly[j];
-        for (int p = kq; p < Nz; p += KQ) {
-            const int k = (int)(__brev((unsigned)p) >> (32 - logn));
-            double2 v = ZB(p);
-            const double lam = lxy + lz[k] - 0.0;
-            v.x = -(v.x * scale) / lam;
-            v.y = -(v.y * scale) / lam;
-            if (i == 0 && j == 0 && k == 0) v = make_double2(0.0, 0.0);
-            ZB(p) = v;
-        }
-    }
-    __syncthreads();
-    // inverse, decimation in time (bit-reversed -> natural): spans 1, 2, ..., Nz/2, conjugate twiddles, fused in pairs
-    h = 1; st = half;
-    for (; (h << 1) <= half; h <<= 2, st >>= 2) {
-        for (int q = kq; q < quarter; q += KQ) {
-            const int jj = q & (h - 1), a = ((q - jj) << 2) + jj;              // blocks of 4h elements, jj < h
-            const double2 x0 = ZB(a), x1 = ZB(a + h), x2 = ZB(a + 2 * h), x3 = ZB(a + 3 * h);
-            const double2 wa = tw[jj * st], wb = tw[jj * (st >> 1)], wc = tw[(jj + h) * (st >> 1)];
-            const double2 t1 = CMULC(x1, wa), t3 = CMULC(x3, wa);
-            const double2 y0 = make_double2(x0.x + t1.x, x0.y + t1.y), y1 = make_double2(x0.x - t1.x, x0.y - t1.y);
-            const double2 y2 = make_double2(x2.x + t3.x, x2.y + t3.y), y3 = make_double2(x2.x - t3.x, x2.y - t3.y);
-            const double2 u2 = CMULC(y2, wb), u3 = CMULC(y3, wc);
-            ZB(a) = make_double2(y0.x + u2.x, y0.y + u2.y);
-            ZB(a + 2 * h) = make_double2(y0.x - u2.x, y0.y - u2.y);
-            ZB(a + h) = make_double2(y1.x + u3.x, y1.y + u3.y);
-            ZB(a + 3 * h) = make_double2(y1.x - u3.x, y1.y - u3.y);
-        }
-        __syncthreads();
-    }
-    if (h <= half) {                          // one radix-2 stage left when log2 Nz is odd (h == half here)
-        for (int q = kq; q < half; q += KQ) {
-            const int jj = q & (h - 1), a = ((q - jj) << 1) + jj, b = a + h;
-            const double2 xa = ZB(a), t = CMULC(ZB(b), tw[jj * st]);
-            ZB(a) = make_double2(xa.x + t.x, xa.y + t.y);
-            ZB(b) = make_double2(xa.x - t.x, xa.y - t.y);
-        }
-        __syncthreads();
-    }
-#undef ZB
-#undef CMUL
-#undef CMULC
-    if (live)
-        for (int k = kq; k < Nz; k += 256 / ZL) hc[base + plane * k] = zbuf[k * ZL + il];
-}
-
-// One-directional FFT of length N = 2^logn along the SLOWEST dimension of a (C, N) complex array (element (c, n) at c + C*n): the
-// column transform rocFFT runs with its row kernel when it is planned as a 1-D strided transform (measured 129 us for 67 MB; this
-// kernel: the same LDS machinery as zline_solve_kernel, ZL consecutive lines per workgroup: 8 = 128-B rows; 4 for lines of 512 and more,
-// whose 64 KB of LDS per 8 lines leave two workgroups per CU -- measured at 512^3: 54.0 -> 51.9 ms/step with 4, 54.1 with 2; at 256^3 8 wins).
-// forward: natural -> radix-4 DIF -> stored through the bit-reversal; inverse: loaded through the bit-reversal -> DIT -> natural,
-// times `scale`. Same arithmetic as rocFFT's to round-off, not bitwise.
-// NC > 0: N = NC at compile time (LineFFT above); NC = 0: any N = 2^logn, the generic loops.
-template <int ZL, int NC = 0>
-__global__ void __launch_bounds__(256, line_min_waves(ZL, NC)) strided_line_fft_kernel(double2 *data, const double2 *tw, long C, int N, int logn, int inverse,
-                                                               double scale, long plane_stride = 0) {
-    extern __shared__ double2 zbuf[];                 // [N][ZL]
-    data += plane_stride * blockIdx.y;                // gridDim.y independent (C, N) arrays `plane_stride` elements apart
-    const int il = threadIdx.x % ZL, kq = threadIdx.x / ZL;
-    const long c = (long)blockIdx.x * ZL + il;
-    const bool live = c < C;
-    if constexpr (NC > 0) {
-        using LF = LineFFT<ZL, NC>;
-        constexpr int KQ = LF::KQ, E = LF::E, LOGN = LF::LOGN;
-        double2 r[E];
-        LF::load(data + (live ? c : (long)blockIdx.x * ZL) + C * kq, C, r);
-        typename LF::Tw2 t2;
-        typename LF::Tw4 t4;
-        if (!inverse) {
-            LF::dif_first_tw(tw, kq, t2, t4);
-#pragma unroll
-            for (int e = 0; e < E; ++e) zbuf[(kq + e * KQ) * ZL + il] = live ? r[e] : make_double2(0.0, 0.0);
-            __syncthreads();
-            LF::forward(zbuf, tw, il, kq, t2, t4);
-            if (live) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) r[e] = zbuf[(kq + e * KQ) * ZL + il];
-#pragma unroll
-                for (int e = 0; e < E; ++e) data[c + C * (long)(__brev((unsigned)(kq + e * KQ)) >> (32 - LOGN))] = r[e];
-            }
-        } else {
-            LF::dit_tw4(tw, kq, 0, t4);
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-                zbuf[(int)(__brev((unsigned)(kq + e * KQ)) >> (32 - LOGN)) * ZL + il] = live ? r[e] : make_double2(0.0, 0.0);
-            __syncthreads();
-            LF::template inverse<0>(zbuf, tw, il, kq, t4);
-            if (live) {
-#pragma unroll
-                for (int e = 0; e < E; ++e) r[e] = zbuf[(kq + e * KQ) * ZL + il];
-#pragma unroll
-                for (int e = 0; e < E; ++e) data[c + C * (kq + e * KQ)] = make_double2(r[e].x * scale, r[e].y * scale);
-            }
-        }
-        return;
-    }
-    const int half = N >> 1, quarter = N >> 2, KQ = 256 / ZL;
-#define ZB(n) zbuf[(n) * ZL + il]
-#define CMUL(ar, ai, w) make_double2((ar) * (w).x - (ai) * (w).y, (ar) * (w).y + (ai) * (w).x)
-#define CMULC(v, w) make_double2((v).x * (w).x + (v).y * (w).y, (v).y * (w).x - (v).x * (w).y)
-    if (!inverse) {
-        for (int k = kq; k < N; k += KQ) zbuf[k * ZL + il] = live ? data[c + C * k] : make_double2(0.0, 0.0);
-        __syncthreads();
-        int h = half, st = 1;
-        if (logn & 1) {
-            for (int q = kq; q < half; q += KQ) {
-                const int jj = q & (h - 1), a = ((q - jj) << 1) + jj, b = a + h;
-                const double2 xa = ZB(a), xb = ZB(b), w = tw[jj * st];
-                ZB(a) = make_double2(xa.x + xb.x, xa.y + xb.y);
-                ZB(b) = CMUL(xa.x - xb.x, xa.y - xb.y, w);
-            }
-            __syncthreads();
-            h >>= 1; st <<= 1;
-        }
-        for (; h >= 2; h >>= 2, st <<= 2) {
-            const int h2 = h >> 1;
-            for (int q = kq; q < quarter; q += KQ) {
-                const int jj = q & (h2 - 1), a = ((q - jj) << 2) + jj;
-                const double2 x0 = ZB(a), x1 = ZB(a + h2), x2 = ZB(a + h), x3 = ZB(a + h + h2);
-                const double2 wa = tw[jj * st], wb = tw[(jj + h2) * st], wc = tw[jj * 2 * st];
-                const double2 y0 = make_double2(x0.x + x2.x, x0.y + x2.y), y2 = CMUL(x0.x - x2.x, x0.y - x2.y, wa);
-                const double2 y1 = make_double2(x1.x + x3.x, x1.y + x3.y), y3 = CMUL(x1.x - x3.x, x1.y - x3.y, wb);
-                ZB(a) = make_double2(y0.x + y1.x, y0.y + y1.y);
-                ZB(a + h2) = CMUL(y0.x - y1.x, y0.y - y1.y, wc);
-                ZB(a + h) = make_double2(y2.x + y3.x, y2.y + y3.y);
-                ZB(a + h + h2) = CMUL(y2.x - y3.x, y2.y - y3.y, wc);
-            }
-            __syncthreads();
-        }
-        if (live)
-            for (int p = kq; p < N; p += KQ) data[c + C * (long)(__brev((unsigned)p) >> (32 - logn))] = zbuf[p * ZL + il];
-    } else {
-        for (int k = kq; k < N; k += KQ)
-            zbuf[(int)(__brev((unsigned)k) >> (32 - logn)) * ZL + il] = live ? data[c + C * k] : make_double2(0.0, 0.0);
-        __syncthreads();
-        int h = 1, st = half;
-        for (; (h << 1) <= half; h <<= 2, st >>= 2) {
-            for (int q = kq; q < quarter; q += KQ) {
-                const int jj = q & (h - 1), a = ((q - jj) << 2) + jj;
-                const double2 x0 = ZB(a), x1 = ZB(a + h), x2 = ZB(a + 2 * h), x3 = ZB(a + 3 * h);
-                const double2 wa = tw[jj * st], wb = tw[jj * (st >> 1)], wc = tw[(jj + h) * (st >> 1)];
-                const double2 t1 = CMULC(x1, wa), t3 = CMULC(x3, wa);
-                const double2 y0 = make_double2(x0.x + t1.x, x0.y + t1.y), y1 = make_double2(x0.x - t1.x, x0.y - t1.y);
-                const double2 y2 = make_double2(x2.x + t3.x, x2.y + t3.y), y3 = make_double2(x2.x - t3.x, x2.y - t3.y);
-                const double2 u2 = CMULC(y2, wb), u3 = CMULC(y3, wc);
-                ZB(a) = make_double2(y0.x + u2.x, y0.y + u2.y);
-                ZB(a + 2 * h) = make_double2(y0.x - u2.x, y0.y - u2.y);
-                ZB(a + h) = make_double2(y1.x + u3.x, y1.y + u3.y);
-                ZB(a + 3 * h) = make_double2(y1.x - u3.x, y1.y - u3.y);
-            }
-            __syncthreads();
-        }
-        if (h <= half) {
-            for (int q = kq; q < half; q += KQ) {
-                const int jj = q & (h - 1), a = ((q - jj) << 1) + jj, b = a + h;
-                const double2 xa = ZB(a), t = CMULC(ZB(b), tw[jj * st]);
-                ZB(a) = make_double2(xa.x + t.x, xa.y + t.y);
-                ZB(b) = make_double2(xa.x - t.x, xa.y - t.y);
-            }
-            __syncthreads();
-        }
-        if (live)
-            for (int k = kq; k < N; k += KQ) {
-                const double2 v = zbuf[k * ZL + il];
-                data[c + C * k] = make_double2(v.x * scale, v.y * scale);
-            }
-    }
-#undef ZB
-#undef CMUL
-#undef CMULC
-}
-
-// The x stage of the distributed FFT solve in ONE pass (distributed_fft_based_poisson_solver.jl:152-166 with the transposes'
-// unpack / pack folded in): a workgroup gathers L whole x-lines (length Nxg = R * Nxl, a power of two) from the all-to-all
-// receive buffer -- chunk p holds columns [p*Nxl, (p+1)*Nxl) of every line (il fastest) --, transforms them forward (radix-4
-// DIF), divides by the eigenvalues in bit-reversed order, transforms back (DIT) and scatters them into the send buffer in
-// the same chunk layout. Replaces unpack + rocFFT + divide + rocFFT + pack (5 passes). LDS: L * Nxg complex.
-__global__ void __launch_bounds__(256) xline_solve_kernel(const double2 *recv, double2 *send, const double2 *tw, const double *lx,
-                                                          const double *ly, const double *lz, int R, int Nxl, int Nyc, int Nz,
-                                                          int logn, int L, int joff, int Ny, double scale) {
-    extern __shared__ double2 zbuf[];                 // [L][Nxg]
-    const int N = R * Nxl;
-    const long nlines = (long)Nyc * Nz, line0 = (long)blockIdx.x * L;
-    const long chunk = (long)Nxl * nlines;
-    const int total = L * N;
-    for (int e = threadIdx.x; e < total; e += 256) {
-        const int ln = e >> logn, n = e & (N - 1);
-        const long line = line0 + ln;
-        const int pch = n / Nxl, il = n - pch * Nxl;
-        zbuf[e] = line < nlines ? recv[pch * chunk + il + (long)Nxl * line] : make_double2(0.0, 0.0);
-    }
-    __syncthreads();
-    const int half = N >> 1, quarter = N >> 2;
-#define ZB(n) zbuf[lo + (n)]
-#define CMUL(ar, ai, w) make_double2((ar) * (w).x - (ai) * (w).y, (ar) * (w).y + (ai) * (w).x)
-#define CMULC(v, w) make_double2((v).x * (w).x + (v).y * (w).y, (v).y * (w).x - (v).x * (w).y)
-    int h = half, st = 1;
-    if (logn & 1) {
-        for (int e = threadIdx.x; e < L * half; e += 256) {
-            const int ln = e >> (logn - 1), q = e & (half - 1), lo = ln << logn;
-            const int jj = q & (h - 1), a = ((q - jj) << 1) + jj, b = a + h;
-            const double2 xa = ZB(a), xb = ZB(b), w = tw[jj * st];
-            ZB(a) = make_double2(xa.x + xb.x, xa.y + xb.y);
-            ZB(b) = CMUL(xa.x - xb.x, xa.y - xb.y, w);
-        }
-        __syncthreads();
-        h >>= 1; st <<= 1;
-    }
-    for (; h >= 2; h >>= 2, st <<= 2) {
-        const int h2 = h >> 1;
-        for (int e = threadIdx.x; e < L * quarter; e += 256) {
-            const int ln = e >> (logn - 2), q = e & (quarter - 1), lo = ln << logn;
-            const int jj = q & (h2 - 1), a = ((q - jj) << 2) + jj;
-            const double2 x0 = ZB(a), x1 = ZB(a + h2), x2 = ZB(a + h), x3 = ZB(a + h + h2);
-            const double2 wa = tw[jj * st], wb = tw[(jj + h2) * st], wc = tw[jj * 2 * st];
-            const double2 y0 = make_double2(x0.x + x2.x, x0.y + x2.y), y2 = CMUL(x0.x - x2.x, x0.y - x2.y, wa);
-            const double2 y1 = make_double2(x1.x + x3.x, x1.y + x3.y), y3 = CMUL(x1.x - x3.x, x1.y - x3.y, wb);
-            ZB(a) = make_double2(y0.x + y1.x, y0.y + y1.y);
-            ZB(a + h2) = CMUL(y0.x - y1.x, y0.y - y1.y, wc);
-            ZB(a + h) = make_double2(y2.x + y3.x, y2.y + y3.y);
-            ZB(a + h + h2) = CMUL(y2.x - y3.x, y2.y - y3.y, wc);
-        }
-        __syncthreads();
-    }
-    for (int e = threadIdx.x; e < total; e += 256) {
-        const int ln = e >> logn, pz = e & (N - 1);
-        const long line = line0 + ln;
-        if (line >= nlines) continue;
-        const int jl = (int)(line % Nyc), k = (int)(line / Nyc);
-        const int i = (int)(__brev((unsigned)pz) >> (32 - logn));
-        const int jg = min(joff + jl, Ny - 1);
-        double2 v = zbuf[e];
-        const double lam = (lx[i] + ly[jg]) + lz[k] - 0.0;
-        v.x = -(v.x * scale) / lam;
-        v.y = -(v.y * scale) / lam;
-        if (i == 0 && joff + jl == 0 && k == 0) v = make_double2(0.0, 0.0);
-        zbuf[e] = v;
-    }
-    __syncthreads();
-    h = 1; st = half;
-    for (; (h << 1) <= half; h <<= 2, st >>= 2) {
-        for (int e = threadIdx.x; e < L * quarter; e += 256) {
-            const int ln = e >> (logn - 2), q = e & (quarter - 1), lo = ln << logn;
-            const int jj = q & (h - 1), a = ((q - jj) << 2) + jj;
-            const double2 x0 = ZB(a), x1 = ZB(a + h), x2 = ZB(a + 2 * h), x3 = ZB(a + 3 * h);
-            const double2 wa = tw[jj * st], wb = tw[jj * (st >> 1)], wc = tw[(jj + h) * (st >> 1)];
-            const double2 t1 = CMULC(x1, wa), t3 = CMULC(x3, wa);
-            const double2 y0 = make_double2(x0.x + t1.x, x0.y + t1.y), y1 = make_double2(x0.x - t1.x, x0.y - t1.y);
-            const double2 y2 = make_double2(x2.x + t3.x, x2.y + t3.y), y3 = make_double2(x2.x - t3.x, x2.y - t3.y);
-            const double2 u2 = CMULC(y2, wb), u3 = CMULC(y3, wc);
-            ZB(a) = make_double2(y0.x + u2.x, y0.y + u2.y);
-            ZB(a + 2 * h) = make_double2(y0.x - u2.x, y0.y - u2.y);
-            ZB(a + h) = make_double2(y1.x + u3.x, y1.y + u3.y);
-            ZB(a + 3 * h) = make_double2(y1.x - u3.x, y1.y - u3.y);
-        }
-        __syncthreads();
-    }
-    if (h <= half) {
-        for (int e = threadIdx.x; e < L * half; e += 256) {
-            const int ln = e >> (logn - 1), q = e & (half - 1), lo = ln << logn;
-            const int jj = q & (h - 1), a = ((q - jj) << 1) + jj, b = a + h;
-            const double2 xa = ZB(a), t = CMULC(ZB(b), tw[jj * st]);
-            ZB(a) = make_double2(xa.x + t.x, xa.y + t.y);
-            ZB(b) = make_double2(xa.x - t.x, xa.y - t.y);
-        }
-        __syncthreads();
-    }
-#undef ZB
-#undef CMUL
-#undef CMULC
-    for (int e = threadIdx.x; e < total; e += 256) {
-        const int ln = e >> logn, n = e & (N - 1);
-        const long line = line0 + ln;
-        if (line >= nlines) continue;
-        const int pch = n / Nxl, il = n - pch * Nxl;
-        send[pch * chunk + il + (long)Nxl * line] = zbuf[e];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
 // Substructured x solve of the distributed FFT Poisson solver (z Periodic): after the local (y, z) transform every (ky, kz) mode
 // is an independent PERIODIC CONSTANT-COEFFICIENT TRIDIAGONAL system along the partitioned x direction,
 //     a (p[i-1] - 2 p[i] + p[i+1]) - (λy + λz) p[i] = r[i],   a = 1/Δx².
@@ -3054,7 +2469,8 @@ __global__ void __launch_bounds__(256) pressure_correction_zfast_strips_kernel(D
 //   spectrum             S[i + Nx (ky + Ny kz)],  kz = 0 .. Nz/2      (x lines contiguous: 4 KB at Nx = 256)
 // * z: the real-to-complex transform of TWO neighbouring x columns at once -- (r[2i'], r[2i'+1]) read as one complex number, a complex
 //   radix-4 line FFT along z in LDS (the machinery of strided_line_fft_kernel: ZL pairs = ZL x 16 B rows per workgroup), and the two
-//   columns' half spectra separated with the Hermitian symmetry WHILE THE LINE IS IN LDS (paired_zline_r2c_kernel / _c2r_kernel);
+//   columns' half spectra separated with the Hermitian symmetry WHILE THE LINE IS IN LDS (paired_zline_r2c_kernel / _c2r_kernel,
+//   ocn_line_fft.h);
 // * y: strided_line_fft_kernel, as on the single-GPU path;
 // * x: one WAVE per line. A lane holds E consecutive elements; the two Thomas recurrences f_i = (r_i - a f_{i-1}) d_i and
 //   y_i = f_i - a d_i y_{i+1} are affine maps, composed across the 64 lanes by a shuffle scan (6 steps), then re-evaluated inside the lane
@@ -3064,122 +2480,6 @@ __global__ void __launch_bounds__(256) pressure_correction_zfast_strips_kernel(D
 // Same solution as the z-fastest variant to round-off (the scan re-associates the recurrences); validated at creation and by the
 // partitioned-vs-single-GPU tests at 1e-12.
 // ---------------------------------------------------------------------------------------------------------------------
-#define OCN_FFT_CMUL(ar, ai, w) make_double2((ar) * (w).x - (ai) * (w).y, (ar) * (w).y + (ai) * (w).x)
-#define OCN_FFT_CMULC(v, w) make_double2((v).x * (w).x + (v).y * (w).y, (v).y * (w).x - (v).x * (w).y)
-// forward radix-4 DIF of the ZL lines in zbuf[N][ZL] (natural order in, frequency f at position bitreverse(f) out)
-template <int ZL> __device__ __forceinline__ void lds_fft_forward(double2 *zbuf, const double2 *tw, int N, int logn, int il, int kq) {
-    const int half = N >> 1, quarter = N >> 2, KQ = 256 / ZL;
-#define ZB(n) zbuf[(n) * ZL + il]
-    int h = half, st = 1;
-    if (logn & 1) {
-        for (int q = kq; q < half; q += KQ) {
-            const int jj = q & (h - 1), a = ((q - jj) << 1) + jj, b = a + h;
-            const double2 xa = ZB(a), xb = ZB(b), w = tw[jj * st];
-            ZB(a) = make_double2(xa.x + xb.x, xa.y + xb.y);
-            ZB(b) = OCN_FFT_CMUL(xa.x - xb.x, xa.y - xb.y, w);
-        }
-        __syncthreads();
-        h >>= 1; st <<= 1;
-    }
-    for (; h >= 2; h >>= 2, st <<= 2) {
-        const int h2 = h >> 1;
-        for (int q = kq; q < quarter; q += KQ) {
-            const int jj = q & (h2 - 1), a = ((q - jj) << 2) + jj;
-            const double2 x0 = ZB(a), x1 = ZB(a + h2), x2 = ZB(a + h), x3 = ZB(a + h + h2);
-            const double2 wa = tw[jj * st], wb = tw[(jj + h2) * st], wc = tw[jj * 2 * st];
-            const double2 y0 = make_double2(x0.x + x2.x, x0.y + x2.y), y2 = OCN_FFT_CMUL(x0.x - x2.x, x0.y - x2.y, wa);
-            const double2 y1 = make_double2(x1.x + x3.x, x1.y + x3.y), y3 = OCN_FFT_CMUL(x1.x - x3.x, x1.y - x3.y, wb);
-            ZB(a) = make_double2(y0.x + y1.x, y0.y + y1.y);
-            ZB(a + h2) = OCN_FFT_CMUL(y0.x - y1.x, y0.y - y1.y, wc);
-            ZB(a + h) = make_double2(y2.x + y3.x, y2.y + y3.y);
-            ZB(a + h + h2) = OCN_FFT_CMUL(y2.x - y3.x, y2.y - y3.y, wc);
-        }
-        __syncthreads();
-    }
-#undef ZB
-}
-// inverse radix-4 DIT (frequency f at position bitreverse(f) in, natural order out, unnormalised)
-template <int ZL> __device__ __forceinline__ void lds_fft_inverse(double2 *zbuf, const double2 *tw, int N, int il, int kq) {
-    const int half = N >> 1, quarter = N >> 2, KQ = 256 / ZL;
-#define ZB(n) zbuf[(n) * ZL + il]
-    int h = 1, st = half;
-    for (; (h << 1) <= half; h <<= 2, st >>= 2) {
-        for (int q = kq; q < quarter; q += KQ) {
-            const int jj = q & (h - 1), a = ((q - jj) << 2) + jj;
-            const double2 x0 = ZB(a), x1 = ZB(a + h), x2 = ZB(a + 2 * h), x3 = ZB(a + 3 * h);
-            const double2 wa = tw[jj * st], wb = tw[jj * (st >> 1)], wc = tw[(jj + h) * (st >> 1)];
-            const double2 t1 = OCN_FFT_CMULC(x1, wa), t3 = OCN_FFT_CMULC(x3, wa);
-            const double2 y0 = make_double2(x0.x + t1.x, x0.y + t1.y), y1 = make_double2(x0.x - t1.x, x0.y - t1.y);
-            const double2 y2 = make_double2(x2.x + t3.x, x2.y + t3.y), y3 = make_double2(x2.x - t3.x, x2.y - t3.y);
-            const double2 u2 = OCN_FFT_CMULC(y2, wb), u3 = OCN_FFT_CMULC(y3, wc);
-            ZB(a) = make_double2(y0.x + u2.x, y0.y + u2.y);
-            ZB(a + 2 * h) = make_double2(y0.x - u2.x, y0.y - u2.y);
-            ZB(a + h) = make_double2(y1.x + u3.x, y1.y + u3.y);
-            ZB(a + 3 * h) = make_double2(y1.x - u3.x, y1.y - u3.y);
-        }
-        __syncthreads();
-    }
-    if (h <= half) {
-        for (int q = kq; q < half; q += KQ) {
-            const int jj = q & (h - 1), a = ((q - jj) << 1) + jj, b = a + h;
-            const double2 xa = ZB(a), t = OCN_FFT_CMULC(ZB(b), tw[jj * st]);
-            ZB(a) = make_double2(xa.x + t.x, xa.y + t.y);
-            ZB(b) = make_double2(xa.x - t.x, xa.y - t.y);
-        }
-        __syncthreads();
-    }
-#undef ZB
-}
-
-// real-to-complex along z of the column PAIRS of a dense x-fastest real array: rp[c + C k] = (r[2c], r[2c+1]) at level k, c = pair index
-// over (x, y) (C = Nx Ny / 2 pairs per level); out: spec[2c + 2C kz], spec[2c + 1 + 2C kz], kz = 0 .. N/2 -- the half spectra of the two
-// columns. With Z = FFT(r_even + i r_odd): X_even[k] = (Z[k] + conj Z[N-k]) / 2, X_odd[k] = (Z[k] - conj Z[N-k]) / (2i).
-template <int ZL>
-__global__ void __launch_bounds__(256) paired_zline_r2c_kernel(const double2 *rp, double2 *spec, const double2 *tw, long C, int N, int logn) {
-    extern __shared__ double2 zbuf[];                 // [N][ZL]
-    const int il = threadIdx.x % ZL, kq = threadIdx.x / ZL, KQ = 256 / ZL;
-    const long c = (long)blockIdx.x * ZL + il;
-    const bool live = c < C;
-    for (int k = kq; k < N; k += KQ) zbuf[k * ZL + il] = live ? rp[c + C * k] : make_double2(0.0, 0.0);
-    __syncthreads();
-    lds_fft_forward<ZL>(zbuf, tw, N, logn, il, kq);
-    if (!live) return;
-    for (int kz = kq; kz <= (N >> 1); kz += KQ) {
-        const int pa = (int)(__brev((unsigned)kz) >> (32 - logn)), pb = (int)(__brev((unsigned)((N - kz) & (N - 1))) >> (32 - logn));
-        const double2 a = zbuf[pa * ZL + il], b = zbuf[pb * ZL + il];
-        double2 *o = spec + 2 * c + 2 * C * (long)kz;
-        o[0] = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
-        o[1] = make_double2(0.5 * (a.y + b.y), -0.5 * (a.x - b.x));
-    }
-}
-// the way back: Z[k] = X_even[k] + i X_odd[k], Z[N-k] = conj X_even[k] + i conj X_odd[k]; the imaginary parts of the k = 0 and k = N/2
-// entries are ignored like a complex-to-real transform ignores them; rp = Re / Im of the inverse transform, times `scale`
-template <int ZL>
-__global__ void __launch_bounds__(256) paired_zline_c2r_kernel(const double2 *spec, double2 *rp, const double2 *tw, long C, int N, int logn, double scale) {
-    extern __shared__ double2 zbuf[];
-    const int il = threadIdx.x % ZL, kq = threadIdx.x / ZL, KQ = 256 / ZL;
-    const long c = (long)blockIdx.x * ZL + il;
-    const bool live = c < C;
-    for (int kz = kq; kz <= (N >> 1); kz += KQ) {
-        const double2 *in = spec + 2 * c + 2 * C * (long)kz;
-        const double2 E = live ? in[0] : make_double2(0.0, 0.0), O = live ? in[1] : make_double2(0.0, 0.0);
-        const int pa = (int)(__brev((unsigned)kz) >> (32 - logn));
-        if (kz == 0 || kz == (N >> 1)) zbuf[pa * ZL + il] = make_double2(E.x, O.x);
-        else {
-            const int pb = (int)(__brev((unsigned)(N - kz)) >> (32 - logn));
-            zbuf[pa * ZL + il] = make_double2(E.x - O.y, E.y + O.x);
-            zbuf[pb * ZL + il] = make_double2(E.x + O.y, O.x - E.y);
-        }
-    }
-    __syncthreads();
-    lds_fft_inverse<ZL>(zbuf, tw, N, il, kq);
-    if (!live) return;
-    for (int k = kq; k < N; k += KQ) {
-        const double2 v = zbuf[k * ZL + il];
-        rp[c + C * k] = make_double2(v.x * scale, v.y * scale);
-    }
-}
-
 // Thomas factors of every mode in the x-fastest layout: rden[i + N m] = 1 / (b_m - a cp[i-1]), cp = a rden (the recurrences of
 // sub_setup_kernel), and of s = T^-1 e_0 only what the interface system needs: its first and last entry (and its sum for the null mode).
 // `scratch` (N M doubles) holds s while it is back-substituted. One thread per mode; runs once.
@@ -3410,15 +2710,9 @@ __global__ void __launch_bounds__(256) source_paired_zline_r2c_kernel(DGrid g, F
         zbuf[kk * ZL + il] = live ? make_double2(1.0 * d0, 1.0 * d1) : make_double2(0.0, 0.0);
     }
     __syncthreads();
-    lds_fft_forward<ZL>(zbuf, tw, N, logn, il, kq);
+    lds_fft_forward(InterleavedLines<ZL>{zbuf, il, kq}, tw, N, logn);
     if (!live) return;
-    for (int kz = kq; kz <= (N >> 1); kz += KQ) {
-        const int pa = (int)(__brev((unsigned)kz) >> (32 - logn)), pb = (int)(__brev((unsigned)((N - kz) & (N - 1))) >> (32 - logn));
-        const double2 a = zbuf[pa * ZL + il], b = zbuf[pb * ZL + il];
-        double2 *o = spec + 2 * c + 2 * C * (long)kz;
-        o[0] = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
-        o[1] = make_double2(0.5 * (a.y + b.y), -0.5 * (a.x - b.x));
-    }
+    paired_zline_separate<ZL>(zbuf, spec, c, C, N, logn, il, kq);
 }
 
 // first / last column of the dense x-fastest array -> dense (Ny, Nz) buffers [j-1 + Ny (k-1)]

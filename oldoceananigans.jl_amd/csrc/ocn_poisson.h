@@ -3,7 +3,7 @@
 // by ocn_api.hip behind the pressure-correction entry points.
 #pragma once
 
-// line-FFT kernels (ocn_kernels.h): lines per workgroup by line length, see strided_line_fft_kernel; the longest line they take: 1024
+// line-FFT kernels (ocn_line_fft.h): lines per workgroup by line length, see strided_line_fft_kernel; the longest line they take: 1024
 // points x 4 lines x 16 B = the 64 KB of LDS a workgroup may ask for
 #ifndef OCN_LINE_MAX
 #define OCN_LINE_MAX 1024
