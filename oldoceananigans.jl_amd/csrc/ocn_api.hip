@@ -2567,43 +2567,13 @@ extern "C" int ocn_cache_tendencies(ocn_grid_t grid, double *const *Gm, const do
 // ---------------------------------------------------------------------------------------------------------------------
 // pressure source term / correction
 // ---------------------------------------------------------------------------------------------------------------------
-static int source_term(const DGrid &g, const double *u, const double *v, const double *w, void *rhs, bool weight, bool real_out = false,
-                       long sj = 0, long sk = 0, bool pad = false, bool wrap = false, int wrap_mask = 0, const double *u_east = nullptr) {
-    if (sj == 0) { sj = g.Nx; sk = (long)g.Nx * g.Ny; }
-    if (real_out)
-        hipLaunchKernelGGL(source_term_kernel<true>, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, u, LOC_U),
-                           make_view(g, v, LOC_V), make_view(g, w, LOC_W), rhs, weight, sj, sk, pad, wrap ? 7 : wrap_mask, u_east);
-    else
-        hipLaunchKernelGGL(source_term_kernel<false>, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, u, LOC_U),
-                           make_view(g, v, LOC_V), make_view(g, w, LOC_W), rhs, weight, sj, sk, false);
-    KERNEL_CHECK();
-    return OCN_OK;
-}
+#include "ocn_pressure_step.h"          // the kernels and the launchers source_term, pressure_correction, divide_interior, ...
 
 extern "C" int ocn_compute_source_term(ocn_grid_t grid, const double *u, const double *v, const double *w, double *rhs_complex,
                                        int weight_by_dz) {
     NEED_INIT();
     if (!grid || !u || !v || !w || !rhs_complex) return fail(OCN_EINVAL, "NULL argument");
     return source_term(grid->d, u, v, w, rhs_complex, weight_by_dz != 0);
-}
-
-static int pressure_correction(const DGrid &g, double *u, double *v, double *w, const double *p, const int *range = nullptr,
-                               double *pdiv = nullptr, double divisor = 1.0) {
-    Range6 r{1, g.Nx, 1, g.Ny, 1, g.Nz};
-    if (range) {
-        const int N[3] = {g.Nx, g.Ny, g.Nz};
-        for (int d = 0; d < 3; ++d)
-            if (range[2 * d] < 1 || range[2 * d + 1] > N[d])
-                return fail(OCN_EINVAL, "range [%d, %d] along dimension %d leaves the interior", range[2 * d], range[2 * d + 1], d);
-        r = Range6{range[0], range[1], range[2], range[3], range[4], range[5]};
-    }
-    const int nx = r.i1 - r.i0 + 1, ny = r.j1 - r.j0 + 1, nz = r.k1 - r.k0 + 1;
-    if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
-    const dim3 blk = nx < 16 ? dim3(4, 64, 1) : BLK;        // an Hx-wide boundary strip: threads along y instead of 61 idle lanes in x
-    hipLaunchKernelGGL(pressure_correction_kernel, grid3(nx, ny, nz, blk), blk, 0, g_stream, g, make_view(g, u, LOC_U),
-                       make_view(g, v, LOC_V), make_view(g, w, LOC_W), make_view(g, p, LOC_C), r, pdiv, divisor);
-    KERNEL_CHECK();
-    return OCN_OK;
 }
 
 extern "C" int ocn_make_pressure_correction_divide(ocn_grid_t grid, double *u, double *v, double *w, const double *p, double *p_divided,
@@ -2623,12 +2593,6 @@ extern "C" int ocn_make_pressure_correction(ocn_grid_t grid, double *u, double *
     NEED_INIT();
     if (!grid || !u || !v || !w || !p) return fail(OCN_EINVAL, "NULL argument");
     return pressure_correction(grid->d, u, v, w, p);
-}
-
-static int divide_interior(const DGrid &g, double *p, double divisor) {
-    hipLaunchKernelGGL(divide_interior_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, p, LOC_C), divisor);
-    KERNEL_CHECK();
-    return OCN_OK;
 }
 
 extern "C" int ocn_divide_interior(ocn_grid_t grid, double *p, double divisor) {
@@ -3837,7 +3801,7 @@ static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = tru
         hipLaunchKernelGGL(substep_source_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, a, pending->dt, pending->gamma, s->rrhs,
                            s->kind == 1);
         KERNEL_CHECK();
-    } else if ((rc = source_term(g, m->U[0], m->U[1], m->U[2], s->rrhs, s->kind == 1, true, 0, 0, false, ppp))) return rc;
+    } else if ((rc = source_term(g, m->U[0], m->U[1], m->U[2], s->rrhs, s->kind == 1, true, SourceLayout{{}, false, ppp ? 7 : 0}))) return rc;
     if ((rc = poisson_solve_real_split(s))) return rc;
     const double dtp = std::fmax(2.220446049250313e-16, dt);
     const bool store_p = keep_p || !m->opt.skip_stage_pressure;
@@ -3851,10 +3815,8 @@ static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = tru
                            make_view(g, m->U[2], LOC_W), (const double *)s->rrhs, make_view(g, m->p, LOC_C), dtp, store_p, tr,
                            (const double *)m->Gn[0], (const double *)m->Gn[1], (const double *)m->Gn[2], pending ? pending->dt : 0.0,
                            pending ? pending->gamma : 0.0);
-    } else
-        hipLaunchKernelGGL(pressure_correction_dense_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, m->U[0], LOC_U),
-                           make_view(g, m->U[1], LOC_V), make_view(g, m->U[2], LOC_W), (const double *)s->rrhs, make_view(g, m->p, LOC_C), dtp,
-                           g.tz == OCN_BOUNDED, store_p);
+    } else          // the whole grid as one column range, x wrapped
+        launch_pressure_correction_dense(g, m->U[0], m->U[1], m->U[2], DenseSolution{s->rrhs, {}}, nullptr, m->p, dtp, store_p, 1, g.Nx);
     KERNEL_CHECK();
     if (!store_p || fold_halos) return OCN_OK;
     double *pp[1] = {m->p};

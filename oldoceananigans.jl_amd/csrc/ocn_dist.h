@@ -367,8 +367,8 @@ struct DistModel {
     bool pencil = false;        // Partition(Rx, Ry) with Ry > 1: a second hop along y per fill (corners ride along)
     double *ss = nullptr, *ns = nullptr, *sr = nullptr, *nr = nullptr;     // y-halo buffers: Hy rows of every prognostic field per side
     bool plain_y = true;        // the non-partitioned y direction is Periodic (what the partitioned solvers transform); Bounded / Flat y: gathered solve
-    // Round 3 -- the pressure step of (connected, Periodic, Periodic) x-slabs without the passes between its stages (ocn_kernels.h,
-    // "Round 3"): one-column exchanges of u and p through dense (Ny, Nz) buffers that the source-term / correction kernels read directly,
+    // Round 3 -- the pressure step of (connected, Periodic, Periodic) x-slabs without the passes between its stages (ocn_pressure_step.h):
+    // one-column exchanges of u and p through dense (Ny, Nz) buffers that the source-term / correction kernels read directly,
     // the solution left z-fastest, the early exchange packed from wrapped interior indices; the column buffers exist when the model was
     // created with option fused_step on a slab that takes it, the option switches it on and off afterwards
     double *cws = nullptr, *ces = nullptr, *cwr = nullptr, *cer = nullptr;   // column buffers: Ny * Nz doubles each
@@ -502,7 +502,7 @@ static int dist_solve_for_pressure(ocn_model_s *m) {
         const DGrid &g = m->grid->d, &G = q->ggrid->d;
         ocn_poisson_s *ps = q->solver;
         const size_t piece = (size_t)q->nmax * q->nymax * g.Nz;
-        if ((rc = source_term(g, m->U[0], m->U[1], m->U[2], q->loc, ps->kind == 1, true, q->nmax, (long)q->nmax * q->nymax))) return rc;
+        if ((rc = source_term(g, m->U[0], m->U[1], m->U[2], q->loc, ps->kind == 1, true, SourceLayout{{q->nmax, (long)q->nmax * q->nymax}}))) return rc;
         if ((rc = ocn_dist_all_gather(dm->dist, q->loc, q->all, piece))) return rc;
         const bool real_path = m->opt.real_fft && !ps->general;
         if (!real_path && (rc = ensure_complex(ps))) return rc;
@@ -541,12 +541,6 @@ static int dist_solve_for_pressure(ocn_model_s *m) {
 // compute_pressure_correction! (pressure_correction.jl:8-20). Of the x halos only ONE column is read before update_state! fills
 // everything again: u[Nx+1] by the divergence, p[0] by the correction. The reference's generic fills move Hx columns of u, v, w and of
 // p here; `thin_halos` exchanges the one column of u and of p -- identical results in every cell that is read.
-// where the solver leaves its dense solution and how cell (i, j, k) is addressed in it: (i-1) + sj (j-1) + sk (k-1)
-struct DenseSolution { const double *p; long sj, sk; };
-static DenseSolution dist_dense_solution(const ocn_dist_poisson_s *s, const DGrid &g) {
-    if (s->xfast) return {(const double *)s->rx, (long)g.Nx, (long)g.Nx * g.Ny};
-    return {(const double *)s->zfield, (long)s->Nxe * s->Nz, (long)s->Nxe};          // transposing solvers: paired-column layout (x, z, y)
-}
 
 // after a failed step: forget a started exchange (the error already on record stays the one reported)
 static void dist_abandon_exchange(ocn_model_s *m) {
@@ -593,8 +587,8 @@ static int dist_compute_pressure_correction_fused(ocn_model_s *m) {
         hipLaunchKernelGGL(column_pack_zfast_kernel, dim3((g.Nz + 255) / 256, g.Ny), dim3(256), 0, g_stream, g.Nx, g.Ny, g.Nz, (const double *)s->rreal,
                            dm->cws, dm->ces);
     else {
-        const DenseSolution d = dist_dense_solution(s, g);
-        hipLaunchKernelGGL(column_pack_dense_kernel, dim3((g.Ny + 255) / 256, g.Nz), dim3(256), 0, g_stream, g.Nx, g.Ny, g.Nz, d.p, dm->cws, dm->ces, d.sj, d.sk);
+        const DenseSolution d = dist_dense_solution(s);
+        hipLaunchKernelGGL(column_pack_dense_kernel, dim3((g.Ny + 255) / 256, g.Nz), dim3(256), 0, g_stream, g.Nx, g.Ny, g.Nz, d.p, dm->cws, dm->ces, d.at.sj, d.at.sk);
     }
     KERNEL_CHECK();
     return dist_exchange_inline(dm->dist, dm->cws, dm->ces, dm->cwr, dm->cer, col);                      // cwr: the west neighbour's p[Nx] = our p[0]
@@ -626,13 +620,12 @@ static int dist_make_pressure_correction(ocn_model_s *m, double dt, bool start_h
         // corrections straight from the z-fastest solution (p[0] from the received column): both strips in one launch, pack from wrapped
         // interior indices (no local fill of the strips), start the exchange, then the interior
         const bool zf = dm->solver->zfirst, zb = g.tz != OCN_PERIODIC;
-        const DenseSolution d = dist_dense_solution(dm->solver, g);
+        const DenseSolution d = dist_dense_solution(dm->solver);
         const double *pd = zf ? (const double *)dm->solver->rreal : d.p, *pw = (const double *)dm->cwr;
         const FView vu = make_view(g, m->U[0], LOC_U), vv = make_view(g, m->U[1], LOC_V), vw = make_view(g, m->U[2], LOC_W), vp = make_view(g, m->p, LOC_C);
         auto pcz = [&](int ia, int ib) {
             if (!zf)         // the solution is dense and x-fastest: the single-GPU path's dense correction on a column range
-                hipLaunchKernelGGL(pressure_correction_dense_slab_kernel, grid3(ib - ia + 1, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, vu, vv, vw, pd, pw, vp, dtp, ia, ib,
-                                   d.sj, d.sk, zb, keep_p);
+                launch_pressure_correction_dense(g, m->U[0], m->U[1], m->U[2], d, pw, m->p, dtp, keep_p, ia, ib);
             else
                 hipLaunchKernelGGL(pressure_correction_zfast_kernel, dim3((ib - ia + 32) / 32, (g.Nz + 31) / 32, (g.Ny + OCN_ZC_JB - 1) / OCN_ZC_JB), dim3(32, 8), 0,
                                    g_stream, g, vu, vv, vw, pd, pw, vp, dtp, ia, ib);
@@ -643,7 +636,7 @@ static int dist_make_pressure_correction(ocn_model_s *m, double dt, bool start_h
         const unsigned sbx = (2 * g.Hx + 7) / 8;          // the two strips hold 2 Hx columns: one block of 8 up to Hx = 4
         if (!zf)
             hipLaunchKernelGGL(pressure_correction_dense_strips_kernel, dim3(sbx, (g.Ny + 31) / 32, g.Nz), dim3(8, 32), 0, g_stream, g, vu, vv, vw, pd, pw, vp, dtp, g.Hx,
-                               d.sj, d.sk, zb, keep_p);
+                               d.at.sj, d.at.sk, zb, keep_p);
         else
             hipLaunchKernelGGL(pressure_correction_zfast_strips_kernel, dim3(sbx, (g.Ny + 31) / 32, g.Nz), dim3(8, 32), 0, g_stream, g, vu, vv, vw, pd, pw, vp, dtp, g.Hx);
         KERNEL_CHECK();
@@ -807,7 +800,7 @@ static int gathered_solve_create(DistModel *dm, const OcnOptions *opt, ocn_grid_
     return OCN_OK;
 }
 
-// the pressure step without fills / copies between its stages (ocn_kernels.h "Round 3"): a partitioned (connected, Periodic, *) slab with one
+// the pressure step without fills / copies between its stages (ocn_pressure_step.h): a partitioned (connected, Periodic, *) slab with one
 // of the accelerated solvers -- the substructured ones (z Periodic: every field shares one parent shape, which the wrapped pack relies on)
 // or the transposing ones (z Periodic or Bounded: the solution stays in their dense paired-column array)
 static int dist_enable_fused_step(const OcnOptions &o, DistModel *dm, const DGrid &g, bool part) {

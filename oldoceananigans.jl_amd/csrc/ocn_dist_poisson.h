@@ -499,6 +499,14 @@ extern "C" int ocn_dist_poisson_forward_local(ocn_dist_poisson_t s) {
     return OCN_OK;
 }
 
+// the paired-column real array of the transposing solvers and of the substructured solver's layout 0: (x, z, y), rows of Nxe
+static DenseLayout dist_paired_columns(const ocn_dist_poisson_s *s) { return {(long)s->Nxe * s->Nz, (long)s->Nxe}; }
+// where the solver leaves its dense x-fastest solution (not the z-fastest layouts: s->rreal, read by their own kernels)
+static DenseSolution dist_dense_solution(const ocn_dist_poisson_s *s) {
+    if (s->xfast) return {(const double *)s->rx, DenseLayout{}.on(s->grid->d)};
+    return {(const double *)s->zfield, dist_paired_columns(s)};
+}
+
 // substructured mode, stage 2: interface unknowns from the gathered payloads, slab correction, rebuild the paired spectrum,
 // inverse local transform, copy into the haloed pressure
 // keep_zfast (z-fastest layout only): leave the solution in the solver's dense z-fastest real array (s->rreal) instead of copying it
@@ -517,7 +525,7 @@ static int dist_poisson_backward_local(ocn_dist_poisson_t s, double *phi, bool k
         launch_paired_zline(*s->opt, false, s->xs, (double2 *)s->rx, s->ztw, C, s->Nz, s->logn_z, 1.0);
         if (!keep_zfast && !phi) return fail(OCN_EINVAL, "NULL pressure field");
         if (!keep_zfast)           // (here: keep the dense x-fastest solution in s->rx)
-            hipLaunchKernelGGL(copy_dense_to_field_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, phi, LOC_C), (const double *)s->rx);
+            launch_copy_dense_to_field(g, phi, dist_dense_solution(s));
         KERNEL_CHECK();
         return OCN_OK;
     }
@@ -551,8 +559,7 @@ static int dist_poisson_backward_local(ocn_dist_poisson_t s, double *phi, bool k
     if ((rc = plan_set_stream(s->plan_loc))) return rc;
     FFT_TRY(hipfftExecZ2Z(s->plan_loc, (hipfftDoubleComplex *)s->zfield, (hipfftDoubleComplex *)s->zfield, HIPFFT_BACKWARD));
     if (!phi) return fail(OCN_EINVAL, "this layout of the substructured solver writes the haloed pressure field: NULL given");
-    hipLaunchKernelGGL(dist_copy_real_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, phi, LOC_C),
-                       (const double *)s->zfield, s->Nxe);
+    launch_copy_dense_to_field(g, phi, dist_dense_solution(s));
     KERNEL_CHECK();
     return OCN_OK;
 }
@@ -574,14 +581,8 @@ extern "C" int ocn_dist_poisson_source_term(ocn_dist_poisson_t s, const double *
     NEED_INIT();
     if (!s || !u || !v || !w) return fail(OCN_EINVAL, "NULL argument");
     if (s->xfast) return source_term(s->grid->d, u, v, w, s->rx, false, true);
-    if (s->zfirst) {
-        const DGrid &g = s->grid->d;
-        hipLaunchKernelGGL(source_term_zfast_kernel, dim3((g.Nx + 31) / 32, (g.Nz + 31) / 32, g.Ny), dim3(32, 8), 0, g_stream, g,
-                           make_view(g, u, LOC_U), make_view(g, v, LOC_V), make_view(g, w, LOC_W), s->rreal);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    return source_term(s->grid->d, u, v, w, s->zfield, s->zmode == 1, true, (long)s->Nxe * s->Nz, (long)s->Nxe, s->Nxe != s->Nxl);
+    if (s->zfirst) return source_term_zfast(s->grid->d, u, v, w, s->rreal);
+    return source_term(s->grid->d, u, v, w, s->zfield, s->zmode == 1, true, SourceLayout{dist_paired_columns(s), s->Nxe != s->Nxl});
 }
 
 // the partitioned model's form (z-fastest layout): no halo is read -- y / z neighbours at wrapped interior indices, u[Nx+1] from `u_east`, the
@@ -601,19 +602,11 @@ static int dist_poisson_source_term_wrapped(ocn_dist_poisson_t s, const double *
         s->src_in_spectrum = true;
         return OCN_OK;
     }
-    if (s->xfast) {
-        hipLaunchKernelGGL(source_term_dense_wrapped_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, u, LOC_U), make_view(g, v, LOC_V),
-                           make_view(g, w, LOC_W), u_east, s->rx);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
+    if (s->xfast) return source_term(g, u, v, w, s->rx, false, true, SourceLayout{{}, false, 6, u_east});
     if (!s->zfirst)     // transposing solvers (paired-column layout): y wraps (Periodic), z wraps when Periodic; a Bounded z reads its wall faces
-        return source_term(g, u, v, w, s->zfield, s->zmode == 1, true, (long)s->Nxe * s->Nz, (long)s->Nxe, s->Nxe != s->Nxl, false,
-                           2 | (s->zmode == 0 ? 4 : 0), u_east);
-    hipLaunchKernelGGL(source_term_zfast_wrapped_kernel, dim3((g.Nx + 31) / 32, (g.Nz + 31) / 32, g.Ny), dim3(32, 8), 0, g_stream, g,
-                       make_view(g, u, LOC_U), make_view(g, v, LOC_V), make_view(g, w, LOC_W), u_east, s->rreal);
-    KERNEL_CHECK();
-    return OCN_OK;
+        return source_term(g, u, v, w, s->zfield, s->zmode == 1, true,
+                           SourceLayout{dist_paired_columns(s), s->Nxe != s->Nxl, 2 | (s->zmode == 0 ? 4 : 0), u_east});
+    return source_term_zfast(g, u, v, w, s->rreal, u_east);
 }
 
 static int transpose_stage(ocn_dist_poisson_s *s, int dir, const double2 *src, double2 *dst) {
@@ -700,8 +693,7 @@ static int dist_poisson_backward_yz(ocn_dist_poisson_t s, double *phi, bool keep
     }
     if (!keep_dense) {
         if (!phi) return fail(OCN_EINVAL, "NULL pressure field");
-        hipLaunchKernelGGL(dist_copy_real_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, phi, LOC_C),
-                           (const double *)s->zfield, s->Nxe);
+        launch_copy_dense_to_field(g, phi, dist_dense_solution(s));
     }
     KERNEL_CHECK();
     return OCN_OK;

@@ -161,7 +161,7 @@ struct ocn_poisson_s {
     bool zfused = false;         // kind 0: 2-D (x, y) plans + zline_solve_kernel instead of 3-D plans + divide kernel
     // split form of the 2-D (x, y) transforms for the model's time-step (Ny = 2^m <= 1024): 1-D R2C / C2R plans along x and the y
     // pass by strided_line_fft_kernel (61 us against the 82 us of the 2-D plan's column kernel); the inverse lands in the dense
-    // real array, which pressure_correction_dense_kernel reads directly
+    // real array, which the dense pressure correction (ocn_pressure_step.h) reads directly
     bool split = false;
     int Nxp = 0;                 // row pitch (complex elements) of hc / hc2 on the split path: Nxh rounded up to a multiple of 8
     hipfftHandle plan_xr2c = 0, plan_xc2r = 0;
@@ -630,7 +630,7 @@ static int poisson_solve_real(ocn_poisson_s *s, double *phi) {
         FFT_TRY(hipfftExecZ2D(s->plan_c2r, (hipfftDoubleComplex *)sol, interior));
     } else {
         FFT_TRY(hipfftExecZ2D(s->plan_c2r, (hipfftDoubleComplex *)sol, s->rrhs));
-        hipLaunchKernelGGL(copy_dense_real_kernel, grid3(g.Nx, g.Ny, g.Nz, BLK), BLK, 0, g_stream, g, make_view(g, phi, LOC_C), s->rrhs);
+        launch_copy_dense_to_field(g, phi, DenseSolution{s->rrhs, {}});        // (fallback when the strided C2R plan is unavailable)
     }
     KERNEL_CHECK();
     return OCN_OK;
