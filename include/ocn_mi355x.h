@@ -815,8 +815,10 @@ int ocn_model_set_background_field(ocn_model_t model, const char *name, const do
  *       everything recomputed -- same bits)
  *   "smag_march" = 1 (step): z-marching Smagorinsky eddy-viscosity kernel that evaluates every strain point value once (0: one
  *       thread per cell, everything recomputed -- same bits)
- *   "fused_halo" = 1 (step): one launch per periodic fill; inside a time-step on a triply periodic grid no launch at all -- the
- *       pressure-correction kernel writes the halos
+ *   "fused_halo" = 1 (step): one launch fills the halos of every Periodic direction of a group of fields (after the wall fills; on
+ *       (Periodic, Periodic, Bounded) grids the bounded z fill rides in it too); inside a time-step on a triply periodic grid no launch
+ *       at all -- the pressure-correction kernel writes the halos. 0: one launch per Periodic direction, z, y, x, each over the whole
+ *       extent of the other two and reading what the previous one wrote -- same bits
  *   pressure solve:
  *   "real_fft" = 1 (step): D2Z / Z2D transforms (0: the reference's complex-to-complex)
  *   "c2r_strided" = 1 (creation): Z2D straight into the interior of the haloed pressure field

@@ -447,149 +447,7 @@ static int check_range(const DGrid &g, const int *range, Range6 *out, const int 
 // ---------------------------------------------------------------------------------------------------------------------
 // halo fills
 // ---------------------------------------------------------------------------------------------------------------------
-static int fill_halo_group(const OcnOptions &o, const ocn_grid_s *grid, double *const *fields, int n, const int loc[3], bool fill_open,
-                           const ocn_bc_t (*bcs)[6], bool extend_x = false) {
-    if (n <= 0) return OCN_OK;
-    const DGrid &g = grid->d;
-    FieldList fl;
-    fl.n = n;
-    for (int f = 0; f < n; ++f) fl.p[f] = fields[f];
-    int P[3];
-    parent_size(g, loc, P);
-    const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz}, T[3] = {g.tx, g.ty, g.tz};
-    FView view = make_view(g, nullptr, loc);
-    // a side with a scheme (bottom / top of w) is skipped by the bounded fill; the fused kernel below has no such case
-    bool scheme_side = false;
-    for (int f = 0; bcs && f < n; ++f)
-        for (int sd = 0; sd < 6; ++sd) scheme_side = scheme_side || bcs[f][sd].kind == OCN_BC_OPEN_SCHEME;
-    // (Periodic | FullyConnected, Periodic, Bounded): bounded z fill + periodic y and x fills as one launch
-    if (!scheme_side && o.fused_halo && (T[0] == OCN_PERIODIC || T[0] == OCN_CONNECTED) && T[1] == OCN_PERIODIC && T[2] == OCN_BOUNDED &&
-        (T[0] == OCN_CONNECTED || N[0] >= H[0]) && N[1] >= H[1]) {
-        const bool face = loc[2] == OCN_FACE, zfill = !face || fill_open;
-        BcSides bc;
-        for (int f = 0; f < n; ++f)
-            for (int sd = 0; sd < 2; ++sd) {
-                bc.kind[f][sd] = bcs ? bcs[f][4 + sd].kind : OCN_BC_DEFAULT;
-                bc.value[f][sd] = bcs ? bcs[f][4 + sd].value : 0.0;
-                bc.arr[f][sd] = bcs ? bcs[f][4 + sd].array : nullptr;
-            }
-        bc.dlo = grid->h_dzf[g.Hz];
-        bc.dhi = grid->h_dzf[g.Nz + g.Hz];
-        const int H0 = T[0] == OCN_CONNECTED ? 0 : H[0], N0 = T[0] == OCN_CONNECTED ? P[0] : N[0];
-        const long total = (zfill ? (long)P[0] * P[1] * 2 : 0) + ((long)P[0] * (2 * H[1]) + (long)(2 * H0) * N[1]) * (P[2] - (zfill ? 2 : 0));
-        hipLaunchKernelGGL(fill_periodic_xy_bounded_z_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g_stream, fl, bc, P[0], P[1],
-                           P[2], N0, N[1], N[2], H0, H[1], H[2], face, zfill, T[0] == OCN_CONNECTED ? H[0] : 0, N[0],
-                           extend_x && T[0] == OCN_CONNECTED ? 1 : 0);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    // order: boundary_condition_ordering.jl:17-46 -- non-periodic first, then periodic; insertion sort with an
-    // always-true `lt` reverses same-class entries => z, y, x inside each class.
-    for (int d = 2; d >= 0; --d) {
-        const bool do_lo = wall_lo(T[d]), do_hi = wall_hi(T[d]);            // one wall only on Right / LeftConnected x, y
-        if (!do_lo && !do_hi) continue;
-        const bool face = loc[d] == OCN_FACE;
-        if (face && !fill_open) continue;
-        BcSides bc;
-        for (int f = 0; f < n; ++f)
-            for (int sd = 0; sd < 2; ++sd) {
-                bc.kind[f][sd] = bcs ? bcs[f][2 * d + sd].kind : OCN_BC_DEFAULT;
-                bc.value[f][sd] = bcs ? bcs[f][2 * d + sd].value : 0.0;
-                bc.arr[f][sd] = bcs ? bcs[f][2 * d + sd].array : nullptr;
-            }
-        // Δ at the boundary faces (flip(Center) = Face): Δxᶠ = Δx, Δyᶠ = Δy, Δzᶠ[1], Δzᶠ[N+1]
-        bc.dlo = d == 0 ? g.dx : (d == 1 ? g.dy : grid->h_dzf[g.Hz]);
-        bc.dhi = d == 0 ? g.dx : (d == 1 ? g.dy : grid->h_dzf[g.Nz + g.Hz]);
-        const int Na = d == 0 ? N[1] : N[0], Nb = d == 2 ? N[1] : N[2];
-        const long total = (long)Na * Nb;
-        const int nb = (int)((total + 255) / 256);
-        if (d == 0) hipLaunchKernelGGL(fill_bounded_kernel<0>, dim3(nb), dim3(256), 0, g_stream, fl, bc, view, Na, Nb, N[0], face, fill_open, do_lo, do_hi);
-        if (d == 1) hipLaunchKernelGGL(fill_bounded_kernel<1>, dim3(nb), dim3(256), 0, g_stream, fl, bc, view, Na, Nb, N[1], face, fill_open, do_lo, do_hi);
-        if (d == 2) {
-            // connected x sides of an x-slab rank's diffusivity fields: the first halo column takes the z fill too (see fill_bounded_kernel)
-            const int el = extend_x && (T[0] == OCN_CONNECTED || T[0] == OCN_LEFT_CONNECTED) ? 1 : 0;
-            const int eh = extend_x && (T[0] == OCN_CONNECTED || T[0] == OCN_RIGHT_CONNECTED) ? 1 : 0;
-            const int nbe = (int)(((long)(Na + el + eh) * Nb + 255) / 256);
-            hipLaunchKernelGGL(fill_bounded_kernel<2>, dim3(nbe), dim3(256), 0, g_stream, fl, bc, view, Na, Nb, N[2], face, fill_open, true, true, el, eh);
-        }
-    }
-    // triply periodic with N >= H everywhere: one launch writes every halo cell from its wrapped interior source
-    if (o.fused_halo && T[0] == OCN_PERIODIC && T[1] == OCN_PERIODIC && T[2] == OCN_PERIODIC && N[0] >= H[0] && N[1] >= H[1] && N[2] >= H[2]) {
-        const long total = (long)P[0] * P[1] * (2 * H[2]) + (long)P[0] * (2 * H[1]) * N[2] + (long)(2 * H[0]) * N[1] * N[2];
-        hipLaunchKernelGGL(fill_periodic_xyz_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g_stream, fl, P[0], P[1], P[2], N[0],
-                           N[1], N[2], H[0], H[1], H[2]);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    // an x-slab rank (x FullyConnected: its x halos come from the neighbours) with periodic y and z: the same kernel with no x slab
-    // -- H0 = 0, N0 = P0 makes every i its own source -- fills the y and z halos over the whole x extent in one launch
-    if (o.fused_halo && T[0] == OCN_CONNECTED && T[1] == OCN_PERIODIC && T[2] == OCN_PERIODIC && N[1] >= H[1] && N[2] >= H[2]) {
-        const long total = (long)P[0] * P[1] * (2 * H[2]) + (long)P[0] * (2 * H[1]) * N[2];
-        hipLaunchKernelGGL(fill_periodic_xyz_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, g_stream, fl, P[0], P[1], P[2], P[0],
-                           N[1], N[2], 0, H[1], H[2]);
-        KERNEL_CHECK();
-        return OCN_OK;
-    }
-    for (int d = 2; d >= 0; --d) {
-        if (T[d] != OCN_PERIODIC) continue;
-        const int Pa = d == 0 ? P[1] : P[0], Pb = d == 2 ? P[1] : P[2];
-        const long total = (long)2 * H[d] * Pa * Pb;
-        const int nb = (int)((total + 255) / 256);
-        if (d == 0) hipLaunchKernelGGL(fill_periodic_kernel<0>, dim3(nb), dim3(256), 0, g_stream, fl, P[0], P[1], P[2], N[0], H[0]);
-        if (d == 1) hipLaunchKernelGGL(fill_periodic_kernel<1>, dim3(nb), dim3(256), 0, g_stream, fl, P[0], P[1], P[2], N[1], H[1]);
-        if (d == 2) hipLaunchKernelGGL(fill_periodic_kernel<2>, dim3(nb), dim3(256), 0, g_stream, fl, P[0], P[1], P[2], N[2], H[2]);
-    }
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-// FieldBoundaryConditions validation: Bounded sides only; Flux / Value / Gradient on fields at Center along the boundary
-// direction, Open on the wall-normal (Face) component
-static int validate_bc(const DGrid &g, const int loc[3], int side, int kind) {
-    const int T[3] = {g.tx, g.ty, g.tz};
-    if (side < 0 || side > 5) return fail(OCN_EINVAL, "side %d out of range (0..5 = west, east, south, north, bottom, top)", side);
-    if (kind < OCN_BC_DEFAULT || kind > OCN_BC_OPEN) return fail(OCN_EINVAL, "unknown boundary condition kind %d", kind);
-    if (kind == OCN_BC_DEFAULT) return OCN_OK;
-    const int d = side / 2;
-    if (!((side & 1) ? wall_hi(T[d]) : wall_lo(T[d])))
-        return fail(OCN_EINVAL, "a non-default boundary condition needs a wall on that side (Bounded topology) in dimension %d", d);
-    if (kind == OCN_BC_OPEN ? loc[d] != OCN_FACE : loc[d] != OCN_CENTER)
-        return fail(OCN_EINVAL, "Flux/Value/Gradient conditions apply to fields at Center, Open to fields at Face along the boundary direction");
-    return OCN_OK;
-}
-
-// groups fields by identical location (identical parent shape) -> one set of launches per group
-static int fill_halo_regions(const OcnOptions &o, const ocn_grid_s *grid, double *const *fields, const int (*locs)[3], int nfields, bool fill_open,
-                             const ocn_bc_t (*bcs)[6] = nullptr, bool extend_x = false) {
-    const DGrid &g = grid->d;
-    if (nfields > OCN_MAX_FIELDS) return fail(OCN_EINVAL, "at most %d fields per call", OCN_MAX_FIELDS);
-    bool done[OCN_MAX_FIELDS] = {false};
-    for (int f = 0; f < nfields; ++f) {
-        if (done[f]) continue;
-        double *grp[OCN_MAX_FIELDS];
-        ocn_bc_t gbc[OCN_MAX_FIELDS][6];
-        int n = 0;
-        int P0[3], P1[3];
-        parent_size(g, locs[f], P0);
-        for (int h = f; h < nfields; ++h) {
-            if (done[h]) continue;
-            parent_size(g, locs[h], P1);
-            bool same = P0[0] == P1[0] && P0[1] == P1[1] && P0[2] == P1[2];
-            for (int d = 0; d < 3 && same; ++d) {
-                const int T[3] = {g.tx, g.ty, g.tz};
-                if ((wall_lo(T[d]) || wall_hi(T[d])) && locs[h][d] != locs[f][d]) same = false;
-            }
-            if (same) {
-                if (bcs) memcpy(gbc[n], bcs[h], sizeof(ocn_bc_t) * 6);
-                grp[n++] = fields[h];
-                done[h] = true;
-            }
-        }
-        int rc = fill_halo_group(o, grid, grp, n, locs[f], fill_open, bcs ? gbc : nullptr, extend_x);
-        if (rc) return rc;
-    }
-    return OCN_OK;
-}
+#include "ocn_boundary_conditions.h"   // the kernels and the launchers fill_halo_regions, validate_bc, compute_flux_bcs, compute_linear_flux_bc
 
 extern "C" int ocn_fill_halo_regions(ocn_grid_t grid, double *const *fields, const int (*locs)[3], int nfields, int fill_open_bcs) {
     NEED_INIT();
@@ -608,39 +466,6 @@ extern "C" int ocn_fill_halo_regions_bcs(ocn_grid_t grid, double *const *fields,
                 if (rc) return rc;
             }
     return fill_halo_regions(g_defaults, grid, fields, locs, nfields, fill_open_bcs != 0, bcs);
-}
-
-static int compute_flux_bcs(const DGrid &g, double *G, const int loc[3], const ocn_bc_t bcs[6]) {
-    const int N[3] = {g.Nx, g.Ny, g.Nz}, T[3] = {g.tx, g.ty, g.tz};
-    FView view = make_view(g, G, loc);
-    for (int d = 0; d < 3; ++d) {
-        const bool lo = wall_lo(T[d]) && bcs[2 * d].kind == OCN_BC_FLUX, hi = wall_hi(T[d]) && bcs[2 * d + 1].kind == OCN_BC_FLUX;
-        if (!lo && !hi) continue;
-        const int Na = d == 0 ? N[1] : N[0], Nb = d == 2 ? N[1] : N[2];
-        const int nb = (int)(((long)Na * Nb + 255) / 256);
-        const double flo = bcs[2 * d].value, fhi = bcs[2 * d + 1].value;
-        const double *alo = lo ? bcs[2 * d].array : nullptr, *ahi = hi ? bcs[2 * d + 1].array : nullptr;
-        if (d == 0) hipLaunchKernelGGL(flux_bc_kernel<0>, dim3(nb), dim3(256), 0, g_stream, g, view, Na, Nb, N[0], loc[0], loc[1], loc[2], lo, flo, hi, fhi, alo, ahi);
-        if (d == 1) hipLaunchKernelGGL(flux_bc_kernel<1>, dim3(nb), dim3(256), 0, g_stream, g, view, Na, Nb, N[1], loc[0], loc[1], loc[2], lo, flo, hi, fhi, alo, ahi);
-        if (d == 2) hipLaunchKernelGGL(flux_bc_kernel<2>, dim3(nb), dim3(256), 0, g_stream, g, view, Na, Nb, N[2], loc[0], loc[1], loc[2], lo, flo, hi, fhi, alo, ahi);
-    }
-    KERNEL_CHECK();
-    return OCN_OK;
-}
-
-static int compute_linear_flux_bc(const DGrid &g, double *G, const int loc[3], int side6, double a, double b, const double *dep) {
-    const int N[3] = {g.Nx, g.Ny, g.Nz}, T[3] = {g.tx, g.ty, g.tz};
-    const int d = side6 / 2, side = side6 % 2;
-    if (!(side ? wall_hi(T[d]) : wall_lo(T[d]))) return fail(OCN_EINVAL, "a Flux condition needs a wall on that side (Bounded direction)");
-    if (loc[d] != OCN_CENTER) return fail(OCN_EINVAL, "a Flux condition needs a field at Center along the boundary direction");
-    const FView vG = make_view(g, G, loc), vP = make_view(g, dep, loc);
-    const int Na = d == 0 ? N[1] : N[0], Nb = d == 2 ? N[1] : N[2];
-    const int nb = (int)(((long)Na * Nb + 255) / 256);
-    if (d == 0) hipLaunchKernelGGL(linear_flux_bc_kernel<0>, dim3(nb), dim3(256), 0, g_stream, g, vG, vP, Na, Nb, N[0], loc[2], side, a, b);
-    if (d == 1) hipLaunchKernelGGL(linear_flux_bc_kernel<1>, dim3(nb), dim3(256), 0, g_stream, g, vG, vP, Na, Nb, N[1], loc[2], side, a, b);
-    if (d == 2) hipLaunchKernelGGL(linear_flux_bc_kernel<2>, dim3(nb), dim3(256), 0, g_stream, g, vG, vP, Na, Nb, N[2], loc[2], side, a, b);
-    KERNEL_CHECK();
-    return OCN_OK;
 }
 
 extern "C" int ocn_compute_linear_flux_bc(ocn_grid_t grid, double *G, const int loc[3], int side, double a, double b, const double *dep) {
@@ -3769,10 +3594,7 @@ static bool periodic_dense_path(const ocn_model_s *m) {
     return !m->dm && !is_immersed(m->grid) && s && s->split && m->opt.split_solve && m->opt.real_fft && !s->general && g.tx == OCN_PERIODIC &&
            g.ty == OCN_PERIODIC && g.tz == OCN_PERIODIC;
 }
-static bool can_fold_halo_fill(const ocn_model_s *m) {                // N >= H: the fused fill's own condition
-    const DGrid &g = m->grid->d;
-    return periodic_dense_path(m) && m->opt.fused_halo && g.Nx >= g.Hx && g.Ny >= g.Hy && g.Nz >= g.Hz;
-}
+static bool can_fold_halo_fill(const ocn_model_s *m) { return periodic_dense_path(m) && m->opt.fused_halo; }
 static bool can_fuse_stage1_source(const ocn_model_s *m) { return periodic_dense_path(m) && m->opt.fuse_substep; }
 
 static int pressure_step(ocn_model_s *m, double dt, bool tendencies_follow = true, bool keep_p = true, const PendingSubstep *pending = nullptr,

@@ -44,6 +44,12 @@ struct FView {
 
 struct Range6 { int i0, i1, j0, j1, k0, k1; };
 
+// up to OCN_MAX_FIELDS fields of identical parent shape that one launch handles (halo fills, halo buffers, the folded pressure correction)
+struct FieldList {
+    double *p[OCN_MAX_FIELDS];
+    int n;
+};
+
 // ---------------------------------------------------------------------------------------------------------------------
 // WENO(order = 5) reconstruction -- src/Advection/weno_interpolants.jl
 // ---------------------------------------------------------------------------------------------------------------------
@@ -225,3 +231,19 @@ __device__ __forceinline__ double biased_interp_low(double s1, double s2, double
     if (B == 2 && (!bounded || outside_biased_halo(i, center, N, 2, lo, hi))) return weno3_biased(s1, s2, s3, s4, left);
     return left ? 1.0 * s2 : 1.0 * s3;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Flux boundary conditions (compute_flux_bcs.jl:57-163). Here and not in ocn_boundary_conditions.h because the tendency epilogues of
+// ocn_kernels.h apply the same term as the stand-alone kernels there.
+// ---------------------------------------------------------------------------------------------------------------------
+// G[1] += flux A / V (side 0), G[N] -= flux A / V (side 1) on a wall of direction d, for a field at z-location lz in level k:
+// V = Az Δz, A by direction (x, y regular at every location)
+__device__ __forceinline__ double add_flux_condition(const DGrid &g, int d, int lz, int k, int side, double flux, double G) {
+    const double dz = lz == 1 /* OCN_FACE */ ? g.dzf[k - 1 + g.Hz] : g.dzc[k - 1 + g.Hz];
+    const double vol = (g.dx * g.dy) * dz;
+    const double area = d == 0 ? g.dy * dz : (d == 1 ? g.dx * dz : g.dx * g.dy);
+    return side ? G - flux * area / vol : G + flux * area / vol;
+}
+// the linear field-dependent flux a + b φ (getbc of a ContinuousBoundaryFunction with field_dependencies = :φ,
+// continuous_boundary_function.jl:128-161); a = 0 leaves b φ without the addition, as the reference's function does
+__device__ __forceinline__ double linear_flux(double a, double b, double phi) { return a == 0.0 ? b * phi : a + b * phi; }

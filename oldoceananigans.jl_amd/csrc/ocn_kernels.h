@@ -1,4 +1,6 @@
 // ocn_kernels.h -- HIP kernels of the hot path (reference kernel inventory: SURVEY.md 2.1). gfx950 / wave64.
+// Families with a header of their own: the line FFTs (ocn_line_fft.h), the kernels around the pressure solve (ocn_pressure_step.h), the
+// halo fills, the Flux-condition kernels and the halo buffers of partitioned runs (ocn_boundary_conditions.h).
 #pragma once
 #include "ocn_device.h"
 #include "ocn_immersed.h"
@@ -1261,21 +1263,17 @@ struct EpilogueArgs {
 __device__ __forceinline__ double epilogue_flux_conditions(const DGrid &g, const EpilogueArgs &a, int f, int i, int j, int k, long q, double G) {
     if (a.any_flux) {
         // compute_x/y/z_bcs!: G[1] += flux A / V, G[N] -= flux A / V (x, then y, then z as the reference launches them)
-        const double dz = a.loc[f][2] == OCN_FACE ? g.dzf[k - 1 + g.Hz] : g.dzc[k - 1 + g.Hz];
-        const double vol = (g.dx * g.dy) * dz;
         const int N[3] = {g.Nx, g.Ny, g.Nz}, idx[3] = {i, j, k};
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            const double area = d == 0 ? g.dy * dz : (d == 1 ? g.dx * dz : g.dx * g.dy);
             // tangential point of the condition: (j, k) on west / east, (i, k) on south / north, (i, j) on bottom / top
             const long ab = d == 0 ? (long)(j - 1) + (long)g.Ny * (k - 1) : (d == 1 ? (long)(i - 1) + (long)g.Nx * (k - 1) : (long)(i - 1) + (long)g.Nx * (j - 1));
-            if (a.has_flux[f][2 * d] && idx[d] == 1) {
-                const double *fa = a.flux_arr[f][2 * d];
-                G += (fa ? fa[ab] : a.flux[f][2 * d]) * area / vol;
-            }
-            if (a.has_flux[f][2 * d + 1] && idx[d] == N[d]) {
-                const double *fa = a.flux_arr[f][2 * d + 1];
-                G -= (fa ? fa[ab] : a.flux[f][2 * d + 1]) * area / vol;
+#pragma unroll
+            for (int side = 0; side < 2; ++side) {
+                const int sd = 2 * d + side;
+                if (!a.has_flux[f][sd] || idx[d] != (side ? N[d] : 1)) continue;
+                const double *fa = a.flux_arr[f][sd];
+                G = add_flux_condition(g, d, a.loc[f][2], k, side, fa ? fa[ab] : a.flux[f][sd], G);
             }
         }
     }
@@ -1285,14 +1283,8 @@ __device__ __forceinline__ double epilogue_flux_conditions(const DGrid &g, const
         const int idxd = d == 0 ? i : (d == 1 ? j : k), Nd = d == 0 ? g.Nx : (d == 1 ? g.Ny : g.Nz);
         if (idxd != ((sd & 1) ? Nd : 1)) continue;
         const double *dp = dep == 0 ? a.u.p : (dep == 1 ? a.v.p : (dep == 2 ? a.w.p : a.c[dep - 3].p));
-        const double dz = a.loc[f][2] == OCN_FACE ? g.dzf[k - 1 + g.Hz] : g.dzc[k - 1 + g.Hz];
-        const double vol = (g.dx * g.dy) * dz;
-        const double area = d == 0 ? g.dy * dz : (d == 1 ? g.dx * dz : g.dx * g.dy);
-        const double phi = dp[q];                      // the dependency sits at the location of the field: same parent index
-        const double a_ = a.lin[n].a, b_ = a.lin[n].b;
-        const double flux = a_ == 0.0 ? b_ * phi : a_ + b_ * phi;
-        if (sd & 1) G -= flux * area / vol;
-        else        G += flux * area / vol;
+        // the dependency sits at the location of the field: same parent index
+        G = add_flux_condition(g, d, a.loc[f][2], k, sd & 1, linear_flux(a.lin[n].a, a.lin[n].b, dp[q]), G);
     }
     return G;
 }
@@ -1362,235 +1354,6 @@ __global__ void __launch_bounds__(256) tendency_epilogue_kernel(DGrid g, typenam
         else            Uv += a.dt * a.gamma * G;
         a.Un[f][q] = Uv;
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// halo fills (src/BoundaryConditions). One launch handles up to OCN_MAX_FIELDS fields of identical parent shape.
-// ---------------------------------------------------------------------------------------------------------------------
-struct FieldList {
-    double *p[OCN_MAX_FIELDS];
-    int n;
-};
-
-// _fill_periodic_*_halo! (fill_halo_regions_periodic.jl:5-33) along dimension D of parent arrays of shape (P0,P1,P2):
-// parent[i] = parent[N+i], parent[N+H+i] = parent[H+i] for i = 1..H, over the whole extent of the two other dims.
-template <int D>
-__global__ void __launch_bounds__(256) fill_periodic_kernel(FieldList fl, int P0, int P1, int P2, int N, int H) {
-    // thread -> (h, a, b): h in [0, 2H) fastest when D == 0 so that accesses stay contiguous in x
-    long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int Pa = D == 0 ? P1 : P0;            // first remaining dim
-    const int Pb = D == 2 ? P1 : P2;            // second remaining dim
-    long total = (long)2 * H * Pa * Pb;
-    if (t >= total) return;
-    int h, a, b;
-    if (D == 0) { h = t % (2 * H); long r = t / (2 * H); a = r % Pa; b = r / Pa; }
-    else        { a = t % Pa; long r = t / Pa; if (D == 1) { h = r % (2 * H); b = r / (2 * H); } else { b = r % Pb; h = r / Pb; } }
-    int dst = h < H ? h : N + h;                // 0-based parent index: west i-1 (i=1..H) | east N+H+i-1
-    int src = h < H ? N + h : h;                //                       N+i-1            | H+i-1  (h-H+H)
-    long s0 = 1, s1 = P0, s2 = (long)P0 * P1;
-    long od, os;
-    if (D == 0) { od = dst * s0 + a * s1 + b * s2; os = src * s0 + a * s1 + b * s2; }
-    else if (D == 1) { od = a * s0 + dst * s1 + b * s2; os = a * s0 + src * s1 + b * s2; }
-    else { od = a * s0 + b * s1 + dst * s2; os = a * s0 + b * s1 + src * s2; }
-    for (int f = 0; f < fl.n; ++f) fl.p[f][od] = fl.p[f][os];
-}
-
-// Triply periodic grids: the three directional fills in ONE launch. Filling z, then y, then x over the whole parent extent
-// (the reference's order) leaves every halo cell -- edges and corners included -- equal to the interior cell at the wrapped
-// index in each direction, so each halo cell can be written directly from that interior cell: same bits, a third of the
-// launches, and the x halos are no longer a separate uncoalesced pass. Thread -> one halo cell of the (P0, P1, P2) parent.
-__global__ void __launch_bounds__(256) fill_periodic_xyz_kernel(FieldList fl, int P0, int P1, int P2, int N0, int N1, int N2, int H0,
-                                                                int H1, int H2) {
-    // halo cells are enumerated as three slabs: all (i, j) of the 2*H2 halo planes; then, for interior k, the 2*H1 halo rows;
-    // then, for interior (j, k), the 2*H0 halo columns
-    const long nz = (long)P0 * P1 * (2 * H2), ny = (long)P0 * (2 * H1) * N2, nx = (long)(2 * H0) * N1 * N2;
-    long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    int i, j, k;
-    if (t < nz) {
-        i = t % P0; const long r = t / P0; j = r % P1; const int hz = r / P1;
-        k = hz < H2 ? hz : N2 + hz;
-    } else if ((t -= nz) < ny) {
-        i = t % P0; const long r = t / P0; const int hy = r % (2 * H1);
-        j = hy < H1 ? hy : N1 + hy;
-        k = H2 + (int)(r / (2 * H1));
-    } else if ((t -= ny) < nx) {
-        const int hx = t % (2 * H0); const long r = t / (2 * H0);
-        i = hx < H0 ? hx : N0 + hx;
-        j = H1 + (int)(r % N1);
-        k = H2 + (int)(r / N1);
-    } else return;
-    // wrapped interior source (0-based parent indices; interior is [H, H + N))
-    const int si = i < H0 ? i + N0 : (i >= H0 + N0 ? i - N0 : i);
-    const int sj = j < H1 ? j + N1 : (j >= H1 + N1 ? j - N1 : j);
-    const int sk = k < H2 ? k + N2 : (k >= H2 + N2 ? k - N2 : k);
-    const long od = i + (long)P0 * (j + (long)P1 * k), os = si + (long)P0 * (sj + (long)P1 * sk);
-    for (int f = 0; f < fl.n; ++f) fl.p[f][od] = fl.p[f][os];
-}
-
-// Bounded directions, ONE halo cell (fill_halo_kernels.jl:69-70), launched over the INTERIOR extent (grid N) of the two
-// other dims. Center fields: Flux / default -> mirror (fill_halo_regions_flux.jl:9-27); Value / Gradient -> linear
-// extrapolation through the boundary face (fill_halo_regions_value_gradient.jl:7-119). Face fields: Open wall value
-// (fill_halo_regions_open.jl:2-7; impenetrable = 0), skipped when fill_open_bcs = false.
-#define OCN_BC_OPEN_SCHEME 5          // internal: an Open side that carries a scheme (ocn_open_boundary.h); never crosses the C ABI
-struct BcSides {
-    int kind[OCN_MAX_FIELDS][2];      // [field][lo | hi], OCN_BC_*
-    double value[OCN_MAX_FIELDS][2];
-    const double *arr[OCN_MAX_FIELDS][2];   // array-valued condition (getbc(::AbstractArray, i, j), boundary_condition.jl:164) or null
-    double dlo, dhi;                  // spacing at the boundary faces (Δ between the first interior and the first halo point)
-    // the condition at tangential interior point (a, b) (1-based) of a dense (Na, .) array, or the number
-    __device__ __forceinline__ double get(int f, int side, long ab) const {
-        const double *p = arr[f][side];
-        return p ? p[ab] : value[f][side];
-    }
-};
-
-// ea_lo / ea_hi (z fill of an x-slab rank's DIFFUSIVITY fields only): also fill the first halo column on a connected x side -- the rank
-// evaluates the eddy diffusivities at i = 0 / Nx + 1 itself, and a serial Periodic run's x fill copies the z-filled value into those
-// cells (the closure's corner interpolations at the rank edge read them); an array-valued condition is read at the nearest interior point
-template <int D>
-__global__ void __launch_bounds__(256) fill_bounded_kernel(FieldList fl, BcSides bc, FView view, int Na, int Nb, int N, bool face,
-                                                           bool fill_open, bool do_lo = true, bool do_hi = true, int ea_lo = 0, int ea_hi = 0) {   // one-sided: Left / RightConnected x
-    long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int Nae = Na + ea_lo + ea_hi;
-    if (t >= (long)Nae * Nb) return;
-    int a = 1 - ea_lo + t % Nae, b = 1 + t / Nae;
-    long lo, ilo, hi, ihi;
-    if (D == 0) { lo = view.lin(face ? 1 : 0, a, b); ilo = view.lin(1, a, b); hi = view.lin(N + 1, a, b); ihi = view.lin(N, a, b); }
-    else if (D == 1) { lo = view.lin(a, face ? 1 : 0, b); ilo = view.lin(a, 1, b); hi = view.lin(a, N + 1, b); ihi = view.lin(a, N, b); }
-    else { lo = view.lin(a, b, face ? 1 : 0); ilo = view.lin(a, b, 1); hi = view.lin(a, b, N + 1); ihi = view.lin(a, b, N); }
-    const long ab = (long)(min(max(a, 1), Na) - 1) + (long)Na * (b - 1);
-    for (int f = 0; f < fl.n; ++f) {
-        double *p = fl.p[f];
-        if (!face) {
-            const double c1 = p[ilo], cN = p[ihi];
-            const int kl = bc.kind[f][0], kh = bc.kind[f][1];
-            double h0 = c1, h1 = cN;
-            if (kl == OCN_BC_VALUE) h0 = c1 + ((c1 - bc.get(f, 0, ab)) / (bc.dlo / 2)) * (-bc.dlo);
-            else if (kl == OCN_BC_GRADIENT) h0 = c1 + bc.get(f, 0, ab) * (-bc.dlo);
-            if (kh == OCN_BC_VALUE) h1 = cN + ((bc.get(f, 1, ab) - cN) / (bc.dhi / 2)) * bc.dhi;
-            else if (kh == OCN_BC_GRADIENT) h1 = cN + bc.get(f, 1, ab) * bc.dhi;
-            if (do_lo) p[lo] = h0;
-            if (do_hi) p[hi] = h1;
-        } else if (fill_open) {
-            // a side with a scheme is left alone: its boundary value is the scheme's state, stepped by open_boundary_step_kernel
-            if (do_lo && bc.kind[f][0] != OCN_BC_OPEN_SCHEME) p[lo] = bc.kind[f][0] == OCN_BC_OPEN ? bc.get(f, 0, ab) : 0.0;
-            if (do_hi && bc.kind[f][1] != OCN_BC_OPEN_SCHEME) p[hi] = bc.kind[f][1] == OCN_BC_OPEN ? bc.get(f, 1, ab) : 0.0;
-        }
-    }
-}
-
-// (Periodic | FullyConnected, Periodic, Bounded) grids: the bounded z fill and the periodic y and x fills in ONE launch. The reference
-// fills z first (one halo cell below and above, over the interior (i, j) only), then y, then x over the whole extent of the other
-// dimensions (boundary_condition_ordering.jl:17-46), which leaves
-//   * the two z-boundary planes (Center fields: k = 0 and N+1; Face fields: the wall planes k = 1 and N+1) holding, at EVERY (i, j) of
-//     the parent, the boundary formula evaluated in the column at the wrapped interior (i, j);
-//   * every other plane -- the deeper z halos included, whose interior (i, j) nobody writes -- holding in its x / y halo cells the
-//     value of the wrapped interior (i, j) of the same plane.
-// Each such cell is written here directly from those sources: same bits, a third of the launches. `zfill`: the z fill runs (Center
-// fields always; Face fields when fill_open_bcs). An x-slab rank (x halos owned by the neighbours) passes H0 = 0, N0 = P0 and XC = Hx:
-// its XC outermost columns are left to the exchange -- in the z-boundary planes they only take part in the periodic y copy.
-// XZ (diffusivity fields of an x-slab rank, see fill_bounded_kernel): the innermost XZ of the XC neighbour columns take the z formula too.
-__global__ void __launch_bounds__(256) fill_periodic_xy_bounded_z_kernel(FieldList fl, BcSides bc, int P0, int P1, int P2, int N0, int N1,
-                                                                         int N2, int H0, int H1, int H2, bool face, bool zfill, int XC,
-                                                                         int NA, int XZ = 0) {
-    const int klo = face ? H2 : H2 - 1, khi = N2 + H2;                       // 0-based parent planes of the z fill
-    const long nA = zfill ? (long)P0 * P1 * 2 : 0;
-    const int nplanes = P2 - (zfill ? 2 : 0);
-    const long rowsB = (long)P0 * (2 * H1), colsB = (long)(2 * H0) * N1, perplane = rowsB + colsB;
-    long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < nA) {
-        const int i = t % P0; const long r = t / P0; const int j = r % P1; const int side = r / P1;
-        const int si = i < H0 ? i + N0 : (i >= H0 + N0 ? i - N0 : i);
-        const int sj = j < H1 ? j + N1 : (j >= H1 + N1 ? j - N1 : j);
-        const long col = si + (long)P0 * sj, plane = (long)P0 * P1;
-        const long od = i + (long)P0 * j + plane * (side ? khi : klo);
-        if (i < XC - XZ || i >= P0 - XC + XZ) {                             // a neighbour's column: periodic y copy only
-            if (sj == j) return;
-            const long os = col + plane * (side ? khi : klo);
-            for (int f = 0; f < fl.n; ++f) fl.p[f][od] = fl.p[f][os];
-            return;
-        }
-        const long ab = (long)min(max(si - H0 - XC, 0), NA - 1) + (long)NA * (sj - H1);      // tangential interior point (i, j) of the source column
-        for (int f = 0; f < fl.n; ++f) {
-            double *p = fl.p[f];
-            double val;
-            if (face) val = bc.kind[f][side] == OCN_BC_OPEN ? bc.get(f, side, ab) : 0.0;
-            else {
-                const double c = p[col + plane * (side ? N2 + H2 - 1 : H2)];         // first / last interior cell of the column
-                const int kd = bc.kind[f][side];
-                val = c;
-                if (side == 0) {
-                    if (kd == OCN_BC_VALUE) val = c + ((c - bc.get(f, 0, ab)) / (bc.dlo / 2)) * (-bc.dlo);
-                    else if (kd == OCN_BC_GRADIENT) val = c + bc.get(f, 0, ab) * (-bc.dlo);
-                } else {
-                    if (kd == OCN_BC_VALUE) val = c + ((bc.get(f, 1, ab) - c) / (bc.dhi / 2)) * bc.dhi;
-                    else if (kd == OCN_BC_GRADIENT) val = c + bc.get(f, 1, ab) * bc.dhi;
-                }
-            }
-            p[od] = val;
-        }
-        return;
-    }
-    t -= nA;
-    if (t >= perplane * nplanes) return;
-    int kp = (int)(t / perplane);
-    if (zfill) { if (kp >= klo) ++kp; if (kp >= khi) ++kp; }
-    long q = t % perplane;
-    int i, j;
-    if (q < rowsB) { i = q % P0; const int hy = q / P0; j = hy < H1 ? hy : N1 + hy; }
-    else { q -= rowsB; const int hx = q % (2 * H0); i = hx < H0 ? hx : N0 + hx; j = H1 + (int)(q / (2 * H0)); }
-    const int si = i < H0 ? i + N0 : (i >= H0 + N0 ? i - N0 : i);
-    const int sj = j < H1 ? j + N1 : (j >= H1 + N1 ? j - N1 : j);
-    const long plane = (long)P0 * P1 * kp;
-    const long od = i + (long)P0 * j + plane, os = si + (long)P0 * sj + plane;
-    for (int f = 0; f < fl.n; ++f) fl.p[f][od] = fl.p[f][os];
-}
-
-// compute_x/y/z_bcs! (compute_flux_bcs.jl:57-163): G[1] += flux * A / V, G[N] -= flux * A / V over the interior extent of
-// the two other dims. area / volume evaluated per cell by the caller-provided metric look-ups.
-template <int D>
-__global__ void __launch_bounds__(256) flux_bc_kernel(DGrid g, FView G, int Na, int Nb, int N, int lx, int ly, int lz, bool has_lo,
-                                                      double flo, bool has_hi, double fhi, const double *alo, const double *ahi) {
-    long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)Na * Nb) return;
-    const int a = 1 + t % Na, b = 1 + t / Na;
-    for (int side = 0; side < 2; ++side) {
-        if (side == 0 ? !has_lo : !has_hi) continue;
-        const int n = side ? N : 1;
-        const int i = D == 0 ? n : a, j = D == 1 ? n : (D == 0 ? a : b), k = D == 2 ? n : b;
-        const double dx = g.dx, dy = g.dy;          // regular in x, y at every location
-        const double dz = lz == OCN_FACE ? g.dzf[k - 1 + g.Hz] : g.dzc[k - 1 + g.Hz];
-        const double vol = (dx * dy) * dz;          // volume = Az * Δz
-        const double area = D == 0 ? dy * dz : (D == 1 ? dx * dz : dx * dy);
-        const double *arr = side ? ahi : alo;
-        const double flux = arr ? arr[(long)(a - 1) + (long)Na * (b - 1)] : (side ? fhi : flo);
-        double &Gq = G.at(i, j, k);
-        if (side) Gq -= flux * area / vol;
-        else      Gq += flux * area / vol;
-    }
-    (void)lx; (void)ly;
-}
-
-// One side of a field-dependent Flux condition of the linear family: flux = a + b φ[i, j, k_boundary] (getbc of a
-// ContinuousBoundaryFunction with field_dependencies = :φ, continuous_boundary_function.jl:128-161; φ at the location of the field that
-// carries the condition => identity interpolation), applied like the valued Flux above.
-template <int D>
-__global__ void __launch_bounds__(256) linear_flux_bc_kernel(DGrid g, FView G, FView P, int Na, int Nb, int N, int lz, int side, double a_,
-                                                             double b_) {
-    long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)Na * Nb) return;
-    const int a = 1 + t % Na, b = 1 + t / Na;
-    const int n = side ? N : 1;
-    const int i = D == 0 ? n : a, j = D == 1 ? n : (D == 0 ? a : b), k = D == 2 ? n : b;
-    const double dx = g.dx, dy = g.dy;
-    const double dz = lz == OCN_FACE ? g.dzf[k - 1 + g.Hz] : g.dzc[k - 1 + g.Hz];
-    const double vol = (dx * dy) * dz;
-    const double area = D == 0 ? dy * dz : (D == 1 ? dx * dz : dx * dy);
-    const double phi = P.at(i, j, k);
-    const double flux = a_ == 0.0 ? b_ * phi : a_ + b_ * phi;
-    double &Gq = G.at(i, j, k);
-    if (side) Gq -= flux * area / vol;
-    else      Gq += flux * area / vol;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2444,89 +2207,8 @@ __global__ void __launch_bounds__(256) rcp64_check_kernel(unsigned long long n, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// distributed x-slab support (src/DistributedComputations)
+// distributed pressure solve (src/DistributedComputations)
 // ---------------------------------------------------------------------------------------------------------------------
-// fill_send_buffers! / recv_from_buffers! for a 1-D x partition (communication_buffers.jl:281-313): the west / east
-// buffers hold Hx x Py x Pz slabs -- the whole parent extent in y and z, so corners ride along (:53,71-76).
-// PACK: west_send <- parent[Hx .. 2Hx), east_send <- parent[Nx .. Nx+Hx);  UNPACK: parent[0 .. Hx) <- west_recv,
-// parent[Nx+Hx .. Nx+2Hx) <- east_recv. Buffers are field-major; field f (its own Py x Pz: Face fields on Bounded
-// dimensions have one more plane) starts at off[f] and holds rows[f] = Py*Pz rows of Hx values.
-struct SlabList {
-    long off[OCN_MAX_FIELDS];
-    long rows[OCN_MAX_FIELDS];
-    int p0[OCN_MAX_FIELDS];                    // parent extent in x of each field
-};
-template <bool PACK>
-__global__ void __launch_bounds__(256) x_halo_buffer_kernel(FieldList fl, SlabList sl, int N, int HX, int H, double *west, double *east,
-                                                            bool do_west, bool do_east) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int h = t % H;
-    const long r = t / H;                      // j + P1 * k
-    for (int f = 0; f < fl.n; ++f) {
-        if (r >= sl.rows[f]) continue;
-        double *p = fl.p[f];
-        const long row = r * sl.p0[f];
-        const long b = sl.off[f] + t;
-        // H = exchanged depth (<= Hx = HX): the depth interior columns next to each side <-> the depth halo columns nearest to it
-        if (PACK) {
-            west[b] = p[row + HX + h];
-            east[b] = p[row + HX + N - H + h];
-        } else {
-            if (do_west) p[row + HX - H + h] = west[b];
-            if (do_east) p[row + N + HX + h] = east[b];
-        }
-    }
-}
-
-// fill_send_buffers! of x_halo_buffer_kernel<true> with the y / z halo rows read at their WRAPPED interior source (y, z Periodic, every
-// field with parent extents (Px, Ny + 2Hy, Nz + 2Hz)): what the buffers would hold after a local fill of the packed columns
-__global__ void __launch_bounds__(256) x_halo_pack_wrapped_kernel(FieldList fl, SlabList sl, int N, int HX, int H, int Ny, int Hy, int Nz, int Hz,
-                                                                  double *west, double *east) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int h = t % H;
-    const long r = t / H;                      // j + P1 * k over the parent extents
-    const int P1 = Ny + 2 * Hy;
-    const int jp = (int)(r % P1), kp = (int)(r / P1);
-    if (kp >= Nz + 2 * Hz) return;
-    const int js = Hy + ((jp - Hy) % Ny + Ny) % Ny, ks = Hz + ((kp - Hz) % Nz + Nz) % Nz;
-    for (int f = 0; f < fl.n; ++f) {
-        const double *p = fl.p[f];
-        const long row = ((long)js + (long)P1 * ks) * sl.p0[f];
-        const long b = sl.off[f] + t;
-        west[b] = p[row + HX + h];
-        east[b] = p[row + HX + N - H + h];
-    }
-}
-
-// the same along y for pencil partitions: the south / north buffers hold Hy rows of the WHOLE parent extent in x and z, so the x halos
-// just received -- the corners of halo_communication.jl:137-162 -- ride along on the second hop
-struct RowList {
-    long off[OCN_MAX_FIELDS];
-    int p0[OCN_MAX_FIELDS], p1[OCN_MAX_FIELDS], p2[OCN_MAX_FIELDS];
-};
-template <bool PACK>
-__global__ void __launch_bounds__(256) y_halo_buffer_kernel(FieldList fl, RowList rl, int N, int HY, int H, double *south, double *north,
-                                                            bool do_south, bool do_north) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int f = 0; f < fl.n; ++f) {
-        const int p0 = rl.p0[f];
-        const long per = (long)p0 * H;
-        if (t >= per * rl.p2[f]) continue;
-        const int i = t % p0, h = (t / p0) % H;
-        const long k = t / per;
-        double *p = fl.p[f];
-        const long base = i + (long)p0 * (long)rl.p1[f] * k;
-        const long b = rl.off[f] + t;
-        if (PACK) {
-            south[b] = p[base + (long)p0 * (HY + h)];
-            north[b] = p[base + (long)p0 * (HY + N - H + h)];
-        } else {
-            if (do_south) p[base + (long)p0 * (HY - H + h)] = south[b];
-            if (do_north) p[base + (long)p0 * (N + HY + h)] = north[b];
-        }
-    }
-}
-
 // transpose staging for the distributed FFT (distributed_transpose.jl:25-95), x-slab partition over R ranks:
 //   y->x pack : zfield (Nxl, Ny, Nz)   -> send chunk d = { (i, jl, k) : j = d*Nyl + jl },  chunk-major
 //   y->x unpack: recv chunk s          -> xfield (Nxg, Nyl, Nz) at i_g = s*Nxl + i

@@ -24,8 +24,9 @@ struct OcnOptions {
     int amd_march = 1;                 // eddy diffusivities by the z-marching kernel that shares the point operands (0: one thread per cell, everything recomputed)
     int smag_march = 1;                // Smagorinsky eddy viscosity by its z-marching kernel (0: one thread per cell, every point value recomputed)
     // halo fills
-    int fused_halo = 1;                // triply periodic grids: the three directional periodic fills as one launch; inside a time-step they
-                                       // ride in the pressure-correction kernel (pressure_step, fold_halos)
+    int fused_halo = 1;                // the periodic fills of all Periodic directions as one launch, with the bounded z fill on (P, P, B) grids
+                                       // (0: one launch per direction, z, y, x); inside a time-step on a triply periodic grid they ride in
+                                       // the pressure-correction kernel (pressure_step, fold_halos)
     // pressure solve
     int real_fft = 1;                  // D2Z / Z2D transforms (0: the reference's complex-to-complex)
     int c2r_strided = 1;               // Z2D straight into the interior of the haloed pressure field

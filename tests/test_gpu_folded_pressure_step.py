@@ -133,7 +133,7 @@ def test_three_steps_against_the_oracle(ocn, oracle, arch, size, ntr):
 
 @pytest.mark.parametrize("size,ntr", CASES, ids=_ids)
 def test_bit_identical_to_the_separate_kernels(ocn, arch, size, ntr):
-    """fused_halo = 0, fuse_substep = 0: fill_periodic_kernel x 3 per fill, rk3_substep_kernel + source_term_kernel, the plain correction
+    """fused_halo = 0, fuse_substep = 0: fill_periodic_xyz_kernel x 3 per fill, rk3_substep_kernel + source_term_kernel, the plain correction
     kernel. Whole parent arrays after 1 and 3 steps"""
     got, want = _folded(ocn, arch, size, ntr), _separate(ocn, arch, size, ntr)
     for a, b, tag in zip(got[:2], want[:2], ("1 step", "3 steps")):
