@@ -3,8 +3,9 @@ nonhydrostatic_tendency_kernel_functions.jl:81-93).
 
   * tendency identity, bitwise: after update_state!, G of a forced model == G of the same model without forcing + F, F evaluated in
     numpy from the same tables and arrays (forcings.evaluate), on the role-kernel, per-value epilogue (FPlane), marching epilogue
-    (ScalarDiffusivity) and per-field kernel ((Bounded, Periodic, Bounded)) configurations, and with the standalone pass forced;
-  * the two forcing-path options give `==` fields after RK3 steps;
+    (ScalarDiffusivity) and per-field kernel ((Bounded, Periodic, Bounded)) configurations, and with the standalone pass forced; the
+    first and the last of these also at sizes of several 64 x 7 tiles of the role kernel;
+  * the two forcing-path options give `==` fields after RK3 steps, also across tile seams;
   * known answers: T ≡ 1 relaxed to 0 at rate 1/τ follows the RK3 stability polynomial / the AB2 recurrence;
   * test/test_forcings.jl's relaxed_time_stepping, two_forcings and seven_forcings, adapted to closure-free forcings;
   * a borrowed Field forcing acts with the value it has when the tendency is evaluated;
@@ -101,10 +102,14 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
-def test_tendency_identity_bitwise(ocn, arch, case):
+# Sizes around the 64 x 7 tiles of the role kernel (those of test_gpu_parity.test_tile_edges_of_the_tendency_kernels that a second x tile,
+# a row tile ending on the range's last row or a live edge wave need): in a second tile the FORCE branch's clamped index
+# (min(i, i1), min(j, j1), max(k - 1, k0)) and the tables of a Relaxation, indexed i - 1 + Hx, start at i0 = 65, 129.
+TILE_SIZES = [(65, 8, 6), (129, 15, 5), (64, 7, 7), (130, 6, 9)]
+
+
+def _identity(ocn, arch, case, size):
     _, topology, physics, options, path = case
-    size = (16, 12, 10)
     topo = tuple(ocn.Periodic if t == "P" else ocn.Bounded for t in topology)
     z = tanh_faces(size[2]) if topology[2] == "B" else (-1.0, 0.0)
     kw = dict(size=size, x=(0.0, 1.0), y=(0.0, 1.0), z=z, topology=topo)
@@ -122,23 +127,55 @@ def test_tendency_identity_bitwise(ocn, arch, case):
     # the role-kernel path keeps the RK3 substep riding in the tendency launch; the standalone pass runs it separately
     assert forced.get_option("fuse_substep_active") == plain.get_option("fuse_substep_active") * (path == 1)
     _check_identity(ocn, plain, forced)
+    return forced
 
 
-def test_role_kernel_and_standalone_forcing_agree_over_rk3_steps(ocn, arch):
-    """forcing inside the role kernel with the fused RK3 substep (path 1) == the standalone pass with separate substeps (path 3)"""
-    size = (16, 16, 16)
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_tendency_identity_bitwise(ocn, arch, case):
+    _identity(ocn, arch, case, (16, 12, 10))
+
+
+@pytest.mark.parametrize("size", TILE_SIZES, ids=["x".join(map(str, s)) for s in TILE_SIZES])
+@pytest.mark.parametrize("case", CASES[:2], ids=[c[0] for c in CASES[:2]])
+def test_tendency_identity_bitwise_across_tile_edges(ocn, arch, case, size):
+    """the identity in and after a role kernel of several tiles: forcing_sum of the in-kernel path evaluates cells of a second and third
+    x tile, of a row tile whose last row is the range's, and beside a live edge-wave column; the x masks of _forcing_set (Gaussians at 0.5
+    and 0.1, piecewise linear at 0.7) differ from column 64 to column 65, so a table read one tile or one column off is seen"""
+    forced = _identity(ocn, arch, case, size)
+    Hx = forced.grid.halo_size[0]
+    tables = [t.mask_table for terms in forced._forcing_terms.values() for t in terms if t.kind == 2 and t.mask_dir == 0]
+    assert len(tables) == 3
+    for table in tables:
+        assert table[64 - 1 + Hx] != table[65 - 1 + Hx] and table[64 - 1 + Hx] != 0.0
+
+
+def _fused_and_standalone_steps(ocn, arch, size, substep_rides=False):
     fields = []
     for fused in (1, 0):
         grid = ocn.RectilinearGrid(arch, size=size, extent=(1, 1, 1))
         m = ocn.NonhydrostaticModel(grid=grid, tracers=("T", "S"), forcing=_forcing_set(ocn, size, np.random.default_rng(5)))
         m.set_option("fused_forcing", fused)
         assert m.get_option("forcing_path") == (1 if fused else 3)
+        assert not substep_rides or m.get_option("fuse_substep_active") == fused
         ocn.set_model(m, **_state(ocn, grid, m))
         for _ in range(3):
-            ocn.time_step(m, 0.01)
+            ocn.time_step(m, min(0.01, 0.1 * grid.Δxᶜᵃᵃ / 0.6))
         fields.append({n: f.parent() for n, f in m.fields().items()})
     for n in fields[0]:
         assert np.array_equal(fields[0][n], fields[1][n]), n
+        assert np.all(np.isfinite(fields[0][n])) and np.abs(fields[0][n]).max() > 0
+
+
+def test_role_kernel_and_standalone_forcing_agree_over_rk3_steps(ocn, arch):
+    """forcing inside the role kernel with the fused RK3 substep (path 1) == the standalone pass with separate substeps (path 3)"""
+    _fused_and_standalone_steps(ocn, arch, (16, 16, 16))
+
+
+@pytest.mark.parametrize("size", TILE_SIZES[:2], ids=["x".join(map(str, s)) for s in TILE_SIZES[:2]])
+def test_role_kernel_and_standalone_forcing_agree_across_tile_edges(ocn, arch, size):
+    """the same 3 RK3 steps at 65 x 8 x 6 and 129 x 15 x 5: the forcing term together with the substep that rides in the kernel, across
+    the seams of its 64 x 7 tiles"""
+    _fused_and_standalone_steps(ocn, arch, size, substep_rides=True)
 
 
 def test_flux_condition_lands_after_forcing(ocn, arch):

@@ -14,7 +14,12 @@ tests/test_immersed_host.py), on the grids of tests/immersed_cases.py:
   7. the answers of the new entry points.
 
 Path 2 (the flux-sharing role kernel) serves G1, G4 and G5 -- periodic in x and y, no Flat direction -- and is what their models take
-by default; tendency_impl = 0 forces path 1 (one field per launch), the only path of G2 and G3."""
+by default; tendency_impl = 0 forces path 1 (one field per launch), the only path of G2 and G3.
+
+G1 .. G5 are one partial tile of that kernel (64 x 7 cells, an eighth wave for the flux lines of row j0 + 7 and column i0 + 64). The
+tile-edge cases T1 .. T6 of tests/immersed_cases.py put immersed cells on both sides of every tile seam and run, on path 2: the tables;
+the raw entry on random arrays (beside path 1), over trimmed ranges and at every chunk length; the model's tendencies without and with
+the closure; path 2 against path 1 over 2 steps; one step against the yardstick on T1."""
 import ctypes as C
 import warnings
 
@@ -48,8 +53,17 @@ def _restatement(ocn, case, boundary=None):
     if key not in _shared:
         grid = IC.underlying_grid(ocn, None, case)
         m = R.Metrics.of_grid(grid)
-        _shared[key] = IR.Immersed(m, IR.cells_of_grid(grid, IC.CASES[case]["boundary"] if boundary is None else boundary, m)[0])
+        _shared[key] = IR.Immersed(m, IR.cells_of_grid(grid, IC.case_of(case)["boundary"] if boundary is None else boundary, m)[0])
     return _shared[key]
+
+
+@pytest.fixture
+def role_kchunk(ocn):
+    """sets the library default of role_kchunk (what the raw entry points read) and restores it"""
+    def set_(v):
+        ocn.set_option("role_kchunk", v)
+    yield set_
+    ocn.set_option("role_kchunk", 0)
 
 
 def _model(ocn, grid, **kw):
@@ -88,6 +102,16 @@ def test_flag_tables_are_the_restatement(ocn, arch, case):
         assert set(np.unique((_core(imm.m, orders) >> (2 * (4 + side))) & 3)) == {1, 2, 3}
 
 
+@pytest.mark.parametrize("case", list(IC.TILE_CASES))
+def test_tile_flag_tables_are_the_restatement(ocn, arch, case):
+    """the two tables on the tile-edge cases, halo entries included: the edge wave of the flux-sharing kernel reads column Nx + 1 and row
+    Ny + 1 (what the cases hold at the seams: tests/test_immersed_host.py::test_tile_cases_hold_what_they_promise)"""
+    imm = _restatement(ocn, case)
+    periphery, orders = IC.immersed_grid(ocn, arch, case).immersed_flags()
+    assert np.array_equal(periphery, imm.periphery), np.argwhere(periphery != imm.periphery)[:5]
+    assert np.array_equal(orders, imm.orders), np.argwhere(orders != imm.orders)[:5]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. the tendencies
 # ---------------------------------------------------------------------------------------------------------------------
@@ -99,6 +123,18 @@ def test_tendencies_are_the_restatement(ocn, arch, tendency_impl, case, closure,
     """after set! (masked, projected) and update_state! the stage tendencies == the restatement evaluated on the model's own halo-filled
     fields, bit for bit over the whole parent array: the immersed cascade, the conditional fluxes, the conditional closure fluxes -- by the
     per-field kernels (path 1) and, where it applies, by the flux-sharing kernel (path 2)"""
+    _tendencies_are_the_restatement(ocn, arch, tendency_impl, case, closure, path)
+
+
+@pytest.mark.parametrize("closure", [False, True], ids=["advection", "with_closure"])
+@pytest.mark.parametrize("case", list(IC.TILE_CASES))
+def test_tile_tendencies_are_the_restatement(ocn, arch, tendency_impl, case, closure):
+    """the same on the tile-edge cases by the flux-sharing kernel (path 2): several tiles, the edge wave's two flux lines and its flag
+    reads live, immersed cells on both sides of every tile seam"""
+    _tendencies_are_the_restatement(ocn, arch, tendency_impl, case, closure, 2)
+
+
+def _tendencies_are_the_restatement(ocn, arch, tendency_impl, case, closure, path):
     tendency_impl(2 if path == 2 else 0)
     ibg = IC.immersed_grid(ocn, arch, case)
     imm = _restatement(ocn, case)
@@ -126,10 +162,10 @@ def test_tendencies_are_the_restatement(ocn, arch, tendency_impl, case, closure,
 
 
 @pytest.mark.parametrize("timestepper", ["RungeKutta3", "QuasiAdamsBashforth2"])
-@pytest.mark.parametrize("case", PATH2)
+@pytest.mark.parametrize("case", PATH2 + tuple(IC.TILE_CASES))
 def test_path_2_is_path_1(ocn, arch, tendency_impl, case, timestepper):
     """the two tendency paths give the same bits: Gⁿ, G⁻, every field and pNHS after 2 steps of a model with FPlane, ScalarDiffusivity and
-    two tracers"""
+    two tracers -- on the small grids and across the tile seams of T1 .. T6"""
     models = []
     for path in (1, 2):
         tendency_impl(2 if path == 2 else 0)
@@ -156,8 +192,11 @@ def test_path_2_is_path_1(ocn, arch, tendency_impl, case, timestepper):
 def test_raw_tendencies_on_path_2(ocn, arch):
     """ocn_compute_tendencies on G1 with random parent arrays (both upwind directions everywhere, transports on the walls) takes the
     flux-sharing kernel under the default tendency_impl and == the restatement; parent entries outside the range keep their bits"""
-    ibg = IC.immersed_grid(ocn, arch, "G1")
-    imm = _restatement(ocn, "G1")
+    _raw_call_is_the_restatement(ocn, IC.immersed_grid(ocn, arch, "G1"), "G1")
+
+
+def _raw_fields(ocn, ibg):
+    """u, v, w and two tracers with random parent arrays P, tendency fields pre-filled with random parent arrays G0"""
     make = {"u": ocn.XFaceField, "v": ocn.YFaceField, "w": ocn.ZFaceField, "c": ocn.CenterField, "d": ocn.CenterField}
     f, P, G, G0 = {}, {}, {}, {}
     for q, n in enumerate("uvwcd"):
@@ -166,10 +205,70 @@ def test_raw_tendencies_on_path_2(ocn, arch):
         G0[n] = np.asfortranarray(np.random.default_rng(80 + q).standard_normal(f[n].shape))
         f[n].set_parent(P[n])
         G[n].set_parent(G0[n])
-    ocn.kernels.compute_tendencies(ibg, f["u"], f["v"], f["w"], [f["c"], f["d"]], G["u"], G["v"], G["w"], [G["c"], G["d"]])
-    for n in "uvwcd":
-        want = IR.advective_tendency(imm.m, imm, n if n in "uvw" else "c", (P["u"], P["v"], P["w"]), P[n], G=G0[n].copy(order="F"))
-        assert np.array_equal(G[n].parent(), want), n
+    return f, P, G, G0
+
+
+def _raw_want(ocn, case, P, G0, rng=None):
+    """the restatement's answer to the raw call on _raw_fields over the range rng, computed once per (case, range) and left alone"""
+    key = ("raw", case, rng)
+    if key not in _shared:
+        imm = _restatement(ocn, case)
+        _shared[key] = {n: IR.advective_tendency(imm.m, imm, n if n in "uvw" else "c", (P["u"], P["v"], P["w"]), P[n], rng=rng, G=G0[n].copy(order="F"))
+                        for n in "uvwcd"}
+    return _shared[key]
+
+
+def _raw_call_is_the_restatement(ocn, ibg, case, rng=None, settings=((None, None),)):
+    """ocn_compute_tendencies over rng == the restatement over the whole parent array of u, v, w, c, d, once per (set, value) of settings"""
+    f, P, G, G0 = _raw_fields(ocn, ibg)
+    want = _raw_want(ocn, case, P, G0, rng)
+    for set_, value in settings:
+        if set_ is not None:
+            set_(value)
+        for n in "uvwcd":
+            G[n].set_parent(G0[n])
+        ocn.kernels.compute_tendencies(ibg, f["u"], f["v"], f["w"], [f["c"], f["d"]], G["u"], G["v"], G["w"], [G["c"], G["d"]], kernel_parameters=rng)
+        for n in "uvwcd":
+            got = G[n].parent()
+            assert np.array_equal(got, want[n]), (case, rng, value, n, "at (i, j, k)", np.argwhere(got != want[n])[:4] - np.array(ibg.halo_size) + 1)
+            assert not np.array_equal(want[n], G0[n])
+
+
+@pytest.mark.parametrize("impl", [2, 0], ids=["path2", "path1"])
+@pytest.mark.parametrize("case", list(IC.TILE_CASES))
+def test_raw_tendencies_across_tile_edges(ocn, arch, tendency_impl, case, impl):
+    """ocn_compute_tendencies with two tracers on random parent arrays on the tile-edge cases, by the flux-sharing kernel (tendency_impl 2)
+    and by the per-field kernels (0): each == the restatement over the whole parent array, entries outside the range keep their bits. Where
+    only path 2 fails the tile logic is at fault; where both do, the tables or the restatement. The raw entry has no report key: a model
+    with two tracers on the same grid answers which path the setting takes."""
+    tendency_impl(impl)
+    ibg = IC.immersed_grid(ocn, arch, case)
+    model = _model(ocn, ibg, tracers=("c", "d"))
+    assert model.get_option("immersed_tendency_path") == (2 if impl == 2 else 1)
+    model.close()
+    _raw_call_is_the_restatement(ocn, ibg, case)
+
+
+TRIMMED = [(3, 127, 2, 13, 2, 4),          # tiles start at i0 = 3: seams at i = 67 and j = 9
+           (2, 65, 3, 9, 1, 5),            # exactly one 64 x 7 tile: its closing faces i1 + 1, j1 + 1 come from the edge wave alone
+           (66, 129, 9, 15, 1, 5)]         # one tile that ends on the periodic edge in x and in y
+
+
+@pytest.mark.parametrize("rng", TRIMMED, ids=["-".join(map(str, r)) for r in TRIMMED])
+def test_trimmed_ranges_across_tile_edges(ocn, arch, rng):
+    """kernel_parameters on T2 (129 x 15 x 5) by the flux-sharing kernel: the tiles, the edge lines and the clamp of the flag index follow
+    the range, not the grid; every field takes the range as it is (no exclude_periphery)"""
+    _raw_call_is_the_restatement(ocn, IC.immersed_grid(ocn, arch, "T2"), "T2", rng=rng)
+
+
+@pytest.mark.parametrize("case", ["T1", "T5"])
+def test_chunk_lengths_across_tile_edges(ocn, arch, role_kchunk, case):
+    """every chunk length of option_variants.chunk_lengths under the immersed instantiation: the flag reads while the z-window is primed
+    and in the peeled plane kc1 + 1 of every chunk, on T1 (Nz = 6, Bounded) and T5 (Nz = 9, Periodic)"""
+    from option_variants import chunk_lengths
+    lengths = tuple(dict.fromkeys(chunk_lengths(IC.TILE_CASES[case]["size"][2])))
+    assert len(lengths) >= 7
+    _raw_call_is_the_restatement(ocn, IC.immersed_grid(ocn, arch, case), case, settings=[(role_kchunk, kc) for kc in lengths])
 
 
 def test_raw_entry_points_honour_the_boundary(ocn, arch):
@@ -268,6 +367,17 @@ def test_model_is_the_orchestrated_yardstick(ocn, oracle, arch, case, timesteppe
     update_state!. The velocity mask is seen directly only where it is the last thing to run, in set! without the projection (the mask of
     ocn_model_set_finalize); the one at the head of the pressure step is covered through the comparison with the yardstick, which has it
     (a build without it fails this test on every grid)."""
+    _model_is_the_orchestrated_yardstick(ocn, oracle, arch, case, timestepper, 3)
+
+
+@pytest.mark.parametrize("timestepper", ["RungeKutta3", "QuasiAdamsBashforth2"])
+def test_tile_model_is_the_orchestrated_yardstick(ocn, oracle, arch, timestepper):
+    """the same physics on T1 (65 x 8 x 6: two x tiles, two row tiles, the edge wave live) for one step -- three RK3 stages, or AB2's
+    forward-Euler first step -- with the same bounds and the same exact zeros"""
+    _model_is_the_orchestrated_yardstick(ocn, oracle, arch, "T1", timestepper, 1)
+
+
+def _model_is_the_orchestrated_yardstick(ocn, oracle, arch, case, timestepper, steps):
     ibg = IC.immersed_grid(ocn, arch, case)
     g = IC.oracle_grid(oracle, case)
     imm = _restatement(ocn, case)
@@ -277,7 +387,7 @@ def test_model_is_the_orchestrated_yardstick(ocn, oracle, arch, case, timesteppe
     model = _model(ocn, ibg, tracers=("b", "S"), timestepper=timestepper, buoyancy=ocn.BuoyancyTracer(), coriolis=ocn.FPlane(f=FCOR),
                    closure=ocn.ScalarDiffusivity(ν=NU, κ={"b": KAPPA, "S": 1e-3}), forcing={"S": forcing},
                    boundary_conditions={"b": F(top=ocn.FluxBoundaryCondition(0.03))})
-    assert model.get_option("immersed_tendency_path") == (2 if case in PATH2 else 1) and model.get_option("forcing_path") == 3
+    assert model.get_option("immersed_tendency_path") == (2 if case in PATH2 + tuple(IC.TILE_CASES) else 1) and model.get_option("forcing_path") == 3
     yard = IR.ImmersedOrchestrated(oracle, g, 2, NU, (KAPPA, 1e-3), imm.cell, buoyancy_index=0, fcor=FCOR, forcing={"c1": forcing},
                                    bcs={"c0": {"top": ("flux", 0.03)}})
     vals = smooth_state({("T" if n == "b" else n): ibg.nodes(f.loc) for n, f in model.fields().items()}, 17)
@@ -292,7 +402,7 @@ def test_model_is_the_orchestrated_yardstick(ocn, oracle, arch, case, timesteppe
     ocn.set_model(model, **vals)
     yard.set(u=vals["u"], v=vals["v"], w=vals["w"], c0=vals["b"], c1=vals["S"])
     dt = 0.05 / ibg.Nx
-    for _ in range(3):
+    for _ in range(steps):
         ocn.time_step(model, dt)
         yard.time_step(dt) if timestepper == "RungeKutta3" else yard.time_step_ab2(dt)
     umax = max(np.abs(yard.U[n]).max() for n in "uvw")
@@ -309,7 +419,7 @@ def test_model_is_the_orchestrated_yardstick(ocn, oracle, arch, case, timesteppe
     pscale = max(np.abs(b).max(), umax * spacing / dt)
     print(f"{case} {timestepper} p: max abs difference {np.max(np.abs(a - b)):.3e} on the scale {pscale:.3e}")
     assert np.max(np.abs(a - b)) < 1e-12 * pscale
-    assert model.clock.time == yard.time and model.clock.iteration == yard.iteration == 3
+    assert model.clock.time == yard.time and model.clock.iteration == yard.iteration == steps
     assert model.clock.last_Δt == yard.last_dt and model.clock.last_stage_Δt == yard.last_stage_dt
     # at the end of a step the velocities at immersed faces are NOT zero: they carry -Δt ∂p until the next mask (the reference's behaviour)
     w_faces = np.broadcast_to(imm.bit(R.LOCS["w"], *(np.arange(1, s + 1).reshape([-1 if q == d else 1 for q in range(3)]) for d, s in enumerate(m.N))), m.N)

@@ -4,7 +4,8 @@
     z <= z_b (:88-108), function and array GridFittedBoundary (:222-282), Flat topologies (:328-356), equality (:389-453); number, array
     and function bottoms on a stretched z; InterfaceImmersedCondition against the loop of grid_fitted_bottom.jl:111-122;
   * the numpy restatement (tests/immersed_reference.py) with an empty boundary == background_reference.advective_tendency == the oracle,
-    bit for bit, on G1, G2 and G3; its predicates on a hand-checked configuration; one finite step of ImmersedOrchestrated on every grid;
+    bit for bit, on G1, G2, G3 and at the tile-edge sizes T1 and T3; its predicates on a hand-checked configuration; what the tile-edge
+    cases hold at every tile seam; one finite step of ImmersedOrchestrated on every grid;
   * halo inflation to buffer + 1 with the reference's warning text; every refusal; the new symbols of the built library.
 
 No GPU."""
@@ -144,15 +145,68 @@ def test_cases_hold_what_they_promise():
     assert (n == 0).any() and (n >= 4).any() and n[3, 0] < n[2, 0] - 3 and n[3, 0] < n[4, 0] - 3 and n[7, 0] > 0 and n[0, 0] == 0
 
 
+@pytest.mark.parametrize("case", list(IC.TILE_CASES))
+def test_tile_cases_hold_what_they_promise(ocn, case):
+    """the tile-edge cases, from the restatement's tables. At every x seam (the faces i = 65, 129, 193 that exist and the wrap Nx | 1): an
+    immersed cell faces a fluid one across it, in both orientations over the case's seams; both x order entries fall below 3 at the seam
+    column and at the column before it; IMM_FCC of the seam face is set at one level of a row and clear at another. The same at every y
+    seam (j = 8, 15, the wrap) with the y entries and IMM_CFC. At every corner the case places, an immersed cell has a fluid diagonal
+    neighbour and IMM_FFC is set. The flags the edge wave reads beyond the periodic edge (column Nx + 1, row Ny + 1) are those of column /
+    row 1. Elsewhere: a column without an immersed cell, and every cascade level the grid admits along z on both sides -- {1, 2, 3} on a
+    Periodic z; next to the walls of a Bounded z the window of buffer 3 is free only for 4 <= k <= Nz - 2 (side ᶠ) / 3 <= k <= Nz - 2
+    (side ᶜ) (test_predicates_by_hand), so level 3 needs Nz >= 6 / Nz >= 5 and T2, T4, T6 (Nz = 5, 4, 5) cannot hold it on every side."""
+    grid, cells = _cells(ocn, case)
+    imm = IR.Immersed(R.Metrics.of_grid(grid), cells)
+    (Nx, Ny, Nz), (Hx, Hy, Hz) = imm.m.N, imm.m.H
+    at = lambda table, i, j, k: table[i - 1 + Hx, j - 1 + Hy, k - 1 + Hz]                       # noqa: E731   1-based, halos in reach
+    cell = lambda i, j, k: at(imm.cell, i, j, k)                                                # noqa: E731
+    bit = lambda loc, i, j, k: ((at(imm.periphery, i, j, k) >> IR.BIT[loc]) & 1).astype(bool)   # noqa: E731
+    order = lambda d, side, i, j, k: (at(imm.orders, i, j, k) >> (2 * (2 * d + side))) & 3      # noqa: E731
+    I, J, K = np.arange(1, Nx + 1), np.arange(1, Ny + 1), np.arange(1, Nz + 1)
+    fcc, cfc, ffc = (R.FACE, R.CENTER, R.CENTER), (R.CENTER, R.FACE, R.CENTER), (R.FACE, R.FACE, R.CENTER)
+
+    def seam(d, before, on, loc):
+        """-> the orientations met across the seam between the lines `before` and `on` along direction d"""
+        line = (lambda n: (n, J[:, None], K[None, :])) if d == 0 else (lambda n: (I[:, None], n, K[None, :]))     # noqa: E731
+        solid_before, solid_on = cell(*line(before)), cell(*line(on))
+        met = {name for name, there in (("solid|fluid", solid_before & ~solid_on), ("fluid|solid", ~solid_before & solid_on)) if there.any()}
+        assert met, (d, on)
+        for n in (before, on):
+            for side in (0, 1):
+                assert (order(d, side, *line(n)) < 3).any(), (d, n, side)
+        flag = bit(loc, *line(on))
+        assert (flag.any(axis=1) & ~flag.all(axis=1)).any(), (d, on)
+        return met
+
+    x_seams, y_seams = IC.seams(Nx, IC.X_SEAMS), IC.seams(Ny, IC.Y_SEAMS)
+    assert [s[1] for s in x_seams] == [i for i in (65, 129, 193) if i <= Nx] + [1] and x_seams[-1][0] == Nx
+    assert [s[1] for s in y_seams] == [j for j in (8, 15) if j <= Ny] + [1] and y_seams[-1][0] == Ny
+    assert set().union(*(seam(0, a, b, fcc) for a, b in x_seams)) == {"solid|fluid", "fluid|solid"}
+    assert set().union(*(seam(1, a, b, cfc) for a, b in y_seams)) == {"solid|fluid", "fluid|solid"}
+    corners = IC.seam_corners((Nx, Ny, Nz))
+    assert corners and (Nx < 65 or corners[0][0] == 65)                                         # where it is live, the edge wave's column
+    for i, j in corners:
+        assert (cell(i, j, K) & ~cell(i - 1, j - 1, K) & bit(ffc, i, j, K)).any(), (i, j)
+    for table in (imm.periphery, imm.orders):
+        assert np.array_equal(at(table, Nx + 1, J[:, None], K[None, :]), at(table, 1, J[:, None], K[None, :]))
+        assert np.array_equal(at(table, I[:, None], Ny + 1, K[None, :]), at(table, I[:, None], 1, K[None, :]))
+    inside = cell(I[:, None, None], J[None, :, None], K[None, None, :])
+    assert (~inside.any(axis=2)).any() and inside.any()
+    periodic = IC.TILE_CASES[case]["topology"][2] == "Periodic"
+    for side, first in ((0, 4), (1, 3)):
+        levels = set(np.unique(order(2, side, I[:, None, None], J[None, :, None], K[None, None, :])))
+        assert levels == ({1, 2, 3} if periodic or first <= Nz - 2 else {1, 2}), (side, levels)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the restatement
 # ---------------------------------------------------------------------------------------------------------------------
 def _cells(ocn, case, boundary=None):
     grid = IC.underlying_grid(ocn, None, case)
-    return grid, IR.cells_of_grid(grid, IC.CASES[case]["boundary"] if boundary is None else boundary)[0]
+    return grid, IR.cells_of_grid(grid, IC.case_of(case)["boundary"] if boundary is None else boundary)[0]
 
 
-@pytest.mark.parametrize("case", list(IC.CASES))
+@pytest.mark.parametrize("case", list(IC.CASES) + list(IC.TILE_CASES))
 def test_package_mask_is_the_restatement(ocn, case):
     grid, cell = _cells(ocn, case)
     ibg = IC.immersed_grid(ocn, None, case)
@@ -188,13 +242,14 @@ def test_predicates_by_hand(ocn):
     assert got == [1, 1, 2, 3, 3, 3, 2, 1, 1]
 
 
-@pytest.mark.parametrize("case", ["G1", "G2", "G3"])
+@pytest.mark.parametrize("case", ["G1", "G2", "G3", "T1", "T3"])
 def test_empty_boundary_is_the_plain_restatement_is_the_oracle(ocn, oracle, case):
-    """with a bottom below the domain the immersed restatement's tendencies == background_reference.advective_tendency == the oracle's
-    compute_G, bit for bit: the order table reproduces outside_*_halo at the walls and no flux is masked"""
+    """with a bottom below the domain (T3, Periodic z: a mask of zeros) the immersed restatement's tendencies ==
+    background_reference.advective_tendency == the oracle's compute_G, bit for bit: the order table reproduces outside_*_halo at the walls
+    and no flux is masked. T1 (65 x 8 x 6) and T3 (64 x 7 x 7) pin the restatement at the tile-edge sizes tests/test_gpu_immersed.py uses."""
     g = IC.oracle_grid(oracle, case)
     m = R.Metrics.of_oracle(g)
-    grid, cell = _cells(ocn, case, IC.EMPTY)
+    grid, cell = _cells(ocn, case, IC.empty_boundary(case))
     assert not cell[tuple(slice(h, s - h) for h, s in zip(m.H, cell.shape))].any()
     imm = IR.Immersed(m, cell)
     assert not (imm.periphery >> 1).any()
