@@ -4631,7 +4631,7 @@ extern "C" int ocn_model_profile_read(ocn_model_t m, double *tendency_ms, int *c
 
 extern "C" int ocn_debug_rcp_check(int variant, int exponent, unsigned long long *mismatches) {
     NEED_INIT();
-    if (!mismatches || exponent < -120 || exponent > 120) return fail(OCN_EINVAL, "invalid argument");
+    if (!mismatches || exponent < -126 || exponent > 127) return fail(OCN_EINVAL, "invalid argument");      // every binade of normal numbers
     unsigned long long *d;
     HIP_TRY(dev_alloc((void **)&d, 8));
     HIP_TRY(hipMemsetAsync(d, 0, 8, g_stream));
@@ -4648,7 +4648,7 @@ extern "C" int ocn_debug_rcp_check(int variant, int exponent, unsigned long long
 extern "C" int ocn_debug_rcp64_check(unsigned long long nsamples, int exp_lo, int exp_hi, unsigned long long seed,
                                      unsigned long long *mismatches) {
     NEED_INIT();
-    if (!mismatches || exp_lo < -1000 || exp_hi > 1000 || exp_lo > exp_hi || nsamples == 0 || nsamples > (1ull << 36))
+    if (!mismatches || exp_lo < -1022 || exp_hi > 1023 || exp_lo > exp_hi || nsamples == 0 || nsamples > (1ull << 36))
         return fail(OCN_EINVAL, "invalid argument");
     unsigned long long *d;
     HIP_TRY(dev_alloc((void **)&d, 8));

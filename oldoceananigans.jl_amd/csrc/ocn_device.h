@@ -58,8 +58,14 @@ struct FieldList {
 // -fhip-fp32-correctly-rounded-divide-sqrt so `1.0f / x` is exact, not v_rcp_f32.
 // Correctly rounded Float32 reciprocal without the generic IEEE-divide expansion (v_div_scale / v_div_fmas /
 // v_div_fixup, ~13 VALU): hardware v_rcp_f32 (1 ulp) + one Markstein correction step. Exact for every normal x whose
-// reciprocal is normal -- verified EXHAUSTIVELY over all 2^23 significands by ocn_debug_rcp_check (tests/test_gpu_parity.py);
-// the WENO argument beta + eps lies in [1e-8, ~1e19], far inside that range.
+// reciprocal is normal -- verified EXHAUSTIVELY over all 2^23 significands by ocn_debug_rcp_check (tests/test_gpu_parity.py; every
+// binade from 2^64 to 2^125 in tests/test_gpu_value_domain.py).
+// DOMAIN: x < 2^126. v_rcp_f32 flushes a subnormal result, so on binades 126 and 127 this returns 0 where the divide returns a
+// subnormal (measured: 8388607 and 8388608 of 2^23 significands differ), and for x = +inf (beta + eps beyond Float32) e = fma(-inf, 0, 1)
+// makes it NaN where the divide returns 0. The WENO argument beta + eps is >= 1e-8 and of the order of the squared jumps of the field:
+// O(1) fields stay below ~1e19; fields with jumps of ~2^60 or more leave the domain, and the reconstruction then differs from the
+// reference's (ratio 0 instead of tau / beta up to 2^128, NaN beyond). A range test that sends such arguments to the divide costs 0.9 %
+// (one wave-uniform test per reconstruction) to 1.7 % (one branch per reciprocal) of the 256^3 step and was not merged.
 #ifndef OCN_RCP_VARIANT
 #define OCN_RCP_VARIANT 1
 #endif
@@ -79,7 +85,9 @@ template <int VARIANT> __device__ __forceinline__ float rcp_rn_f32(float x) {
 // IEEE divide expands to v_div_scale x2, v_rcp_f64, 2 Newton steps, v_mul, v_fma, v_div_fmas, v_div_fixup (11 VALU). For a
 // numerator of 1 and a denominator far from the exponent limits the scale factors are 1, v_div_fmas is a plain fma and
 // v_div_fixup passes its argument through, so the SAME operation sequence without them (7 VALU) returns the same bits.
-// sum(α) >= C★-sum = 1 and <= ~1e45 here. Checked against `1.0 / x` on sampled inputs by ocn_debug_rcp64_check.
+// sum(α) >= C★-sum = 1; a smooth sub-stencil beside a step of height h gives sum(α) ~ (h^2 / 1e-8)^2: 1e51 at h = 2^30, 2^858 on the
+// largest state the tests use. Checked against `1.0 / x` by ocn_debug_rcp64_check: no mismatch in 2^24 samples per window on exponents
+// 0 .. 1020 and -1020 .. -60 (tests/test_gpu_parity.py, tests/test_gpu_value_domain.py).
 #ifndef OCN_RCP64_VARIANT
 #define OCN_RCP64_VARIANT 1
 #endif
