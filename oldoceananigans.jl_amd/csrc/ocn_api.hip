@@ -26,6 +26,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -1921,6 +1922,34 @@ extern "C" int ocn_add_buoyancy_acceleration(ocn_grid_t grid, int kind, const do
     return add_buoyancy_acceleration(grid->d, kind, bT, S, grav, alpha, beta, ghat_x, ghat_y, Gu, Gv, range);
 }
 
+// ---- closures: ScalarDiffusivity, AnisotropicMinimumDissipation, Smagorinsky (kernels: ocn_closures.h) ----
+// fn(std::integral_constant<int, F>()) for the run-time field kind F: the kernels take it as a template argument
+template <class Fn> static void with_field(int F, Fn fn) {
+    switch (F) {
+        case F_U: fn(std::integral_constant<int, F_U>()); break;
+        case F_V: fn(std::integral_constant<int, F_V>()); break;
+        case F_W: fn(std::integral_constant<int, F_W>()); break;
+        default: fn(std::integral_constant<int, F_C>()); break;
+    }
+}
+
+// what the eddy-coefficient closures refuse; `arrays`: the caller is an entry point that takes their coefficient arrays
+static int refuse_flat(const DGrid &g, const char *feature, int code = OCN_ENOTSUP, bool arrays = false) {
+    if (g.tx != OCN_FLAT && g.ty != OCN_FLAT && g.tz != OCN_FLAT) return OCN_OK;
+    return arrays ? fail(code, "eddy-coefficient arrays (%s) need a grid without Flat directions", feature)
+                  : fail(code, "%s needs a grid without Flat directions", feature);
+}
+
+// the arguments the four ocn_compute_closure_tendencies* entry points share. per_tracer: the argument with one entry per tracer (κ, κₑ or Pr)
+static int check_closure_arguments(ocn_grid_t grid, const double *u, const double *v, const double *w, const double *const *tracers, int ntracers,
+                                   const void *per_tracer, const double *Gu, const double *Gv, const double *Gw, double *const *Gc,
+                                   bool nu_e_missing = false) {
+    if (!grid || !u || !v || !w || nu_e_missing || !Gu || !Gv || !Gw || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 ||
+        (ntracers > 0 && (!tracers || !Gc || !per_tracer)))
+        return fail(OCN_EINVAL, "invalid argument");
+    return OCN_OK;
+}
+
 static int closure_tendencies(const DGrid &g, const double *u, const double *v, const double *w, const double *const *tr, int ntr,
                               double nu, const double *kappa, double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range,
                               const double *nu_e = nullptr, const double *const *kappa_e = nullptr, const double *Pr = nullptr, bool vi = false,
@@ -1940,25 +1969,17 @@ static int closure_tendencies(const DGrid &g, const double *u, const double *v, 
         if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
         const FView vc = make_view(g, c ? c : u, LOC_C), vG = make_view(g, G, loc);
         const dim3 grd = grid3(nx, ny, nz, BLK);
-        if (im) {               // constant coefficients, explicit, every flux conditional (immersed_closure_tendency_kernel)
-            if (F == F_U) hipLaunchKernelGGL(immersed_closure_tendency_kernel<F_U>, grd, BLK, 0, g_stream, g, *im, vu, vv, vw, vc, vG, coef, r);
-            if (F == F_V) hipLaunchKernelGGL(immersed_closure_tendency_kernel<F_V>, grd, BLK, 0, g_stream, g, *im, vu, vv, vw, vc, vG, coef, r);
-            if (F == F_W) hipLaunchKernelGGL(immersed_closure_tendency_kernel<F_W>, grd, BLK, 0, g_stream, g, *im, vu, vv, vw, vc, vG, coef, r);
-            if (F == F_C) hipLaunchKernelGGL(immersed_closure_tendency_kernel<F_C>, grd, BLK, 0, g_stream, g, *im, vu, vv, vw, vc, vG, coef, r);
-            return OCN_OK;
-        }
-        if (vi) {               // constant coefficients, the explicit part of a vertically implicit discretisation
-            if (F == F_U) hipLaunchKernelGGL((closure_tendency_kernel<F_U, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
-            if (F == F_V) hipLaunchKernelGGL((closure_tendency_kernel<F_V, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
-            if (F == F_W) hipLaunchKernelGGL((closure_tendency_kernel<F_W, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
-            if (F == F_C) hipLaunchKernelGGL((closure_tendency_kernel<F_C, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK);
-            return OCN_OK;
-        }
-        if (F == F_U) hipLaunchKernelGGL(closure_tendency_kernel<F_U>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
-        if (F == F_V) hipLaunchKernelGGL(closure_tendency_kernel<F_V>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
-        if (F == F_W) hipLaunchKernelGGL(closure_tendency_kernel<F_W>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
-        if (F == F_C && !prd) hipLaunchKernelGGL(closure_tendency_kernel<F_C>, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK);
-        if (F == F_C && prd) hipLaunchKernelGGL(closure_tendency_prandtl_kernel, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, vK);
+        with_field(F, [&](auto field) {
+            constexpr int FF = decltype(field)::value;
+            if (im)             // constant coefficients, explicit, every flux conditional
+                hipLaunchKernelGGL((closure_tendency_kernel<FF, false, ImmView>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK, *im);
+            else if (vi)        // constant coefficients, the explicit part of a vertically implicit discretisation
+                hipLaunchKernelGGL((closure_tendency_kernel<FF, true>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, false, vK, NoImm());
+            else if (prd)       // (tracers only)
+                hipLaunchKernelGGL(closure_tendency_prandtl_kernel, grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, vK);
+            else
+                hipLaunchKernelGGL((closure_tendency_kernel<FF>), grd, BLK, 0, g_stream, g, vu, vv, vw, vc, vG, coef, r, var, vK, NoImm());
+        });
         return OCN_OK;
     };
     int rc;
@@ -1976,9 +1997,7 @@ extern "C" int ocn_compute_closure_tendencies(ocn_grid_t grid, const double *u, 
                                               const double *const *tracers, int ntracers, double nu, const double *kappa,
                                               double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range) {
     NEED_INIT();
-    if (!grid || !u || !v || !w || !Gu || !Gv || !Gw || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 ||
-        (ntracers > 0 && (!tracers || !Gc || !kappa)))
-        return fail(OCN_EINVAL, "invalid argument");
+    if (int rc = check_closure_arguments(grid, u, v, w, tracers, ntracers, kappa, Gu, Gv, Gw, Gc)) return rc;
     if (nu < 0) return fail(OCN_EINVAL, "viscosity must be non-negative");
     const ImmView im = imm_view(grid);
     return closure_tendencies(grid->d, u, v, w, tracers, ntracers, nu, kappa, Gu, Gv, Gw, Gc, range, nullptr, nullptr, nullptr, false,
@@ -1991,9 +2010,7 @@ extern "C" int ocn_compute_closure_tendencies_vertically_implicit(ocn_grid_t gri
                                                                   const double *const *tracers, int ntracers, double nu, const double *kappa,
                                                                   double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range) {
     NEED_INIT();
-    if (!grid || !u || !v || !w || !Gu || !Gv || !Gw || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 ||
-        (ntracers > 0 && (!tracers || !Gc || !kappa)))
-        return fail(OCN_EINVAL, "invalid argument");
+    if (int rc = check_closure_arguments(grid, u, v, w, tracers, ntracers, kappa, Gu, Gv, Gw, Gc)) return rc;
     if (nu < 0) return fail(OCN_EINVAL, "viscosity must be non-negative");
     if (grid->d.tz != OCN_BOUNDED)
         return fail(OCN_EINVAL, "VerticallyImplicitTimeDiscretization can only be specified on grids that are Bounded in the z-direction.");
@@ -2043,29 +2060,40 @@ extern "C" int ocn_compute_closure_tendencies_field(ocn_grid_t grid, const doubl
                                                     const int *range) {
     NEED_INIT();
     if (int rc_ = refuse_immersed(grid, "a closure with diffusivity fields (AnisotropicMinimumDissipation)")) return rc_;
-    if (!grid || !u || !v || !w || !nu_e || !Gu || !Gv || !Gw || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 ||
-        (ntracers > 0 && (!tracers || !Gc || !kappa_e)))
-        return fail(OCN_EINVAL, "invalid argument");
-    if (grid->d.tx == OCN_FLAT || grid->d.ty == OCN_FLAT || grid->d.tz == OCN_FLAT)
-        return fail(OCN_ENOTSUP, "eddy-coefficient arrays (AnisotropicMinimumDissipation) need a grid without Flat directions");
+    if (int rc = check_closure_arguments(grid, u, v, w, tracers, ntracers, kappa_e, Gu, Gv, Gw, Gc, !nu_e)) return rc;
+    if (int rc = refuse_flat(grid->d, "AnisotropicMinimumDissipation", OCN_ENOTSUP, true)) return rc;
     return closure_tendencies(grid->d, u, v, w, tracers, ntracers, 0.0, nullptr, Gu, Gv, Gw, Gc, range, nu_e, kappa_e);
+}
+
+// the range of an eddy-coefficient kernel: the interior, or `range` -- the stencils reach one cell further, so it may extend into the halos
+// by at most H - 1
+static int stencil_range(const DGrid &g, const int *range, Range6 *r) {
+    *r = Range6{1, g.Nx, 1, g.Ny, 1, g.Nz};
+    if (!range) return OCN_OK;
+    const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz};
+    for (int d = 0; d < 3; ++d)
+        if (range[2 * d] < 2 - H[d] || range[2 * d + 1] > N[d] + H[d] - 1)
+            return fail(OCN_EINVAL, "range [%d, %d] along dimension %d leaves no halo for the stencil", range[2 * d], range[2 * d + 1], d);
+    *r = Range6{range[0], range[1], range[2], range[3], range[4], range[5]};
+    return OCN_OK;
+}
+
+// the launch of a z-marching eddy-coefficient kernel (ocn_closures.h): 63 columns per wave, 4 rows per block, chunks of at most `maxchunk`
+// levels so that ~2000 blocks fill the chip
+struct MarchGrid { dim3 grd, blk; int kchunk; };
+static MarchGrid march_grid(int nx, int ny, int nz, int maxchunk = 1 << 30) {
+    const int bx = (nx + 62) / 63, by = (ny + 3) / 4;
+    const int want = std::max(1, 2048 / std::max(1, bx * by));
+    const int kchunk = std::min(maxchunk, std::max(std::min(nz, 8), (nz + want - 1) / want));
+    return MarchGrid{dim3(bx, by, (nz + kchunk - 1) / kchunk), dim3(64, 4), kchunk};
 }
 
 static int amd_diffusivities(const OcnOptions &o, const DGrid &g, double Cnu, const double *Ckappa, const double *u, const double *v, const double *w,
                              const double *const *tr, int ntr, double *nu_e, double *const *kappa_e, const int *range = nullptr) {
-    if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT)
-        return fail(OCN_ENOTSUP, "AnisotropicMinimumDissipation needs a grid without Flat directions");
+    if (int rc = refuse_flat(g, "AnisotropicMinimumDissipation")) return rc;
     AmdArgs a;
     a.ntr = ntr; a.Cnu = Cnu;
-    a.r = Range6{1, g.Nx, 1, g.Ny, 1, g.Nz};
-    if (range) {
-        // the stencils reach one cell further: the range may extend into the halos by at most H - 1
-        const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz};
-        for (int d = 0; d < 3; ++d)
-            if (range[2 * d] < 2 - H[d] || range[2 * d + 1] > N[d] + H[d] - 1)
-                return fail(OCN_EINVAL, "range [%d, %d] along dimension %d leaves no halo for the stencil", range[2 * d], range[2 * d + 1], d);
-        a.r = Range6{range[0], range[1], range[2], range[3], range[4], range[5]};
-    }
+    if (int rc = stencil_range(g, range, &a.r)) return rc;
     const int nx = a.r.i1 - a.r.i0 + 1, ny = a.r.j1 - a.r.j0 + 1, nz = a.r.k1 - a.r.k0 + 1;
     if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
     a.u = make_view(g, u, LOC_U); a.v = make_view(g, v, LOC_V); a.w = make_view(g, w, LOC_W);
@@ -2076,16 +2104,12 @@ static int amd_diffusivities(const OcnOptions &o, const DGrid &g, double Cnu, co
         a.Ck[t] = Ckappa[t];
     }
     if (o.amd_march && ntr <= 3) {
-        // z-marching kernel (ocn_kernels.h): 63 columns per wave, 4 rows per block, chunks of levels so that ~2000 blocks fill the chip
-        const int bx = (nx + 62) / 63, by = (ny + 3) / 4;
-        const int want = std::max(1, 2048 / std::max(1, bx * by));
-        const int kchunk = std::min(OCN_AMD_MAXCHUNK, std::max(std::min(nz, 8), (nz + want - 1) / want));
-        const dim3 grd(bx, by, (nz + kchunk - 1) / kchunk), blk(64, 4);
+        const MarchGrid m = march_grid(nx, ny, nz, OCN_AMD_MAXCHUNK);       // (the kernel's per-level LDS table holds that many levels)
         switch (ntr) {
-            case 0: hipLaunchKernelGGL(amd_diffusivities_march_kernel<0>, grd, blk, 0, g_stream, g, a, kchunk); break;
-            case 1: hipLaunchKernelGGL(amd_diffusivities_march_kernel<1>, grd, blk, 0, g_stream, g, a, kchunk); break;
-            case 2: hipLaunchKernelGGL(amd_diffusivities_march_kernel<2>, grd, blk, 0, g_stream, g, a, kchunk); break;
-            default: hipLaunchKernelGGL(amd_diffusivities_march_kernel<3>, grd, blk, 0, g_stream, g, a, kchunk); break;
+            case 0: hipLaunchKernelGGL(amd_diffusivities_march_kernel<0>, m.grd, m.blk, 0, g_stream, g, a, m.kchunk); break;
+            case 1: hipLaunchKernelGGL(amd_diffusivities_march_kernel<1>, m.grd, m.blk, 0, g_stream, g, a, m.kchunk); break;
+            case 2: hipLaunchKernelGGL(amd_diffusivities_march_kernel<2>, m.grd, m.blk, 0, g_stream, g, a, m.kchunk); break;
+            default: hipLaunchKernelGGL(amd_diffusivities_march_kernel<3>, m.grd, m.blk, 0, g_stream, g, a, m.kchunk); break;
         }
     } else
         hipLaunchKernelGGL(amd_diffusivities_kernel, grid3(nx, ny, nz, BLK), BLK, 0, g_stream, g, a);
@@ -2108,13 +2132,10 @@ extern "C" int ocn_compute_closure_tendencies_smagorinsky(ocn_grid_t grid, const
                                                           double *Gu, double *Gv, double *Gw, double *const *Gc, const int *range) {
     NEED_INIT();
     if (int rc_ = refuse_immersed(grid, "Smagorinsky")) return rc_;
-    if (!grid || !u || !v || !w || !nu_e || !Gu || !Gv || !Gw || ntracers < 0 || ntracers > OCN_MAX_FIELDS - 3 ||
-        (ntracers > 0 && (!tracers || !Gc || !Pr)))
-        return fail(OCN_EINVAL, "invalid argument");
+    if (int rc = check_closure_arguments(grid, u, v, w, tracers, ntracers, Pr, Gu, Gv, Gw, Gc, !nu_e)) return rc;
     for (int t = 0; t < ntracers; ++t)
         if (!(Pr[t] > 0)) return fail(OCN_EINVAL, "the Prandtl number must be positive");
-    if (grid->d.tx == OCN_FLAT || grid->d.ty == OCN_FLAT || grid->d.tz == OCN_FLAT)
-        return fail(OCN_ENOTSUP, "eddy-coefficient arrays (Smagorinsky) need a grid without Flat directions");
+    if (int rc = refuse_flat(grid->d, "Smagorinsky", OCN_ENOTSUP, true)) return rc;
     const double one = 1.0;
     return closure_tendencies(grid->d, u, v, w, tracers, ntracers, 0.0, nullptr, Gu, Gv, Gw, Gc, range, nu_e, nullptr, ntracers > 0 ? Pr : &one);
 }
@@ -2124,17 +2145,9 @@ static int smagorinsky_viscosity(const OcnOptions &o, ocn_grid_t grid, double C,
                                  double grav, double alpha, double beta, const double *u, const double *v, const double *w, double *nu_e,
                                  const int *range = nullptr) {
     const DGrid &g = grid->d;
-    if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT) return fail(OCN_ENOTSUP, "Smagorinsky needs a grid without Flat directions");
+    if (int rc = refuse_flat(g, "Smagorinsky")) return rc;
     SmagArgs a;
-    a.r = Range6{1, g.Nx, 1, g.Ny, 1, g.Nz};
-    if (range) {
-        // the stencils reach one cell further: the range may extend into the halos by at most H - 1
-        const int N[3] = {g.Nx, g.Ny, g.Nz}, H[3] = {g.Hx, g.Hy, g.Hz};
-        for (int d = 0; d < 3; ++d)
-            if (range[2 * d] < 2 - H[d] || range[2 * d + 1] > N[d] + H[d] - 1)
-                return fail(OCN_EINVAL, "range [%d, %d] along dimension %d leaves no halo for the stencil", range[2 * d], range[2 * d + 1], d);
-        a.r = Range6{range[0], range[1], range[2], range[3], range[4], range[5]};
-    }
+    if (int rc = stencil_range(g, range, &a.r)) return rc;
     const int nx = a.r.i1 - a.r.i0 + 1, ny = a.r.j1 - a.r.j0 + 1, nz = a.r.k1 - a.r.k0 + 1;
     if (nx <= 0 || ny <= 0 || nz <= 0) return OCN_OK;
     if (!lilly) bk = 0;                      // the constant coefficient reads no tracer
@@ -2143,15 +2156,11 @@ static int smagorinsky_viscosity(const OcnOptions &o, ocn_grid_t grid, double C,
     a.nu_e = make_view(g, nu_e, LOC_C);
     a.C = C; a.Cb = Cb; a.grav = grav; a.alpha = alpha; a.beta = beta; a.df2 = grid->df2;
     if (o.smag_march) {
-        // 63 columns per wave, 4 rows per block, chunks of levels so that ~2000 blocks fill the chip (as amd_diffusivities)
-        const int bx = (nx + 62) / 63, by = (ny + 3) / 4;
-        const int want = std::max(1, 2048 / std::max(1, bx * by));
-        const int kchunk = std::max(std::min(nz, 8), (nz + want - 1) / want);
-        const dim3 grd(bx, by, (nz + kchunk - 1) / kchunk), blk(64, 4);
-        if (!lilly) hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<0, false>), grd, blk, 0, g_stream, g, a, kchunk);
-        else if (bk == 0) hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<0, true>), grd, blk, 0, g_stream, g, a, kchunk);
-        else if (bk == 1) hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<1, true>), grd, blk, 0, g_stream, g, a, kchunk);
-        else hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<2, true>), grd, blk, 0, g_stream, g, a, kchunk);
+        const MarchGrid m = march_grid(nx, ny, nz);
+        if (!lilly) hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<0, false>), m.grd, m.blk, 0, g_stream, g, a, m.kchunk);
+        else if (bk == 0) hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<0, true>), m.grd, m.blk, 0, g_stream, g, a, m.kchunk);
+        else if (bk == 1) hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<1, true>), m.grd, m.blk, 0, g_stream, g, a, m.kchunk);
+        else hipLaunchKernelGGL((smagorinsky_viscosity_march_kernel<2, true>), m.grd, m.blk, 0, g_stream, g, a, m.kchunk);
     } else {
         const dim3 grd = grid3(nx, ny, nz, BLK);
         if (!lilly) hipLaunchKernelGGL((smagorinsky_viscosity_kernel<0, false>), grd, BLK, 0, g_stream, g, a);
@@ -2187,7 +2196,7 @@ static int alloc_parent_zeroed(ocn_grid_t grid, const int loc[3], double **p);
 
 static int dynamic_smagorinsky_check_grid(const ocn_grid_s *grid, int mask) {
     const DGrid &g = grid->d;
-    if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT) return fail(OCN_EINVAL, "Smagorinsky needs a grid without Flat directions");
+    if (int rc = refuse_flat(g, "Smagorinsky", OCN_EINVAL)) return rc;
     if (no_connected_topology(g, "a dynamic Smagorinsky coefficient")) return OCN_ENOTSUP;
     if (g.Hx < 2 || g.Hy < 2 || g.Hz < 2) return fail(OCN_EINVAL, "a dynamic Smagorinsky coefficient needs halos of at least 2 (the filtered velocities read u, v, w to ±2)");
     if (mask == 0 && (!grid->has_nodes || !grid->nodes_c[0]))
@@ -2301,7 +2310,7 @@ extern "C" int ocn_compute_dynamic_smagorinsky_viscosity(ocn_grid_t grid, int av
     if (int rc_ = refuse_immersed(grid, "DynamicSmagorinsky")) return rc_;
     if (!grid || !u || !v || !w || !nu_e || !J_LM || !J_MM || averaging_mask < 0 || averaging_mask > 7) return fail(OCN_EINVAL, "invalid argument");
     const DGrid &g = grid->d;
-    if (g.tx == OCN_FLAT || g.ty == OCN_FLAT || g.tz == OCN_FLAT) return fail(OCN_EINVAL, "Smagorinsky needs a grid without Flat directions");
+    if (int rc = refuse_flat(g, "Smagorinsky", OCN_EINVAL)) return rc;
     if (no_connected_topology(g, "a dynamic Smagorinsky coefficient")) return OCN_ENOTSUP;
     return dynamic_smagorinsky_viscosity(grid, averaging_mask, minimum_numerator, J_LM, J_MM, u, v, w, nu_e);
 }
@@ -2465,7 +2474,7 @@ struct Closure {
     double minimum_numerator = 0.0;
     int64_t interval = 1, offset = 0;
     bool eddy() const { return kind == AMD || kind == SMAGORINSKY; }      // the closures with diffusivity fields (Smagorinsky: νₑ only, smagorinsky.jl:131-139)
-    // the CLO coordinate of the epilogue kernels (ocn_kernels.h): 0 none, 1 constant ν, κ, 2 coefficient arrays, 3 the same with the tracers'
+    // the CLO coordinate of the epilogue kernels (ocn_kernels.h, ocn_epilogue_march.h; their closure term: ocn_closures.h): 0 none, 1 constant ν, κ, 2 coefficient arrays, 3 the same with the tracers'
     // coefficient divided by a Prandtl number (Smagorinsky with some Pr ≠ 1), 4 the explicit part of a vertically implicit ScalarDiffusivity
     int clo(int ntr) const {
         for (int t = 0; t < ntr && kind == SMAGORINSKY; ++t)

@@ -52,26 +52,18 @@ __device__ __forceinline__ double dyn_filter(const FView &f, int i, int j, int k
     return s / 12;
 }
 
-// the three diagonal strain components and the interpolated squares of a cell, as smagorinsky_viscosity_kernel forms them
-__device__ __forceinline__ SmagCell dyn_cell(const ClosureCtx &X, int i, int j, int k) {
-    auto q12 = [&](int ii, int jj, int kk) { const double x = X.S12(ii, jj, kk); return x * x; };
-    auto q13 = [&](int ii, int jj, int kk) { const double x = X.S13(ii, jj, kk); return x * x; };
-    auto q23 = [&](int ii, int jj, int kk) { const double x = X.S23(ii, jj, kk); return x * x; };
-    SmagCell c;
-    c.s11 = X.S11(i, j, k); c.s22 = X.S22(i, j, k); c.s33 = X.S33(i, j, k);
-    c.ixy12 = 0.5 * (0.5 * (q12(i, j, k) + q12(i + 1, j, k)) + 0.5 * (q12(i, j + 1, k) + q12(i + 1, j + 1, k)));
-    c.ixz13 = 0.5 * (0.5 * (q13(i, j, k) + q13(i + 1, j, k)) + 0.5 * (q13(i, j, k + 1) + q13(i + 1, j, k + 1)));
-    c.iyz23 = 0.5 * (0.5 * (q23(i, j, k) + q23(i, j + 1, k)) + 0.5 * (q23(i, j, k + 1) + q23(i, j + 1, k + 1)));
-    c.dzb_k = 0.0; c.dzb_k1 = 0.0;
-    return c;
-}
-
-// the six strain components at ccc, in the order 11, 22, 33, 12, 13, 23
+// the six strain components at ccc, in the order 11, 22, 33, 12, 13, 23 (the squares of a cell: smag_cell, ocn_closures.h)
 __device__ __forceinline__ void dyn_strain(const ClosureCtx &X, int i, int j, int k, double s[6]) {
     s[0] = X.S11(i, j, k); s[1] = X.S22(i, j, k); s[2] = X.S33(i, j, k);
-    s[3] = 0.5 * (0.5 * (X.S12(i, j, k) + X.S12(i + 1, j, k)) + 0.5 * (X.S12(i, j + 1, k) + X.S12(i + 1, j + 1, k)));
-    s[4] = 0.5 * (0.5 * (X.S13(i, j, k) + X.S13(i + 1, j, k)) + 0.5 * (X.S13(i, j, k + 1) + X.S13(i + 1, j, k + 1)));
-    s[5] = 0.5 * (0.5 * (X.S23(i, j, k) + X.S23(i, j + 1, k)) + 0.5 * (X.S23(i, j, k + 1) + X.S23(i, j + 1, k + 1)));
+    s[3] = interp_xy([&](int a, int b, int d) { return X.S12(a, b, d); }, i, j, k);
+    s[4] = interp_xz([&](int a, int b, int d) { return X.S13(a, b, d); }, i, j, k);
+    s[5] = interp_yz([&](int a, int b, int d) { return X.S23(a, b, d); }, i, j, k);
+}
+
+__device__ __forceinline__ double dyn_sigma(const ClosureCtx &X, int i, int j, int k) {      // Σ = sqrt(Σ²) of a cell
+    SmagCell c;
+    smag_cell(X, i, j, k, c);
+    return sqrt(smag_strain_squared(c));
 }
 
 // pass 1 over i = 0 .. Nx + 1, j = 0 .. Ny + 1, k = 0 .. Nz + 1 (_compute_Σ!, dynamic_coefficient.jl:142-149, and the filtered velocities)
@@ -82,16 +74,14 @@ __global__ void __launch_bounds__(256) dyn_filter_sigma_kernel(DGrid g, DynArgs 
     a.vb.at(i, j, k) = dyn_filter(a.v, i, j, k);
     a.wb.at(i, j, k) = dyn_filter(a.w, i, j, k);
     if (i < 1 || i > g.Nx || j < 1 || j > g.Ny || k < 1 || k > g.Nz) return;
-    const ClosureCtx X{g, a.u, a.v, a.w, 0.0, false, false, false, false, a.u};
-    a.Sig.at(i, j, k) = sqrt(smag_strain_squared(dyn_cell(X, i, j, k)));
+    a.Sig.at(i, j, k) = dyn_sigma(ClosureCtx{g, a.u, a.v, a.w}, i, j, k);
 }
 
 // pass 2 over the interior (_compute_Σ̄!, dynamic_coefficient.jl:151-158)
 __global__ void __launch_bounds__(256) dyn_sigma_bar_kernel(DGrid g, DynArgs a) {
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
     if (i > g.Nx || j > g.Ny) return;
-    const ClosureCtx XB{g, a.ub, a.vb, a.wb, 0.0, false, false, false, false, a.ub};
-    a.Sigb.at(i, j, k) = sqrt(smag_strain_squared(dyn_cell(XB, i, j, k)));
+    a.Sigb.at(i, j, k) = dyn_sigma(ClosureCtx{g, a.ub, a.vb, a.wb}, i, j, k);
 }
 
 // clamp(x, lo, hi) (Base: ifelse(x > hi, hi, ifelse(x < lo, lo, x)))
@@ -102,7 +92,7 @@ template <bool LAGR>
 __global__ void __launch_bounds__(256) dyn_lm_mm_kernel(DGrid g, DynArgs a, PGeom pg) {
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
     if (i > g.Nx || j > g.Ny) return;
-    const ClosureCtx X{g, a.u, a.v, a.w, 0.0, false, false, false, false, a.u};
+    const ClosureCtx X{g, a.u, a.v, a.w};
     // the filter sums of uᵢuⱼ (fl) and of Σ Σᵢⱼ (fm) over the cell, i + 1, i - 1, j + 1, j - 1, k + 1, k - 1 -- the order the reference adds them in
     double fl[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, fm[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll 1
@@ -131,7 +121,7 @@ __global__ void __launch_bounds__(256) dyn_lm_mm_kernel(DGrid g, DynArgs a, PGeo
     const double wb0 = a.wb.at(i, j, k), wb1 = a.wb.at(i, j, k + 1);
     const double ubc = 0.5 * (ub0 + ub1), vbc = 0.5 * (vb0 + vb1), wbc = 0.5 * (wb0 + wb1);
     const double tb[6] = {0.5 * (ub0 * ub0 + ub1 * ub1), 0.5 * (vb0 * vb0 + vb1 * vb1), 0.5 * (wb0 * wb0 + wb1 * wb1), ubc * vbc, ubc * wbc, vbc * wbc};
-    const ClosureCtx XB{g, a.ub, a.vb, a.wb, 0.0, false, false, false, false, a.ub};
+    const ClosureCtx XB{g, a.ub, a.vb, a.wb};
     double sb[6];
     dyn_strain(XB, i, j, k, sb);
     const double sigb = a.Sigb.at(i, j, k);
@@ -182,8 +172,9 @@ __global__ void __launch_bounds__(256) dyn_fill_mean_kernel(double *p, long n, c
 __global__ void __launch_bounds__(256) smagorinsky_viscosity_dynamic_kernel(DGrid g, SmagArgs a, DynCoefficient d) {
     const int i = 1 + blockIdx.x * blockDim.x + threadIdx.x, j = 1 + blockIdx.y * blockDim.y + threadIdx.y, k = 1 + blockIdx.z;
     if (i > g.Nx || j > g.Ny) return;
-    const ClosureCtx X{g, a.u, a.v, a.w, 0.0, false, false, false, false, a.u};
-    const SmagCell c = dyn_cell(X, i, j, k);
+    const ClosureCtx X{g, a.u, a.v, a.w};
+    SmagCell c;
+    smag_cell(X, i, j, k, c);
     const long q = d.off + (i - 1) * d.s[0] + (j - 1) * d.s[1] + (k - 1) * d.s[2];
     const double jl = jl_max(d.jlm[q], d.jmin), jm = d.jmm[q];
     const double cs2 = jm > 0 ? jl / jm : 0.0;             // fluid at rest: 𝒥ᴹᴹ = 0 and the quotient Inf -- discarded, νₑ = 0

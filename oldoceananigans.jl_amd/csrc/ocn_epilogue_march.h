@@ -1,6 +1,7 @@
 // The one-pass tendency epilogue (ocn_kernels.h: tendency_epilogue_kernel) as a z-march. Same terms, same operations on the same values --
-// every flux below is the expression of ClosureCtx::vf.. / closure_divergence with its operands taken from registers -- but each POINT
-// quantity is evaluated once instead of once per consumer:
+// every flux below calls the point formulas of ocn_closures.h (strain_offdiag, viscous_flux, diffusive_flux, prandtl_coefficient) that
+// ClosureCtx::vf.. / closure_divergence call, with its operands taken from registers -- but each POINT quantity is evaluated once instead
+// of once per consumer:
 //
 //   the viscous flux tensor is symmetric: vf12 at an ffc point is read by u (its y difference) and by v (its x difference), vf13 by u
 //   and w, vf23 by v and w. The per-field kernel evaluates 6 fluxes for each of the three velocity tendencies and 6 per tracer, every
@@ -49,6 +50,8 @@ __global__ void __launch_bounds__(512) tendency_epilogue_march_kernel(DGrid g, E
     bool do_c[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) do_c[t] = CLO && t < NTR && (VAR || a.kappa[t] != 0.0);
+    // tracer t's coefficient at the face between the ccc values ka and kb: the number κ, or the arrays' mean (PRD: divided by Pr)
+    auto kface = [&](int t, double ka, double kb) { return PRD ? prandtl_coefficient(0.5 * (ka + kb), a.kappa[t]) : (VAR ? 0.5 * (ka + kb) : a.kappa[t]); };
 
     // ---- level kc0 - 1: what the face level kc0 and vf33(kc0 - 1) need of the level below
     double u_m, v_m, v1_m, w_m, n_m = a.nu, kfcc_m = a.nu, kcfc_m = a.nu, kcfc1_m = a.nu, c_m[NT], k_m[NT];
@@ -109,16 +112,15 @@ __global__ void __launch_bounds__(512) tendency_epilogue_march_kernel(DGrid g, E
         // ---- face level L: vf13, vf23 (rows j, j + 1), the tracers' z flux; vf33 of level L - 1
         const double rdzf = g.rdzf[tz], dzf = g.dzf[tz];
         const double w_w = lane_prev(wL[1]);
-        const double p13 = -(2 * (kfcf * (0.5 * ((uL[1] - u_m) * rdzf + (wL[1] - w_w) * rdx))));
-        const double p23_j = -(2 * (kcff_j * (0.5 * ((vL[1] - v_m) * rdzf + (wL[1] - wL[0]) * rdy))));
-        const double p23_j1 = -(2 * (kcff_j1 * (0.5 * ((vL[2] - v1_m) * rdzf + (wL[2] - wL[1]) * rdy))));
-        const double p33 = -(2 * (n_m * ((wL[1] - w_m) * g.rdzc[tz - 1])));             // vf33(i, j, L - 1)
+        const double p13 = viscous_flux(kfcf, strain_offdiag(uL[1] - u_m, rdzf, wL[1] - w_w, rdx));
+        const double p23_j = viscous_flux(kcff_j, strain_offdiag(vL[1] - v_m, rdzf, wL[1] - wL[0], rdy));
+        const double p23_j1 = viscous_flux(kcff_j1, strain_offdiag(vL[2] - v1_m, rdzf, wL[2] - wL[1], rdy));
+        const double p33 = viscous_flux(n_m, (wL[1] - w_m) * g.rdzc[tz - 1]);           // vf33(i, j, L - 1)
         const double sw_new = ((dy_ * dzf) * lane_next(p13) - (dy_ * dzf) * p13) + ((dx_ * dzf) * p23_j1 - (dx_ * dzf) * p23_j);
         double qz[NT];
 #pragma unroll
         for (int t = 0; t < NTR; ++t) {
-            const double kccf = PRD ? (0.5 * (k_m[t] + kL[t][1])) / a.kappa[t] : (VAR ? 0.5 * (k_m[t] + kL[t][1]) : a.kappa[t]);
-            qz[t] = -(kccf * ((cL[t][1] - c_m[t]) * rdzf));
+            qz[t] = diffusive_flux(kface(t, k_m[t], kL[t][1]), (cL[t][1] - c_m[t]) * rdzf);
         }
 
         // ---- complete cell k = L - 1
@@ -173,20 +175,18 @@ __global__ void __launch_bounds__(512) tendency_epilogue_march_kernel(DGrid g, E
         if (L <= kc1) {
             const double dzc = g.dzc[tz], ax = dy_ * dzc, ay = dx_ * dzc;
             const double u_e = lane_next(uL[1]), v_w = lane_prev(vL[1]), v1_w = lane_prev(vL[2]);
-            const double p11 = -(2 * (nL[1] * ((u_e - uL[1]) * rdx)));
-            const double p22_j = -(2 * (nL[1] * ((vL[2] - vL[1]) * rdy))), p22_jm = -(2 * (nL[0] * ((vL[1] - vL[0]) * rdy)));
+            const double p11 = viscous_flux(nL[1], (u_e - uL[1]) * rdx);
+            const double p22_j = viscous_flux(nL[1], (vL[2] - vL[1]) * rdy), p22_jm = viscous_flux(nL[0], (vL[1] - vL[0]) * rdy);
             const double kffc_j = VAR ? 0.5 * (kfcc[0] + kfcc[1]) : a.nu, kffc_j1 = VAR ? 0.5 * (kfcc[1] + kfcc[2]) : a.nu;
-            const double p12_j = -(2 * (kffc_j * (0.5 * ((uL[1] - uL[0]) * rdy + (vL[1] - v_w) * rdx))));
-            const double p12_j1 = -(2 * (kffc_j1 * (0.5 * ((uL[2] - uL[1]) * rdy + (vL[2] - v1_w) * rdx))));
+            const double p12_j = viscous_flux(kffc_j, strain_offdiag(uL[1] - uL[0], rdy, vL[1] - v_w, rdx));
+            const double p12_j1 = viscous_flux(kffc_j1, strain_offdiag(uL[2] - uL[1], rdy, vL[2] - v1_w, rdx));
             s_u = (ax * p11 - ax * lane_prev(p11)) + (ay * p12_j1 - ay * p12_j);
             s_v = (ax * lane_next(p12_j) - ax * p12_j) + (ay * p22_j - ay * p22_jm);
 #pragma unroll
             for (int t = 0; t < NTR; ++t) {
-                const double kx = PRD ? (0.5 * (lane_prev(kL[t][1]) + kL[t][1])) / a.kappa[t] : (VAR ? 0.5 * (lane_prev(kL[t][1]) + kL[t][1]) : a.kappa[t]);
-                const double ky_j = PRD ? (0.5 * (kL[t][0] + kL[t][1])) / a.kappa[t] : (VAR ? 0.5 * (kL[t][0] + kL[t][1]) : a.kappa[t]);
-                const double ky_j1 = PRD ? (0.5 * (kL[t][1] + kL[t][2])) / a.kappa[t] : (VAR ? 0.5 * (kL[t][1] + kL[t][2]) : a.kappa[t]);
-                const double qx = -(kx * ((cL[t][1] - lane_prev(cL[t][1])) * rdx));
-                const double qy_j = -(ky_j * ((cL[t][1] - cL[t][0]) * rdy)), qy_j1 = -(ky_j1 * ((cL[t][2] - cL[t][1]) * rdy));
+                const double qx = diffusive_flux(kface(t, lane_prev(kL[t][1]), kL[t][1]), (cL[t][1] - lane_prev(cL[t][1])) * rdx);
+                const double qy_j = diffusive_flux(kface(t, kL[t][0], kL[t][1]), (cL[t][1] - cL[t][0]) * rdy);
+                const double qy_j1 = diffusive_flux(kface(t, kL[t][1], kL[t][2]), (cL[t][2] - cL[t][1]) * rdy);
                 s_c[t] = (ax * lane_next(qx) - ax * qx) + (ay * qy_j1 - ay * qy_j);
             }
             if (COR) {

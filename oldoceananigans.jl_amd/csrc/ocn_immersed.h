@@ -40,6 +40,7 @@ enum { IMM_INACTIVE = 0, IMM_FCC = 1, IMM_CFC = 2, IMM_CCF = 3, IMM_FFC = 4, IMM
 // what the plain instantiations pass where the immersed ones pass an ImmView: no data, every test a compile-time `false`
 struct NoImm {
     static constexpr bool on = false;
+    __device__ __forceinline__ static double flux(int, int, int, int, double q) { return q; }      // no boundary: every flux is itself
 };
 
 // The two tables of a grid, addressed with the reference's 1-based (i, j, k). Kept out of DGrid -- that struct is a by-value argument of
